@@ -16,6 +16,13 @@ step, different tracks every step; weak scaling: per-GPU work is fixed) into a d
 scores over RCCL on the device buffers themselves.  The pool is resident in HBM before the timed
 region.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set up, warm up, time the --steps steps, write the last
+step's scores if --dump-outputs DIR is given (DIR/scores.npy, float32: rank 0's pairs of that step in
+tile order, row-major within a tile, i < j on diagonal tiles), print the line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = wall milliseconds of one timed step, `phases_s`, `fence`, ...).
+`--full` adds `roofline`, `cpu_baseline` (with the self-check), `strong` (the sub-grid leg) and `other`;
+in a plain line the first three are null and `other` is absent.
+
 Also in the line:
   roofline      the dominant kernel (accumulated HIP-event time on the library's own stream)
                 against the byte model SURVEY.md 8d fixes (10 B/cell: f32 distance matrix written
@@ -541,6 +548,76 @@ def strong_core(ctx, params, lengths, tile, rank, world, local_rank, collective,
     return res
 
 
+def roofline_of(prof, value, world, steps, elapsed, clocked_elapsed):
+    """`--full`: the roofline object of the dominant kernel (HIP events on the library's stream, from the kernel-clock pass
+    `prof` over the same `steps` steps behind the timed region)."""
+    kname, kst = max(prof.items(), key=lambda kv: kv[1]["ms"])
+    launches = max(1, kst["launches"])
+    cells_per_launch = kst["cells"] / launches
+    avg_ms = kst["ms"] / launches
+    algo_bytes = ALGO_BYTES_PER_CELL[kname] * cells_per_launch
+    if kname in ("csm_long_kernel", "band_kernel"):
+        algo_bytes += 48.0 * 2 * T_FRAMES * (cells_per_launch / float((T_FRAMES - M_STACK) ** 2))
+    achieved = algo_bytes / (avg_ms * 1e-3) / 1e9
+    # HBM traffic and pipe utilisations come from rocprofv3 --pmc passes of a SEPARATE run (counters and this run's
+    # timing cannot be collected together); the records carry the hash of the kernel sources they were taken
+    # on and are reported only when it is the hash of THIS build -- a kernel change without a re-profile
+    # yields null, not stale numbers.
+    traffic, traffic_source, real_bound = None, None, None
+    sha = kernel_source_sha16()
+    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(tpath):
+        try:
+            tj = json.load(open(tpath))
+            if tj.get("kernel_source_sha16") != sha:
+                traffic_source = "profiles/pmc_traffic.json was taken on other kernel sources (%s, this build %s): not reported" % (
+                    tj.get("kernel_source_sha16"), sha)
+            elif kname in tj and tj[kname].get("cells_per_launch"):
+                traffic = tj[kname]["hbm_bytes_per_launch"] * cells_per_launch / tj[kname]["cells_per_launch"]
+                traffic_source = ("profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in a separate run "
+                                  "(%s, same kernel sources %s), scaled by cells per launch" % (tj.get("source"), sha))
+        except Exception:
+            traffic = None
+    rpath = os.path.join(ROOT, "profiles", "real_bound.json")
+    if os.path.exists(rpath):
+        try:
+            rj = json.load(open(rpath))
+            real_bound = rj.get(kname) if rj.get("kernel_source_sha16") == sha else None
+        except Exception:
+            real_bound = None
+    bpp = chain_bytes_per_pair(T_FRAMES, T_FRAMES)
+    # SURVEY 8d's flop model of the same kernel: 2 x 108 flop per cell (the reference's 108-dim formulation of
+    # the cross-similarity matrix), per launch, against the f32-input MFMA peak
+    flops_pair = 2.0 * 12 * M_STACK * float((T_FRAMES - M_STACK) ** 2)
+    mfma_tf = value / world * flops_pair / 1e12
+    bound = derive_bound(real_bound)
+    return {"bound": bound or "hbm",
+            "bound_source": ("busiest unit in the counter record of this kernel (real_bound)" if bound else
+                             "no counter record of this build's kernel sources: the byte model's own bound"),
+            "model": "`achieved` / `frac` price the kernel with the HBM byte model of SURVEY 8d (4 B per cell and launch: a "
+                     "THROUGHPUT PROXY -- the pipeline keeps the distance matrix out of HBM, see `traffic`); what the SIMDs "
+                     "wait for is `bound` / real_bound; the 8d flop model of the same launch is in mfma_model",
+            "kernel": kname, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+            "traffic_source": traffic_source, "real_bound": real_bound,
+            "mfma_model": {"flops_per_pair": flops_pair, "achieved": round(mfma_tf, 2),
+                           "peak": F32_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": round(mfma_tf / F32_MFMA_PEAK_TF, 4),
+                           "note": "SURVEY 8d: 2 x 108 flop per cell of the pair's matrix, once per pair, over the whole chain's "
+                                   "time per pair; the kernels contract K = 12 per frame pair (window sums give the 108-dim "
+                                   "product) but sweep the matrix twice (column pass, row pass)"},
+            "avg_launch_ms": round(avg_ms, 3), "algorithmic_bytes_per_launch": algo_bytes,
+            "kernels_ms_per_step": {k: round(v["ms"] / steps, 3) for k, v in prof.items()},
+            "kernel_clock_pass": {"what": "avg_launch_ms / kernels_ms_per_step: HIP events around every launch on the library's "
+                                          "stream, taken in a SECOND pass over the same steps' tiles behind the timed region (the "
+                                          "clocks serialise the alignment sweeps onto the band kernels' stream; the timed region "
+                                          "runs without them, sweeps on two side streams: `value` is the product path)",
+                                  "ms_per_step": round(1e3 * clocked_elapsed / steps, 3),
+                                  "timed_region_ms_per_step": round(1e3 * elapsed / steps, 3)},
+            "chain": {"algorithmic_bytes_per_pair": bpp,
+                      "achieved": round(value / world * bpp / 1e9, 1),
+                      "frac": round(value / world * bpp / 1e9 / HBM_PEAK_GBS, 4)}}
+
+
 def run_strong(args, clock, out, rank, world, local_rank):
     """`--strong`: the WHOLE pair grid of the pool (5 000 tracks: 12 497 500 pairs) once, split over the N ranks
     (strong_core).  Strong scaling: total work fixed.  `value` = pairs / (kernels + exchange), max over ranks;
@@ -603,8 +680,13 @@ def main():
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: the whole pair grid of the pool once, split over the ranks, ONE final all-gather of "
                          "the per-rank score buffers, rank-0 scatter reported beside it (minutes at 5000 tracks on one GPU)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-other", action="store_true", help="skip the SiMPle / EarlyFusion / covers-shaped legs (the `other` object)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: CPU baseline + self-check, the kernel-clock pass (roofline), the "
+                         "sub-grid `strong` leg, the `other` legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's scores (rank 0's pairs) as DIR/scores.npy (float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-other", action="store_true", help="--full: skip the SiMPle / EarlyFusion / covers-shaped legs (the `other` object)")
     ap.add_argument("--plan-only", action="store_true",
                     help="rendezvous, deal the tiles, print the plan as one JSON line and stop: no GPU work "
                          "(checks a multi-rank launch on any box; ACX_BENCH_BACKEND=gloo without GPUs)")
@@ -612,6 +694,10 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench: --steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.strong:
+        raise SystemExit("bench: --dump-outputs writes the weak-scaling steps' scores; not with --strong")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
     out = json_only_stdout()
@@ -681,7 +767,7 @@ def main():
         frames, offsets = make_pool(args.tracks, T_FRAMES)
     # ---- CPU baseline first: worker processes are forked (and joined) before any GPU state exists
     cpu = cpu_sample = cpu_scores = None
-    if world == 1 and rank == 0 and not args.no_cpu:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu:
         try:
             cpu_sample, cpu_scores, cpu = cpu_baseline(frames, offsets, pairs_of(slice_of(args.warmup)[1]), args.tracks, clock)
         except Exception as e:                       # the reported baseline must not take the measurement with it
@@ -779,34 +865,48 @@ def main():
     else:
         total_pairs = my_pairs
     ranks_seen = dist.get_world_size() if collective else 1        # what the collective actually spanned
-    with clock.phase("kernel_clock_pass"):
-        ctx.profile_enable(True)
-        ctx.profile_reset()
-        fence()
-        tk0 = time.perf_counter()
-        for s in range(args.warmup, args.warmup + args.steps):
-            step(s, exchange=False)
-        fence()
-        clocked_elapsed = time.perf_counter() - tk0
-        prof = ctx.profile()
-        ctx.profile_enable(False)
-    my_kernels_s = sum(v["ms"] for v in prof.values()) / 1e3
-    if collective:
-        box = [None] * world
-        dist.all_gather_object(box, (rank, round(my_kernels_s, 4), round(my_pairs)))
-        for r, ks, pp_ in box:
-            infos[r]["kernels_s"] = ks
-            infos[r]["pairs"] = int(pp_)
-    else:
-        infos[0]["kernels_s"] = round(my_kernels_s, 4)
-        infos[0]["pairs"] = int(round(my_pairs))
+    if args.dump_outputs and rank == 0:
+        with clock.phase("dump_outputs"):
+            # `local` still holds the last timed step's scores (tile after tile from local[0], as step() rebased them)
+            buf = local.cpu().numpy() if collective else local.read(np.float32, slice_floats)
+            tiles = slice_of(args.warmup + args.steps - 1)[1]
+            parts = []
+            for t in tiles:
+                o = t.offset - tiles[0].offset
+                blk = buf[o:o + t.rows * t.cols].reshape(t.rows, t.cols)
+                i, j = np.meshgrid(np.arange(t.rows), np.arange(t.cols), indexing="ij")
+                parts.append(blk[i < j] if t.diagonal else blk.ravel())       # the pairs of pairs_of(tiles), same order
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "scores.npy"), np.concatenate(parts).astype(np.float32))
+    if args.full:
+        with clock.phase("kernel_clock_pass"):
+            ctx.profile_enable(True)
+            ctx.profile_reset()
+            fence()
+            tk0 = time.perf_counter()
+            for s in range(args.warmup, args.warmup + args.steps):
+                step(s, exchange=False)
+            fence()
+            clocked_elapsed = time.perf_counter() - tk0
+            prof = ctx.profile()
+            ctx.profile_enable(False)
+        my_kernels_s = sum(v["ms"] for v in prof.values()) / 1e3
+        if collective:
+            box = [None] * world
+            dist.all_gather_object(box, (rank, round(my_kernels_s, 4), round(my_pairs)))
+            for r, ks, pp_ in box:
+                infos[r]["kernels_s"] = ks
+                infos[r]["pairs"] = int(pp_)
+        else:
+            infos[0]["kernels_s"] = round(my_kernels_s, 4)
+            infos[0]["pairs"] = int(round(my_pairs))
     # ---- N > 1 (or a forced one-rank world): the path as ONE job on a sub-grid of the same pool -- the real plan, the real
     # per-rank buffers through the ONE exchange, rank 0's device-to-host copy + scatter + mirror, the matrix checked against
     # the pair-list path.  Outside the timed region above; reported under `strong` in the same line.
     strong = None
-    # (one GPU without a collective: only in the full default run -- `--no-other` is what the profiler passes use, and their
-    #  per-kernel means must stay those of the timed steps' launches)
-    if (collective or not args.no_other) and not os.environ.get("ACX_BENCH_NO_STRONG_LEG"):
+    # (only with --full; one GPU without a collective: only when the `other` legs run too -- `--no-other` is what the profiler
+    #  passes use, and their per-kernel means must stay those of the timed steps' launches)
+    if args.full and (collective or not args.no_other) and not os.environ.get("ACX_BENCH_NO_STRONG_LEG"):
         n_sub = min(args.tracks, STRONG_LEG_TRACKS if collective else STRONG_LEG_TRACKS_ONE)
         with clock.phase("strong_leg"):
             # (acx_grid_run plans over the WHOLE pool of the context: the sub-grid gets a pool of its own, the first n_sub tracks)
@@ -820,72 +920,7 @@ def main():
 
     if rank == 0:
         value = total_pairs / elapsed
-        # ---- roofline of the dominant kernel (HIP events on the library's stream)
-        kname, kst = max(prof.items(), key=lambda kv: kv[1]["ms"])
-        launches = max(1, kst["launches"])
-        cells_per_launch = kst["cells"] / launches
-        avg_ms = kst["ms"] / launches
-        algo_bytes = ALGO_BYTES_PER_CELL[kname] * cells_per_launch
-        if kname in ("csm_long_kernel", "band_kernel"):
-            algo_bytes += 48.0 * 2 * T_FRAMES * (cells_per_launch / float((T_FRAMES - M_STACK) ** 2))
-        achieved = algo_bytes / (avg_ms * 1e-3) / 1e9
-        # HBM traffic and pipe utilisations come from rocprofv3 --pmc passes of a SEPARATE run (counters and this run's
-        # timing cannot be collected together); the records carry the hash of the kernel sources they were taken
-        # on and are reported only when it is the hash of THIS build -- a kernel change without a re-profile
-        # yields null, not stale numbers.
-        traffic, traffic_source, real_bound = None, None, None
-        sha = kernel_source_sha16()
-        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                if tj.get("kernel_source_sha16") != sha:
-                    traffic_source = "profiles/pmc_traffic.json was taken on other kernel sources (%s, this build %s): not reported" % (
-                        tj.get("kernel_source_sha16"), sha)
-                elif kname in tj and tj[kname].get("cells_per_launch"):
-                    traffic = tj[kname]["hbm_bytes_per_launch"] * cells_per_launch / tj[kname]["cells_per_launch"]
-                    traffic_source = ("profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in a separate run "
-                                      "(%s, same kernel sources %s), scaled by cells per launch" % (tj.get("source"), sha))
-            except Exception:
-                traffic = None
-        rpath = os.path.join(ROOT, "profiles", "real_bound.json")
-        if os.path.exists(rpath):
-            try:
-                rj = json.load(open(rpath))
-                real_bound = rj.get(kname) if rj.get("kernel_source_sha16") == sha else None
-            except Exception:
-                real_bound = None
-        bpp = chain_bytes_per_pair(T_FRAMES, T_FRAMES)
-        # SURVEY 8d's flop model of the same kernel: 2 x 108 flop per cell (the reference's 108-dim formulation of
-        # the cross-similarity matrix), per launch, against the f32-input MFMA peak
-        flops_pair = 2.0 * 12 * M_STACK * float((T_FRAMES - M_STACK) ** 2)
-        mfma_tf = value / world * flops_pair / 1e12
-        bound = derive_bound(real_bound)
-        roofline = {"bound": bound or "hbm",
-                    "bound_source": ("busiest unit in the counter record of this kernel (real_bound)" if bound else
-                                     "no counter record of this build's kernel sources: the byte model's own bound"),
-                    "model": "`achieved` / `frac` price the kernel with the HBM byte model of SURVEY 8d (4 B per cell and launch: a "
-                             "THROUGHPUT PROXY -- the pipeline keeps the distance matrix out of HBM, see `traffic`); what the SIMDs "
-                             "wait for is `bound` / real_bound; the 8d flop model of the same launch is in mfma_model",
-                    "kernel": kname, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                    "traffic_source": traffic_source, "real_bound": real_bound,
-                    "mfma_model": {"flops_per_pair": flops_pair, "achieved": round(mfma_tf, 2),
-                                   "peak": F32_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": round(mfma_tf / F32_MFMA_PEAK_TF, 4),
-                                   "note": "SURVEY 8d: 2 x 108 flop per cell of the pair's matrix, once per pair, over the whole chain's "
-                                           "time per pair; the kernels contract K = 12 per frame pair (window sums give the 108-dim "
-                                           "product) but sweep the matrix twice (column pass, row pass)"},
-                    "avg_launch_ms": round(avg_ms, 3), "algorithmic_bytes_per_launch": algo_bytes,
-                    "kernels_ms_per_step": {k: round(v["ms"] / args.steps, 3) for k, v in prof.items()},
-                    "kernel_clock_pass": {"what": "avg_launch_ms / kernels_ms_per_step: HIP events around every launch on the library's "
-                                                  "stream, taken in a SECOND pass over the same steps' tiles behind the timed region (the "
-                                                  "clocks serialise the alignment sweeps onto the band kernels' stream; the timed region "
-                                                  "runs without them, sweeps on two side streams: `value` is the product path)",
-                                          "ms_per_step": round(1e3 * clocked_elapsed / args.steps, 3),
-                                          "timed_region_ms_per_step": round(1e3 * elapsed / args.steps, 3)},
-                    "chain": {"algorithmic_bytes_per_pair": bpp,
-                              "achieved": round(value / world * bpp / 1e9, 1),
-                              "frac": round(value / world * bpp / 1e9 / HBM_PEAK_GBS, 4)}}
+        roofline = roofline_of(prof, value, world, args.steps, elapsed, clocked_elapsed) if args.full else None
         if cpu_sample is not None and len(cpu_sample):
             with clock.phase("self_check"):
                 got = ctx.serra09_pairs(cpu_sample, params)
@@ -898,7 +933,7 @@ def main():
             "rccl_version": rccl_version(collective, backend), "ranks": infos, "strong": strong, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "fence": ("dist.barrier + torch.cuda.synchronize on both sides of the timed region" if collective else
                       "hipDeviceSynchronize (libacx acx_dev_sync) on both sides of the timed region; one rank, no torch in the process"),
             "config": {"workload": "configs[2]: synthetic %d tracks x %d-frame HPCP (seed 1234), Serra09 Qmax "
@@ -918,7 +953,7 @@ def main():
                 line["phases_s"]["total_wall"] = round(time.perf_counter() - _T_START, 3)
                 print(json.dumps(line), file=out, flush=True)
 
-        if world == 1 and not args.no_other:
+        if args.full and world == 1 and not args.no_other:
             # the companion legs, outside the timed region above (bench_other.py): Serra09 on covers80-shaped lengths and the
             # other two algorithms at their BASELINE configs[3] / [4] per-track shapes, each with its own roofline and CPU
             # baseline, each under a hard wall limit.  A leg that hangs in native code cannot take the headline with it:

@@ -8,7 +8,7 @@ OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp; cd - > /dev/null
 PY=$(which python3)
-ARGS="bench.py --no-cpu --no-other --steps 2 --warmup 1 --tracks 640"
+ARGS="bench.py --full --no-cpu --no-other --steps 2 --warmup 1 --tracks 640"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- $PY $ARGS > $OUT/stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- $PY $ARGS > $OUT/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o pmc -- $PY $ARGS > $OUT/pmc_write.log 2>&1

@@ -373,15 +373,19 @@ def test_bench_strong_gloo_world_of_two():
     assert [r["rank"] for r in line["ranks"]] == [0, 1] and all(r["pci_bus_id"] for r in line["ranks"])
 
 
-def _bench_default(env_extra, nproc, extra_args=(), expect_rc=0, with_other=False):
-    """The driver's command (`bench.py --gpus N --steps K --warmup W`, weak scaling) as a child process on a small pool."""
+def _bench_default(env_extra, nproc, extra_args=(), expect_rc=0, with_other=False, full=True, steps=2):
+    """The driver's command (`bench.py --gpus N --steps K --warmup W`, weak scaling) as a child process on a small pool;
+    `--full` unless `full=False`."""
     import json
     import os
     env = dict(os.environ)
     env.update(env_extra)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("ACX_BENCH_STRONG_TRACKS", "192")
-    args = ["--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--tracks", "640", "--no-cpu"] + ([] if with_other else ["--no-other"]) + list(extra_args)
+    args = ["--gpus", str(nproc), "--steps", str(steps), "--warmup", "1", "--tracks", "640"]
+    if full:
+        args += ["--full", "--no-cpu"] + ([] if with_other else ["--no-other"])
+    args += list(extra_args)
     if nproc > 1:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py")] + args
@@ -431,6 +435,36 @@ def test_bench_refuses_ranks_that_share_a_gpu():
     prints no JSON line."""
     r = _bench_default({"ACX_BENCH_BACKEND": "gloo", "ACX_BENCH_REQUIRE_DISTINCT": "1"}, 2, expect_rc=3)
     assert "hold the same GPU" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_steps_scores(ctx, tmp_path):
+    """The plain command (no `--full`) times its steps and prints the headline only -- no CPU baseline, kernel-clock pass,
+    sub-grid leg or `other` legs -- and `--dump-outputs DIR` writes the last timed step's scores, equal to the pair-list
+    path of the library on that step's pairs of the same seeded pool."""
+    import bench
+    from acoss_amd import _lib
+    steps, warmup, n = 3, 1, 640
+    line = _bench_default({}, 1, extra_args=["--dump-outputs", str(tmp_path)], full=False, steps=steps)
+    assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "track-pairs/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["full"] is False
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["strong"] is None and "other" not in line
+    assert not {"kernel_clock_pass", "strong_leg", "cpu_1core", "cpu_all_cores", "self_check"} & set(line["phases_s"])
+    scores = np.load(str(tmp_path / "scores.npy"))
+    # the last timed step's tiles, as bench.py deals them
+    plan = _lib.grid_plan(np.full(n, bench.T_FRAMES, np.int64), _lib.ALGO_SERRA09, True, world=1, tile=bench.TILE, want_tiles=True)
+    mine = [t for t in plan["tiles"] if t.rank == 0]
+    k = ((warmup + steps - 1) % (len(mine) // bench.TILES_PER_STEP)) * bench.TILES_PER_STEP
+    pairs = []
+    for t in mine[k:k + bench.TILES_PER_STEP]:
+        i, j = np.meshgrid(np.arange(t.row0, t.row0 + t.rows), np.arange(t.col0, t.col0 + t.cols), indexing="ij")
+        keep = (i < j) if t.diagonal else np.ones_like(i, bool)
+        pairs.append(np.stack([i[keep], j[keep]], 1))
+    pairs = np.ascontiguousarray(np.concatenate(pairs).astype(np.int32))
+    assert scores.dtype == np.float32 and scores.shape == (len(pairs),)
+    frames, offsets = bench.make_pool(n, bench.T_FRAMES)
+    ctx.upload_pool(frames, offsets)
+    want = ctx.serra09_pairs(pairs, _lib.serra09_params())
+    assert np.array_equal(scores, want) and float(want.max()) > 0
 
 
 def test_rccl_inside_libacx_world_of_one():
