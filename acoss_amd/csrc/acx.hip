@@ -25,9 +25,7 @@
 #include "simple_kernels.hpp"
 #include "ef_kernels.hpp"
 #include "ef_rowstat2_kernels.hpp"
-#include "ef_gemm_persist_kernels.hpp"
 #include "ef_gemm_dma_kernels.hpp"
-#include "ef_gemm_ws_kernels.hpp"
 #include "ef_prep_kernels.hpp"
 #include "grid.hpp"
 
@@ -945,14 +943,12 @@ struct SegBatch {
     std::vector<acx::EfSegWg> wgs;          // workgroup tiles of 8 x 8 groups (128 x 128 cells: ef_gemm_seg_f32_kernel)
     std::vector<acx::EfSegWg> wgs2;         // tiles of 16 x 8 groups (256 x 128 cells: ef_gemm_rect_bf16x3_kernel<0>): ty, first column group, groups
     std::vector<acx::EfSegWg> wgs3;         // the same for chroma (<1>): the columns of a tile stop at the end of their reference track
-    std::vector<acx::EfSegWg> wgs5, wgs6;   // tiles of 8 x 8 groups (128 x 128 cells: ef_gemm_rect_ws_kernel) in the same format: mfcc / ssm, chroma
 };
 void ef_build_rects(const std::vector<acx::EfPair> &pd, const std::vector<int64_t> &efoff, int n_tracks, SegBatch &sb,
                     std::vector<int32_t> &qslot, std::vector<int32_t> &rslot)
 {
     sb.rowg.clear(); sb.colg.clear(); sb.rects.clear(); sb.ptab.clear(); sb.wgs.clear(); sb.wgs2.clear(); sb.wgs3.clear();
-    sb.wgs5.clear(); sb.wgs6.clear();
-    std::vector<uint8_t> mark, mark2, mark3, mark6;
+    std::vector<uint8_t> mark, mark2, mark3;
     std::vector<int32_t> cfirst;                  // chroma: first column chunk of every reference slot (+ one past the last)
     std::vector<std::pair<int32_t, int32_t>> cchunk;     // (first group, groups) of every column chunk
     std::vector<int32_t> gfirst_q, gfirst_r;      // first group of every slot (+ one past the last)
@@ -1001,7 +997,6 @@ void ef_build_rects(const std::vector<acx::EfPair> &pd, const std::vector<int64_
         cfirst.push_back((int32_t)cchunk.size());
         const int ncc = (int)cchunk.size();
         mark3.assign((size_t)tiles_y2 * ncc, 0);
-        mark6.assign((size_t)tiles_y * ncc, 0);
         for (const auto &m : members) {
             const int a = m.second / SEG_TRACKS, b = m.second % SEG_TRACKS;
             sb.ptab[(size_t)R.ptab0 + (size_t)a * R.ncols + b] = m.first;
@@ -1014,8 +1009,6 @@ void ef_build_rects(const std::vector<acx::EfPair> &pd, const std::vector<int64_
                 }
             for (int ty = gfirst_q[a] / 16; ty <= (gfirst_q[a + 1] - 1) / 16; ++ty)
                 for (int ci = cfirst[b]; ci < cfirst[b + 1]; ++ci) mark3[(size_t)ty * ncc + ci] = 1;
-            for (int ty = gfirst_q[a] / 8; ty <= (gfirst_q[a + 1] - 1) / 8; ++ty)
-                for (int ci = cfirst[b]; ci < cfirst[b + 1]; ++ci) mark6[(size_t)ty * ncc + ci] = 1;
         }
         const int32_t rid = (int32_t)sb.rects.size();
         for (int ty = 0; ty < tiles_y; ++ty)
@@ -1027,12 +1020,6 @@ void ef_build_rects(const std::vector<acx::EfPair> &pd, const std::vector<int64_
         for (int ty = 0; ty < tiles_y2; ++ty)
             for (int ci = 0; ci < ncc; ++ci)
                 if (mark3[(size_t)ty * ncc + ci]) sb.wgs3.push_back(acx::EfSegWg{rid, ty, cchunk[(size_t)ci].first, cchunk[(size_t)ci].second});
-        for (int ty = 0; ty < tiles_y; ++ty)
-            for (int tx = 0; tx < tiles_x; ++tx)
-                if (mark[(size_t)ty * tiles_x + tx]) sb.wgs5.push_back(acx::EfSegWg{rid, ty, 8 * tx, std::min(8, R.nh - 8 * tx)});
-        for (int ty = 0; ty < tiles_y; ++ty)
-            for (int ci = 0; ci < ncc; ++ci)
-                if (mark6[(size_t)ty * ncc + ci]) sb.wgs6.push_back(acx::EfSegWg{rid, ty, cchunk[(size_t)ci].first, cchunk[(size_t)ci].second});
         sb.rects.push_back(R);
         for (int32_t t : qs) qslot[(size_t)t] = -1;
         for (int32_t t : rs) rslot[(size_t)t] = -1;
@@ -1058,6 +1045,134 @@ void ef_build_rects(const std::vector<acx::EfPair> &pd, const std::vector<int64_
     close();
 }
 }  // namespace
+
+// The three cross-similarity GEMMs of one batch into its scratch: mfcc and ssm (squared Euclidean distances, z = 0 / 1) and chroma
+// (cosine, the first song rolled by the pair's OTI, z = 2).  One kernel path per mode:
+//   ACX_EF_GEMM_F16X2 (default)   ef_gemm_rect_persist_dma_kernel<0 / 1>: one workgroup per CU walks the tiles, operands by LDS-DMA;
+//                                 ACX_EF_PERSIST=0: ef_gemm_rect_bf16x3_kernel<0 / 1, 1>, one workgroup per tile -- the same bits, kept
+//                                 as an independent cross-check of the DMA kernel
+//   ACX_EF_GEMM_BF16X3            ef_gemm_rect_bf16x3_kernel<0 / 1, 0>
+//   ACX_EF_GEMM_BF16X3_CHROMA_F32 ef_gemm_rect_bf16x3_kernel<0, 0>; chroma: ef_gemm_seg_f32_kernel (f32 MFMAs; so is every rectangle
+//                                 mode's chroma when the split does not cover the block shape, ef_kp[2] == 0)
+//   ACX_EF_GEMM_BF16X3_PAIRWISE   ef_gemm_bf16x3_kernel, one pair per grid row; chroma: ef_gemm_kernel
+//   ACX_EF_GEMM_F32               ef_gemm_kernel
+static int launch_ef_gemms(acx_ctx *c, const SegBatch &seg, int B, int tiles_x, int tiles_y)
+{
+    int rc;
+    const bool f16 = c->ef_gemm == ACX_EF_GEMM_F16X2;
+    if (c->ef_gemm != ACX_EF_GEMM_F32 && c->ef_split_fmt != (f16 ? 1 : 0))
+        if ((rc = ef_build_splits(c, f16 ? 1 : 0)) != ACX_OK) return rc;
+    if (c->ef_gemm == ACX_EF_GEMM_F32) {
+        hipLaunchKernelGGL(acx::ef_gemm_kernel, dim3(tiles_x * tiles_y, B, 3), dim3(256), 0, c->stream,
+                           c->d_ef[0], c->d_ef[1], c->d_ef[2], c->d_efn[0], c->d_efn[1], c->d_efoff, c->d_efpd,
+                           c->d_scratch, c->ef_dims[0], c->ef_dims[1], c->ef_dims[2], tiles_x, 0);
+        return ACX_OK;
+    }
+    if (c->ef_gemm == ACX_EF_GEMM_BF16X3_PAIRWISE) {
+        hipLaunchKernelGGL(acx::ef_gemm_bf16x3_kernel, dim3(tiles_x * tiles_y, B, 2), dim3(acx::EFB_THREADS), 0, c->stream,
+                           c->d_efs[0], c->d_efs[1], c->d_efn[0], c->d_efn[1], c->d_efoff, c->d_efpd,
+                           c->d_scratch, c->ef_kp[0], c->ef_kp[1], tiles_x);
+        hipLaunchKernelGGL(acx::ef_gemm_kernel, dim3(tiles_x * tiles_y, B, 1), dim3(256), 0, c->stream,
+                           c->d_ef[0], c->d_ef[1], c->d_ef[2], c->d_efn[0], c->d_efn[1], c->d_efoff, c->d_efpd,
+                           c->d_scratch, c->ef_dims[0], c->ef_dims[1], c->ef_dims[2], tiles_x, 2);
+        return ACX_OK;
+    }
+    // the rectangle modes: the batch's rectangles to the device (the copies are staged before they return: `seg` may be rebuilt
+    // for the next batch)
+    if ((rc = ensure(c, c->d_segr, c->segr_cap, seg.rowg.size())) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_segc, c->segc_cap, seg.colg.size())) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_rects, c->rects_cap, seg.rects.size())) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_ptab, c->ptab_cap, seg.ptab.size())) != ACX_OK) return rc;
+    ACX_HIP(c, hipMemcpyAsync(c->d_segr, seg.rowg.data(), sizeof(acx::EfSegGroup) * seg.rowg.size(), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(c->d_segc, seg.colg.data(), sizeof(acx::EfSegGroup) * seg.colg.size(), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(c->d_rects, seg.rects.data(), sizeof(acx::EfSegRect) * seg.rects.size(), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(c->d_ptab, seg.ptab.data(), sizeof(int32_t) * seg.ptab.size(), hipMemcpyHostToDevice, c->stream));
+    if (seg.wgs.size() > 0x7fffffffu || seg.wgs3.size() > 0x7fffffffu)
+        return fail(c, ACX_ERR_UNSUPPORTED, "earlyfusion: batch too large for one launch");
+    if (!c->ef_rect_attr) {
+        for (const void *k : {reinterpret_cast<const void *>(acx::ef_gemm_rect_bf16x3_kernel<0, 0>),
+                              reinterpret_cast<const void *>(acx::ef_gemm_rect_bf16x3_kernel<1, 0>),
+                              reinterpret_cast<const void *>(acx::ef_gemm_rect_bf16x3_kernel<0, 1>),
+                              reinterpret_cast<const void *>(acx::ef_gemm_rect_bf16x3_kernel<1, 1>),
+                              reinterpret_cast<const void *>(acx::ef_gemm_rect_persist_dma_kernel<0>),
+                              reinterpret_cast<const void *>(acx::ef_gemm_rect_persist_dma_kernel<1>)})
+            ACX_HIP(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
+        ACX_HIP(c, hipMalloc((void **)&c->d_efctr, 2 * sizeof(unsigned)));
+        c->ef_rect_attr = true;
+    }
+    // a list of workgroup tiles to the device
+    auto upload = [c](const std::vector<acx::EfSegWg> &w, acx::EfSegWg *&d, size_t &cap) -> int {
+        const int rc = ensure(c, d, cap, w.size());
+        if (rc != ACX_OK) return rc;
+        ACX_HIP(c, hipMemcpyAsync(d, w.data(), sizeof(acx::EfSegWg) * w.size(), hipMemcpyHostToDevice, c->stream));
+        return ACX_OK;
+    };
+    using RectKernel = decltype(&acx::ef_gemm_rect_bf16x3_kernel<0, 0>);
+    // one workgroup per tile: mfcc and ssm over the 256 x 128-cell tiles of wgs2, chroma over those of wgs3 (their columns stop at
+    // the end of their reference track)
+    auto rect_eucl = [&](RectKernel kern) -> int {
+        if (seg.wgs2.empty()) return ACX_OK;
+        if ((rc = upload(seg.wgs2, c->d_segw2, c->segw2_cap)) != ACX_OK) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)seg.wgs2.size(), 1, 2), dim3(acx::EFR_THREADS), acx::EFR_LDS_BYTES, c->stream,
+                           c->d_efs[0], c->d_efs[1], c->d_efn[0], c->d_efn[1], c->d_efpd, c->d_rects, c->d_segw2, c->d_segr, c->d_segc,
+                           c->d_ptab, c->d_scratch, c->ef_kp[0], c->ef_kp[1], c->d_efsc[0], c->d_efsc[1]);
+        return ACX_OK;
+    };
+    auto rect_chroma = [&](RectKernel kern) -> int {
+        if (seg.wgs3.empty()) return ACX_OK;
+        if ((rc = upload(seg.wgs3, c->d_segw3, c->segw3_cap)) != ACX_OK) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)seg.wgs3.size(), 1, 1), dim3(acx::EFR_THREADS), acx::EFR_LDS_BYTES, c->stream,
+                           c->d_efs[2], c->d_efs[2], (const float *)nullptr, (const float *)nullptr, c->d_efpd, c->d_rects, c->d_segw3,
+                           c->d_segr, c->d_segc, c->d_ptab, c->d_scratch, c->ef_kp[2], c->ef_kp[2], c->d_efsc[2], c->d_efsc[2]);
+        return ACX_OK;
+    };
+    // chroma on f32 MFMAs over the 128 x 128-cell tiles of wgs
+    auto f32_chroma = [&]() -> int {
+        if (seg.wgs.empty()) return ACX_OK;
+        if ((rc = upload(seg.wgs, c->d_segw, c->segw_cap)) != ACX_OK) return rc;
+        hipLaunchKernelGGL(acx::ef_gemm_seg_f32_kernel, dim3((unsigned)seg.wgs.size()), dim3(256), 0, c->stream,
+                           c->d_ef[2], c->d_efpd, c->d_rects, c->d_segw, c->d_segr, c->d_segc, c->d_ptab, c->d_scratch, c->ef_dims[2]);
+        return ACX_OK;
+    };
+    const bool chroma_split = c->ef_kp[2] > 0;
+    static const bool one_tile = [] { const char *e = getenv("ACX_EF_PERSIST"); return e && e[0] == '0'; }();
+    if (f16 && !one_tile) {
+        // one workgroup per CU, each walking the tiles that the counters d_efctr[0] (mfcc, ssm) and [1] (chroma) deal out
+        const int ncu = std::max(1, c->n_cu);
+        if (!seg.wgs2.empty()) {
+            if ((rc = upload(seg.wgs2, c->d_segw2, c->segw2_cap)) != ACX_OK) return rc;
+            const int nt = (int)seg.wgs2.size();
+            const unsigned grid = (unsigned)std::min<int64_t>(ncu, 2 * (int64_t)nt);
+            ACX_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_efctr, (int)(2 * grid), 1, c->stream));
+            hipLaunchKernelGGL(acx::ef_gemm_rect_persist_dma_kernel<0>, dim3(grid), dim3(acx::EFR_THREADS), acx::EFR_LDS_BYTES, c->stream,
+                               c->d_efs[0], c->d_efs[1], c->d_efn[0], c->d_efn[1], c->d_efpd, c->d_rects, c->d_segw2, c->d_segr,
+                               c->d_segc, c->d_ptab, c->d_scratch, c->ef_kp[0], c->ef_kp[1], c->d_efsc[0], c->d_efsc[1], nt, 2, c->d_efctr);
+        }
+        if (!chroma_split) return f32_chroma();
+        if (!seg.wgs3.empty()) {
+            if ((rc = upload(seg.wgs3, c->d_segw3, c->segw3_cap)) != ACX_OK) return rc;
+            const int nt = (int)seg.wgs3.size();
+            const unsigned grid = (unsigned)std::min(ncu, nt);
+            ACX_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(c->d_efctr + 1), (int)(2 * grid), 1, c->stream));
+            hipLaunchKernelGGL(acx::ef_gemm_rect_persist_dma_kernel<1>, dim3(grid), dim3(acx::EFR_THREADS), acx::EFR_LDS_BYTES, c->stream,
+                               c->d_efs[2], c->d_efs[2], (const float *)nullptr, (const float *)nullptr, c->d_efpd, c->d_rects,
+                               c->d_segw3, c->d_segr, c->d_segc, c->d_ptab, c->d_scratch, c->ef_kp[2], c->ef_kp[2],
+                               c->d_efsc[2], c->d_efsc[2], nt, 1, c->d_efctr + 1);
+        }
+        return ACX_OK;
+    }
+    if (f16) {
+        if ((rc = rect_eucl(acx::ef_gemm_rect_bf16x3_kernel<0, 1>)) != ACX_OK) return rc;
+        return chroma_split ? rect_chroma(acx::ef_gemm_rect_bf16x3_kernel<1, 1>) : f32_chroma();
+    }
+    if (c->ef_gemm == ACX_EF_GEMM_BF16X3) {
+        if ((rc = rect_eucl(acx::ef_gemm_rect_bf16x3_kernel<0, 0>)) != ACX_OK) return rc;
+        return chroma_split ? rect_chroma(acx::ef_gemm_rect_bf16x3_kernel<1, 0>) : f32_chroma();
+    }
+    // ACX_EF_GEMM_BF16X3_CHROMA_F32
+    if ((rc = rect_eucl(acx::ef_gemm_rect_bf16x3_kernel<0, 0>)) != ACX_OK) return rc;
+    return f32_chroma();
+}
 
 static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params &p, float *out, const EfDebug *dbg,
                        const float *ext_matrix, int extM, int extN, const DevDst *dd);
@@ -1235,162 +1350,7 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
             {
                 const int tiles_x = (maxN + acx::EF_TILE - 1) / acx::EF_TILE, tiles_y = (maxM + acx::EF_TILE - 1) / acx::EF_TILE;
                 ProfScope ps(c, KS_EFGEMM, cells);
-                // mfcc, ssm: bf16 matrix pipe on the three-term splits; chroma (cosine, rolled by the pair's OTI): f32 MFMA
-                if (c->ef_gemm != ACX_EF_GEMM_F32 && c->ef_split_fmt != (c->ef_gemm == ACX_EF_GEMM_F16X2 ? 1 : 0))
-                    if ((rc = ef_build_splits(c, c->ef_gemm == ACX_EF_GEMM_F16X2 ? 1 : 0)) != ACX_OK) return rc;
-                if (c->ef_gemm == ACX_EF_GEMM_F32) {
-                    hipLaunchKernelGGL(acx::ef_gemm_kernel, dim3(tiles_x * tiles_y, B, 3), dim3(256), 0, c->stream,
-                                       c->d_ef[0], c->d_ef[1], c->d_ef[2], c->d_efn[0], c->d_efn[1], c->d_efoff, c->d_efpd,
-                                       c->d_scratch, c->ef_dims[0], c->ef_dims[1], c->ef_dims[2], tiles_x, 0);
-                } else {
-                    if (c->ef_gemm == ACX_EF_GEMM_BF16X3_PAIRWISE) {
-                        hipLaunchKernelGGL(acx::ef_gemm_bf16x3_kernel, dim3(tiles_x * tiles_y, B, 2), dim3(acx::EFB_THREADS), 0, c->stream,
-                                           c->d_efs[0], c->d_efs[1], c->d_efn[0], c->d_efn[1], c->d_efoff, c->d_efpd,
-                                           c->d_scratch, c->ef_kp[0], c->ef_kp[1], tiles_x);
-                    } else {
-                        if ((rc = ensure(c, c->d_segr, c->segr_cap, seg.rowg.size())) != ACX_OK) return rc;
-                        if ((rc = ensure(c, c->d_segc, c->segc_cap, seg.colg.size())) != ACX_OK) return rc;
-                        if ((rc = ensure(c, c->d_rects, c->rects_cap, seg.rects.size())) != ACX_OK) return rc;
-                        if ((rc = ensure(c, c->d_ptab, c->ptab_cap, seg.ptab.size())) != ACX_OK) return rc;
-                        ACX_HIP(c, hipMemcpyAsync(c->d_segr, seg.rowg.data(), sizeof(acx::EfSegGroup) * seg.rowg.size(), hipMemcpyHostToDevice, c->stream));
-                        ACX_HIP(c, hipMemcpyAsync(c->d_segc, seg.colg.data(), sizeof(acx::EfSegGroup) * seg.colg.size(), hipMemcpyHostToDevice, c->stream));
-                        ACX_HIP(c, hipMemcpyAsync(c->d_rects, seg.rects.data(), sizeof(acx::EfSegRect) * seg.rects.size(), hipMemcpyHostToDevice, c->stream));
-                        ACX_HIP(c, hipMemcpyAsync(c->d_ptab, seg.ptab.data(), sizeof(int32_t) * seg.ptab.size(), hipMemcpyHostToDevice, c->stream));
-                        // (the copies are staged before they return: `seg` may be rebuilt for the next batch)
-                        if (seg.wgs.size() > 0x7fffffffu || seg.wgs3.size() > 0x7fffffffu)
-                            return fail(c, ACX_ERR_UNSUPPORTED, "earlyfusion: batch too large for one launch");
-                        if (!c->ef_rect_attr) {
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_bf16x3_kernel<0, 0>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_bf16x3_kernel<1, 0>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_bf16x3_kernel<0, 1>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_bf16x3_kernel<1, 1>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_persist_kernel<0, 0>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_persist_kernel<1, 0>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_persist_kernel<0, 1>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_persist_kernel<1, 1>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_dma_kernel<0>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_dma_kernel<1>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_ws_kernel<0>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFW_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_ws_kernel<1>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFW_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_dma2_kernel<0>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_dma2_kernel<1>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_persist_dma_kernel<0>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::ef_gemm_rect_persist_dma_kernel<1>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-                            ACX_HIP(c, hipMalloc((void **)&c->d_efctr, 2 * sizeof(unsigned)));
-                            c->ef_rect_attr = true;
-                        }
-                        // Which kernel runs the three GEMMs (round 6, profiles/r06_ef.md):
-                        //   fp16 arithmetic (default):  ONE workgroup per CU walks the tiles, operands by LDS-DMA into three buffers
-                        //                               (ef_gemm_rect_persist_dma_kernel); ACX_EF_DMA=0: through the staging registers
-                        //                               (ef_gemm_rect_persist_kernel); ACX_EF_PERSIST=0: one workgroup per tile
-                        //   bf16x3:                     one workgroup per tile through the staging registers (round 5's kernel: the persistent
-                        //                               build and the DMA build -- two buffers -- both measure within noise of it, matrix
-                        //                               pipe 0.69 busy either way); ACX_EF_PERSIST=1 / ACX_EF_DMA=1: those builds
-                        const bool f16 = c->ef_gemm == ACX_EF_GEMM_F16X2;
-                        static const int persist_env = [] { const char *e = getenv("ACX_EF_PERSIST"); return !e ? -1 : (e[0] == '0' ? 0 : 1); }();
-                        static const int dma_env = [] { const char *e = getenv("ACX_EF_DMA"); return !e ? -1 : (e[0] == '0' ? 0 : 1); }();
-                        const bool persist = persist_env < 0 ? f16 : persist_env == 1;
-                        const bool use_dma = dma_env != 0 && f16;
-                        const auto pers_eucl = use_dma ? &acx::ef_gemm_rect_persist_dma_kernel<0>
-                                               : (f16 ? &acx::ef_gemm_rect_persist_kernel<0, 1> : &acx::ef_gemm_rect_persist_kernel<0, 0>);
-                        const auto pers_chroma = use_dma ? &acx::ef_gemm_rect_persist_dma_kernel<1>
-                                                 : (f16 ? &acx::ef_gemm_rect_persist_kernel<1, 1> : &acx::ef_gemm_rect_persist_kernel<1, 0>);
-                        // (bf16x3 by DMA into its two buffers, one workgroup per tile: only on request, ACX_EF_DMA=1 -- 31.5-31.7 against
-                        //  31.6 ms per 8128 pairs, profiles/r06_ef.md: that arithmetic runs at the matrix pipe's power budget)
-                        const bool use_dma2 = dma_env == 1 && !f16;
-                        const auto rect_eucl = use_dma ? &acx::ef_gemm_rect_dma_kernel<0> : (use_dma2 ? &acx::ef_gemm_rect_dma2_kernel<0>
-                                               : (f16 ? &acx::ef_gemm_rect_bf16x3_kernel<0, 1> : &acx::ef_gemm_rect_bf16x3_kernel<0, 0>));
-                        const auto rect_chroma = use_dma ? &acx::ef_gemm_rect_dma_kernel<1> : (use_dma2 ? &acx::ef_gemm_rect_dma2_kernel<1>
-                                                 : (f16 ? &acx::ef_gemm_rect_bf16x3_kernel<1, 1> : &acx::ef_gemm_rect_bf16x3_kernel<1, 0>));
-                        const int ncu = std::max(1, c->n_cu);
-                        if (!seg.wgs2.empty()) {
-                            if ((rc = ensure(c, c->d_segw2, c->segw2_cap, seg.wgs2.size())) != ACX_OK) return rc;
-                            ACX_HIP(c, hipMemcpyAsync(c->d_segw2, seg.wgs2.data(), sizeof(acx::EfSegWg) * seg.wgs2.size(), hipMemcpyHostToDevice, c->stream));
-                            static const bool ws_env = [] { const char *e = getenv("ACX_EF_WS"); return e && e[0] == '1'; }();
-                            if (ws_env && f16 && !seg.wgs5.empty()) {       // (experiment: wave-specialised workgroups, 128 x 128 tiles)
-                                if ((rc = ensure(c, c->d_segw2, c->segw2_cap, seg.wgs5.size())) != ACX_OK) return rc;
-                                ACX_HIP(c, hipMemcpyAsync(c->d_segw2, seg.wgs5.data(), sizeof(acx::EfSegWg) * seg.wgs5.size(), hipMemcpyHostToDevice, c->stream));
-                                const int nt = (int)seg.wgs5.size();
-                                const unsigned grid = (unsigned)std::min<int64_t>(ncu, 2 * (int64_t)nt);
-                                hipLaunchKernelGGL(acx::ef_gemm_rect_ws_kernel<0>, dim3(grid), dim3(acx::EFW_THREADS), acx::EFW_LDS_BYTES, c->stream,
-                                                   c->d_efs[0], c->d_efs[1], c->d_efn[0], c->d_efn[1], c->d_efpd, c->d_rects, c->d_segw2, c->d_segr,
-                                                   c->d_segc, c->d_ptab, c->d_scratch, c->ef_kp[0], c->ef_kp[1], c->d_efsc[0], c->d_efsc[1], nt, 2);
-                            } else
-                            if (persist) {
-                                const int nt = (int)seg.wgs2.size();
-                                const unsigned grid = (unsigned)std::min<int64_t>(ncu, 2 * (int64_t)nt);
-                                ACX_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_efctr, (int)(2 * grid), 1, c->stream));
-                                hipLaunchKernelGGL(pers_eucl, dim3(grid), dim3(acx::EFR_THREADS), acx::EFR_LDS_BYTES, c->stream,
-                                                   c->d_efs[0], c->d_efs[1], c->d_efn[0], c->d_efn[1], c->d_efpd, c->d_rects, c->d_segw2, c->d_segr,
-                                                   c->d_segc, c->d_ptab, c->d_scratch, c->ef_kp[0], c->ef_kp[1], c->d_efsc[0], c->d_efsc[1], nt, 2, c->d_efctr);
-                            } else
-                            hipLaunchKernelGGL(rect_eucl,
-                                               dim3((unsigned)seg.wgs2.size(), 1, 2), dim3(acx::EFR_THREADS),
-                                               acx::EFR_LDS_BYTES, c->stream, c->d_efs[0], c->d_efs[1], c->d_efn[0], c->d_efn[1], c->d_efpd,
-                                               c->d_rects, c->d_segw2, c->d_segr, c->d_segc, c->d_ptab, c->d_scratch, c->ef_kp[0], c->ef_kp[1],
-                                               c->d_efsc[0], c->d_efsc[1]);
-                        }
-                        // chroma (cosine, the first song rolled by the pair's OTI): the same kernel on the bin-major split
-                        // pool; ACX_EF_GEMM_BF16X3_CHROMA_F32 (and block shapes the split does not cover): f32 MFMAs
-                        if ((c->ef_gemm == ACX_EF_GEMM_BF16X3 || f16) && c->ef_kp[2] > 0) {
-                            if (!seg.wgs3.empty()) {
-                                if ((rc = ensure(c, c->d_segw3, c->segw3_cap, seg.wgs3.size())) != ACX_OK) return rc;
-                                ACX_HIP(c, hipMemcpyAsync(c->d_segw3, seg.wgs3.data(), sizeof(acx::EfSegWg) * seg.wgs3.size(), hipMemcpyHostToDevice, c->stream));
-                                static const bool ws_env3 = [] { const char *e = getenv("ACX_EF_WS"); return e && e[0] == '1'; }();
-                                if (ws_env3 && f16 && !seg.wgs6.empty()) {
-                                    if ((rc = ensure(c, c->d_segw3, c->segw3_cap, seg.wgs6.size())) != ACX_OK) return rc;
-                                    ACX_HIP(c, hipMemcpyAsync(c->d_segw3, seg.wgs6.data(), sizeof(acx::EfSegWg) * seg.wgs6.size(), hipMemcpyHostToDevice, c->stream));
-                                    const int nt = (int)seg.wgs6.size();
-                                    const unsigned grid = (unsigned)std::min(ncu, nt);
-                                    hipLaunchKernelGGL(acx::ef_gemm_rect_ws_kernel<1>, dim3(grid), dim3(acx::EFW_THREADS), acx::EFW_LDS_BYTES, c->stream,
-                                                       c->d_efs[2], c->d_efs[2], (const float *)nullptr, (const float *)nullptr, c->d_efpd, c->d_rects,
-                                                       c->d_segw3, c->d_segr, c->d_segc, c->d_ptab, c->d_scratch, c->ef_kp[2], c->ef_kp[2],
-                                                       c->d_efsc[2], c->d_efsc[2], nt, 1);
-                                } else
-                                if (persist) {
-                                    const int nt = (int)seg.wgs3.size();
-                                    const unsigned grid = (unsigned)std::min(ncu, nt);
-                                    ACX_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(c->d_efctr + 1), (int)(2 * grid), 1, c->stream));
-                                    hipLaunchKernelGGL(pers_chroma, dim3(grid), dim3(acx::EFR_THREADS), acx::EFR_LDS_BYTES, c->stream,
-                                                       c->d_efs[2], c->d_efs[2], (const float *)nullptr, (const float *)nullptr, c->d_efpd, c->d_rects,
-                                                       c->d_segw3, c->d_segr, c->d_segc, c->d_ptab, c->d_scratch, c->ef_kp[2], c->ef_kp[2],
-                                                       c->d_efsc[2], c->d_efsc[2], nt, 1, c->d_efctr + 1);
-                                } else
-                                hipLaunchKernelGGL(rect_chroma,
-                                                   dim3((unsigned)seg.wgs3.size(), 1, 1), dim3(acx::EFR_THREADS),
-                                                   acx::EFR_LDS_BYTES, c->stream, c->d_efs[2], c->d_efs[2], (const float *)nullptr, (const float *)nullptr,
-                                                   c->d_efpd, c->d_rects, c->d_segw3, c->d_segr, c->d_segc, c->d_ptab, c->d_scratch, c->ef_kp[2], c->ef_kp[2],
-                                                   c->d_efsc[2], c->d_efsc[2]);
-                            }
-                        } else if (!seg.wgs.empty()) {
-                            if ((rc = ensure(c, c->d_segw, c->segw_cap, seg.wgs.size())) != ACX_OK) return rc;
-                            ACX_HIP(c, hipMemcpyAsync(c->d_segw, seg.wgs.data(), sizeof(acx::EfSegWg) * seg.wgs.size(), hipMemcpyHostToDevice, c->stream));
-                            hipLaunchKernelGGL(acx::ef_gemm_seg_f32_kernel, dim3((unsigned)seg.wgs.size()), dim3(256), 0, c->stream,
-                                               c->d_ef[2], c->d_efpd, c->d_rects, c->d_segw, c->d_segr, c->d_segc, c->d_ptab,
-                                               c->d_scratch, c->ef_dims[2]);
-                        }
-                    }
-                    if (c->ef_gemm == ACX_EF_GEMM_BF16X3_PAIRWISE)
-                        hipLaunchKernelGGL(acx::ef_gemm_kernel, dim3(tiles_x * tiles_y, B, 1), dim3(256), 0, c->stream,
-                                           c->d_ef[0], c->d_ef[1], c->d_ef[2], c->d_efn[0], c->d_efn[1], c->d_efoff, c->d_efpd,
-                                           c->d_scratch, c->ef_dims[0], c->ef_dims[1], c->ef_dims[2], tiles_x, 2);
-                }
+                if ((rc = launch_ef_gemms(c, seg, B, tiles_x, tiles_y)) != ACX_OK) return rc;
             }
         }
         const int nfeat = ext_matrix ? 1 : 3;

@@ -43,7 +43,7 @@ def other_source_sha16():
     """Hash of the kernel sources the companion legs run (scripts/make_traffic_other.py stamps its record with it)."""
     import hashlib
     h = hashlib.sha256()
-    for f in ("serra09_kernels.hpp", "serra09_band2_kernels.hpp", "acx_band.hip", "ef_kernels.hpp", "ef_gemm_persist_kernels.hpp", "ef_gemm_dma_kernels.hpp", "ef_rowstat2_kernels.hpp", "simple_kernels.hpp", "Makefile"):
+    for f in ("serra09_kernels.hpp", "serra09_band2_kernels.hpp", "acx_band.hip", "ef_kernels.hpp", "ef_gemm_dma_kernels.hpp", "ef_rowstat2_kernels.hpp", "simple_kernels.hpp", "Makefile"):
         with open(os.path.join(ROOT, "acoss_amd", "csrc", f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]

@@ -1,8 +1,8 @@
-"""Development aid (GPU box): race screen of the EarlyFusion GEMMs that stage their operands by LDS-DMA (ef_gemm_dma_kernels.hpp) -- an
+"""Development aid (GPU box): race screen of the EarlyFusion GEMM that stages its operands by LDS-DMA (ef_gemm_dma_kernels.hpp) -- an
 early read of a DMA'd buffer passes whenever the data happens to land first, so one clean run proves little.  Several pools (dense
 grid tiles, sparse pair lists, tracks of 1-40 blocks: rims and idle waves everywhere), each run REPS times in the default build
 (persistent + DMA) and compared bit for bit with ONE run of the register-staging one-tile kernel in a child process
-(ACX_EF_PERSIST=0 ACX_EF_DMA=0).   python scripts/ef_dma_soak.py [reps]"""
+(ACX_EF_PERSIST=0).   python scripts/ef_dma_soak.py [reps]"""
 import os
 import subprocess
 import sys
@@ -50,7 +50,7 @@ if __name__ == "__main__":
         sys.exit(0)
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     tmp = "/tmp/ef_soak_ref.npz"
-    env = dict(os.environ, ACX_EF_PERSIST="0", ACX_EF_DMA="0")
+    env = dict(os.environ, ACX_EF_PERSIST="0")
     subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", tmp], env=env)
     ref = np.load(tmp)
     bad = 0

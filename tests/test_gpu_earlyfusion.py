@@ -470,9 +470,10 @@ def test_every_gemm_instantiation_per_cell_in_multi_pair_rectangles(ctx):
     """Every instantiation of ef_gemm_rect_bf16x3_kernel<CH, F16> (mfcc / ssm and chroma, three bf16 terms and two fp16 terms)
     on rectangles that hold MANY pairs -- the product path's tiles: operands shared between the pairs of a track, sub-tiles
     dropped into their own pair's matrix, track ends inside a workgroup tile -- cell by cell against f64 products, and bit for bit
-    against the one-pair rectangle of acx_ef_debug_pair.  (The fp16 / bf16 K = 32 MFMA returns garbage when its destination
-    registers overlap a dying source operand, tests/test_isa_lint.py: whether the compiler allocates that way depends on the
-    instantiation and on what surrounds the k loop, so each one is checked through the launch the product takes.)"""
+    against the one-pair rectangle of acx_ef_debug_pair.  (How the compiler allocates and schedules the k loop's K = 32 MFMAs
+    depends on the instantiation and on what surrounds the loop, so each one is checked through the launch the product takes.
+    A destination over a source operand, once suspected, measured harmless in round 6: scripts/isa_lint.py,
+    profiles/r06_mfma_overlap_probe.txt.)"""
     rng = np.random.default_rng(61)
     nbs = [1, 15, 16, 17, 33, 128, 129, 300, 47, 250, 64, 96] + [int(v) for v in rng.integers(20, 140, 12)]
 
@@ -520,9 +521,9 @@ def test_every_gemm_instantiation_per_cell_in_multi_pair_rectangles(ctx):
 
 def test_short_k_loops_of_small_feature_dims(ctx):
     """Feature dimensions far below the reference's 650 / 1225 / 480: k loops of one to four 32-k chunks.  The persistent GEMM
-    (ef_gemm_persist_kernels.hpp) resolves its next tile behind the first four chunks of a k loop of at least seven; shorter loops take
-    the path that resolves it behind the loop -- no DA-TACOS-shaped set ever runs it.  Cells against f64 products, both 16-bit
-    arithmetics, many pairs per rectangle, several tiles per workgroup."""
+    (ef_gemm_rect_persist_dma_kernel, ef_gemm_dma_kernels.hpp) resolves its next tile behind the first four chunks of a k loop of at
+    least seven; shorter loops take the path that resolves it behind the loop -- no DA-TACOS-shaped set ever runs it.  Cells against
+    f64 products, both 16-bit arithmetics, many pairs per rectangle, several tiles per workgroup."""
     rng = np.random.default_rng(77)
     for dims in ((40, 100, 96), (20, 32, 96), (200, 230, 192)):
         G = dims[2] // 12
@@ -748,24 +749,22 @@ ctx.close()
 
 @pytest.mark.timeout(900)
 def test_gemm_kernel_variants_give_the_same_bits(tmp_path):
-    """The rectangle GEMMs exist as several kernels per arithmetic -- one workgroup per tile or a persistent workgroup per CU, operands through
-    the staging registers or by LDS-DMA, and (fp16 arithmetic, an experiment) wave-specialised workgroups on 128 x 128 tiles -- chosen per
-    process (ACX_EF_PERSIST, ACX_EF_DMA, ACX_EF_WS).  Same
-    tiles, same MFMAs in the same order: every variant must return the default's scores bit for bit, on a pair list that fills whole
-    grid rectangles, on random pairs (sparse rectangles, one pair per tile) and with tracks of 1-17 blocks (rims everywhere)."""
+    """The fp16 arithmetic's rectangle GEMMs exist as two kernels, chosen per process: the default persistent workgroup per CU with its
+    operands by LDS-DMA (ef_gemm_rect_persist_dma_kernel) and, with ACX_EF_PERSIST=0, one workgroup per tile with its operands through the
+    staging registers (ef_gemm_rect_bf16x3_kernel<CH, 1>), kept as an independent cross-check.  Same tiles, same MFMAs in the same
+    order: the cross-check must return the default's scores bit for bit, on a pair list that fills whole grid rectangles, on random
+    pairs (sparse rectangles, one pair per tile) and with tracks of 1-17 blocks (rims everywhere).  The bf16x3 arithmetic has one
+    kernel: it runs once, for the shape check against the fp16 scores."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     results = {}
-    for mode, variants in (("f16x2", ({}, {"ACX_EF_DMA": "0"}, {"ACX_EF_PERSIST": "0"}, {"ACX_EF_PERSIST": "0", "ACX_EF_DMA": "0"}, {"ACX_EF_WS": "1"})),
-                           ("bf16x3", ({}, {"ACX_EF_PERSIST": "1"}, {"ACX_EF_DMA": "1"}))):
+    for mode, variants in (("f16x2", ({}, {"ACX_EF_PERSIST": "0"})), ("bf16x3", ({},))):
         for k, extra in enumerate(variants):
             out = str(tmp_path / ("%s_%d.npy" % (mode, k)))
             env = dict(os.environ)
-            env.pop("ACX_EF_DMA", None)
             env.pop("ACX_EF_PERSIST", None)
-            env.pop("ACX_EF_WS", None)
             env.update(extra)
             subprocess.check_call([sys.executable, "-c", _VARIANT_SNIPPET % {"root": root, "mode": mode, "out": out}], env=env, timeout=300)
             results[(mode, k)] = np.load(out)
