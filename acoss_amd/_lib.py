@@ -33,12 +33,14 @@ EXPORTS = [
     "acx_dev_alloc", "acx_dev_free", "acx_dev_read", "acx_dev_sync",
     "acx_comm_id", "acx_comm_init", "acx_comm_destroy", "acx_grid_allgather", "acx_pair_grid_ranks", "acx_set_ef_fuse",
     "acx_device_info", "acx_ef_debug_pairs",
+    "acx_ftm2d_default_params", "acx_ftm2d_pool_begin", "acx_ftm2d_pool_tracks", "acx_ftm2d_pool_end",
+    "acx_ftm2d_upload_shingles", "acx_ftm2d_download_shingles", "acx_ftm2d_debug_track", "acx_ftm2d_pairs",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
 
-ALGO_SERRA09, ALGO_CHENFUSION, ALGO_SIMPLE, ALGO_EARLYFUSION = 0, 1, 2, 3
-GRID_PLANES = {ALGO_SERRA09: 1, ALGO_CHENFUSION: 2, ALGO_SIMPLE: 1, ALGO_EARLYFUSION: 4}
+ALGO_SERRA09, ALGO_CHENFUSION, ALGO_SIMPLE, ALGO_EARLYFUSION, ALGO_FTM2D = 0, 1, 2, 3, 4
+GRID_PLANES = {ALGO_SERRA09: 1, ALGO_CHENFUSION: 2, ALGO_SIMPLE: 1, ALGO_EARLYFUSION: 4, ALGO_FTM2D: 1}
 
 
 class AcxError(RuntimeError):
@@ -71,6 +73,11 @@ class SimpleParams(ctypes.Structure):
 class EfPrepParams(ctypes.Structure):
     """acx_ef_prep_params (include/acx.h); defaults = EarlyFusion ctor, earlyfusion_traile.py:44-45."""
     _fields_ = [("blocksize", ctypes.c_int32), ("mfccs_per_block", ctypes.c_int32), ("chromas_per_block", ctypes.c_int32)]
+
+
+class Ftm2dParams(ctypes.Structure):
+    """acx_ftm2d_params (include/acx.h); defaults = FTM2D ctor, ftm2d.py:23."""
+    _fields_ = [("pwr", ctypes.c_double), ("c", ctypes.c_double), ("win", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class Serra09Params(ctypes.Structure):
@@ -231,6 +238,16 @@ def load():
     L.acx_grid_scatter.argtypes = [lp, ctypes.c_int32, gp, fp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                    ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64, ctypes.c_int32]
     L.acx_pair_grid.argtypes = [vp, gp, vp, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64, ctypes.c_int32]
+    fpp = ctypes.POINTER(Ftm2dParams)
+    L.acx_ftm2d_default_params.restype = None
+    L.acx_ftm2d_default_params.argtypes = [fpp]
+    L.acx_ftm2d_pool_begin.argtypes = [vp, ctypes.c_int32, fpp]
+    L.acx_ftm2d_pool_tracks.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, fp, lp, lp, lp]
+    L.acx_ftm2d_pool_end.argtypes = [vp]
+    L.acx_ftm2d_upload_shingles.argtypes = [vp, dp, ctypes.c_int32, ctypes.c_int32]
+    L.acx_ftm2d_download_shingles.argtypes = [vp, dp, ctypes.c_int64]
+    L.acx_ftm2d_debug_track.argtypes = [vp, fp, ctypes.c_int64, lp, ctypes.c_int64, fpp, fp, dp, dp, dp, dp, lp]
+    L.acx_ftm2d_pairs.argtypes = [vp, ip, ctypes.c_int64, fp]
     _check_hip_version(L)
     _lib = L
     return L
@@ -254,6 +271,30 @@ def _fptr(a):
 
 def _lptr(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def _dptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+def _params_ptr(params):
+    """The grid calls' `const void *params`: the struct's address, or NULL (FTM2D takes no parameters)."""
+    return None if params is None else ctypes.cast(ctypes.byref(params), ctypes.c_void_p)
+
+
+def ftm2d_params(pwr=1.96, win=75, c=5):
+    """acx_ftm2d_params (FTM2D ctor arguments PWR, WIN, C)."""
+    return Ftm2dParams(float(pwr), float(c), int(win), 0)
+
+
+def _ftm2d_pack(tracks):
+    """[{"chroma": (T, 12), "onsets": (n,)}] -> chroma (sum T, 12) f32, offsets, onsets int64, offsets."""
+    ch = [np.ascontiguousarray(t["chroma"], dtype=np.float32).reshape(-1, 12) for t in tracks]
+    on = [np.ascontiguousarray(t["onsets"], dtype=np.int64).reshape(-1) for t in tracks]
+    coff = np.concatenate([[0], np.cumsum([len(a) for a in ch])]).astype(np.int64)
+    ooff = np.concatenate([[0], np.cumsum([len(a) for a in on])]).astype(np.int64)
+    cat = lambda xs, shape, dt: np.ascontiguousarray(np.concatenate(xs)) if sum(len(x) for x in xs) else np.zeros(shape, dt)
+    return cat(ch, (1, 12), np.float32), coff, cat(on, (1,), np.int64), ooff
 
 
 def grid_plan(lengths, algo, symmetric, world=1, tile=0, want_tiles=False):
@@ -665,8 +706,7 @@ class Context(object):
                 if P.dtype != np.float32 or P.shape != (n, n) or not P.flags["C_CONTIGUOUS"]:
                     raise ValueError("pair_grid_ranks: planes must be C-contiguous (N, N) float32")
             ptrs, ld = (ctypes.c_void_p * len(planes))(*[P.ctypes.data for P in planes]), n
-        self._check(self._L.acx_pair_grid_ranks(self._h, ctypes.byref(spec), ctypes.cast(ctypes.byref(params), ctypes.c_void_p),
-                                                ptrs, int(ld), int(bool(mirror))))
+        self._check(self._L.acx_pair_grid_ranks(self._h, ctypes.byref(spec), _params_ptr(params), ptrs, int(ld), int(bool(mirror))))
 
     # ------------------------------------------------------------------ the N x N pair grid
     def torch_device(self):
@@ -684,7 +724,7 @@ class Context(object):
     def grid_run(self, spec, params, rank, dev_ptr, first=0, count=-1):
         """acx_grid_run: this rank's tiles [first, first + count) into the DEVICE buffer at `dev_ptr`
         (e.g. torch_tensor.data_ptr()) of floats_per_rank[rank] floats."""
-        self._check(self._L.acx_grid_run(self._h, ctypes.byref(spec), ctypes.cast(ctypes.byref(params), ctypes.c_void_p),
+        self._check(self._L.acx_grid_run(self._h, ctypes.byref(spec), _params_ptr(params),
                                          int(rank), int(first), int(count), ctypes.c_void_p(int(dev_ptr))))
 
     def pair_grid(self, algo, symmetric, params, planes, mirror, tile=0):
@@ -695,7 +735,7 @@ class Context(object):
             if P.dtype != np.float32 or P.shape != (n, n) or not P.flags["C_CONTIGUOUS"]:
                 raise ValueError("pair_grid: planes must be C-contiguous (N, N) float32")
         ptrs = (ctypes.c_void_p * len(planes))(*[P.ctypes.data for P in planes])
-        self._check(self._L.acx_pair_grid(self._h, ctypes.byref(spec), ctypes.cast(ctypes.byref(params), ctypes.c_void_p),
+        self._check(self._L.acx_pair_grid(self._h, ctypes.byref(spec), _params_ptr(params),
                                           ptrs, n, int(bool(mirror))))
 
     def snf_fuse_dists(self, Ds, K=20, niters=20, reg_diag=1.0, mu=0.5, want_ws=False):
@@ -759,6 +799,70 @@ class Context(object):
         self._check(self._L.acx_qmax_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                                             R.shape[0], R.shape[1], ctypes.byref(p), ctypes.byref(score)))
         return float(score.value)
+
+    # ------------------------------------------------------------------ FTM2D
+    def ftm2d_pool_begin(self, n_tracks, pwr=1.96, win=75, c=5):
+        """Open an (n_tracks, 12 WIN) shingle pool (acx_ftm2d_pool_begin)."""
+        self._check(self._L.acx_ftm2d_pool_begin(self._h, int(n_tracks), ctypes.byref(ftm2d_params(pwr, win, c))))
+        self.ftm2d_shape = (int(n_tracks), 12 * int(win))
+
+    def ftm2d_pool_tracks(self, first, tracks):
+        """Shingles of tracks [first, first + len(tracks)) from their raw features: dicts with "chroma" (T, 12) and
+        "onsets" (beat frame indices) (acx_ftm2d_pool_tracks)."""
+        ch, coff, on, ooff = _ftm2d_pack(tracks)
+        self._check(self._L.acx_ftm2d_pool_tracks(self._h, int(first), len(tracks), _fptr(ch), _lptr(coff), _lptr(on), _lptr(ooff)))
+
+    def ftm2d_pool_end(self):
+        self._check(self._L.acx_ftm2d_pool_end(self._h))
+
+    def ftm2d_upload_raw_pool(self, tracks, pwr=1.96, win=75, c=5, batch=256):
+        """FTM2D.load_features for every track on the device.  `tracks`: any sequence (len + indexing) of dicts with
+        "chroma" and "onsets" -- indexed `batch` tracks at a time, so a lazy sequence that reads feature files keeps
+        at most one batch of raw features in host memory."""
+        n = len(tracks)
+        self.ftm2d_pool_begin(n, pwr, win, c)
+        for t0 in range(0, n, int(batch)):
+            self.ftm2d_pool_tracks(t0, [tracks[i] for i in range(t0, min(n, t0 + int(batch)))])
+        self.ftm2d_pool_end()
+
+    def ftm2d_upload_shingles(self, shingles):
+        """Ready (N, D) f64 shingles instead (acx_ftm2d_upload_shingles)."""
+        S = np.ascontiguousarray(shingles, dtype=np.float64)
+        if S.ndim != 2:
+            raise ValueError("ftm2d_upload_shingles: shingles must be (N, D)")
+        self._check(self._L.acx_ftm2d_upload_shingles(self._h, _dptr(S), S.shape[0], S.shape[1]))
+        self.ftm2d_shape = S.shape
+
+    def ftm2d_download_shingles(self):
+        out = np.empty(self.ftm2d_shape, np.float64)
+        self._check(self._L.acx_ftm2d_download_shingles(self._h, _dptr(out), out.size))
+        return out
+
+    def ftm2d_pairs(self, pairs):
+        """(K,) float32 exp(-|s_i - s_j|^2) of the shingle pool (acx_ftm2d_pairs)."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        out = np.empty(len(pairs), np.float32)
+        self._check(self._L.acx_ftm2d_pairs(self._h, pairs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(pairs), _fptr(out)))
+        return out
+
+    def ftm2d_debug_track(self, chroma, onsets, pwr=1.96, win=75, c=5):
+        """One track's intermediates (acx_ftm2d_debug_track): synced (nbeats, 12) f32, pwr (nbeats, 12), logwin (nwin, D),
+        median (D,), shingle (D,)."""
+        chroma = np.ascontiguousarray(chroma, dtype=np.float32).reshape(-1, 12)
+        onsets = np.ascontiguousarray(onsets, dtype=np.int64).reshape(-1)
+        p = ftm2d_params(pwr, win, c)
+        dims = np.zeros(3, np.int64)
+        ch_ptr = _fptr(chroma if len(chroma) else np.zeros((1, 12), np.float32))
+        on_ptr = _lptr(onsets if len(onsets) else np.zeros(1, np.int64))
+        self._check(self._L.acx_ftm2d_debug_track(self._h, ch_ptr, len(chroma), on_ptr, len(onsets), ctypes.byref(p),
+                                                  None, None, None, None, None, _lptr(dims)))
+        nb, nw, D = (int(x) for x in dims)
+        out = dict(synced=np.empty((nb, 12), np.float32), pwr=np.empty((nb, 12)), logwin=np.empty((max(nw, 0), D)),
+                   median=np.empty(D), shingle=np.empty(D))
+        self._check(self._L.acx_ftm2d_debug_track(self._h, ch_ptr, len(chroma), on_ptr, len(onsets), ctypes.byref(p),
+                                                  _fptr(out["synced"]), _dptr(out["pwr"]), _dptr(out["logwin"]),
+                                                  _dptr(out["median"]), _dptr(out["shingle"]), _lptr(dims)))
+        return out
 
     def profile_enable(self, on=True):
         self._check(self._L.acx_profile_enable(self._h, int(bool(on))))

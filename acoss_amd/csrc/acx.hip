@@ -27,6 +27,7 @@
 #include "ef_rowstat2_kernels.hpp"
 #include "ef_gemm_dma_kernels.hpp"
 #include "ef_prep_kernels.hpp"
+#include "ftm2d_kernels.hpp"
 #include "grid.hpp"
 
 using acx::PairDesc;
@@ -114,6 +115,12 @@ struct acx_ctx {
     int32_t ef_fuse = ACX_EF_FUSE_FAST;               // arithmetic of getWCSM's weights and the fused matrix (acx_set_ef_fuse)
     int32_t ef_open = 0;                              // > 0: a pool of that many tracks is being filled (acx_ef_pool_begin .. _end)
     std::vector<uint8_t> ef_filled;                   // per track of the open pool: handed over by acx_ef_pool_tracks yet?
+    // FTM2D shingle pool: (ftm_n, ftm_dim) f64, one row per track
+    double *d_ftm = nullptr;
+    int32_t ftm_n = 0, ftm_dim = 0;
+    int32_t ftm_open = 0;                             // > 0: a pool of that many tracks is being filled (acx_ftm2d_pool_begin .. _end)
+    std::vector<uint8_t> ftm_filled;                  // per track of the open pool: handed over by acx_ftm2d_pool_tracks yet?
+    acx_ftm2d_params ftm_params = {0.0, 0.0, 0, 0};
     // multi-GPU inside the library (acx_comm_*): one RCCL communicator rank per context
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -1595,6 +1602,7 @@ void acx_destroy(acx_ctx *c)
     if (c->d_pairs) (void)hipFree(c->d_pairs);
     if (c->d_out64) (void)hipFree(c->d_out64);
     ef_free_pool(c);
+    if (c->d_ftm) (void)hipFree(c->d_ftm);
     if (c->d_efpd) (void)hipFree(c->d_efpd);
     if (c->d_efbits) (void)hipFree(c->d_efbits);
     if (c->d_segr) (void)hipFree(c->d_segr);
@@ -2535,6 +2543,305 @@ int acx_sw_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, float *sco
     return ACX_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// FTM2D (ftm2d.py): shingles of raw chroma + beat onsets built on the device, pair scores
+// ---------------------------------------------------------------------------------------
+void acx_ftm2d_default_params(acx_ftm2d_params *p)
+{
+    if (!p) return;
+    p->pwr = 1.96;      // FTM2D ctor, ftm2d.py:23
+    p->c = 5.0;
+    p->win = 75;
+    p->reserved = 0;
+}
+
+static int ftm2d_check_params(acx_ctx *c, const char *who, const acx_ftm2d_params *p)
+{
+    if (!p) return fail(c, ACX_ERR_INVALID, std::string(who) + ": params must not be NULL");
+    if (p->win < 1 || p->win > acx::FTM_MAXWIN)
+        return fail(c, ACX_ERR_INVALID, std::string(who) + ": WIN must be in 1..256 on the device (got " + std::to_string(p->win) + ")");
+    if (!std::isfinite(p->pwr) || !std::isfinite(p->c)) return fail(c, ACX_ERR_INVALID, std::string(who) + ": PWR and C must be finite");
+    return ACX_OK;
+}
+
+static void ftm2d_free_pool(acx_ctx *c)
+{
+    if (c->d_ftm) (void)hipFree(c->d_ftm);
+    c->d_ftm = nullptr;
+    c->ftm_n = c->ftm_dim = 0;
+    c->ftm_open = 0;
+    c->ftm_filled.clear();
+}
+
+// Host copies of one track's intermediates (acx_ftm2d_debug_track); any may be NULL.
+struct FtmDebug { float *synced; double *pwr, *logwin, *median; };
+
+// Shingles of tracks [0, nt) (chroma rows coff[t] .. coff[t + 1], onsets ooff[t] .. ooff[t + 1]) into d_out, a DEVICE
+// (nt, 12 WIN) f64 array.  Every track is checked before the first launch (negative onset, fewer beats than WIN, a
+// window matrix beyond the scratch limit); `track_base` only names tracks in messages.  Then sub-batches of whole
+// tracks whose window matrices fit the scratch limit (and whose chroma fits RAW_SLICE_FLOATS) run F1 .. F5.
+static int ftm2d_build(acx_ctx *c, const char *who, const float *chroma, const int64_t *coff, const int64_t *onsets,
+                       const int64_t *ooff, int32_t nt, int32_t track_base, const acx_ftm2d_params &p, double *d_out,
+                       const FtmDebug *dbg)
+{
+    const int win = p.win, D = 12 * win;
+    const int64_t lim = std::min<int64_t>(scratch_limit_bytes(c), (int64_t)4 << 30);     // window matrices per sub-batch (bytes)
+    // librosa.util.sync(X, onsets, pad=True): boundaries unique(clip(onsets, 0, T) + {0, T}), librosa.util.fix_frames
+    std::vector<int64_t> nbeat((size_t)nt), bnd;
+    std::vector<std::vector<int64_t>> tb((size_t)nt);
+    for (int t = 0; t < nt; ++t) {
+        if (coff[t + 1] < coff[t] || ooff[t + 1] < ooff[t]) return fail(c, ACX_ERR_INVALID, std::string(who) + ": offsets must be non-decreasing");
+        const int64_t T = coff[t + 1] - coff[t];
+        std::vector<int64_t> &b = tb[t];
+        b.reserve((size_t)(ooff[t + 1] - ooff[t]) + 2);
+        b.push_back(0);
+        b.push_back(T);
+        for (int64_t k = ooff[t]; k < ooff[t + 1]; ++k) {
+            if (onsets[k] < 0)
+                return fail(c, ACX_ERR_INVALID, std::string(who) + ": track " + std::to_string(track_base + t) + " has a negative onset (" +
+                            std::to_string(onsets[k]) + "); librosa.util.fix_frames raises there");
+            b.push_back(std::min(onsets[k], T));
+        }
+        std::sort(b.begin(), b.end());
+        b.erase(std::unique(b.begin(), b.end()), b.end());
+        nbeat[t] = (int64_t)b.size() - 1;
+        if (nbeat[t] < win)
+            return fail(c, ACX_ERR_INVALID, std::string(who) + ": track " + std::to_string(track_base + t) + " has " + std::to_string(nbeat[t]) +
+                        " beats, fewer than WIN = " + std::to_string(win) + " (btchroma_to_fftmat returns None there)");
+        if ((nbeat[t] - win + 1) * D * (int64_t)sizeof(double) > lim)
+            return fail(c, ACX_ERR_NOMEM, std::string(who) + ": the window matrix of track " + std::to_string(track_base + t) + " does not fit the scratch limit");
+    }
+    // twiddles exp(-2 pi i m / n), n = 12 and WIN
+    std::vector<double> tw12(24), twW(2 * (size_t)win);
+    for (int m = 0; m < 12; ++m) { tw12[2 * m] = std::cos(2.0 * M_PI * m / 12.0); tw12[2 * m + 1] = -std::sin(2.0 * M_PI * m / 12.0); }
+    for (int m = 0; m < win; ++m) { twW[2 * m] = std::cos(2.0 * M_PI * m / win); twW[2 * m + 1] = -std::sin(2.0 * M_PI * m / win); }
+    // windows per workgroup of ftm2d_window_kernel: as many (<= 8) as LDS holds
+    auto lds_bytes = [&](int nw) { return sizeof(double) * (size_t)(2 * 7 * (nw + win - 1) + 2 * win + nw * 7 * win + nw); };
+    int nw = acx::FTM_NW;
+    while (nw > 1 && lds_bytes(nw) > (size_t)acx::FTM_LDS) --nw;
+    float *d_ch = nullptr, *d_sync = nullptr;
+    int64_t *d_coff = nullptr, *d_bnd = nullptr, *d_boff = nullptr, *d_woff = nullptr;
+    double *d_pwr = nullptr, *d_G = nullptr, *d_lw = nullptr, *d_med = nullptr, *d_tw = nullptr;
+    acx::FtmBlock *d_blk = nullptr;
+    auto cleanup = [&]() {
+        void *ps[] = {d_ch, d_sync, d_coff, d_bnd, d_boff, d_woff, d_pwr, d_G, d_lw, d_med, d_blk};
+        for (void *q : ps) if (q) (void)hipFree(q);
+        d_ch = d_sync = nullptr; d_coff = d_bnd = d_boff = d_woff = nullptr; d_pwr = d_G = d_lw = d_med = nullptr; d_blk = nullptr;
+    };
+    auto cleanup_all = [&]() { cleanup(); if (d_tw) (void)hipFree(d_tw); d_tw = nullptr; };
+#define ACX_HIPC(expr_) do { const hipError_t ec_ = (expr_); if (ec_ != hipSuccess) { cleanup_all(); ACX_HIP(c, ec_); } } while (0)
+    ACX_HIPC(hipMalloc((void **)&d_tw, sizeof(double) * (24 + 2 * (size_t)win)));
+    ACX_HIPC(hipMemcpy(d_tw, tw12.data(), sizeof(double) * 24, hipMemcpyHostToDevice));
+    ACX_HIPC(hipMemcpy(d_tw + 24, twW.data(), sizeof(double) * 2 * win, hipMemcpyHostToDevice));
+    for (int t0 = 0; t0 < nt;) {
+        int t1 = t0 + 1;
+        int64_t lw = (nbeat[t0] - win + 1) * D * (int64_t)sizeof(double);
+        while (t1 < nt && t1 - t0 < 65535) {
+            const int64_t more = (nbeat[t1] - win + 1) * D * (int64_t)sizeof(double);
+            if (lw + more > lim || (coff[t1 + 1] - coff[t0]) * 12 > RAW_SLICE_FLOATS) break;
+            lw += more;
+            ++t1;
+        }
+        const int n = t1 - t0;
+        const int64_t rows = coff[t1] - coff[t0];
+        std::vector<int64_t> lc(n + 1), lb(n + 1), lwo(n + 1), lbnd;
+        std::vector<acx::FtmBlock> blk;
+        lc[0] = lb[0] = lwo[0] = 0;
+        for (int t = 0; t < n; ++t) {
+            lc[t + 1] = coff[t0 + t + 1] - coff[t0];
+            lb[t + 1] = lb[t] + nbeat[t0 + t];
+            const int64_t nwin = nbeat[t0 + t] - win + 1;
+            lwo[t + 1] = lwo[t] + nwin;
+            for (int64_t b : tb[t0 + t]) lbnd.push_back(lc[t] + b);
+            for (int64_t w = 0; w < nwin; w += nw) blk.push_back(acx::FtmBlock{t, (int32_t)w});
+        }
+        const int64_t nb = lb[n], nwt = lwo[n];
+        ACX_HIPC(hipMalloc((void **)&d_ch, sizeof(float) * std::max<int64_t>(1, rows) * 12));
+        ACX_HIPC(hipMalloc((void **)&d_coff, sizeof(int64_t) * (n + 1)));
+        ACX_HIPC(hipMalloc((void **)&d_bnd, sizeof(int64_t) * lbnd.size()));
+        ACX_HIPC(hipMalloc((void **)&d_boff, sizeof(int64_t) * (n + 1)));
+        ACX_HIPC(hipMalloc((void **)&d_woff, sizeof(int64_t) * (n + 1)));
+        ACX_HIPC(hipMalloc((void **)&d_sync, sizeof(float) * nb * 12));
+        ACX_HIPC(hipMalloc((void **)&d_pwr, sizeof(double) * nb * 12));
+        ACX_HIPC(hipMalloc((void **)&d_G, sizeof(double) * nb * 14));
+        ACX_HIPC(hipMalloc((void **)&d_lw, sizeof(double) * nwt * D));
+        ACX_HIPC(hipMalloc((void **)&d_med, sizeof(double) * n * D));
+        ACX_HIPC(hipMalloc((void **)&d_blk, sizeof(acx::FtmBlock) * blk.size()));
+        ACX_HIPC(hipMemcpyAsync(d_ch, chroma + coff[t0] * 12, sizeof(float) * rows * 12, hipMemcpyHostToDevice, c->stream));
+        ACX_HIPC(hipMemcpyAsync(d_coff, lc.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, c->stream));
+        ACX_HIPC(hipMemcpyAsync(d_bnd, lbnd.data(), sizeof(int64_t) * lbnd.size(), hipMemcpyHostToDevice, c->stream));
+        ACX_HIPC(hipMemcpyAsync(d_boff, lb.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, c->stream));
+        ACX_HIPC(hipMemcpyAsync(d_woff, lwo.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, c->stream));
+        ACX_HIPC(hipMemcpyAsync(d_blk, blk.data(), sizeof(acx::FtmBlock) * blk.size(), hipMemcpyHostToDevice, c->stream));
+        {   // (the host buffers above are pageable: the copies are staged before the calls return)
+            const int rcs = scan_nonfinite(c, who, "chroma", d_ch, rows * 12, 12, 0, d_coff, n, false, track_base + t0);
+            if (rcs != ACX_OK) { cleanup_all(); return rcs; }
+        }
+        hipLaunchKernelGGL(acx::ftm2d_sync_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, c->stream, d_ch, d_bnd, d_boff, n, nb, d_sync);
+        hipLaunchKernelGGL(acx::ftm2d_beat_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, d_sync, nb, p.pwr, d_tw, d_pwr, d_G);
+        hipLaunchKernelGGL(acx::ftm2d_window_kernel, dim3((unsigned)blk.size()), dim3(256), lds_bytes(nw), c->stream, d_G, d_boff, d_woff, d_blk,
+                           d_tw + 24, win, nw, p.c, d_lw);
+        int maxw = 0;
+        for (int t = 0; t < n; ++t) maxw = std::max<int>(maxw, (int)(lwo[t + 1] - lwo[t]));
+        if (maxw <= 64 * 8)
+            hipLaunchKernelGGL((acx::ftm2d_median_kernel<8>), dim3((D + 3) / 4, n), dim3(256), 0, c->stream, d_lw, d_woff, D, d_med);
+        else
+            hipLaunchKernelGGL((acx::ftm2d_median_kernel<32>), dim3((D + 3) / 4, n), dim3(256), 0, c->stream, d_lw, d_woff, D, d_med);
+        hipLaunchKernelGGL(acx::ftm2d_normalize_kernel, dim3(n), dim3(64), 0, c->stream, d_med, D, d_out + (int64_t)t0 * D);
+        ACX_HIPC(hipGetLastError());
+        if (dbg) {      // one track
+            if (dbg->synced) ACX_HIPC(hipMemcpyAsync(dbg->synced, d_sync, sizeof(float) * nb * 12, hipMemcpyDeviceToHost, c->stream));
+            if (dbg->pwr) ACX_HIPC(hipMemcpyAsync(dbg->pwr, d_pwr, sizeof(double) * nb * 12, hipMemcpyDeviceToHost, c->stream));
+            if (dbg->median) ACX_HIPC(hipMemcpyAsync(dbg->median, d_med, sizeof(double) * D, hipMemcpyDeviceToHost, c->stream));
+            if (dbg->logwin) {      // (D, nwin) on the device -> (nwin, D) like btchroma_to_fftmat(...).T
+                std::vector<double> h((size_t)nwt * D);
+                ACX_HIPC(hipMemcpyAsync(h.data(), d_lw, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
+                ACX_HIPC(hipStreamSynchronize(c->stream));
+                for (int64_t w = 0; w < nwt; ++w)
+                    for (int d = 0; d < D; ++d) dbg->logwin[w * D + d] = h[(size_t)d * nwt + w];
+            }
+        }
+        ACX_HIPC(hipStreamSynchronize(c->stream));
+        cleanup();
+        t0 = t1;
+    }
+#undef ACX_HIPC
+    cleanup_all();
+    return ACX_OK;
+}
+
+int acx_ftm2d_pool_begin(acx_ctx *c, int32_t n_tracks, const acx_ftm2d_params *params)
+{
+    if (!c) return ACX_ERR_INVALID;
+    int rc = ftm2d_check_params(c, "ftm2d_pool_begin", params);
+    if (rc != ACX_OK) return rc;
+    if (n_tracks < 1) return fail(c, ACX_ERR_INVALID, "ftm2d_pool_begin: n_tracks must be >= 1");
+    ACX_HIP(c, hipSetDevice(c->device));
+    ftm2d_free_pool(c);
+    const int D = 12 * params->win;
+    const hipError_t e = hipMalloc((void **)&c->d_ftm, sizeof(double) * (size_t)n_tracks * D);
+    if (e != hipSuccess) { c->d_ftm = nullptr; return fail(c, ACX_ERR_NOMEM, std::string("ftm2d_pool_begin: ") + hipGetErrorString(e)); }
+    c->ftm_n = n_tracks;
+    c->ftm_dim = D;
+    c->ftm_open = n_tracks;
+    c->ftm_filled.assign((size_t)n_tracks, 0);
+    c->ftm_params = *params;
+    return ACX_OK;
+}
+
+int acx_ftm2d_pool_tracks(acx_ctx *c, int32_t first_track, int32_t count, const float *chroma, const int64_t *chroma_offsets,
+                          const int64_t *onsets, const int64_t *onset_offsets)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!c->ftm_open) return fail(c, ACX_ERR_STATE, "ftm2d_pool_tracks: no pool is open (acx_ftm2d_pool_begin)");
+    if (!chroma || !chroma_offsets || !onsets || !onset_offsets || count < 1 || first_track < 0 || first_track > c->ftm_n - count)
+        return fail(c, ACX_ERR_INVALID, "ftm2d_pool_tracks: bad argument (tracks must lie in the open pool)");
+    ACX_HIP(c, hipSetDevice(c->device));
+    c->nf_zeroed = 0;
+    const int rc = ftm2d_build(c, "ftm2d_pool_tracks", chroma, chroma_offsets, onsets, onset_offsets, count, first_track, c->ftm_params,
+                               c->d_ftm + (int64_t)first_track * c->ftm_dim, nullptr);
+    if (rc != ACX_OK) return rc;
+    for (int t = 0; t < count; ++t) c->ftm_filled[(size_t)first_track + t] = 1;
+    return ACX_OK;
+}
+
+int acx_ftm2d_pool_end(acx_ctx *c)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!c->ftm_open) return fail(c, ACX_ERR_STATE, "ftm2d_pool_end: no pool is open (acx_ftm2d_pool_begin)");
+    for (int t = 0; t < c->ftm_n; ++t)
+        if (!c->ftm_filled[t]) return fail(c, ACX_ERR_STATE, "ftm2d_pool_end: track " + std::to_string(t) + " was never handed over (acx_ftm2d_pool_tracks)");
+    c->ftm_open = 0;
+    c->ftm_filled.clear();
+    return ACX_OK;
+}
+
+int acx_ftm2d_upload_shingles(acx_ctx *c, const double *shingles, int32_t n_tracks, int32_t dim)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!shingles || n_tracks < 1 || dim < 1) return fail(c, ACX_ERR_INVALID, "ftm2d_upload_shingles: bad argument");
+    ACX_HIP(c, hipSetDevice(c->device));
+    ftm2d_free_pool(c);
+    const size_t n = (size_t)n_tracks * dim;
+    const hipError_t e = hipMalloc((void **)&c->d_ftm, sizeof(double) * n);
+    if (e != hipSuccess) { c->d_ftm = nullptr; return fail(c, ACX_ERR_NOMEM, std::string("ftm2d_upload_shingles: ") + hipGetErrorString(e)); }
+    ACX_HIP(c, hipMemcpy(c->d_ftm, shingles, sizeof(double) * n, hipMemcpyHostToDevice));
+    c->ftm_n = n_tracks;
+    c->ftm_dim = dim;
+    return ACX_OK;
+}
+
+int acx_ftm2d_download_shingles(acx_ctx *c, double *shingles, int64_t capacity)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!c->d_ftm || c->ftm_open) return fail(c, ACX_ERR_STATE, "ftm2d_download_shingles: no shingle pool (acx_ftm2d_pool_* or acx_ftm2d_upload_shingles)");
+    const int64_t need = (int64_t)c->ftm_n * c->ftm_dim;
+    if (!shingles || capacity < need) return fail(c, ACX_ERR_INVALID, "ftm2d_download_shingles: buffer too small");
+    ACX_HIP(c, hipSetDevice(c->device));
+    ACX_HIP(c, hipMemcpy(shingles, c->d_ftm, sizeof(double) * need, hipMemcpyDeviceToHost));
+    return ACX_OK;
+}
+
+int acx_ftm2d_debug_track(acx_ctx *c, const float *chroma, int64_t n_frames, const int64_t *onsets, int64_t n_onsets,
+                          const acx_ftm2d_params *params, float *synced, double *pwr, double *logwin, double *median,
+                          double *shingle, int64_t *dims)
+{
+    if (!c) return ACX_ERR_INVALID;
+    int rc = ftm2d_check_params(c, "ftm2d_debug_track", params);
+    if (rc != ACX_OK) return rc;
+    if (!chroma || !onsets || n_frames < 0 || n_onsets < 0 || !dims) return fail(c, ACX_ERR_INVALID, "ftm2d_debug_track: bad argument");
+    const int64_t coff[2] = {0, n_frames}, ooff[2] = {0, n_onsets};
+    {   // the shape first (the same boundaries ftm2d_build computes)
+        std::vector<int64_t> b = {0, n_frames};
+        for (int64_t k = 0; k < n_onsets; ++k) b.push_back(std::min(std::max<int64_t>(onsets[k], 0), n_frames));
+        std::sort(b.begin(), b.end());
+        b.erase(std::unique(b.begin(), b.end()), b.end());
+        const int64_t nb = (int64_t)b.size() - 1;
+        dims[0] = nb;
+        dims[1] = std::max<int64_t>(0, nb - params->win + 1);
+        dims[2] = 12 * (int64_t)params->win;
+    }
+    if (!synced && !pwr && !logwin && !median && !shingle) return ACX_OK;
+    ACX_HIP(c, hipSetDevice(c->device));
+    c->nf_zeroed = 0;
+    double *d_s = nullptr;
+    ACX_HIP(c, hipMalloc((void **)&d_s, sizeof(double) * 12 * params->win));
+    FtmDebug dbg{synced, pwr, logwin, median};
+    rc = ftm2d_build(c, "ftm2d_debug_track", chroma, coff, onsets, ooff, 1, 0, *params, d_s, &dbg);
+    if (rc == ACX_OK && shingle) {
+        const hipError_t e = hipMemcpy(shingle, d_s, sizeof(double) * 12 * params->win, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(c, ACX_ERR_HIP, std::string("ftm2d_debug_track: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(d_s);
+    return rc;
+}
+
+int acx_ftm2d_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, float *out)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (K < 0 || (K > 0 && (!pairs || !out))) return fail(c, ACX_ERR_INVALID, "ftm2d_pairs: bad argument");
+    if (!c->d_ftm || c->ftm_open) return fail(c, ACX_ERR_STATE, "ftm2d_pairs: no shingle pool (acx_ftm2d_pool_* or acx_ftm2d_upload_shingles)");
+    for (int64_t k = 0; k < K; ++k)     // the whole list before the first launch
+        if (pairs[2 * k] < 0 || pairs[2 * k + 1] < 0 || pairs[2 * k] >= c->ftm_n || pairs[2 * k + 1] >= c->ftm_n)
+            return fail(c, ACX_ERR_INVALID, "ftm2d_pairs: track index out of range in pair " + std::to_string(k));
+    if (K == 0) return ACX_OK;
+    ACX_HIP(c, hipSetDevice(c->device));
+    const int64_t CH = (int64_t)1 << 22;
+    int rc;
+    if ((rc = ensure(c, c->d_pairs, c->pairs_cap, (size_t)2 * std::min(K, CH))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_out, c->out_cap, (size_t)std::min(K, CH))) != ACX_OK) return rc;
+    for (int64_t k0 = 0; k0 < K; k0 += CH) {
+        const int64_t n = std::min(CH, K - k0);
+        ACX_HIP(c, hipMemcpyAsync(c->d_pairs, pairs + 2 * k0, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(acx::ftm2d_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_ftm, c->ftm_dim,
+                           c->d_pairs, n, c->d_out);
+        ACX_HIP(c, hipGetLastError());
+        ACX_HIP(c, hipMemcpyAsync(out + k0, c->d_out, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return ACX_OK;
+}
+
 // Device state of one similarity-network-fusion run: P matrices (two generations), the kNN kernels,
 // two N x N work buffers.
 struct SnfRun {
@@ -2703,6 +3010,10 @@ static int pool_lengths(acx_ctx *c, int algo, std::vector<int64_t> &len)
     case ACX_ALGO_EARLYFUSION:
         if (!c->d_ef[0] || c->ef_open) return fail(c, ACX_ERR_STATE, "grid: block-feature pool not uploaded (acx_ef_upload_pool)");
         off = &c->h_efoff; n = c->ef_ntracks; break;
+    case ACX_ALGO_FTM2D:       // one shingle per track: every pair costs the same
+        if (!c->d_ftm || c->ftm_open) return fail(c, ACX_ERR_STATE, "grid: FTM2D shingle pool not uploaded (acx_ftm2d_pool_* / acx_ftm2d_upload_shingles)");
+        len.assign((size_t)c->ftm_n, 1);
+        return ACX_OK;
     default: return fail(c, ACX_ERR_INVALID, "grid: unknown algorithm");
     }
     len.resize(n);
@@ -2830,11 +3141,37 @@ static int run_simple_tiles(acx_ctx *c, const std::vector<acx_grid_tile> &mine, 
     return ACX_OK;
 }
 
+// FTM2D over a slice of tiles: every tile cut into 64 x 64 blocks of pairs (the lower blocks of a symmetric diagonal tile
+// hold no pair and are left out), one workgroup per block, scores straight into d_scores.  No pair list anywhere.
+static int run_ftm2d_tiles(acx_ctx *c, const std::vector<acx_grid_tile> &mine, int symmetric, float *d_scores)
+{
+    std::vector<acx::FtmTileItem> items;
+    for (const acx_grid_tile &t : mine)
+        for (int r0 = 0; r0 < t.rows; r0 += acx::FTM_TM)
+            for (int c0 = 0; c0 < t.cols; c0 += acx::FTM_TM) {
+                if (t.diagonal && symmetric && r0 > c0) continue;
+                items.push_back(acx::FtmTileItem{t.row0, t.col0, t.rows, t.cols, r0, c0, t.diagonal, 0, t.offset});
+            }
+    if (items.empty()) return ACX_OK;
+    const size_t tbytes = sizeof(acx::FtmTileItem) * items.size();
+    if (tbytes > c->tiles_cap) {
+        if (c->d_tiles) ACX_HIP(c, hipFree(c->d_tiles));
+        c->d_tiles = nullptr; c->tiles_cap = 0;
+        ACX_HIP(c, hipMalloc(&c->d_tiles, tbytes));
+        c->tiles_cap = tbytes;
+    }
+    ACX_HIP(c, hipMemcpyAsync(c->d_tiles, items.data(), tbytes, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(acx::ftm2d_tile_kernel, dim3((unsigned)items.size()), dim3(256), 0, c->stream, c->d_ftm, c->ftm_dim,
+                       static_cast<const acx::FtmTileItem *>(c->d_tiles), symmetric, d_scores);
+    ACX_HIP(c, hipGetLastError());
+    return ACX_OK;
+}
+
 int acx_grid_run(acx_ctx *c, const acx_grid_spec *spec, const void *params, int32_t rank, int64_t first, int64_t count,
                  float *d_scores)
 {
     if (!c) return ACX_ERR_INVALID;
-    if (!acx::grid_spec_ok(spec) || !params || !d_scores || rank < 0 || rank >= spec->world || first < 0)
+    if (!acx::grid_spec_ok(spec) || (!params && spec->algo != ACX_ALGO_FTM2D) || !d_scores || rank < 0 || rank >= spec->world || first < 0)
         return fail(c, ACX_ERR_INVALID, "grid_run: bad argument");
     std::vector<int64_t> len;
     int rc = pool_lengths(c, spec->algo, len);
@@ -2847,6 +3184,12 @@ int acx_grid_run(acx_ctx *c, const acx_grid_spec *spec, const void *params, int3
         const int64_t lo = mine.front().offset;
         const int64_t hi = mine.back().offset + (int64_t)mine.back().rows * mine.back().cols * w;
         ACX_HIP(c, hipMemsetAsync(d_scores + lo, 0, sizeof(float) * (size_t)(hi - lo), c->stream));
+    }
+    if (spec->algo == ACX_ALGO_FTM2D) {
+        rc = run_ftm2d_tiles(c, mine, spec->symmetric, d_scores);
+        if (rc != ACX_OK) return rc;
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        return ACX_OK;
     }
     if (spec->algo == ACX_ALGO_SIMPLE) {
         if (!c->d_frames64) return fail(c, ACX_ERR_STATE, "grid_run: f64 feature pool not uploaded (acx_upload_pool_f64)");
@@ -2902,7 +3245,8 @@ int acx_grid_scatter(const int64_t *lengths, int32_t n_tracks, const acx_grid_sp
 int acx_pair_grid(acx_ctx *c, const acx_grid_spec *spec, const void *params, float *const *D, int64_t ld, int32_t mirror)
 {
     if (!c) return ACX_ERR_INVALID;
-    if (!acx::grid_spec_ok(spec) || spec->world != 1 || !params || !D) return fail(c, ACX_ERR_INVALID, "pair_grid: bad argument (world must be 1)");
+    if (!acx::grid_spec_ok(spec) || spec->world != 1 || (!params && spec->algo != ACX_ALGO_FTM2D) || !D)
+        return fail(c, ACX_ERR_INVALID, "pair_grid: bad argument (world must be 1)");
     for (int e = 0; e < acx::grid_planes(spec->algo); ++e) if (!D[e]) return fail(c, ACX_ERR_INVALID, "pair_grid: null plane");
     std::vector<int64_t> len;
     int rc = pool_lengths(c, spec->algo, len);
@@ -3137,7 +3481,7 @@ int acx_pair_grid_ranks(acx_ctx *c, const acx_grid_spec *spec_in, const void *pa
     // scatters nothing.
     if (!c) return ACX_ERR_INVALID;
     if (!c->comm) return fail(c, ACX_ERR_STATE, "pair_grid_ranks: no communicator (acx_comm_init)");
-    if (!spec_in || !params) return fail(c, ACX_ERR_INVALID, "pair_grid_ranks: bad argument");
+    if (!spec_in || (!params && spec_in->algo != ACX_ALGO_FTM2D)) return fail(c, ACX_ERR_INVALID, "pair_grid_ranks: bad argument");
     acx_grid_spec spec = *spec_in;
     spec.world = c->comm_world;
     if (!acx::grid_spec_ok(&spec)) return fail(c, ACX_ERR_INVALID, "pair_grid_ranks: bad grid spec");

@@ -20,6 +20,7 @@ inline int grid_planes(int algo)
     case ACX_ALGO_CHENFUSION: return 2;
     case ACX_ALGO_SIMPLE: return 1;
     case ACX_ALGO_EARLYFUSION: return 4;
+    case ACX_ALGO_FTM2D: return 1;
     default: return 0;
     }
 }

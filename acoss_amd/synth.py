@@ -154,3 +154,37 @@ def earlyfusion_cover_set(n_works=30, versions=5, seed=4321, nb_range=(60, 100),
                                chroma_med=np.median(ch.reshape(-1, 12), axis=0)))
             labels.append("w%d" % w)
     return tracks, labels
+
+
+def ftm2d_cover_set(n_works=8, versions=3, seed=4321, nbeats_range=(110, 170), frames_per_beat=(6, 14), intro=(0, 120),
+                    noise=0.15, clique_sizes=None):
+    """Raw features for FTM2D (ftm2d.py:53-57): per track a chroma (T, 12) f32 and its beat onsets (frame indices).
+    A work is a beat-level chord sequence (segments of 2-8 beats of one triad); a version transposes it (circular
+    shift of the bins), re-times it at the beat level (factor U[0.85, 1.2], nearest beat), gives every beat its own
+    length in frames, puts a noise intro of its own length in front (the first onset is not frame 0) and adds fresh
+    noise to every frame.  Returns (tracks, labels): tracks = [{"chroma", "onsets"}]."""
+    rng = np.random.default_rng(seed)
+    tri = _triads()
+    if clique_sizes is None:
+        clique_sizes = [versions] * n_works
+    tracks, labels = [], []
+    for w, nv in enumerate(clique_sizes):
+        nb = int(rng.integers(nbeats_range[0], nbeats_range[1] + 1))
+        seq = []
+        c = int(rng.integers(0, 24))
+        while len(seq) < nb:
+            seq += [c] * int(rng.integers(2, 9))
+            c = (c + int(rng.choice([-5, -2, 2, 5, 7, 1]))) % 24
+        base = tri[np.array(seq[:nb])]
+        for _ in range(nv):
+            nbv = max(2, int(round(nb * float(rng.uniform(0.85, 1.2)))))
+            beats = base[np.clip(np.round(np.linspace(0, nb - 1, nbv)).astype(int), 0, nb - 1)]
+            lens = rng.integers(frames_per_beat[0], frames_per_beat[1] + 1, nbv)
+            n_intro = int(rng.integers(intro[0], intro[1] + 1))
+            x = np.concatenate([rng.random((n_intro, NBINS)) * 0.3, np.repeat(beats, lens, axis=0)])
+            x = np.roll(x, int(rng.integers(0, 12)), axis=1) + noise * rng.random((len(x), NBINS))
+            onsets = n_intro + np.concatenate([[0], np.cumsum(lens)[:-1]])
+            tracks.append(dict(chroma=_frame_max_normalise(x), onsets=onsets.astype(np.int64)))
+            labels.append("w%d" % w)
+    return tracks, labels
+

@@ -389,6 +389,69 @@ int acx_csm_binary_sw(acx_ctx *ctx, const float *D, int32_t M, int32_t N, double
  * (the reference raises IOError). */
 int acx_sw_binary(acx_ctx *ctx, const uint8_t *B, int32_t M, int32_t N, float *score);
 
+/* ---- FTM2D (2D Fourier transform magnitudes, Bertin-Mahieux & Ellis) ------ */
+
+/* Constructor arguments of FTM2D (ftm2d.py:23): defaults PWR 1.96, WIN 75, C 5. */
+typedef struct {
+    double pwr;         /* chrompwr exponent (ftm2d.py:58)                                        */
+    double c;           /* log(C x + 1) compression of every window (:61)                         */
+    int32_t win;        /* beats per window (:60); 1..256 on the device                           */
+    int32_t reserved;   /* 0                                                                      */
+} acx_ftm2d_params;
+
+void acx_ftm2d_default_params(acx_ftm2d_params *p);
+
+/*
+ * The shingle pool of a collection -- FTM2D.load_features(i) for every track (ftm2d.py:38-64) -- built on the device
+ * from raw features streamed in batches of whole tracks, so that the host never holds the collection's chroma at once
+ * (the reference keeps only the shingles, self.shingles, :29):
+ *   acx_ftm2d_pool_begin   allocates an (n_tracks, 12 WIN) f64 pool for `params` (copied)
+ *   acx_ftm2d_pool_tracks  tracks [first_track, first_track + count): chroma (sum T_i, 12) f32 as loaded
+ *                          (feats[chroma_type]), track i at rows chroma_offsets[i] .. chroma_offsets[i + 1]; beat onsets
+ *                          (frame indices, feats['madmom_features']['onsets'], :55) at onset_offsets[i] .. [i + 1] --
+ *                          the packed layout of acx_ef_upload_raw_pool, offsets (count + 1) index into the arrays given.
+ *                          Per track: librosa.util.sync(X.T, onsets, aggregate=np.median) (onsets clipped to [0, T],
+ *                          0 and T added, np.unique; f32 median per bin and segment, bit-identical to np.median),
+ *                          chrompwr, |fft2| of every WIN-beat window in fftshift order as WIN-point DFTs of the 7
+ *                          chroma-DFT rows (rows 7..11 by conjugate symmetry), window L2 norm, log(C x + 1), exact f64
+ *                          median over the windows, final L2 norm -- f64 from the synced f32 values.  The WHOLE batch is
+ *                          checked first: a negative onset or fewer than WIN beats fails with ACX_ERR_INVALID naming the
+ *                          first such track and nothing is launched (the reference raises / returns None there, :60,
+ *                          :130); NaN / Inf chroma follows the context's non-finite policy.  The window matrices run in
+ *                          sub-batches under acx_set_scratch_limit.  Slices may come in any order and again (last wins)
+ *   acx_ftm2d_pool_end     checks that every track was handed over (else ACX_ERR_STATE naming the first missing one;
+ *                          the pool stays open); the pool is usable from here on
+ * A track whose shingle median is all zero (silent chroma) gets NaN, as in the reference (:63).
+ */
+int acx_ftm2d_pool_begin(acx_ctx *ctx, int32_t n_tracks, const acx_ftm2d_params *params);
+int acx_ftm2d_pool_tracks(acx_ctx *ctx, int32_t first_track, int32_t count, const float *chroma, const int64_t *chroma_offsets,
+                          const int64_t *onsets, const int64_t *onset_offsets);
+int acx_ftm2d_pool_end(acx_ctx *ctx);
+
+/* Ready shingles instead (synthetic benchmarks, FTM2D.set_features): (n_tracks, dim) f64 row-major, any dim >= 1.
+ * Replaces the pool. */
+int acx_ftm2d_upload_shingles(acx_ctx *ctx, const double *shingles, int32_t n_tracks, int32_t dim);
+/* Copy the shingle pool back: `shingles` has room for `capacity` doubles (n_tracks x dim needed). */
+int acx_ftm2d_download_shingles(acx_ctx *ctx, double *shingles, int64_t capacity);
+
+/*
+ * One track through the same kernels with every intermediate (tests; the pool is not touched).  dims[3] =
+ * {nbeats, nwin = nbeats - WIN + 1, D = 12 WIN} is always written, so a call with every output NULL asks for the
+ * shape.  Outputs (any may be NULL): synced (nbeats, 12) f32 -- the beat-synchronous chroma, TIME-major (hpcp.T of
+ * ftm2d.py:56); pwr (nbeats, 12) f64 -- chrompwr (:58), time-major; logwin (nwin, D) f64 -- log(C |fft2| / norm + 1)
+ * of every window (:60-61); median (D) f64 -- before the final norm (:62); shingle (D) f64 (:63).
+ */
+int acx_ftm2d_debug_track(acx_ctx *ctx, const float *chroma, int64_t n_frames, const int64_t *onsets, int64_t n_onsets,
+                          const acx_ftm2d_params *params, float *synced, double *pwr, double *logwin, double *median,
+                          double *shingle, int64_t *dims);
+
+/*
+ * out[k] = exp(-sum((s_i - s_j)^2)) for pair (i, j) = (pairs[2k], pairs[2k+1]) -- the value FTM2D.similarity() stores
+ * into the float32 Ds['main'][i, j] (ftm2d.py:85-97): the sum in f64 over the dimensions in order (difference form,
+ * no cancellation), exp in f64, rounded to f32.  i == j gives 1.  The whole list is checked before the first launch.
+ */
+int acx_ftm2d_pairs(acx_ctx *ctx, const int32_t *pairs, int64_t K, float *out);
+
 /* ---- late fusion (N x N post-step) ---------------------------------------- */
 
 /*
@@ -430,10 +493,10 @@ int acx_snf_fuse_dists(acx_ctx *ctx, const double *const *Ds, int32_t m, int32_t
  * buffer (block after block in deal order; a block is rows x cols x planes floats, planes
  * fastest); the only exchange of the whole path is one all-gather of those buffers.
  */
-enum { ACX_ALGO_SERRA09 = 0, ACX_ALGO_CHENFUSION = 1, ACX_ALGO_SIMPLE = 2, ACX_ALGO_EARLYFUSION = 3 };
+enum { ACX_ALGO_SERRA09 = 0, ACX_ALGO_CHENFUSION = 1, ACX_ALGO_SIMPLE = 2, ACX_ALGO_EARLYFUSION = 3, ACX_ALGO_FTM2D = 4 };
 
 typedef struct {
-    int32_t algo;       /* ACX_ALGO_*: 1 / 2 (qmax, dmax) / 1 / 4 (mfccs, ssms, chromas, early) score planes */
+    int32_t algo;       /* ACX_ALGO_*: 1 / 2 (qmax, dmax) / 1 / 4 (mfccs, ssms, chromas, early) / 1 score planes */
     int32_t symmetric;  /* 1: unordered pairs i < j   0: ordered pairs i != j (all_pairwise's `symmetric`) */
     int32_t tile;       /* tracks per block edge; 0: 128, halved while a rank would get fewer than 32 blocks */
     int32_t world;      /* number of ranks */
@@ -463,7 +526,8 @@ int acx_grid_plan(const int64_t *lengths, int32_t n_tracks, const acx_grid_spec 
                   int64_t capacity, int64_t *n_tiles, int64_t *floats_per_rank, double *cost_per_rank);
 
 /* Track lengths the grid of `algo` is planned on: pooled frames (Serra09 / ChenFusion: the f32
- * pool; SiMPle: the f64 pool) or blocks (EarlyFusion).  lengths: room for `capacity` entries. */
+ * pool; SiMPle: the f64 pool), blocks (EarlyFusion) or 1 for every track (FTM2D: all pairs cost the
+ * same).  lengths: room for `capacity` entries. */
 int acx_pool_lengths(acx_ctx *ctx, int32_t algo, int64_t *lengths, int32_t capacity, int32_t *n_tracks);
 
 /*
@@ -471,7 +535,9 @@ int acx_pool_lengths(acx_ctx *ctx, int32_t algo, int64_t *lengths, int32_t capac
  * d_scores, a DEVICE buffer of floats_per_rank[rank] floats owned by the caller (e.g. the
  * storage of a torch tensor that is handed to the all-gather next).  The slice's part of the
  * buffer is zeroed first.  params: acx_serra09_params (Serra09, ChenFusion), acx_simple_params,
- * acx_ef_params.  Replaces the similarity(idxs) fan-out of algorithm_template.py:172-187.
+ * acx_ef_params; FTM2D takes none (NULL; the scores are those of acx_ftm2d_pairs, bit for bit, from a tile
+ * kernel that stages both sides' shingles in LDS).  Replaces the similarity(idxs) fan-out of
+ * algorithm_template.py:172-187.
  */
 int acx_grid_run(acx_ctx *ctx, const acx_grid_spec *spec, const void *params, int32_t rank, int64_t first,
                  int64_t count, float *d_scores);
