@@ -35,6 +35,7 @@ EXPORTS = [
     "acx_device_info", "acx_ef_debug_pairs",
     "acx_ftm2d_default_params", "acx_ftm2d_pool_begin", "acx_ftm2d_pool_tracks", "acx_ftm2d_pool_end",
     "acx_ftm2d_upload_shingles", "acx_ftm2d_download_shingles", "acx_ftm2d_debug_track", "acx_ftm2d_pairs",
+    "acx_rank_columns", "acx_topk_rows",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -248,6 +249,9 @@ def load():
     L.acx_ftm2d_download_shingles.argtypes = [vp, dp, ctypes.c_int64]
     L.acx_ftm2d_debug_track.argtypes = [vp, fp, ctypes.c_int64, lp, ctypes.c_int64, fpp, fp, dp, dp, dp, dp, lp]
     L.acx_ftm2d_pairs.argtypes = [vp, ip, ctypes.c_int64, fp]
+    L.acx_rank_columns.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ip, ip, lp, ip, ip,
+                                   ctypes.POINTER(ctypes.c_uint8)]
+    L.acx_topk_rows.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ip, ip, ctypes.c_int32, ip, fp]
     _check_hip_version(L)
     _lib = L
     return L
@@ -275,6 +279,31 @@ def _lptr(a):
 
 def _dptr(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+def _iptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
+def _row_slabs(D, rows, slab_bytes):
+    """The score rows `rows` of the 2-D array `D` as float32 slabs for acx_rank_columns / acx_topk_rows: yields
+    (first, count, slab, ld) where `slab` holds rows[first : first + count] in order, one per ld floats.  float32 rows
+    that lie unit-stride in memory and are asked for as one ascending run are handed over as they are (no copy, a memmap
+    included); anything else -- float64, a strided view, scattered rows -- is converted `slab_bytes` at a time, never as a
+    whole second matrix."""
+    n = D.shape[1]
+    R = len(rows)
+    if R == 0:
+        return
+    direct = (isinstance(D, np.ndarray) and D.dtype == np.float32 and (n == 1 or D.strides[1] == 4) and D.strides[0] % 4 == 0
+              and D.strides[0] >= 4 * n and (R == 1 or bool(np.all(np.diff(rows) == 1))))
+    if direct:
+        yield 0, R, D[int(rows[0]):int(rows[0]) + R], D.strides[0] // 4
+        return
+    step = max(1, int(slab_bytes) // (4 * n))
+    for a in range(0, R, step):
+        b = min(R, a + step)
+        yield a, b - a, np.ascontiguousarray(D[rows[a:b]], dtype=np.float32), n
 
 
 def _params_ptr(params):
@@ -863,6 +892,60 @@ class Context(object):
                                                   _fptr(out["synced"]), _dptr(out["pwr"]), _dptr(out["logwin"]),
                                                   _dptr(out["median"]), _dptr(out["shingle"]), _lptr(dims)))
         return out
+
+    # ------------------------------------------------------------------ ranking of finished score rows
+    RANK_SLAB_BYTES = 64 << 20      # rows converted per call when the matrix cannot be handed over as it is
+
+    def _rank_args(self, who, D, rows, posn):
+        if not hasattr(D, "shape") or len(D.shape) != 2:
+            raise ValueError("%s: scores must be a 2-D array (tracks x columns)" % who)
+        n = int(D.shape[1])
+        rows = np.arange(D.shape[0], dtype=np.int32) if rows is None else np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        if len(rows) and (rows.min() < 0 or rows.max() >= D.shape[0]):
+            raise ValueError("%s: rows must be row indices of the score matrix" % who)
+        if posn is not None:
+            posn = np.ascontiguousarray(posn, dtype=np.int32).reshape(-1)
+            if len(posn) != n:
+                raise ValueError("%s: posn must have one entry per column (%d), got %d" % (who, n, len(posn)))
+        return n, rows, posn
+
+    def rank_columns(self, D, rows, moff, mates, posn=None):
+        """acx_rank_columns: the 1-based positions of listed columns in the stable descending order of score rows.
+        D: (N, n) scores, row t = the scores of track t (its own cell D[t, t] takes no part); rows: the tracks to rank
+        (None: all); mates[moff[i] : moff[i + 1]]: the listed columns of rows[i]; posn: (n,) tie ranks or None (the
+        column index).  Returns (pos (moff[-1],) int32, flag (len(rows),) uint8): a row with NaN / -inf outside its own
+        cell has flag 1 and positions -1."""
+        n, rows, posn = self._rank_args("rank_columns", D, rows, posn)
+        moff = np.ascontiguousarray(moff, dtype=np.int64).reshape(-1)
+        mates = np.ascontiguousarray(mates, dtype=np.int32).reshape(-1)
+        if len(moff) != len(rows) + 1 or moff[0] != 0 or (len(moff) > 1 and np.any(np.diff(moff) < 0)) or moff[-1] != len(mates):
+            raise ValueError("rank_columns: moff must hold len(rows) + 1 non-decreasing offsets from 0 to len(mates)")
+        pos = np.full(len(mates), -1, np.int32)
+        flag = np.zeros(len(rows), np.uint8)
+        for a, cnt, slab, ld in _row_slabs(D, rows, self.RANK_SLAB_BYTES):
+            mo = np.ascontiguousarray(moff[a:a + cnt + 1] - moff[a])
+            m0, m1 = int(moff[a]), int(moff[a + cnt])
+            # (views of pos / flag: the library writes this slab's results in place)
+            self._check(self._L.acx_rank_columns(self._h, ctypes.c_void_p(slab.ctypes.data), int(ld), n, int(cnt),
+                                                 _iptr(rows[a:a + cnt]), None if posn is None else _iptr(posn), _lptr(mo),
+                                                 _iptr(mates[m0:m1]) if m1 > m0 else None, _iptr(pos[m0:m1]) if m1 > m0 else None,
+                                                 flag[a:a + cnt].ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        return pos, flag
+
+    def topk_rows(self, D, k, rows=None, posn=None):
+        """acx_topk_rows: (idx (R, k) int32, score (R, k) float32), the k best other columns of every row of `rows`
+        (None: all) in stable descending order -- np.argsort(-row, kind="stable") with the own cell removed, NaN last.
+        Fewer than k other columns: the tail is index -1, score NaN."""
+        n, rows, posn = self._rank_args("topk_rows", D, rows, posn)
+        k = int(k)
+        idx = np.full((len(rows), max(k, 0)), -1, np.int32)
+        score = np.full((len(rows), max(k, 0)), np.nan, np.float32)
+        if len(rows) == 0:      # nothing to stage: the library still judges the arguments
+            self._check(self._L.acx_topk_rows(self._h, None, max(n, 1), n, 0, None, None if posn is None else _iptr(posn), k, None, None))
+        for a, cnt, slab, ld in _row_slabs(D, rows, self.RANK_SLAB_BYTES):
+            self._check(self._L.acx_topk_rows(self._h, ctypes.c_void_p(slab.ctypes.data), int(ld), n, int(cnt), _iptr(rows[a:a + cnt]),
+                                              None if posn is None else _iptr(posn), k, _iptr(idx[a:a + cnt]), _fptr(score[a:a + cnt])))
+        return idx, score
 
     def profile_enable(self, on=True):
         self._check(self._L.acx_profile_enable(self._h, int(bool(on))))

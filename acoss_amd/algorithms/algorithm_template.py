@@ -50,6 +50,10 @@ class CoverAlgorithm(object):
     # override this with 1 (whole list per call).
     n_chunks = 45
 
+    # where getEvalStatistics ranks the score rows: "host" (numpy, eval_statistics) or "device" (libacx's ranking kernels,
+    # eval_statistics_device: the same statistics from integer positions counted on the GPU)
+    eval_engine = "host"
+
     def __init__(self, dataset_csv, name="Serra09", datapath="features_benchmark", shortname="full",
                  cachedir="cache", similarity_types=["main"]):
         self.name = name
@@ -279,18 +283,47 @@ class CoverAlgorithm(object):
                 print("Could not clean-up automatically.")
 
     # ------------------------------------------------------------------ evaluation
-    def getEvalStatistics(self, similarity_type, topsidx=[1, 10, 100, 1000]):
+    def _rank_context(self):
+        """The libacx context that ranks finished score rows (getEvalStatistics(engine="device"), top_matches): the
+        object's own if it has one already, else one created here on the object's device -- never through _grid():
+        ranking a matrix must not trigger a pool upload, and user subclasses without any device code rank too.
+        No GPU: _lib.Context raises AcxError; there is no host fallback."""
+        ctx = getattr(self, "_ctx", None)
+        if isinstance(ctx, _lib.Context) and getattr(ctx, "_h", None):
+            return ctx
+        if getattr(self, "_rank_ctx", None) is None or not self._rank_ctx._h:
+            dev = getattr(self, "_device", None)
+            if dev is None:
+                dev = getattr(self, "device", None)
+            self._rank_ctx = _lib.Context(int(os.environ.get("LOCAL_RANK", "0")) if dev is None else int(dev))
+        return self._rank_ctx
+
+    def top_matches(self, similarity_type, k=10, rows=None):
+        """The k best other tracks of every track (or of `rows`) by Ds[similarity_type], best first, ties in index order:
+        (idx (R, k) int32, score (R, k) float32) = np.argsort(-row, kind="stable")[:k] with the track itself removed,
+        computed on the device (acx_topk_rows).  Fewer than k other tracks: the tail is index -1, score NaN."""
+        return self._rank_context().topk_rows(self.Ds[similarity_type], k, rows=rows)
+
+    def getEvalStatistics(self, similarity_type, topsidx=[1, 10, 100, 1000], engine=None):
         """MR, MRR, MDR, MAP and Top-k of one similarity matrix; appends a row to
         results_<shortname>_<name>.csv.  Same definitions as the reference (:205-290),
         including MRR's division by ALL N songs and the %.3g CSV format.
+        engine: "host" (numpy), "device" (the rows are ranked by libacx on the GPU, eval_statistics_device; no GPU raises
+        AcxError) or None = the class attribute `eval_engine` ("host").
         Under torch.distributed this is a COLLECTIVE: rank 0 (the owner of the matrices) evaluates and
         writes the CSV, the tuple is broadcast and returned on every rank -- so every rank must call it
         (`if rank == 0: algo.getEvalStatistics(...)` would leave rank 0 waiting in the broadcast)."""
         rank, ws = _dist.world()
+        engine = self.eval_engine if engine is None else engine
+        if engine not in ("host", "device"):
+            raise ValueError("getEvalStatistics: engine must be 'host' or 'device', got %r" % (engine,))
 
         def evaluate():
+            cliques = [sorted(self.cliques[s]) for s in self.cliques]
+            if engine == "device":
+                return eval_statistics_device(self.Ds[similarity_type], cliques, topsidx, ctx=self._rank_context())
             D = np.array(self.Ds[similarity_type], dtype=np.float32)
-            return eval_statistics(D, [sorted(self.cliques[s]) for s in self.cliques], topsidx)
+            return eval_statistics(D, cliques, topsidx)
         MR, MRR, MDR, MAP, tops = _dist.on_root(evaluate)
         if rank != 0:
             return MR, MRR, MDR, MAP, tops
@@ -314,6 +347,167 @@ class CoverAlgorithm(object):
         return MR, MRR, MDR, MAP, tops
 
 
+def _clique_order(cliques):
+    """Cliques largest first (stable): (Ks sorted, idx = the tracks in that clique-contiguous order)."""
+    Ks = np.array([len(c) for c in cliques])
+    order = np.argsort(-Ks, kind="stable")
+    Ks = Ks[order]
+    cl = [list(cliques[i]) for i in order]
+    idx = np.array([t for c in cl for t in c], dtype=np.int64)
+    return Ks, idx
+
+
+def _finish_counted(pos, Kb):
+    """The tail of the counting branch for one block of rows: `pos` (rows, kmax) f64 holds the 1-based positions of every
+    row's clique mates in any column order, +inf where there is none; Kb the rows' clique sizes.  Returns (rank of the
+    first mate, average precision) per row.  Sorts `pos` in place."""
+    kmax = pos.shape[1]
+    pos.sort(axis=1)                                     # ascending; missing mates (+inf) last
+    nm = (Kb - 1)[:, None]
+    t = np.arange(1, kmax + 1, dtype=np.float64)[None, :]
+    contrib = np.where(t <= nm, t / pos, 0.0)
+    return pos[:, 0], contrib.sum(axis=1) / (Kb - 1)
+
+
+def _rank_sorted(Db, row_start, row_K):
+    """The sorting branch for one block of rows of the clique-ordered matrix (own cells -inf): (rank of the first mate,
+    average precision) per row from a stable argsort; row_start / row_K: first column and size of every row's clique."""
+    nb = Db.shape[0]
+    srt = np.argsort(-Db, axis=1, kind="stable")
+    member = (srt >= row_start[:, None]) & (srt < (row_start + row_K)[:, None])
+    rr, kk = np.nonzero(member)              # row-major: per row, ascending rank position
+    # the last member of every row is the song itself (-inf sorts last): drop it
+    first = np.concatenate([[0], np.cumsum(row_K)])[:-1]
+    last = first + row_K - 1
+    keep = np.ones(len(rr), dtype=bool)
+    keep[last] = False
+    pos = (kk + 1)[keep].astype(np.float64)
+    rows = rr[keep]
+    within = np.arange(len(rr)) - np.repeat(first, row_K)
+    num = (within + 1)[keep].astype(np.float64)
+    ranks = pos[np.searchsorted(rows, np.arange(nb))]
+    sums = np.bincount(rows, weights=num / pos, minlength=nb)
+    return ranks, sums / (row_K - 1)
+
+
+def _finish_statistics(ranks, allmap, N, n_eval, topsidx):
+    """MR, MRR, MDR, MAP, Top-k from the per-row ranks / average precisions (NaN for rows that are not evaluated)."""
+    if n_eval == 0:
+        warnings.warn("no clique with at least two songs")
+    MAP = float(np.nanmean(allmap)) if n_eval else float("nan")
+    ranks = ranks[~np.isnan(ranks)]
+    MR = float(np.mean(ranks)) if len(ranks) else float("nan")
+    MRR = float(1.0 / N * np.sum(1.0 / ranks))
+    MDR = float(np.median(ranks)) if len(ranks) else float("nan")
+    tops = np.array([np.sum(ranks <= t) for t in topsidx], dtype=np.float64)
+    return MR, MRR, MDR, MAP, tops
+
+
+def rank_plan(cliques, N):
+    """What eval_statistics_device asks the device for.  The cliques are laid out as eval_statistics does (largest first,
+    stable); a track's place in that layout is its tie rank.  Returns a dict:
+      idx     (N,) int64   the tracks in clique order;   Ks  clique sizes in that order;   n_eval  rows of cliques >= 2
+      posn    (N,) int32   posn[track] = its place in idx (the tie order of every row)
+      rows    (R,) int32   the tracks whose rows are ranked, ascending -- the evaluated tracks, or, when these cover at
+                           least half of the span between the first and the last of them, the WHOLE span (a float32
+                           matrix is then handed over as it lies in memory; the extra rows list no columns)
+      moff    (R + 1,) int64, mates (moff[-1],) int32   the clique mates (track indices, clique order, own track left
+                           out) of every row of `rows`
+      where   (n_eval, 2) int64   for the e-th track of idx: first entry and number of its mates in `mates`."""
+    Ks, idx = _clique_order(cliques)
+    if len(idx) != N or not np.array_equal(np.sort(idx), np.arange(N)):
+        raise ValueError("eval_statistics_device: the cliques must hold every track of the matrix exactly once")
+    n_eval = int(np.sum(Ks[Ks >= 2]))
+    posn = np.empty(N, np.int32)
+    posn[idx] = np.arange(N, dtype=np.int32)
+    starts = np.concatenate([[0], np.cumsum(Ks)])[:-1]
+    row_start = np.repeat(starts, Ks)[:n_eval]
+    row_K = np.repeat(Ks, Ks)[:n_eval]
+    ev = np.sort(idx[:n_eval])
+    if n_eval and 2 * n_eval >= int(ev[-1] - ev[0]) + 1:
+        rows = np.arange(ev[0], ev[-1] + 1, dtype=np.int32)
+    else:
+        rows = ev.astype(np.int32)
+    place = posn[rows].astype(np.int64)                     # a row's place in clique order (>= n_eval: lists nothing)
+    ev_mask = place < n_eval
+    pe = place[ev_mask]
+    K = row_K[pe] if n_eval else np.zeros(0, np.int64)
+    nmate = np.zeros(len(rows), np.int64)
+    nmate[ev_mask] = K - 1
+    moff = np.concatenate([[0], np.cumsum(nmate)]).astype(np.int64)
+    # every evaluated row's clique as places in clique order, the row's own place dropped
+    within = np.arange(int(K.sum())) - np.repeat(np.cumsum(K) - K, K)
+    members = np.repeat(row_start[pe], K) + within if n_eval else np.zeros(0, np.int64)
+    mates = idx[members[members != np.repeat(pe, K)]].astype(np.int32)
+    where = np.zeros((n_eval, 2), np.int64)
+    where[pe, 0] = moff[:-1][ev_mask]
+    where[pe, 1] = nmate[ev_mask]
+    return dict(idx=idx, Ks=Ks, n_eval=n_eval, posn=posn, rows=rows, moff=moff, mates=mates, where=where)
+
+
+def _statistics_from_positions(D, plan, pos, flag, topsidx, row_block, info=None):
+    """The statistics from the integer positions acx_rank_columns returned for `plan` (rank_plan): block by block in clique
+    order, exactly the host's counting branch with the production of `pos` replaced (same blocks, same padded width, same
+    tail: numpy's row sums group their terms by that width).  Rows the device flagged (NaN / -inf) are ranked here by
+    the sorting branch -- the reference's reading of such a row."""
+    idx, Ks, n_eval, where = plan["idx"], plan["Ks"], plan["n_eval"], plan["where"]
+    N = len(idx)
+    starts = np.concatenate([[0], np.cumsum(Ks)])[:-1]
+    row_start = np.repeat(starts, Ks)
+    row_K = np.repeat(Ks, Ks)
+    ranks = np.full(N, np.nan)
+    allmap = np.full(N, np.nan)
+    flag_of_track = np.zeros(N, bool)
+    flag_of_track[plan["rows"]] = flag.astype(bool)
+    flagged = flag_of_track[idx[:n_eval]]                   # in clique order
+    for r0 in range(0, n_eval, row_block):
+        r1 = min(n_eval, r0 + row_block)
+        Kb = row_K[r0:r1]
+        kmax = int(Kb.max())
+        P = np.full((r1 - r0, kmax), np.inf)
+        cols = np.arange(kmax - 1)[None, :]
+        have = cols < where[r0:r1, 1][:, None]
+        src = where[r0:r1, 0][:, None] + cols
+        P[:, :kmax - 1][have] = pos[src[have]]
+        P[flagged[r0:r1]] = np.inf
+        ranks[r0:r1], allmap[r0:r1] = _finish_counted(P, Kb)
+    host_rows = np.nonzero(flagged)[0]
+    for a in range(0, len(host_rows), row_block):
+        hr = host_rows[a:a + row_block]
+        Db = np.array(np.asarray(D)[idx[hr]][:, idx], dtype=np.float32)
+        Db[np.arange(len(hr)), hr] = -np.inf
+        ranks[hr], allmap[hr] = _rank_sorted(Db, row_start[hr], row_K[hr])
+    if info is not None:
+        info["device_rows"] = int(n_eval - len(host_rows))
+        info["host_rows"] = int(len(host_rows))
+    return _finish_statistics(ranks, allmap, N, n_eval, topsidx)
+
+
+def eval_statistics_device(D, cliques, topsidx=(1, 10, 100, 1000), ctx=None, info=None, row_block=1024):
+    """eval_statistics with the rows ranked on the GPU: libacx counts the 1-based positions of every evaluated track's
+    clique mates in the stable descending order of its score row (acx_rank_columns; tie order = the clique-contiguous
+    layout eval_statistics uses, own cell ignored) and the host turns those integers into MR, MRR, MDR, MAP and Top-k
+    with the code that finishes eval_statistics' counting branch -- the same numbers as
+    eval_statistics(D, cliques, topsidx, count_max_clique=<huge>), bit for bit, on finite matrices.  Rows that hold NaN
+    or -inf outside their own cell are flagged by the device and ranked here by the sorting branch.
+    D: (N, N) scores, any dtype or strides (float32 rows are passed as they lie, a memmap included; anything else is
+    converted a slab of rows at a time); ctx: a _lib.Context (None: one on device 0 for this call); info: a dict that
+    receives {"device_rows", "host_rows"}.  No GPU: AcxError -- there is no host fallback."""
+    N = int(D.shape[0])
+    if len(D.shape) != 2 or D.shape[1] != N:
+        raise ValueError("eval_statistics_device: D must be square")
+    plan = rank_plan(cliques, N)
+    own = ctx is None
+    if own:
+        ctx = _lib.Context(0)
+    try:
+        pos, flag = ctx.rank_columns(D, plan["rows"], plan["moff"], plan["mates"], posn=plan["posn"])
+    finally:
+        if own:
+            ctx.close()
+    return _statistics_from_positions(D, plan, pos, flag, topsidx, row_block, info)
+
+
 def eval_statistics(D, cliques, topsidx=(1, 10, 100, 1000), row_block=1024, count_max_clique=24):
     """Vectorised evaluation.  `cliques`: list of lists of track indices (dict insertion
     order).  Rows are reordered so that cliques are contiguous, largest first; the
@@ -323,11 +517,7 @@ def eval_statistics(D, cliques, topsidx=(1, 10, 100, 1000), row_block=1024, coun
     otherwise (and for rows that hold NaN); both give the same numbers."""
     D = np.array(D, dtype=np.float32)
     N = D.shape[0]
-    Ks = np.array([len(c) for c in cliques])
-    order = np.argsort(-Ks, kind="stable")
-    Ks = Ks[order]
-    cl = [list(cliques[i]) for i in order]
-    idx = np.array([t for c in cl for t in c], dtype=np.int64)
+    Ks, idx = _clique_order(cliques)
     D = D[idx, :][:, idx]
     np.fill_diagonal(D, -np.inf)
     starts = np.concatenate([[0], np.cumsum(Ks)])[:-1]
@@ -360,34 +550,7 @@ def eval_statistics(D, cliques, topsidx=(1, 10, 100, 1000), row_block=1024, coun
                 if np.count_nonzero(eq) > r1 - r0:               # ties beyond the cell itself: the left ones come first
                     p = p + np.count_nonzero(eq & (col[None, :] < cc[:, None]), axis=1)
                 pos[ok, m] = p[ok]
-            pos.sort(axis=1)                                     # ascending; missing mates (+inf) last
-            nm = (Kb - 1)[:, None]
-            t = np.arange(1, kmax + 1, dtype=np.float64)[None, :]
-            contrib = np.where(t <= nm, t / pos, 0.0)
-            ranks[r0:r1] = pos[:, 0]
-            allmap[r0:r1] = contrib.sum(axis=1) / (Kb - 1)
+            ranks[r0:r1], allmap[r0:r1] = _finish_counted(pos, Kb)
             continue
-        srt = np.argsort(-Db, axis=1, kind="stable")
-        member = (srt >= row_start[r0:r1, None]) & (srt < (row_start[r0:r1] + row_K[r0:r1])[:, None])
-        rr, kk = np.nonzero(member)              # row-major: per row, ascending rank position
-        # the last member of every row is the song itself (-inf sorts last): drop it
-        first = np.concatenate([[0], np.cumsum(row_K[r0:r1])])[:-1]
-        last = first + row_K[r0:r1] - 1
-        keep = np.ones(len(rr), dtype=bool)
-        keep[last] = False
-        pos = (kk + 1)[keep].astype(np.float64)
-        rows = rr[keep]
-        within = np.arange(len(rr)) - np.repeat(first, row_K[r0:r1])
-        num = (within + 1)[keep].astype(np.float64)
-        ranks[r0:r1] = pos[np.searchsorted(rows, np.arange(r1 - r0))]
-        sums = np.bincount(rows, weights=num / pos, minlength=r1 - r0)
-        allmap[r0:r1] = sums / (row_K[r0:r1] - 1)
-    if n_eval == 0:
-        warnings.warn("no clique with at least two songs")
-    MAP = float(np.nanmean(allmap)) if n_eval else float("nan")
-    ranks = ranks[~np.isnan(ranks)]
-    MR = float(np.mean(ranks)) if len(ranks) else float("nan")
-    MRR = float(1.0 / N * np.sum(1.0 / ranks))
-    MDR = float(np.median(ranks)) if len(ranks) else float("nan")
-    tops = np.array([np.sum(ranks <= t) for t in topsidx], dtype=np.float64)
-    return MR, MRR, MDR, MAP, tops
+        ranks[r0:r1], allmap[r0:r1] = _rank_sorted(Db, row_start[r0:r1], row_K[r0:r1])
+    return _finish_statistics(ranks, allmap, N, n_eval, topsidx)

@@ -28,6 +28,7 @@
 #include "ef_gemm_dma_kernels.hpp"
 #include "ef_prep_kernels.hpp"
 #include "ftm2d_kernels.hpp"
+#include "rank_kernels.hpp"
 #include "grid.hpp"
 
 using acx::PairDesc;
@@ -42,7 +43,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -121,6 +122,11 @@ struct acx_ctx {
     int32_t ftm_open = 0;                             // > 0: a pool of that many tracks is being filled (acx_ftm2d_pool_begin .. _end)
     std::vector<uint8_t> ftm_filled;                  // per track of the open pool: handed over by acx_ftm2d_pool_tracks yet?
     acx_ftm2d_params ftm_params = {0.0, 0.0, 0, 0};
+    // ranking of score rows (acx_rank_columns / acx_topk_rows): two staging slots of whole rows, pinned + device (grow-only)
+    float *rank_h[2] = {nullptr, nullptr}; size_t rank_h_cap[2] = {0, 0};
+    float *rank_d[2] = {nullptr, nullptr}; size_t rank_d_cap[2] = {0, 0};
+    hipEvent_t rank_ev[2] = {nullptr, nullptr};
+    bool rank_attr = false;
     // multi-GPU inside the library (acx_comm_*): one RCCL communicator rank per context
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -165,7 +171,8 @@ struct acx_ctx {
     KStat stats[KS_COUNT] = {{"oti_kernel", 0, 0, 0}, {"norms_kernel", 0, 0, 0}, {"band_kernel", 0, 0, 0},
                              {"csm_long_kernel", 0, 0, 0}, {"rowsel_long_kernel", 0, 0, 0}, {"qmax_bits_kernel", 0, 0, 0},
                              {"simple_kernel", 0, 0, 0}, {"ef_gemm_kernel", 0, 0, 0}, {"ef_rowstat_kernel", 0, 0, 0},
-                             {"ef_fuse_kernel", 0, 0, 0}, {"sw_kernel", 0, 0, 0}};
+                             {"ef_fuse_kernel", 0, 0, 0}, {"sw_kernel", 0, 0, 0}, {"rank_columns_kernel", 0, 0, 0},
+                             {"topk_rows_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
 };
@@ -1603,6 +1610,11 @@ void acx_destroy(acx_ctx *c)
     if (c->d_out64) (void)hipFree(c->d_out64);
     ef_free_pool(c);
     if (c->d_ftm) (void)hipFree(c->d_ftm);
+    for (int e = 0; e < 2; ++e) {
+        if (c->rank_h[e]) (void)hipHostFree(c->rank_h[e]);
+        if (c->rank_d[e]) (void)hipFree(c->rank_d[e]);
+        if (c->rank_ev[e]) (void)hipEventDestroy(c->rank_ev[e]);
+    }
     if (c->d_efpd) (void)hipFree(c->d_efpd);
     if (c->d_efbits) (void)hipFree(c->d_efbits);
     if (c->d_segr) (void)hipFree(c->d_segr);
@@ -2840,6 +2852,221 @@ int acx_ftm2d_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, float *out)
         ACX_HIP(c, hipStreamSynchronize(c->stream));
     }
     return ACX_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Ranking of finished score rows (rank_kernels.hpp): evaluation positions and top-k lists
+// ---------------------------------------------------------------------------------------
+static const int64_t RANK_SLICE_BYTES = (int64_t)64 << 20;       // a staging piece of whole rows (two are in flight)
+
+// What both calls check of their common arguments, before anything is allocated or launched.
+static int rank_check_common(acx_ctx *c, const char *who, const float *scores, int64_t ld, int32_t n, int32_t n_rows, const int32_t *self,
+                             const int32_t *posn)
+{
+    const std::string w(who);
+    if (n < 1) return fail(c, ACX_ERR_INVALID, w + ": n must be >= 1 (got " + std::to_string(n) + ")");
+    if (n_rows < 0) return fail(c, ACX_ERR_INVALID, w + ": n_rows must be >= 0 (got " + std::to_string(n_rows) + ")");
+    if (ld < n) return fail(c, ACX_ERR_INVALID, w + ": ld = " + std::to_string(ld) + " is smaller than n = " + std::to_string(n));
+    if (n_rows > 0 && (!scores || !self)) return fail(c, ACX_ERR_INVALID, w + ": scores and self must not be NULL");
+    for (int32_t r = 0; r < n_rows; ++r)
+        if (self[r] < 0 || self[r] >= n)
+            return fail(c, ACX_ERR_INVALID, w + ": self[" + std::to_string(r) + "] = " + std::to_string(self[r]) + " is not a column in [0, " + std::to_string(n) + ")");
+    if (posn)
+        for (int32_t i = 0; i < n; ++i)
+            if (posn[i] < 0) return fail(c, ACX_ERR_INVALID, w + ": posn[" + std::to_string(i) + "] = " + std::to_string(posn[i]) + " is negative");
+    return ACX_OK;
+}
+
+// Rows per staging piece: whole rows, RANK_SLICE_BYTES at most, and everything the call holds on the device (two pieces,
+// `per_row_out` bytes of results per row, `fixed` bytes of tables) within the scratch limit.
+static int rank_piece_rows(acx_ctx *c, const char *who, int32_t n, int32_t n_rows, int64_t per_row_out, int64_t fixed, int32_t *rows)
+{
+    const int64_t row_bytes = (int64_t)round_up(n, 4) * 4;
+    const int64_t lim = scratch_limit_bytes(c) - fixed;
+    if (lim < 2 * (row_bytes + per_row_out))
+        return fail(c, ACX_ERR_NOMEM, std::string(who) + ": two rows of " + std::to_string(n) + " scores and their results do not fit the scratch limit");
+    const int64_t pr = std::min<int64_t>(RANK_SLICE_BYTES / row_bytes, lim / (2 * (row_bytes + per_row_out)));
+    *rows = (int32_t)std::max<int64_t>(1, std::min<int64_t>(pr, n_rows));
+    return ACX_OK;
+}
+
+// Stages the slab to the device piece by piece through the two pinned slots and calls run(d_rows, ldd, r0, nr) for every
+// piece (run launches on c->stream and returns an ACX code).  The host packs piece p + 1 while piece p is copied and ranked.
+extern "C++" {
+template <typename F>
+static int rank_for_pieces(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int32_t n_rows, int32_t piece, F run)
+{
+    const int64_t ldd = round_up(n, 4);
+    int rc;
+    for (int e = 0; e < 2; ++e) {
+        const size_t need = (size_t)ldd * piece;
+        if (need > c->rank_h_cap[e]) {
+            if (c->rank_h[e]) { (void)hipHostFree(c->rank_h[e]); c->rank_h[e] = nullptr; c->rank_h_cap[e] = 0; }
+            if (hipHostMalloc((void **)&c->rank_h[e], need * sizeof(float), hipHostMallocDefault) != hipSuccess) {
+                c->rank_h[e] = nullptr;
+                (void)hipGetLastError();
+                return fail(c, ACX_ERR_NOMEM, "rank: cannot allocate a pinned staging slot of " + std::to_string(need * sizeof(float)) + " bytes");
+            }
+            c->rank_h_cap[e] = need;
+        }
+        if ((rc = ensure(c, c->rank_d[e], c->rank_d_cap[e], need)) != ACX_OK) return rc;
+        if (!c->rank_ev[e]) ACX_HIP(c, hipEventCreateWithFlags(&c->rank_ev[e], hipEventDisableTiming));
+        if (n_rows <= piece) break;                                        // one piece: one slot
+    }
+    int p = 0;
+    for (int32_t r0 = 0; r0 < n_rows; r0 += piece, ++p) {
+        const int32_t nr = std::min(piece, n_rows - r0);
+        const int e = p & 1;
+        if (p >= 2) ACX_HIP(c, hipEventSynchronize(c->rank_ev[e]));        // the slot's previous piece is done with it
+        for (int32_t r = 0; r < nr; ++r) memcpy(c->rank_h[e] + (size_t)r * ldd, scores + (size_t)(r0 + r) * ld, sizeof(float) * (size_t)n);
+        ACX_HIP(c, hipMemcpyAsync(c->rank_d[e], c->rank_h[e], sizeof(float) * (size_t)ldd * nr, hipMemcpyHostToDevice, c->stream));
+        if ((rc = run(c->rank_d[e], ldd, r0, nr)) != ACX_OK) return rc;
+        ACX_HIP(c, hipEventRecord(c->rank_ev[e], c->stream));
+    }
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
+}
+}  // extern "C++"
+
+static int rank_lds_attr(acx_ctx *c)
+{
+    if (c->rank_attr) return ACX_OK;
+    const int row = 4 * (acx::RANK_ROW_LDS + 8);
+    ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::rank_columns_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, row));
+    ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::topk_rows_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   row + 12 * acx::RANK_KMAX));
+    c->rank_attr = true;
+    return ACX_OK;
+}
+
+int acx_rank_columns(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int32_t n_rows, const int32_t *self, const int32_t *posn,
+                     const int64_t *moff, const int32_t *mates, int32_t *out_pos, uint8_t *out_flag)
+{
+    if (!c) return ACX_ERR_INVALID;
+    int rc = rank_check_common(c, "rank_columns", scores, ld, n, n_rows, self, posn);
+    if (rc != ACX_OK) return rc;
+    if (!moff) return fail(c, ACX_ERR_INVALID, "rank_columns: moff must not be NULL");
+    if (moff[0] != 0) return fail(c, ACX_ERR_INVALID, "rank_columns: moff[0] must be 0");
+    for (int32_t r = 0; r < n_rows; ++r)
+        if (moff[r + 1] < moff[r]) return fail(c, ACX_ERR_INVALID, "rank_columns: moff must be non-decreasing (moff[" + std::to_string(r + 1) + "])");
+    const int64_t M = moff[n_rows];
+    if (n_rows > 0 && !out_flag) return fail(c, ACX_ERR_INVALID, "rank_columns: out_flag must not be NULL");
+    if (M > 0 && (!mates || !out_pos)) return fail(c, ACX_ERR_INVALID, "rank_columns: mates and out_pos must not be NULL");
+    for (int32_t r = 0; r < n_rows; ++r)
+        for (int64_t j = moff[r]; j < moff[r + 1]; ++j) {
+            if (mates[j] < 0 || mates[j] >= n)
+                return fail(c, ACX_ERR_INVALID, "rank_columns: mates[" + std::to_string(j) + "] = " + std::to_string(mates[j]) + " is not a column in [0, " + std::to_string(n) + ")");
+            if (mates[j] == self[r])
+                return fail(c, ACX_ERR_INVALID, "rank_columns: mates[" + std::to_string(j) + "] is row " + std::to_string(r) + "'s own column (self)");
+        }
+    if (n_rows == 0) return ACX_OK;
+    const int64_t fixed = 8 * (int64_t)(n_rows + 1) + 8 * M + 5 * (int64_t)n_rows + 4 * (int64_t)n;
+    int32_t piece = 0;
+    if ((rc = rank_piece_rows(c, "rank_columns", n, n_rows, 0, fixed, &piece)) != ACX_OK) return rc;
+    ACX_HIP(c, hipSetDevice(c->device));
+    if ((rc = rank_lds_attr(c)) != ACX_OK) return rc;
+    // the tables of the whole call in one device block: moff | mates | out_pos | self | posn | out_flag
+    const size_t o_mates = sizeof(int64_t) * (size_t)(n_rows + 1), o_pos = o_mates + 4 * (size_t)M, o_self = o_pos + 4 * (size_t)M,
+                 o_posn = o_self + 4 * (size_t)n_rows, o_flag = o_posn + (posn ? 4 * (size_t)n : 0), total = o_flag + (size_t)n_rows;
+    char *d_tab = nullptr;
+    {
+        const hipError_t e = hipMalloc((void **)&d_tab, total);
+        if (e != hipSuccess) return fail(c, ACX_ERR_NOMEM, std::string("rank_columns: ") + hipGetErrorString(e));
+    }
+    auto body = [&]() -> int {
+        ACX_HIP(c, hipMemcpyAsync(d_tab, moff, sizeof(int64_t) * (size_t)(n_rows + 1), hipMemcpyHostToDevice, c->stream));
+        if (M > 0) ACX_HIP(c, hipMemcpyAsync(d_tab + o_mates, mates, 4 * (size_t)M, hipMemcpyHostToDevice, c->stream));
+        ACX_HIP(c, hipMemcpyAsync(d_tab + o_self, self, 4 * (size_t)n_rows, hipMemcpyHostToDevice, c->stream));
+        if (posn) ACX_HIP(c, hipMemcpyAsync(d_tab + o_posn, posn, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        const int64_t *d_moff = reinterpret_cast<const int64_t *>(d_tab);
+        const int32_t *d_mates = reinterpret_cast<const int32_t *>(d_tab + o_mates), *d_self = reinterpret_cast<const int32_t *>(d_tab + o_self);
+        const int32_t *d_posn = posn ? reinterpret_cast<const int32_t *>(d_tab + o_posn) : nullptr;
+        int32_t *d_pos = reinterpret_cast<int32_t *>(d_tab + o_pos);
+        uint8_t *d_flag = reinterpret_cast<uint8_t *>(d_tab + o_flag);
+        const bool in_lds = n <= acx::RANK_ROW_LDS;
+        const size_t lds = in_lds ? 16 * (size_t)((n + 3) / 4 + 1) : 0;
+        int rcp = rank_for_pieces(c, scores, ld, n, n_rows, piece, [&](const float *d_rows, int64_t ldd, int32_t r0, int32_t nr) -> int {
+            ProfScope ps(c, KS_RANK, (int64_t)nr * n);
+            if (in_lds)
+                hipLaunchKernelGGL((acx::rank_columns_kernel<true>), dim3((unsigned)nr), dim3(acx::RANK_THREADS), lds, c->stream, d_rows, ldd, (int)n,
+                                   d_self + r0, d_posn, d_moff + r0, d_mates, (int64_t)0, d_pos, d_flag + r0);
+            else
+                hipLaunchKernelGGL((acx::rank_columns_kernel<false>), dim3((unsigned)nr), dim3(acx::RANK_THREADS), 0, c->stream, d_rows, ldd, (int)n,
+                                   d_self + r0, d_posn, d_moff + r0, d_mates, (int64_t)0, d_pos, d_flag + r0);
+            return ACX_OK;
+        });
+        if (rcp != ACX_OK) return rcp;
+        ACX_LAUNCHES_OK(c);
+        if (M > 0) ACX_HIP(c, hipMemcpy(out_pos, d_pos, 4 * (size_t)M, hipMemcpyDeviceToHost));
+        ACX_HIP(c, hipMemcpy(out_flag, d_flag, (size_t)n_rows, hipMemcpyDeviceToHost));
+        return ACX_OK;
+    };
+    rc = body();
+    if (rc != ACX_OK) quiesce(c); else drain_profile(c);
+    (void)hipFree(d_tab);
+    return rc;
+}
+
+int acx_topk_rows(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int32_t n_rows, const int32_t *self, const int32_t *posn, int32_t k,
+                  int32_t *out_idx, float *out_score)
+{
+    if (!c) return ACX_ERR_INVALID;
+    int rc = rank_check_common(c, "topk_rows", scores, ld, n, n_rows, self, posn);
+    if (rc != ACX_OK) return rc;
+    if (k < 1) return fail(c, ACX_ERR_INVALID, "topk_rows: k must be >= 1 (got " + std::to_string(k) + ")");
+    if (k > acx::RANK_KMAX)
+        return fail(c, ACX_ERR_UNSUPPORTED, "topk_rows: k = " + std::to_string(k) + " is over the limit of " + std::to_string(acx::RANK_KMAX));
+    if (n_rows > 0 && (!out_idx || !out_score)) return fail(c, ACX_ERR_INVALID, "topk_rows: out_idx and out_score must not be NULL");
+    if (n_rows == 0) return ACX_OK;
+    const int64_t fixed = 4 * (int64_t)n_rows + 4 * (int64_t)n;
+    int32_t piece = 0;
+    if ((rc = rank_piece_rows(c, "topk_rows", n, n_rows, 8 * (int64_t)k, fixed, &piece)) != ACX_OK) return rc;
+    ACX_HIP(c, hipSetDevice(c->device));
+    if ((rc = rank_lds_attr(c)) != ACX_OK) return rc;
+    int P = 4;
+    while (P < std::min<int>(k, n - 1)) P <<= 1;
+    // self | posn | two result slots of `piece` rows (indices, scores)
+    const size_t o_posn = 4 * (size_t)n_rows, o_res = o_posn + (posn ? 4 * (size_t)n : 0), slot_bytes = 8 * (size_t)k * piece,
+                 total = o_res + 2 * slot_bytes;
+    char *d_tab = nullptr;
+    {
+        const hipError_t e = hipMalloc((void **)&d_tab, total);
+        if (e != hipSuccess) return fail(c, ACX_ERR_NOMEM, std::string("topk_rows: ") + hipGetErrorString(e));
+    }
+    auto body = [&]() -> int {
+        ACX_HIP(c, hipMemcpyAsync(d_tab, self, 4 * (size_t)n_rows, hipMemcpyHostToDevice, c->stream));
+        if (posn) ACX_HIP(c, hipMemcpyAsync(d_tab + o_posn, posn, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        const int32_t *d_self = reinterpret_cast<const int32_t *>(d_tab);
+        const int32_t *d_posn = posn ? reinterpret_cast<const int32_t *>(d_tab + o_posn) : nullptr;
+        const bool in_lds = n <= acx::RANK_ROW_LDS;
+        const size_t lds = 12 * (size_t)P + (in_lds ? 4 * (size_t)(n + 3) : 0);
+        int p = 0;
+        int rcp = rank_for_pieces(c, scores, ld, n, n_rows, piece, [&](const float *d_rows, int64_t ldd, int32_t r0, int32_t nr) -> int {
+            // (the result slot alternates with the staging slot: its previous copy to the host was issued on the same stream)
+            int32_t *d_idx = reinterpret_cast<int32_t *>(d_tab + o_res + (size_t)(p & 1) * slot_bytes);
+            float *d_sc = reinterpret_cast<float *>(d_idx + (size_t)k * piece);
+            ++p;
+            {
+                ProfScope ps(c, KS_TOPK, (int64_t)nr * n);
+                if (in_lds)
+                    hipLaunchKernelGGL((acx::topk_rows_kernel<true>), dim3((unsigned)nr), dim3(acx::RANK_THREADS), lds, c->stream, d_rows, ldd, (int)n,
+                                       d_self + r0, d_posn, (int)k, P, d_idx, d_sc);
+                else
+                    hipLaunchKernelGGL((acx::topk_rows_kernel<false>), dim3((unsigned)nr), dim3(acx::RANK_THREADS), lds, c->stream, d_rows, ldd, (int)n,
+                                       d_self + r0, d_posn, (int)k, P, d_idx, d_sc);
+            }
+            ACX_HIP(c, hipMemcpyAsync(out_idx + (size_t)r0 * k, d_idx, 4 * (size_t)k * nr, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(out_score + (size_t)r0 * k, d_sc, 4 * (size_t)k * nr, hipMemcpyDeviceToHost, c->stream));
+            return ACX_OK;
+        });
+        if (rcp != ACX_OK) return rcp;
+        ACX_LAUNCHES_OK(c);
+        return ACX_OK;
+    };
+    rc = body();
+    if (rc != ACX_OK) quiesce(c); else drain_profile(c);
+    (void)hipFree(d_tab);
+    return rc;
 }
 
 // Device state of one similarity-network-fusion run: P matrices (two generations), the kNN kernels,

@@ -557,6 +557,34 @@ int acx_grid_scatter(const int64_t *lengths, int32_t n_tracks, const acx_grid_sp
 int acx_pair_grid(acx_ctx *ctx, const acx_grid_spec *spec, const void *params, float *const *D, int64_t ld,
                   int32_t mirror);
 
+/* ---- ranking of finished score rows: evaluation positions and top-k ----- */
+
+/*
+ * Everything a user does with a finished N x N score matrix orders its rows (getEvalStatistics,
+ * algorithm_template.py:205-290: the positions of a track's clique mates; candidate lists: the first k columns).
+ * Both calls take a ROW SLAB in HOST memory: n_rows rows of n floats with leading dimension ld; row r is the score row
+ * of track self[r], whose own cell takes no part.  posn: n distinct non-negative tie ranks, or NULL (= the column index).
+ * ONE order: column a comes before column b iff s[a] > s[b], or s[a] == s[b] and posn[a] < posn[b] -- IEEE comparison,
+ * so -0.0 and +0.0 tie.
+ *   acx_rank_columns  for every listed column m of row r (mates[moff[r] .. moff[r + 1]), any number, moff[0] = 0) its
+ *                     1-based position 1 + #{c != self: s[c] > s[m]} + #{c != self: s[c] == s[m], posn[c] < posn[m]}
+ *                     into out_pos (moff[n_rows] entries).  A row that holds a NaN or a -inf outside its own cell is
+ *                     FLAGGED (out_flag[r] = 1, its positions -1): the host decides what such a row means.  +inf is an
+ *                     ordinary value.
+ *   acx_topk_rows     the first k columns of the order and their scores (bit copies) into out_idx / out_score
+ *                     (n_rows x k).  NaN cells come after every number (after -inf too), among themselves by posn --
+ *                     what np.argsort(-row, kind="stable") does.  Fewer than k other columns: the tail is index -1,
+ *                     score NaN.  k <= 1024; beyond: ACX_ERR_UNSUPPORTED.
+ * The slab goes to the device in pieces of whole rows (64 MB) through two pinned slots, within acx_set_scratch_limit
+ * (two rows that do not fit: ACX_ERR_NOMEM); n is not limited by the LDS.  The whole argument list is validated before
+ * the first launch (indices in [0, n), moff non-decreasing, a mate equal to self[r] is ACX_ERR_INVALID, the message
+ * names the argument); nothing is left in flight on error.
+ */
+int acx_rank_columns(acx_ctx *ctx, const float *scores, int64_t ld, int32_t n, int32_t n_rows, const int32_t *self,
+                     const int32_t *posn, const int64_t *moff, const int32_t *mates, int32_t *out_pos, uint8_t *out_flag);
+int acx_topk_rows(acx_ctx *ctx, const float *scores, int64_t ld, int32_t n, int32_t n_rows, const int32_t *self,
+                  const int32_t *posn, int32_t k, int32_t *out_idx, float *out_score);
+
 /* ---- multi-GPU inside the library: RCCL over xGMI, no Python ------------- */
 
 /*

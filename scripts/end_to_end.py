@@ -3,7 +3,7 @@ for Serra09 (coverid.py:57-70): Serra09.all_pairwise(symmetric=True) + normalize
 getEvalStatistics() on the synthetic 5 000-track x 2000-frame pool of bench.py (12 497 500 pairs), wall time
 per phase -> profiles/r03_end_to_end.json (via gpurun_out/).
 
-    python scripts/end_to_end.py [n_tracks] [frames | covers]        (covers: lengths uniform in 150 .. 650 pooled frames, the
+    python scripts/end_to_end.py [n_tracks] [frames | covers] [--eval host|device|both]        (covers: lengths uniform in 150 .. 650 pooled frames, the
                                                                        shape of covers80 / DA-TACOS tracks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/end_to_end.py [n_tracks] [frames]
 
@@ -22,6 +22,34 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 from acoss_amd.algorithms.rqa_serra09 import Serra09  # noqa: E402
 
+
+def _pop_eval_option(argv):
+    """--eval host|device|both (default host) out of argv: which engine ranks the score rows in getEvalStatistics."""
+    mode = "host"
+    if "--eval" in argv:
+        k = argv.index("--eval")
+        if k + 1 >= len(argv) or argv[k + 1] not in ("host", "device", "both"):
+            sys.exit("--eval takes host, device or both")
+        mode = argv[k + 1]
+        del argv[k:k + 2]
+    return mode
+
+
+def _timed_eval(alg, key, mode, times):
+    """getEvalStatistics(key) by the engine(s) of `mode`; seconds per engine are added to times[engine].  both: the two
+    engines rank the same matrix and must return equal tuples."""
+    res = {}
+    for engine in (("host", "device") if mode == "both" else (mode,)):
+        t0 = time.time()
+        res[engine] = alg.getEvalStatistics(key, engine=engine)
+        times[engine] = times.get(engine, 0.0) + time.time() - t0
+    if mode == "both":
+        h, d = res["host"], res["device"]
+        assert tuple(h[:4]) == tuple(d[:4]) and np.array_equal(h[4], d[4]), "engines disagree on %s: %s vs %s" % (key, h, d)
+    return res["host" if mode != "device" else "device"]
+
+
+EVAL = _pop_eval_option(sys.argv)
 N = int(sys.argv[1]) if len(sys.argv) > 1 else bench.N_TRACKS
 COVERS = len(sys.argv) > 2 and sys.argv[2] == "covers"
 T = 0 if COVERS else (int(sys.argv[2]) if len(sys.argv) > 2 else bench.T_FRAMES)
@@ -74,9 +102,9 @@ ph["all_pairwise_s"] = time.time() - t0
 t0 = time.time()
 alg.normalize_by_length()
 ph["normalize_by_length_s"] = time.time() - t0
-t0 = time.time()
-res = alg.getEvalStatistics("main")
-ph["getEvalStatistics_s"] = time.time() - t0
+eval_s = {}
+res = _timed_eval(alg, "main", EVAL, eval_s)             # (a collective under torch.distributed, whatever the engine)
+ph["getEvalStatistics_s"] = eval_s["device" if EVAL == "device" else "host"]
 sys.stderr.write("[end_to_end rank %d/%d] %s\n" % (rank, world, json.dumps({k: round(v, 2) for k, v in ph.items()})))
 per_rank = [ph]
 if dist is not None:
@@ -104,6 +132,7 @@ if rank == 0:
            "note": "all_pairwise includes the tile plan, every kernel, the device-to-host copy of the tile scores (one GPU: 256 MB "
                    "slices; N GPUs: after the one all-gather), the scatter + mirror into the N x N float32 memmap and writing the "
                    "<prefix>_Ds.npz cache; rank 0's clock (it owns the result), every rank's clock in phases_s_per_rank",
+           "eval_engine": EVAL, "getEvalStatistics_s_by_engine": {k: round(v, 3) for k, v in eval_s.items()},
            "stats": {"MR": res[0], "MRR": res[1], "MDR": res[2], "MAP": res[3]}}
     print(json.dumps(rec))
     with open(os.path.join(out_dir, "end_to_end.json"), "w") as f:

@@ -4,7 +4,7 @@ do_late_fusion() + getEvalStatistics() for all six similarity types, on a synthe
 blocks each (block features i.i.d., generated on the device slice by slice: 56 GB at N = 15 000, which no host array
 ever holds) -> gpurun_out/end_to_end_ef.json.
 
-    python scripts/end_to_end_ef.py [n_tracks]
+    python scripts/end_to_end_ef.py [n_tracks] [--eval host|device|both]
 
 The i.i.d. pool has no cover structure (every 5 consecutive tracks are labelled as one work so that the evaluation does
 its full amount of work); what is measured is time per phase."""
@@ -21,6 +21,34 @@ sys.path.insert(0, ROOT)
 from acoss_amd import _lib  # noqa: E402
 from acoss_amd.algorithms.earlyfusion_traile import EarlyFusion  # noqa: E402
 
+
+def _pop_eval_option(argv):
+    """--eval host|device|both (default host) out of argv: which engine ranks the score rows in getEvalStatistics."""
+    mode = "host"
+    if "--eval" in argv:
+        k = argv.index("--eval")
+        if k + 1 >= len(argv) or argv[k + 1] not in ("host", "device", "both"):
+            sys.exit("--eval takes host, device or both")
+        mode = argv[k + 1]
+        del argv[k:k + 2]
+    return mode
+
+
+def _timed_eval(alg, key, mode, times):
+    """getEvalStatistics(key) by the engine(s) of `mode`; seconds per engine are added to times[engine].  both: the two
+    engines rank the same matrix and must return equal tuples."""
+    res = {}
+    for engine in (("host", "device") if mode == "both" else (mode,)):
+        t0 = time.time()
+        res[engine] = alg.getEvalStatistics(key, engine=engine)
+        times[engine] = times.get(engine, 0.0) + time.time() - t0
+    if mode == "both":
+        h, d = res["host"], res["device"]
+        assert tuple(h[:4]) == tuple(d[:4]) and np.array_equal(h[4], d[4]), "engines disagree on %s: %s vs %s" % (key, h, d)
+    return res["host" if mode != "device" else "device"]
+
+
+EVAL = _pop_eval_option(sys.argv)
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 15000
 out_dir = os.path.join(ROOT, "gpurun_out")
 os.makedirs(out_dir, exist_ok=True)
@@ -67,15 +95,16 @@ ph["all_pairwise_s"] = time.time() - t0
 t0 = time.time()
 ef.do_late_fusion()
 ph["do_late_fusion_s"] = time.time() - t0
-t0 = time.time()
-stats = {k: ef.getEvalStatistics(k)[:4] for k in list(ef.Ds.keys())}
-ph["getEvalStatistics_x6_s"] = time.time() - t0
+eval_s = {}
+stats = {k: _timed_eval(ef, k, EVAL, eval_s)[:4] for k in list(ef.Ds.keys())}
+ph["getEvalStatistics_x6_s"] = eval_s["device" if EVAL == "device" else "host"]
 pairs = N * (N - 1) // 2
 total = sum(ph.values())
 rec = {"workload": "configs[4]: %d tracks of 300-500 blocks (%d blocks, %.1f GB of block features on the device), EarlyFusionTraile, all %d "
                    "unordered pairs, one MI355X" % (N, int(off[-1]), off[-1] * 2355 * 4 / 1e9, pairs),
        "phases_s": {k: round(v, 2) for k, v in ph.items()}, "total_s": round(total, 2),
        "pairs_per_s_all_pairwise": round(pairs / ph["all_pairwise_s"], 1), "pairs_per_s_end_to_end": round(pairs / total, 1),
+       "eval_engine": EVAL, "getEvalStatistics_x6_s_by_engine": {k: round(v, 3) for k, v in eval_s.items()},
        "similarity_types": list(ef.Ds.keys()), "MAP": {k: v[3] for k, v in stats.items()}}
 print(json.dumps(rec))
 with open(os.path.join(out_dir, "end_to_end_ef.json"), "w") as f:
