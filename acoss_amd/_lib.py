@@ -36,6 +36,7 @@ EXPORTS = [
     "acx_ftm2d_default_params", "acx_ftm2d_pool_begin", "acx_ftm2d_pool_tracks", "acx_ftm2d_pool_end",
     "acx_ftm2d_upload_shingles", "acx_ftm2d_download_shingles", "acx_ftm2d_debug_track", "acx_ftm2d_pairs",
     "acx_rank_columns", "acx_topk_rows",
+    "acx_query_scores", "acx_query_topk",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -64,6 +65,12 @@ class GridTile(ctypes.Structure):
     _fields_ = [("row0", ctypes.c_int32), ("col0", ctypes.c_int32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32),
                 ("rank", ctypes.c_int32), ("diagonal", ctypes.c_int32), ("offset", ctypes.c_int64),
                 ("cost", ctypes.c_double)]
+
+
+class QuerySpec(ctypes.Structure):
+    """acx_query_spec (include/acx.h)."""
+    _fields_ = [("algo", ctypes.c_int32), ("symmetric", ctypes.c_int32), ("col_mode", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 class SimpleParams(ctypes.Structure):
@@ -252,6 +259,9 @@ def load():
     L.acx_rank_columns.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ip, ip, lp, ip, ip,
                                    ctypes.POINTER(ctypes.c_uint8)]
     L.acx_topk_rows.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ip, ip, ctypes.c_int32, ip, fp]
+    qp = ctypes.POINTER(QuerySpec)
+    L.acx_query_scores.argtypes = [vp, qp, vp, ip, ctypes.c_int32, dp, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64]
+    L.acx_query_topk.argtypes = [vp, qp, vp, ip, ctypes.c_int32, ip, ctypes.c_int32, dp, ctypes.c_int32, ip, fp]
     _check_hip_version(L)
     _lib = L
     return L
@@ -945,6 +955,46 @@ class Context(object):
         for a, cnt, slab, ld in _row_slabs(D, rows, self.RANK_SLAB_BYTES):
             self._check(self._L.acx_topk_rows(self._h, ctypes.c_void_p(slab.ctypes.data), int(ld), n, int(cnt), _iptr(rows[a:a + cnt]),
                                               None if posn is None else _iptr(posn), k, _iptr(idx[a:a + cnt]), _fptr(score[a:a + cnt])))
+        return idx, score
+
+    # ------------------------------------------------------------------ queries against the uploaded collection
+    def _query_args(self, algo, symmetric, queries, col, col_mode):
+        spec = QuerySpec(int(algo), int(bool(symmetric)), int(col_mode), 0)
+        queries = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+        if col is not None:
+            col = np.ascontiguousarray(col, dtype=np.float64).reshape(-1)
+        return spec, queries, col
+
+    def query_scores(self, algo, symmetric, params, queries, col=None, col_mode=0):
+        """acx_query_scores: the finished score rows of `queries` (track indices of the uploaded pool, duplicates
+        allowed) against every track, (planes, Q, N) float32 -- plane order as in GRID_PLANES; a query's own cell is 0.
+        symmetric: the pair {q, c} is computed as (min, max) (the cell all_pairwise(symmetric=True) computes and
+        mirrors), else as (q, c).  col_mode 0: the raw score s; 1: s / col[c]; 2: -(col[c] / s), in f64, rounded once
+        (col: one value per track).  The scores never leave the device before they are finished."""
+        spec, queries, col = self._query_args(algo, symmetric, queries, col, col_mode)
+        n = len(self.pool_lengths(algo))
+        w = GRID_PLANES[int(algo)]
+        out = np.zeros((w, len(queries), n), np.float32)
+        ptrs = (ctypes.c_void_p * w)(*[out[e].ctypes.data for e in range(w)])
+        self._check(self._L.acx_query_scores(self._h, ctypes.byref(spec), _params_ptr(params), _iptr(queries), len(queries),
+                                             None if col is None else _dptr(col), ptrs, n))
+        return out
+
+    def query_topk(self, algo, symmetric, params, queries, k, candidates=None, col=None, col_mode=0):
+        """acx_query_topk: (idx (Q, planes, k) int32, score (Q, planes, k) float32), the k best candidates of every query
+        and plane -- larger score first, ties in ascending track index, NaN last, the query itself left out; fewer than k
+        candidates: the tail is index -1, score NaN.  candidates: strictly ascending track indices (None: every track);
+        only their columns are computed.  Scores as in query_scores; ranked on the device, only the lists come back."""
+        spec, queries, col = self._query_args(algo, symmetric, queries, col, col_mode)
+        w = GRID_PLANES[int(algo)]
+        k = int(k)
+        idx = np.full((len(queries), w, max(k, 0)), -1, np.int32)
+        score = np.full((len(queries), w, max(k, 0)), np.nan, np.float32)
+        cands = None if candidates is None else np.ascontiguousarray(candidates, dtype=np.int32).reshape(-1)
+        cptr = None if cands is None else _iptr(cands)      # (NULL means "every track"; an empty list is not NULL)
+        self._check(self._L.acx_query_topk(self._h, ctypes.byref(spec), _params_ptr(params), _iptr(queries), len(queries),
+                                           cptr, 0 if cands is None else len(cands), None if col is None else _dptr(col), k,
+                                           _iptr(idx), _fptr(score)))
         return idx, score
 
     def profile_enable(self, on=True):

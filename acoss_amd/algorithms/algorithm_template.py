@@ -270,6 +270,87 @@ class CoverAlgorithm(object):
         if rank == 0:
             _lib.grid_scatter(lengths, plan["spec"], gathered, stride, planes, mirror=symmetric)
 
+    # ------------------------------------------------------------------ queries against the collection
+    # What a device-backed class tells identify() / query_rows() about the sequence coverid.benchmark() runs for it:
+    # the similarity types the device computes (the planes of _grid(), in plane order), the types that only exist as a
+    # fusion of whole matrices, and the orientation all_pairwise is called with there.
+    _identify_planes = ("main",)
+    _identify_fused = ()
+    _identify_symmetric = True
+
+    def _identify_norm(self):
+        """(col_mode, col) of the class's normalize_by_length as acx_query_spec states it (include/acx.h): (0, None) for
+        a class without one."""
+        return 0, None
+
+    def _query_setup(self, who, queries, similarity_types):
+        """Argument checks of identify() / query_rows(), all before the first library call (no pool is uploaded, no GPU
+        is touched, for a call that cannot run): -> (queries int32 (Q,), the similarity types asked for)."""
+        if not hasattr(self, "_grid"):
+            raise NotImplementedError("%s: %s has no device path (_grid()); a class that brings its own CPU similarity() "
+                                      "answers queries through similarity(idxs) and top_matches()" % (who, type(self).__name__))
+        types = list(self._identify_planes) if similarity_types is None else list(similarity_types)
+        for t in types:
+            if t in self._identify_fused:
+                raise NotImplementedError("%s: '%s' is a fusion of whole N x N matrices (do_late_fusion) and cannot be "
+                                          "computed for a band of query rows" % (who, t))
+            if t not in self._identify_planes:
+                raise ValueError("%s: unknown similarity type '%s' (available: %s)" % (who, t, list(self._identify_planes)))
+        q = np.asarray(queries)
+        if q.size and not np.issubdtype(q.dtype, np.integer):
+            raise ValueError("%s: queries must be integer track indices" % who)
+        q = q.reshape(-1).astype(np.int64)
+        if q.size and (q.min() < 0 or q.max() >= self.N):
+            raise ValueError("%s: queries must be track indices in [0, %d)" % (who, self.N))
+        return q.astype(np.int32), types
+
+    def _query_call(self):
+        ctx, algo, params, keys = self._grid()
+        if tuple(keys) != tuple(self._identify_planes):
+            raise RuntimeError("%s: _grid() planes %s differ from _identify_planes %s" % (type(self).__name__, keys, self._identify_planes))
+        mode, col = self._identify_norm()
+        return ctx, algo, params, mode, col
+
+    def identify(self, queries, k=10, candidates=None, similarity_types=None):
+        """Which k tracks of the collection are the covers of these tracks?  queries: track indices (any order,
+        duplicates allowed); candidates: the tracks that may be listed -- any integer sequence, flattened; it must then
+        be strictly ascending (None: every track).  Returns {type: (idx (Q, k) int32, score (Q, k) float32)} for the
+        similarity types the device computes (similarity_types: a subset, None: all): values and order are those of
+        coverid.benchmark()'s sequence for the class -- all_pairwise(...), normalize_by_length() where the class has
+        one (ChenFusion: with the sign flip of do_late_fusion, larger = closer), top_matches(type, k, rows=queries) --
+        but only the Q rows are computed (acx_query_topk): the scores stay on the device, are normalised and ranked
+        there, and `Ds` is not written.  A query never lists itself; fewer than k candidates: the tail is -1 / NaN.
+        Fused types need the whole matrix: NotImplementedError.  Not a collective: under a process group every rank
+        that calls it computes on its own GPU."""
+        q, types = self._query_setup("identify", queries, similarity_types)
+        k = int(k)
+        if k < 1:
+            raise ValueError("identify: k must be >= 1 (got %d)" % k)
+        cands = None
+        if candidates is not None:
+            cands = np.asarray(candidates)
+            if cands.size and not np.issubdtype(cands.dtype, np.integer):
+                raise ValueError("identify: candidates must be integer track indices")
+            cands = cands.reshape(-1).astype(np.int64)
+            if cands.size and (cands.min() < 0 or cands.max() >= self.N):
+                raise ValueError("identify: candidates must be track indices in [0, %d)" % self.N)
+            if np.any(np.diff(cands) <= 0):
+                raise ValueError("identify: candidates must be strictly ascending")
+            cands = cands.astype(np.int32)
+        ctx, algo, params, mode, col = self._query_call()
+        idx, score = ctx.query_topk(algo, self._identify_symmetric, params, q, k, candidates=cands, col=col, col_mode=mode)
+        planes = list(self._identify_planes)
+        return {t: (np.ascontiguousarray(idx[:, planes.index(t)]), np.ascontiguousarray(score[:, planes.index(t)])) for t in types}
+
+    def query_rows(self, queries, similarity_types=None):
+        """The same rows in full: {type: (Q, N) float32}, the finished scores of every query against every track (its
+        own cell 0), as identify() ranks them (acx_query_scores).  `Ds` is not written."""
+        q, types = self._query_setup("query_rows", queries, similarity_types)
+        ctx, algo, params, mode, col = self._query_call()
+        rows = ctx.query_scores(algo, self._identify_symmetric, params, q, col=col, col_mode=mode)
+        planes = list(self._identify_planes)
+        return {t: rows[planes.index(t)] for t in types}
+
     def cleanup_memmap(self):
         """Remove the memmap files behind the similarity matrices."""
         for s in list(self.Ds.keys()):

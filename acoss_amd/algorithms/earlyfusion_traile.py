@@ -112,6 +112,9 @@ class EarlyFusion(CoverAlgorithm):
             self._pool_ready = True
         return self._ctx
 
+    _identify_planes = ("mfccs", "ssms", "chromas", "early")
+    _identify_fused = ("late", "early+late")
+
     def _grid(self):
         return (self._context(), _lib.ALGO_EARLYFUSION, _lib.EfParams(float(self.kappa), int(self.K)),
                 ["mfccs", "ssms", "chromas", "early"])

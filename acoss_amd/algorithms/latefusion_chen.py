@@ -36,6 +36,13 @@ class ChenFusion(Serra09):
         CoverAlgorithm.__init__(self, dataset_csv=dataset_csv, name="LateFusionChen", datapath=datapath,
                                 shortname=shortname, similarity_types=["qmax", "dmax"])
 
+    _identify_planes = ("qmax", "dmax")
+    _identify_fused = ("Late",)
+
+    def _identify_norm(self):
+        """identify() / query_rows(): -(sqrt(T_c) / s), normalize_by_length with the sign flip of do_late_fusion."""
+        return 2, np.sqrt(self._pooled_lengths().astype(np.float64))
+
     def _grid(self):
         return self._context(), _lib.ALGO_CHENFUSION, self._params(), ["qmax", "dmax"]
 

@@ -153,6 +153,10 @@ class Serra09(CoverAlgorithm):
         """all_pairwise runs the whole N x N grid inside libacx (algorithm_template._all_pairwise_grid)."""
         return self._context(), _lib.ALGO_SERRA09, self._params(), ["main"]
 
+    def _identify_norm(self):
+        """identify() / query_rows(): normalize_by_length below as a column mode (acx_query_spec: s / sqrt(T_c))."""
+        return 1, np.sqrt(self._pooled_lengths().astype(np.float64))
+
     def similarity(self, idxs):
         idxs = np.asarray(idxs).reshape(-1, 2)
         if len(idxs) == 0:

@@ -27,6 +27,7 @@ class Simple(CoverAlgorithm):
     SSLEN: subsequence length; WIN / SKIP: window and hop of the dimensionality reduction.
     """
     n_chunks = 1
+    _identify_symmetric = False      # identify(): benchmark() runs all_pairwise(symmetric=False), row q = the ordered pairs (q, c)
 
     def __init__(self, dataset_csv, datapath, chroma_type='hpcp', shortname='Covers80',
                  SSLEN=10, WIN=200, SKIP=100, device=None, nonfinite="raise"):

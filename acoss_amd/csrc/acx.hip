@@ -29,6 +29,7 @@
 #include "ef_prep_kernels.hpp"
 #include "ftm2d_kernels.hpp"
 #include "rank_kernels.hpp"
+#include "query_kernels.hpp"
 #include "grid.hpp"
 
 using acx::PairDesc;
@@ -43,7 +44,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -127,6 +128,7 @@ struct acx_ctx {
     float *rank_d[2] = {nullptr, nullptr}; size_t rank_d_cap[2] = {0, 0};
     hipEvent_t rank_ev[2] = {nullptr, nullptr};
     bool rank_attr = false;
+    bool query_attr = false;                          // query_topk_kernel's dynamic LDS limit is raised (acx_query_topk)
     // multi-GPU inside the library (acx_comm_*): one RCCL communicator rank per context
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -172,7 +174,8 @@ struct acx_ctx {
                              {"csm_long_kernel", 0, 0, 0}, {"rowsel_long_kernel", 0, 0, 0}, {"qmax_bits_kernel", 0, 0, 0},
                              {"simple_kernel", 0, 0, 0}, {"ef_gemm_kernel", 0, 0, 0}, {"ef_rowstat_kernel", 0, 0, 0},
                              {"ef_fuse_kernel", 0, 0, 0}, {"sw_kernel", 0, 0, 0}, {"rank_columns_kernel", 0, 0, 0},
-                             {"topk_rows_kernel", 0, 0, 0}};
+                             {"topk_rows_kernel", 0, 0, 0}, {"ftm2d_tile_kernel", 0, 0, 0}, {"query_rows_kernel", 0, 0, 0},
+                             {"query_topk_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
 };
@@ -3530,6 +3533,331 @@ int acx_pair_grid(acx_ctx *c, const acx_grid_spec *spec, const void *params, flo
     (void)hipHostFree(h);
     if (grid_timing)
         fprintf(stderr, "[acx pair_grid] %d slice(s): device %.2f s, copy to the host %.2f s, scatter + mirror %.2f s\n", nslices, tg[0], tg[1], tg[2]);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------
+// Query bands: given queries against the uploaded collection, scores / top-k without an N x N matrix
+// ---------------------------------------------------------------------------------------
+// A band is R query rows x N columns x planes floats on the device (the slab, plane fastest), filled by the pair
+// kernels through a DevDst and finished by query_kernels.hpp.  A band's device memory -- slab plus its results -- takes
+// at most HALF of the scratch limit; while the pair kernels of a band run under a limit the caller set, they see what
+// is left of it.  R <= QUERY_BAND_ROWS: with EarlyFusion a band x 128 collection tracks is then one dense rectangle.
+static const int QUERY_BAND_ROWS = 128;
+
+struct QueryCall {
+    int algo = 0, w = 1, n = 0, symmetric = 0, mode = 0;
+    const void *params = nullptr;
+};
+
+// Everything both calls check of their common arguments, before anything is allocated or launched.
+static int query_check(acx_ctx *c, const char *who, const acx_query_spec *spec, const void *params, const int32_t *queries,
+                       int32_t n_queries, const int32_t *cands, int32_t n_cands, const double *col, QueryCall &Q)
+{
+    const std::string w(who);
+    if (!spec) return fail(c, ACX_ERR_INVALID, w + ": spec must not be NULL");
+    if (acx::grid_planes(spec->algo) <= 0) return fail(c, ACX_ERR_INVALID, w + ": spec.algo = " + std::to_string(spec->algo) + " is not an ACX_ALGO_* value");
+    if (spec->symmetric != 0 && spec->symmetric != 1) return fail(c, ACX_ERR_INVALID, w + ": spec.symmetric must be 0 or 1");
+    if (spec->col_mode < 0 || spec->col_mode > 2) return fail(c, ACX_ERR_INVALID, w + ": spec.col_mode must be 0, 1 or 2");
+    if (spec->reserved != 0) return fail(c, ACX_ERR_INVALID, w + ": spec.reserved must be 0");
+    if (!params && spec->algo != ACX_ALGO_FTM2D) return fail(c, ACX_ERR_INVALID, w + ": params must not be NULL for this algorithm");
+    std::vector<int64_t> len;
+    const int rc = pool_lengths(c, spec->algo, len);
+    if (rc != ACX_OK) return fail(c, rc, w + ": the pool of spec.algo is not uploaded (" + c->err + ")");
+    const int n = (int)len.size();
+    if (n_queries < 0) return fail(c, ACX_ERR_INVALID, w + ": n_queries must be >= 0 (got " + std::to_string(n_queries) + ")");
+    if (n_queries > 0 && !queries) return fail(c, ACX_ERR_INVALID, w + ": queries must not be NULL");
+    for (int32_t i = 0; i < n_queries; ++i)
+        if (queries[i] < 0 || queries[i] >= n)
+            return fail(c, ACX_ERR_INVALID, w + ": queries[" + std::to_string(i) + "] = " + std::to_string(queries[i]) + " is not a track in [0, " + std::to_string(n) + ")");
+    if (cands) {
+        if (n_cands < 0) return fail(c, ACX_ERR_INVALID, w + ": n_cands must be >= 0 (got " + std::to_string(n_cands) + ")");
+        for (int32_t j = 0; j < n_cands; ++j) {
+            if (cands[j] < 0 || cands[j] >= n)
+                return fail(c, ACX_ERR_INVALID, w + ": cands[" + std::to_string(j) + "] = " + std::to_string(cands[j]) + " is not a track in [0, " + std::to_string(n) + ")");
+            if (j > 0 && cands[j] <= cands[j - 1])
+                return fail(c, ACX_ERR_INVALID, w + ": cands must be strictly ascending (cands[" + std::to_string(j) + "])");
+        }
+    }
+    if (spec->col_mode == 0 && col) return fail(c, ACX_ERR_INVALID, w + ": col must be NULL when spec.col_mode is 0");
+    if (spec->col_mode != 0 && !col) return fail(c, ACX_ERR_INVALID, w + ": col must not be NULL when spec.col_mode is 1 or 2");
+    if (col)
+        for (int i = 0; i < n; ++i)
+            if (!std::isfinite(col[i])) return fail(c, ACX_ERR_INVALID, w + ": col[" + std::to_string(i) + "] is not finite");
+    Q.algo = spec->algo; Q.w = acx::grid_planes(spec->algo); Q.n = n; Q.symmetric = spec->symmetric; Q.mode = spec->col_mode;
+    Q.params = params;
+    return ACX_OK;
+}
+
+// Rows per band: `per_row` bytes of device memory per query row within half of the scratch limit.
+static int query_band_rows(acx_ctx *c, const char *who, int n_queries, int64_t per_row, int *rows)
+{
+    const int64_t half = scratch_limit_bytes(c) / 2;
+    if (half < per_row)
+        return fail(c, ACX_ERR_NOMEM, std::string(who) + ": one query row (" + std::to_string(per_row) + " bytes of scores and results) does not fit half of the scratch limit");
+    *rows = (int)std::min<int64_t>(std::min(n_queries, QUERY_BAND_ROWS), half / per_row);
+    return ACX_OK;
+}
+
+// The pairs of a band (queries q[0 .. nr) x the columns) and where their scores go in the slab.  Columns come in
+// blocks of 128, so that an EarlyFusion rectangle is one block x the band.  Pass 0: the cells computed as (query,
+// column) -- all of an ordered band, the columns above the query of a symmetric one --, column by column: neighbouring
+// pairs share their second track (what simple_kernel wants).  Pass 1 (symmetric): the cells computed as (column,
+// query), query by query.  A query's own column is left out.
+static void query_band_pairs(const int32_t *q, int nr, const int32_t *cols, int ncols, int n, int w, int symmetric,
+                             std::vector<int32_t> &pairs, std::vector<int64_t> &idx)
+{
+    pairs.clear(); idx.clear();
+    const int CB = 128;
+    for (int j0 = 0; j0 < ncols; j0 += CB) {
+        const int j1 = std::min(ncols, j0 + CB);
+        for (int j = j0; j < j1; ++j) {
+            const int col = cols ? cols[j] : j;
+            for (int r = 0; r < nr; ++r) {
+                if (col == q[r] || (symmetric && col < q[r])) continue;
+                pairs.push_back(q[r]); pairs.push_back(col);
+                idx.push_back(((int64_t)r * n + col) * w);
+            }
+        }
+        if (!symmetric) continue;
+        for (int r = 0; r < nr; ++r)
+            for (int j = j0; j < j1; ++j) {
+                const int col = cols ? cols[j] : j;
+                if (col >= q[r]) break;
+                pairs.push_back(col); pairs.push_back(q[r]);
+                idx.push_back(((int64_t)r * n + col) * w);
+            }
+    }
+}
+
+// SiMPle over a pair list whose scores stay on the device: simple_kernel as acx_simple_pairs launches it, then the
+// f64 -> f32 scatter of the grid path.
+static int run_simple_list(acx_ctx *c, const int32_t *pairs, const int64_t *idx, int64_t K, const acx_simple_params &sp, float *d_scores)
+{
+    const int sslen = sp.sslen;
+    if (sslen < 1 || sslen > acx::SIMPLE_MAXL) return fail(c, ACX_ERR_UNSUPPORTED, "simple: SSLEN must be in 1..16 on the device");
+    int maxn = 0;
+    for (int64_t k = 0; k < 2 * K; ++k) {
+        const int t = pairs[k];
+        const int n = (int)(c->h_off64[t + 1] - c->h_off64[t]);
+        if (n < sslen) return fail(c, ACX_ERR_SHORT, "simple: track " + std::to_string(t) + " is shorter than SSLEN");
+        if (n > acx::SIMPLE_MAXN) return fail(c, ACX_ERR_UNSUPPORTED, "simple: tracks with more than 6000 pooled frames are not supported on the device");
+        maxn = std::max(maxn, n);
+    }
+    const size_t smem = 64 + sizeof(double) * (2 * (size_t)maxn + (size_t)maxn / 48 + 4);
+    int rc = ensure_winnorm(c, sslen);
+    if (rc != ACX_OK) return rc;
+    const int64_t CHUNK = (int64_t)1 << 22;
+    if ((rc = ensure(c, c->d_pairs, c->pairs_cap, (size_t)2 * std::min(K, CHUNK))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_out64, c->out64_cap, (size_t)std::min(K, CHUNK))) != ACX_OK) return rc;
+    for (int64_t k0 = 0; k0 < K; k0 += CHUNK) {
+        const int n = (int)std::min(CHUNK, K - k0);
+        ACX_HIP(c, hipMemcpyAsync(c->d_pairs, pairs + 2 * k0, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
+        if ((rc = stage_idx(c, idx + k0, n)) != ACX_OK) return rc;
+        {
+            ProfScope ps(c, KS_SIMPLE, n);
+            switch (sslen) {
+#define ACX_L(L_) case L_: rc = launch_simple<L_>(c, n, smem, sp.oti); break;
+                ACX_L(1) ACX_L(2) ACX_L(3) ACX_L(4) ACX_L(5) ACX_L(6) ACX_L(7) ACX_L(8)
+                ACX_L(9) ACX_L(10) ACX_L(11) ACX_L(12) ACX_L(13) ACX_L(14) ACX_L(15) ACX_L(16)
+#undef ACX_L
+            }
+            if (rc != ACX_OK) return rc;
+        }
+        hipLaunchKernelGGL(scatter_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_out64, c->d_idx, d_scores, n);
+        ACX_LAUNCHES_OK(c);
+        ACX_HIP(c, hipStreamSynchronize(c->stream));      // (the pinned staging of the destinations is reused by the next chunk)
+    }
+    return ACX_OK;
+}
+
+// FTM2D: the band as tiles of the tile kernel -- per query row and run of consecutive columns, the columns above the
+// query as a 1 x cols tile (query, column); those below it as a rows x 1 tile (column, query) when symmetric, as a
+// second 1 x cols tile otherwise.  A tile's scores are rows x cols floats at its offset: both shapes fill the slab row.
+static int run_ftm2d_band(acx_ctx *c, const int32_t *q, int nr, const int32_t *cols, int ncols, int n, int symmetric, float *d_slab)
+{
+    std::vector<acx_grid_tile> tiles;
+    auto add = [&](int r, int a, int b) {             // columns [a, b) of slab row r, none of them the query
+        if (a >= b) return;
+        acx_grid_tile t;
+        t.rank = 0; t.diagonal = 0; t.cost = 0.0;
+        t.offset = (int64_t)r * n + a;
+        if (symmetric && b <= q[r]) { t.row0 = a; t.rows = b - a; t.col0 = q[r]; t.cols = 1; }
+        else { t.row0 = q[r]; t.rows = 1; t.col0 = a; t.cols = b - a; }
+        tiles.push_back(t);
+    };
+    for (int j0 = 0; j0 < ncols;) {
+        int j1 = j0 + 1;
+        const int a = cols ? cols[j0] : 0;
+        if (cols) { while (j1 < ncols && cols[j1] == cols[j1 - 1] + 1) ++j1; } else j1 = ncols;
+        const int b = a + (j1 - j0);
+        for (int r = 0; r < nr; ++r) {
+            add(r, a, std::min(b, q[r]));
+            add(r, std::max(a, q[r] + 1), b);
+        }
+        j0 = j1;
+    }
+    ProfScope ps(c, KS_FTMTILE, (int64_t)nr * ncols);
+    return run_ftm2d_tiles(c, tiles, symmetric, d_slab);
+}
+
+// One band through the pair kernels: on return every score of the band lies in d_slab (the runners wait for their
+// last batch; the SiMPle and FTM2D paths are drained here).
+static int query_run_band(acx_ctx *c, const QueryCall &Q, const int32_t *q, int nr, const int32_t *cols, int ncols, float *d_slab,
+                          int64_t band_bytes, std::vector<int32_t> &pairs, std::vector<int64_t> &idx)
+{
+    ACX_HIP(c, hipMemsetAsync(d_slab, 0, sizeof(float) * (size_t)nr * Q.n * Q.w, c->stream));
+    if (Q.algo == ACX_ALGO_FTM2D) {
+        const int rc = run_ftm2d_band(c, q, nr, cols, ncols, Q.n, Q.symmetric, d_slab);
+        if (rc != ACX_OK) return rc;
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        return ACX_OK;
+    }
+    query_band_pairs(q, nr, cols, ncols, Q.n, Q.w, Q.symmetric, pairs, idx);
+    const int64_t K = (int64_t)idx.size();
+    if (K == 0) { ACX_HIP(c, hipStreamSynchronize(c->stream)); return ACX_OK; }
+    if (Q.algo == ACX_ALGO_SIMPLE) return run_simple_list(c, pairs.data(), idx.data(), K, *static_cast<const acx_simple_params *>(Q.params), d_slab);
+    // a limit the caller set covers the band too: the pair kernels batch within what the band leaves of it
+    const int64_t saved = c->scratch_limit;
+    if (saved > 0) c->scratch_limit = std::max<int64_t>(1, saved - band_bytes);
+    DevDst dd{d_slab, idx.data()};
+    int rc;
+    if (Q.algo == ACX_ALGO_EARLYFUSION)
+        rc = run_ef(c, pairs.data(), K, *static_cast<const acx_ef_params *>(Q.params), nullptr, nullptr, nullptr, 0, 0, &dd);
+    else
+        rc = run_serra09(c, pairs.data(), K, *static_cast<const acx_serra09_params *>(Q.params), nullptr, nullptr,
+                         Q.algo == ACX_ALGO_CHENFUSION, &dd);
+    c->scratch_limit = saved;
+    if (rc != ACX_OK) return rc;
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
+}
+
+int acx_query_scores(acx_ctx *c, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
+                     const double *col, float *const *rows, int64_t ld)
+{
+    if (!c) return ACX_ERR_INVALID;
+    QueryCall Q;
+    int rc = query_check(c, "query_scores", spec, params, queries, n_queries, nullptr, 0, col, Q);
+    if (rc != ACX_OK) return rc;
+    if (!rows) return fail(c, ACX_ERR_INVALID, "query_scores: rows must not be NULL");
+    for (int e = 0; e < Q.w; ++e)
+        if (n_queries > 0 && !rows[e]) return fail(c, ACX_ERR_INVALID, "query_scores: rows[" + std::to_string(e) + "] must not be NULL");
+    if (ld < Q.n) return fail(c, ACX_ERR_INVALID, "query_scores: ld = " + std::to_string(ld) + " is smaller than the number of tracks " + std::to_string(Q.n));
+    if (n_queries == 0) return ACX_OK;
+    const int64_t per_row = 2 * (int64_t)Q.n * Q.w * 4;           // the slab row and its finished copy
+    int R = 0;
+    if ((rc = query_band_rows(c, "query_scores", n_queries, per_row, &R)) != ACX_OK) return rc;
+    ACX_HIP(c, hipSetDevice(c->device));
+    const size_t slab_floats = (size_t)R * Q.n * Q.w;
+    const size_t o_col = 2 * slab_floats * 4, o_q = o_col + (col ? 8 * (size_t)Q.n : 0), total = o_q + 4 * (size_t)n_queries;
+    char *d_mem = nullptr;
+    {
+        const hipError_t e = hipMalloc((void **)&d_mem, total);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, ACX_ERR_NOMEM, std::string("query_scores: ") + hipGetErrorString(e)); }
+    }
+    auto body = [&]() -> int {
+        float *d_slab = reinterpret_cast<float *>(d_mem), *d_fin = d_slab + slab_floats;
+        const double *d_col = col ? reinterpret_cast<const double *>(d_mem + o_col) : nullptr;
+        int32_t *d_q = reinterpret_cast<int32_t *>(d_mem + o_q);
+        if (col) ACX_HIP(c, hipMemcpyAsync(d_mem + o_col, col, 8 * (size_t)Q.n, hipMemcpyHostToDevice, c->stream));
+        ACX_HIP(c, hipMemcpyAsync(d_q, queries, 4 * (size_t)n_queries, hipMemcpyHostToDevice, c->stream));
+        std::vector<int32_t> pairs;
+        std::vector<int64_t> idx;
+        for (int r0 = 0; r0 < n_queries; r0 += R) {
+            const int nr = std::min(R, n_queries - r0);
+            int rcb = query_run_band(c, Q, queries + r0, nr, nullptr, Q.n, d_slab, (int64_t)R * per_row, pairs, idx);
+            if (rcb != ACX_OK) return rcb;
+            {
+                ProfScope ps(c, KS_QROWS, (int64_t)nr * Q.n * Q.w);
+                hipLaunchKernelGGL(acx::query_rows_kernel, dim3((unsigned)((Q.n + 255) / 256), (unsigned)nr, (unsigned)Q.w), dim3(256), 0, c->stream,
+                                   d_slab, Q.n, Q.w, nr, d_q + r0, d_col, Q.mode, d_fin);
+            }
+            ACX_LAUNCHES_OK(c);
+            for (int e = 0; e < Q.w; ++e)
+                ACX_HIP(c, hipMemcpy2DAsync(rows[e] + (size_t)r0 * ld, sizeof(float) * (size_t)ld, d_fin + (size_t)e * nr * Q.n, sizeof(float) * (size_t)Q.n,
+                                            sizeof(float) * (size_t)Q.n, (size_t)nr, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        return ACX_OK;
+    };
+    rc = body();
+    if (rc != ACX_OK) quiesce(c); else drain_profile(c);
+    (void)hipFree(d_mem);
+    return rc;
+}
+
+int acx_query_topk(acx_ctx *c, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
+                   const int32_t *cands, int32_t n_cands, const double *col, int32_t k, int32_t *out_idx, float *out_score)
+{
+    if (!c) return ACX_ERR_INVALID;
+    QueryCall Q;
+    int rc = query_check(c, "query_topk", spec, params, queries, n_queries, cands, n_cands, col, Q);
+    if (rc != ACX_OK) return rc;
+    if (k < 1) return fail(c, ACX_ERR_INVALID, "query_topk: k must be >= 1 (got " + std::to_string(k) + ")");
+    if (k > acx::RANK_KMAX)
+        return fail(c, ACX_ERR_UNSUPPORTED, "query_topk: k = " + std::to_string(k) + " is over the limit of " + std::to_string(acx::RANK_KMAX));
+    if (n_queries > 0 && (!out_idx || !out_score)) return fail(c, ACX_ERR_INVALID, "query_topk: out_idx and out_score must not be NULL");
+    if (n_queries == 0) return ACX_OK;
+    const int ncand = cands ? n_cands : Q.n;
+    const int64_t per_row = (int64_t)Q.n * Q.w * 4 + 8 * (int64_t)Q.w * k;      // the slab row and its results
+    int R = 0;
+    if ((rc = query_band_rows(c, "query_topk", n_queries, per_row, &R)) != ACX_OK) return rc;
+    ACX_HIP(c, hipSetDevice(c->device));
+    if (!c->query_attr) {
+        ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::query_topk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       4 * acx::RANK_ROW_LDS + 12 * acx::RANK_KMAX + acx::QUERY_LDS_FIXED));
+        c->query_attr = true;
+    }
+    int P = 4;
+    while (P < std::min<int>(k, ncand)) P <<= 1;
+    // slab | col | queries | cands | the band's results (indices, scores)
+    const size_t slab_floats = (size_t)R * Q.n * Q.w, res = (size_t)R * Q.w * k;
+    const size_t o_col = slab_floats * 4, o_q = o_col + (col ? 8 * (size_t)Q.n : 0), o_c = o_q + 4 * (size_t)n_queries,
+                 o_res = o_c + (cands ? 4 * (size_t)n_cands : 0), total = o_res + 8 * res;
+    char *d_mem = nullptr;
+    {
+        const hipError_t e = hipMalloc((void **)&d_mem, total);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, ACX_ERR_NOMEM, std::string("query_topk: ") + hipGetErrorString(e)); }
+    }
+    auto body = [&]() -> int {
+        float *d_slab = reinterpret_cast<float *>(d_mem);
+        const double *d_col = col ? reinterpret_cast<const double *>(d_mem + o_col) : nullptr;
+        int32_t *d_q = reinterpret_cast<int32_t *>(d_mem + o_q);
+        const int32_t *d_c = cands ? reinterpret_cast<const int32_t *>(d_mem + o_c) : nullptr;
+        int32_t *d_idx = reinterpret_cast<int32_t *>(d_mem + o_res);
+        float *d_sc = reinterpret_cast<float *>(d_idx + res);
+        if (col) ACX_HIP(c, hipMemcpyAsync(d_mem + o_col, col, 8 * (size_t)Q.n, hipMemcpyHostToDevice, c->stream));
+        ACX_HIP(c, hipMemcpyAsync(d_q, queries, 4 * (size_t)n_queries, hipMemcpyHostToDevice, c->stream));
+        if (cands && n_cands > 0) ACX_HIP(c, hipMemcpyAsync(d_mem + o_c, cands, 4 * (size_t)n_cands, hipMemcpyHostToDevice, c->stream));
+        const bool in_lds = ncand <= acx::RANK_ROW_LDS;
+        const size_t lds = 12 * (size_t)P + acx::QUERY_LDS_FIXED + (in_lds ? 4 * (size_t)ncand : 0);
+        std::vector<int32_t> pairs;
+        std::vector<int64_t> idx;
+        for (int r0 = 0; r0 < n_queries; r0 += R) {
+            const int nr = std::min(R, n_queries - r0);
+            int rcb = query_run_band(c, Q, queries + r0, nr, cands, ncand, d_slab, (int64_t)R * per_row, pairs, idx);
+            if (rcb != ACX_OK) return rcb;
+            {
+                ProfScope ps(c, KS_QTOPK, (int64_t)nr * ncand * Q.w);
+                if (in_lds)
+                    hipLaunchKernelGGL((acx::query_topk_kernel<true>), dim3((unsigned)nr, (unsigned)Q.w), dim3(acx::RANK_THREADS), lds, c->stream,
+                                       d_slab, Q.n, Q.w, d_q + r0, d_c, ncand, d_col, Q.mode, (int)k, P, d_idx, d_sc);
+                else
+                    hipLaunchKernelGGL((acx::query_topk_kernel<false>), dim3((unsigned)nr, (unsigned)Q.w), dim3(acx::RANK_THREADS), lds, c->stream,
+                                       d_slab, Q.n, Q.w, d_q + r0, d_c, ncand, d_col, Q.mode, (int)k, P, d_idx, d_sc);
+            }
+            ACX_LAUNCHES_OK(c);
+            const size_t nres = (size_t)nr * Q.w * k;
+            ACX_HIP(c, hipMemcpyAsync(out_idx + (size_t)r0 * Q.w * k, d_idx, 4 * nres, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(out_score + (size_t)r0 * Q.w * k, d_sc, 4 * nres, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        return ACX_OK;
+    };
+    rc = body();
+    if (rc != ACX_OK) quiesce(c); else drain_profile(c);
+    (void)hipFree(d_mem);
     return rc;
 }
 

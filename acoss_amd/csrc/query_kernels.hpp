@@ -1,0 +1,148 @@
+// Finish of a query band (acx_query_scores / acx_query_topk, include/acx.h): from the band's score slab to finished rows
+// or ranked candidate lists without leaving the device.
+//
+// The slab is what the pair kernels' scatter left behind: R rows (the band's queries) x N columns (every track of the
+// pool) x W planes, plane fastest -- slab[(r N + c) W + e] = score plane e of the pair {query r, track c} in the
+// orientation the call selected.  A query's own cell is never computed (it holds 0 from the band's memset and is never
+// read as a score).
+//   value of a cell   col_mode 0: s    1: (float)((double)s / col[c])    2: -(float)(col[c] / (double)s)
+//                     one IEEE f64 division and one rounding to f32: the bits numpy's (D / norm).astype(float32) and
+//                     -(norm / D).astype(float32) produce (normalize_by_length of Serra09 / ChenFusion)
+//   Q1  query_rows_kernel   the finished rows, de-interleaved: out[e][r N + c], own cell 0
+//   Q2  query_topk_kernel   one workgroup per (row, plane): the first k candidates of the order of rank_kernels.hpp --
+//                           larger value first (-0.0 and +0.0 tie), ties by ascending track index, NaN after every
+//                           number -- by the same radix select over rank_key64(value, track) and the same bitonic sort
+//                           as topk_rows_kernel, so the order is that kernel's by construction.  The candidates are a
+//                           strictly ascending track list (or every track); the own track is skipped also when listed.
+//                           Up to RANK_ROW_LDS candidates keep their finished values in LDS (the slab is read once);
+//                           more are re-read -- and re-finished, the same operations on the same bits -- per pass.
+// Every store is a plain C++ store.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rank_kernels.hpp"
+
+namespace acx {
+
+__device__ __forceinline__ float query_value(float s, const double *__restrict__ col, int c, int mode)
+{
+    if (mode == 0) return s;
+    if (mode == 1) return (float)((double)s / col[c]);
+    return -(float)(col[c] / (double)s);
+}
+
+// Q1.  grid: (ceil(N / 256), R, W).  out: W planes of R x N floats.
+__global__ __launch_bounds__(256) void query_rows_kernel(const float *__restrict__ slab, int N, int W, int R,
+                                                         const int32_t *__restrict__ self_of, const double *__restrict__ col,
+                                                         int mode, float *__restrict__ out)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, e = blockIdx.z;
+    if (c >= N) return;
+    const float s = slab[((int64_t)r * N + c) * W + e];
+    out[((int64_t)e * R + r) * N + c] = c == self_of[r] ? 0.0f : query_value(s, col, c, mode);
+}
+
+// Q2.  grid: (R, W).  cands: ncand strictly ascending tracks, or NULL (candidate j is track j, ncand = N).
+// out_idx / out_score: R x W x k.  P = the power of two >= max(4, min(k, ncand)) (<= RANK_KMAX): slots of the LDS sort.
+// Dynamic LDS: 12 P bytes (keys, tracks) + QUERY_LDS_FIXED (histogram, scan, three counters) + IN_LDS ? 4 ncand : 0.
+constexpr int QUERY_LDS_FIXED = 4 * (256 + 256 + 4);
+template <bool IN_LDS>
+__global__ __launch_bounds__(RANK_THREADS) void query_topk_kernel(const float *__restrict__ slab, int N, int W,
+                                                                   const int32_t *__restrict__ self_of,
+                                                                   const int32_t *__restrict__ cands, int ncand,
+                                                                   const double *__restrict__ col, int mode, int k, int P,
+                                                                   int32_t *__restrict__ out_idx, float *__restrict__ out_score)
+{
+    // (all LDS in the dynamic region: static variables in front of it would move its base off 16 bytes and the 64-bit
+    //  key accesses off their natural alignment)
+    extern __shared__ float4 rank_lds4[];
+    uint64_t *skey = reinterpret_cast<uint64_t *>(rank_lds4);
+    int32_t *scol = reinterpret_cast<int32_t *>(skey + P);
+    int *hist = reinterpret_cast<int *>(scol + P), *scan = hist + 256;
+    int &sel_digit = scan[256], &sel_below = scan[257], &n_taken = scan[258];
+    float *lrow = reinterpret_cast<float *>(scan + 260);
+    const int r = blockIdx.x, e = blockIdx.y, tid = threadIdx.x;
+    const float *row = slab + (int64_t)r * N * W + e;
+    const int self = self_of[r];
+    auto track_of = [&](int j) { return cands ? cands[j] : j; };
+    auto value_of = [&](int c) { return query_value(row[(int64_t)c * W], col, c, mode); };
+    int mine_self = 0;
+    for (int j = tid; j < ncand; j += RANK_THREADS) {
+        const int c = track_of(j);
+        if (c == self) { mine_self = 1; continue; }
+        if (IN_LDS) lrow[j] = value_of(c);
+    }
+    for (int s = tid; s < P; s += RANK_THREADS) { skey[s] = ~0ull; scol[s] = -1; }
+    if (tid == 0) n_taken = 0;
+    const int nvalid = ncand - (__syncthreads_or(mine_self) ? 1 : 0);       // candidates there are to list
+    const int kk = min(k, nvalid);
+    auto key_of = [&](int j, int c) { return rank_key64(IN_LDS ? lrow[j] : value_of(c), (uint32_t)c); };
+    // the kk-th smallest key (1-based) among the candidates: most significant byte first
+    uint64_t prefix = 0, mask = 0;
+    if (kk > 0 && kk < nvalid) {
+        int want = kk;
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            hist[tid] = 0;
+            __syncthreads();
+            for (int j = tid; j < ncand; j += RANK_THREADS) {
+                const int c = track_of(j);
+                if (c == self) continue;
+                const uint64_t key = key_of(j, c);
+                if ((key & mask) == prefix) atomicAdd(&hist[(int)((key >> shift) & 255)], 1);
+            }
+            __syncthreads();
+            const int mine = hist[tid];
+            int x = mine;                             // inclusive scan over the 256 bins
+            for (int o = 1; o < 256; o <<= 1) {
+                scan[tid] = x;
+                __syncthreads();
+                if (tid >= o) x += scan[tid - o];
+                __syncthreads();
+            }
+            if (x - mine < want && want <= x) { sel_digit = tid; sel_below = x - mine; }
+            __syncthreads();
+            prefix |= (uint64_t)sel_digit << shift;
+            mask |= (uint64_t)255 << shift;
+            want -= sel_below;
+            __syncthreads();
+        }
+    } else {
+        prefix = ~0ull;                               // everything (kk == nvalid); kk == 0 takes nothing below
+    }
+    if (kk > 0) {
+        for (int j = tid; j < ncand; j += RANK_THREADS) {
+            const int c = track_of(j);
+            if (c == self) continue;
+            const uint64_t key = key_of(j, c);
+            if (key <= prefix) {
+                const int s = atomicAdd(&n_taken, 1);
+                if (s < P) { skey[s] = key; scol[s] = c; }        // (the keys are distinct: exactly kk <= P are taken)
+            }
+        }
+    }
+    __syncthreads();
+    // bitonic sort of the P slots, ascending by key (unused slots hold ~0: last)
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < (P >> 1); t += RANK_THREADS) {
+                const int lo = ((t / stride) * stride << 1) + (t % stride), hi = lo + stride;
+                const bool up = (lo & size) == 0;
+                const uint64_t a = skey[lo], b = skey[hi];
+                if ((a > b) == up) {
+                    skey[lo] = b; skey[hi] = a;
+                    const int32_t ca = scol[lo]; scol[lo] = scol[hi]; scol[hi] = ca;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const int64_t o = ((int64_t)r * W + e) * k;
+    for (int p = tid; p < k; p += RANK_THREADS) {
+        const int c = p < P ? scol[p] : -1;
+        out_idx[o + p] = c;
+        out_score[o + p] = c >= 0 ? value_of(c) : __builtin_nanf("");
+    }
+}
+
+}  // namespace acx

@@ -585,6 +585,52 @@ int acx_rank_columns(acx_ctx *ctx, const float *scores, int64_t ld, int32_t n, i
 int acx_topk_rows(acx_ctx *ctx, const float *scores, int64_t ld, int32_t n, int32_t n_rows, const int32_t *self,
                   const int32_t *posn, int32_t k, int32_t *out_idx, float *out_score);
 
+/* ---- queries against the uploaded collection: scores and top-k without N x N */
+
+/*
+ * The question a cover-song identification engine is asked: given these Q tracks, which k tracks of the collection are
+ * their covers?  Queries and candidates are INDICES into the pool that is already uploaded (the collection and the
+ * queries are uploaded together); duplicate queries are allowed.  The queries run in BANDS of up to 128 rows: a band's
+ * pairs go through the same pair kernels as acx_*_pairs / acx_grid_run, its scores stay on the device (band rows x
+ * n_tracks x planes floats), are normalised and ranked there, and only the results come back.
+ *
+ *   raw score   of the cell (query q, track c): bit for bit what acx_serra09_pairs / acx_chenfusion_pairs /
+ *               acx_simple_pairs (rounded to f32, as Ds['main'] stores it) / acx_earlyfusion_pairs / acx_ftm2d_pairs
+ *               return for that pair in the orientation `symmetric` selects.  Planes as in acx_grid_spec.
+ *   col_mode    applied once per cell with an IEEE f64 division and ONE rounding to f32 -- the bits of the classes'
+ *               normalize_by_length (rqa_serra09.py:71-83: mode 1 with col = sqrt(T_c); latefusion_chen.py:75-85 and the
+ *               later `*= -1` of do_late_fusion :90: mode 2)
+ *   own column  a query's own column takes no part and is never computed: its cell is 0 in acx_query_scores; acx_query_topk
+ *               skips it, also when `cands` lists it
+ *   order       the one of acx_topk_rows with posn == NULL: larger score first, -0.0 and +0.0 tie; ties in ascending track
+ *               index; -inf is an ordinary value; NaN comes after every number.  Fewer than k candidates: the tail is
+ *               index -1, score NaN.  k <= 1024; beyond: ACX_ERR_UNSUPPORTED
+ *   memory      a band (its scores plus its results) takes at most HALF of acx_set_scratch_limit, the pair kernels of the
+ *               band what is left of a limit the caller set; one row that does not fit: ACX_ERR_NOMEM
+ *   errors      the whole argument list is validated before the first launch -- spec (algo, symmetric, col_mode,
+ *               reserved == 0), params (NULL only for FTM2D), the pool of spec->algo present (else ACX_ERR_STATE), every
+ *               query and candidate a track in [0, n_tracks), `cands` strictly ascending, col present iff col_mode != 0
+ *               and finite, k -- and the message names the argument; a failed call leaves nothing in flight
+ * params: per algorithm exactly as for acx_grid_run (FTM2D: NULL).
+ */
+typedef struct {
+    int32_t algo;       /* ACX_ALGO_* */
+    int32_t symmetric;  /* 1: the pair {q, c} is computed as (min(q, c), max(q, c)), the cell all_pairwise(symmetric=True)
+                              computes and mirrors.  0: as (q, c), row q of an ordered grid (SiMPle) */
+    int32_t col_mode;   /* 0: s   1: (float)((double)s / col[c])   2: -(float)(col[c] / (double)s)   (s = 0 -> -inf) */
+    int32_t reserved;   /* 0 */
+} acx_query_spec;
+
+/* The finished rows in full: rows[e][i * ld + c] = plane e of (queries[i], track c); planes of n_queries x ld host floats,
+ * ld >= n_tracks.  col: n_tracks values, NULL iff col_mode == 0. */
+int acx_query_scores(acx_ctx *ctx, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
+                     const double *col, float *const *rows, int64_t ld);
+
+/* The k first candidates of every query and plane: out_idx / out_score are n_queries x planes x k.  cands: n_cands strictly
+ * ascending track indices, or NULL: every track (n_cands is ignored).  Only the candidates' columns are computed. */
+int acx_query_topk(acx_ctx *ctx, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
+                   const int32_t *cands, int32_t n_cands, const double *col, int32_t k, int32_t *out_idx, float *out_score);
+
 /* ---- multi-GPU inside the library: RCCL over xGMI, no Python ------------- */
 
 /*
