@@ -36,7 +36,7 @@ EXPORTS = [
     "acx_ftm2d_default_params", "acx_ftm2d_pool_begin", "acx_ftm2d_pool_tracks", "acx_ftm2d_pool_end",
     "acx_ftm2d_upload_shingles", "acx_ftm2d_download_shingles", "acx_ftm2d_debug_track", "acx_ftm2d_pairs",
     "acx_rank_columns", "acx_topk_rows",
-    "acx_query_scores", "acx_query_topk",
+    "acx_query_scores", "acx_query_topk", "acx_query_ranks",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -262,6 +262,7 @@ def load():
     qp = ctypes.POINTER(QuerySpec)
     L.acx_query_scores.argtypes = [vp, qp, vp, ip, ctypes.c_int32, dp, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64]
     L.acx_query_topk.argtypes = [vp, qp, vp, ip, ctypes.c_int32, ip, ctypes.c_int32, dp, ctypes.c_int32, ip, fp]
+    L.acx_query_ranks.argtypes = [vp, qp, vp, ip, ctypes.c_int32, dp, ip, lp, ip, ip, ctypes.POINTER(ctypes.c_uint8)]
     _check_hip_version(L)
     _lib = L
     return L
@@ -996,6 +997,33 @@ class Context(object):
                                            cptr, 0 if cands is None else len(cands), None if col is None else _dptr(col), k,
                                            _iptr(idx), _fptr(score)))
         return idx, score
+
+    def query_ranks(self, algo, symmetric, params, queries, moff, mates, posn=None, col=None, col_mode=0):
+        """acx_query_ranks: (pos (planes, M) int32, flag (Q, planes) uint8), M = moff[-1] -- for every plane, the 1-based
+        positions of the tracks mates[moff[i] : moff[i + 1]] in the finished row of queries[i] (scores as in query_scores,
+        every track of the pool a column, the query's own left out): larger score first, ties by posn (None: the track
+        index).  A (query, plane) with NaN / -inf outside the own column has flag 1 and positions -1.  Counted on the
+        device; only the integers come back."""
+        spec, queries, col = self._query_args(algo, symmetric, queries, col, col_mode)
+        w = GRID_PLANES[int(algo)]
+        moff = np.ascontiguousarray(moff, dtype=np.int64).reshape(-1)
+        mates = np.ascontiguousarray(mates, dtype=np.int32).reshape(-1)
+        if len(moff) != len(queries) + 1:
+            raise ValueError("query_ranks: moff must hold len(queries) + 1 offsets")
+        if moff[-1] != len(mates):
+            raise ValueError("query_ranks: moff[-1] must be len(mates)")
+        if posn is not None:
+            posn = np.ascontiguousarray(posn, dtype=np.int32).reshape(-1)
+            n = len(self.pool_lengths(algo))
+            if len(posn) != n:
+                raise ValueError("query_ranks: posn must have one entry per track (%d), got %d" % (n, len(posn)))
+        pos = np.full((w, len(mates)), -1, np.int32)
+        flag = np.zeros((len(queries), w), np.uint8)
+        self._check(self._L.acx_query_ranks(self._h, ctypes.byref(spec), _params_ptr(params), _iptr(queries), len(queries),
+                                            None if col is None else _dptr(col), None if posn is None else _iptr(posn),
+                                            _lptr(moff), _iptr(mates), _iptr(pos),
+                                            flag.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        return pos, flag
 
     def profile_enable(self, on=True):
         self._check(self._L.acx_profile_enable(self._h, int(bool(on))))

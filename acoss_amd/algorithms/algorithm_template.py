@@ -351,6 +351,45 @@ class CoverAlgorithm(object):
         planes = list(self._identify_planes)
         return {t: rows[planes.index(t)] for t in types}
 
+    def evaluate(self, queries=None, similarity_types=None, topsidx=[1, 10, 100, 1000], report=False, info=None, row_block=1024):
+        """MR, MRR, MDR, MAP and Top-k of a query set against the collection without an N x N matrix:
+        {type: (MR, MRR, MDR, MAP, tops)} for the similarity types the device computes (similarity_types: a subset,
+        None: all).  Values and orientation are identify()'s -- coverid.benchmark()'s sequence for the class, ChenFusion
+        with its sign flip --, the tie order is getEvalStatistics': the clique-contiguous layout of rank_plan.  Only the
+        rows of the queries that have a clique mate are computed, in bands (acx_query_ranks): the scores stay on the
+        device, are normalised there, and the positions of every query's clique mates are counted there; only those
+        integers come back.  `Ds` is not written.
+        queries: distinct track indices in any order (duplicates: ValueError), None: every track -- then the result is
+        all_pairwise(symmetric=...) + normalize_by_length() + getEvalStatistics(type, engine="device") bit for bit.
+        With a subset MR, MDR, MAP and Top-k run over the queries that have at least one clique mate and MRR divides by
+        the number of queries given (the reference's division by all songs, applied to the subset).  The cliques are
+        `self.cliques`: every track must be labelled.  A (query, type) whose finished row holds NaN or -inf outside its
+        own cell is ranked on the host by the sorting branch from query_rows(), a block of rows at a time.
+        info: a dict that receives {type: {"device_rows", "host_rows"}}.  report=True prints and appends the lines
+        getEvalStatistics writes.  Fused types need the whole matrix: NotImplementedError.  Not a collective: under a
+        process group every rank that calls it computes on its own GPU."""
+        q, types = self._query_setup("evaluate", np.arange(self.N) if queries is None else queries, similarity_types)
+        if len(np.unique(q)) != len(q):
+            raise ValueError("evaluate: queries must be distinct track indices")
+        if not self.cliques and _dist.single():
+            self.get_all_clique_ids()
+        plan = evaluate_plan([sorted(self.cliques[s]) for s in self.cliques], self.N, None if queries is None else q)
+        ctx, algo, params, mode, col = self._query_call()
+        pos, flag = ctx.query_ranks(algo, self._identify_symmetric, params, plan["rows"], plan["moff"], plan["mates"],
+                                    posn=plan["posn"], col=col, col_mode=mode)
+        planes = list(self._identify_planes)
+        out = {}
+        for t in types:
+            e = planes.index(t)
+            inf = {}
+            out[t] = _statistics_from_positions(None, plan, pos[e], flag[:, e], topsidx, row_block, inf,
+                                                rows_of=lambda tracks, t=t: self.query_rows(tracks, [t])[t])
+            if info is not None:
+                info[t] = inf
+            if report:
+                self._report_statistics(t, topsidx, *out[t])
+        return out
+
     def cleanup_memmap(self):
         """Remove the memmap files behind the similarity matrices."""
         for s in list(self.Ds.keys()):
@@ -408,6 +447,12 @@ class CoverAlgorithm(object):
         MR, MRR, MDR, MAP, tops = _dist.on_root(evaluate)
         if rank != 0:
             return MR, MRR, MDR, MAP, tops
+        self._report_statistics(similarity_type, topsidx, MR, MRR, MDR, MAP, tops)
+        return MR, MRR, MDR, MAP, tops
+
+    def _report_statistics(self, similarity_type, topsidx, MR, MRR, MDR, MAP, tops):
+        """The reference's report of one tuple (:270-290): the printed block and one line appended to
+        results_<shortname>_<name>.csv (the header first when the file is new)."""
         print("%s %s STATS\n-------------------------\nMR = %.3g\nMRR = %.3g\nMDR = %.3g\nMAP = %.3g"
               % (self.name, similarity_type, MR, MRR, MDR, MAP))
         for t, v in zip(topsidx, tops):
@@ -425,7 +470,6 @@ class CoverAlgorithm(object):
             for t in tops:
                 fout.write(", %.3g" % t)
             fout.write("\n")
-        return MR, MRR, MDR, MAP, tops
 
 
 def _clique_order(cliques):
@@ -526,13 +570,55 @@ def rank_plan(cliques, N):
     return dict(idx=idx, Ks=Ks, n_eval=n_eval, posn=posn, rows=rows, moff=moff, mates=mates, where=where)
 
 
-def _statistics_from_positions(D, plan, pos, flag, topsidx, row_block, info=None):
-    """The statistics from the integer positions acx_rank_columns returned for `plan` (rank_plan): block by block in clique
-    order, exactly the host's counting branch with the production of `pos` replaced (same blocks, same padded width, same
-    tail: numpy's row sums group their terms by that width).  Rows the device flagged (NaN / -inf) are ranked here by
-    the sorting branch -- the reference's reading of such a row."""
+def evaluate_plan(cliques, N, queries=None):
+    """rank_plan for a query set (CoverAlgorithm.evaluate): the same clique layout and tie order, but only the queries
+    that have a clique mate are rows -- in clique order --, and no row is there only to keep a span whole.
+    queries: distinct track indices, None: every track.  The dict of rank_plan, plus
+      ev     (E,) int64   the places (in clique order, ascending) of the queries that are evaluated; rows = idx[ev]
+      n_mrr  the number MRR divides by: the queries given (N for None)
+    `where` stays indexed by place: rows outside `ev` list nothing."""
+    base = rank_plan(cliques, N)
+    idx, Ks, n_eval, posn = base["idx"], base["Ks"], base["n_eval"], base["posn"]
+    if queries is None:
+        ev = np.arange(n_eval, dtype=np.int64)
+        n_mrr = N
+    else:
+        queries = np.asarray(queries, dtype=np.int64).reshape(-1)
+        if len(np.unique(queries)) != len(queries):
+            raise ValueError("evaluate: queries must be distinct track indices")
+        if len(queries) and (queries.min() < 0 or queries.max() >= N):
+            raise ValueError("evaluate: queries must be track indices in [0, %d)" % N)
+        place = np.sort(posn[queries].astype(np.int64))
+        ev = place[place < n_eval]
+        n_mrr = len(queries)
+    starts = np.concatenate([[0], np.cumsum(Ks)])[:-1]
+    row_start = np.repeat(starts, Ks)[ev]
+    K = np.repeat(Ks, Ks)[ev]
+    nmate = K - 1
+    moff = np.concatenate([[0], np.cumsum(nmate)]).astype(np.int64)
+    within = np.arange(int(K.sum())) - np.repeat(np.cumsum(K) - K, K)
+    members = np.repeat(row_start, K) + within
+    mates = idx[members[members != np.repeat(ev, K)]].astype(np.int32)
+    where = np.zeros((n_eval, 2), np.int64)
+    where[ev, 0] = moff[:-1]
+    where[ev, 1] = nmate
+    return dict(idx=idx, Ks=Ks, n_eval=n_eval, posn=posn, rows=idx[ev].astype(np.int32), moff=moff, mates=mates, where=where,
+                ev=ev, n_mrr=int(n_mrr))
+
+
+def _statistics_from_positions(D, plan, pos, flag, topsidx, row_block, info=None, rows_of=None):
+    """The statistics from the integer positions acx_rank_columns / acx_query_ranks returned for `plan` (rank_plan,
+    evaluate_plan): block by block in clique order, exactly the host's counting branch with the production of `pos`
+    replaced (same blocks, same padded width, same tail: numpy's row sums group their terms by that width).  Rows the
+    device flagged (NaN / -inf) are ranked here by the sorting branch -- the reference's reading of such a row; their
+    score rows come from rows_of(tracks) -> (len(tracks), N) (None: the rows of the matrix D).
+    A plan with "ev" evaluates those places only (ascending, in clique order) and MRR divides by its "n_mrr"."""
     idx, Ks, n_eval, where = plan["idx"], plan["Ks"], plan["n_eval"], plan["where"]
     N = len(idx)
+    ev = plan["ev"] if "ev" in plan else np.arange(n_eval)
+    if rows_of is None:
+        def rows_of(tracks):
+            return np.asarray(D)[tracks]
     starts = np.concatenate([[0], np.cumsum(Ks)])[:-1]
     row_start = np.repeat(starts, Ks)
     row_K = np.repeat(Ks, Ks)
@@ -540,28 +626,28 @@ def _statistics_from_positions(D, plan, pos, flag, topsidx, row_block, info=None
     allmap = np.full(N, np.nan)
     flag_of_track = np.zeros(N, bool)
     flag_of_track[plan["rows"]] = flag.astype(bool)
-    flagged = flag_of_track[idx[:n_eval]]                   # in clique order
-    for r0 in range(0, n_eval, row_block):
-        r1 = min(n_eval, r0 + row_block)
-        Kb = row_K[r0:r1]
+    flagged = flag_of_track[idx[ev]]                        # in clique order
+    for r0 in range(0, len(ev), row_block):
+        pl = ev[r0:r0 + row_block]
+        Kb = row_K[pl]
         kmax = int(Kb.max())
-        P = np.full((r1 - r0, kmax), np.inf)
+        P = np.full((len(pl), kmax), np.inf)
         cols = np.arange(kmax - 1)[None, :]
-        have = cols < where[r0:r1, 1][:, None]
-        src = where[r0:r1, 0][:, None] + cols
+        have = cols < where[pl, 1][:, None]
+        src = where[pl, 0][:, None] + cols
         P[:, :kmax - 1][have] = pos[src[have]]
-        P[flagged[r0:r1]] = np.inf
-        ranks[r0:r1], allmap[r0:r1] = _finish_counted(P, Kb)
-    host_rows = np.nonzero(flagged)[0]
+        P[flagged[r0:r0 + row_block]] = np.inf
+        ranks[pl], allmap[pl] = _finish_counted(P, Kb)
+    host_rows = ev[flagged]
     for a in range(0, len(host_rows), row_block):
         hr = host_rows[a:a + row_block]
-        Db = np.array(np.asarray(D)[idx[hr]][:, idx], dtype=np.float32)
+        Db = np.array(np.asarray(rows_of(idx[hr]))[:, idx], dtype=np.float32)
         Db[np.arange(len(hr)), hr] = -np.inf
         ranks[hr], allmap[hr] = _rank_sorted(Db, row_start[hr], row_K[hr])
     if info is not None:
-        info["device_rows"] = int(n_eval - len(host_rows))
+        info["device_rows"] = int(len(ev) - len(host_rows))
         info["host_rows"] = int(len(host_rows))
-    return _finish_statistics(ranks, allmap, N, n_eval, topsidx)
+    return _finish_statistics(ranks, allmap, plan.get("n_mrr", N), len(ev), topsidx)
 
 
 def eval_statistics_device(D, cliques, topsidx=(1, 10, 100, 1000), ctx=None, info=None, row_block=1024):

@@ -44,7 +44,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -129,6 +129,7 @@ struct acx_ctx {
     hipEvent_t rank_ev[2] = {nullptr, nullptr};
     bool rank_attr = false;
     bool query_attr = false;                          // query_topk_kernel's dynamic LDS limit is raised (acx_query_topk)
+    bool query_rank_attr = false;                     // query_rank_kernel's (acx_query_ranks)
     // multi-GPU inside the library (acx_comm_*): one RCCL communicator rank per context
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -175,7 +176,7 @@ struct acx_ctx {
                              {"simple_kernel", 0, 0, 0}, {"ef_gemm_kernel", 0, 0, 0}, {"ef_rowstat_kernel", 0, 0, 0},
                              {"ef_fuse_kernel", 0, 0, 0}, {"sw_kernel", 0, 0, 0}, {"rank_columns_kernel", 0, 0, 0},
                              {"topk_rows_kernel", 0, 0, 0}, {"ftm2d_tile_kernel", 0, 0, 0}, {"query_rows_kernel", 0, 0, 0},
-                             {"query_topk_kernel", 0, 0, 0}};
+                             {"query_topk_kernel", 0, 0, 0}, {"query_rank_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
 };
@@ -3851,6 +3852,112 @@ int acx_query_topk(acx_ctx *c, const acx_query_spec *spec, const void *params, c
             const size_t nres = (size_t)nr * Q.w * k;
             ACX_HIP(c, hipMemcpyAsync(out_idx + (size_t)r0 * Q.w * k, d_idx, 4 * nres, hipMemcpyDeviceToHost, c->stream));
             ACX_HIP(c, hipMemcpyAsync(out_score + (size_t)r0 * Q.w * k, d_sc, 4 * nres, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        return ACX_OK;
+    };
+    rc = body();
+    if (rc != ACX_OK) quiesce(c); else drain_profile(c);
+    (void)hipFree(d_mem);
+    return rc;
+}
+
+int acx_query_ranks(acx_ctx *c, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
+                    const double *col, const int32_t *posn, const int64_t *moff, const int32_t *mates, int32_t *out_pos,
+                    uint8_t *out_flag)
+{
+    if (!c) return ACX_ERR_INVALID;
+    QueryCall Q;
+    int rc = query_check(c, "query_ranks", spec, params, queries, n_queries, nullptr, 0, col, Q);
+    if (rc != ACX_OK) return rc;
+    if (!moff) return fail(c, ACX_ERR_INVALID, "query_ranks: moff must not be NULL");
+    if (moff[0] != 0) return fail(c, ACX_ERR_INVALID, "query_ranks: moff[0] must be 0");
+    int64_t maxm = 0;
+    for (int32_t r = 0; r < n_queries; ++r) {
+        if (moff[r + 1] < moff[r]) return fail(c, ACX_ERR_INVALID, "query_ranks: moff must be non-decreasing (moff[" + std::to_string(r + 1) + "])");
+        maxm = std::max(maxm, moff[r + 1] - moff[r]);
+    }
+    const int64_t M = moff[n_queries];
+    if (n_queries > 0 && !out_flag) return fail(c, ACX_ERR_INVALID, "query_ranks: out_flag must not be NULL");
+    if (M > 0 && (!mates || !out_pos)) return fail(c, ACX_ERR_INVALID, "query_ranks: mates and out_pos must not be NULL");
+    for (int32_t r = 0; r < n_queries; ++r)
+        for (int64_t j = moff[r]; j < moff[r + 1]; ++j) {
+            if (mates[j] < 0 || mates[j] >= Q.n)
+                return fail(c, ACX_ERR_INVALID, "query_ranks: mates[" + std::to_string(j) + "] = " + std::to_string(mates[j]) + " is not a track in [0, " + std::to_string(Q.n) + ")");
+            if (mates[j] == queries[r])
+                return fail(c, ACX_ERR_INVALID, "query_ranks: mates[" + std::to_string(j) + "] is queries[" + std::to_string(r) + "] itself");
+        }
+    if (posn) {
+        std::vector<std::pair<int32_t, int32_t>> seen((size_t)Q.n);
+        for (int i = 0; i < Q.n; ++i) {
+            if (posn[i] < 0) return fail(c, ACX_ERR_INVALID, "query_ranks: posn[" + std::to_string(i) + "] = " + std::to_string(posn[i]) + " is negative");
+            seen[i] = {posn[i], i};
+        }
+        std::sort(seen.begin(), seen.end());
+        for (int i = 1; i < Q.n; ++i)
+            if (seen[i].first == seen[i - 1].first)
+                return fail(c, ACX_ERR_INVALID, "query_ranks: posn must hold distinct tie ranks (posn[" + std::to_string(seen[i].second) + "] = posn[" +
+                                                    std::to_string(seen[i - 1].second) + "] = " + std::to_string(seen[i].first) + ")");
+    }
+    if (n_queries == 0) return ACX_OK;
+    // the slab row and its results: every row is charged the longest mate list of the call (positions and flags per plane)
+    const int64_t per_row = (int64_t)Q.n * Q.w * 4 + (int64_t)Q.w * (4 * maxm + 1);
+    int R = 0;
+    if ((rc = query_band_rows(c, "query_ranks", n_queries, per_row, &R)) != ACX_OK) return rc;
+    ACX_HIP(c, hipSetDevice(c->device));
+    if (!c->query_rank_attr) {
+        ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::query_rank_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       4 * acx::RANK_ROW_LDS + acx::QUERY_RANK_LDS_FIXED));
+        c->query_rank_attr = true;
+    }
+    int64_t band_m = 0;                                // the most positions one band returns per plane
+    for (int r0 = 0; r0 < n_queries; r0 += R) band_m = std::max(band_m, moff[std::min(n_queries, r0 + R)] - moff[r0]);
+    // slab | moff | col | queries | mates | posn | the band's positions (plane by plane) | its flags
+    const size_t slab_floats = (size_t)R * Q.n * Q.w;
+    const size_t o_moff = (slab_floats * 4 + 7) & ~(size_t)7, o_col = o_moff + 8 * (size_t)(n_queries + 1), o_q = o_col + (col ? 8 * (size_t)Q.n : 0),
+                 o_m = o_q + 4 * (size_t)n_queries, o_posn = o_m + 4 * (size_t)M, o_pos = o_posn + (posn ? 4 * (size_t)Q.n : 0),
+                 o_flag = o_pos + 4 * (size_t)Q.w * (size_t)band_m, total = o_flag + (size_t)R * Q.w;
+    char *d_mem = nullptr;
+    {
+        const hipError_t e = hipMalloc((void **)&d_mem, total);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, ACX_ERR_NOMEM, std::string("query_ranks: ") + hipGetErrorString(e)); }
+    }
+    auto body = [&]() -> int {
+        float *d_slab = reinterpret_cast<float *>(d_mem);
+        const int64_t *d_moff = reinterpret_cast<const int64_t *>(d_mem + o_moff);
+        const double *d_col = col ? reinterpret_cast<const double *>(d_mem + o_col) : nullptr;
+        int32_t *d_q = reinterpret_cast<int32_t *>(d_mem + o_q);
+        const int32_t *d_mates = reinterpret_cast<const int32_t *>(d_mem + o_m);
+        const int32_t *d_posn = posn ? reinterpret_cast<const int32_t *>(d_mem + o_posn) : nullptr;
+        int32_t *d_pos = reinterpret_cast<int32_t *>(d_mem + o_pos);
+        uint8_t *d_flag = reinterpret_cast<uint8_t *>(d_mem + o_flag);
+        ACX_HIP(c, hipMemcpyAsync(d_mem + o_moff, moff, 8 * (size_t)(n_queries + 1), hipMemcpyHostToDevice, c->stream));
+        if (col) ACX_HIP(c, hipMemcpyAsync(d_mem + o_col, col, 8 * (size_t)Q.n, hipMemcpyHostToDevice, c->stream));
+        ACX_HIP(c, hipMemcpyAsync(d_q, queries, 4 * (size_t)n_queries, hipMemcpyHostToDevice, c->stream));
+        if (M > 0) ACX_HIP(c, hipMemcpyAsync(d_mem + o_m, mates, 4 * (size_t)M, hipMemcpyHostToDevice, c->stream));
+        if (posn) ACX_HIP(c, hipMemcpyAsync(d_mem + o_posn, posn, 4 * (size_t)Q.n, hipMemcpyHostToDevice, c->stream));
+        const bool in_lds = Q.n <= acx::RANK_ROW_LDS;
+        const size_t lds = acx::QUERY_RANK_LDS_FIXED + (in_lds ? 16 * (size_t)((Q.n + 3) / 4) : 0);
+        std::vector<int32_t> pairs;
+        std::vector<int64_t> idx;
+        for (int r0 = 0; r0 < n_queries; r0 += R) {
+            const int nr = std::min(R, n_queries - r0);
+            int rcb = query_run_band(c, Q, queries + r0, nr, nullptr, Q.n, d_slab, (int64_t)R * per_row, pairs, idx);
+            if (rcb != ACX_OK) return rcb;
+            const int64_t mb = moff[r0 + nr] - moff[r0];       // this band's positions per plane
+            {
+                ProfScope ps(c, KS_QRANK, (int64_t)nr * Q.n * Q.w);
+                if (in_lds)
+                    hipLaunchKernelGGL((acx::query_rank_kernel<true>), dim3((unsigned)nr, (unsigned)Q.w), dim3(acx::RANK_THREADS), lds, c->stream,
+                                       d_slab, Q.n, Q.w, d_q + r0, d_col, Q.mode, d_posn, d_moff + r0, d_mates + moff[r0], moff[r0], mb, d_pos, d_flag);
+                else
+                    hipLaunchKernelGGL((acx::query_rank_kernel<false>), dim3((unsigned)nr, (unsigned)Q.w), dim3(acx::RANK_THREADS), lds, c->stream,
+                                       d_slab, Q.n, Q.w, d_q + r0, d_col, Q.mode, d_posn, d_moff + r0, d_mates + moff[r0], moff[r0], mb, d_pos, d_flag);
+            }
+            ACX_LAUNCHES_OK(c);
+            for (int e = 0; e < Q.w && mb > 0; ++e)
+                ACX_HIP(c, hipMemcpyAsync(out_pos + (size_t)e * M + moff[r0], d_pos + (size_t)e * mb, 4 * (size_t)mb, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(out_flag + (size_t)r0 * Q.w, d_flag, (size_t)nr * Q.w, hipMemcpyDeviceToHost, c->stream));
             ACX_HIP(c, hipStreamSynchronize(c->stream));
         }
         return ACX_OK;

@@ -1,5 +1,5 @@
-// Finish of a query band (acx_query_scores / acx_query_topk, include/acx.h): from the band's score slab to finished rows
-// or ranked candidate lists without leaving the device.
+// Finish of a query band (acx_query_scores / acx_query_topk / acx_query_ranks, include/acx.h): from the band's score slab
+// to finished rows, ranked candidate lists or the positions of listed tracks without leaving the device.
 //
 // The slab is what the pair kernels' scatter left behind: R rows (the band's queries) x N columns (every track of the
 // pool) x W planes, plane fastest -- slab[(r N + c) W + e] = score plane e of the pair {query r, track c} in the
@@ -16,6 +16,12 @@
 //                           strictly ascending track list (or every track); the own track is skipped also when listed.
 //                           Up to RANK_ROW_LDS candidates keep their finished values in LDS (the slab is read once);
 //                           more are re-read -- and re-finished, the same operations on the same bits -- per pass.
+//   Q3  query_rank_kernel   one workgroup per (row, plane): the 1-based positions of listed tracks (a query's clique
+//                           mates) among the row's finished values, by the counting of rank_columns_kernel -- plain
+//                           float comparisons, ties by posn --, eight mates per pass over the row.  The own column is
+//                           stored as NaN (no comparison counts it); a NaN or a -inf anywhere else flags the (row, plane)
+//                           and its positions are -1.  Up to RANK_ROW_LDS tracks keep their finished values in LDS; more
+//                           are re-read -- and re-finished, the same operations on the same bits -- per pass.
 // Every store is a plain C++ store.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -142,6 +148,104 @@ __global__ __launch_bounds__(RANK_THREADS) void query_topk_kernel(const float *_
         const int c = p < P ? scol[p] : -1;
         out_idx[o + p] = c;
         out_score[o + p] = c >= 0 ? value_of(c) : __builtin_nanf("");
+    }
+}
+
+// Q3.  grid: (R, W).  mates[moff[r] - mate_base .. moff[r + 1] - mate_base): the listed tracks of row r (none is the row's
+// own track: checked by the host); posn: N distinct tie ranks or NULL (the track index).
+// out_pos[e * plane_stride + moff[r] - mate_base + j]: position of the j-th listed track in plane e, or -1 where the
+// (row, plane) is flagged; out_flag[r W + e] in {0, 1}.
+// Dynamic LDS: QUERY_RANK_LDS_FIXED (the RANK_MB counters) + IN_LDS ? 16 * ((N + 3) / 4) : 0.
+constexpr int QUERY_RANK_LDS_FIXED = 16 * ((4 * RANK_MB + 15) / 16);
+template <bool IN_LDS>
+__global__ __launch_bounds__(RANK_THREADS) void query_rank_kernel(const float *__restrict__ slab, int N, int W,
+                                                                   const int32_t *__restrict__ self_of,
+                                                                   const double *__restrict__ col, int mode,
+                                                                   const int32_t *__restrict__ posn,
+                                                                   const int64_t *__restrict__ moff,
+                                                                   const int32_t *__restrict__ mates, int64_t mate_base,
+                                                                   int64_t plane_stride, int32_t *__restrict__ out_pos,
+                                                                   uint8_t *__restrict__ out_flag)
+{
+    // (all LDS in the dynamic region, the counters in front: the row's quads stay on 16 bytes)
+    extern __shared__ float4 rank_lds4[];
+    int *acc = reinterpret_cast<int *>(rank_lds4);
+    float4 *lrow4 = rank_lds4 + QUERY_RANK_LDS_FIXED / 16;
+    float *lrow = reinterpret_cast<float *>(lrow4);
+    const int r = blockIdx.x, e = blockIdx.y, tid = threadIdx.x;
+    const float *row = slab + (int64_t)r * N * W + e;
+    const int self = self_of[r];
+    const int nq = (N + 3) >> 2;
+    // the finished value of column c; the own column and the padding of the last quad are NaN, which no comparison counts
+    auto value_of = [&](int c) { return (c < N && c != self) ? query_value(row[(int64_t)c * W], col, c, mode) : __builtin_nanf(""); };
+    // pass 0: the finished row (into LDS).  A NaN anywhere else, or a -inf, flags the (row, plane): with the own column
+    // and the padding as the only NaNs allowed, a clean row holds exactly 4 nq - N + 1 of them.
+    int nans = 0, minf = 0;
+    for (int c = tid; c < 4 * nq; c += RANK_THREADS) {
+        const float v = value_of(c);
+        if (IN_LDS) lrow[c] = v;
+        nans += (v != v) ? 1 : 0;
+        minf |= rank_bad(v) ? 1 : 0;
+    }
+    if (tid < RANK_MB) acc[tid] = 0;
+    __syncthreads();
+    nans = rank_wave_sum(nans);
+    if ((tid & 63) == 0 && nans) atomicAdd(&acc[0], nans);
+    const bool any_minf = __syncthreads_or(minf) != 0;
+    const bool flagged = any_minf || acc[0] != 4 * nq - N + 1;
+    __syncthreads();
+    const int64_t m0 = moff[r] - mate_base, m1 = moff[r + 1] - mate_base;
+    int32_t *pos = out_pos + (int64_t)e * plane_stride;
+    if (tid == 0) out_flag[(int64_t)r * W + e] = flagged ? 1 : 0;
+    if (flagged) {
+        for (int64_t j = m0 + tid; j < m1; j += RANK_THREADS) pos[j] = -1;
+        return;
+    }
+    for (int64_t b0 = m0; b0 < m1; b0 += RANK_MB) {
+        float mv[RANK_MB];
+        int mp[RANK_MB], cnt[RANK_MB];
+#pragma unroll
+        for (int j = 0; j < RANK_MB; ++j) {      // wave-uniform: the mates' values and tie ranks
+            const bool on = b0 + j < m1;
+            const int m = on ? mates[b0 + j] : 0;
+            mv[j] = on ? value_of(m) : __builtin_nanf("");
+            mp[j] = on ? (posn ? posn[m] : m) : 0;
+            cnt[j] = 0;
+        }
+        if (tid < RANK_MB) acc[tid] = 0;
+        for (int q = tid; q < nq; q += RANK_THREADS) {
+            float v[4];
+            if (IN_LDS) {
+                const float4 v4 = lrow4[q];
+                v[0] = v4.x; v[1] = v4.y; v[2] = v4.z; v[3] = v4.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] = value_of(4 * q + i);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                bool have = false;
+                int pc = 0;
+#pragma unroll
+                for (int j = 0; j < RANK_MB; ++j) {
+                    if (v[i] > mv[j]) {
+                        ++cnt[j];
+                    } else if (v[i] == mv[j]) {       // a tie (the mate's own cell included): the tie order decides
+                        if (!have) { const int c = 4 * q + i; pc = posn ? posn[c] : c; have = true; }
+                        cnt[j] += pc < mp[j] ? 1 : 0;
+                    }
+                }
+            }
+        }
+        __syncthreads();                              // acc zeroed
+#pragma unroll
+        for (int j = 0; j < RANK_MB; ++j) {
+            const int s = rank_wave_sum(cnt[j]);
+            if ((tid & 63) == 0 && s) atomicAdd(&acc[j], s);
+        }
+        __syncthreads();
+        if (tid < RANK_MB && b0 + tid < m1) pos[b0 + tid] = 1 + acc[tid];
+        __syncthreads();
     }
 }
 

@@ -631,6 +631,22 @@ int acx_query_scores(acx_ctx *ctx, const acx_query_spec *spec, const void *param
 int acx_query_topk(acx_ctx *ctx, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
                    const int32_t *cands, int32_t n_cands, const double *col, int32_t k, int32_t *out_idx, float *out_score);
 
+/* Evaluation of a query set without an N x N matrix: the 1-based positions of listed tracks (a query's clique mates) in
+ * the query's finished row -- acx_rank_columns' counting applied to the band's slab on the device.  For every plane e and
+ * every listed track m of query i (mates[moff[i] .. moff[i + 1]), any number, moff[0] = 0):
+ *     out_pos[e * moff[n_queries] + j] = 1 + #{c != q: s[c] > s[m]} + #{c != q: s[c] == s[m], posn[c] < posn[m]}
+ * over EVERY track c of the pool (all columns of the band are computed), s = the finished values of plane e (col_mode as
+ * above), IEEE comparisons: -0.0 and +0.0 tie, +inf is an ordinary value.  posn: n_tracks distinct non-negative tie ranks,
+ * or NULL (= the track index).  A (query, plane) whose finished values hold a NaN or a -inf outside the query's own column
+ * (col_mode 2 turns a raw score of 0 into -inf) is FLAGGED: out_flag[i * planes + e] = 1 and its positions are -1; the
+ * host decides what such a row means (acx_query_scores returns it).  Bands and memory as acx_query_topk; every row is
+ * charged the longest mate list of the call.  Validated before the first launch, beyond the common rules above: moff[0]
+ * == 0 and non-decreasing, every mate a track in [0, n_tracks), a mate equal to its own query is ACX_ERR_INVALID, posn
+ * distinct and non-negative; the message names the argument. */
+int acx_query_ranks(acx_ctx *ctx, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
+                    const double *col, const int32_t *posn, const int64_t *moff, const int32_t *mates, int32_t *out_pos,
+                    uint8_t *out_flag);
+
 /* ---- multi-GPU inside the library: RCCL over xGMI, no Python ------------- */
 
 /*
