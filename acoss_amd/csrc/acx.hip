@@ -1512,6 +1512,20 @@ int launch_simple(acx_ctx *c, int n, size_t smem, int oti)
     return ACX_OK;
 }
 
+// simple_kernel's LDS per wave for tracks of up to maxn frames: the hand-over row + the profile keys
+static size_t simple_smem(int maxn) { return 64 + sizeof(double) * (2 * (size_t)maxn + (size_t)maxn / 48 + 4); }
+
+static int launch_simple_sslen(acx_ctx *c, int sslen, int n, size_t smem, int oti)
+{
+    switch (sslen) {
+#define ACX_L(L_) case L_: return launch_simple<L_>(c, n, smem, oti);
+        ACX_L(1) ACX_L(2) ACX_L(3) ACX_L(4) ACX_L(5) ACX_L(6) ACX_L(7) ACX_L(8)
+        ACX_L(9) ACX_L(10) ACX_L(11) ACX_L(12) ACX_L(13) ACX_L(14) ACX_L(15) ACX_L(16)
+#undef ACX_L
+    }
+    return fail(c, ACX_ERR_UNSUPPORTED, "simple: SSLEN must be in 1..16 on the device");
+}
+
 // |x_t|^2 summed over every window of `sslen` frames of the f64 pool: built on first use per (pool, SSLEN)
 static int ensure_winnorm(acx_ctx *c, int sslen)
 {
@@ -1527,6 +1541,39 @@ static int ensure_winnorm(acx_ctx *c, int sslen)
                        c->d_frames64, c->d_toff64, c->d_wn64, sslen);
     ACX_HIP(c, hipGetLastError());
     c->wn64_L = sslen;
+    return ACX_OK;
+}
+
+// What the device-resident SiMPle runs do before their first launch: SSLEN and the length of every track that
+// each_track(visit) visits are checked, *smem is set for the longest of them and the window norms are there.
+template <typename Each>
+static int simple_front(acx_ctx *c, int sslen, Each each_track, size_t *smem)
+{
+    if (sslen < 1 || sslen > acx::SIMPLE_MAXL) return fail(c, ACX_ERR_UNSUPPORTED, "simple: SSLEN must be in 1..16 on the device");
+    int maxn = 0, rc = ACX_OK;
+    each_track([&](int t) {
+        const int n = (int)(c->h_off64[t + 1] - c->h_off64[t]);
+        if (rc != ACX_OK) return;                     // (the first finding stands)
+        if (n < sslen) rc = fail(c, ACX_ERR_SHORT, "simple: track " + std::to_string(t) + " is shorter than SSLEN");
+        else if (n > acx::SIMPLE_MAXN) rc = fail(c, ACX_ERR_UNSUPPORTED, "simple: tracks with more than 6000 pooled frames are not supported on the device");
+        maxn = std::max(maxn, n);
+    });
+    if (rc != ACX_OK) return rc;
+    *smem = simple_smem(maxn);
+    return ensure_winnorm(c, sslen);
+}
+
+// The tile descriptors of a launch in c->d_tiles (grown as needed; pageable source: the copy is staged before the call
+// returns, the host's copy may be reused at once)
+static int upload_tiles(acx_ctx *c, const void *tiles, size_t bytes)
+{
+    if (bytes > c->tiles_cap) {
+        if (c->d_tiles) ACX_HIP(c, hipFree(c->d_tiles));
+        c->d_tiles = nullptr; c->tiles_cap = 0;
+        ACX_HIP(c, hipMalloc(&c->d_tiles, bytes));
+        c->tiles_cap = bytes;
+    }
+    ACX_HIP(c, hipMemcpyAsync(c->d_tiles, tiles, bytes, hipMemcpyHostToDevice, c->stream));
     return ACX_OK;
 }
 
@@ -2079,7 +2126,7 @@ int acx_simple_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, int32_t sslen,
             maxn = std::max(maxn, n);
         }
     }
-    const size_t smem = 64 + sizeof(double) * (2 * (size_t)maxn + (size_t)maxn / 48 + 4);   // per wave: the hand-over row + the profile keys
+    const size_t smem = simple_smem(maxn);
     int rcw = ensure_winnorm(c, sslen);
     if (rcw != ACX_OK) return rcw;
     const int64_t chunk = 1 << 22;
@@ -2103,13 +2150,7 @@ int acx_simple_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, int32_t sslen,
         ACX_HIP(c, hipMemcpyAsync(c->d_pairs, sorted.data(), sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
         {
             ProfScope ps(c, KS_SIMPLE, n);
-            switch (sslen) {
-#define ACX_L(L_) case L_: rc = launch_simple<L_>(c, n, smem, oti); break;
-                ACX_L(1) ACX_L(2) ACX_L(3) ACX_L(4) ACX_L(5) ACX_L(6) ACX_L(7) ACX_L(8)
-                ACX_L(9) ACX_L(10) ACX_L(11) ACX_L(12) ACX_L(13) ACX_L(14) ACX_L(15) ACX_L(16)
-#undef ACX_L
-            }
-            if (rc != ACX_OK) return rc;
+            if ((rc = launch_simple_sslen(c, sslen, n, smem, oti)) != ACX_OK) return rc;
         }
         ACX_HIP(c, hipGetLastError());
         tmp.resize(n);
@@ -2881,6 +2922,60 @@ static int rank_check_common(acx_ctx *c, const char *who, const float *scores, i
     return ACX_OK;
 }
 
+// What the two position calls check of a mate list.  `item`: what a mate is ("column" / "track"); a mate that is row r's
+// own (own[r]) is reported as "mates[j] <own_a>r<own_b>".
+static int rank_check_mates(acx_ctx *c, const char *who, int32_t n, int32_t n_rows, const int32_t *own, const char *item, const char *own_a,
+                            const char *own_b, const int64_t *moff, const int32_t *mates, const int32_t *out_pos, const uint8_t *out_flag)
+{
+    const std::string w(who);
+    if (!moff) return fail(c, ACX_ERR_INVALID, w + ": moff must not be NULL");
+    if (moff[0] != 0) return fail(c, ACX_ERR_INVALID, w + ": moff[0] must be 0");
+    for (int32_t r = 0; r < n_rows; ++r)
+        if (moff[r + 1] < moff[r]) return fail(c, ACX_ERR_INVALID, w + ": moff must be non-decreasing (moff[" + std::to_string(r + 1) + "])");
+    if (n_rows > 0 && !out_flag) return fail(c, ACX_ERR_INVALID, w + ": out_flag must not be NULL");
+    if (moff[n_rows] > 0 && (!mates || !out_pos)) return fail(c, ACX_ERR_INVALID, w + ": mates and out_pos must not be NULL");
+    for (int32_t r = 0; r < n_rows; ++r)
+        for (int64_t j = moff[r]; j < moff[r + 1]; ++j) {
+            if (mates[j] < 0 || mates[j] >= n)
+                return fail(c, ACX_ERR_INVALID, w + ": mates[" + std::to_string(j) + "] = " + std::to_string(mates[j]) + " is not a " + item + " in [0, " + std::to_string(n) + ")");
+            if (mates[j] == own[r]) return fail(c, ACX_ERR_INVALID, w + ": mates[" + std::to_string(j) + "] " + own_a + std::to_string(r) + own_b);
+        }
+    return ACX_OK;
+}
+
+// What the two top-k calls check of k and their outputs.
+static int rank_check_k(acx_ctx *c, const char *who, int32_t k, int32_t n_rows, const int32_t *out_idx, const float *out_score)
+{
+    const std::string w(who);
+    if (k < 1) return fail(c, ACX_ERR_INVALID, w + ": k must be >= 1 (got " + std::to_string(k) + ")");
+    if (k > acx::RANK_KMAX) return fail(c, ACX_ERR_UNSUPPORTED, w + ": k = " + std::to_string(k) + " is over the limit of " + std::to_string(acx::RANK_KMAX));
+    if (n_rows > 0 && (!out_idx || !out_score)) return fail(c, ACX_ERR_INVALID, w + ": out_idx and out_score must not be NULL");
+    return ACX_OK;
+}
+
+extern "C++" {
+// One device block of `total` bytes for the length of a call: body(d_mem) issues the call's work and returns an ACX code;
+// the device is done with the block when it is freed.
+template <typename F>
+static int with_device_block(acx_ctx *c, const char *who, size_t total, F body)
+{
+    char *d_mem = nullptr;
+    const hipError_t e = hipMalloc((void **)&d_mem, total);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, ACX_ERR_NOMEM, std::string(who) + ": " + hipGetErrorString(e)); }
+    const int rc = body(d_mem);
+    if (rc != ACX_OK) quiesce(c); else drain_profile(c);
+    (void)hipFree(d_mem);
+    return rc;
+}
+}  // extern "C++"
+
+// One launch of a kernel template <bool IN_LDS> of rank_kernels.hpp / query_kernels.hpp (256 threads) on c->stream
+#define ACX_LAUNCH_IN_LDS(KERNEL_, in_lds_, grid_, lds_, ...)                                                                        \
+    do {                                                                                                                             \
+        if (in_lds_) hipLaunchKernelGGL((acx::KERNEL_<true>), grid_, dim3(acx::RANK_THREADS), lds_, c->stream, __VA_ARGS__);         \
+        else hipLaunchKernelGGL((acx::KERNEL_<false>), grid_, dim3(acx::RANK_THREADS), lds_, c->stream, __VA_ARGS__);                \
+    } while (0)
+
 // Rows per staging piece: whole rows, RANK_SLICE_BYTES at most, and everything the call holds on the device (two pieces,
 // `per_row_out` bytes of results per row, `fixed` bytes of tables) within the scratch limit.
 static int rank_piece_rows(acx_ctx *c, const char *who, int32_t n, int32_t n_rows, int64_t per_row_out, int64_t fixed, int32_t *rows)
@@ -2935,10 +3030,11 @@ static int rank_for_pieces(acx_ctx *c, const float *scores, int64_t ld, int32_t 
 static int rank_lds_attr(acx_ctx *c)
 {
     if (c->rank_attr) return ACX_OK;
-    const int row = 4 * (acx::RANK_ROW_LDS + 8);
-    ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::rank_columns_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, row));
+    const int row = 4 * acx::RANK_ROW_LDS;
+    ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::rank_columns_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   row + acx::RANK_COUNT_LDS_FIXED));
     ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::topk_rows_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   row + 12 * acx::RANK_KMAX));
+                                   row + 12 * acx::RANK_KMAX + acx::RANK_SELECT_LDS_FIXED));
     c->rank_attr = true;
     return ACX_OK;
 }
@@ -2949,20 +3045,9 @@ int acx_rank_columns(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int
     if (!c) return ACX_ERR_INVALID;
     int rc = rank_check_common(c, "rank_columns", scores, ld, n, n_rows, self, posn);
     if (rc != ACX_OK) return rc;
-    if (!moff) return fail(c, ACX_ERR_INVALID, "rank_columns: moff must not be NULL");
-    if (moff[0] != 0) return fail(c, ACX_ERR_INVALID, "rank_columns: moff[0] must be 0");
-    for (int32_t r = 0; r < n_rows; ++r)
-        if (moff[r + 1] < moff[r]) return fail(c, ACX_ERR_INVALID, "rank_columns: moff must be non-decreasing (moff[" + std::to_string(r + 1) + "])");
+    if ((rc = rank_check_mates(c, "rank_columns", n, n_rows, self, "column", "is row ", "'s own column (self)", moff, mates, out_pos, out_flag)) != ACX_OK)
+        return rc;
     const int64_t M = moff[n_rows];
-    if (n_rows > 0 && !out_flag) return fail(c, ACX_ERR_INVALID, "rank_columns: out_flag must not be NULL");
-    if (M > 0 && (!mates || !out_pos)) return fail(c, ACX_ERR_INVALID, "rank_columns: mates and out_pos must not be NULL");
-    for (int32_t r = 0; r < n_rows; ++r)
-        for (int64_t j = moff[r]; j < moff[r + 1]; ++j) {
-            if (mates[j] < 0 || mates[j] >= n)
-                return fail(c, ACX_ERR_INVALID, "rank_columns: mates[" + std::to_string(j) + "] = " + std::to_string(mates[j]) + " is not a column in [0, " + std::to_string(n) + ")");
-            if (mates[j] == self[r])
-                return fail(c, ACX_ERR_INVALID, "rank_columns: mates[" + std::to_string(j) + "] is row " + std::to_string(r) + "'s own column (self)");
-        }
     if (n_rows == 0) return ACX_OK;
     const int64_t fixed = 8 * (int64_t)(n_rows + 1) + 8 * M + 5 * (int64_t)n_rows + 4 * (int64_t)n;
     int32_t piece = 0;
@@ -2972,12 +3057,7 @@ int acx_rank_columns(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int
     // the tables of the whole call in one device block: moff | mates | out_pos | self | posn | out_flag
     const size_t o_mates = sizeof(int64_t) * (size_t)(n_rows + 1), o_pos = o_mates + 4 * (size_t)M, o_self = o_pos + 4 * (size_t)M,
                  o_posn = o_self + 4 * (size_t)n_rows, o_flag = o_posn + (posn ? 4 * (size_t)n : 0), total = o_flag + (size_t)n_rows;
-    char *d_tab = nullptr;
-    {
-        const hipError_t e = hipMalloc((void **)&d_tab, total);
-        if (e != hipSuccess) return fail(c, ACX_ERR_NOMEM, std::string("rank_columns: ") + hipGetErrorString(e));
-    }
-    auto body = [&]() -> int {
+    return with_device_block(c, "rank_columns", total, [&](char *d_tab) -> int {
         ACX_HIP(c, hipMemcpyAsync(d_tab, moff, sizeof(int64_t) * (size_t)(n_rows + 1), hipMemcpyHostToDevice, c->stream));
         if (M > 0) ACX_HIP(c, hipMemcpyAsync(d_tab + o_mates, mates, 4 * (size_t)M, hipMemcpyHostToDevice, c->stream));
         ACX_HIP(c, hipMemcpyAsync(d_tab + o_self, self, 4 * (size_t)n_rows, hipMemcpyHostToDevice, c->stream));
@@ -2988,15 +3068,11 @@ int acx_rank_columns(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int
         int32_t *d_pos = reinterpret_cast<int32_t *>(d_tab + o_pos);
         uint8_t *d_flag = reinterpret_cast<uint8_t *>(d_tab + o_flag);
         const bool in_lds = n <= acx::RANK_ROW_LDS;
-        const size_t lds = in_lds ? 16 * (size_t)((n + 3) / 4 + 1) : 0;
+        const size_t lds = acx::RANK_COUNT_LDS_FIXED + (in_lds ? 16 * (size_t)((n + 3) / 4) : 0);
         int rcp = rank_for_pieces(c, scores, ld, n, n_rows, piece, [&](const float *d_rows, int64_t ldd, int32_t r0, int32_t nr) -> int {
             ProfScope ps(c, KS_RANK, (int64_t)nr * n);
-            if (in_lds)
-                hipLaunchKernelGGL((acx::rank_columns_kernel<true>), dim3((unsigned)nr), dim3(acx::RANK_THREADS), lds, c->stream, d_rows, ldd, (int)n,
-                                   d_self + r0, d_posn, d_moff + r0, d_mates, (int64_t)0, d_pos, d_flag + r0);
-            else
-                hipLaunchKernelGGL((acx::rank_columns_kernel<false>), dim3((unsigned)nr), dim3(acx::RANK_THREADS), 0, c->stream, d_rows, ldd, (int)n,
-                                   d_self + r0, d_posn, d_moff + r0, d_mates, (int64_t)0, d_pos, d_flag + r0);
+            ACX_LAUNCH_IN_LDS(rank_columns_kernel, in_lds, dim3((unsigned)nr), lds, d_rows, ldd, (int)n, d_self + r0, d_posn, d_moff + r0, d_mates,
+                              (int64_t)0, d_pos, d_flag + r0);
             return ACX_OK;
         });
         if (rcp != ACX_OK) return rcp;
@@ -3004,11 +3080,7 @@ int acx_rank_columns(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int
         if (M > 0) ACX_HIP(c, hipMemcpy(out_pos, d_pos, 4 * (size_t)M, hipMemcpyDeviceToHost));
         ACX_HIP(c, hipMemcpy(out_flag, d_flag, (size_t)n_rows, hipMemcpyDeviceToHost));
         return ACX_OK;
-    };
-    rc = body();
-    if (rc != ACX_OK) quiesce(c); else drain_profile(c);
-    (void)hipFree(d_tab);
-    return rc;
+    });
 }
 
 int acx_topk_rows(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int32_t n_rows, const int32_t *self, const int32_t *posn, int32_t k,
@@ -3017,10 +3089,7 @@ int acx_topk_rows(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int32_
     if (!c) return ACX_ERR_INVALID;
     int rc = rank_check_common(c, "topk_rows", scores, ld, n, n_rows, self, posn);
     if (rc != ACX_OK) return rc;
-    if (k < 1) return fail(c, ACX_ERR_INVALID, "topk_rows: k must be >= 1 (got " + std::to_string(k) + ")");
-    if (k > acx::RANK_KMAX)
-        return fail(c, ACX_ERR_UNSUPPORTED, "topk_rows: k = " + std::to_string(k) + " is over the limit of " + std::to_string(acx::RANK_KMAX));
-    if (n_rows > 0 && (!out_idx || !out_score)) return fail(c, ACX_ERR_INVALID, "topk_rows: out_idx and out_score must not be NULL");
+    if ((rc = rank_check_k(c, "topk_rows", k, n_rows, out_idx, out_score)) != ACX_OK) return rc;
     if (n_rows == 0) return ACX_OK;
     const int64_t fixed = 4 * (int64_t)n_rows + 4 * (int64_t)n;
     int32_t piece = 0;
@@ -3032,18 +3101,13 @@ int acx_topk_rows(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int32_
     // self | posn | two result slots of `piece` rows (indices, scores)
     const size_t o_posn = 4 * (size_t)n_rows, o_res = o_posn + (posn ? 4 * (size_t)n : 0), slot_bytes = 8 * (size_t)k * piece,
                  total = o_res + 2 * slot_bytes;
-    char *d_tab = nullptr;
-    {
-        const hipError_t e = hipMalloc((void **)&d_tab, total);
-        if (e != hipSuccess) return fail(c, ACX_ERR_NOMEM, std::string("topk_rows: ") + hipGetErrorString(e));
-    }
-    auto body = [&]() -> int {
+    return with_device_block(c, "topk_rows", total, [&](char *d_tab) -> int {
         ACX_HIP(c, hipMemcpyAsync(d_tab, self, 4 * (size_t)n_rows, hipMemcpyHostToDevice, c->stream));
         if (posn) ACX_HIP(c, hipMemcpyAsync(d_tab + o_posn, posn, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
         const int32_t *d_self = reinterpret_cast<const int32_t *>(d_tab);
         const int32_t *d_posn = posn ? reinterpret_cast<const int32_t *>(d_tab + o_posn) : nullptr;
         const bool in_lds = n <= acx::RANK_ROW_LDS;
-        const size_t lds = 12 * (size_t)P + (in_lds ? 4 * (size_t)(n + 3) : 0);
+        const size_t lds = 12 * (size_t)P + acx::RANK_SELECT_LDS_FIXED + (in_lds ? 16 * (size_t)((n + 3) / 4) : 0);
         int p = 0;
         int rcp = rank_for_pieces(c, scores, ld, n, n_rows, piece, [&](const float *d_rows, int64_t ldd, int32_t r0, int32_t nr) -> int {
             // (the result slot alternates with the staging slot: its previous copy to the host was issued on the same stream)
@@ -3052,12 +3116,7 @@ int acx_topk_rows(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int32_
             ++p;
             {
                 ProfScope ps(c, KS_TOPK, (int64_t)nr * n);
-                if (in_lds)
-                    hipLaunchKernelGGL((acx::topk_rows_kernel<true>), dim3((unsigned)nr), dim3(acx::RANK_THREADS), lds, c->stream, d_rows, ldd, (int)n,
-                                       d_self + r0, d_posn, (int)k, P, d_idx, d_sc);
-                else
-                    hipLaunchKernelGGL((acx::topk_rows_kernel<false>), dim3((unsigned)nr), dim3(acx::RANK_THREADS), lds, c->stream, d_rows, ldd, (int)n,
-                                       d_self + r0, d_posn, (int)k, P, d_idx, d_sc);
+                ACX_LAUNCH_IN_LDS(topk_rows_kernel, in_lds, dim3((unsigned)nr), lds, d_rows, ldd, (int)n, d_self + r0, d_posn, (int)k, P, d_idx, d_sc);
             }
             ACX_HIP(c, hipMemcpyAsync(out_idx + (size_t)r0 * k, d_idx, 4 * (size_t)k * nr, hipMemcpyDeviceToHost, c->stream));
             ACX_HIP(c, hipMemcpyAsync(out_score + (size_t)r0 * k, d_sc, 4 * (size_t)k * nr, hipMemcpyDeviceToHost, c->stream));
@@ -3066,11 +3125,7 @@ int acx_topk_rows(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int32_
         if (rcp != ACX_OK) return rcp;
         ACX_LAUNCHES_OK(c);
         return ACX_OK;
-    };
-    rc = body();
-    if (rc != ACX_OK) quiesce(c); else drain_profile(c);
-    (void)hipFree(d_tab);
-    return rc;
+    });
 }
 
 // Device state of one similarity-network-fusion run: P matrices (two generations), the kNN kernels,
@@ -3306,22 +3361,13 @@ static const std::vector<acx_grid_tile> &cached_plan(acx_ctx *c, const std::vect
 // Nothing comes back to the host and the host waits for nothing between chunks.
 static int run_simple_tiles(acx_ctx *c, const std::vector<acx_grid_tile> &mine, int symmetric, const acx_simple_params &sp, float *d_scores)
 {
-    const int sslen = sp.sslen;
-    if (sslen < 1 || sslen > acx::SIMPLE_MAXL) return fail(c, ACX_ERR_UNSUPPORTED, "simple: SSLEN must be in 1..16 on the device");
-    int maxn = 0;
-    for (const acx_grid_tile &t : mine) {
-        for (int side = 0; side < 2; ++side) {
-            const int a0 = side ? t.col0 : t.row0, a1 = a0 + (side ? t.cols : t.rows);
-            for (int tr = a0; tr < a1; ++tr) {
-                const int n = (int)(c->h_off64[tr + 1] - c->h_off64[tr]);
-                if (n < sslen) return fail(c, ACX_ERR_SHORT, "simple: track " + std::to_string(tr) + " is shorter than SSLEN");
-                if (n > acx::SIMPLE_MAXN) return fail(c, ACX_ERR_UNSUPPORTED, "simple: tracks with more than 6000 pooled frames are not supported on the device");
-                maxn = std::max(maxn, n);
-            }
+    size_t smem = 0;
+    int rc = simple_front(c, sp.sslen, [&](auto visit) {
+        for (const acx_grid_tile &t : mine) {
+            for (int tr = t.row0; tr < t.row0 + t.rows; ++tr) visit(tr);
+            for (int tr = t.col0; tr < t.col0 + t.cols; ++tr) visit(tr);
         }
-    }
-    const size_t smem = 64 + sizeof(double) * (2 * (size_t)maxn + (size_t)maxn / 48 + 4);
-    int rc = ensure_winnorm(c, sslen);
+    }, &smem);
     if (rc != ACX_OK) return rc;
     const int64_t CHUNK = (int64_t)1 << 22;
     std::vector<TileDev> td;
@@ -3343,26 +3389,12 @@ static int run_simple_tiles(acx_ctx *c, const std::vector<acx_grid_tile> &mine, 
             if ((rc = ensure(c, c->d_pairs, c->pairs_cap, (size_t)2 * n)) != ACX_OK) return rc;
             if ((rc = ensure(c, c->d_out64, c->out64_cap, (size_t)n)) != ACX_OK) return rc;
             if ((rc = ensure(c, c->d_idx, c->idx_cap, (size_t)n)) != ACX_OK) return rc;
-            const size_t tbytes = sizeof(TileDev) * td.size();
-            if (tbytes > c->tiles_cap) {
-                if (c->d_tiles) ACX_HIP(c, hipFree(c->d_tiles));
-                c->d_tiles = nullptr; c->tiles_cap = 0;
-                ACX_HIP(c, hipMalloc(&c->d_tiles, tbytes));
-                c->tiles_cap = tbytes;
-            }
-            // (pageable source: the copy is staged before the call returns, `td` may be reused at once)
-            ACX_HIP(c, hipMemcpyAsync(c->d_tiles, td.data(), tbytes, hipMemcpyHostToDevice, c->stream));
+            if ((rc = upload_tiles(c, td.data(), sizeof(TileDev) * td.size())) != ACX_OK) return rc;
             hipLaunchKernelGGL(grid_pairs_kernel, dim3((unsigned)std::min<int64_t>((maxP + 255) / 256, 256), (unsigned)td.size()), dim3(256), 0,
                                c->stream, static_cast<const TileDev *>(c->d_tiles), symmetric, 1, c->d_pairs, c->d_idx);
             {
                 ProfScope ps(c, KS_SIMPLE, n);
-                switch (sslen) {
-#define ACX_L(L_) case L_: rc = launch_simple<L_>(c, (int)n, smem, sp.oti); break;
-                    ACX_L(1) ACX_L(2) ACX_L(3) ACX_L(4) ACX_L(5) ACX_L(6) ACX_L(7) ACX_L(8)
-                    ACX_L(9) ACX_L(10) ACX_L(11) ACX_L(12) ACX_L(13) ACX_L(14) ACX_L(15) ACX_L(16)
-#undef ACX_L
-                }
-                if (rc != ACX_OK) return rc;
+                if ((rc = launch_simple_sslen(c, sp.sslen, (int)n, smem, sp.oti)) != ACX_OK) return rc;
             }
             hipLaunchKernelGGL(scatter_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_out64, c->d_idx, d_scores, (int)n);
             ACX_HIP(c, hipGetLastError());
@@ -3384,14 +3416,8 @@ static int run_ftm2d_tiles(acx_ctx *c, const std::vector<acx_grid_tile> &mine, i
                 items.push_back(acx::FtmTileItem{t.row0, t.col0, t.rows, t.cols, r0, c0, t.diagonal, 0, t.offset});
             }
     if (items.empty()) return ACX_OK;
-    const size_t tbytes = sizeof(acx::FtmTileItem) * items.size();
-    if (tbytes > c->tiles_cap) {
-        if (c->d_tiles) ACX_HIP(c, hipFree(c->d_tiles));
-        c->d_tiles = nullptr; c->tiles_cap = 0;
-        ACX_HIP(c, hipMalloc(&c->d_tiles, tbytes));
-        c->tiles_cap = tbytes;
-    }
-    ACX_HIP(c, hipMemcpyAsync(c->d_tiles, items.data(), tbytes, hipMemcpyHostToDevice, c->stream));
+    const int rc = upload_tiles(c, items.data(), sizeof(acx::FtmTileItem) * items.size());
+    if (rc != ACX_OK) return rc;
     hipLaunchKernelGGL(acx::ftm2d_tile_kernel, dim3((unsigned)items.size()), dim3(256), 0, c->stream, c->d_ftm, c->ftm_dim,
                        static_cast<const acx::FtmTileItem *>(c->d_tiles), symmetric, d_scores);
     ACX_HIP(c, hipGetLastError());
@@ -3635,18 +3661,8 @@ static void query_band_pairs(const int32_t *q, int nr, const int32_t *cols, int 
 // f64 -> f32 scatter of the grid path.
 static int run_simple_list(acx_ctx *c, const int32_t *pairs, const int64_t *idx, int64_t K, const acx_simple_params &sp, float *d_scores)
 {
-    const int sslen = sp.sslen;
-    if (sslen < 1 || sslen > acx::SIMPLE_MAXL) return fail(c, ACX_ERR_UNSUPPORTED, "simple: SSLEN must be in 1..16 on the device");
-    int maxn = 0;
-    for (int64_t k = 0; k < 2 * K; ++k) {
-        const int t = pairs[k];
-        const int n = (int)(c->h_off64[t + 1] - c->h_off64[t]);
-        if (n < sslen) return fail(c, ACX_ERR_SHORT, "simple: track " + std::to_string(t) + " is shorter than SSLEN");
-        if (n > acx::SIMPLE_MAXN) return fail(c, ACX_ERR_UNSUPPORTED, "simple: tracks with more than 6000 pooled frames are not supported on the device");
-        maxn = std::max(maxn, n);
-    }
-    const size_t smem = 64 + sizeof(double) * (2 * (size_t)maxn + (size_t)maxn / 48 + 4);
-    int rc = ensure_winnorm(c, sslen);
+    size_t smem = 0;
+    int rc = simple_front(c, sp.sslen, [&](auto visit) { for (int64_t k = 0; k < 2 * K; ++k) visit(pairs[k]); }, &smem);
     if (rc != ACX_OK) return rc;
     const int64_t CHUNK = (int64_t)1 << 22;
     if ((rc = ensure(c, c->d_pairs, c->pairs_cap, (size_t)2 * std::min(K, CHUNK))) != ACX_OK) return rc;
@@ -3657,13 +3673,7 @@ static int run_simple_list(acx_ctx *c, const int32_t *pairs, const int64_t *idx,
         if ((rc = stage_idx(c, idx + k0, n)) != ACX_OK) return rc;
         {
             ProfScope ps(c, KS_SIMPLE, n);
-            switch (sslen) {
-#define ACX_L(L_) case L_: rc = launch_simple<L_>(c, n, smem, sp.oti); break;
-                ACX_L(1) ACX_L(2) ACX_L(3) ACX_L(4) ACX_L(5) ACX_L(6) ACX_L(7) ACX_L(8)
-                ACX_L(9) ACX_L(10) ACX_L(11) ACX_L(12) ACX_L(13) ACX_L(14) ACX_L(15) ACX_L(16)
-#undef ACX_L
-            }
-            if (rc != ACX_OK) return rc;
+            if ((rc = launch_simple_sslen(c, sp.sslen, n, smem, sp.oti)) != ACX_OK) return rc;
         }
         hipLaunchKernelGGL(scatter_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_out64, c->d_idx, d_scores, n);
         ACX_LAUNCHES_OK(c);
@@ -3734,6 +3744,28 @@ static int query_run_band(acx_ctx *c, const QueryCall &Q, const int32_t *q, int 
     return ACX_OK;
 }
 
+// The bands of a call, R query rows each: every band through the pair kernels into d_slab, then launch(r0, nr) -- the
+// call's finishing kernel -- and, the launches checked, copies(r0, nr) -- its results on their way to the host.
+extern "C++" {
+template <typename L, typename C>
+static int query_for_bands(acx_ctx *c, const QueryCall &Q, const int32_t *queries, int n_queries, int R, const int32_t *cols, int ncols,
+                           float *d_slab, int64_t per_row, L launch, C copies)
+{
+    std::vector<int32_t> pairs;
+    std::vector<int64_t> idx;
+    for (int r0 = 0; r0 < n_queries; r0 += R) {
+        const int nr = std::min(R, n_queries - r0);
+        int rc = query_run_band(c, Q, queries + r0, nr, cols, ncols, d_slab, (int64_t)R * per_row, pairs, idx);
+        if (rc != ACX_OK) return rc;
+        launch(r0, nr);
+        ACX_LAUNCHES_OK(c);
+        if ((rc = copies(r0, nr)) != ACX_OK) return rc;
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return ACX_OK;
+}
+}  // extern "C++"
+
 int acx_query_scores(acx_ctx *c, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
                      const double *col, float *const *rows, int64_t ld)
 {
@@ -3752,40 +3784,25 @@ int acx_query_scores(acx_ctx *c, const acx_query_spec *spec, const void *params,
     ACX_HIP(c, hipSetDevice(c->device));
     const size_t slab_floats = (size_t)R * Q.n * Q.w;
     const size_t o_col = 2 * slab_floats * 4, o_q = o_col + (col ? 8 * (size_t)Q.n : 0), total = o_q + 4 * (size_t)n_queries;
-    char *d_mem = nullptr;
-    {
-        const hipError_t e = hipMalloc((void **)&d_mem, total);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, ACX_ERR_NOMEM, std::string("query_scores: ") + hipGetErrorString(e)); }
-    }
-    auto body = [&]() -> int {
+    return with_device_block(c, "query_scores", total, [&](char *d_mem) -> int {
         float *d_slab = reinterpret_cast<float *>(d_mem), *d_fin = d_slab + slab_floats;
         const double *d_col = col ? reinterpret_cast<const double *>(d_mem + o_col) : nullptr;
         int32_t *d_q = reinterpret_cast<int32_t *>(d_mem + o_q);
         if (col) ACX_HIP(c, hipMemcpyAsync(d_mem + o_col, col, 8 * (size_t)Q.n, hipMemcpyHostToDevice, c->stream));
         ACX_HIP(c, hipMemcpyAsync(d_q, queries, 4 * (size_t)n_queries, hipMemcpyHostToDevice, c->stream));
-        std::vector<int32_t> pairs;
-        std::vector<int64_t> idx;
-        for (int r0 = 0; r0 < n_queries; r0 += R) {
-            const int nr = std::min(R, n_queries - r0);
-            int rcb = query_run_band(c, Q, queries + r0, nr, nullptr, Q.n, d_slab, (int64_t)R * per_row, pairs, idx);
-            if (rcb != ACX_OK) return rcb;
-            {
+        return query_for_bands(c, Q, queries, n_queries, R, nullptr, Q.n, d_slab, per_row,
+            [&](int r0, int nr) {
                 ProfScope ps(c, KS_QROWS, (int64_t)nr * Q.n * Q.w);
                 hipLaunchKernelGGL(acx::query_rows_kernel, dim3((unsigned)((Q.n + 255) / 256), (unsigned)nr, (unsigned)Q.w), dim3(256), 0, c->stream,
                                    d_slab, Q.n, Q.w, nr, d_q + r0, d_col, Q.mode, d_fin);
-            }
-            ACX_LAUNCHES_OK(c);
-            for (int e = 0; e < Q.w; ++e)
-                ACX_HIP(c, hipMemcpy2DAsync(rows[e] + (size_t)r0 * ld, sizeof(float) * (size_t)ld, d_fin + (size_t)e * nr * Q.n, sizeof(float) * (size_t)Q.n,
-                                            sizeof(float) * (size_t)Q.n, (size_t)nr, hipMemcpyDeviceToHost, c->stream));
-            ACX_HIP(c, hipStreamSynchronize(c->stream));
-        }
-        return ACX_OK;
-    };
-    rc = body();
-    if (rc != ACX_OK) quiesce(c); else drain_profile(c);
-    (void)hipFree(d_mem);
-    return rc;
+            },
+            [&](int r0, int nr) -> int {
+                for (int e = 0; e < Q.w; ++e)
+                    ACX_HIP(c, hipMemcpy2DAsync(rows[e] + (size_t)r0 * ld, sizeof(float) * (size_t)ld, d_fin + (size_t)e * nr * Q.n, sizeof(float) * (size_t)Q.n,
+                                                sizeof(float) * (size_t)Q.n, (size_t)nr, hipMemcpyDeviceToHost, c->stream));
+                return ACX_OK;
+            });
+    });
 }
 
 int acx_query_topk(acx_ctx *c, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
@@ -3795,10 +3812,7 @@ int acx_query_topk(acx_ctx *c, const acx_query_spec *spec, const void *params, c
     QueryCall Q;
     int rc = query_check(c, "query_topk", spec, params, queries, n_queries, cands, n_cands, col, Q);
     if (rc != ACX_OK) return rc;
-    if (k < 1) return fail(c, ACX_ERR_INVALID, "query_topk: k must be >= 1 (got " + std::to_string(k) + ")");
-    if (k > acx::RANK_KMAX)
-        return fail(c, ACX_ERR_UNSUPPORTED, "query_topk: k = " + std::to_string(k) + " is over the limit of " + std::to_string(acx::RANK_KMAX));
-    if (n_queries > 0 && (!out_idx || !out_score)) return fail(c, ACX_ERR_INVALID, "query_topk: out_idx and out_score must not be NULL");
+    if ((rc = rank_check_k(c, "query_topk", k, n_queries, out_idx, out_score)) != ACX_OK) return rc;
     if (n_queries == 0) return ACX_OK;
     const int ncand = cands ? n_cands : Q.n;
     const int64_t per_row = (int64_t)Q.n * Q.w * 4 + 8 * (int64_t)Q.w * k;      // the slab row and its results
@@ -3807,7 +3821,7 @@ int acx_query_topk(acx_ctx *c, const acx_query_spec *spec, const void *params, c
     ACX_HIP(c, hipSetDevice(c->device));
     if (!c->query_attr) {
         ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::query_topk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       4 * acx::RANK_ROW_LDS + 12 * acx::RANK_KMAX + acx::QUERY_LDS_FIXED));
+                                       4 * acx::RANK_ROW_LDS + 12 * acx::RANK_KMAX + acx::RANK_SELECT_LDS_FIXED));
         c->query_attr = true;
     }
     int P = 4;
@@ -3816,12 +3830,7 @@ int acx_query_topk(acx_ctx *c, const acx_query_spec *spec, const void *params, c
     const size_t slab_floats = (size_t)R * Q.n * Q.w, res = (size_t)R * Q.w * k;
     const size_t o_col = slab_floats * 4, o_q = o_col + (col ? 8 * (size_t)Q.n : 0), o_c = o_q + 4 * (size_t)n_queries,
                  o_res = o_c + (cands ? 4 * (size_t)n_cands : 0), total = o_res + 8 * res;
-    char *d_mem = nullptr;
-    {
-        const hipError_t e = hipMalloc((void **)&d_mem, total);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, ACX_ERR_NOMEM, std::string("query_topk: ") + hipGetErrorString(e)); }
-    }
-    auto body = [&]() -> int {
+    return with_device_block(c, "query_topk", total, [&](char *d_mem) -> int {
         float *d_slab = reinterpret_cast<float *>(d_mem);
         const double *d_col = col ? reinterpret_cast<const double *>(d_mem + o_col) : nullptr;
         int32_t *d_q = reinterpret_cast<int32_t *>(d_mem + o_q);
@@ -3832,34 +3841,20 @@ int acx_query_topk(acx_ctx *c, const acx_query_spec *spec, const void *params, c
         ACX_HIP(c, hipMemcpyAsync(d_q, queries, 4 * (size_t)n_queries, hipMemcpyHostToDevice, c->stream));
         if (cands && n_cands > 0) ACX_HIP(c, hipMemcpyAsync(d_mem + o_c, cands, 4 * (size_t)n_cands, hipMemcpyHostToDevice, c->stream));
         const bool in_lds = ncand <= acx::RANK_ROW_LDS;
-        const size_t lds = 12 * (size_t)P + acx::QUERY_LDS_FIXED + (in_lds ? 4 * (size_t)ncand : 0);
-        std::vector<int32_t> pairs;
-        std::vector<int64_t> idx;
-        for (int r0 = 0; r0 < n_queries; r0 += R) {
-            const int nr = std::min(R, n_queries - r0);
-            int rcb = query_run_band(c, Q, queries + r0, nr, cands, ncand, d_slab, (int64_t)R * per_row, pairs, idx);
-            if (rcb != ACX_OK) return rcb;
-            {
+        const size_t lds = 12 * (size_t)P + acx::RANK_SELECT_LDS_FIXED + (in_lds ? 4 * (size_t)ncand : 0);
+        return query_for_bands(c, Q, queries, n_queries, R, cands, ncand, d_slab, per_row,
+            [&](int r0, int nr) {
                 ProfScope ps(c, KS_QTOPK, (int64_t)nr * ncand * Q.w);
-                if (in_lds)
-                    hipLaunchKernelGGL((acx::query_topk_kernel<true>), dim3((unsigned)nr, (unsigned)Q.w), dim3(acx::RANK_THREADS), lds, c->stream,
-                                       d_slab, Q.n, Q.w, d_q + r0, d_c, ncand, d_col, Q.mode, (int)k, P, d_idx, d_sc);
-                else
-                    hipLaunchKernelGGL((acx::query_topk_kernel<false>), dim3((unsigned)nr, (unsigned)Q.w), dim3(acx::RANK_THREADS), lds, c->stream,
-                                       d_slab, Q.n, Q.w, d_q + r0, d_c, ncand, d_col, Q.mode, (int)k, P, d_idx, d_sc);
-            }
-            ACX_LAUNCHES_OK(c);
-            const size_t nres = (size_t)nr * Q.w * k;
-            ACX_HIP(c, hipMemcpyAsync(out_idx + (size_t)r0 * Q.w * k, d_idx, 4 * nres, hipMemcpyDeviceToHost, c->stream));
-            ACX_HIP(c, hipMemcpyAsync(out_score + (size_t)r0 * Q.w * k, d_sc, 4 * nres, hipMemcpyDeviceToHost, c->stream));
-            ACX_HIP(c, hipStreamSynchronize(c->stream));
-        }
-        return ACX_OK;
-    };
-    rc = body();
-    if (rc != ACX_OK) quiesce(c); else drain_profile(c);
-    (void)hipFree(d_mem);
-    return rc;
+                ACX_LAUNCH_IN_LDS(query_topk_kernel, in_lds, dim3((unsigned)nr, (unsigned)Q.w), lds, d_slab, Q.n, Q.w, d_q + r0, d_c, ncand, d_col, Q.mode,
+                                  (int)k, P, d_idx, d_sc);
+            },
+            [&](int r0, int nr) -> int {
+                const size_t nres = (size_t)nr * Q.w * k;
+                ACX_HIP(c, hipMemcpyAsync(out_idx + (size_t)r0 * Q.w * k, d_idx, 4 * nres, hipMemcpyDeviceToHost, c->stream));
+                ACX_HIP(c, hipMemcpyAsync(out_score + (size_t)r0 * Q.w * k, d_sc, 4 * nres, hipMemcpyDeviceToHost, c->stream));
+                return ACX_OK;
+            });
+    });
 }
 
 int acx_query_ranks(acx_ctx *c, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
@@ -3870,23 +3865,11 @@ int acx_query_ranks(acx_ctx *c, const acx_query_spec *spec, const void *params, 
     QueryCall Q;
     int rc = query_check(c, "query_ranks", spec, params, queries, n_queries, nullptr, 0, col, Q);
     if (rc != ACX_OK) return rc;
-    if (!moff) return fail(c, ACX_ERR_INVALID, "query_ranks: moff must not be NULL");
-    if (moff[0] != 0) return fail(c, ACX_ERR_INVALID, "query_ranks: moff[0] must be 0");
-    int64_t maxm = 0;
-    for (int32_t r = 0; r < n_queries; ++r) {
-        if (moff[r + 1] < moff[r]) return fail(c, ACX_ERR_INVALID, "query_ranks: moff must be non-decreasing (moff[" + std::to_string(r + 1) + "])");
-        maxm = std::max(maxm, moff[r + 1] - moff[r]);
-    }
+    if ((rc = rank_check_mates(c, "query_ranks", Q.n, n_queries, queries, "track", "is queries[", "] itself", moff, mates, out_pos, out_flag)) != ACX_OK)
+        return rc;
     const int64_t M = moff[n_queries];
-    if (n_queries > 0 && !out_flag) return fail(c, ACX_ERR_INVALID, "query_ranks: out_flag must not be NULL");
-    if (M > 0 && (!mates || !out_pos)) return fail(c, ACX_ERR_INVALID, "query_ranks: mates and out_pos must not be NULL");
-    for (int32_t r = 0; r < n_queries; ++r)
-        for (int64_t j = moff[r]; j < moff[r + 1]; ++j) {
-            if (mates[j] < 0 || mates[j] >= Q.n)
-                return fail(c, ACX_ERR_INVALID, "query_ranks: mates[" + std::to_string(j) + "] = " + std::to_string(mates[j]) + " is not a track in [0, " + std::to_string(Q.n) + ")");
-            if (mates[j] == queries[r])
-                return fail(c, ACX_ERR_INVALID, "query_ranks: mates[" + std::to_string(j) + "] is queries[" + std::to_string(r) + "] itself");
-        }
+    int64_t maxm = 0;
+    for (int32_t r = 0; r < n_queries; ++r) maxm = std::max(maxm, moff[r + 1] - moff[r]);
     if (posn) {
         std::vector<std::pair<int32_t, int32_t>> seen((size_t)Q.n);
         for (int i = 0; i < Q.n; ++i) {
@@ -3907,7 +3890,7 @@ int acx_query_ranks(acx_ctx *c, const acx_query_spec *spec, const void *params, 
     ACX_HIP(c, hipSetDevice(c->device));
     if (!c->query_rank_attr) {
         ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::query_rank_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       4 * acx::RANK_ROW_LDS + acx::QUERY_RANK_LDS_FIXED));
+                                       4 * acx::RANK_ROW_LDS + acx::RANK_COUNT_LDS_FIXED));
         c->query_rank_attr = true;
     }
     int64_t band_m = 0;                                // the most positions one band returns per plane
@@ -3917,12 +3900,7 @@ int acx_query_ranks(acx_ctx *c, const acx_query_spec *spec, const void *params, 
     const size_t o_moff = (slab_floats * 4 + 7) & ~(size_t)7, o_col = o_moff + 8 * (size_t)(n_queries + 1), o_q = o_col + (col ? 8 * (size_t)Q.n : 0),
                  o_m = o_q + 4 * (size_t)n_queries, o_posn = o_m + 4 * (size_t)M, o_pos = o_posn + (posn ? 4 * (size_t)Q.n : 0),
                  o_flag = o_pos + 4 * (size_t)Q.w * (size_t)band_m, total = o_flag + (size_t)R * Q.w;
-    char *d_mem = nullptr;
-    {
-        const hipError_t e = hipMalloc((void **)&d_mem, total);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, ACX_ERR_NOMEM, std::string("query_ranks: ") + hipGetErrorString(e)); }
-    }
-    auto body = [&]() -> int {
+    return with_device_block(c, "query_ranks", total, [&](char *d_mem) -> int {
         float *d_slab = reinterpret_cast<float *>(d_mem);
         const int64_t *d_moff = reinterpret_cast<const int64_t *>(d_mem + o_moff);
         const double *d_col = col ? reinterpret_cast<const double *>(d_mem + o_col) : nullptr;
@@ -3937,35 +3915,22 @@ int acx_query_ranks(acx_ctx *c, const acx_query_spec *spec, const void *params, 
         if (M > 0) ACX_HIP(c, hipMemcpyAsync(d_mem + o_m, mates, 4 * (size_t)M, hipMemcpyHostToDevice, c->stream));
         if (posn) ACX_HIP(c, hipMemcpyAsync(d_mem + o_posn, posn, 4 * (size_t)Q.n, hipMemcpyHostToDevice, c->stream));
         const bool in_lds = Q.n <= acx::RANK_ROW_LDS;
-        const size_t lds = acx::QUERY_RANK_LDS_FIXED + (in_lds ? 16 * (size_t)((Q.n + 3) / 4) : 0);
-        std::vector<int32_t> pairs;
-        std::vector<int64_t> idx;
-        for (int r0 = 0; r0 < n_queries; r0 += R) {
-            const int nr = std::min(R, n_queries - r0);
-            int rcb = query_run_band(c, Q, queries + r0, nr, nullptr, Q.n, d_slab, (int64_t)R * per_row, pairs, idx);
-            if (rcb != ACX_OK) return rcb;
-            const int64_t mb = moff[r0 + nr] - moff[r0];       // this band's positions per plane
-            {
+        const size_t lds = acx::RANK_COUNT_LDS_FIXED + (in_lds ? 16 * (size_t)((Q.n + 3) / 4) : 0);
+        // (a band's positions per plane: moff[r0 + nr] - moff[r0])
+        return query_for_bands(c, Q, queries, n_queries, R, nullptr, Q.n, d_slab, per_row,
+            [&](int r0, int nr) {
                 ProfScope ps(c, KS_QRANK, (int64_t)nr * Q.n * Q.w);
-                if (in_lds)
-                    hipLaunchKernelGGL((acx::query_rank_kernel<true>), dim3((unsigned)nr, (unsigned)Q.w), dim3(acx::RANK_THREADS), lds, c->stream,
-                                       d_slab, Q.n, Q.w, d_q + r0, d_col, Q.mode, d_posn, d_moff + r0, d_mates + moff[r0], moff[r0], mb, d_pos, d_flag);
-                else
-                    hipLaunchKernelGGL((acx::query_rank_kernel<false>), dim3((unsigned)nr, (unsigned)Q.w), dim3(acx::RANK_THREADS), lds, c->stream,
-                                       d_slab, Q.n, Q.w, d_q + r0, d_col, Q.mode, d_posn, d_moff + r0, d_mates + moff[r0], moff[r0], mb, d_pos, d_flag);
-            }
-            ACX_LAUNCHES_OK(c);
-            for (int e = 0; e < Q.w && mb > 0; ++e)
-                ACX_HIP(c, hipMemcpyAsync(out_pos + (size_t)e * M + moff[r0], d_pos + (size_t)e * mb, 4 * (size_t)mb, hipMemcpyDeviceToHost, c->stream));
-            ACX_HIP(c, hipMemcpyAsync(out_flag + (size_t)r0 * Q.w, d_flag, (size_t)nr * Q.w, hipMemcpyDeviceToHost, c->stream));
-            ACX_HIP(c, hipStreamSynchronize(c->stream));
-        }
-        return ACX_OK;
-    };
-    rc = body();
-    if (rc != ACX_OK) quiesce(c); else drain_profile(c);
-    (void)hipFree(d_mem);
-    return rc;
+                ACX_LAUNCH_IN_LDS(query_rank_kernel, in_lds, dim3((unsigned)nr, (unsigned)Q.w), lds, d_slab, Q.n, Q.w, d_q + r0, d_col, Q.mode, d_posn,
+                                  d_moff + r0, d_mates + moff[r0], moff[r0], moff[r0 + nr] - moff[r0], d_pos, d_flag);
+            },
+            [&](int r0, int nr) -> int {
+                const int64_t mb = moff[r0 + nr] - moff[r0];
+                for (int e = 0; e < Q.w && mb > 0; ++e)
+                    ACX_HIP(c, hipMemcpyAsync(out_pos + (size_t)e * M + moff[r0], d_pos + (size_t)e * mb, 4 * (size_t)mb, hipMemcpyDeviceToHost, c->stream));
+                ACX_HIP(c, hipMemcpyAsync(out_flag + (size_t)r0 * Q.w, d_flag, (size_t)nr * Q.w, hipMemcpyDeviceToHost, c->stream));
+                return ACX_OK;
+            });
+    });
 }
 
 // ---- device buffers for hosts that hold no GPU runtime of their own ------------------------------------------

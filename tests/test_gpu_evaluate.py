@@ -62,7 +62,7 @@ def _positions(fin, queries, moff, mates, posn):
 def test_query_ranks_equal_reference(ctx, name):
     """Positions and flags for all five algorithms, col_mode 0 / 1 / 2, posn given and None: tests/_rank_ref.py on the
     raw rows of the pair-list entry points finished by tests/_query_ref.py.  One query lists every other track, one
-    lists nothing, one comes twice with different lists."""
+    lists nothing, one comes twice with different lists.  acx_rank_columns on the same finished rows must agree."""
     algo, sym, params, pair_fn, n, w, col, _ = _setup(ctx, name)
     queries = [7, 2, 9, 7, 5]
     lists = [[c for c in range(n) if c != 7], [], [1, 3], [0, 10], [8, 4, 6]]
@@ -81,6 +81,9 @@ def test_query_ranks_equal_reference(ctx, name):
                 print(name, mode, e, "flagged rows", int(wf.sum()))
                 assert np.array_equal(flag[:, e], wf), (mode, e)
                 assert np.array_equal(pos[e], wp), (mode, e)
+                # the two APIs on the same finished rows: acx_rank_columns gives these positions and flags
+                rp, rf = ctx.rank_columns(_matrix(fin, queries, n), queries, moff, mates, posn=posn)
+                assert np.array_equal(pos[e], rp) and np.array_equal(flag[:, e], rf), ("rank_columns", mode, e)
                 p2, f2 = _positions(fin, queries, moff, mates, posn)
                 assert np.array_equal(p2, wp) and np.array_equal(f2, wf), "the two numpy statements agree"
                 flagged += int(wf.sum())

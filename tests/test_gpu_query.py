@@ -121,10 +121,24 @@ def test_rows_equal_pair_list(ctx, name):
                     k += 1
 
 
+def _assert_topk_rows_agrees(ctx, fin, n, k, gi, gs, what):
+    """The two APIs on the same finished rows: acx_topk_rows over the rows of query_scores, placed in an (n, n) matrix,
+    gives the indices of query_topk and the bits of its scores (NaN compared as bits)."""
+    for e in range(fin.shape[0]):
+        D = np.zeros((n, n), np.float32)
+        D[np.asarray(QUERIES)] = fin[e]
+        ri, rs = ctx.topk_rows(D, k, rows=QUERIES)
+        assert np.array_equal(gi[:, e], ri), ("topk_rows", k, e, what)
+        assert _same(gs[:, e], rs), ("topk_rows", k, e, what)
+
+
 @pytest.mark.parametrize("name", ALGOS)
 def test_topk_equals_reference(ctx, name):
     algo, sym, params, pair_fn, n, w, col, _ = _setup(ctx, name)
     raw = _raw_rows(pair_fn, n, QUERIES, sym, w)
+    fin = {0: ctx.query_scores(algo, sym, params, QUERIES)}
+    for mode in (1, 2):
+        fin[mode] = ctx.query_scores(algo, sym, params, QUERIES, col=col, col_mode=mode)
     cand = np.array(sorted(set(range(1, n, 2)) | {2, 7}), np.int32)      # holds two of the queries (7 and 2) and misses others
     for k in (1, 10, n - 1, n + 5):
         for cands in (None, cand):
@@ -136,6 +150,8 @@ def test_topk_equals_reference(ctx, name):
                 assert _same(gs[:, e], ws), (k, e, cands is not None)
             for i, q in enumerate(QUERIES):
                 assert q not in gi[i]
+            if cands is None:
+                _assert_topk_rows_agrees(ctx, fin[0], n, k, gi, gs, 0)
     gi, _ = ctx.query_topk(algo, sym, params, QUERIES, n + 5)
     assert np.all(gi[:, :, n - 1:] == -1) and np.all(gi[:, :, :n - 1] >= 0)
     for mode in (1, 2):
@@ -144,6 +160,8 @@ def test_topk_equals_reference(ctx, name):
             for e in range(w):
                 wi, ws = qref.topk(raw[e], QUERIES, 10, candidates=cands, col=col, col_mode=mode)
                 assert np.array_equal(gi[:, e], wi) and _same(gs[:, e], ws), (mode, e)
+            if cands is None:
+                _assert_topk_rows_agrees(ctx, fin[mode], n, 10, gi, gs, mode)
     gi, gs = ctx.query_topk(algo, sym, params, QUERIES, 3, candidates=np.zeros(0, np.int32))
     assert np.all(gi == -1) and np.all(np.isnan(gs))
 
