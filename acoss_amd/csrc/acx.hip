@@ -31,8 +31,11 @@
 #include "rank_kernels.hpp"
 #include "query_kernels.hpp"
 #include "grid.hpp"
+#include "device_buffer.hpp"
 
 using acx::PairDesc;
+using acx::DeviceBuffer;
+using acx::PinnedBuffer;
 
 namespace {
 
@@ -56,11 +59,11 @@ struct PendingEvent {
 struct Serra09Slot {
     std::vector<PairDesc> pd, sorted;
     std::vector<int> perm;
-    PairDesc *d_pd = nullptr; size_t pd_cap = 0;
-    float *d_out = nullptr;   size_t out_cap = 0;
-    float *h_out = nullptr;   size_t h_cap = 0;      // pinned
-    int64_t *h_idx = nullptr; size_t hidx_cap = 0;   // pinned: destinations of the batch's scores (grid runs)
-    int64_t *d_idx = nullptr; size_t didx_cap = 0;
+    DeviceBuffer<PairDesc> d_pd;
+    DeviceBuffer<float> d_out;
+    PinnedBuffer<float> h_out;
+    PinnedBuffer<int64_t> h_idx;                     // destinations of the batch's scores (grid runs)
+    DeviceBuffer<int64_t> d_idx;
     hipEvent_t done = nullptr;
     hipEvent_t cls_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // a size class's recurrence bitmap is complete
     bool busy = false;
@@ -95,15 +98,15 @@ struct acx_ctx {
     std::vector<int64_t> h_off;
     int32_t n_tracks = 0, dim = 0;
     // f64 pool (SiMPle)
-    double *d_frames64 = nullptr;
-    int64_t *d_toff64 = nullptr;
-    double *d_prof64 = nullptr;
-    double *d_wn64 = nullptr;     // window norms of the f64 pool for subsequence length wn64_L (SiMPle)
+    DeviceBuffer<double> d_frames64;
+    DeviceBuffer<int64_t> d_toff64;
+    DeviceBuffer<double> d_prof64;
+    DeviceBuffer<double> d_wn64;  // window norms of the f64 pool for subsequence length wn64_L (SiMPle)
     int wn64_L = 0;
     std::vector<int64_t> h_off64;
     int32_t n_tracks64 = 0;
-    int32_t *d_pairs = nullptr; size_t pairs_cap = 0;
-    double *d_out64 = nullptr;  size_t out64_cap = 0;
+    DeviceBuffer<int32_t> d_pairs;
+    DeviceBuffer<double> d_out64;
     // EarlyFusion pool
     float *d_ef[3] = {nullptr, nullptr, nullptr};
     unsigned short *d_efs[3] = {nullptr, nullptr, nullptr};   // mfcc / ssm / chroma block features as three-term bf16 splits
@@ -124,8 +127,8 @@ struct acx_ctx {
     std::vector<uint8_t> ftm_filled;                  // per track of the open pool: handed over by acx_ftm2d_pool_tracks yet?
     acx_ftm2d_params ftm_params = {0.0, 0.0, 0, 0};
     // ranking of score rows (acx_rank_columns / acx_topk_rows): two staging slots of whole rows, pinned + device (grow-only)
-    float *rank_h[2] = {nullptr, nullptr}; size_t rank_h_cap[2] = {0, 0};
-    float *rank_d[2] = {nullptr, nullptr}; size_t rank_d_cap[2] = {0, 0};
+    PinnedBuffer<float> rank_h[2];
+    DeviceBuffer<float> rank_d[2];
     hipEvent_t rank_ev[2] = {nullptr, nullptr};
     bool rank_attr = false;
     bool query_attr = false;                          // query_topk_kernel's dynamic LDS limit is raised (acx_query_topk)
@@ -133,41 +136,37 @@ struct acx_ctx {
     // multi-GPU inside the library (acx_comm_*): one RCCL communicator rank per context
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
-    std::vector<void *> dev_bufs;                      // acx_dev_alloc'ed buffers still alive (freed with the context)
+    std::vector<DeviceBuffer<char>> dev_bufs;          // acx_dev_alloc'ed buffers still alive (freed with the context)
     int32_t ef_dims[3] = {0, 0, 0};
-    acx::EfPair *d_efpd = nullptr; size_t efpd_cap = 0;
+    DeviceBuffer<acx::EfPair> d_efpd;
     // rectangles of the rectangle GEMM (ef_gemm_rect_bf16x3_kernel): row / column groups, rectangles, pair tables
-    acx::EfSegGroup *d_segr = nullptr; size_t segr_cap = 0;
-    acx::EfSegGroup *d_segc = nullptr; size_t segc_cap = 0;
-    acx::EfSegRect *d_rects = nullptr; size_t rects_cap = 0;
-    int32_t *d_ptab = nullptr;         size_t ptab_cap = 0;
-    acx::EfSegWg *d_segw = nullptr;    size_t segw_cap = 0;
-    acx::EfSegWg *d_segw2 = nullptr;   size_t segw2_cap = 0;
-    acx::EfSegWg *d_segw3 = nullptr;   size_t segw3_cap = 0;
+    DeviceBuffer<acx::EfSegGroup> d_segr, d_segc;
+    DeviceBuffer<acx::EfSegRect> d_rects;
+    DeviceBuffer<int32_t> d_ptab;
+    DeviceBuffer<acx::EfSegWg> d_segw, d_segw2, d_segw3;
     int launch_fail_stat = -1;                         // kernel family (KS_*) of the first failed launch since the last check
     bool ef_rect_attr = false;
-    unsigned *d_efctr = nullptr;                       // tile counters of the persistent rectangle GEMMs (one per launch of a batch)
+    DeviceBuffer<unsigned> d_efctr;                    // tile counters of the persistent rectangle GEMMs (one per launch of a batch)
     int n_cu = 0;
     int ef_split_fmt = 0;                             // what d_efs holds: 0 three bf16 terms, 1 two fp16 terms of x / d_efsc[row]
     float *d_efsc[3] = {nullptr, nullptr, nullptr};   // fmt 1: the power-of-two scale of every pool row (ef_rowscale_kernel)
     // scratch (grow-only)
-    float *d_scratch = nullptr; size_t scratch_cap = 0;   // floats
-    float *d_thr = nullptr;     size_t thr_cap = 0;
-    unsigned *d_efbits = nullptr; size_t efbits_cap = 0;     // EarlyFusion: the binarised matrices of a batch (ef_rowstat_kernel -> sw_bits_kernel)
+    DeviceBuffer<float> d_scratch, d_thr;
+    DeviceBuffer<unsigned> d_efbits;                         // EarlyFusion: the binarised matrices of a batch (ef_rowstat_kernel -> sw_bits_kernel)
     Serra09Slot slot[2];
-    float *d_out = nullptr;     size_t out_cap = 0;
-    unsigned long long *d_bits = nullptr; size_t bits_cap = 0;   // recurrence bitmaps (u64 words)
+    DeviceBuffer<float> d_out;
+    DeviceBuffer<unsigned long long> d_bits;              // recurrence bitmaps (u64 words)
     int64_t scratch_limit = 0;                            // bytes
     size_t total_mem = 0;
     // the pair grid: last plan (a pure function of lengths and spec; sorting 10^4 tiles per call is what the cache saves)
     std::vector<int64_t> plan_len;
     acx_grid_spec plan_spec = {-1, 0, 0, 0};
     std::vector<acx_grid_tile> plan_tiles;
-    int64_t *d_idx = nullptr;   size_t idx_cap = 0;       // score destinations of a chunk of pairs (grid runs)
-    int64_t *h_idx = nullptr;   size_t hidx_cap = 0;      // pinned staging of the same
-    void *d_tiles = nullptr;    size_t tiles_cap = 0;     // tile descriptors of a chunk (device-side pair enumeration), bytes
+    DeviceBuffer<int64_t> d_idx;                          // score destinations of a chunk of pairs (grid runs)
+    PinnedBuffer<int64_t> h_idx;                          // pinned staging of the same
+    DeviceBuffer<char> d_tiles;                           // tile descriptors of a chunk (device-side pair enumeration), bytes
     int nonfinite_policy = ACX_NONFINITE_REJECT;          // what an upload does with NaN / Inf features
-    int *d_nf = nullptr;                                  // {first offending track, values zeroed} of the upload scan
+    DeviceBuffer<int> d_nf;                               // {first offending track, values zeroed} of the upload scan
     int64_t nf_zeroed = 0;                                // values zeroed by the last upload
     // profiling
     bool prof = false;
@@ -196,17 +195,29 @@ int fail(acx_ctx *c, int code, const std::string &msg)
             return fail(ctx, ACX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-template <typename T>
-int ensure(acx_ctx *c, T *&ptr, size_t &cap, size_t need)
+// The one place where a failed (grow-only) allocation becomes ACX_ERR_NOMEM.
+template <typename T, bool PINNED>
+int ensure(acx_ctx *c, DeviceBuffer<T, PINNED> &buf, size_t need)
 {
-    if (need <= cap) return ACX_OK;
-    if (ptr) { ACX_HIP(c, hipFree(ptr)); ptr = nullptr; cap = 0; }
-    void *p = nullptr;
-    hipError_t e = hipMalloc(&p, need * sizeof(T));
+    const hipError_t e = buf.grow(need);
     if (e != hipSuccess)
-        return fail(c, ACX_ERR_NOMEM, "hipMalloc of " + std::to_string(need * sizeof(T)) + " bytes failed: " + hipGetErrorString(e));
-    ptr = static_cast<T *>(p);
-    cap = need;
+        return fail(c, ACX_ERR_NOMEM, std::string(PINNED ? "hipHostMalloc of " : "hipMalloc of ") + std::to_string(need * sizeof(T)) +
+                                          " bytes failed: " + hipGetErrorString(e));
+    return ACX_OK;
+}
+
+// Whole tracks [t0, t1) at a time: a slice takes at least one track and grows while fits(t0, t1) holds and it has fewer than
+// max_tracks tracks; body(t0, t1) returns an ACX code, the first that is not ACX_OK ends the loop.
+template <typename Fits, typename Body>
+int for_track_slices(int n_tracks, int max_tracks, Fits fits, Body body)
+{
+    for (int t0 = 0; t0 < n_tracks;) {
+        int t1 = t0 + 1;
+        while (t1 < n_tracks && t1 - t0 < max_tracks && fits(t0, t1 + 1)) ++t1;
+        const int rc = body(t0, t1);
+        if (rc != ACX_OK) return rc;
+        t0 = t1;
+    }
     return ACX_OK;
 }
 
@@ -273,7 +284,7 @@ int scan_nonfinite(acx_ctx *c, const char *who, const char *what, T *d_x, int64_
                    const int64_t *d_off, int n_tracks, bool nan_zero_always = false, int track_base = 0)
 {
     if (n <= 0) return ACX_OK;
-    if (!c->d_nf) ACX_HIP(c, hipMalloc((void **)&c->d_nf, 2 * sizeof(int)));
+    if (const int rc = ensure(c, c->d_nf, 2); rc != ACX_OK) return rc;
     const int init[2] = {0x7fffffff, 0};
     ACX_HIP(c, hipMemcpyAsync(c->d_nf, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
     const bool zero = c->nonfinite_policy == ACX_NONFINITE_ZERO;
@@ -370,8 +381,10 @@ int ensure_tau(acx_ctx *c, int tau)
     c->normtab_m = 0; c->normtab_span = -1;
     c->pool_tau = 0;
     const int n = c->n_tracks;
+    DeviceBuffer<float> frames, frot;            // built here and handed to the context when complete: a failure leaves no half-built pool
+    DeviceBuffer<int64_t> toff;
     if (tau == 1) {
-        c->d_frames = c->d_frames0; c->d_toff = c->d_toff0; c->h_off = c->h_off0;
+        c->h_off = c->h_off0;
     } else {
         c->h_off.assign((size_t)n + 1, 0);
         int maxT = 1;
@@ -382,28 +395,32 @@ int ensure_tau(acx_ctx *c, int tau)
             maxT = std::max<int>(maxT, (int)Td);
         }
         const int64_t total = c->h_off[n];
-        ACX_HIP(c, hipMalloc((void **)&c->d_frames, sizeof(float) * std::max<int64_t>(1, total) * acx::NBIN));
-        ACX_HIP(c, hipMalloc((void **)&c->d_toff, sizeof(int64_t) * (n + 1)));
-        ACX_HIP(c, hipMemcpy(c->d_toff, c->h_off.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
+        ACX_HIP(c, frames.grow((size_t)std::max<int64_t>(1, total) * acx::NBIN));
+        ACX_HIP(c, toff.grow((size_t)n + 1));
+        ACX_HIP(c, hipMemcpy(toff, c->h_off.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
         if (total > 0) {
             hipLaunchKernelGGL(acx::decimate_kernel, dim3(n, (maxT * acx::NBIN + 255) / 256), dim3(256), 0, c->stream,
-                               c->d_frames0, c->d_toff0, c->d_toff, c->d_frames, tau);
+                               c->d_frames0, c->d_toff0, toff.get(), frames.get(), tau);
             ACX_HIP(c, hipGetLastError());
         }
     }
     const int64_t total = c->h_off[n];
+    const float *active = tau == 1 ? c->d_frames0 : frames.get();
     // rotated copy of the active pool: the band kernel loads its MFMA operands from it (12 bytes per
     // lane per 16-frame tile, already in the rotated chain order) -- 144 B per frame
-    ACX_HIP(c, hipMalloc((void **)&c->d_frot, sizeof(float) * (std::max<int64_t>(1, total) + 2 * POOL_SLACK) * acx::FROT));
-    ACX_HIP(c, hipMemsetAsync(c->d_frot, 0, sizeof(float) * POOL_SLACK * acx::FROT, c->stream));
-    ACX_HIP(c, hipMemsetAsync(c->d_frot + (POOL_SLACK + total) * acx::FROT, 0, sizeof(float) * POOL_SLACK * acx::FROT, c->stream));
+    ACX_HIP(c, frot.grow((size_t)(std::max<int64_t>(1, total) + 2 * POOL_SLACK) * acx::FROT));
+    ACX_HIP(c, hipMemsetAsync(frot, 0, sizeof(float) * POOL_SLACK * acx::FROT, c->stream));
+    ACX_HIP(c, hipMemsetAsync(frot + (POOL_SLACK + total) * acx::FROT, 0, sizeof(float) * POOL_SLACK * acx::FROT, c->stream));
     if (total > 0) {
         const int64_t nout = total * acx::FROT;
         hipLaunchKernelGGL(acx::rotpool_kernel, dim3((unsigned)std::min<int64_t>((nout + 255) / 256, 1 << 22)), dim3(256), 0, c->stream,
-                           c->d_frames, c->d_frot + POOL_SLACK * acx::FROT, total);
+                           active, frot + POOL_SLACK * acx::FROT, total);
         ACX_HIP(c, hipGetLastError());
     }
     ACX_HIP(c, hipStreamSynchronize(c->stream));
+    c->d_frames = tau == 1 ? c->d_frames0 : frames.release();
+    c->d_toff = tau == 1 ? c->d_toff0 : toff.release();
+    c->d_frot = frot.release();
     c->pool_tau = tau;
     return ACX_OK;
 }
@@ -428,17 +445,14 @@ int ensure_f16pool(acx_ctx *c)
     // norms, made from the exact f32 values, would no longer match the Gram.  HPCP / CREMA frames are normalised to a
     // maximum of 1; a pool whose largest value lies outside [2^-8, 2^15] is refused (rescale it, or use ACX_ARITH_EXACT).
     if (total > 0) {
-        unsigned *d_m = nullptr, h_m = 0u;
-        ACX_HIP(c, hipMalloc((void **)&d_m, sizeof(unsigned)));
-        hipError_t em = hipMemsetAsync(d_m, 0, sizeof(unsigned), c->stream);
-        if (em == hipSuccess) {
-            hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)std::min<int64_t>((total * acx::NBIN + 255) / 256, 4096)), dim3(256), 0, c->stream,
-                               c->d_frames, total * acx::NBIN, d_m);
-            em = hipMemcpyAsync(&h_m, d_m, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream);
-        }
-        if (em == hipSuccess) em = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_m);                            // (on every path: a failed copy used to leak it)
-        ACX_HIP(c, em);
+        DeviceBuffer<unsigned> d_m;
+        unsigned h_m = 0u;
+        ACX_HIP(c, d_m.grow(1));
+        ACX_HIP(c, hipMemsetAsync(d_m, 0, sizeof(unsigned), c->stream));
+        hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)std::min<int64_t>((total * acx::NBIN + 255) / 256, 4096)), dim3(256), 0, c->stream,
+                           c->d_frames, total * acx::NBIN, d_m.get());
+        ACX_HIP(c, hipMemcpyAsync(&h_m, d_m, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
         float mx;
         memcpy(&mx, &h_m, sizeof(mx));
         if (!(mx >= 0.00390625f && mx <= 32768.0f))
@@ -446,15 +460,17 @@ int ensure_f16pool(acx_ctx *c)
                                                     std::to_string(mx) + "): rescale the pool or use the exact arithmetic");
     }
     const size_t halfs = (size_t)(std::max<int64_t>(1, total) + 2 * POOL_SLACK) * acx::FH;
-    const hipError_t e = hipMalloc((void **)&c->d_fh, sizeof(_Float16) * halfs);
-    if (e != hipSuccess) { c->d_fh = nullptr; return fail(c, ACX_ERR_NOMEM, std::string("serra09: the f16 operand pool does not fit the device: ") + hipGetErrorString(e)); }
-    ACX_HIP(c, hipMemsetAsync(c->d_fh, 0, sizeof(_Float16) * halfs, c->stream));
+    DeviceBuffer<_Float16> fh;                         // the context's once it is complete
+    const hipError_t e = fh.grow(halfs);
+    if (e != hipSuccess) return fail(c, ACX_ERR_NOMEM, std::string("serra09: the f16 operand pool does not fit the device: ") + hipGetErrorString(e));
+    ACX_HIP(c, hipMemsetAsync(fh, 0, sizeof(_Float16) * halfs, c->stream));
     if (total > 0) {
         hipLaunchKernelGGL(acx::rotpool_f16_kernel, dim3((unsigned)std::min<int64_t>((total * 12 + 255) / 256, 1 << 22)), dim3(256), 0, c->stream,
-                           c->d_frames, c->d_fh + POOL_SLACK * acx::FH, total);
+                           c->d_frames, fh + POOL_SLACK * acx::FH, total);
         ACX_HIP(c, hipGetLastError());
     }
     ACX_HIP(c, hipStreamSynchronize(c->stream));
+    c->d_fh = fh.release();
     return ACX_OK;
 }
 
@@ -465,6 +481,7 @@ int ensure_normtab(acx_ctx *c, const acx_serra09_params &p)
     if (c->d_normtab && c->normtab_m == p.m && c->normtab_span == span) return ACX_OK;
     if (c->d_normtab) { ACX_HIP(c, hipFree(c->d_normtab)); c->d_normtab = nullptr; }
     if (c->d_noff) { ACX_HIP(c, hipFree(c->d_noff)); c->d_noff = nullptr; }
+    c->normtab_m = 0; c->normtab_span = -1;            // (a failure below must not leave the old key on a new, unfinished table)
     std::vector<int64_t> noff((size_t)c->n_tracks + 1);
     int64_t tot = 0;
     int maxM = 1;
@@ -617,6 +634,37 @@ int validate_serra09_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, const ac
     return ACX_OK;
 }
 
+// One alignment sweep (Qmax, or Dmax) over the recurrence bitmaps of B pairs, one wave per pair: pair k's score goes to dst[k w].
+// cols: bitmap columns a lane owns -- 8 / 16 / 32 for rows of up to 505 / 1017 / 2041 cells, 0: the long kernel (any length; its strip
+// records live in `scratch`).  multi: 16 / 32 packs four / two pairs into a wave (rows of <= 249 / 505 cells, the default penalties
+// only); 0: one wave per pair.  The default penalties (0.5 / 0.5) take the packed 16-bit integer DP in half-units, two cells per
+// instruction.
+void launch_qmax_sweep(hipStream_t st, const PairDesc *pd, int B, const unsigned long long *bits, float *scratch, float *dst, int w,
+                       float gamma_o, float gamma_e, int dp_start, bool dmax, int cols, int multi)
+{
+#define ACX_QB3(E_, D_, C_) hipLaunchKernelGGL((acx::qmax_bits_kernel<E_, D_, C_>), dim3(B), dim3(64), 0, st, pd, bits, dst, w, gamma_o, gamma_e, dp_start)
+#define ACX_QBL(E_, D_) hipLaunchKernelGGL((acx::qmax_bits_long_kernel<E_, D_>), dim3(B), dim3(64), 0, st, pd, bits, scratch, dst, w, gamma_o, gamma_e, dp_start)
+#define ACX_QB(E_, D_) do { if (cols == 8) ACX_QB3(E_, D_, 8); else if (cols == 16) ACX_QB3(E_, D_, 16); else if (cols == 32) ACX_QB3(E_, D_, 32); \
+                            else ACX_QBL(E_, D_); } while (0)
+#define ACX_QH(C_, D_) hipLaunchKernelGGL((acx::qmax_bits_h16_kernel<C_, D_>), dim3(B), dim3(64), 0, st, pd, bits, dst, w, dp_start)
+#define ACX_QM(G_, D_) hipLaunchKernelGGL((acx::qmax_bits_h16_multi_kernel<G_, D_>), dim3((B + 64 / G_ - 1) / (64 / G_)), dim3(64), 0, st, \
+                                          pd, B, bits, dst, w, dp_start)
+    const bool eqg = gamma_o == gamma_e;
+    if (eqg && gamma_o == 0.5f && cols != 0) {
+        if (multi == 16) { if (dmax) ACX_QM(16, true); else ACX_QM(16, false); }
+        else if (multi == 32) { if (dmax) ACX_QM(32, true); else ACX_QM(32, false); }
+        else if (dmax) { if (cols == 8) ACX_QH(8, true); else if (cols == 16) ACX_QH(16, true); else ACX_QH(32, true); }
+        else { if (cols == 8) ACX_QH(8, false); else if (cols == 16) ACX_QH(16, false); else ACX_QH(32, false); }
+    }
+    else if (eqg) { if (dmax) ACX_QB(true, true); else ACX_QB(true, false); }
+    else { if (dmax) ACX_QB(false, true); else ACX_QB(false, false); }
+#undef ACX_QM
+#undef ACX_QH
+#undef ACX_QB
+#undef ACX_QBL
+#undef ACX_QB3
+}
+
 int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
                      const DebugOut *dbg, bool both, const DevDst *dd);
 
@@ -737,26 +785,16 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         if (cls_begin[NC] > 0 && p.arith == ACX_ARITH_F16X2 && (rc = ensure_f16pool(c)) != ACX_OK) return rc;
         // (the band kernel reads its column thresholds 16 bytes at a time without a bounds check, up to
         // 64 x 32 floats behind a pair's column-threshold row: the arena carries that much slack)
-        if ((rc = ensure(c, c->d_scratch, c->scratch_cap, (size_t)std::max<int64_t>(used, 1))) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_bits, c->bits_cap, (size_t)std::max<int64_t>(used_bits, 1))) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_thr, c->thr_cap, (size_t)used_thr + 64 * 32 + 16)) != ACX_OK) return rc;
-        if ((rc = ensure(c, S.d_pd, S.pd_cap, (size_t)B)) != ACX_OK) return rc;
-        if ((rc = ensure(c, S.d_out, S.out_cap, (size_t)2 * B)) != ACX_OK) return rc;
-        if ((size_t)2 * B > S.h_cap) {
-            if (S.h_out) ACX_HIP(c, hipHostFree(S.h_out));
-            S.h_out = nullptr; S.h_cap = 0;
-            ACX_HIP(c, hipHostMalloc((void **)&S.h_out, sizeof(float) * 2 * (size_t)B, hipHostMallocDefault));
-            S.h_cap = (size_t)2 * B;
-        }
+        if ((rc = ensure(c, c->d_scratch, (size_t)std::max<int64_t>(used, 1))) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_bits, (size_t)std::max<int64_t>(used_bits, 1))) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_thr, (size_t)used_thr + 64 * 32 + 16)) != ACX_OK) return rc;
+        if ((rc = ensure(c, S.d_pd, (size_t)B)) != ACX_OK) return rc;
+        if ((rc = ensure(c, S.d_out, (size_t)2 * B)) != ACX_OK) return rc;
+        if ((rc = ensure(c, S.h_out, (size_t)2 * B)) != ACX_OK) return rc;
         ACX_HIP(c, hipMemcpyAsync(S.d_pd, pd.data(), sizeof(PairDesc) * B, hipMemcpyHostToDevice, c->stream));
         if (dd) {     // destinations of the batch's scores (staged here: the scatter may run on the second stream)
-            if ((size_t)B > S.hidx_cap) {
-                if (S.h_idx) ACX_HIP(c, hipHostFree(S.h_idx));
-                S.h_idx = nullptr; S.hidx_cap = 0;
-                ACX_HIP(c, hipHostMalloc((void **)&S.h_idx, sizeof(int64_t) * (size_t)B, hipHostMallocDefault));
-                S.hidx_cap = (size_t)B;
-            }
-            if ((rc = ensure(c, S.d_idx, S.didx_cap, (size_t)B)) != ACX_OK) return rc;
+            if ((rc = ensure(c, S.h_idx, (size_t)B)) != ACX_OK) return rc;
+            if ((rc = ensure(c, S.d_idx, (size_t)B)) != ACX_OK) return rc;
             for (int k2 = 0; k2 < B; ++k2) S.h_idx[k2] = dd->idx[k0 + perm[k2]];
             ACX_HIP(c, hipMemcpyAsync(S.d_idx, S.h_idx, sizeof(int64_t) * B, hipMemcpyHostToDevice, c->stream));
         }
@@ -843,7 +881,6 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         }
         {   // K3: one sweep per requested alignment over the SAME recurrence bitmap:
             // both == 0: Qmax or Dmax as p.dmax says; both == 1: out[2k] = Qmax, out[2k+1] = Dmax
-            const bool eqg = p.gamma_o == p.gamma_e;
             // one launch per size class: a lane owns 8 / 8 / 16 / 16 / 32 columns of rows up to 249 / 505 / 761 / 1017 / 2041 cells
             hipError_t wait_err = hipSuccess;            // (a failed cross-stream wait would let a sweep read an unfinished bitmap: reported, not ignored)
             auto sweep = [&](bool dmax, float *dst, hipStream_t qs) {
@@ -852,32 +889,11 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
                     if (Bc <= 0) continue;
                     if (use_q) { const hipError_t e_ = hipStreamWaitEvent(qs, S.cls_ev[cl], 0); if (e_ != hipSuccess) wait_err = e_; }
                     ProfScope ps(c, KS_QMAX, cls_cells[cl], qs);      // (its first event stands behind the wait)
-#define ACX_QB3(E_, D_, C_) hipLaunchKernelGGL((acx::qmax_bits_kernel<E_, D_, C_>), dim3(Bc), dim3(64), 0, qs, \
-                                               S.d_pd + b0, c->d_bits, dst + (size_t)b0 * w, w, p.gamma_o, p.gamma_e, p.dp_start)
-#define ACX_QBL(E_, D_) hipLaunchKernelGGL((acx::qmax_bits_long_kernel<E_, D_>), dim3(Bc), dim3(64), 0, qs, \
-                                           S.d_pd + b0, c->d_bits, c->d_scratch, dst + (size_t)b0 * w, w, p.gamma_o, p.gamma_e, p.dp_start)
-#define ACX_QB(E_, D_) do { if (cl <= 1) ACX_QB3(E_, D_, 8); else if (cl <= 3) ACX_QB3(E_, D_, 16); else if (cl == 4) ACX_QB3(E_, D_, 32); \
-                            else ACX_QBL(E_, D_); } while (0)
-                    // the default penalties (0.5 / 0.5): packed 16-bit integer DP in half-units, two cells per instruction
-                    if (eqg && p.gamma_o == 0.5f && cl < NC) {
-#define ACX_QH(C_, D_) hipLaunchKernelGGL((acx::qmax_bits_h16_kernel<C_, D_>), dim3(Bc), dim3(64), 0, qs, \
-                                          S.d_pd + b0, c->d_bits, dst + (size_t)b0 * w, w, p.dp_start)
-                        // rows of <= 249 / 505 cells: four / two pairs per wave (qmax_bits_h16_multi_kernel; ACX_QMAX_MULTI=0: one wave per pair)
-                        static const bool multi = [] { const char *e = getenv("ACX_QMAX_MULTI"); return !(e && e[0] == '0'); }();
-#define ACX_QM(G_, D_) hipLaunchKernelGGL((acx::qmax_bits_h16_multi_kernel<G_, D_>), dim3((Bc + 64 / G_ - 1) / (64 / G_)), dim3(64), 0, qs, \
-                                          S.d_pd + b0, Bc, c->d_bits, dst + (size_t)b0 * w, w, p.dp_start)
-                        if (multi && cl == 0) { if (dmax) ACX_QM(16, true); else ACX_QM(16, false); }
-                        else if (multi && cl == 1) { if (dmax) ACX_QM(32, true); else ACX_QM(32, false); }
-                        else if (dmax) { if (cl <= 1) ACX_QH(8, true); else if (cl <= 3) ACX_QH(16, true); else ACX_QH(32, true); }
-                        else { if (cl <= 1) ACX_QH(8, false); else if (cl <= 3) ACX_QH(16, false); else ACX_QH(32, false); }
-#undef ACX_QM
-#undef ACX_QH
-                    }
-                    else if (eqg) { if (dmax) ACX_QB(true, true); else ACX_QB(true, false); }
-                    else { if (dmax) ACX_QB(false, true); else ACX_QB(false, false); }
-#undef ACX_QB
-#undef ACX_QBL
-#undef ACX_QB3
+                    // the default penalties' packed kernels take rows of <= 249 / 505 cells four / two pairs per wave (ACX_QMAX_MULTI=0: one wave per pair)
+                    static const bool multi = [] { const char *e = getenv("ACX_QMAX_MULTI"); return !(e && e[0] == '0'); }();
+                    const int cols = cl <= 1 ? 8 : (cl <= 3 ? 16 : (cl == 4 ? 32 : 0));
+                    launch_qmax_sweep(qs, S.d_pd + b0, Bc, c->d_bits, c->d_scratch, dst + (size_t)b0 * w, w, p.gamma_o, p.gamma_e, p.dp_start, dmax,
+                                      cols, multi && cl == 0 ? 16 : (multi && cl == 1 ? 32 : 0));
                 }
             };
             if (both && use_q) {      // the two alignments of a pair read the same bitmap and write different halves of d_out: side by side
@@ -934,13 +950,8 @@ struct EfDebug { float *csm, *fused; int32_t *oti; int64_t which = 0; };      //
 static int stage_idx(acx_ctx *c, const int64_t *idx, int64_t n)
 {
     int rc;
-    if ((size_t)n > c->hidx_cap) {
-        if (c->h_idx) ACX_HIP(c, hipHostFree(c->h_idx));
-        c->h_idx = nullptr; c->hidx_cap = 0;
-        ACX_HIP(c, hipHostMalloc((void **)&c->h_idx, sizeof(int64_t) * (size_t)n, hipHostMallocDefault));
-        c->hidx_cap = (size_t)n;
-    }
-    if ((rc = ensure(c, c->d_idx, c->idx_cap, (size_t)n)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->h_idx, (size_t)n)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_idx, (size_t)n)) != ACX_OK) return rc;
     memcpy(c->h_idx, idx, sizeof(int64_t) * (size_t)n);
     ACX_HIP(c, hipMemcpyAsync(c->d_idx, c->h_idx, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     return ACX_OK;
@@ -1097,10 +1108,10 @@ static int launch_ef_gemms(acx_ctx *c, const SegBatch &seg, int B, int tiles_x, 
     }
     // the rectangle modes: the batch's rectangles to the device (the copies are staged before they return: `seg` may be rebuilt
     // for the next batch)
-    if ((rc = ensure(c, c->d_segr, c->segr_cap, seg.rowg.size())) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_segc, c->segc_cap, seg.colg.size())) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_rects, c->rects_cap, seg.rects.size())) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_ptab, c->ptab_cap, seg.ptab.size())) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_segr, seg.rowg.size())) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_segc, seg.colg.size())) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_rects, seg.rects.size())) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_ptab, seg.ptab.size())) != ACX_OK) return rc;
     ACX_HIP(c, hipMemcpyAsync(c->d_segr, seg.rowg.data(), sizeof(acx::EfSegGroup) * seg.rowg.size(), hipMemcpyHostToDevice, c->stream));
     ACX_HIP(c, hipMemcpyAsync(c->d_segc, seg.colg.data(), sizeof(acx::EfSegGroup) * seg.colg.size(), hipMemcpyHostToDevice, c->stream));
     ACX_HIP(c, hipMemcpyAsync(c->d_rects, seg.rects.data(), sizeof(acx::EfSegRect) * seg.rects.size(), hipMemcpyHostToDevice, c->stream));
@@ -1115,12 +1126,12 @@ static int launch_ef_gemms(acx_ctx *c, const SegBatch &seg, int B, int tiles_x, 
                               reinterpret_cast<const void *>(acx::ef_gemm_rect_persist_dma_kernel<0>),
                               reinterpret_cast<const void *>(acx::ef_gemm_rect_persist_dma_kernel<1>)})
             ACX_HIP(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, acx::EFR_LDS_BYTES));
-        ACX_HIP(c, hipMalloc((void **)&c->d_efctr, 2 * sizeof(unsigned)));
+        if ((rc = ensure(c, c->d_efctr, 2)) != ACX_OK) return rc;
         c->ef_rect_attr = true;
     }
     // a list of workgroup tiles to the device
-    auto upload = [c](const std::vector<acx::EfSegWg> &w, acx::EfSegWg *&d, size_t &cap) -> int {
-        const int rc = ensure(c, d, cap, w.size());
+    auto upload = [c](const std::vector<acx::EfSegWg> &w, DeviceBuffer<acx::EfSegWg> &d) -> int {
+        const int rc = ensure(c, d, w.size());
         if (rc != ACX_OK) return rc;
         ACX_HIP(c, hipMemcpyAsync(d, w.data(), sizeof(acx::EfSegWg) * w.size(), hipMemcpyHostToDevice, c->stream));
         return ACX_OK;
@@ -1130,7 +1141,7 @@ static int launch_ef_gemms(acx_ctx *c, const SegBatch &seg, int B, int tiles_x, 
     // the end of their reference track)
     auto rect_eucl = [&](RectKernel kern) -> int {
         if (seg.wgs2.empty()) return ACX_OK;
-        if ((rc = upload(seg.wgs2, c->d_segw2, c->segw2_cap)) != ACX_OK) return rc;
+        if ((rc = upload(seg.wgs2, c->d_segw2)) != ACX_OK) return rc;
         hipLaunchKernelGGL(kern, dim3((unsigned)seg.wgs2.size(), 1, 2), dim3(acx::EFR_THREADS), acx::EFR_LDS_BYTES, c->stream,
                            c->d_efs[0], c->d_efs[1], c->d_efn[0], c->d_efn[1], c->d_efpd, c->d_rects, c->d_segw2, c->d_segr, c->d_segc,
                            c->d_ptab, c->d_scratch, c->ef_kp[0], c->ef_kp[1], c->d_efsc[0], c->d_efsc[1]);
@@ -1138,7 +1149,7 @@ static int launch_ef_gemms(acx_ctx *c, const SegBatch &seg, int B, int tiles_x, 
     };
     auto rect_chroma = [&](RectKernel kern) -> int {
         if (seg.wgs3.empty()) return ACX_OK;
-        if ((rc = upload(seg.wgs3, c->d_segw3, c->segw3_cap)) != ACX_OK) return rc;
+        if ((rc = upload(seg.wgs3, c->d_segw3)) != ACX_OK) return rc;
         hipLaunchKernelGGL(kern, dim3((unsigned)seg.wgs3.size(), 1, 1), dim3(acx::EFR_THREADS), acx::EFR_LDS_BYTES, c->stream,
                            c->d_efs[2], c->d_efs[2], (const float *)nullptr, (const float *)nullptr, c->d_efpd, c->d_rects, c->d_segw3,
                            c->d_segr, c->d_segc, c->d_ptab, c->d_scratch, c->ef_kp[2], c->ef_kp[2], c->d_efsc[2], c->d_efsc[2]);
@@ -1147,7 +1158,7 @@ static int launch_ef_gemms(acx_ctx *c, const SegBatch &seg, int B, int tiles_x, 
     // chroma on f32 MFMAs over the 128 x 128-cell tiles of wgs
     auto f32_chroma = [&]() -> int {
         if (seg.wgs.empty()) return ACX_OK;
-        if ((rc = upload(seg.wgs, c->d_segw, c->segw_cap)) != ACX_OK) return rc;
+        if ((rc = upload(seg.wgs, c->d_segw)) != ACX_OK) return rc;
         hipLaunchKernelGGL(acx::ef_gemm_seg_f32_kernel, dim3((unsigned)seg.wgs.size()), dim3(256), 0, c->stream,
                            c->d_ef[2], c->d_efpd, c->d_rects, c->d_segw, c->d_segr, c->d_segc, c->d_ptab, c->d_scratch, c->ef_dims[2]);
         return ACX_OK;
@@ -1158,7 +1169,7 @@ static int launch_ef_gemms(acx_ctx *c, const SegBatch &seg, int B, int tiles_x, 
         // one workgroup per CU, each walking the tiles that the counters d_efctr[0] (mfcc, ssm) and [1] (chroma) deal out
         const int ncu = std::max(1, c->n_cu);
         if (!seg.wgs2.empty()) {
-            if ((rc = upload(seg.wgs2, c->d_segw2, c->segw2_cap)) != ACX_OK) return rc;
+            if ((rc = upload(seg.wgs2, c->d_segw2)) != ACX_OK) return rc;
             const int nt = (int)seg.wgs2.size();
             const unsigned grid = (unsigned)std::min<int64_t>(ncu, 2 * (int64_t)nt);
             ACX_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_efctr, (int)(2 * grid), 1, c->stream));
@@ -1168,7 +1179,7 @@ static int launch_ef_gemms(acx_ctx *c, const SegBatch &seg, int B, int tiles_x, 
         }
         if (!chroma_split) return f32_chroma();
         if (!seg.wgs3.empty()) {
-            if ((rc = upload(seg.wgs3, c->d_segw3, c->segw3_cap)) != ACX_OK) return rc;
+            if ((rc = upload(seg.wgs3, c->d_segw3)) != ACX_OK) return rc;
             const int nt = (int)seg.wgs3.size();
             const unsigned grid = (unsigned)std::min(ncu, nt);
             ACX_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(c->d_efctr + 1), (int)(2 * grid), 1, c->stream));
@@ -1352,11 +1363,11 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
         ++nbatches;
         const int B = (int)pd.size();
         const double t_b = now();
-        if ((rc = ensure(c, c->d_scratch, c->scratch_cap, (size_t)used)) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_thr, c->thr_cap, (size_t)used_s)) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_efbits, c->efbits_cap, (size_t)used_b)) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_efpd, c->efpd_cap, (size_t)B)) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_out, c->out_cap, (size_t)4 * B)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_scratch, (size_t)used)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_thr, (size_t)used_s)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_efbits, (size_t)used_b)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_efpd, (size_t)B)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_out, (size_t)4 * B)) != ACX_OK) return rc;
         ACX_HIP(c, hipMemcpyAsync(c->d_efpd, pd.data(), sizeof(EfPair) * B, hipMemcpyHostToDevice, c->stream));
         const int rows_g = (std::max(maxM, maxN) + 3) / 4;
         if (ext_matrix) {
@@ -1530,11 +1541,12 @@ static int launch_simple_sslen(acx_ctx *c, int sslen, int n, size_t smem, int ot
 static int ensure_winnorm(acx_ctx *c, int sslen)
 {
     if (c->d_wn64 && c->wn64_L == sslen) return ACX_OK;
-    if (c->d_wn64) { ACX_HIP(c, hipFree(c->d_wn64)); c->d_wn64 = nullptr; }
+    ACX_HIP(c, c->d_wn64.reset());
+    c->wn64_L = 0;
     const int64_t total = c->h_off64[c->n_tracks64];
     int maxn = 1;
     for (int t = 0; t < c->n_tracks64; ++t) maxn = std::max<int>(maxn, (int)(c->h_off64[t + 1] - c->h_off64[t]));
-    ACX_HIP(c, hipMalloc((void **)&c->d_wn64, sizeof(double) * std::max<int64_t>(1, total)));
+    ACX_HIP(c, c->d_wn64.grow((size_t)std::max<int64_t>(1, total)));
     ACX_HIP(c, hipMemsetAsync(c->d_wn64, 0, sizeof(double) * std::max<int64_t>(1, total), c->stream));
     // (grid.x = tracks: up to 2^31 - 1)
     hipLaunchKernelGGL(acx::simple_winnorm_kernel, dim3(c->n_tracks64, std::min(64, (maxn + 255) / 256)), dim3(256), 0, c->stream,
@@ -1567,12 +1579,7 @@ static int simple_front(acx_ctx *c, int sslen, Each each_track, size_t *smem)
 // returns, the host's copy may be reused at once)
 static int upload_tiles(acx_ctx *c, const void *tiles, size_t bytes)
 {
-    if (bytes > c->tiles_cap) {
-        if (c->d_tiles) ACX_HIP(c, hipFree(c->d_tiles));
-        c->d_tiles = nullptr; c->tiles_cap = 0;
-        ACX_HIP(c, hipMalloc(&c->d_tiles, bytes));
-        c->tiles_cap = bytes;
-    }
+    if (const int rc = ensure(c, c->d_tiles, bytes); rc != ACX_OK) return rc;
     ACX_HIP(c, hipMemcpyAsync(c->d_tiles, tiles, bytes, hipMemcpyHostToDevice, c->stream));
     return ACX_OK;
 }
@@ -1621,6 +1628,7 @@ acx_ctx *acx_create(int device, int *err)
 }
 
 static void comm_release(acx_ctx *c);
+static void ftm2d_free_pool(acx_ctx *c);
 
 void acx_destroy(acx_ctx *c)
 {
@@ -1630,56 +1638,23 @@ void acx_destroy(acx_ctx *c)
     if (c->qstream) (void)hipStreamSynchronize(c->qstream);
     if (c->qstream2) (void)hipStreamSynchronize(c->qstream2);
     comm_release(c);
-    for (void *b : c->dev_bufs) (void)hipFree(b);
-    c->dev_bufs.clear();
     drain_profile(c);
     for (hipEvent_t ev : c->event_pool) (void)hipEventDestroy(ev);
-    free_pool(c);
-    if (c->d_scratch) (void)hipFree(c->d_scratch);
-    if (c->d_thr) (void)hipFree(c->d_thr);
     for (Serra09Slot &sl : c->slot) {
-        if (sl.d_pd) (void)hipFree(sl.d_pd);
-        if (sl.d_out) (void)hipFree(sl.d_out);
-        if (sl.h_out) (void)hipHostFree(sl.h_out);
-        if (sl.h_idx) (void)hipHostFree(sl.h_idx);
-        if (sl.d_idx) (void)hipFree(sl.d_idx);
         if (sl.done) (void)hipEventDestroy(sl.done);
         for (hipEvent_t ev : sl.cls_ev)
             if (ev) (void)hipEventDestroy(ev);
     }
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->d_nf) (void)hipFree(c->d_nf);
-    if (c->d_idx) (void)hipFree(c->d_idx);
-    if (c->h_idx) (void)hipHostFree(c->h_idx);
-    if (c->d_tiles) (void)hipFree(c->d_tiles);
-    if (c->d_bits) (void)hipFree(c->d_bits);
-    if (c->d_frames64) (void)hipFree(c->d_frames64);
-    if (c->d_toff64) (void)hipFree(c->d_toff64);
-    if (c->d_prof64) (void)hipFree(c->d_prof64);
-    if (c->d_wn64) (void)hipFree(c->d_wn64);
-    if (c->d_pairs) (void)hipFree(c->d_pairs);
-    if (c->d_out64) (void)hipFree(c->d_out64);
-    ef_free_pool(c);
-    if (c->d_ftm) (void)hipFree(c->d_ftm);
-    for (int e = 0; e < 2; ++e) {
-        if (c->rank_h[e]) (void)hipHostFree(c->rank_h[e]);
-        if (c->rank_d[e]) (void)hipFree(c->rank_d[e]);
-        if (c->rank_ev[e]) (void)hipEventDestroy(c->rank_ev[e]);
-    }
-    if (c->d_efpd) (void)hipFree(c->d_efpd);
-    if (c->d_efbits) (void)hipFree(c->d_efbits);
-    if (c->d_segr) (void)hipFree(c->d_segr);
-    if (c->d_segc) (void)hipFree(c->d_segc);
-    if (c->d_rects) (void)hipFree(c->d_rects);
-    if (c->d_ptab) (void)hipFree(c->d_ptab);
-    if (c->d_segw) (void)hipFree(c->d_segw);
-    if (c->d_segw2) (void)hipFree(c->d_segw2);
-    if (c->d_segw3) (void)hipFree(c->d_segw3);
-    if (c->d_efctr) (void)hipFree(c->d_efctr);
+    for (hipEvent_t ev : c->rank_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    if (c->q2_done) (void)hipEventDestroy(c->q2_done);
     if (c->qstream) (void)hipStreamDestroy(c->qstream);
     if (c->qstream2) (void)hipStreamDestroy(c->qstream2);
-    if (c->q2_done) (void)hipEventDestroy(c->q2_done);
     (void)hipStreamDestroy(c->stream);
+    // the pools that are raw pointers (an active pool may alias the upload); every other buffer frees itself with the context
+    free_pool(c);
+    ef_free_pool(c);
+    ftm2d_free_pool(c);
     delete c;
 }
 
@@ -1715,6 +1690,7 @@ int acx_set_nonfinite_policy(acx_ctx *c, int32_t policy)
 int64_t acx_nonfinite_zeroed(const acx_ctx *c) { return c ? c->nf_zeroed : 0; }
 
 static int upload_pool_impl(acx_ctx *c, const float *frames, const int64_t *offsets, int32_t n_tracks, int32_t dim);
+static int fill_pool(acx_ctx *c, const float *frames, const int64_t *offsets, int32_t n_tracks, int32_t dim);
 static int upload_pool_f64_impl(acx_ctx *c, const double *frames, const int64_t *offsets, int32_t n_tracks, int32_t dim);
 
 int acx_upload_pool(acx_ctx *c, const float *frames, const int64_t *offsets, int32_t n_tracks, int32_t dim)
@@ -1732,6 +1708,13 @@ static int upload_pool_impl(acx_ctx *c, const float *frames, const int64_t *offs
         if (offsets[i + 1] < offsets[i]) return fail(c, ACX_ERR_INVALID, "upload_pool: offsets must be non-decreasing");
     ACX_HIP(c, hipSetDevice(c->device));
     free_pool(c);
+    const int rc = fill_pool(c, frames, offsets, n_tracks, dim);
+    if (rc != ACX_OK) { free_pool(c); c->n_tracks = 0; }      // whatever failed: no pool, the next call says so (ACX_ERR_STATE)
+    return rc;
+}
+
+static int fill_pool(acx_ctx *c, const float *frames, const int64_t *offsets, int32_t n_tracks, int32_t dim)
+{
     const int64_t total = offsets[n_tracks];
     c->h_off0.assign(offsets, offsets + n_tracks + 1);
     c->n_tracks = n_tracks;
@@ -1742,7 +1725,7 @@ static int upload_pool_impl(acx_ctx *c, const float *frames, const int64_t *offs
     ACX_HIP(c, hipMemcpy(c->d_toff0, offsets, sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
     {
         const int rc = scan_nonfinite(c, "upload_pool", "frames", c->d_frames0, total * dim, dim, 0, c->d_toff0, n_tracks);
-        if (rc != ACX_OK) { free_pool(c); c->n_tracks = 0; return rc; }
+        if (rc != ACX_OK) return rc;
     }
     std::vector<float> cleaned;                     // policy ZERO and something was zeroed: the host-side sums below see what the device holds
     if (c->nf_zeroed > 0 && dim == acx::NBIN) {
@@ -1774,9 +1757,17 @@ static int upload_pool_impl(acx_ctx *c, const float *frames, const int64_t *offs
     return ACX_OK;
 }
 
-// Raw pools are prepared in slices of whole tracks so that the staging buffer stays bounded
-// whatever the collection size (a 15 k-track collection is ~60 GB of raw chroma).
+// Raw pools are prepared in slices of whole tracks (for_track_slices) so that the staging buffer stays bounded
+// whatever the collection size (a 15 k-track collection is ~60 GB of raw chroma): 1 GiB of raw features, or the
+// scratch limit where acx_set_scratch_limit set a smaller one.  Every preparation kernel works per track, so
+// where the slices end changes no result.
 static const int64_t RAW_SLICE_FLOATS = (int64_t)1 << 28;       // 1 GiB of f32
+
+static int64_t raw_slice_bytes(const acx_ctx *c)
+{
+    const int64_t bytes = RAW_SLICE_FLOATS * (int64_t)sizeof(float);
+    return c->scratch_limit > 0 ? std::min(bytes, c->scratch_limit) : bytes;
+}
 
 static int check_raw_args(acx_ctx *c, const char *who, const float *raw, const int64_t *roff, int32_t n_tracks, int32_t dim)
 {
@@ -1804,53 +1795,32 @@ int acx_upload_raw_pool(acx_ctx *c, const float *raw, const int64_t *raw_offsets
     }
     const int64_t ptotal = poff[n_tracks];
     std::vector<float> pooled((size_t)std::max<int64_t>(1, ptotal) * 12);
-    int64_t *d_roff = nullptr, *d_poff = nullptr;
-    float *d_raw = nullptr, *d_pooled = nullptr;
-    auto cleanup = [&]() {
-        if (d_roff) (void)hipFree(d_roff);
-        if (d_poff) (void)hipFree(d_poff);
-        if (d_raw) (void)hipFree(d_raw);
-        if (d_pooled) (void)hipFree(d_pooled);
-    };
-#define ACX_HIPC(expr_) do { const hipError_t ec_ = (expr_); if (ec_ != hipSuccess) { cleanup(); ACX_HIP(c, ec_); } } while (0)
-    ACX_HIPC(hipMalloc((void **)&d_roff, sizeof(int64_t) * (n_tracks + 1)));
-    ACX_HIPC(hipMalloc((void **)&d_poff, sizeof(int64_t) * (n_tracks + 1)));
-    ACX_HIPC(hipMemcpy(d_roff, raw_offsets, sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
-    ACX_HIPC(hipMemcpy(d_poff, poff.data(), sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
-    int64_t cap_raw = 0, cap_pooled = 0;
-    for (int t0 = 0; t0 < n_tracks;) {
-        int t1 = t0 + 1;
-        while (t1 < n_tracks && (raw_offsets[t1 + 1] - raw_offsets[t0]) * 12 <= RAW_SLICE_FLOATS) ++t1;
-        const int64_t nraw = raw_offsets[t1] - raw_offsets[t0], npool = poff[t1] - poff[t0];
-        if (npool > 0) {
-            if (nraw * 12 > cap_raw) {
-                if (d_raw) (void)hipFree(d_raw);
-                d_raw = nullptr;
-                cap_raw = nraw * 12;
-                ACX_HIPC(hipMalloc((void **)&d_raw, sizeof(float) * cap_raw));
-            }
-            if (npool * 12 > cap_pooled) {
-                if (d_pooled) (void)hipFree(d_pooled);
-                d_pooled = nullptr;
-                cap_pooled = npool * 12;
-                ACX_HIPC(hipMalloc((void **)&d_pooled, sizeof(float) * cap_pooled));
-            }
-            ACX_HIPC(hipMemcpyAsync(d_raw, raw + raw_offsets[t0] * 12, sizeof(float) * nraw * 12, hipMemcpyHostToDevice, c->stream));
-            if ((rc = scan_nonfinite(c, "upload_raw_pool", "raw chroma", d_raw, nraw * 12, 12, raw_offsets[t0], d_roff, n_tracks)) != ACX_OK) {
-                cleanup();
-                return rc;
-            }
+    DeviceBuffer<int64_t> d_roff, d_poff;
+    DeviceBuffer<float> d_raw, d_pooled;             // staging of one slice: grown as needed, reused by the next
+    ACX_HIP(c, d_roff.grow((size_t)n_tracks + 1));
+    ACX_HIP(c, d_poff.grow((size_t)n_tracks + 1));
+    ACX_HIP(c, hipMemcpy(d_roff, raw_offsets, sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
+    ACX_HIP(c, hipMemcpy(d_poff, poff.data(), sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
+    const int64_t budget = raw_slice_bytes(c);
+    rc = for_track_slices(
+        n_tracks, n_tracks, [&](int t0, int t1) { return (raw_offsets[t1] - raw_offsets[t0]) * 12 * (int64_t)sizeof(float) <= budget; },
+        [&](int t0, int t1) -> int {
+            const int64_t nraw = raw_offsets[t1] - raw_offsets[t0], npool = poff[t1] - poff[t0];
+            if (npool <= 0) return ACX_OK;
+            ACX_HIP(c, d_raw.grow((size_t)nraw * 12));
+            ACX_HIP(c, d_pooled.grow((size_t)npool * 12));
+            ACX_HIP(c, hipMemcpyAsync(d_raw, raw + raw_offsets[t0] * 12, sizeof(float) * nraw * 12, hipMemcpyHostToDevice, c->stream));
+            const int rcs = scan_nonfinite(c, "upload_raw_pool", "raw chroma", d_raw.get(), nraw * 12, 12, raw_offsets[t0], d_roff.get(), n_tracks);
+            if (rcs != ACX_OK) return rcs;
             const int64_t blocks = (npool + acx::POOL_FPB - 1) / acx::POOL_FPB;
             hipLaunchKernelGGL(acx::pool_median_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream,
-                               d_raw, raw_offsets[t0], d_roff, d_poff, n_tracks, poff[t0], poff[t1], fac, d_pooled);
-            ACX_HIPC(hipGetLastError());
-            ACX_HIPC(hipMemcpyAsync(pooled.data() + poff[t0] * 12, d_pooled, sizeof(float) * npool * 12, hipMemcpyDeviceToHost, c->stream));
-            ACX_HIPC(hipStreamSynchronize(c->stream));
-        }
-        t0 = t1;
-    }
-#undef ACX_HIPC
-    cleanup();
+                               d_raw.get(), raw_offsets[t0], d_roff.get(), d_poff.get(), n_tracks, poff[t0], poff[t1], fac, d_pooled.get());
+            ACX_HIP(c, hipGetLastError());
+            ACX_HIP(c, hipMemcpyAsync(pooled.data() + poff[t0] * 12, d_pooled, sizeof(float) * npool * 12, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipStreamSynchronize(c->stream));
+            return ACX_OK;
+        });
+    if (rc != ACX_OK) return rc;
     if (pooled_offsets_out) memcpy(pooled_offsets_out, poff.data(), sizeof(int64_t) * (n_tracks + 1));
     return upload_pool_impl(c, pooled.data(), poff.data(), n_tracks, dim);
 }
@@ -1933,32 +1903,15 @@ int acx_qmax_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const ac
     }
     int rc;
     Serra09Slot &S = c->slot[0];
-    if ((rc = ensure(c, c->d_bits, c->bits_cap, words.size())) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_scratch, c->scratch_cap, (size_t)8 * M + 16)) != ACX_OK) return rc;     // strip records of the long DP
-    if ((rc = ensure(c, S.d_pd, S.pd_cap, (size_t)1)) != ACX_OK) return rc;
-    if ((rc = ensure(c, S.d_out, S.out_cap, (size_t)2)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_bits, words.size())) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_scratch, (size_t)8 * M + 16)) != ACX_OK) return rc;     // strip records of the long DP
+    if ((rc = ensure(c, S.d_pd, (size_t)1)) != ACX_OK) return rc;
+    if ((rc = ensure(c, S.d_out, (size_t)2)) != ACX_OK) return rc;
     ACX_HIP(c, hipMemcpyAsync(c->d_bits, words.data(), sizeof(unsigned long long) * words.size(), hipMemcpyHostToDevice, c->stream));
     ACX_HIP(c, hipMemcpyAsync(S.d_pd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
     const int nd = (std::max(M, N) + acx::BAND - 1 + 63) / 64;
-    const int cl = nd <= 8 ? 0 : (nd <= 16 ? 1 : (nd <= 32 ? 2 : 3));
-    const bool eqg = params->gamma_o == params->gamma_e, dmax = params->dmax != 0;
-#define ACX_QB3(E_, D_, C_) hipLaunchKernelGGL((acx::qmax_bits_kernel<E_, D_, C_>), dim3(1), dim3(64), 0, c->stream, \
-                                           S.d_pd, c->d_bits, S.d_out, 1, params->gamma_o, params->gamma_e, params->dp_start)
-#define ACX_QBL(E_, D_) hipLaunchKernelGGL((acx::qmax_bits_long_kernel<E_, D_>), dim3(1), dim3(64), 0, c->stream, \
-                                       S.d_pd, c->d_bits, c->d_scratch, S.d_out, 1, params->gamma_o, params->gamma_e, params->dp_start)
-#define ACX_QB(E_, D_) do { if (cl == 0) ACX_QB3(E_, D_, 8); else if (cl == 1) ACX_QB3(E_, D_, 16); else if (cl == 2) ACX_QB3(E_, D_, 32); \
-                        else ACX_QBL(E_, D_); } while (0)
-    if (eqg && params->gamma_o == 0.5f && cl < 3) {
-#define ACX_QH1(C_, D_) hipLaunchKernelGGL((acx::qmax_bits_h16_kernel<C_, D_>), dim3(1), dim3(64), 0, c->stream, S.d_pd, c->d_bits, S.d_out, 1, params->dp_start)
-        if (dmax) { if (cl == 0) ACX_QH1(8, true); else if (cl == 1) ACX_QH1(16, true); else ACX_QH1(32, true); }
-        else { if (cl == 0) ACX_QH1(8, false); else if (cl == 1) ACX_QH1(16, false); else ACX_QH1(32, false); }
-#undef ACX_QH1
-    }
-    else if (eqg) { if (dmax) ACX_QB(true, true); else ACX_QB(true, false); }
-    else { if (dmax) ACX_QB(false, true); else ACX_QB(false, false); }
-#undef ACX_QB
-#undef ACX_QBL
-#undef ACX_QB3
+    launch_qmax_sweep(c->stream, S.d_pd, 1, c->d_bits, c->d_scratch, S.d_out, 1, params->gamma_o, params->gamma_e, params->dp_start,
+                      params->dmax != 0, nd <= 8 ? 8 : (nd <= 16 ? 16 : (nd <= 32 ? 32 : 0)), 0);
     ACX_HIP(c, hipGetLastError());
     ACX_HIP(c, hipMemcpyAsync(score, S.d_out, sizeof(float), hipMemcpyDeviceToHost, c->stream));
     ACX_HIP(c, hipStreamSynchronize(c->stream));
@@ -1979,31 +1932,26 @@ static int upload_pool_f64_impl(acx_ctx *c, const double *frames, const int64_t 
     for (int i = 0; i < n_tracks; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(c, ACX_ERR_INVALID, "upload_pool_f64: offsets must be non-decreasing");
     ACX_HIP(c, hipSetDevice(c->device));
-    if (c->d_frames64) { (void)hipFree(c->d_frames64); c->d_frames64 = nullptr; }
-    if (c->d_toff64) { (void)hipFree(c->d_toff64); c->d_toff64 = nullptr; }
-    if (c->d_prof64) { (void)hipFree(c->d_prof64); c->d_prof64 = nullptr; }
-    if (c->d_wn64) { (void)hipFree(c->d_wn64); c->d_wn64 = nullptr; }
+    // the old pool goes first (two pools need not fit side by side); the new one is the context's once it is complete, so
+    // whatever fails below leaves no pool and the next call says so (ACX_ERR_STATE)
+    (void)c->d_frames64.reset(); (void)c->d_toff64.reset(); (void)c->d_prof64.reset(); (void)c->d_wn64.reset();
     c->wn64_L = 0;
+    c->n_tracks64 = 0;
     const int64_t total = offsets[n_tracks];
     std::vector<double> cleaned;
-    c->h_off64.assign(offsets, offsets + n_tracks + 1);
-    c->n_tracks64 = n_tracks;
-    ACX_HIP(c, hipMalloc((void **)&c->d_frames64, sizeof(double) * std::max<int64_t>(1, total) * 12));
-    ACX_HIP(c, hipMalloc((void **)&c->d_toff64, sizeof(int64_t) * (n_tracks + 1)));
-    ACX_HIP(c, hipMemcpy(c->d_frames64, frames, sizeof(double) * total * 12, hipMemcpyHostToDevice));
-    ACX_HIP(c, hipMemcpy(c->d_toff64, offsets, sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
+    DeviceBuffer<double> d_frames, d_prof;
+    DeviceBuffer<int64_t> d_toff;
+    ACX_HIP(c, d_frames.grow((size_t)std::max<int64_t>(1, total) * 12));
+    ACX_HIP(c, d_toff.grow((size_t)n_tracks + 1));
+    ACX_HIP(c, hipMemcpy(d_frames, frames, sizeof(double) * total * 12, hipMemcpyHostToDevice));
+    ACX_HIP(c, hipMemcpy(d_toff, offsets, sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
     {
         const int64_t before = c->nf_zeroed;
-        const int rc = scan_nonfinite(c, "upload_pool_f64", "frames", c->d_frames64, total * 12, 12, 0, c->d_toff64, n_tracks);
-        if (rc != ACX_OK) {
-            (void)hipFree(c->d_frames64); c->d_frames64 = nullptr;
-            (void)hipFree(c->d_toff64); c->d_toff64 = nullptr;
-            c->n_tracks64 = 0;
-            return rc;
-        }
+        const int rc = scan_nonfinite(c, "upload_pool_f64", "frames", d_frames.get(), total * 12, 12, 0, d_toff.get(), n_tracks);
+        if (rc != ACX_OK) return rc;
         if (c->nf_zeroed > before) {      // policy ZERO: the profile below sums what the device holds
             cleaned.resize((size_t)total * 12);
-            ACX_HIP(c, hipMemcpy(cleaned.data(), c->d_frames64, sizeof(double) * total * 12, hipMemcpyDeviceToHost));
+            ACX_HIP(c, hipMemcpy(cleaned.data(), d_frames, sizeof(double) * total * 12, hipMemcpyDeviceToHost));
             frames = cleaned.data();
         }
     }
@@ -2012,8 +1960,11 @@ static int upload_pool_f64_impl(acx_ctx *c, const double *frames, const int64_t 
     for (int t = 0; t < n_tracks; ++t)
         for (int64_t f = offsets[t]; f < offsets[t + 1]; ++f)
             for (int b = 0; b < 12; ++b) prof[(size_t)t * 12 + b] += frames[f * 12 + b];
-    ACX_HIP(c, hipMalloc((void **)&c->d_prof64, sizeof(double) * prof.size()));
-    ACX_HIP(c, hipMemcpy(c->d_prof64, prof.data(), sizeof(double) * prof.size(), hipMemcpyHostToDevice));
+    ACX_HIP(c, d_prof.grow(prof.size()));
+    ACX_HIP(c, hipMemcpy(d_prof, prof.data(), sizeof(double) * prof.size(), hipMemcpyHostToDevice));
+    c->h_off64.assign(offsets, offsets + n_tracks + 1);
+    c->n_tracks64 = n_tracks;
+    c->d_frames64 = std::move(d_frames); c->d_toff64 = std::move(d_toff); c->d_prof64 = std::move(d_prof);
     return ACX_OK;
 }
 
@@ -2045,53 +1996,32 @@ int acx_simple_upload_raw_pool(acx_ctx *c, const float *raw, const int64_t *raw_
     }
     const int64_t ptotal = poff[n_tracks];
     std::vector<double> feats((size_t)std::max<int64_t>(1, ptotal) * 12);
-    int64_t *d_roff = nullptr, *d_poff = nullptr;
-    float *d_raw = nullptr;
-    double *d_feats = nullptr;
-    auto cleanup = [&]() {
-        if (d_roff) (void)hipFree(d_roff);
-        if (d_poff) (void)hipFree(d_poff);
-        if (d_raw) (void)hipFree(d_raw);
-        if (d_feats) (void)hipFree(d_feats);
-    };
-#define ACX_HIPC(expr_) do { const hipError_t ec_ = (expr_); if (ec_ != hipSuccess) { cleanup(); ACX_HIP(c, ec_); } } while (0)
-    ACX_HIPC(hipMalloc((void **)&d_roff, sizeof(int64_t) * (n_tracks + 1)));
-    ACX_HIPC(hipMalloc((void **)&d_poff, sizeof(int64_t) * (n_tracks + 1)));
-    ACX_HIPC(hipMemcpy(d_roff, raw_offsets, sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
-    ACX_HIPC(hipMemcpy(d_poff, poff.data(), sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
-    int64_t cap_raw = 0, cap_feats = 0;
-    for (int t0 = 0; t0 < n_tracks;) {
-        int t1 = t0 + 1;
-        while (t1 < n_tracks && t1 - t0 < 65535 && (raw_offsets[t1 + 1] - raw_offsets[t0]) * 12 <= RAW_SLICE_FLOATS) ++t1;
-        const int64_t nraw = raw_offsets[t1] - raw_offsets[t0], npool = poff[t1] - poff[t0];
-        if (npool > 0) {
-            if (nraw * 12 > cap_raw) {
-                if (d_raw) (void)hipFree(d_raw);
-                d_raw = nullptr;
-                cap_raw = nraw * 12;
-                ACX_HIPC(hipMalloc((void **)&d_raw, sizeof(float) * cap_raw));
-            }
-            if (npool * 12 > cap_feats) {
-                if (d_feats) (void)hipFree(d_feats);
-                d_feats = nullptr;
-                cap_feats = npool * 12;
-                ACX_HIPC(hipMalloc((void **)&d_feats, sizeof(double) * cap_feats));
-            }
-            ACX_HIPC(hipMemcpyAsync(d_raw, raw + raw_offsets[t0] * 12, sizeof(float) * nraw * 12, hipMemcpyHostToDevice, c->stream));
-            if ((rc = scan_nonfinite(c, "simple_upload_raw_pool", "raw chroma", d_raw, nraw * 12, 12, raw_offsets[t0], d_roff, n_tracks)) != ACX_OK) {
-                cleanup();
-                return rc;
-            }
+    DeviceBuffer<int64_t> d_roff, d_poff;
+    DeviceBuffer<float> d_raw;                       // staging of one slice: grown as needed, reused by the next
+    DeviceBuffer<double> d_feats;
+    ACX_HIP(c, d_roff.grow((size_t)n_tracks + 1));
+    ACX_HIP(c, d_poff.grow((size_t)n_tracks + 1));
+    ACX_HIP(c, hipMemcpy(d_roff, raw_offsets, sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
+    ACX_HIP(c, hipMemcpy(d_poff, poff.data(), sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
+    const int64_t budget = raw_slice_bytes(c);
+    rc = for_track_slices(
+        n_tracks, 65535, [&](int t0, int t1) { return (raw_offsets[t1] - raw_offsets[t0]) * 12 * (int64_t)sizeof(float) <= budget; },
+        [&](int t0, int t1) -> int {
+            const int64_t nraw = raw_offsets[t1] - raw_offsets[t0], npool = poff[t1] - poff[t0];
+            if (npool <= 0) return ACX_OK;
+            ACX_HIP(c, d_raw.grow((size_t)nraw * 12));
+            ACX_HIP(c, d_feats.grow((size_t)npool * 12));
+            ACX_HIP(c, hipMemcpyAsync(d_raw, raw + raw_offsets[t0] * 12, sizeof(float) * nraw * 12, hipMemcpyHostToDevice, c->stream));
+            const int rcs = scan_nonfinite(c, "simple_upload_raw_pool", "raw chroma", d_raw.get(), nraw * 12, 12, raw_offsets[t0], d_roff.get(), n_tracks);
+            if (rcs != ACX_OK) return rcs;
             hipLaunchKernelGGL(acx::simple_prep_kernel, dim3((unsigned)(t1 - t0)), dim3(256), 0, c->stream,
-                               d_raw, raw_offsets[t0], d_roff, d_poff, t0, win, skip, sw, d_feats, poff[t0]);
-            ACX_HIPC(hipGetLastError());
-            ACX_HIPC(hipMemcpyAsync(feats.data() + poff[t0] * 12, d_feats, sizeof(double) * npool * 12, hipMemcpyDeviceToHost, c->stream));
-            ACX_HIPC(hipStreamSynchronize(c->stream));
-        }
-        t0 = t1;
-    }
-#undef ACX_HIPC
-    cleanup();
+                               d_raw.get(), raw_offsets[t0], d_roff.get(), d_poff.get(), t0, win, skip, sw, d_feats.get(), poff[t0]);
+            ACX_HIP(c, hipGetLastError());
+            ACX_HIP(c, hipMemcpyAsync(feats.data() + poff[t0] * 12, d_feats, sizeof(double) * npool * 12, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipStreamSynchronize(c->stream));
+            return ACX_OK;
+        });
+    if (rc != ACX_OK) return rc;
     if (pooled_offsets_out) memcpy(pooled_offsets_out, poff.data(), sizeof(int64_t) * (n_tracks + 1));
     return upload_pool_f64_impl(c, feats.data(), poff.data(), n_tracks, 12);
 }
@@ -2131,8 +2061,8 @@ int acx_simple_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, int32_t sslen,
     if (rcw != ACX_OK) return rcw;
     const int64_t chunk = 1 << 22;
     int rc;
-    if ((rc = ensure(c, c->d_pairs, c->pairs_cap, (size_t)2 * std::min(K, chunk))) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_out64, c->out64_cap, (size_t)std::min(K, chunk))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_pairs, (size_t)2 * std::min(K, chunk))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_out64, (size_t)std::min(K, chunk))) != ACX_OK) return rc;
     std::vector<int32_t> order, sorted, bucket;
     std::vector<double> tmp;
     for (int64_t k0 = 0; k0 < K; k0 += chunk) {
@@ -2201,7 +2131,16 @@ static int ef_build_splits(acx_ctx *c, int fmt)
 // The block features are on the device (d_ef[0..2], d_efmed): unit-norm chroma rows in place
 // (X / XNorm with zero norms -> 1, cross_recurrence.py:66-71) and the squared row norms of the
 // Euclidean features (np.sum(X**2, 1), :46; f64 accumulation), once per pool.
+static int ef_norms_and_splits(acx_ctx *c, const int64_t *offsets, int32_t n_tracks, const int32_t *dims);
+
 static int ef_finish_pool(acx_ctx *c, const int64_t *offsets, int32_t n_tracks, const int32_t *dims)
+{
+    const int rc = ef_norms_and_splits(c, offsets, n_tracks, dims);
+    if (rc != ACX_OK) ef_free_pool(c);                // whatever failed: no pool, the next call says so (ACX_ERR_STATE)
+    return rc;
+}
+
+static int ef_norms_and_splits(acx_ctx *c, const int64_t *offsets, int32_t n_tracks, const int32_t *dims)
 {
     const int64_t nb = offsets[n_tracks];
     c->h_efoff.assign(offsets, offsets + n_tracks + 1);
@@ -2213,7 +2152,7 @@ static int ef_finish_pool(acx_ctx *c, const int64_t *offsets, int32_t n_tracks, 
         static const char *what[3] = {"mfcc blocks", "ssm blocks", "chroma blocks"};
         for (int k = 0; k < 3; ++k) {
             const int rc = scan_nonfinite(c, "ef pool", what[k], c->d_ef[k], nb * dims[k], dims[k], 0, c->d_efoff, n_tracks);
-            if (rc != ACX_OK) { ef_free_pool(c); return rc; }
+            if (rc != ACX_OK) return rc;
         }
     }
     for (int k = 0; k < 2; ++k)
@@ -2235,7 +2174,7 @@ static int ef_finish_pool(acx_ctx *c, const int64_t *offsets, int32_t n_tracks, 
     }
     {
         const int rc = ef_build_splits(c, c->ef_gemm == ACX_EF_GEMM_F16X2 ? 1 : 0);
-        if (rc != ACX_OK) { ef_free_pool(c); return rc; }
+        if (rc != ACX_OK) return rc;
     }
     ACX_HIP(c, hipStreamSynchronize(c->stream));
     return ACX_OK;
@@ -2281,7 +2220,10 @@ int acx_ef_pool_begin(acx_ctx *c, const int64_t *offsets, int32_t n_tracks, cons
         const hipError_t e = hipMalloc((void **)&c->d_ef[k], sizeof(float) * std::max<int64_t>(1, nb) * dims[k]);
         if (e != hipSuccess) { ef_free_pool(c); return fail(c, ACX_ERR_NOMEM, std::string("ef_pool_begin: the block features do not fit the device: ") + hipGetErrorString(e)); }
     }
-    ACX_HIP(c, hipMalloc((void **)&c->d_efmed, sizeof(double) * 12 * n_tracks));
+    {
+        const hipError_t e = hipMalloc((void **)&c->d_efmed, sizeof(double) * 12 * n_tracks);
+        if (e != hipSuccess) { ef_free_pool(c); ACX_HIP(c, e); }
+    }
     c->h_efoff.assign(offsets, offsets + n_tracks + 1);
     for (int k = 0; k < 3; ++k) c->ef_dims[k] = dims[k];
     c->ef_open = n_tracks;
@@ -2348,10 +2290,15 @@ int acx_ef_upload_pool(acx_ctx *c, const float *mfccs, const float *ssms, const 
     return rc;
 }
 
-// Block features of tracks [0, n_tracks) into fresh device arrays (caller frees / adopts them).
+// Block features of tracks [0, n_tracks) into fresh device arrays: the caller's, to adopt (release()) or to let drop.
+struct EfBlocks {
+    DeviceBuffer<float> feat[3];         // mfcc / ssm / chroma block features
+    DeviceBuffer<double> med;            // chroma median, 12 per track
+};
+
 static int ef_build_blocks(acx_ctx *c, const float *chroma, const int64_t *coff, const float *mfcc, const int64_t *moff,
                            int32_t ncoef, const int64_t *onsets, const int64_t *ooff, int32_t n_tracks,
-                           const acx_ef_prep_params &pp, std::vector<int64_t> &boff, float *d_out[3], double *&d_med)
+                           const acx_ef_prep_params &pp, std::vector<int64_t> &boff, EfBlocks &out)
 {
     if (pp.blocksize < 1 || pp.mfccs_per_block < 2 || pp.chromas_per_block < 1 || ncoef < 1)
         return fail(c, ACX_ERR_INVALID, "ef block features: bad parameter");
@@ -2367,72 +2314,49 @@ static int ef_build_blocks(acx_ctx *c, const float *chroma, const int64_t *coff,
     }
     const int64_t nb = boff[n_tracks];
     const int dims[3] = {pp.mfccs_per_block * ncoef, pp.mfccs_per_block * (pp.mfccs_per_block - 1) / 2, pp.chromas_per_block * 12};
-    d_out[0] = d_out[1] = d_out[2] = nullptr; d_med = nullptr;
-    float *d_ch = nullptr, *d_mf = nullptr;
-    int64_t *d_on = nullptr, *d_coff = nullptr, *d_moff = nullptr, *d_ooff = nullptr, *d_boff = nullptr;
-    auto cleanup_in = [&]() {
-        if (d_ch) (void)hipFree(d_ch);
-        if (d_mf) (void)hipFree(d_mf);
-        if (d_on) (void)hipFree(d_on);
-        if (d_coff) (void)hipFree(d_coff);
-        if (d_moff) (void)hipFree(d_moff);
-        if (d_ooff) (void)hipFree(d_ooff);
-        if (d_boff) (void)hipFree(d_boff);
-        d_ch = d_mf = nullptr; d_on = d_coff = d_moff = d_ooff = d_boff = nullptr;
-    };
-    auto cleanup_all = [&]() {
-        cleanup_in();
-        for (int k = 0; k < 3; ++k) if (d_out[k]) { (void)hipFree(d_out[k]); d_out[k] = nullptr; }
-        if (d_med) { (void)hipFree(d_med); d_med = nullptr; }
-    };
-#define ACX_HIPC(expr_) do { const hipError_t ec_ = (expr_); if (ec_ != hipSuccess) { cleanup_all(); ACX_HIP(c, ec_); } } while (0)
-    for (int k = 0; k < 3; ++k) ACX_HIPC(hipMalloc((void **)&d_out[k], sizeof(float) * std::max<int64_t>(1, nb) * dims[k]));
-    ACX_HIPC(hipMalloc((void **)&d_med, sizeof(double) * 12 * n_tracks));
-    // whole tracks in slices of about 1 GiB of raw features
-    for (int t0 = 0; t0 < n_tracks;) {
-        int t1 = t0 + 1;
-        auto slice_floats = [&](int a, int b2) { return (coff[b2] - coff[a]) * 12 + (moff[b2] - moff[a]) * ncoef; };
-        while (t1 < n_tracks && t1 - t0 < 65535 && slice_floats(t0, t1 + 1) <= RAW_SLICE_FLOATS) ++t1;
-        const int nt = t1 - t0;
-        const int64_t nch = coff[t1] - coff[t0], nmf = moff[t1] - moff[t0], non = ooff[t1] - ooff[t0], nbs = boff[t1] - boff[t0];
-        std::vector<int64_t> lc(nt + 1), lm(nt + 1), lo(nt + 1), lb(nt + 1);
-        for (int t = 0; t <= nt; ++t) {
-            lc[t] = coff[t0 + t] - coff[t0]; lm[t] = moff[t0 + t] - moff[t0];
-            lo[t] = ooff[t0 + t] - ooff[t0]; lb[t] = boff[t0 + t] - boff[t0];
-        }
-        ACX_HIPC(hipMalloc((void **)&d_ch, sizeof(float) * std::max<int64_t>(1, nch) * 12));
-        ACX_HIPC(hipMalloc((void **)&d_mf, sizeof(float) * std::max<int64_t>(1, nmf) * ncoef));
-        ACX_HIPC(hipMalloc((void **)&d_on, sizeof(int64_t) * std::max<int64_t>(1, non)));
-        ACX_HIPC(hipMalloc((void **)&d_coff, sizeof(int64_t) * (nt + 1)));
-        ACX_HIPC(hipMalloc((void **)&d_moff, sizeof(int64_t) * (nt + 1)));
-        ACX_HIPC(hipMalloc((void **)&d_ooff, sizeof(int64_t) * (nt + 1)));
-        ACX_HIPC(hipMalloc((void **)&d_boff, sizeof(int64_t) * (nt + 1)));
-        ACX_HIPC(hipMemcpyAsync(d_ch, chroma + coff[t0] * 12, sizeof(float) * nch * 12, hipMemcpyHostToDevice, c->stream));
-        ACX_HIPC(hipMemcpyAsync(d_mf, mfcc + moff[t0] * ncoef, sizeof(float) * nmf * ncoef, hipMemcpyHostToDevice, c->stream));
-        ACX_HIPC(hipMemcpyAsync(d_on, onsets + ooff[t0], sizeof(int64_t) * non, hipMemcpyHostToDevice, c->stream));
-        ACX_HIPC(hipMemcpyAsync(d_coff, lc.data(), sizeof(int64_t) * (nt + 1), hipMemcpyHostToDevice, c->stream));
-        ACX_HIPC(hipMemcpyAsync(d_moff, lm.data(), sizeof(int64_t) * (nt + 1), hipMemcpyHostToDevice, c->stream));
-        ACX_HIPC(hipMemcpyAsync(d_ooff, lo.data(), sizeof(int64_t) * (nt + 1), hipMemcpyHostToDevice, c->stream));
-        ACX_HIPC(hipMemcpyAsync(d_boff, lb.data(), sizeof(int64_t) * (nt + 1), hipMemcpyHostToDevice, c->stream));
-        {   // NaN MFCCs count as 0 like in the reference (earlyfusion_traile.py:105); anything else non-finite follows the policy
-            int rcs = scan_nonfinite(c, "ef block features", "raw chroma", d_ch, nch * 12, 12, 0, d_coff, nt, false, t0);
-            if (rcs == ACX_OK) rcs = scan_nonfinite(c, "ef block features", "MFCCs", d_mf, nmf * ncoef, ncoef, 0, d_moff, nt, true, t0);
-            if (rcs != ACX_OK) { cleanup_all(); return rcs; }
-        }
-        if (nbs > 0) {
-            acx::EfPrepParams kp{pp.blocksize, pp.mfccs_per_block, pp.chromas_per_block, ncoef};
-            hipLaunchKernelGGL(acx::ef_blocks_kernel, dim3((unsigned)nbs), dim3(256), 0, c->stream,
-                               d_ch, d_coff, d_mf, d_moff, d_on, d_ooff, d_boff, nt, kp,
-                               d_out[0] + boff[t0] * dims[0], d_out[1] + boff[t0] * dims[1], d_out[2] + boff[t0] * dims[2]);
-        }
-        hipLaunchKernelGGL(acx::ef_chroma_median_kernel, dim3(nt, 12), dim3(64), 0, c->stream, d_ch, d_coff, d_med + (size_t)t0 * 12);
-        ACX_HIPC(hipGetLastError());
-        ACX_HIPC(hipStreamSynchronize(c->stream));
-        cleanup_in();
-        t0 = t1;
-    }
-#undef ACX_HIPC
-    return ACX_OK;
+    for (int k = 0; k < 3; ++k) ACX_HIP(c, out.feat[k].grow((size_t)std::max<int64_t>(1, nb) * dims[k]));
+    ACX_HIP(c, out.med.grow((size_t)12 * n_tracks));
+    DeviceBuffer<float> d_ch, d_mf;                  // staging of one slice: grown as needed, reused by the next
+    DeviceBuffer<int64_t> d_on, d_coff, d_moff, d_ooff, d_boff;
+    const int64_t budget = raw_slice_bytes(c);
+    auto slice_bytes = [&](int a, int b2) { return ((coff[b2] - coff[a]) * 12 + (moff[b2] - moff[a]) * ncoef) * (int64_t)sizeof(float); };
+    return for_track_slices(
+        n_tracks, 65535, [&](int t0, int t1) { return slice_bytes(t0, t1) <= budget; },
+        [&](int t0, int t1) -> int {
+            const int nt = t1 - t0;
+            const int64_t nch = coff[t1] - coff[t0], nmf = moff[t1] - moff[t0], non = ooff[t1] - ooff[t0], nbs = boff[t1] - boff[t0];
+            std::vector<int64_t> lc(nt + 1), lm(nt + 1), lo(nt + 1), lb(nt + 1);
+            for (int t = 0; t <= nt; ++t) {
+                lc[t] = coff[t0 + t] - coff[t0]; lm[t] = moff[t0 + t] - moff[t0];
+                lo[t] = ooff[t0 + t] - ooff[t0]; lb[t] = boff[t0 + t] - boff[t0];
+            }
+            ACX_HIP(c, d_ch.grow((size_t)std::max<int64_t>(1, nch) * 12));
+            ACX_HIP(c, d_mf.grow((size_t)std::max<int64_t>(1, nmf) * ncoef));
+            ACX_HIP(c, d_on.grow((size_t)std::max<int64_t>(1, non)));
+            for (DeviceBuffer<int64_t> *b : {&d_coff, &d_moff, &d_ooff, &d_boff}) ACX_HIP(c, b->grow((size_t)nt + 1));
+            ACX_HIP(c, hipMemcpyAsync(d_ch, chroma + coff[t0] * 12, sizeof(float) * nch * 12, hipMemcpyHostToDevice, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(d_mf, mfcc + moff[t0] * ncoef, sizeof(float) * nmf * ncoef, hipMemcpyHostToDevice, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(d_on, onsets + ooff[t0], sizeof(int64_t) * non, hipMemcpyHostToDevice, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(d_coff, lc.data(), sizeof(int64_t) * (nt + 1), hipMemcpyHostToDevice, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(d_moff, lm.data(), sizeof(int64_t) * (nt + 1), hipMemcpyHostToDevice, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(d_ooff, lo.data(), sizeof(int64_t) * (nt + 1), hipMemcpyHostToDevice, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(d_boff, lb.data(), sizeof(int64_t) * (nt + 1), hipMemcpyHostToDevice, c->stream));
+            // NaN MFCCs count as 0 like in the reference (earlyfusion_traile.py:105); anything else non-finite follows the policy
+            // (the host offset tables above are pageable: their copies are staged before the calls return)
+            int rcs = scan_nonfinite(c, "ef block features", "raw chroma", d_ch.get(), nch * 12, 12, 0, d_coff.get(), nt, false, t0);
+            if (rcs == ACX_OK) rcs = scan_nonfinite(c, "ef block features", "MFCCs", d_mf.get(), nmf * ncoef, ncoef, 0, d_moff.get(), nt, true, t0);
+            if (rcs != ACX_OK) return rcs;
+            if (nbs > 0) {
+                acx::EfPrepParams kp{pp.blocksize, pp.mfccs_per_block, pp.chromas_per_block, ncoef};
+                hipLaunchKernelGGL(acx::ef_blocks_kernel, dim3((unsigned)nbs), dim3(256), 0, c->stream,
+                                   d_ch.get(), d_coff.get(), d_mf.get(), d_moff.get(), d_on.get(), d_ooff.get(), d_boff.get(), nt, kp,
+                                   out.feat[0] + boff[t0] * dims[0], out.feat[1] + boff[t0] * dims[1], out.feat[2] + boff[t0] * dims[2]);
+            }
+            hipLaunchKernelGGL(acx::ef_chroma_median_kernel, dim3(nt, 12), dim3(64), 0, c->stream, d_ch.get(), d_coff.get(), out.med + (size_t)t0 * 12);
+            ACX_HIP(c, hipGetLastError());
+            ACX_HIP(c, hipStreamSynchronize(c->stream));
+            return ACX_OK;
+        });
 }
 
 static int ef_check_raw(acx_ctx *c, const char *who, const float *chroma, const float *mfcc, const int64_t *onsets,
@@ -2454,19 +2378,14 @@ int acx_ef_block_features(acx_ctx *c, const float *chroma, int64_t n_chroma, con
     c->nf_zeroed = 0;
     const int64_t coff[2] = {0, n_chroma}, moff[2] = {0, n_mfcc}, ooff[2] = {0, n_beats};
     std::vector<int64_t> boff;
-    float *d_out[3];
-    double *d_med;
-    if ((rc = ef_build_blocks(c, chroma, coff, mfcc, moff, ncoef, onsets, ooff, 1, *prep, boff, d_out, d_med)) != ACX_OK) return rc;
+    EfBlocks blocks;
+    if ((rc = ef_build_blocks(c, chroma, coff, mfcc, moff, ncoef, onsets, ooff, 1, *prep, boff, blocks)) != ACX_OK) return rc;
     const int64_t nb = boff[1];
     const int dims[3] = {prep->mfccs_per_block * ncoef, prep->mfccs_per_block * (prep->mfccs_per_block - 1) / 2, prep->chromas_per_block * 12};
     float *dst[3] = {mfccs, ssms, chromas};
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 3 && e == hipSuccess; ++k)
-        if (dst[k] && nb > 0) e = hipMemcpy(dst[k], d_out[k], sizeof(float) * nb * dims[k], hipMemcpyDeviceToHost);
-    if (e == hipSuccess && chroma_med) e = hipMemcpy(chroma_med, d_med, sizeof(double) * 12, hipMemcpyDeviceToHost);
-    for (int k = 0; k < 3; ++k) (void)hipFree(d_out[k]);
-    (void)hipFree(d_med);
-    ACX_HIP(c, e);
+    for (int k = 0; k < 3; ++k)
+        if (dst[k] && nb > 0) ACX_HIP(c, hipMemcpy(dst[k], blocks.feat[k], sizeof(float) * nb * dims[k], hipMemcpyDeviceToHost));
+    if (chroma_med) ACX_HIP(c, hipMemcpy(chroma_med, blocks.med, sizeof(double) * 12, hipMemcpyDeviceToHost));
     return ACX_OK;
 }
 
@@ -2482,12 +2401,11 @@ int acx_ef_upload_raw_pool(acx_ctx *c, const float *chroma, const int64_t *chrom
     ef_free_pool(c);
     c->nf_zeroed = 0;
     std::vector<int64_t> boff;
-    float *d_out[3];
-    double *d_med;
+    EfBlocks blocks;
     if ((rc = ef_build_blocks(c, chroma, chroma_offsets, mfcc, mfcc_offsets, ncoef, onsets, onset_offsets, n_tracks, *prep, boff,
-                              d_out, d_med)) != ACX_OK) return rc;
-    for (int k = 0; k < 3; ++k) c->d_ef[k] = d_out[k];
-    c->d_efmed = d_med;
+                              blocks)) != ACX_OK) return rc;
+    for (int k = 0; k < 3; ++k) c->d_ef[k] = blocks.feat[k].release();
+    c->d_efmed = blocks.med.release();
     const int32_t dims[3] = {prep->mfccs_per_block * ncoef, prep->mfccs_per_block * (prep->mfccs_per_block - 1) / 2, prep->chromas_per_block * 12};
     if (block_offsets_out) memcpy(block_offsets_out, boff.data(), sizeof(int64_t) * (n_tracks + 1));
     return ef_finish_pool(c, boff.data(), n_tracks, dims);
@@ -2580,10 +2498,10 @@ int acx_sw_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, float *sco
     d.ctN = 0; d.pad = 0; d.offB = 0; d.offC = 0; d.offS = 0;
     int rc;
     ACX_HIP(c, hipSetDevice(c->device));
-    if ((rc = ensure(c, c->d_scratch, c->scratch_cap, (size_t)M * d.pitchC)) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_thr, c->thr_cap, (size_t)acx::ef_s_total(d))) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_efpd, c->efpd_cap, (size_t)1)) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_out, c->out_cap, (size_t)4)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_scratch, (size_t)M * d.pitchC)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_thr, (size_t)acx::ef_s_total(d))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efpd, (size_t)1)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_out, (size_t)4)) != ACX_OK) return rc;
     ACX_HIP(c, hipMemcpyAsync(c->d_efpd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
     ACX_HIP(c, hipMemcpy2DAsync(c->d_scratch, sizeof(float) * d.pitchC, Cm.data(), sizeof(float) * N, sizeof(float) * N, M,
                                 hipMemcpyHostToDevice, c->stream));
@@ -2676,29 +2594,20 @@ static int ftm2d_build(acx_ctx *c, const char *who, const float *chroma, const i
     auto lds_bytes = [&](int nw) { return sizeof(double) * (size_t)(2 * 7 * (nw + win - 1) + 2 * win + nw * 7 * win + nw); };
     int nw = acx::FTM_NW;
     while (nw > 1 && lds_bytes(nw) > (size_t)acx::FTM_LDS) --nw;
-    float *d_ch = nullptr, *d_sync = nullptr;
-    int64_t *d_coff = nullptr, *d_bnd = nullptr, *d_boff = nullptr, *d_woff = nullptr;
-    double *d_pwr = nullptr, *d_G = nullptr, *d_lw = nullptr, *d_med = nullptr, *d_tw = nullptr;
-    acx::FtmBlock *d_blk = nullptr;
-    auto cleanup = [&]() {
-        void *ps[] = {d_ch, d_sync, d_coff, d_bnd, d_boff, d_woff, d_pwr, d_G, d_lw, d_med, d_blk};
-        for (void *q : ps) if (q) (void)hipFree(q);
-        d_ch = d_sync = nullptr; d_coff = d_bnd = d_boff = d_woff = nullptr; d_pwr = d_G = d_lw = d_med = nullptr; d_blk = nullptr;
-    };
-    auto cleanup_all = [&]() { cleanup(); if (d_tw) (void)hipFree(d_tw); d_tw = nullptr; };
-#define ACX_HIPC(expr_) do { const hipError_t ec_ = (expr_); if (ec_ != hipSuccess) { cleanup_all(); ACX_HIP(c, ec_); } } while (0)
-    ACX_HIPC(hipMalloc((void **)&d_tw, sizeof(double) * (24 + 2 * (size_t)win)));
-    ACX_HIPC(hipMemcpy(d_tw, tw12.data(), sizeof(double) * 24, hipMemcpyHostToDevice));
-    ACX_HIPC(hipMemcpy(d_tw + 24, twW.data(), sizeof(double) * 2 * win, hipMemcpyHostToDevice));
-    for (int t0 = 0; t0 < nt;) {
-        int t1 = t0 + 1;
-        int64_t lw = (nbeat[t0] - win + 1) * D * (int64_t)sizeof(double);
-        while (t1 < nt && t1 - t0 < 65535) {
-            const int64_t more = (nbeat[t1] - win + 1) * D * (int64_t)sizeof(double);
-            if (lw + more > lim || (coff[t1 + 1] - coff[t0]) * 12 > RAW_SLICE_FLOATS) break;
-            lw += more;
-            ++t1;
-        }
+    DeviceBuffer<double> d_tw;
+    ACX_HIP(c, d_tw.grow(24 + 2 * (size_t)win));
+    ACX_HIP(c, hipMemcpy(d_tw, tw12.data(), sizeof(double) * 24, hipMemcpyHostToDevice));
+    ACX_HIP(c, hipMemcpy(d_tw + 24, twW.data(), sizeof(double) * 2 * win, hipMemcpyHostToDevice));
+    DeviceBuffer<float> d_ch, d_sync;                // staging and intermediates of one slice: grown as needed, reused by the next
+    DeviceBuffer<int64_t> d_coff, d_bnd, d_boff, d_woff;
+    DeviceBuffer<double> d_pwr, d_G, d_lw, d_med;
+    DeviceBuffer<acx::FtmBlock> d_blk;
+    // a slice: its window matrices within `lim`, its chroma within the staging budget
+    std::vector<int64_t> wbytes((size_t)nt + 1, 0);
+    for (int t = 0; t < nt; ++t) wbytes[t + 1] = wbytes[t] + (nbeat[t] - win + 1) * D * (int64_t)sizeof(double);
+    const int64_t budget = raw_slice_bytes(c);
+    auto fits = [&](int t0, int t1) { return wbytes[t1] - wbytes[t0] <= lim && (coff[t1] - coff[t0]) * 12 * (int64_t)sizeof(float) <= budget; };
+    return for_track_slices(nt, 65535, fits, [&](int t0, int t1) -> int {
         const int n = t1 - t0;
         const int64_t rows = coff[t1] - coff[t0];
         std::vector<int64_t> lc(n + 1), lb(n + 1), lwo(n + 1), lbnd;
@@ -2713,26 +2622,26 @@ static int ftm2d_build(acx_ctx *c, const char *who, const float *chroma, const i
             for (int64_t w = 0; w < nwin; w += nw) blk.push_back(acx::FtmBlock{t, (int32_t)w});
         }
         const int64_t nb = lb[n], nwt = lwo[n];
-        ACX_HIPC(hipMalloc((void **)&d_ch, sizeof(float) * std::max<int64_t>(1, rows) * 12));
-        ACX_HIPC(hipMalloc((void **)&d_coff, sizeof(int64_t) * (n + 1)));
-        ACX_HIPC(hipMalloc((void **)&d_bnd, sizeof(int64_t) * lbnd.size()));
-        ACX_HIPC(hipMalloc((void **)&d_boff, sizeof(int64_t) * (n + 1)));
-        ACX_HIPC(hipMalloc((void **)&d_woff, sizeof(int64_t) * (n + 1)));
-        ACX_HIPC(hipMalloc((void **)&d_sync, sizeof(float) * nb * 12));
-        ACX_HIPC(hipMalloc((void **)&d_pwr, sizeof(double) * nb * 12));
-        ACX_HIPC(hipMalloc((void **)&d_G, sizeof(double) * nb * 14));
-        ACX_HIPC(hipMalloc((void **)&d_lw, sizeof(double) * nwt * D));
-        ACX_HIPC(hipMalloc((void **)&d_med, sizeof(double) * n * D));
-        ACX_HIPC(hipMalloc((void **)&d_blk, sizeof(acx::FtmBlock) * blk.size()));
-        ACX_HIPC(hipMemcpyAsync(d_ch, chroma + coff[t0] * 12, sizeof(float) * rows * 12, hipMemcpyHostToDevice, c->stream));
-        ACX_HIPC(hipMemcpyAsync(d_coff, lc.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, c->stream));
-        ACX_HIPC(hipMemcpyAsync(d_bnd, lbnd.data(), sizeof(int64_t) * lbnd.size(), hipMemcpyHostToDevice, c->stream));
-        ACX_HIPC(hipMemcpyAsync(d_boff, lb.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, c->stream));
-        ACX_HIPC(hipMemcpyAsync(d_woff, lwo.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, c->stream));
-        ACX_HIPC(hipMemcpyAsync(d_blk, blk.data(), sizeof(acx::FtmBlock) * blk.size(), hipMemcpyHostToDevice, c->stream));
+        ACX_HIP(c, d_ch.grow((size_t)std::max<int64_t>(1, rows) * 12));
+        ACX_HIP(c, d_coff.grow((size_t)n + 1));
+        ACX_HIP(c, d_bnd.grow(lbnd.size()));
+        ACX_HIP(c, d_boff.grow((size_t)n + 1));
+        ACX_HIP(c, d_woff.grow((size_t)n + 1));
+        ACX_HIP(c, d_sync.grow((size_t)nb * 12));
+        ACX_HIP(c, d_pwr.grow((size_t)nb * 12));
+        ACX_HIP(c, d_G.grow((size_t)nb * 14));
+        ACX_HIP(c, d_lw.grow((size_t)nwt * D));
+        ACX_HIP(c, d_med.grow((size_t)n * D));
+        ACX_HIP(c, d_blk.grow(blk.size()));
+        ACX_HIP(c, hipMemcpyAsync(d_ch, chroma + coff[t0] * 12, sizeof(float) * rows * 12, hipMemcpyHostToDevice, c->stream));
+        ACX_HIP(c, hipMemcpyAsync(d_coff, lc.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, c->stream));
+        ACX_HIP(c, hipMemcpyAsync(d_bnd, lbnd.data(), sizeof(int64_t) * lbnd.size(), hipMemcpyHostToDevice, c->stream));
+        ACX_HIP(c, hipMemcpyAsync(d_boff, lb.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, c->stream));
+        ACX_HIP(c, hipMemcpyAsync(d_woff, lwo.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, c->stream));
+        ACX_HIP(c, hipMemcpyAsync(d_blk, blk.data(), sizeof(acx::FtmBlock) * blk.size(), hipMemcpyHostToDevice, c->stream));
         {   // (the host buffers above are pageable: the copies are staged before the calls return)
-            const int rcs = scan_nonfinite(c, who, "chroma", d_ch, rows * 12, 12, 0, d_coff, n, false, track_base + t0);
-            if (rcs != ACX_OK) { cleanup_all(); return rcs; }
+            const int rcs = scan_nonfinite(c, who, "chroma", d_ch.get(), rows * 12, 12, 0, d_coff.get(), n, false, track_base + t0);
+            if (rcs != ACX_OK) return rcs;
         }
         hipLaunchKernelGGL(acx::ftm2d_sync_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, c->stream, d_ch, d_bnd, d_boff, n, nb, d_sync);
         hipLaunchKernelGGL(acx::ftm2d_beat_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, d_sync, nb, p.pwr, d_tw, d_pwr, d_G);
@@ -2745,26 +2654,22 @@ static int ftm2d_build(acx_ctx *c, const char *who, const float *chroma, const i
         else
             hipLaunchKernelGGL((acx::ftm2d_median_kernel<32>), dim3((D + 3) / 4, n), dim3(256), 0, c->stream, d_lw, d_woff, D, d_med);
         hipLaunchKernelGGL(acx::ftm2d_normalize_kernel, dim3(n), dim3(64), 0, c->stream, d_med, D, d_out + (int64_t)t0 * D);
-        ACX_HIPC(hipGetLastError());
+        ACX_HIP(c, hipGetLastError());
         if (dbg) {      // one track
-            if (dbg->synced) ACX_HIPC(hipMemcpyAsync(dbg->synced, d_sync, sizeof(float) * nb * 12, hipMemcpyDeviceToHost, c->stream));
-            if (dbg->pwr) ACX_HIPC(hipMemcpyAsync(dbg->pwr, d_pwr, sizeof(double) * nb * 12, hipMemcpyDeviceToHost, c->stream));
-            if (dbg->median) ACX_HIPC(hipMemcpyAsync(dbg->median, d_med, sizeof(double) * D, hipMemcpyDeviceToHost, c->stream));
+            if (dbg->synced) ACX_HIP(c, hipMemcpyAsync(dbg->synced, d_sync, sizeof(float) * nb * 12, hipMemcpyDeviceToHost, c->stream));
+            if (dbg->pwr) ACX_HIP(c, hipMemcpyAsync(dbg->pwr, d_pwr, sizeof(double) * nb * 12, hipMemcpyDeviceToHost, c->stream));
+            if (dbg->median) ACX_HIP(c, hipMemcpyAsync(dbg->median, d_med, sizeof(double) * D, hipMemcpyDeviceToHost, c->stream));
             if (dbg->logwin) {      // (D, nwin) on the device -> (nwin, D) like btchroma_to_fftmat(...).T
                 std::vector<double> h((size_t)nwt * D);
-                ACX_HIPC(hipMemcpyAsync(h.data(), d_lw, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
-                ACX_HIPC(hipStreamSynchronize(c->stream));
+                ACX_HIP(c, hipMemcpyAsync(h.data(), d_lw, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
+                ACX_HIP(c, hipStreamSynchronize(c->stream));
                 for (int64_t w = 0; w < nwt; ++w)
                     for (int d = 0; d < D; ++d) dbg->logwin[w * D + d] = h[(size_t)d * nwt + w];
             }
         }
-        ACX_HIPC(hipStreamSynchronize(c->stream));
-        cleanup();
-        t0 = t1;
-    }
-#undef ACX_HIPC
-    cleanup_all();
-    return ACX_OK;
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        return ACX_OK;
+    });
 }
 
 int acx_ftm2d_pool_begin(acx_ctx *c, int32_t n_tracks, const acx_ftm2d_params *params)
@@ -2861,15 +2766,14 @@ int acx_ftm2d_debug_track(acx_ctx *c, const float *chroma, int64_t n_frames, con
     if (!synced && !pwr && !logwin && !median && !shingle) return ACX_OK;
     ACX_HIP(c, hipSetDevice(c->device));
     c->nf_zeroed = 0;
-    double *d_s = nullptr;
-    ACX_HIP(c, hipMalloc((void **)&d_s, sizeof(double) * 12 * params->win));
+    DeviceBuffer<double> d_s;
+    ACX_HIP(c, d_s.grow((size_t)12 * params->win));
     FtmDebug dbg{synced, pwr, logwin, median};
     rc = ftm2d_build(c, "ftm2d_debug_track", chroma, coff, onsets, ooff, 1, 0, *params, d_s, &dbg);
     if (rc == ACX_OK && shingle) {
         const hipError_t e = hipMemcpy(shingle, d_s, sizeof(double) * 12 * params->win, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(c, ACX_ERR_HIP, std::string("ftm2d_debug_track: ") + hipGetErrorString(e));
     }
-    (void)hipFree(d_s);
     return rc;
 }
 
@@ -2885,8 +2789,8 @@ int acx_ftm2d_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, float *out)
     ACX_HIP(c, hipSetDevice(c->device));
     const int64_t CH = (int64_t)1 << 22;
     int rc;
-    if ((rc = ensure(c, c->d_pairs, c->pairs_cap, (size_t)2 * std::min(K, CH))) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_out, c->out_cap, (size_t)std::min(K, CH))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_pairs, (size_t)2 * std::min(K, CH))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_out, (size_t)std::min(K, CH))) != ACX_OK) return rc;
     for (int64_t k0 = 0; k0 < K; k0 += CH) {
         const int64_t n = std::min(CH, K - k0);
         ACX_HIP(c, hipMemcpyAsync(c->d_pairs, pairs + 2 * k0, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
@@ -2959,12 +2863,11 @@ extern "C++" {
 template <typename F>
 static int with_device_block(acx_ctx *c, const char *who, size_t total, F body)
 {
-    char *d_mem = nullptr;
-    const hipError_t e = hipMalloc((void **)&d_mem, total);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, ACX_ERR_NOMEM, std::string(who) + ": " + hipGetErrorString(e)); }
-    const int rc = body(d_mem);
+    DeviceBuffer<char> d_mem;
+    const hipError_t e = d_mem.grow(total);
+    if (e != hipSuccess) return fail(c, ACX_ERR_NOMEM, std::string(who) + ": " + hipGetErrorString(e));
+    const int rc = body(d_mem.get());
     if (rc != ACX_OK) quiesce(c); else drain_profile(c);
-    (void)hipFree(d_mem);
     return rc;
 }
 }  // extern "C++"
@@ -2999,16 +2902,9 @@ static int rank_for_pieces(acx_ctx *c, const float *scores, int64_t ld, int32_t 
     int rc;
     for (int e = 0; e < 2; ++e) {
         const size_t need = (size_t)ldd * piece;
-        if (need > c->rank_h_cap[e]) {
-            if (c->rank_h[e]) { (void)hipHostFree(c->rank_h[e]); c->rank_h[e] = nullptr; c->rank_h_cap[e] = 0; }
-            if (hipHostMalloc((void **)&c->rank_h[e], need * sizeof(float), hipHostMallocDefault) != hipSuccess) {
-                c->rank_h[e] = nullptr;
-                (void)hipGetLastError();
-                return fail(c, ACX_ERR_NOMEM, "rank: cannot allocate a pinned staging slot of " + std::to_string(need * sizeof(float)) + " bytes");
-            }
-            c->rank_h_cap[e] = need;
-        }
-        if ((rc = ensure(c, c->rank_d[e], c->rank_d_cap[e], need)) != ACX_OK) return rc;
+        if (c->rank_h[e].grow(need) != hipSuccess)
+            return fail(c, ACX_ERR_NOMEM, "rank: cannot allocate a pinned staging slot of " + std::to_string(need * sizeof(float)) + " bytes");
+        if ((rc = ensure(c, c->rank_d[e], need)) != ACX_OK) return rc;
         if (!c->rank_ev[e]) ACX_HIP(c, hipEventCreateWithFlags(&c->rank_ev[e], hipEventDisableTiming));
         if (n_rows <= piece) break;                                        // one piece: one slot
     }
@@ -3132,21 +3028,9 @@ int acx_topk_rows(acx_ctx *c, const float *scores, int64_t ld, int32_t n, int32_
 // two N x N work buffers.
 struct SnfRun {
     int m = 0, n = 0, K = 0;
-    std::vector<double *> cur, nxt, dV;
-    std::vector<int32_t *> dJ;
-    double *acc = nullptr, *ut = nullptr, *md = nullptr;
-    void release()
-    {
-        for (double *p : cur) if (p) (void)hipFree(p);
-        for (double *p : nxt) if (p) (void)hipFree(p);
-        for (double *p : dV) if (p) (void)hipFree(p);
-        for (int32_t *p : dJ) if (p) (void)hipFree(p);
-        if (acc) (void)hipFree(acc);
-        if (ut) (void)hipFree(ut);
-        if (md) (void)hipFree(md);
-        cur.clear(); nxt.clear(); dV.clear(); dJ.clear();
-        acc = ut = md = nullptr;
-    }
+    std::vector<DeviceBuffer<double>> cur, nxt, dV;
+    std::vector<DeviceBuffer<int32_t>> dJ;
+    DeviceBuffer<double> acc, ut, md;
 };
 
 static int snf_alloc(acx_ctx *c, SnfRun &R, int m, int n, int K)
@@ -3156,18 +3040,16 @@ static int snf_alloc(acx_ctx *c, SnfRun &R, int m, int n, int K)
     const size_t need = ((size_t)2 * m + 2) * nn * sizeof(double) + (size_t)m * n * K * (sizeof(double) + sizeof(int32_t));
     if (need > (size_t)(0.8 * (double)c->total_mem)) return fail(c, ACX_ERR_NOMEM, "snf_fuse: matrices do not fit the device");
     R.m = m; R.n = n; R.K = K;
-    R.cur.assign(m, nullptr); R.nxt.assign(m, nullptr); R.dV.assign(m, nullptr); R.dJ.assign(m, nullptr);
-#define ACX_HIPC(expr_) do { const hipError_t ec_ = (expr_); if (ec_ != hipSuccess) { R.release(); ACX_HIP(c, ec_); } } while (0)
-    ACX_HIPC(hipMalloc((void **)&R.acc, nn * sizeof(double)));
-    ACX_HIPC(hipMalloc((void **)&R.ut, nn * sizeof(double)));
-    ACX_HIPC(hipMalloc((void **)&R.md, (size_t)n * sizeof(double)));
+    R.cur.resize(m); R.nxt.resize(m); R.dV.resize(m); R.dJ.resize(m);
+    ACX_HIP(c, R.acc.grow(nn));
+    ACX_HIP(c, R.ut.grow(nn));
+    ACX_HIP(c, R.md.grow((size_t)n));
     for (int i = 0; i < m; ++i) {
-        ACX_HIPC(hipMalloc((void **)&R.cur[i], nn * sizeof(double)));
-        ACX_HIPC(hipMalloc((void **)&R.nxt[i], nn * sizeof(double)));
-        ACX_HIPC(hipMalloc((void **)&R.dV[i], (size_t)n * K * sizeof(double)));
-        ACX_HIPC(hipMalloc((void **)&R.dJ[i], (size_t)n * K * sizeof(int32_t)));
+        ACX_HIP(c, R.cur[i].grow(nn));
+        ACX_HIP(c, R.nxt[i].grow(nn));
+        ACX_HIP(c, R.dV[i].grow((size_t)n * K));
+        ACX_HIP(c, R.dJ[i].grow((size_t)n * K));
     }
-#undef ACX_HIPC
     return ACX_OK;
 }
 
@@ -3184,7 +3066,7 @@ static int snf_loop(acx_ctx *c, SnfRun &R, int niters, double reg_diag, double *
     for (int it = 0; it < niters; ++it) {
         // from the second sweep on the reference's two work lists alias: a matrix updated earlier in the
         // sweep is already seen by the later ones (similarity_fusion.py:179)
-        std::vector<double *> &src = it == 0 ? R.cur : R.nxt;
+        std::vector<DeviceBuffer<double>> &src = it == 0 ? R.cur : R.nxt;
         for (int i = 0; i < m; ++i) {
             acx::SnfSrc sp;
             sp.count = 0;
@@ -3237,10 +3119,8 @@ int acx_snf_fuse(acx_ctx *c, const double *const *Ws, const int32_t *const *Js, 
         if (e == hipSuccess) e = hipMemcpyAsync(R.acc, Ws[i], nn * sizeof(double), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) hipLaunchKernelGGL(acx::snf_rownorm_kernel, dim3(n), dim3(256), 0, c->stream, R.acc, R.cur[i], n);
     }
-    if (e != hipSuccess) { R.release(); ACX_HIP(c, e); }
-    rc = snf_loop(c, R, niters, reg_diag, out);
-    R.release();
-    return rc;
+    ACX_HIP(c, e);
+    return snf_loop(c, R, niters, reg_diag, out);
 }
 
 int acx_snf_fuse_dists(acx_ctx *c, const double *const *Ds, int32_t m, int32_t n, int32_t K, int32_t niters, double reg_diag,
@@ -3273,10 +3153,8 @@ int acx_snf_fuse_dists(acx_ctx *c, const double *const *Ds, int32_t m, int32_t n
         hipLaunchKernelGGL(acx::snf_rownorm_kernel, dim3(n), dim3(256), 0, c->stream, R.ut, R.cur[i], n);
         if (e == hipSuccess) e = hipGetLastError();
     }
-    if (e != hipSuccess) { R.release(); ACX_HIP(c, e); }
-    rc = snf_loop(c, R, niters, reg_diag, out);
-    R.release();
-    return rc;
+    ACX_HIP(c, e);
+    return snf_loop(c, R, niters, reg_diag, out);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3386,12 +3264,12 @@ static int run_simple_tiles(acx_ctx *c, const std::vector<acx_grid_tile> &mine, 
         }
         if (n > 0) {
             if (n > 0x7fffffff) return fail(c, ACX_ERR_UNSUPPORTED, "simple: a single tile holds more than 2^31 pairs");
-            if ((rc = ensure(c, c->d_pairs, c->pairs_cap, (size_t)2 * n)) != ACX_OK) return rc;
-            if ((rc = ensure(c, c->d_out64, c->out64_cap, (size_t)n)) != ACX_OK) return rc;
-            if ((rc = ensure(c, c->d_idx, c->idx_cap, (size_t)n)) != ACX_OK) return rc;
+            if ((rc = ensure(c, c->d_pairs, (size_t)2 * n)) != ACX_OK) return rc;
+            if ((rc = ensure(c, c->d_out64, (size_t)n)) != ACX_OK) return rc;
+            if ((rc = ensure(c, c->d_idx, (size_t)n)) != ACX_OK) return rc;
             if ((rc = upload_tiles(c, td.data(), sizeof(TileDev) * td.size())) != ACX_OK) return rc;
             hipLaunchKernelGGL(grid_pairs_kernel, dim3((unsigned)std::min<int64_t>((maxP + 255) / 256, 256), (unsigned)td.size()), dim3(256), 0,
-                               c->stream, static_cast<const TileDev *>(c->d_tiles), symmetric, 1, c->d_pairs, c->d_idx);
+                               c->stream, reinterpret_cast<const TileDev *>(c->d_tiles.get()), symmetric, 1, c->d_pairs, c->d_idx);
             {
                 ProfScope ps(c, KS_SIMPLE, n);
                 if ((rc = launch_simple_sslen(c, sp.sslen, (int)n, smem, sp.oti)) != ACX_OK) return rc;
@@ -3419,7 +3297,7 @@ static int run_ftm2d_tiles(acx_ctx *c, const std::vector<acx_grid_tile> &mine, i
     const int rc = upload_tiles(c, items.data(), sizeof(acx::FtmTileItem) * items.size());
     if (rc != ACX_OK) return rc;
     hipLaunchKernelGGL(acx::ftm2d_tile_kernel, dim3((unsigned)items.size()), dim3(256), 0, c->stream, c->d_ftm, c->ftm_dim,
-                       static_cast<const acx::FtmTileItem *>(c->d_tiles), symmetric, d_scores);
+                       reinterpret_cast<const acx::FtmTileItem *>(c->d_tiles.get()), symmetric, d_scores);
     ACX_HIP(c, hipGetLastError());
     return ACX_OK;
 }
@@ -3523,12 +3401,10 @@ int acx_pair_grid(acx_ctx *c, const acx_grid_spec *spec, const void *params, flo
         cap = std::max(cap, fl);
         a = b;
     }
-    float *d = nullptr, *h = nullptr;
-    ACX_HIP(c, hipMalloc((void **)&d, sizeof(float) * (size_t)std::max<int64_t>(1, cap)));
-    if (hipHostMalloc((void **)&h, sizeof(float) * (size_t)std::max<int64_t>(1, cap), hipHostMallocDefault) != hipSuccess) {
-        (void)hipFree(d);
-        return fail(c, ACX_ERR_NOMEM, "pair_grid: cannot allocate the pinned staging slice");
-    }
+    DeviceBuffer<float> d;
+    PinnedBuffer<float> h;
+    ACX_HIP(c, d.grow((size_t)std::max<int64_t>(1, cap)));
+    if (h.grow((size_t)std::max<int64_t>(1, cap)) != hipSuccess) return fail(c, ACX_ERR_NOMEM, "pair_grid: cannot allocate the pinned staging slice");
     // development aid (ACX_GRID_TIMING=1): the host's seconds in the three steps of a slice
     static const bool grid_timing = [] { const char *e = getenv("ACX_GRID_TIMING"); return e && e[0] == '1'; }();
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -3556,8 +3432,6 @@ int acx_pair_grid(acx_ctx *c, const acx_grid_spec *spec, const void *params, flo
         ++nslices;
         a = b;
     }
-    (void)hipFree(d);
-    (void)hipHostFree(h);
     if (grid_timing)
         fprintf(stderr, "[acx pair_grid] %d slice(s): device %.2f s, copy to the host %.2f s, scatter + mirror %.2f s\n", nslices, tg[0], tg[1], tg[2]);
     return rc;
@@ -3665,8 +3539,8 @@ static int run_simple_list(acx_ctx *c, const int32_t *pairs, const int64_t *idx,
     int rc = simple_front(c, sp.sslen, [&](auto visit) { for (int64_t k = 0; k < 2 * K; ++k) visit(pairs[k]); }, &smem);
     if (rc != ACX_OK) return rc;
     const int64_t CHUNK = (int64_t)1 << 22;
-    if ((rc = ensure(c, c->d_pairs, c->pairs_cap, (size_t)2 * std::min(K, CHUNK))) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_out64, c->out64_cap, (size_t)std::min(K, CHUNK))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_pairs, (size_t)2 * std::min(K, CHUNK))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_out64, (size_t)std::min(K, CHUNK))) != ACX_OK) return rc;
     for (int64_t k0 = 0; k0 < K; k0 += CHUNK) {
         const int n = (int)std::min(CHUNK, K - k0);
         ACX_HIP(c, hipMemcpyAsync(c->d_pairs, pairs + 2 * k0, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
@@ -3939,25 +3813,26 @@ int acx_dev_alloc(acx_ctx *c, int64_t bytes, void **d_ptr)
     if (!c) return ACX_ERR_INVALID;
     if (bytes < 0 || !d_ptr) return fail(c, ACX_ERR_INVALID, "dev_alloc: bad argument");
     ACX_HIP(c, hipSetDevice(c->device));
-    void *p = nullptr;
-    const hipError_t e = hipMalloc(&p, (size_t)std::max<int64_t>(bytes, 4));
+    DeviceBuffer<char> buf;
+    const hipError_t e = buf.grow((size_t)std::max<int64_t>(bytes, 4));
     if (e != hipSuccess) return fail(c, ACX_ERR_NOMEM, std::string("dev_alloc: ") + hipGetErrorString(e));
-    ACX_HIP(c, hipMemsetAsync(p, 0, (size_t)std::max<int64_t>(bytes, 4), c->stream));
+    ACX_HIP(c, hipMemsetAsync(buf, 0, buf.capacity(), c->stream));
     ACX_HIP(c, hipStreamSynchronize(c->stream));
-    c->dev_bufs.push_back(p);
-    *d_ptr = p;
+    *d_ptr = buf.get();
+    c->dev_bufs.push_back(std::move(buf));
     return ACX_OK;
 }
 
 int acx_dev_free(acx_ctx *c, void *d_ptr)
 {
     if (!c) return ACX_ERR_INVALID;
-    auto it = std::find(c->dev_bufs.begin(), c->dev_bufs.end(), d_ptr);
+    auto it = std::find_if(c->dev_bufs.begin(), c->dev_bufs.end(), [&](const DeviceBuffer<char> &b) { return b.get() == d_ptr; });
     if (it == c->dev_bufs.end()) return fail(c, ACX_ERR_INVALID, "dev_free: not a buffer of this context");
     ACX_HIP(c, hipSetDevice(c->device));
     ACX_HIP(c, hipStreamSynchronize(c->stream));
+    const hipError_t e = it->reset();
     c->dev_bufs.erase(it);
-    ACX_HIP(c, hipFree(d_ptr));
+    ACX_HIP(c, e);
     return ACX_OK;
 }
 
@@ -4115,8 +3990,8 @@ int acx_pair_grid_ranks(acx_ctx *c, const acx_grid_spec *spec_in, const void *pa
     const int w = acx::grid_planes(spec.algo);
     const int world = spec.world;
     ACX_HIP(c, hipSetDevice(c->device));
-    float *d_st = nullptr;                                      // [0] this rank's status, [1 .. world] everybody's
-    ACX_HIP(c, hipMalloc((void **)&d_st, sizeof(float) * (size_t)(world + 1)));
+    DeviceBuffer<float> d_st;                                   // [0] this rank's status, [1 .. world] everybody's
+    ACX_HIP(c, d_st.grow((size_t)world + 1));
     int st = ACX_OK;
     std::string why;
     auto local_fail = [&](int code, const std::string &msg) { if (st == ACX_OK) { st = code; why = msg; } };
@@ -4135,18 +4010,15 @@ int acx_pair_grid_ranks(acx_ctx *c, const acx_grid_spec *spec_in, const void *pa
     std::vector<int64_t> fl;
     std::vector<double> co;
     int64_t stride = 1;
-    float *d_local = nullptr, *d_all = nullptr;
+    DeviceBuffer<float> d_local, d_all;
     if (st == ACX_OK) {
         acx::grid_plan(len.data(), (int)len.size(), spec, tiles, fl, co);
         for (int r = 0; r < world; ++r) stride = std::max(stride, fl[r]);
         // (+ 1: the status float behind the tiles)
-        if (hipMalloc((void **)&d_local, sizeof(float) * (size_t)(stride + 1)) != hipSuccess ||
-            hipMalloc((void **)&d_all, sizeof(float) * (size_t)(stride + 1) * world) != hipSuccess) {
-            (void)hipGetLastError();
+        if (d_local.grow((size_t)(stride + 1)) != hipSuccess || d_all.grow((size_t)(stride + 1) * world) != hipSuccess) {
             local_fail(ACX_ERR_NOMEM, "pair_grid_ranks: the gathered score buffers do not fit the device");
         }
     }
-    auto release = [&]() { if (d_local) (void)hipFree(d_local); if (d_all) (void)hipFree(d_all); (void)hipFree(d_st); };
     // every rank's status, before any rank starts its tiles
     std::vector<float> hst((size_t)world + 1, 0.0f);
     auto exchange_status = [&](int mine) -> int {                // returns the first failing rank, -1 if none, -2 on a HIP / RCCL error
@@ -4158,7 +4030,6 @@ int acx_pair_grid_ranks(acx_ctx *c, const acx_grid_spec *spec_in, const void *pa
         return -1;
     };
     auto fail_all = [&](int bad_rank) -> int {
-        release();
         if (bad_rank == -2) return fail(c, ACX_ERR_HIP, "pair_grid_ranks: the status exchange failed");
         if (st != ACX_OK) return fail(c, st, why);
         return fail(c, (int)hst[bad_rank], "pair_grid_ranks: rank " + std::to_string(bad_rank) + " failed (its own context holds the message)");
@@ -4175,7 +4046,7 @@ int acx_pair_grid_ranks(acx_ctx *c, const acx_grid_spec *spec_in, const void *pa
     }
     // (a rank whose tiles failed still joins: the others must not be left waiting, and they learn about it from the status float)
     const int rg = acx_grid_allgather(c, d_local, d_all, stride + 1);
-    if (rg != ACX_OK) { release(); return rg; }
+    if (rg != ACX_OK) return rg;
     if (hipMemcpy2D(hst.data(), sizeof(float), d_all + stride, sizeof(float) * (size_t)(stride + 1), sizeof(float), (size_t)world,
                     hipMemcpyDeviceToHost) != hipSuccess) return fail_all(-2);
     bad = -1;
@@ -4188,7 +4059,6 @@ int acx_pair_grid_ranks(acx_ctx *c, const acx_grid_spec *spec_in, const void *pa
         if (e != hipSuccess) out = fail(c, ACX_ERR_HIP, std::string("pair_grid_ranks: ") + hipGetErrorString(e));
         else acx::grid_scatter(tiles, spec, h.data(), stride + 1, 0, -1, D, ld, mirror);
     }
-    release();
     return out;
 }
 
@@ -4240,16 +4110,14 @@ static int debug_sqrt(acx_ctx *c, const float *in, int64_t n, float *out, bool e
 {
     if (!c || !in || !out || n <= 0) return ACX_ERR_INVALID;
     ACX_HIP(c, hipSetDevice(c->device));
-    float *d_in = nullptr, *d_o = nullptr;
-    ACX_HIP(c, hipMalloc((void **)&d_in, sizeof(float) * n));
-    ACX_HIP(c, hipMalloc((void **)&d_o, sizeof(float) * n));
+    DeviceBuffer<float> d_in, d_o;
+    ACX_HIP(c, d_in.grow((size_t)n));
+    ACX_HIP(c, d_o.grow((size_t)n));
     ACX_HIP(c, hipMemcpy(d_in, in, sizeof(float) * n, hipMemcpyHostToDevice));
-    if (ef) hipLaunchKernelGGL(acx::ef_sqrt_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_in, d_o, n);
-    else hipLaunchKernelGGL(acx::sqrt_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_in, d_o, n);
+    if (ef) hipLaunchKernelGGL(acx::ef_sqrt_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_in.get(), d_o.get(), n);
+    else hipLaunchKernelGGL(acx::sqrt_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_in.get(), d_o.get(), n);
     ACX_HIP(c, hipStreamSynchronize(c->stream));
     ACX_HIP(c, hipMemcpy(out, d_o, sizeof(float) * n, hipMemcpyDeviceToHost));
-    (void)hipFree(d_in);
-    (void)hipFree(d_o);
     return ACX_OK;
 }
 

@@ -105,6 +105,28 @@ def test_raw_pool_equals_uploaded_block_features(ctx):
     assert np.max(np.abs(a - c)) <= 2.0
 
 
+def test_sliced_raw_pool_is_bit_identical(ctx):
+    """A scratch limit below the raw features makes the collection-level entry point stage them in slices of whole tracks
+    (a slice takes tracks while their raw chroma and MFCCs fit the limit, and at least one).  The block kernels work per
+    track: block offsets and pair scores equal those of the unsliced upload bit for bit."""
+    import oracle
+    rng = np.random.default_rng(9)
+    # a frame is 12 + 13 floats = 100 bytes; 1500 frames per slice: {600, 700} {2400} {650, 500} {900, 550} -- slices of
+    # two tracks and a track over the budget on its own
+    tracks = [_track(rng, T, nb) for T, nb in ((600, 31), (700, 44), (2400, 52), (650, 38), (500, 27), (900, 49), (550, 33))]
+    pairs = oracle.all_pairs(len(tracks), True).astype(np.int32)
+    boff = ctx.ef_upload_raw_pool(tracks)
+    want = ctx.earlyfusion_pairs(pairs)
+    try:
+        ctx.set_scratch_limit(100 * 1500)
+        boff_s = ctx.ef_upload_raw_pool(tracks)
+    finally:
+        ctx.set_scratch_limit(0)
+    assert np.array_equal(boff_s, boff) and np.array_equal(np.diff(boff), [len(t["onsets"]) - 20 for t in tracks])
+    got = ctx.earlyfusion_pairs(pairs)
+    assert got.tobytes() == want.tobytes()
+
+
 def test_earlyfusion_class_from_raw_feature_files(tmp_path, monkeypatch):
     """EarlyFusion over track files that hold raw features only: load_features(i) computes the blocks
     on the device, all_pairwise builds the whole pool there, and the grid equals the pair list."""

@@ -49,10 +49,23 @@ def test_rejects_and_names_the_track():
             ctx.upload_pool_f64(g, offsets)
         raw = np.repeat(frames, 3, axis=0)
         raw[3 * offsets[6] + 2, 5] = np.nan
-        with pytest.raises(ValueError, match=r"track 6 holds"):
+        with pytest.raises(ValueError, match=r"track 6 holds") as unsliced:
             ctx.upload_raw_pool(raw, 3 * offsets, fac=3)
         with pytest.raises(ValueError, match=r"track 6 holds"):
             ctx.simple_upload_raw_pool(raw, 3 * offsets, win=6, skip=3)
+        # ... and in slices: 1500 raw frames (48 bytes each) per slice is {0, 1, 2} {3, 4, 5} {6, 7, 8} {9, 10, 11} for these
+        # lengths, so the upload fails in its THIRD slice -- with the same error, and the context takes a clean pool after it
+        assert (3 * np.diff(offsets)).tolist() == [672, 258, 312, 342, 312, 666, 705, 540, 231, 261, 399, 456]
+        try:
+            ctx.set_scratch_limit(12 * 4 * 1500)
+            with pytest.raises(ValueError) as sliced:
+                ctx.upload_raw_pool(raw, 3 * offsets, fac=3)
+            assert str(sliced.value) == str(unsliced.value)
+            poff = ctx.upload_raw_pool(np.repeat(frames, 3, axis=0), 3 * offsets, fac=3)
+            assert np.array_equal(poff, offsets)
+            assert np.array_equal(ctx.download_pool(poff[-1]), np.asarray(frames, np.float32))     # (the median of three equal frames)
+        finally:
+            ctx.set_scratch_limit(0)
     finally:
         ctx.close()
 

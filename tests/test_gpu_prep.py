@@ -90,6 +90,38 @@ def test_simple_features_on_device(ctx):
     np.testing.assert_allclose(ctx.download_pool_f64(poff[-1]), np.concatenate(want), rtol=1e-13, atol=1e-16)
 
 
+def test_sliced_raw_uploads_are_bit_identical(ctx):
+    """A scratch limit below the raw features makes both raw uploads stage them in slices of whole tracks: a slice takes
+    tracks while their raw chroma (48 bytes a frame) fits the limit, and at least one.  The preparation kernels work per
+    track, so the pooled offsets and every byte of the pool equal those of the unsliced upload."""
+    rng = np.random.default_rng(21)
+    # Serra09, 1300 frames per slice: {400, 1} {1234, 41} {80} {4001} {39, 2} -- slices of several tracks, a track over
+    # the budget on its own, tracks shorter than fac
+    raw, roff = _pack(_raw_tracks(rng, [400, 1, 1234, 41, 80, 4001, 39, 2]))
+    poff = ctx.upload_raw_pool(raw, roff, 40)
+    want = ctx.download_pool(poff[-1])
+    try:
+        ctx.set_scratch_limit(12 * 4 * 1300)
+        poff_s = ctx.upload_raw_pool(raw, roff, 40)
+        got = ctx.download_pool(poff_s[-1])
+    finally:
+        ctx.set_scratch_limit(0)
+    assert np.array_equal(poff_s, poff)
+    assert got.tobytes() == want.tobytes()
+    # SiMPle, 3000 frames per slice: {1000, 1099} {2543} {1100} {7777} {1000, 1234}
+    raw, roff = _pack(_raw_tracks(rng, [1000, 1099, 2543, 1100, 7777, 1000, 1234]))
+    poff = ctx.simple_upload_raw_pool(raw, roff)
+    want = ctx.download_pool_f64(poff[-1])
+    try:
+        ctx.set_scratch_limit(12 * 4 * 3000)
+        poff_s = ctx.simple_upload_raw_pool(raw, roff)
+        got = ctx.download_pool_f64(poff_s[-1])
+    finally:
+        ctx.set_scratch_limit(0)
+    assert np.array_equal(poff_s, poff)
+    assert got.tobytes() == want.tobytes()
+
+
 def test_errors(ctx):
     rng = np.random.default_rng(1)
     raw, roff = _pack(_raw_tracks(rng, [100, 200]))
