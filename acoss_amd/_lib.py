@@ -37,6 +37,7 @@ EXPORTS = [
     "acx_ftm2d_upload_shingles", "acx_ftm2d_download_shingles", "acx_ftm2d_debug_track", "acx_ftm2d_pairs",
     "acx_rank_columns", "acx_topk_rows",
     "acx_query_scores", "acx_query_topk", "acx_query_ranks",
+    "acx_serra09_debug_bits",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -201,6 +202,7 @@ def load():
     L.acx_serra09_pairs.argtypes = [vp, ip, ctypes.c_int64, pp, fp]
     L.acx_chenfusion_pairs.argtypes = [vp, ip, ctypes.c_int64, pp, fp]
     L.acx_serra09_debug_pair.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, pp, fp, fp, fp, fp, fp, ip, fp, ip]
+    L.acx_serra09_debug_bits.argtypes = [vp, ip, ctypes.c_int64, pp, fp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int64)]
     L.acx_serra09_embed_len.restype = ctypes.c_int32
     L.acx_serra09_embed_len.argtypes = [ctypes.c_int32, pp]
     L.acx_profile_enable.argtypes = [vp, ctypes.c_int]
@@ -830,6 +832,23 @@ class Context(object):
                                                    ctypes.byref(oti), ctypes.byref(score), dims))
         assert (dims[0], dims[1]) == (Mq, Mr)
         return dict(d2=d2, eps_q=eq, eps_r=er, thr_q=tq, thr_r=tr, oti=int(oti.value), score=float(score.value))
+
+    def serra09_debug_bits(self, pairs, params=None):
+        """The product path's scores and recurrence plots (acx_serra09_debug_bits): (scores (K,) float32, [R_k]) with R_k the
+        (Mq, Mr) uint8 plot of pair k as the kernels of serra09_pairs wrote it.  The list must fit one batch.
+        self.outside_bits: set bits found in the pairs' bitmap words outside the matrices' columns (the sweeps mask those)."""
+        p = params or serra09_params()
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        dims = [(max(self.serra09_embed_len(self.lengths[i], p), 0), max(self.serra09_embed_len(self.lengths[j], p), 0))
+                for i, j in pairs]
+        off = np.concatenate([[0], np.cumsum([a * b for a, b in dims], dtype=np.int64)])
+        scores = np.empty(len(pairs), np.float32)
+        R = np.empty(max(int(off[-1]), 1), np.uint8)
+        outside = ctypes.c_int64(0)
+        self._check(self._L.acx_serra09_debug_bits(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), _fptr(scores),
+                                                   R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(outside)))
+        self.outside_bits = int(outside.value)
+        return scores, [R[off[k]:off[k + 1]].reshape(dims[k]) for k in range(len(pairs))]
 
     def qmax_binary(self, R, params=None):
         """Qmax / Dmax of a binary (M, N) cross recurrence plot (acx_qmax_binary)."""

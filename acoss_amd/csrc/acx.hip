@@ -1879,6 +1879,85 @@ int acx_serra09_debug_pair(acx_ctx *c, int32_t i, int32_t j, const acx_serra09_p
     return rc;
 }
 
+// Would run_serra09 take the whole list in ONE batch?  The same arithmetic as its batch loop, for the product path (no D2 in the
+// scratch but for streaming-class pairs).  A pair the loop would refuse (index, length, scratch limit) answers true: the run itself
+// reports it, before its first launch.
+static bool serra09_one_batch(const acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in)
+{
+    if (K > 65535) return false;
+    acx_serra09_params p = p_in;
+    p.tau = 1;
+    const int64_t limit_floats = scratch_limit_bytes(c) / 4;
+    int64_t used = 0, used_bits = 0;
+    for (int64_t k = 0; k < K; ++k) {
+        const int qi = pairs[2 * k], ri = pairs[2 * k + 1];
+        if (qi < 0 || ri < 0 || qi >= c->n_tracks || ri >= c->n_tracks) return true;
+        const int64_t Tq = c->h_off0[qi + 1] - c->h_off0[qi], Tr = c->h_off0[ri + 1] - c->h_off0[ri];
+        const int Mq = embed_len((int)((Tq + p_in.tau - 1) / p_in.tau), p), Mr = embed_len((int)((Tr + p_in.tau - 1) / p_in.tau), p);
+        if (Mq <= 0 || Mr <= 0) return true;
+        const bool is_long = p.m > acx::MAX_M || (std::max(Mq, Mr) + acx::BAND - 1 + 63) / 64 > 32;
+        const int64_t nw = (Mr + acx::BAND - 1 + 63) / 64;
+        const int64_t need = is_long ? (int64_t)Mq * round_up(Mr, 64) + (int64_t)Mr * round_up(Mq, 64) + 8 * (int64_t)Mq : 0;
+        if (need + 2 * (int64_t)Mq * nw > limit_floats) return true;
+        used += need;
+        used_bits += (int64_t)Mq * nw;
+        if (used + 2 * used_bits > limit_floats) return false;
+    }
+    return true;
+}
+
+int acx_serra09_debug_bits(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, float *scores,
+                           uint8_t *R_out, int64_t *outside)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (K < 0 || (K > 0 && (!pairs || !scores || !R_out)) || !params) return fail(c, ACX_ERR_INVALID, "serra09_debug_bits: bad argument");
+    if (outside) *outside = 0;
+    if (K == 0) return ACX_OK;
+    if (!c->d_frames0) return fail(c, ACX_ERR_STATE, "serra09: feature pool not uploaded (acx_upload_pool)");
+    int rc = check_params(c, *params);
+    if (rc != ACX_OK) return rc;
+    if (!serra09_one_batch(c, pairs, K, *params))
+        return fail(c, ACX_ERR_UNSUPPORTED, "serra09_debug_bits: the pair list does not fit one batch");
+    // the product call itself: no debug flag reaches a kernel, the sweeps keep their stream, the batch keeps its class sort
+    if ((rc = run_serra09(c, pairs, K, *params, scores, nullptr)) != ACX_OK) return rc;
+    // one batch: slot 0 still holds its descriptors (sorted by class key) and perm[k2] = position in `pairs` of sorted pair k2;
+    // collect_slot has waited for the sweeps, which waited for every band kernel
+    const Serra09Slot &S = c->slot[0];
+    if (S.B != K) return fail(c, ACX_ERR_STATE, "serra09_debug_bits: the run took more than one batch");
+    int64_t words = 0;
+    std::vector<int64_t> offR((size_t)K + 1, 0);
+    for (int k2 = 0; k2 < S.B; ++k2) {
+        const PairDesc &d = S.pd[k2];
+        words = std::max<int64_t>(words, d.offT + (int64_t)d.Mq * d.nw);
+        offR[(size_t)S.perm[k2] + 1] = (int64_t)d.Mq * d.Mr;
+    }
+    for (int64_t k = 0; k < K; ++k) offR[k + 1] += offR[k];
+    std::vector<unsigned long long> h((size_t)words);
+    ACX_HIP(c, hipMemcpy(h.data(), c->d_bits, sizeof(unsigned long long) * (size_t)words, hipMemcpyDeviceToHost));
+    // the inverse of acx_qmax_binary's packing: bit b of word t of row i = column 64 t + b - 7 + (i & 7)
+    int64_t out_bits = 0;
+    for (int k2 = 0; k2 < S.B; ++k2) {
+        const PairDesc &d = S.pd[k2];
+        uint8_t *R = R_out + offR[S.perm[k2]];
+        for (int i = 0; i < d.Mq; ++i) {
+            const int c0 = (i & (acx::BAND - 1)) - (acx::BAND - 1);
+            const unsigned long long *row = h.data() + d.offT + (int64_t)i * d.nw;
+            uint8_t *Ri = R + (int64_t)i * d.Mr;
+            memset(Ri, 0, (size_t)d.Mr);
+            for (int t = 0; t < d.nw; ++t) {
+                unsigned long long wd = row[t];
+                while (wd) {
+                    const int j = 64 * t + __builtin_ctzll(wd) + c0;
+                    wd &= wd - 1;
+                    if (j >= 0 && j < d.Mr) Ri[j] = 1; else ++out_bits;
+                }
+            }
+        }
+    }
+    if (outside) *outside = out_bits;
+    return ACX_OK;
+}
+
 int acx_qmax_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, float *score)
 {
     if (!c) return ACX_ERR_INVALID;

@@ -183,12 +183,32 @@ int acx_chenfusion_pairs(acx_ctx *ctx, const int32_t *pairs, int64_t K,
  *   thrq (Mq), thrr (Mr)   the same thresholds moved to the d2 domain
  *                          (largest f32 x with sqrt(x) <=/< eps)
  *   oti, score, dims[2] = {Mq, Mr}
+ * To hand back d2 and the thresholds this entry runs the D2-WRITING instantiations of the band
+ * kernels, with the thresholds' d-domain values kept, on one stream, one pair per batch: not the
+ * kernels acx_serra09_pairs launches.  acx_serra09_debug_bits observes those.
  */
 int acx_serra09_debug_pair(acx_ctx *ctx, int32_t i, int32_t j,
                            const acx_serra09_params *params,
                            float *d2, float *epsq, float *epsr,
                            float *thrq, float *thrr,
                            int32_t *oti, float *score, int32_t *dims);
+
+/*
+ * The recurrence plots of the PRODUCT path, for parity tests: runs exactly what acx_serra09_pairs
+ * runs for the list (same kernels, same size-class sort, same streams; scores: K floats) and then
+ * copies the batch's recurrence bitmaps back and unpacks them on the host:
+ *   R_out   uint8 (Mq_k x Mr_k) plots, row-major, concatenated in the order of `pairs`
+ *           (sum of Mq_k * Mr_k bytes)
+ *   outside (may be NULL) number of set bits found in the pairs' bitmap words at columns outside
+ *           [0, Mr).  The alignment sweeps do not rely on these being zero: every sweep kernel
+ *           masks the columns left of 0 and right of the matrix itself, so this is a figure to
+ *           report, not an invariant.
+ * The list must fit ONE batch (the scratch limit, 65535 pairs); otherwise ACX_ERR_UNSUPPORTED and
+ * nothing is launched.  Validation is acx_serra09_pairs'.
+ */
+int acx_serra09_debug_bits(acx_ctx *ctx, const int32_t *pairs, int64_t K,
+                           const acx_serra09_params *params, float *scores,
+                           uint8_t *R_out, int64_t *outside);
 
 /*
  * The alignment alone (tests): Qmax ('serra09', params->dmax = 0) or Dmax ('chen17', dmax = 1) of a

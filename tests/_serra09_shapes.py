@@ -1,0 +1,211 @@
+"""
+Shape sets for the Serra09 band and sweep kernels (tests/test_gpu_serra09_shapes.py; their design is checked on the CPU by
+tests/test_serra09_shapes_design.py).  Importable without a GPU: numpy, acoss_amd.synth and the CPU oracle only.
+
+The product path (run_serra09_impl, acoss_amd/csrc/acx.hip) sorts a batch by the size classes of a pair's two sides and picks a
+band kernel (launch_band_m, acoss_amd/csrc/acx_band.hip) and a sweep kernel per class; the sets below put tracks on both sides of
+every class edge and of every tile count, in every (reference class, query class) combination.
+"""
+import functools
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+BAND = 8
+NC = 5
+UPPER = (249, 505, 761, 1017, 2041)      # the longest row (cells) of classes 0 .. 4
+LOWER = (250, 506, 762, 1018)            # the shortest row of classes 1 .. 4
+
+
+def cls(M):
+    """Size class of a row of M cells: cls1 of run_serra09_impl (acoss_amd/csrc/acx.hip) -- nd = (M + BAND - 1 + 63) / 64 tiles,
+    <= 4 / 8 / 12 / 16 / 32 of them, i.e. M <= 249 / 505 / 761 / 1017 / 2041; 5: the streaming kernels."""
+    nd = (M + BAND - 1 + 63) // 64
+    return 0 if nd <= 4 else 1 if nd <= 8 else 2 if nd <= 12 else 3 if nd <= 16 else 4 if nd <= 32 else 5
+
+
+def key(Mq, Mr):
+    """(cr, cq): the row pass and the sweep run per cr (rows of Mr cells), the column pass per (cr, cq) (rows of Mq cells)."""
+    return cls(Mr), cls(Mq)
+
+
+def family(m, c):
+    """The band kernel family a pass whose longest row is of class c launches for stack size m, as launch_band_m
+    (acoss_amd/csrc/acx_band.hip) decides it by default (no ACX_BAND2)."""
+    if m <= 9:
+        return ("band2_kernel<M, B2_NV, 16>", "band2_kernel<M, B2_NV, 32>", "band2_kernel<M, B2_NV_MID, 32>",
+                "band_kernel<M<=9, 4>", "band_kernel<M<=9, 8>")[c]
+    return ("band_kernel<M>=10, 2>", "band_kernel<M>=10, 2>", "band_kernel<M>=10, 4>", "band_kernel<M>=10, 4>",
+            "band_kernel<M>=10, 8>")[c]
+
+
+FAMILIES = frozenset(family(m, c) for m in (9, 10) for c in range(NC))
+
+
+def _embed_len(T, m):
+    import oracle
+    return oracle.serra09_embed_len(T, oracle.serra09_params(m=m))
+
+
+def frames_for(M, m):
+    """The pooled length T whose embedded length is M (tau = 1, embed_full = 0: T = M + m, but by the function)."""
+    T = M
+    while _embed_len(T, m) < M:
+        T += 1
+    assert _embed_len(T, m) == M
+    return T
+
+
+def _pack(tracks, Ms, pairs, **extra):
+    from acoss_amd import synth
+    frames, offsets = synth.pack(tracks)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    return dict(frames=frames, offsets=offsets, pairs=pairs, M=np.asarray(Ms, np.int64), **extra)
+
+
+def _work(rng, T):
+    """One long chord sequence in the style of synth.cover_set: triads held for 4-16 frames."""
+    from acoss_amd import synth
+    tri = synth._triads()
+    chords = []
+    c = int(rng.integers(0, 24))
+    while len(chords) < T:
+        chords += [c] * int(rng.integers(4, 17))
+        c = (c + int(rng.choice([-5, -2, 2, 5, 7, 1]))) % 24
+    return tri[np.array(chords[:T])]
+
+
+def _version(rng, excerpt):
+    from acoss_amd import synth
+    x = np.roll(excerpt, int(rng.integers(0, 12)), axis=1) + 0.05 * rng.random(excerpt.shape)
+    return synth._frame_max_normalise(x)
+
+
+def _iid(rng, T):
+    from acoss_amd import synth
+    return synth._frame_max_normalise(rng.random((T, 12)))
+
+
+@functools.lru_cache(maxsize=4)
+def edge_set(m, seed=0):
+    """Tracks at both sides of every class edge (249 | 250, 505 | 506, 761 | 762, 1017 | 1018), at 2041, 40 and 3 cells: per length one
+    excerpt from the START of one long work and one from its END (rolled, noisy versions of it), so that alignments run through
+    the first and the last tiles.  45 pairs, 26.8 Mcells: the 25 (query edge, reference edge) combinations of the upper edges
+    (every (cr, cq) key), each lower edge against its upper neighbour in both orders, against its twin, a 40- and a 3-cell track."""
+    rng = np.random.default_rng([seed, m, 1])
+    lengths = list(UPPER) + list(LOWER) + [3, 40]
+    W = frames_for(max(lengths), m) + 500
+    work = _work(rng, W)
+    tracks, Ms, start, end = [], [], {}, {}
+    for M in lengths:
+        T = frames_for(M, m)
+        start[M] = len(tracks); tracks.append(_version(rng, work[:T])); Ms.append(M)
+        end[M] = len(tracks); tracks.append(_version(rng, work[W - T:])); Ms.append(M)
+    pairs = [(start[a], end[b]) for a in UPPER for b in UPPER]
+    for lo, up in zip(LOWER, UPPER):
+        pairs += [(start[lo], end[up]), (end[up], start[lo])]
+    for lo in LOWER:
+        pairs += [(start[lo], end[lo]), (start[lo], end[40]), (start[lo], end[3])]
+    return _pack(tracks, Ms, pairs, start=start, end=end)
+
+
+@functools.lru_cache(maxsize=2)
+def tile_edge_set(m, seed=0):
+    """i.i.d. tracks of 57 + 64 k (k = 0 .. 31) and 58 + 64 k (k = 0 .. 30) cells -- the last length of a tile count and the first
+    of the next, for every count `ndata` takes -- each against one 300-cell track in both orders: 126 pairs."""
+    rng = np.random.default_rng([seed, m, 2])
+    Ms = [57 + 64 * k for k in range(32)] + [58 + 64 * k for k in range(31)] + [300]
+    tracks = [_iid(rng, frames_for(M, m)) for M in Ms]
+    f = len(Ms) - 1
+    pairs = [(i, f) for i in range(f)] + [(f, i) for i in range(f)]
+    return _pack(tracks, Ms, pairs)
+
+
+@functools.lru_cache(maxsize=3)
+def row_residue_set(m, seed=0):
+    """Queries of 1 .. 17 and 248 .. 251 cells (every row count mod 8, the tails of four and of two rows per wave) against references of
+    100, 400, 700, 1000 and 1500 cells (one per class): 105 pairs."""
+    rng = np.random.default_rng([seed, m, 3])
+    q = list(range(1, 18)) + [248, 249, 250, 251]
+    r = [100, 400, 700, 1000, 1500]
+    Ms = q + r
+    tracks = [_iid(rng, frames_for(M, m)) for M in Ms]
+    pairs = [(i, len(q) + j) for i in range(len(q)) for j in range(len(r))]
+    return _pack(tracks, Ms, pairs)
+
+
+def subset(d, pairs):
+    """The same tracks with another pair list."""
+    out = dict(d)
+    out["pairs"] = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    return out
+
+
+def track(d, i):
+    return d["frames"][d["offsets"][i]:d["offsets"][i + 1]]
+
+
+def workers():
+    from acoss_amd import utils
+    return max(1, min(16, utils.effective_cpus()))
+
+
+def pool_map(fn, items):
+    """fn over items on min(16, effective CPUs) threads (the oracle's C routines run without the GIL and keep no global state)."""
+    items = list(items)
+    with ThreadPoolExecutor(workers()) as ex:
+        return list(ex.map(fn, items))
+
+
+def oracle_plots(d, **kw):
+    """The oracle over the set's pairs: (scores (K,) float32, [R_k]) with the parameters kw (oracle.serra09_params)."""
+    import oracle
+    oracle.lib()
+    p = oracle.serra09_params(**kw)
+    def one(ij):
+        s, it = oracle.serra09_pair(track(d, ij[0]), track(d, ij[1]), p, want_intermediates=True)
+        return s, it["R"]               # (the distances are dropped here: 16 MB for a 2041 x 2041 pair)
+    res = pool_map(one, d["pairs"])
+    return np.array([s for s, _ in res], np.float32), [R for _, R in res]
+
+
+def oracle_scores(d, **kw):
+    """The full-chain oracle's scores alone."""
+    import oracle
+    oracle.lib()
+    p = oracle.serra09_params(**kw)
+    return np.array(pool_map(lambda ij: oracle.serra09_pair(track(d, ij[0]), track(d, ij[1]), p), d["pairs"]), np.float32)
+
+
+def oracle_sweeps(Rs, gamma_o=0.5, gamma_e=0.5, dmax=False):
+    import oracle
+    oracle.lib()
+    return np.array(pool_map(lambda R: oracle.qmax_binary(R, gamma_o, gamma_e, dmax), Rs), np.float32)
+
+
+def describe(d, k, m):
+    """The label of pair k in failure messages: m, Mq, Mr, the class key and the band kernel families of its two passes."""
+    i, j = d["pairs"][k]
+    Mq, Mr = int(d["M"][i]), int(d["M"][j])
+    cr, cq = key(Mq, Mr)
+    return "m=%d pair %d (tracks %d, %d) Mq=%d Mr=%d (cr, cq)=(%d, %d) row pass %s, column pass %s" % (
+        m, k, i, j, Mq, Mr, cr, cq, family(m, cr), family(m, cq))
+
+
+def assert_plots_equal(d, m, got, want, tag=""):
+    """Bit for bit; the message names the pair, its kernels, the number of differing cells and the first of them."""
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g.shape == w.shape, "%s %s: shape %s vs %s" % (tag, describe(d, k, m), g.shape, w.shape)
+        if not np.array_equal(g, w):
+            bad = np.argwhere(g != w)
+            raise AssertionError("%s %s: recurrence plot differs in %d of %d cells, first at (row %d, column %d): device %d, oracle %d" % (
+                tag, describe(d, k, m), len(bad), g.size, bad[0][0], bad[0][1], g[tuple(bad[0])], w[tuple(bad[0])]))
+
+
+def assert_scores_equal(d, m, got, want, tag=""):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, (tag, got.shape, want.shape)
+    if not np.array_equal(got, want):
+        bad = np.nonzero((got != want).reshape(len(got), -1).any(axis=1))[0]
+        raise AssertionError("%s scores differ for %d of %d pairs, first: %s: device %s, oracle %s" % (
+            tag, len(bad), len(got), describe(d, int(bad[0]), m), got[bad[0]], want[bad[0]]))

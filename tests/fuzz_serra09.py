@@ -17,19 +17,24 @@ t_end = time.time() + budget
 rounds = pairs_done = fails = 0
 while time.time() < t_end:
     rounds += 1
-    m = int(rng.choice([1, 2, 4, 7, 9, 9, 9, 12, 16]))
+    m = int(rng.choice([9] * 8 + list(range(1, 17))))       # every compiled stack size; a third of the rounds the default
     kw = dict(m=m, kappa=float(rng.choice([0.0, 0.004, 0.02, 0.095, 0.095, 0.3, 0.7, 1.0])), pct_mode=int(rng.integers(0, 4)),
               inclusive=int(rng.integers(0, 2)), dp_start=int(rng.choice([2, 3])), embed_full=int(rng.integers(0, 2)),
               oti=bool(rng.integers(0, 2)), oti_target=int(rng.integers(0, 2)), dmax=int(rng.integers(0, 2)))
     if rng.random() < 0.3:
         kw.update(gamma_o=float(rng.choice([0.25, 1.0, 1.5])), gamma_e=float(rng.choice([0.25, 0.5, 2.0])))
     ntr = int(rng.integers(3, 7))
-    tmax = int(rng.choice([60, 150, 400, 700, 1100, 2040 - m]))
+    # (also the longest rows of the size classes of run_serra09_impl: 249 / 505 / 761 / 1017 cells)
+    tmax = int(rng.choice([60, 150, 400, 700, 1100, 2040 - m, 249, 505, 761, 1017 + m]))
+    on_edge = tmax in (249, 505, 761, 1017 + m)
     if tmax > 1500:
         ntr = 3
     tracks = []
-    for _ in range(ntr):
+    for t in range(ntr):
         T = int(rng.integers(m + 2, tmax + m + 2))
+        if on_edge and t < 2:                  # one track ON the edge and one just beyond it (tests/_serra09_shapes.py: cls)
+            e = tmax - m if tmax > 1017 else tmax
+            T = e + t + (m - 1 if kw["embed_full"] else m)
         kind = rng.random()
         if kind < 0.1:
             T = min(T, 2050 - 2 * m) if tmax > 1500 else T
