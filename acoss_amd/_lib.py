@@ -37,7 +37,7 @@ EXPORTS = [
     "acx_ftm2d_upload_shingles", "acx_ftm2d_download_shingles", "acx_ftm2d_debug_track", "acx_ftm2d_pairs",
     "acx_rank_columns", "acx_topk_rows",
     "acx_query_scores", "acx_query_topk", "acx_query_ranks",
-    "acx_serra09_debug_bits",
+    "acx_serra09_debug_bits", "acx_serra09_plan", "acx_serra09_family_name",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -87,6 +87,11 @@ class EfPrepParams(ctypes.Structure):
 class Ftm2dParams(ctypes.Structure):
     """acx_ftm2d_params (include/acx.h); defaults = FTM2D ctor, ftm2d.py:23."""
     _fields_ = [("pwr", ctypes.c_double), ("c", ctypes.c_double), ("win", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class Serra09PlanRec(ctypes.Structure):
+    """acx_serra09_plan_rec (include/acx.h)."""
+    _fields_ = [(name, ctypes.c_int32) for name in ("Mq", "Mr", "batch", "cr", "cq", "row_family", "col_family", "sweep_cols", "sweep_pack")]
 
 
 class Serra09Params(ctypes.Structure):
@@ -203,6 +208,9 @@ def load():
     L.acx_chenfusion_pairs.argtypes = [vp, ip, ctypes.c_int64, pp, fp]
     L.acx_serra09_debug_pair.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, pp, fp, fp, fp, fp, fp, ip, fp, ip]
     L.acx_serra09_debug_bits.argtypes = [vp, ip, ctypes.c_int64, pp, fp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int64)]
+    L.acx_serra09_plan.argtypes = [lp, ctypes.c_int32, ip, ctypes.c_int64, pp, ctypes.c_int64, ctypes.POINTER(Serra09PlanRec)]
+    L.acx_serra09_family_name.restype = ctypes.c_char_p
+    L.acx_serra09_family_name.argtypes = [ctypes.c_int32, ctypes.c_int32]
     L.acx_serra09_embed_len.restype = ctypes.c_int32
     L.acx_serra09_embed_len.argtypes = [ctypes.c_int32, pp]
     L.acx_profile_enable.argtypes = [vp, ctypes.c_int]
@@ -360,6 +368,32 @@ def grid_plan(lengths, algo, symmetric, world=1, tile=0, want_tiles=False):
             raise ValueError("acx_grid_plan: bad argument")
         out["tiles"] = tiles
     return out
+
+
+def serra09_plan(lengths, pairs, params=None, scratch_limit=0):
+    """acx_serra09_plan: what acx_serra09_pairs would do with the (K, 2) pair list on a pool of these pooled track lengths -- a pure
+    host function, no GPU needed.  Returns a (K,) structured array with the fields of acx_serra09_plan_rec (Mq, Mr, batch, cr, cq,
+    row_family, col_family, sweep_cols, sweep_pack).  A list the run would refuse raises AcxError with the run's code as `.code`."""
+    L = load()
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    params = params if params is not None else serra09_params()
+    out = np.zeros(len(pairs), dtype=np.dtype(Serra09PlanRec))
+    rc = L.acx_serra09_plan(_lptr(lengths), len(lengths), _iptr(pairs), len(pairs), ctypes.byref(params), int(scratch_limit),
+                            out.ctypes.data_as(ctypes.POINTER(Serra09PlanRec)))
+    if rc != ACX_OK:
+        err = AcxError("acx_serra09_plan: code %d: %s" % (rc, (L.acx_last_error(None) or b"bad argument").decode()))
+        err.code = rc
+        raise err
+    return out
+
+
+def serra09_family_name(family, m):
+    """Printable name of an ACX_SERRA09_FAMILY_* value for stack size m, as the library spells it."""
+    name = load().acx_serra09_family_name(int(family), int(m))
+    if name is None:
+        raise ValueError("unknown Serra09 kernel family %r" % (family,))
+    return name.decode()
 
 
 def grid_scatter(lengths, spec, gathered, rank_stride, planes, mirror, first=0, count=-1):

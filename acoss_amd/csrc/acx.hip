@@ -31,6 +31,7 @@
 #include "rank_kernels.hpp"
 #include "query_kernels.hpp"
 #include "grid.hpp"
+#include "serra09_plan.hpp"
 #include "device_buffer.hpp"
 
 using acx::PairDesc;
@@ -302,16 +303,6 @@ int scan_nonfinite(acx_ctx *c, const char *who, const char *what, T *d_x, int64_
     return ACX_OK;
 }
 
-// Number of embedded frames of a track of T pooled frames (oracle embed_len): the stack at base
-// frame i = 0, tau, 2 tau, ... holds frames i, i + tau, ..., i + (m - 1) tau.
-int embed_len(int T, const acx_serra09_params &p)
-{
-    int span = p.embed_full ? (p.m - 1) * p.tau : p.m * p.tau;
-    int L = T - span;
-    if (L <= 0) return 0;
-    return (L + p.tau - 1) / p.tau;
-}
-
 int check_params(acx_ctx *c, const acx_serra09_params &p)
 {
     if (p.m < 1 || p.m > acx::MAX_M_LONG) return fail(c, ACX_ERR_UNSUPPORTED, "serra09: m must be in 1..33 on the device");
@@ -332,13 +323,13 @@ int check_params(acx_ctx *c, const acx_serra09_params &p)
 constexpr int64_t POOL_SLACK = 96;      // frames (rotated pool) / floats (norm table) on either side
 
 // band_kernel is launched from its own translation unit (acx_band.hip)
-bool launch_band(acx_ctx *c, int m, const PairDesc *dpd, int B, int maxRows, int maxCols, const acx_serra09_params &p, int role, int write_d2,
+bool launch_band(acx_ctx *c, int m, const PairDesc *dpd, int B, int maxRows, int cls, const acx_serra09_params &p, int role, int write_d2,
                  int want_eps)
 {
     const float *operands = p.arith == ACX_ARITH_F16X2 ? reinterpret_cast<const float *>(c->d_fh + POOL_SLACK * acx::FH) : c->d_frot + POOL_SLACK * acx::FROT;
     acx::BandLaunch L{c->stream, operands, c->d_toff, c->d_normtab + POOL_SLACK, c->d_noff, c->d_scratch, c->d_thr,
                       c->d_bits, p.kappa, p.pct_mode, p.inclusive, p.oti_target};
-    return acx::launch_band_kernel(L, m, dpd, B, maxRows, maxCols, role, write_d2, want_eps, p.arith);
+    return acx::launch_band_kernel(L, m, dpd, B, maxRows, acx::serra09_band_family(cls, m, p.arith), role, write_d2, want_eps, p.arith);
 }
 
 template <int M>
@@ -613,34 +604,26 @@ void quiesce(acx_ctx *c)
 }
 
 // The WHOLE pair list is checked before the first launch: indices, tracks shorter than the stack, pairs that cannot fit the
-// scratch limit on their own.  (The batch loop below used to find these when it reached them -- with earlier batches in flight.)
-int validate_serra09_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p, bool dbg, int64_t limit_floats)
+// scratch limit on their own.  (The batch loop used to find these when it reached them -- with earlier batches in flight.)
+int validate_serra09_pairs(acx_ctx *c, const acx::Serra09Lengths &len, const int32_t *pairs, int64_t K, const acx_serra09_params &p, bool dbg,
+                           int64_t limit_floats)
 {
-    const bool band_ok = p.m <= acx::MAX_M;
-    for (int64_t k = 0; k < K; ++k) {
-        const int qi = pairs[2 * k], ri = pairs[2 * k + 1];
-        if (qi < 0 || ri < 0 || qi >= c->n_tracks || ri >= c->n_tracks)
-            return fail(c, ACX_ERR_INVALID, "serra09: track index out of range in pair " + std::to_string(k));
-        const int Mq = embed_len((int)(c->h_off[qi + 1] - c->h_off[qi]), p), Mr = embed_len((int)(c->h_off[ri + 1] - c->h_off[ri]), p);
-        if (Mq <= 0 || Mr <= 0)
-            return fail(c, ACX_ERR_SHORT, "serra09: track shorter than the delay-embedding stack (pair " + std::to_string(k) + ")");
-        const bool is_long = !band_ok || (std::max(Mq, Mr) + acx::BAND - 1 + 63) / 64 > 32;
-        const int64_t pitchD = round_up(Mr, 64), pitchT = round_up(Mq, 64), nw = (Mr + acx::BAND - 1 + 63) / 64;
-        const int64_t needD = (dbg || is_long) ? (int64_t)Mq * pitchD : 0;
-        const int64_t needL = is_long ? (int64_t)Mr * pitchT + 8 * (int64_t)Mq : 0;
-        if (needD + needL + 2 * (int64_t)Mq * nw > limit_floats)
-            return fail(c, ACX_ERR_NOMEM, "serra09: pair " + std::to_string(k) + " does not fit the scratch limit");
+    int64_t k = 0;
+    switch (acx::serra09_check_pairs(len, pairs, K, p, dbg, limit_floats, &k)) {
+    case ACX_ERR_INVALID: return fail(c, ACX_ERR_INVALID, "serra09: track index out of range in pair " + std::to_string(k));
+    case ACX_ERR_SHORT: return fail(c, ACX_ERR_SHORT, "serra09: track shorter than the delay-embedding stack (pair " + std::to_string(k) + ")");
+    case ACX_ERR_NOMEM: return fail(c, ACX_ERR_NOMEM, "serra09: pair " + std::to_string(k) + " does not fit the scratch limit");
     }
     return ACX_OK;
 }
 
 // One alignment sweep (Qmax, or Dmax) over the recurrence bitmaps of B pairs, one wave per pair: pair k's score goes to dst[k w].
 // cols: bitmap columns a lane owns -- 8 / 16 / 32 for rows of up to 505 / 1017 / 2041 cells, 0: the long kernel (any length; its strip
-// records live in `scratch`).  multi: 16 / 32 packs four / two pairs into a wave (rows of <= 249 / 505 cells, the default penalties
-// only); 0: one wave per pair.  The default penalties (0.5 / 0.5) take the packed 16-bit integer DP in half-units, two cells per
-// instruction.
+// records live in `scratch`).  pack: 4 / 2 pairs share a wave (rows of <= 249 / 505 cells, the default penalties only); 1: one wave
+// per pair.  Both come from the size class's row of serra09_plan.hpp (serra09_sweep).  The default penalties (0.5 / 0.5) take the
+// packed 16-bit integer DP in half-units, two cells per instruction.
 void launch_qmax_sweep(hipStream_t st, const PairDesc *pd, int B, const unsigned long long *bits, float *scratch, float *dst, int w,
-                       float gamma_o, float gamma_e, int dp_start, bool dmax, int cols, int multi)
+                       float gamma_o, float gamma_e, int dp_start, bool dmax, int cols, int pack)
 {
 #define ACX_QB3(E_, D_, C_) hipLaunchKernelGGL((acx::qmax_bits_kernel<E_, D_, C_>), dim3(B), dim3(64), 0, st, pd, bits, dst, w, gamma_o, gamma_e, dp_start)
 #define ACX_QBL(E_, D_) hipLaunchKernelGGL((acx::qmax_bits_long_kernel<E_, D_>), dim3(B), dim3(64), 0, st, pd, bits, scratch, dst, w, gamma_o, gamma_e, dp_start)
@@ -651,8 +634,8 @@ void launch_qmax_sweep(hipStream_t st, const PairDesc *pd, int B, const unsigned
                                           pd, B, bits, dst, w, dp_start)
     const bool eqg = gamma_o == gamma_e;
     if (eqg && gamma_o == 0.5f && cols != 0) {
-        if (multi == 16) { if (dmax) ACX_QM(16, true); else ACX_QM(16, false); }
-        else if (multi == 32) { if (dmax) ACX_QM(32, true); else ACX_QM(32, false); }
+        if (pack == 4) { if (dmax) ACX_QM(16, true); else ACX_QM(16, false); }
+        else if (pack == 2) { if (dmax) ACX_QM(32, true); else ACX_QM(32, false); }
         else if (dmax) { if (cols == 8) ACX_QH(8, true); else if (cols == 16) ACX_QH(16, true); else ACX_QH(32, true); }
         else { if (cols == 8) ACX_QH(8, false); else if (cols == 16) ACX_QH(16, false); else ACX_QH(32, false); }
     }
@@ -663,6 +646,27 @@ void launch_qmax_sweep(hipStream_t st, const PairDesc *pd, int B, const unsigned
 #undef ACX_QB
 #undef ACX_QBL
 #undef ACX_QB3
+}
+
+// The streaming class (a side beyond the last band class, or m > MAX_M) up to its recurrence bitmap, on the main stream: `B` pairs
+// whose descriptors are `dpd` on the device and `pd` on the host, spanning `e`.
+void launch_streaming_class(acx_ctx *c, const PairDesc *dpd, const PairDesc *pd, int B, const acx::Serra09Extent &e, const acx_serra09_params &p)
+{
+    {   // L1: D2 and D2^T
+        const int tiles_x = (e.Mr + acx::LT - 1) / acx::LT, tiles_y = (e.Mq + acx::LT - 1) / acx::LT;
+        ProfScope ps(c, KS_CSM, e.cells);
+        hipLaunchKernelGGL(acx::csm_long_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, c->stream,
+                           c->d_frames, c->d_toff, dpd, c->d_scratch, tiles_x, p.oti_target, p.m);
+    }
+    {   // L2: thresholds of every row and column;  L3: recurrence bitmap
+        int maxRows = 0;
+        for (int k2 = 0; k2 < B; ++k2) maxRows = std::max(maxRows, pd[k2].Mq + pd[k2].Mr);
+        ProfScope ps(c, KS_SEL, e.cells);
+        hipLaunchKernelGGL(acx::rowsel_long_kernel, dim3((maxRows + 3) / 4, B), dim3(256), 0, c->stream,
+                           dpd, c->d_scratch, c->d_thr, p.kappa, p.pct_mode, p.inclusive);
+        hipLaunchKernelGGL(acx::binarise_long_kernel, dim3((e.Mq + 3) / 4, B), dim3(256), 0, c->stream,
+                           dpd, c->d_scratch, c->d_thr, c->d_bits);
+    }
 }
 
 int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
@@ -688,10 +692,11 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
     if ((rc = ensure_tau(c, p_in.tau)) != ACX_OK) return rc;
     acx_serra09_params p = p_in;
     p.tau = 1;                                   // from here on: the decimated pool
+    const acx::Serra09Lengths len{c->h_off.data(), c->n_tracks, 1};
     const int64_t limit_floats = scratch_limit_bytes(c) / 4;
-    const bool band_ok = p.m <= acx::MAX_M;      // larger stacks: every pair takes the long-track kernels
+    constexpr int NC = acx::SERRA09_NC;          // band size classes; class NC: the streaming kernels
     const int w = both ? 2 : 1;
-    if ((rc = validate_serra09_pairs(c, pairs, K, p, dbg != nullptr, limit_floats)) != ACX_OK) return rc;
+    if ((rc = validate_serra09_pairs(c, len, pairs, K, p, dbg != nullptr, limit_floats)) != ACX_OK) return rc;
     for (int s = 0; s < 2; ++s) {
         if (!c->slot[s].done) ACX_HIP(c, hipEventCreateWithFlags(&c->slot[s].done, hipEventDisableTiming));
         // (a slot is never marked free without its work being waited for: a failed call drains the streams, quiesce())
@@ -702,92 +707,23 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
     for (int batch = 0; k0 < K; ++batch) {
         Serra09Slot &S = c->slot[batch & 1];
         if ((rc = collect_slot(c, S, out)) != ACX_OK) return rc;
+        // the plan of the batch (serra09_plan.hpp): its pairs and their arena offsets, then the sort by size-class key --
+        // `S.perm[k]` = position in the batch of sorted pair k
         std::vector<PairDesc> &pd = S.pd;
-        pd.clear();
-        int64_t used = 0, used_thr = 0, used_bits = 0;
-        int64_t k = k0;
-        for (; k < K && pd.size() < 65535; ++k) {
-            const int qi = pairs[2 * k], ri = pairs[2 * k + 1];
-            if (qi < 0 || ri < 0 || qi >= c->n_tracks || ri >= c->n_tracks)
-                return fail(c, ACX_ERR_INVALID, "serra09: track index out of range in pair " + std::to_string(k));
-            PairDesc d;
-            d.q = qi; d.r = ri;
-            d.Tq = (int)(c->h_off[qi + 1] - c->h_off[qi]);
-            d.Tr = (int)(c->h_off[ri + 1] - c->h_off[ri]);
-            d.Mq = embed_len(d.Tq, p);
-            d.Mr = embed_len(d.Tr, p);
-            if (d.Mq <= 0 || d.Mr <= 0)
-                return fail(c, ACX_ERR_SHORT, "serra09: track shorter than the delay-embedding stack (pair " + std::to_string(k) + ")");
-            d.oti = 0;
-            d.pitchD = round_up(d.Mr, 64);
-            d.pitchT = round_up(d.Mq, 64);
-            d.nw = (d.Mr + acx::BAND - 1 + 63) / 64;
-            d.pos_q = acx::pct_position(d.Mq, p.kappa, p.pct_mode);
-            d.pos_r = acx::pct_position(d.Mr, p.kappa, p.pct_mode);
-            const bool is_long = !band_ok || (std::max(d.Mq, d.Mr) + acx::BAND - 1 + 63) / 64 > 32;
-            const int64_t needD = (dbg != nullptr || is_long) ? (int64_t)d.Mq * d.pitchD : 0;     // the band pipeline keeps D2 out of HBM
-            const int64_t needL = is_long ? (int64_t)d.Mr * d.pitchT + 8 * (int64_t)d.Mq : 0;      // D2^T + the DP's strip records
-            const int64_t need_bits = (int64_t)d.Mq * d.nw;
-            if (needD + needL + 2 * need_bits > limit_floats)
-                return fail(c, ACX_ERR_NOMEM, "serra09: pair " + std::to_string(k) + " does not fit the scratch limit");
-            if (used + needD + needL + 2 * (used_bits + need_bits) > limit_floats) break;
-            d.offD = used;
-            d.offL = used + needD;
-            d.offT = used_bits;
-            d.offX = used_thr;
-            used += needD + needL;
-            used_bits += need_bits;
-            used_thr += 3 * ((int64_t)d.pitchD + d.pitchT);
-            pd.push_back(d);
-        }
+        acx::Serra09Arena used;
+        const int64_t k = acx::serra09_pack_batch(len, pairs, k0, K, p, dbg != nullptr, limit_floats, pd, used);
+        if (k == k0) return fail(c, ACX_ERR_STATE, "serra09: the batch plan made no progress at pair " + std::to_string(k0));
         const int B = (int)pd.size();
-        // Pairs are processed in size classes PER PASS: a pass whose rows hold <= 249 / 505 / 761 / 1017 / 2041 cells runs the band
-        // kernel that fits (band2_kernel with four rows per wave, two rows per wave at 16 / 24 positions per lane, band_kernel with
-        // 16 / 32 values per lane).  The row pass (and the alignment sweep behind it) has rows of Mr cells, the column pass rows of Mq cells, so a
-        // pair carries two classes (cr, cq) and the batch is sorted by the key NC cr + cq: the row pass and the sweep take the NC
-        // keys of one cr in ONE launch, the column pass one launch per key -- a short track paired with a long one does not drag
-        // BOTH passes through the wider kernel.  Key NC * NC: a side beyond 2041 cells (or m > 16), the streaming kernels.
-        // `perm[k]` = position in the batch of sorted pair k.
-        constexpr int NC = 5;
-        std::vector<int> &perm = S.perm;
-        perm.resize(B);
-        int key_begin[NC * NC + 2];
-        {
-            auto cls1 = [&](int M) {
-                const int nd = (M + acx::BAND - 1 + 63) / 64;
-                return nd <= 4 ? 0 : (nd <= 8 ? 1 : (nd <= 12 ? 2 : (nd <= 16 ? 3 : (nd <= 32 ? 4 : 5))));
-            };
-            auto key_of = [&](const PairDesc &d) {
-                const int cr = cls1(d.Mr), cq = cls1(d.Mq);
-                return (!band_ok || cr == NC || cq == NC) ? NC * NC : NC * cr + cq;
-            };
-            int cnt[NC * NC + 1];
-            for (int kk = 0; kk <= NC * NC; ++kk) cnt[kk] = 0;
-            for (const PairDesc &d : pd) cnt[key_of(d)]++;
-            key_begin[0] = 0;
-            for (int kk = 0; kk <= NC * NC; ++kk) key_begin[kk + 1] = key_begin[kk] + cnt[kk];
-            int fill[NC * NC + 1];
-            for (int kk = 0; kk <= NC * NC; ++kk) fill[kk] = key_begin[kk];
-            std::vector<PairDesc> &sorted = S.sorted;
-            sorted.resize(B);
-            for (int k2 = 0; k2 < B; ++k2) {
-                const int kk = key_of(pd[k2]);
-                perm[fill[kk]] = k2;
-                sorted[fill[kk]++] = pd[k2];
-            }
-            pd.swap(sorted);
-        }
-        // row-pass classes (keys NC cr .. NC cr + NC - 1) + the long class, as [begin, end) ranges
-        int cls_begin[NC + 2];
-        for (int cl = 0; cl <= NC; ++cl) cls_begin[cl] = key_begin[NC * cl];
-        cls_begin[NC + 1] = B;
+        const acx::Serra09Sort srt = acx::serra09_sort_batch(pd, S.sorted, S.perm, p.m);
+        const int *key_begin = srt.key_begin, *cls_begin = srt.cls_begin;
+        const std::vector<int> &perm = S.perm;
         if (cls_begin[NC] > 0 && (rc = ensure_normtab(c, p)) != ACX_OK) return rc;
         if (cls_begin[NC] > 0 && p.arith == ACX_ARITH_F16X2 && (rc = ensure_f16pool(c)) != ACX_OK) return rc;
         // (the band kernel reads its column thresholds 16 bytes at a time without a bounds check, up to
         // 64 x 32 floats behind a pair's column-threshold row: the arena carries that much slack)
-        if ((rc = ensure(c, c->d_scratch, (size_t)std::max<int64_t>(used, 1))) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_bits, (size_t)std::max<int64_t>(used_bits, 1))) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_thr, (size_t)used_thr + 64 * 32 + 16)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_scratch, (size_t)std::max<int64_t>(used.scratch, 1))) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_bits, (size_t)std::max<int64_t>(used.bits, 1))) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_thr, (size_t)used.thr + 64 * 32 + 16)) != ACX_OK) return rc;
         if ((rc = ensure(c, S.d_pd, (size_t)B)) != ACX_OK) return rc;
         if ((rc = ensure(c, S.d_out, (size_t)2 * B)) != ACX_OK) return rc;
         if ((rc = ensure(c, S.h_out, (size_t)2 * B)) != ACX_OK) return rc;
@@ -805,8 +741,8 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         // and of the NEXT batch, whose row pass -- the writer of the shared bitmap arena -- waits for this batch's sweeps (S.done).
         // Not for batches with long pairs (their sweep's strip records live in the shared scratch), the debug entry point, or while
         // the per-kernel event clocks are on (acx_profile_enable: a kernel's time is then its time ALONE, not beside another launch).
-        static const bool q_overlap = [] { const char *e = getenv("ACX_QMAX_STREAM"); return !(e && e[0] == '0'); }();
-        const bool use_q = q_overlap && !dbg && !c->prof && cls_begin[NC + 1] == cls_begin[NC];
+        // (ACX_QMAX_STREAM=0 keeps them on the main stream.)
+        const bool use_q = acx::serra09_switches().qstream && !dbg && !c->prof && cls_begin[NC + 1] == cls_begin[NC];
         if (use_q && !c->qstream) ACX_HIP(c, hipStreamCreateWithFlags(&c->qstream, hipStreamNonBlocking));
         if (use_q && both && !c->qstream2) {
             ACX_HIP(c, hipStreamCreateWithFlags(&c->qstream2, hipStreamNonBlocking));
@@ -819,10 +755,8 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         Serra09Slot &Sprev = c->slot[(batch & 1) ^ 1];
         bool bits_free = !(Sprev.busy && Sprev.on_q);     // false: the previous batch's sweeps may still be reading the bitmap arena
 
-        int64_t cells = 0;
-        for (const PairDesc &d : pd) cells += (int64_t)d.Mq * d.Mr;
         {   // K0
-            ProfScope ps(c, KS_OTI, cells);
+            ProfScope ps(c, KS_OTI, acx::serra09_extent(pd, 0, B).cells);
             hipLaunchKernelGGL(acx::oti_kernel, dim3((B + 255) / 256), dim3(256), 0, c->stream,
                                S.d_pd, B, c->d_gch, p.oti, p.oti_target, c->d_toff, c->d_noff);
         }
@@ -831,57 +765,34 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
             cls_cells[cl] = 0;
             const int b0 = cls_begin[cl], Bc = cls_begin[cl + 1] - b0;
             if (Bc <= 0) continue;
-            int cMq = 0, cMr = 0;
-            int64_t ccells = 0;
-            for (int k2 = b0; k2 < b0 + Bc; ++k2) {
-                cMq = std::max(cMq, pd[k2].Mq); cMr = std::max(cMr, pd[k2].Mr);
-                ccells += (int64_t)pd[k2].Mq * pd[k2].Mr;
-            }
-            cls_cells[cl] = ccells;
+            const acx::Serra09Extent ce = acx::serra09_extent(pd, b0, b0 + Bc);
+            cls_cells[cl] = ce.cells;
             if (cl < NC) {
                 bool ok = true;
                 // K1' role 1: rows = reference frames (Mq cells each) -> column thresholds; one launch per (cr, cq) key
                 for (int cq = 0; cq < NC; ++cq) {
                     const int q0 = key_begin[NC * cl + cq], Bq = key_begin[NC * cl + cq + 1] - q0;
                     if (Bq <= 0) continue;
-                    int qMq = 0, qMr = 0;
-                    int64_t qcells = 0;
-                    for (int k2 = q0; k2 < q0 + Bq; ++k2) {
-                        qMq = std::max(qMq, pd[k2].Mq); qMr = std::max(qMr, pd[k2].Mr);
-                        qcells += (int64_t)pd[k2].Mq * pd[k2].Mr;
-                    }
-                    ProfScope ps(c, KS_BAND, qcells);
-                    ok = ok && launch_band(c, p.m, S.d_pd + q0, Bq, qMr, qMq, p, 1, 0, dbg ? 1 : 0);
+                    const acx::Serra09Extent qe = acx::serra09_extent(pd, q0, q0 + Bq);
+                    ProfScope ps(c, KS_BAND, qe.cells);
+                    ok = ok && launch_band(c, p.m, S.d_pd + q0, Bq, qe.Mr, cq, p, 1, 0, dbg ? 1 : 0);
                 }
                 if (!bits_free) { ACX_HIP(c, hipStreamWaitEvent(c->stream, Sprev.done, 0)); bits_free = true; }
                 {   // K1' role 0: rows = query frames (Mr cells each) -> row thresholds + recurrence bitmap (needs role 1)
-                    ProfScope ps(c, KS_BAND, ccells);
-                    ok = ok && launch_band(c, p.m, S.d_pd + b0, Bc, cMq, cMr, p, 0, dbg ? 1 : 0, dbg ? 1 : 0);
+                    ProfScope ps(c, KS_BAND, ce.cells);
+                    ok = ok && launch_band(c, p.m, S.d_pd + b0, Bc, ce.Mq, cl, p, 0, dbg ? 1 : 0, dbg ? 1 : 0);
                 }
                 if (use_q) ACX_HIP(c, hipEventRecord(S.cls_ev[cl], c->stream));
                 if (!ok) return fail(c, ACX_ERR_UNSUPPORTED, "serra09: this build of libacx has no band kernel for the requested m");
             } else {
                 if (!bits_free) { ACX_HIP(c, hipStreamWaitEvent(c->stream, Sprev.done, 0)); bits_free = true; }
-                {   // L1: D2 and D2^T
-                    const int tiles_x = (cMr + acx::LT - 1) / acx::LT, tiles_y = (cMq + acx::LT - 1) / acx::LT;
-                    ProfScope ps(c, KS_CSM, ccells);
-                    hipLaunchKernelGGL(acx::csm_long_kernel, dim3(tiles_x * tiles_y, Bc), dim3(256), 0, c->stream,
-                                       c->d_frames, c->d_toff, S.d_pd + b0, c->d_scratch, tiles_x, p.oti_target, p.m);
-                }
-                {   // L2: thresholds of every row and column;  L3: recurrence bitmap
-                    int maxRows = 0;
-                    for (int k2 = b0; k2 < b0 + Bc; ++k2) maxRows = std::max(maxRows, pd[k2].Mq + pd[k2].Mr);
-                    ProfScope ps(c, KS_SEL, ccells);
-                    hipLaunchKernelGGL(acx::rowsel_long_kernel, dim3((maxRows + 3) / 4, Bc), dim3(256), 0, c->stream,
-                                       S.d_pd + b0, c->d_scratch, c->d_thr, p.kappa, p.pct_mode, p.inclusive);
-                    hipLaunchKernelGGL(acx::binarise_long_kernel, dim3((cMq + 3) / 4, Bc), dim3(256), 0, c->stream,
-                                       S.d_pd + b0, c->d_scratch, c->d_thr, c->d_bits);
-                }
+                launch_streaming_class(c, S.d_pd + b0, &pd[b0], Bc, ce, p);
             }
         }
         {   // K3: one sweep per requested alignment over the SAME recurrence bitmap:
             // both == 0: Qmax or Dmax as p.dmax says; both == 1: out[2k] = Qmax, out[2k+1] = Dmax
-            // one launch per size class: a lane owns 8 / 8 / 16 / 16 / 32 columns of rows up to 249 / 505 / 761 / 1017 / 2041 cells
+            // one launch per size class, with the columns per lane and the pairs per wave of that class's row of the plan's table
+            // (the default penalties' packed kernels take the two narrow classes four / two pairs per wave; ACX_QMAX_MULTI=0: one)
             hipError_t wait_err = hipSuccess;            // (a failed cross-stream wait would let a sweep read an unfinished bitmap: reported, not ignored)
             auto sweep = [&](bool dmax, float *dst, hipStream_t qs) {
                 for (int cl = 0; cl <= NC; ++cl) {
@@ -889,11 +800,9 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
                     if (Bc <= 0) continue;
                     if (use_q) { const hipError_t e_ = hipStreamWaitEvent(qs, S.cls_ev[cl], 0); if (e_ != hipSuccess) wait_err = e_; }
                     ProfScope ps(c, KS_QMAX, cls_cells[cl], qs);      // (its first event stands behind the wait)
-                    // the default penalties' packed kernels take rows of <= 249 / 505 cells four / two pairs per wave (ACX_QMAX_MULTI=0: one wave per pair)
-                    static const bool multi = [] { const char *e = getenv("ACX_QMAX_MULTI"); return !(e && e[0] == '0'); }();
-                    const int cols = cl <= 1 ? 8 : (cl <= 3 ? 16 : (cl == 4 ? 32 : 0));
+                    const acx::Serra09Sweep sw = acx::serra09_sweep(cl);
                     launch_qmax_sweep(qs, S.d_pd + b0, Bc, c->d_bits, c->d_scratch, dst + (size_t)b0 * w, w, p.gamma_o, p.gamma_e, p.dp_start, dmax,
-                                      cols, multi && cl == 0 ? 16 : (multi && cl == 1 ? 32 : 0));
+                                      sw.cols, sw.pack);
                 }
             };
             if (both && use_q) {      // the two alignments of a pair read the same bitmap and write different halves of d_out: side by side
@@ -1846,7 +1755,7 @@ void acx_serra09_default_params(acx_serra09_params *p)
 int32_t acx_serra09_embed_len(int32_t T, const acx_serra09_params *p)
 {
     if (!p || p->m < 1 || p->tau < 1) return 0;
-    return embed_len(T, *p);
+    return acx::serra09_embed_len(T, p->m, p->tau, p->embed_full);
 }
 
 int acx_serra09_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, float *out)
@@ -1879,31 +1788,18 @@ int acx_serra09_debug_pair(acx_ctx *c, int32_t i, int32_t j, const acx_serra09_p
     return rc;
 }
 
-// Would run_serra09 take the whole list in ONE batch?  The same arithmetic as its batch loop, for the product path (no D2 in the
-// scratch but for streaming-class pairs).  A pair the loop would refuse (index, length, scratch limit) answers true: the run itself
-// reports it, before its first launch.
-static bool serra09_one_batch(const acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in)
+// Would run_serra09 take the whole list in ONE batch?  The plan's own packing from pair 0, for the product path (no D2 in the
+// scratch but for streaming-class pairs), on the uploaded pool's lengths (ensure_tau has not run yet).  A list the run would refuse
+// (index, length, scratch limit) answers true: the run itself reports it, before its first launch.
+static bool serra09_one_batch(const acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p)
 {
-    if (K > 65535) return false;
-    acx_serra09_params p = p_in;
-    p.tau = 1;
+    const acx::Serra09Lengths len{c->h_off0.data(), c->n_tracks, p.tau};
     const int64_t limit_floats = scratch_limit_bytes(c) / 4;
-    int64_t used = 0, used_bits = 0;
-    for (int64_t k = 0; k < K; ++k) {
-        const int qi = pairs[2 * k], ri = pairs[2 * k + 1];
-        if (qi < 0 || ri < 0 || qi >= c->n_tracks || ri >= c->n_tracks) return true;
-        const int64_t Tq = c->h_off0[qi + 1] - c->h_off0[qi], Tr = c->h_off0[ri + 1] - c->h_off0[ri];
-        const int Mq = embed_len((int)((Tq + p_in.tau - 1) / p_in.tau), p), Mr = embed_len((int)((Tr + p_in.tau - 1) / p_in.tau), p);
-        if (Mq <= 0 || Mr <= 0) return true;
-        const bool is_long = p.m > acx::MAX_M || (std::max(Mq, Mr) + acx::BAND - 1 + 63) / 64 > 32;
-        const int64_t nw = (Mr + acx::BAND - 1 + 63) / 64;
-        const int64_t need = is_long ? (int64_t)Mq * round_up(Mr, 64) + (int64_t)Mr * round_up(Mq, 64) + 8 * (int64_t)Mq : 0;
-        if (need + 2 * (int64_t)Mq * nw > limit_floats) return true;
-        used += need;
-        used_bits += (int64_t)Mq * nw;
-        if (used + 2 * used_bits > limit_floats) return false;
-    }
-    return true;
+    int64_t bad = 0;
+    if (acx::serra09_check_pairs(len, pairs, K, p, false, limit_floats, &bad) != ACX_OK) return true;
+    std::vector<PairDesc> pd;
+    acx::Serra09Arena used;
+    return acx::serra09_pack_batch(len, pairs, 0, K, p, false, limit_floats, pd, used) == K;
 }
 
 int acx_serra09_debug_bits(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, float *scores,
@@ -1970,7 +1866,7 @@ int acx_qmax_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const ac
     memset(&d, 0, sizeof(d));
     d.Mq = M; d.Mr = N; d.Tq = M; d.Tr = N;
     d.pitchD = round_up(N, 64); d.pitchT = 0;
-    d.nw = (N + acx::BAND - 1 + 63) / 64;
+    d.nw = acx::serra09_tiles(N);
     std::vector<unsigned long long> words((size_t)M * d.nw, 0ull);
     for (int i = 0; i < M; ++i) {
         const int c0 = (i & (acx::BAND - 1)) - (acx::BAND - 1);
@@ -1988,9 +1884,9 @@ int acx_qmax_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const ac
     if ((rc = ensure(c, S.d_out, (size_t)2)) != ACX_OK) return rc;
     ACX_HIP(c, hipMemcpyAsync(c->d_bits, words.data(), sizeof(unsigned long long) * words.size(), hipMemcpyHostToDevice, c->stream));
     ACX_HIP(c, hipMemcpyAsync(S.d_pd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
-    const int nd = (std::max(M, N) + acx::BAND - 1 + 63) / 64;
+    // (one pair of any shape: the class of its longer side, never packed)
     launch_qmax_sweep(c->stream, S.d_pd, 1, c->d_bits, c->d_scratch, S.d_out, 1, params->gamma_o, params->gamma_e, params->dp_start,
-                      params->dmax != 0, nd <= 8 ? 8 : (nd <= 16 ? 16 : (nd <= 32 ? 32 : 0)), 0);
+                      params->dmax != 0, acx::serra09_sweep(acx::serra09_row_class(std::max(M, N))).cols, 1);
     ACX_HIP(c, hipGetLastError());
     ACX_HIP(c, hipMemcpyAsync(score, S.d_out, sizeof(float), hipMemcpyDeviceToHost, c->stream));
     ACX_HIP(c, hipStreamSynchronize(c->stream));
@@ -3283,6 +3179,49 @@ int acx_grid_plan(const int64_t *lengths, int32_t n_tracks, const acx_grid_spec 
     }
     return ACX_OK;
 }
+
+// The Serra09 batch plan of a pair list without a device: run_serra09_impl's own checks, packing, sort and kernel choice
+// (serra09_plan.hpp), one record per pair.  Messages of a refused list: acx_last_error(NULL).
+int acx_serra09_plan(const int64_t *lengths, int32_t n_tracks, const int32_t *pairs, int64_t K, const acx_serra09_params *params,
+                     int64_t scratch_limit, acx_serra09_plan_rec *out)
+{
+    if (!lengths || n_tracks < 1 || K < 0 || (K > 0 && (!pairs || !out)) || !params) return ACX_ERR_INVALID;
+    int rc = check_params(nullptr, *params);
+    if (rc != ACX_OK) return rc;
+    std::vector<int64_t> off((size_t)n_tracks + 1, 0);
+    for (int t = 0; t < n_tracks; ++t) off[t + 1] = off[t] + std::max<int64_t>(lengths[t], 0);
+    const acx::Serra09Lengths len{off.data(), n_tracks, params->tau};
+    const char *env = getenv("ACX_SCRATCH_GB");
+    const int64_t limit_floats = scratch_limit > 0 ? scratch_limit / 4
+                                 : (env && atof(env) > 0 ? (int64_t)(atof(env) * (double)(1ull << 30)) / 4 : INT64_MAX / 4);
+    if ((rc = validate_serra09_pairs(nullptr, len, pairs, K, *params, false, limit_floats)) != ACX_OK) return rc;
+    std::vector<PairDesc> pd, tmp;
+    std::vector<int> perm;
+    int64_t k0 = 0;
+    for (int batch = 0; k0 < K; ++batch) {
+        acx::Serra09Arena used;
+        const int64_t k = acx::serra09_pack_batch(len, pairs, k0, K, *params, false, limit_floats, pd, used);
+        if (k == k0) return ACX_ERR_STATE;
+        const acx::Serra09Sort srt = acx::serra09_sort_batch(pd, tmp, perm, params->m);
+        for (int cl = 0; cl <= acx::SERRA09_NC; ++cl) {
+            const acx::Serra09Sweep sw = acx::serra09_sweep(cl);
+            for (int k2 = srt.cls_begin[cl]; k2 < srt.cls_begin[cl + 1]; ++k2) {
+                acx_serra09_plan_rec &r = out[k0 + perm[k2]];
+                const bool band = cl < acx::SERRA09_NC;
+                r.Mq = pd[k2].Mq; r.Mr = pd[k2].Mr;
+                r.batch = batch;
+                r.cr = cl; r.cq = band ? acx::serra09_row_class(pd[k2].Mq) : acx::SERRA09_NC;
+                r.row_family = band ? acx::serra09_band_family(r.cr, params->m, params->arith) : ACX_SERRA09_FAMILY_STREAMING;
+                r.col_family = band ? acx::serra09_band_family(r.cq, params->m, params->arith) : ACX_SERRA09_FAMILY_STREAMING;
+                r.sweep_cols = sw.cols; r.sweep_pack = sw.pack;
+            }
+        }
+        k0 = k;
+    }
+    return ACX_OK;
+}
+
+const char *acx_serra09_family_name(int32_t family, int32_t m) { return acx::serra09_family_name(family, m); }
 
 int acx_pool_lengths(acx_ctx *c, int32_t algo, int64_t *lengths, int32_t capacity, int32_t *n_tracks)
 {

@@ -1,68 +1,60 @@
-// libacx: launcher of the Serra09 band kernel (serra09_kernels.hpp, K1').  A translation unit of its
-// own: the Makefile compiles it with -mllvm -amdgpu-sched-strategy=max-ilp, which gives this kernel
+// libacx: launcher of the Serra09 band kernels (serra09_kernels.hpp, serra09_band2_kernels.hpp, K1').  A translation unit of
+// its own: the Makefile compiles it with -mllvm -amdgpu-sched-strategy=max-ilp, which gives these kernels
 // +1 % and would cost simple_kernel 26 % and ef_rowstat_kernel 20 %.
+// WHICH kernel a pass runs is not decided here: serra09_plan.hpp holds the size classes, the kernel per class and the
+// ACX_BAND2 switch; the launcher receives the family and maps it onto the instantiations.
 #include <hip/hip_runtime.h>
-
-#include <cstdlib>
 
 #include "serra09_kernels.hpp"
 #include "serra09_band2_kernels.hpp"
+#include "serra09_plan.hpp"
 
 namespace acx {
 
 namespace {
 
+// `family`: the plan's answer for the pass's size class (serra09_band_family, serra09_plan.hpp -- the class limits, the choice
+// per stack size and arithmetic, and ACX_BAND2 live there); this switch only maps it onto the instantiations.
 template <int M>
-bool launch_band_m(const BandLaunch &L, const PairDesc *dpd, int B, int maxRows, int maxCols, int role, int write_d2, int want_eps, int arith)
+bool launch_band_m(const BandLaunch &L, const PairDesc *dpd, int B, int maxRows, int family, int role, int write_d2, int want_eps, int arith)
 {
     const dim3 grid((maxRows + BAND - 1) / BAND, B, 1);
-    const int ndata = (maxCols + BAND - 1 + 63) / 64;      // tiles per band that hold matrix cells
 #define ACX_BAND_K(V4_, R_, W_, A_) hipLaunchKernelGGL((band_kernel<M, V4_, R_, W_, A_>), grid, dim3(BAND_THREADS), 0, L.stream, \
                                                   L.frot, L.toff, L.normtab, L.noff, dpd, L.scratch, L.thr, L.bits, L.kappa, \
                                                   L.pct_mode, L.inclusive, L.oti_target, want_eps)
     // (the variant that also writes D2 exists for the row pass only: the debug entry point)
-#define ACX_BAND(V4_, A_) do { if (role) ACX_BAND_K(V4_, 1, false, A_); else if (write_d2) ACX_BAND_K(V4_, 0, true, A_); else ACX_BAND_K(V4_, 0, false, A_); } while (0)
-    if (arith == 0) {
-        // rows of <= 505 cells, m <= 9: the two-rows-per-wave kernel (serra09_band2_kernels.hpp); ACX_BAND2=0 keeps band_kernel<M, 2>
-        if constexpr (M <= 9) {
-            static const bool two_rows = [] { const char *e = getenv("ACX_BAND2"); return !(e && e[0] == '0'); }();
-            // (a second class of it, 24 positions per lane: rows of <= 761 cells -- ACX_BAND2=1 keeps that one on band_kernel<M, 4>)
-            static const bool mid_two_rows = [] { const char *e = getenv("ACX_BAND2"); return !(e && (e[0] == '0' || e[0] == '1')); }();
+#define ACX_BAND_A(V4_, A_) do { if (role) ACX_BAND_K(V4_, 1, false, A_); else if (write_d2) ACX_BAND_K(V4_, 0, true, A_); else ACX_BAND_K(V4_, 0, false, A_); } while (0)
+    // the opt-in f16x2 Gram: the default stack size only
+#define ACX_BAND(V4_) do { if (arith == ACX_ARITH_EXACT) ACX_BAND_A(V4_, 0); else if constexpr (M == 9) ACX_BAND_A(V4_, 1); else return false; return true; } while (0)
+    // the kernels of two and four rows per wave (serra09_band2_kernels.hpp): m <= 9, the exact arithmetic
 #define ACX_BAND2_K(R_, W_, NV_, GL_) hipLaunchKernelGGL((band2_kernel<M, R_, W_, NV_, GL_>), grid, dim3(64 * B2Geom<NV_, GL_>::WAVES), 0, L.stream, L.frot, L.normtab, \
                                                          dpd, L.scratch, L.thr, L.bits, L.pct_mode, L.inclusive, L.oti_target, want_eps)
-#define ACX_BAND2(NV_, GL_) do { if (role) ACX_BAND2_K(1, false, NV_, GL_); else if (write_d2) ACX_BAND2_K(0, true, NV_, GL_); else ACX_BAND2_K(0, false, NV_, GL_); } while (0)
-            // (rows of <= 249 cells: FOUR rows per wave -- ACX_BAND2=2 keeps them on the two-row kernel)
-            static const bool four_rows = [] { const char *e = getenv("ACX_BAND2"); return !(e && (e[0] == '0' || e[0] == '1' || e[0] == '2')); }();
-            if (ndata <= 4 && two_rows && four_rows) { ACX_BAND2(B2_NV, 16); return true; }
-            if (ndata <= 8 && two_rows) { ACX_BAND2(B2_NV, 32); return true; }
-            if (ndata > 8 && ndata <= 12 && two_rows && mid_two_rows) { ACX_BAND2(B2_NV_MID, 32); return true; }
-#undef ACX_BAND2
-#undef ACX_BAND2_K
-        }
-        if (ndata <= 8) ACX_BAND(2, 0);
-        else if (ndata <= 16) ACX_BAND(4, 0);
-        else ACX_BAND(8, 0);
-        return true;
-    }
-    // the opt-in f16x2 Gram: the default stack size only
-    if constexpr (M == 9) {
-        if (arith != 1) return false;
-        if (ndata <= 8) ACX_BAND(2, 1);
-        else if (ndata <= 16) ACX_BAND(4, 1);
-        else ACX_BAND(8, 1);
-        return true;
+#define ACX_BAND2(NV_, GL_) do { if constexpr (M <= 9) { if (arith != ACX_ARITH_EXACT) return false; \
+                                     if (role) ACX_BAND2_K(1, false, NV_, GL_); else if (write_d2) ACX_BAND2_K(0, true, NV_, GL_); else ACX_BAND2_K(0, false, NV_, GL_); \
+                                     return true; } return false; } while (0)
+    if (arith != ACX_ARITH_EXACT && arith != ACX_ARITH_F16X2) return false;
+    switch (family) {
+    case ACX_SERRA09_FAMILY_BAND2_4ROWS: ACX_BAND2(B2_NV, 16);
+    case ACX_SERRA09_FAMILY_BAND2_2ROWS: ACX_BAND2(B2_NV, 32);
+    case ACX_SERRA09_FAMILY_BAND2_MID: ACX_BAND2(B2_NV_MID, 32);
+    case ACX_SERRA09_FAMILY_BAND_2: ACX_BAND(2);
+    case ACX_SERRA09_FAMILY_BAND_4: ACX_BAND(4);
+    case ACX_SERRA09_FAMILY_BAND_8: ACX_BAND(8);
     }
     return false;
-#undef ACX_BAND_K
+#undef ACX_BAND2
+#undef ACX_BAND2_K
 #undef ACX_BAND
+#undef ACX_BAND_A
+#undef ACX_BAND_K
 }
 
 }  // namespace
 
-bool launch_band_kernel(const BandLaunch &L, int m, const PairDesc *dpd, int B, int maxRows, int maxCols, int role, int write_d2, int want_eps, int arith)
+bool launch_band_kernel(const BandLaunch &L, int m, const PairDesc *dpd, int B, int maxRows, int family, int role, int write_d2, int want_eps, int arith)
 {
     switch (m) {
-#define ACX_CASE(M_) case M_: return launch_band_m<M_>(L, dpd, B, maxRows, maxCols, role, write_d2, want_eps, arith);
+#define ACX_CASE(M_) case M_: return launch_band_m<M_>(L, dpd, B, maxRows, family, role, write_d2, want_eps, arith);
 #ifdef ACX_FAST_BUILD   /* development builds: only the default stack size */
 #ifndef ACX_FAST_BUILD_M
 #define ACX_FAST_BUILD_M 9

@@ -991,10 +991,11 @@ struct BandLaunch {
     float kappa;
     int pct_mode, inclusive, oti_target;
 };
-// role 1 / 0 over B pairs of one size class; false when the stack size m has no instantiation
+// role 1 / 0 over B pairs of one size class; false when the stack size m has no instantiation of `family`
+// (family: ACX_SERRA09_FAMILY_* as serra09_band_family (serra09_plan.hpp) chose it for the pass's class, m and arith)
 // (want_eps: also evaluate and store every row's eps -- the debug entry point; the production passes skip it where they can)
 // (arith: 0 = the exact f32 Gram, 1 = the opt-in f16x2 Gram, m = 9 only; L.frot then points at the f16 operand pool)
-bool launch_band_kernel(const BandLaunch &L, int m, const struct PairDesc *dpd, int B, int maxRows, int maxCols, int role,
+bool launch_band_kernel(const BandLaunch &L, int m, const struct PairDesc *dpd, int B, int maxRows, int family, int role,
                         int write_d2, int want_eps, int arith);
 
 // development builds only (scripts/ab_build.sh ablN -DACX_ABL=N): the band kernel stops behind stage N -- 1 sweep, 2 exchange +

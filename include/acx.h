@@ -222,6 +222,46 @@ int acx_qmax_binary(acx_ctx *ctx, const uint8_t *R, int32_t M, int32_t N, const 
 /* Number of embedded frames for a pooled length T (0 if too short). */
 int32_t acx_serra09_embed_len(int32_t T, const acx_serra09_params *params);
 
+/*
+ * The batch plan of a pair list, for tests and tools -- no context, no device: what acx_serra09_pairs /
+ * acx_chenfusion_pairs would do with the list on a pool of these track lengths, told by the functions the run itself
+ * calls (acoss_amd/csrc/serra09_plan.hpp; the per-process switches ACX_BAND2 / ACX_QMAX_MULTI / ACX_QMAX_STREAM apply).
+ *   lengths       pooled frames per track, as uploaded (n_tracks of them); params->tau decimates them as the run does
+ *   scratch_limit bytes, as acx_set_scratch_limit; 0: the default without a device -- env ACX_SCRATCH_GB, else unbounded
+ *                 (a context's default is 40 % of ITS device's memory)
+ *   out           K records, in the order of `pairs`:
+ *     Mq, Mr                 embedded lengths (rows, columns of the pair's matrix)
+ *     batch                  the batch the pair runs in (batches are contiguous runs of the list)
+ *     cr, cq                 size classes 0..4 of its rows (Mr cells: row pass and sweep) and columns (Mq cells: column
+ *                            pass); 5: the streaming kernels (then both are 5)
+ *     row_family, col_family ACX_SERRA09_FAMILY_* of the band kernel of its row pass / column pass
+ *     sweep_cols, sweep_pack the alignment sweep: bitmap columns a lane owns (0: the streaming sweep) and pairs per wave
+ *                            (what the default penalties 0.5 / 0.5 run; other penalties take one wave per pair)
+ * A list the run would refuse returns the run's code for it (ACX_ERR_INVALID: an index, ACX_ERR_SHORT: a track shorter
+ * than the stack, ACX_ERR_NOMEM: a pair beyond the scratch limit, ACX_ERR_UNSUPPORTED: the parameters) and fills nothing.
+ */
+enum {
+    ACX_SERRA09_FAMILY_BAND2_4ROWS = 0,   /* band2_kernel<M, B2_NV, 16>: four rows per wave, rows of <= 249 cells, m <= 9   */
+    ACX_SERRA09_FAMILY_BAND2_2ROWS = 1,   /* band2_kernel<M, B2_NV, 32>: two rows per wave, <= 505 cells, m <= 9            */
+    ACX_SERRA09_FAMILY_BAND2_MID = 2,     /* band2_kernel<M, B2_NV_MID, 32>: 24 positions per lane, <= 761 cells, m <= 9    */
+    ACX_SERRA09_FAMILY_BAND_2 = 3,        /* band_kernel<M, 2>: 8 values per lane, <= 505 cells                             */
+    ACX_SERRA09_FAMILY_BAND_4 = 4,        /* band_kernel<M, 4>: 16 values per lane, <= 1017 cells                           */
+    ACX_SERRA09_FAMILY_BAND_8 = 5,        /* band_kernel<M, 8>: 32 values per lane, <= 2041 cells                           */
+    ACX_SERRA09_FAMILY_STREAMING = 6      /* csm_long_kernel, rowsel_long_kernel, binarise_long_kernel: any length, m <= 33 */
+};
+typedef struct acx_serra09_plan_rec {
+    int32_t Mq, Mr;
+    int32_t batch;
+    int32_t cr, cq;
+    int32_t row_family, col_family;
+    int32_t sweep_cols, sweep_pack;
+} acx_serra09_plan_rec;
+int acx_serra09_plan(const int64_t *lengths, int32_t n_tracks, const int32_t *pairs, int64_t K,
+                     const acx_serra09_params *params, int64_t scratch_limit, acx_serra09_plan_rec *out);
+/* Printable name of a family for stack size m (band_kernel's names tell m <= 9 from m >= 10: the same limits, another
+ * kernel beside it); NULL for an unknown family.  The string is static. */
+const char *acx_serra09_family_name(int32_t family, int32_t m);
+
 /* ---- SiMPle (similarity matrix profile) ---------------------------------- */
 
 /*

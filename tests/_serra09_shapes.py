@@ -1,10 +1,14 @@
 """
 Shape sets for the Serra09 band and sweep kernels (tests/test_gpu_serra09_shapes.py; their design is checked on the CPU by
-tests/test_serra09_shapes_design.py).  Importable without a GPU: numpy, acoss_amd.synth and the CPU oracle only.
+tests/test_serra09_shapes_design.py).  Importable without a GPU: numpy, acoss_amd.synth, the CPU oracle and libacx's device-free
+plan report.
 
 The product path (run_serra09_impl, acoss_amd/csrc/acx.hip) sorts a batch by the size classes of a pair's two sides and picks a
-band kernel (launch_band_m, acoss_amd/csrc/acx_band.hip) and a sweep kernel per class; the sets below put tracks on both sides of
-every class edge and of every tile count, in every (reference class, query class) combination.
+band kernel and a sweep kernel per class.  The class limits and the kernel per class live in ONE place, the table of
+acoss_amd/csrc/serra09_plan.hpp; `cls`, `key` and `family` below do not restate it: they ask the library (acx_serra09_plan, the
+functions the run itself calls), so the design test reads the table the library was compiled with and `describe` names the kernel
+it would launch.  The sets put tracks on both sides of every class edge and of every tile count, in every (reference class, query
+class) combination; UPPER and LOWER are the literals they are built from.
 """
 import functools
 from concurrent.futures import ThreadPoolExecutor
@@ -17,29 +21,38 @@ UPPER = (249, 505, 761, 1017, 2041)      # the longest row (cells) of classes 0 
 LOWER = (250, 506, 762, 1018)            # the shortest row of classes 1 .. 4
 
 
-def cls(M):
-    """Size class of a row of M cells: cls1 of run_serra09_impl (acoss_amd/csrc/acx.hip) -- nd = (M + BAND - 1 + 63) / 64 tiles,
-    <= 4 / 8 / 12 / 16 / 32 of them, i.e. M <= 249 / 505 / 761 / 1017 / 2041; 5: the streaming kernels."""
-    nd = (M + BAND - 1 + 63) // 64
-    return 0 if nd <= 4 else 1 if nd <= 8 else 2 if nd <= 12 else 3 if nd <= 16 else 4 if nd <= 32 else 5
+@functools.lru_cache(maxsize=None)
+def _plan(Mq, Mr, m):
+    """The library's plan record of one pair of Mq x Mr cells at stack size m (tau = 1, embed_full = 0: T = M + m frames)."""
+    from acoss_amd import _lib
+    rec = _lib.serra09_plan([Mq + m, Mr + m], [[0, 1]], _lib.serra09_params(m=m))[0]
+    assert (int(rec["Mq"]), int(rec["Mr"])) == (Mq, Mr)
+    return rec
 
 
-def key(Mq, Mr):
+def cls(M, m=9):
+    """Size class of a row of M cells (serra09_row_class): 0 .. 4, or 5 for the streaming kernels."""
+    return int(_plan(M, M, m)["cr"])
+
+
+def key(Mq, Mr, m=9):
     """(cr, cq): the row pass and the sweep run per cr (rows of Mr cells), the column pass per (cr, cq) (rows of Mq cells)."""
-    return cls(Mr), cls(Mq)
+    rec = _plan(Mq, Mr, m)
+    return int(rec["cr"]), int(rec["cq"])
 
 
 def family(m, c):
-    """The band kernel family a pass whose longest row is of class c launches for stack size m, as launch_band_m
-    (acoss_amd/csrc/acx_band.hip) decides it by default (no ACX_BAND2)."""
-    if m <= 9:
-        return ("band2_kernel<M, B2_NV, 16>", "band2_kernel<M, B2_NV, 32>", "band2_kernel<M, B2_NV_MID, 32>",
-                "band_kernel<M<=9, 4>", "band_kernel<M<=9, 8>")[c]
-    return ("band_kernel<M>=10, 2>", "band_kernel<M>=10, 2>", "band_kernel<M>=10, 4>", "band_kernel<M>=10, 4>",
-            "band_kernel<M>=10, 8>")[c]
+    """The band kernel family a pass whose longest row is of class c launches for stack size m, by the library's name for it
+    (serra09_band_family; the process's ACX_BAND2 applies, as it does to the run)."""
+    from acoss_amd import _lib
+    M = UPPER[c] if c < NC else UPPER[-1] + 1
+    return _lib.serra09_family_name(_plan(M, M, m)["row_family"], m)
 
 
-FAMILIES = frozenset(family(m, c) for m in (9, 10) for c in range(NC))
+def __getattr__(name):
+    if name == "FAMILIES":          # (on first use: importing this module does not load the library)
+        return frozenset(family(m, c) for m in (9, 10) for c in range(NC))
+    raise AttributeError(name)
 
 
 def _embed_len(T, m):
@@ -187,7 +200,7 @@ def describe(d, k, m):
     """The label of pair k in failure messages: m, Mq, Mr, the class key and the band kernel families of its two passes."""
     i, j = d["pairs"][k]
     Mq, Mr = int(d["M"][i]), int(d["M"][j])
-    cr, cq = key(Mq, Mr)
+    cr, cq = key(Mq, Mr, m)
     return "m=%d pair %d (tracks %d, %d) Mq=%d Mr=%d (cr, cq)=(%d, %d) row pass %s, column pass %s" % (
         m, k, i, j, Mq, Mr, cr, cq, family(m, cr), family(m, cq))
 

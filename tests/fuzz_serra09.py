@@ -24,7 +24,7 @@ while time.time() < t_end:
     if rng.random() < 0.3:
         kw.update(gamma_o=float(rng.choice([0.25, 1.0, 1.5])), gamma_e=float(rng.choice([0.25, 0.5, 2.0])))
     ntr = int(rng.integers(3, 7))
-    # (also the longest rows of the size classes of run_serra09_impl: 249 / 505 / 761 / 1017 cells)
+    # (also the longest rows of the size classes of acoss_amd/csrc/serra09_plan.hpp's table: 249 / 505 / 761 / 1017 cells)
     tmax = int(rng.choice([60, 150, 400, 700, 1100, 2040 - m, 249, 505, 761, 1017 + m]))
     on_edge = tmax in (249, 505, 761, 1017 + m)
     if tmax > 1500:
@@ -32,7 +32,7 @@ while time.time() < t_end:
     tracks = []
     for t in range(ntr):
         T = int(rng.integers(m + 2, tmax + m + 2))
-        if on_edge and t < 2:                  # one track ON the edge and one just beyond it (tests/_serra09_shapes.py: cls)
+        if on_edge and t < 2:                  # one track ON the edge and one just beyond it (the class limits: acoss_amd/csrc/serra09_plan.hpp)
             e = tmax - m if tmax > 1017 else tmax
             T = e + t + (m - 1 if kw["embed_full"] else m)
         kind = rng.random()

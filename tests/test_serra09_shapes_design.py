@@ -1,7 +1,8 @@
 """
 CPU-only: the shape sets of tests/_serra09_shapes.py reach what tests/test_gpu_serra09_shapes.py says they reach -- every (cr, cq) class
 key of the product path's batch sort, both sides of every inner class edge as rows AND as columns, every band kernel family in both
-roles -- and the recurrence plots they give the kernels are neither empty nor full.
+roles -- and the recurrence plots they give the kernels are neither empty nor full.  S.cls / S.key / S.family are the library's own
+answers (acx_serra09_plan: the table of acoss_amd/csrc/serra09_plan.hpp, no device needed), so the literals below pin that table.
 """
 import numpy as np
 import pytest
