@@ -17,7 +17,7 @@ t_end = time.time() + budget
 rounds = pairs_done = fails = 0
 while time.time() < t_end:
     rounds += 1
-    m = int(rng.choice([9] * 8 + list(range(1, 17))))       # every compiled stack size; a third of the rounds the default
+    m = int(rng.choice([9] * 16 + list(range(1, 34))))      # every stack size, 17 .. 33 (the streaming kernels) included; a third of the rounds the default
     kw = dict(m=m, kappa=float(rng.choice([0.0, 0.004, 0.02, 0.095, 0.095, 0.3, 0.7, 1.0])), pct_mode=int(rng.integers(0, 4)),
               inclusive=int(rng.integers(0, 2)), dp_start=int(rng.choice([2, 3])), embed_full=int(rng.integers(0, 2)),
               oti=bool(rng.integers(0, 2)), oti_target=int(rng.integers(0, 2)), dmax=int(rng.integers(0, 2)))
@@ -27,7 +27,8 @@ while time.time() < t_end:
     # (also the longest rows of the size classes of acoss_amd/csrc/serra09_plan.hpp's table: 249 / 505 / 761 / 1017 cells)
     tmax = int(rng.choice([60, 150, 400, 700, 1100, 2040 - m, 249, 505, 761, 1017 + m]))
     on_edge = tmax in (249, 505, 761, 1017 + m)
-    if tmax > 1500:
+    stream = rng.random() < 0.1                # one round in ten: one track beyond the band classes (rows of more than 2041 cells)
+    if tmax > 1500 or stream:
         ntr = 3
     tracks = []
     for t in range(ntr):
@@ -35,9 +36,11 @@ while time.time() < t_end:
         if on_edge and t < 2:                  # one track ON the edge and one just beyond it (the class limits: acoss_amd/csrc/serra09_plan.hpp)
             e = tmax - m if tmax > 1017 else tmax
             T = e + t + (m - 1 if kw["embed_full"] else m)
+        if stream and t == 0:
+            T = int(rng.integers(2042 + m, 4500))
         kind = rng.random()
         if kind < 0.1:
-            T = min(T, 2050 - 2 * m) if tmax > 1500 else T
+            T = min(T, 2050 - 2 * m) if tmax > 1500 and not (stream and t == 0) else T
             x = np.tile(rng.random((1, 12)), (T, 1))       # a constant track: every distance equal
         elif kind < 0.6:
             x = rng.random((T, 12))

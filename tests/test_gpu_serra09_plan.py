@@ -68,3 +68,24 @@ def test_a_stack_of_17_streams_every_pair(ctx):
     assert "band_kernel" not in n
     assert n["csm_long_kernel"] == 1 and n["rowsel_long_kernel"] == 1 and n["qmax_bits_kernel"] == 1
     assert np.array_equal(got, oracle.serra09_pairs(frames, offsets, pairs, oracle.serra09_params(m=m)))
+
+
+def test_long_sides_stream_in_one_launch_each(ctx):
+    """long_set(9): 103 pairs with a side beyond 2041 cells, m = 9.  The report puts them all into class 5 of one batch, and the run
+    launches no band kernel: one csm_long_kernel, one rowsel_long_kernel and one sweep per call, two sweeps for chenfusion_pairs."""
+    from acoss_amd import _lib
+    m = 9
+    d = S.long_set(m)
+    p = _lib.serra09_params(m=m)
+    rec = _lib.serra09_plan(np.diff(d["offsets"]), d["pairs"], p)
+    assert len(rec) == 103 and np.all(rec["batch"] == 0) and np.all(rec["cr"] == 5) and np.all(rec["cq"] == 5) and np.all(rec["sweep_cols"] == 0)
+    assert {_lib.serra09_family_name(f, m) for f in rec["row_family"]} == {"csm_long_kernel + rowsel_long_kernel"}
+    ctx.upload_pool(d["frames"], d["offsets"])
+    _, n = _launches(ctx, ctx.serra09_pairs, d["pairs"], p)
+    print("serra09_pairs:", n)
+    assert "band_kernel" not in n
+    assert n["csm_long_kernel"] == 1 and n["rowsel_long_kernel"] == 1 and n["qmax_bits_kernel"] == 1 and n["oti_kernel"] == 1
+    _, n = _launches(ctx, ctx.chenfusion_pairs, d["pairs"], p)
+    print("chenfusion_pairs:", n)
+    assert "band_kernel" not in n
+    assert n["csm_long_kernel"] == 1 and n["rowsel_long_kernel"] == 1 and n["qmax_bits_kernel"] == 2
