@@ -38,6 +38,8 @@ EXPORTS = [
     "acx_rank_columns", "acx_topk_rows",
     "acx_query_scores", "acx_query_topk", "acx_query_ranks",
     "acx_serra09_debug_bits", "acx_serra09_plan", "acx_serra09_family_name",
+    "acx_pool_append", "acx_pool_append_raw", "acx_pool_append_f64", "acx_ef_pool_append", "acx_ftm2d_append_shingles",
+    "acx_pool_truncate",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -273,6 +275,12 @@ def load():
     L.acx_query_scores.argtypes = [vp, qp, vp, ip, ctypes.c_int32, dp, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64]
     L.acx_query_topk.argtypes = [vp, qp, vp, ip, ctypes.c_int32, ip, ctypes.c_int32, dp, ctypes.c_int32, ip, fp]
     L.acx_query_ranks.argtypes = [vp, qp, vp, ip, ctypes.c_int32, dp, ip, lp, ip, ip, ctypes.POINTER(ctypes.c_uint8)]
+    L.acx_pool_append.argtypes = [vp, fp, lp, ctypes.c_int32, ctypes.c_int32]
+    L.acx_pool_append_raw.argtypes = [vp, fp, lp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, lp]
+    L.acx_pool_append_f64.argtypes = [vp, dp, lp, ctypes.c_int32, ctypes.c_int32]
+    L.acx_ef_pool_append.argtypes = [vp, fp, fp, fp, dp, lp, ctypes.c_int32]
+    L.acx_ftm2d_append_shingles.argtypes = [vp, dp, ctypes.c_int32, ctypes.c_int32]
+    L.acx_pool_truncate.argtypes = [vp, ctypes.c_int32, ctypes.c_int32]
     _check_hip_version(L)
     _lib = L
     return L
@@ -672,6 +680,7 @@ class Context(object):
         self._check(self._L.acx_ef_upload_raw_pool(self._h, _fptr(ch), _lptr(coff), _fptr(mf), _lptr(moff), ncoef,
                                                    _lptr(on), _lptr(ooff), len(tracks), ctypes.byref(p), _lptr(boff)))
         self.ef_blocks = np.diff(boff)
+        self._ef_dims = (int(mfccs_per_block) * int(ncoef), int(mfccs_per_block) * (int(mfccs_per_block) - 1) // 2, int(chromas_per_block) * 12)
         return boff
 
     def earlyfusion_pairs(self, pairs, kappa=0.1, K=10):
@@ -1010,6 +1019,82 @@ class Context(object):
             self._check(self._L.acx_topk_rows(self._h, ctypes.c_void_p(slab.ctypes.data), int(ld), n, int(cnt), _iptr(rows[a:a + cnt]),
                                               None if posn is None else _iptr(posn), k, _iptr(idx[a:a + cnt]), _fptr(score[a:a + cnt])))
         return idx, score
+
+    # ------------------------------------------------------------------ appends: tracks behind an uploaded pool
+    # Offsets are relative to the appended tracks (offsets[0] == 0).  Afterwards every call answers as it does after one
+    # upload of the whole final track list; a failed append leaves the pool as it was (include/acx.h).
+    def _refresh_lengths(self):
+        """n_tracks / lengths (what serra09_debug_pair sizes its buffers by) as the library holds them."""
+        self.lengths = self.pool_lengths(ALGO_SERRA09)
+        self.n_tracks = len(self.lengths)
+
+    def pool_append(self, frames, offsets):
+        """Pooled (sum T, dim) f32 frames of len(offsets) - 1 tracks behind the pool of upload_pool / upload_raw_pool."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if frames.ndim != 2 or offsets.ndim != 1 or len(offsets) < 1 or offsets[-1] != frames.shape[0]:
+            raise ValueError("pool_append: frames must be (sum T, dim) and offsets (n+1,) with offsets[-1] == sum T")
+        self._check(self._L.acx_pool_append(self._h, _fptr(frames), _lptr(offsets), len(offsets) - 1, frames.shape[1]))
+        self._refresh_lengths()
+
+    def pool_append_raw(self, raw, raw_offsets, fac=40):
+        """Raw (sum T0, 12) f32 chroma behind the same pool: block medians and the OTI's chroma profile on the device;
+        returns the pooled offsets of the new tracks (relative)."""
+        raw = np.ascontiguousarray(raw, dtype=np.float32)
+        raw_offsets = np.ascontiguousarray(raw_offsets, dtype=np.int64)
+        if raw_offsets.ndim != 1 or len(raw_offsets) < 1 or (raw.ndim == 2 and raw_offsets[-1] != raw.shape[0]):
+            raise ValueError("pool_append_raw: raw must be (sum T0, 12) and raw_offsets (n+1,) with raw_offsets[-1] == sum T0")
+        poff = np.zeros(len(raw_offsets), np.int64)
+        self._check(self._L.acx_pool_append_raw(self._h, _fptr(raw), _lptr(raw_offsets), len(raw_offsets) - 1,
+                                                raw.shape[1] if raw.ndim == 2 else 12, int(fac), _lptr(poff)))
+        self._refresh_lengths()
+        return poff
+
+    def pool_append_f64(self, frames, offsets):
+        """SiMPle features, (sum n, 12) f64 time-major, behind the pool of upload_pool_f64."""
+        frames = np.ascontiguousarray(frames, dtype=np.float64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if frames.ndim != 2 or offsets.ndim != 1 or len(offsets) < 1 or offsets[-1] != frames.shape[0]:
+            raise ValueError("pool_append_f64: frames must be (sum n, 12) and offsets (n+1,)")
+        self._check(self._L.acx_pool_append_f64(self._h, _dptr(frames), _lptr(offsets), len(offsets) - 1, frames.shape[1]))
+
+    def ef_pool_append(self, tracks):
+        """Block-feature dicts (as ef_upload_pool takes them) behind a finished EarlyFusion pool."""
+        tracks = list(tracks)
+        if not tracks:
+            raise ValueError("ef_pool_append: no tracks")
+        dims = getattr(self, "_ef_dims", None)
+        mats = [np.ascontiguousarray(np.concatenate([np.asarray(t[k]) for t in tracks], axis=0), dtype=np.float32)
+                for k in ("mfccs", "ssms", "chromas")]
+        if any(m.ndim != 2 for m in mats) or len({m.shape[0] for m in mats}) != 1:
+            raise ValueError("ef_pool_append: mfccs, ssms and chromas must be (blocks, dim) with the same blocks per track")
+        if dims is not None and tuple(m.shape[1] for m in mats) != tuple(dims):
+            raise ValueError("ef_pool_append: dims %s differ from the pool's %s" % ([m.shape[1] for m in mats], list(dims)))
+        med = np.ascontiguousarray(np.stack([np.asarray(t["chroma_med"], dtype=np.float64).reshape(12) for t in tracks]))
+        offs = np.concatenate([[0], np.cumsum([np.asarray(t["mfccs"]).shape[0] for t in tracks])]).astype(np.int64)
+        self._check(self._L.acx_ef_pool_append(self._h, _fptr(mats[0]), _fptr(mats[1]), _fptr(mats[2]), _dptr(med), _lptr(offs), len(tracks)))
+        if getattr(self, "ef_blocks", None) is not None:
+            self.ef_blocks = np.concatenate([np.asarray(self.ef_blocks, np.int64), np.diff(offs)])
+
+    def ftm2d_append_shingles(self, shingles):
+        """(Q, D) f64 shingles behind a finished FTM2D pool."""
+        S = np.ascontiguousarray(shingles, dtype=np.float64)
+        if S.ndim != 2:
+            raise ValueError("ftm2d_append_shingles: shingles must be (Q, D)")
+        self._check(self._L.acx_ftm2d_append_shingles(self._h, _dptr(S), S.shape[0], S.shape[1]))
+        if getattr(self, "ftm2d_shape", None) is not None:
+            self.ftm2d_shape = (self.ftm2d_shape[0] + S.shape[0], self.ftm2d_shape[1])
+
+    def pool_truncate(self, algo, n_tracks):
+        """Keep the first n_tracks tracks of the pool of `algo` (ALGO_*; Serra09 and ChenFusion share one)."""
+        self._check(self._L.acx_pool_truncate(self._h, int(algo), int(n_tracks)))
+        n = int(n_tracks)
+        if int(algo) in (ALGO_SERRA09, ALGO_CHENFUSION):
+            self._refresh_lengths()
+        if int(algo) == ALGO_FTM2D and getattr(self, "ftm2d_shape", None) is not None:
+            self.ftm2d_shape = (n, self.ftm2d_shape[1])
+        if int(algo) == ALGO_EARLYFUSION and getattr(self, "ef_blocks", None) is not None:
+            self.ef_blocks = np.asarray(self.ef_blocks)[:n]
 
     # ------------------------------------------------------------------ queries against the uploaded collection
     def _query_args(self, algo, symmetric, queries, col, col_mode):

@@ -304,6 +304,20 @@ class CoverAlgorithm(object):
             raise ValueError("%s: queries must be track indices in [0, %d)" % (who, self.N))
         return q.astype(np.int32), types
 
+    def _check_candidates(self, who, candidates, what):
+        """The candidates of identify() / identify_tracks(): None, or strictly ascending track indices in [0, N) as int32."""
+        if candidates is None:
+            return None
+        cands = np.asarray(candidates)
+        if cands.size and not np.issubdtype(cands.dtype, np.integer):
+            raise ValueError("%s: candidates must be integer track indices" % who)
+        cands = cands.reshape(-1).astype(np.int64)
+        if cands.size and (cands.min() < 0 or cands.max() >= self.N):
+            raise ValueError("%s: candidates must be %s in [0, %d)" % (who, what, self.N))
+        if np.any(np.diff(cands) <= 0):
+            raise ValueError("%s: candidates must be strictly ascending" % who)
+        return cands.astype(np.int32)
+
     def _query_call(self):
         ctx, algo, params, keys = self._grid()
         if tuple(keys) != tuple(self._identify_planes):
@@ -326,17 +340,7 @@ class CoverAlgorithm(object):
         k = int(k)
         if k < 1:
             raise ValueError("identify: k must be >= 1 (got %d)" % k)
-        cands = None
-        if candidates is not None:
-            cands = np.asarray(candidates)
-            if cands.size and not np.issubdtype(cands.dtype, np.integer):
-                raise ValueError("identify: candidates must be integer track indices")
-            cands = cands.reshape(-1).astype(np.int64)
-            if cands.size and (cands.min() < 0 or cands.max() >= self.N):
-                raise ValueError("identify: candidates must be track indices in [0, %d)" % self.N)
-            if np.any(np.diff(cands) <= 0):
-                raise ValueError("identify: candidates must be strictly ascending")
-            cands = cands.astype(np.int32)
+        cands = self._check_candidates("identify", candidates, "track indices")
         ctx, algo, params, mode, col = self._query_call()
         idx, score = ctx.query_topk(algo, self._identify_symmetric, params, q, k, candidates=cands, col=col, col_mode=mode)
         planes = list(self._identify_planes)
@@ -350,6 +354,83 @@ class CoverAlgorithm(object):
         rows = ctx.query_scores(algo, self._identify_symmetric, params, q, col=col, col_mode=mode)
         planes = list(self._identify_planes)
         return {t: rows[planes.index(t)] for t in types}
+
+    # ------------------------------------------------------------------ tracks the collection does not hold
+    def _check_tracks(self, who, tracks, **how):
+        """Per class: the tracks of identify_tracks() / score_tracks() in the format of the class's injection method,
+        checked and converted WITHOUT touching the library (ValueError for a wrong shape or dtype).  `how`: the class's
+        own options of that format (Serra09: raw).  Returns what _append_tracks takes, whatever the class needs there."""
+        raise NotImplementedError("%s: %s has no append path (_check_tracks / _append_tracks)" % (who, type(self).__name__))
+
+    def _append_tracks(self, ctx, checked):
+        """Per class: put what _check_tracks returned behind the uploaded pool (Context.*_append*) and return what
+        _identify_norm needs for the new columns: its `col` values for them, or None for a class without a norm."""
+        raise NotImplementedError
+
+    def _tracks_setup(self, who, tracks, similarity_types, candidates, how):
+        """Argument checks of identify_tracks() / score_tracks(), all before the first library call:
+        -> (what _check_tracks returned, the number of tracks, the similarity types, the candidates)."""
+        _, types = self._query_setup(who, [], similarity_types)
+        try:
+            tracks = list(tracks)
+        except TypeError:
+            raise ValueError("%s: tracks must be a list of tracks" % who)
+        if not tracks:
+            raise ValueError("%s: tracks must hold at least one track" % who)
+        checked = self._check_tracks(who, tracks, **how)
+        return checked, len(tracks), types, self._check_candidates(who, candidates, "tracks of the collection, indices")
+
+    def _with_appended(self, checked, Q, call):
+        """call(ctx, algo, params, mode, col, queries) with the Q tracks behind the collection's pool as tracks N .. N + Q - 1;
+        whatever happens, the pool holds the N tracks of the collection again afterwards."""
+        ctx, algo, params, mode, col = self._query_call()
+        N = self.N
+        try:
+            tail = self._append_tracks(ctx, checked)
+            if col is not None:
+                col = np.concatenate([np.asarray(col, np.float64).reshape(-1), np.asarray(tail, np.float64).reshape(-1)])
+            return call(ctx, algo, params, mode, col, np.arange(N, N + Q, dtype=np.int32))
+        finally:
+            if len(ctx.pool_lengths(algo)) > N:
+                ctx.pool_truncate(algo, N)
+
+    def identify_tracks(self, tracks, k=10, candidates=None, similarity_types=None):
+        """identify() for tracks the collection does NOT hold.  tracks: a list in the format of the class's injection
+        method (Serra09 / ChenFusion: pooled (T, 12) f32 chroma, or with raw=True raw (T0, 12) chroma, pooled by
+        downsample_fac on the device, on the host by pool_median above 64; SiMPle: (12, n) f64; EarlyFusion: block-feature
+        dicts; FTM2D: (12 WIN,) shingles).  They are appended behind the uploaded
+        pool (O(Q) work: the collection is not uploaded again), asked about as queries N .. N + Q - 1 against the
+        candidates [0, N) -- or `candidates`, strictly ascending indices in [0, N) --, and taken away again: `Ds`, N,
+        the cliques and the pool are as before.  Returns what identify() returns; the values are those of
+        identify(queries=[N ..], candidates=range(N)) on a collection of the N + Q tracks: a symmetric class computes a
+        cell as the pair (candidate, new track), SiMPle as (new track, candidate)."""
+        return self._identify_tracks(tracks, k, candidates, similarity_types)
+
+    def _identify_tracks(self, tracks, k, candidates, similarity_types, **how):
+        """identify_tracks(); how: the options of the class's own track format, handed to its _check_tracks."""
+        k = int(k)
+        if k < 1:
+            raise ValueError("identify_tracks: k must be >= 1 (got %d)" % k)
+        checked, Q, types, cands = self._tracks_setup("identify_tracks", tracks, similarity_types, candidates, how)
+        if cands is None:
+            cands = np.arange(self.N, dtype=np.int32)
+        idx, score = self._with_appended(checked, Q, lambda ctx, algo, params, mode, col, q: ctx.query_topk(
+            algo, self._identify_symmetric, params, q, k, candidates=cands, col=col, col_mode=mode))
+        planes = list(self._identify_planes)
+        return {t: (np.ascontiguousarray(idx[:, planes.index(t)]), np.ascontiguousarray(score[:, planes.index(t)])) for t in types}
+
+    def score_tracks(self, tracks, similarity_types=None):
+        """query_rows() for tracks the collection does not hold: {type: (Q, N) float32}, the finished scores of every new
+        track against every track of the collection, as identify_tracks() ranks them."""
+        return self._score_tracks(tracks, similarity_types)
+
+    def _score_tracks(self, tracks, similarity_types, **how):
+        checked, Q, types, _ = self._tracks_setup("score_tracks", tracks, similarity_types, None, how)
+        N = self.N
+        rows = self._with_appended(checked, Q, lambda ctx, algo, params, mode, col, q: ctx.query_scores(
+            algo, self._identify_symmetric, params, q, col=col, col_mode=mode))
+        planes = list(self._identify_planes)
+        return {t: np.ascontiguousarray(rows[planes.index(t)][:, :N]) for t in types}
 
     def evaluate(self, queries=None, similarity_types=None, topsidx=[1, 10, 100, 1000], report=False, info=None, row_block=1024):
         """MR, MRR, MDR, MAP and Top-k of a query set against the collection without an N x N matrix:

@@ -112,6 +112,31 @@ class EarlyFusion(CoverAlgorithm):
             self._pool_ready = True
         return self._ctx
 
+    def _check_tracks(self, who, tracks):
+        out = []
+        for i, t in enumerate(tracks):
+            if not isinstance(t, dict) or not all(k in t for k in _KEYS):
+                raise ValueError("%s: track %d must be a dict of block features with the keys %s" % (who, i, list(_KEYS)))
+            mats = {k: np.asarray(t[k]) for k in ("mfccs", "ssms", "chromas")}
+            for k, m in mats.items():
+                if m.ndim != 2 or m.dtype.kind != "f":
+                    raise ValueError("%s: track %d: %s must be a floating-point (blocks, dim) array, got %s %s" % (who, i, k, m.dtype, m.shape))
+            if len({m.shape[0] for m in mats.values()}) != 1:
+                raise ValueError("%s: track %d: mfccs, ssms and chromas must have the same number of blocks" % (who, i))
+            ref = self.all_block_feats.get(0) if self.all_block_feats else None
+            ref = ref if ref is not None else (out[0] if out else None)
+            if ref is not None and any(mats[k].shape[1] != np.asarray(ref[k]).shape[1] for k in mats):
+                raise ValueError("%s: track %d: block-feature widths %s differ from the collection's" % (who, i, [mats[k].shape[1] for k in mats]))
+            med = np.asarray(t["chroma_med"], dtype=np.float64)
+            if med.size != 12:
+                raise ValueError("%s: track %d: chroma_med must hold 12 values" % (who, i))
+            out.append(dict(mfccs=mats["mfccs"], ssms=mats["ssms"], chromas=mats["chromas"], chroma_med=med.reshape(12)))
+        return out
+
+    def _append_tracks(self, ctx, tracks):
+        ctx.ef_pool_append(tracks)
+        return None
+
     _identify_planes = ("mfccs", "ssms", "chromas", "early")
     _identify_fused = ("late", "early+late")
 

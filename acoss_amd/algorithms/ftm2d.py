@@ -115,6 +115,21 @@ class FTM2D(CoverAlgorithm):
             self._pool_ready = True
         return self._ctx
 
+    def _check_tracks(self, who, tracks):
+        out = []
+        for i, t in enumerate(tracks):
+            t = np.asarray(t)
+            if t.ndim != 1 or t.shape[0] != 12 * int(self.WIN):
+                raise ValueError("%s: track %d must be a (%d,) shingle, got shape %s" % (who, i, 12 * int(self.WIN), t.shape))
+            if t.dtype.kind != "f":
+                raise ValueError("%s: track %d must be a floating-point shingle, got dtype %s" % (who, i, t.dtype))
+            out.append(np.asarray(t, dtype=np.float64))
+        return out
+
+    def _append_tracks(self, ctx, tracks):
+        ctx.ftm2d_append_shingles(np.stack(tracks))
+        return None
+
     def _grid(self):
         return self._context(), _lib.ALGO_FTM2D, None, ["main"]
 

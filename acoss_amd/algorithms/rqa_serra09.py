@@ -157,6 +157,43 @@ class Serra09(CoverAlgorithm):
         """identify() / query_rows(): normalize_by_length below as a column mode (acx_query_spec: s / sqrt(T_c))."""
         return 1, np.sqrt(self._pooled_lengths().astype(np.float64))
 
+    # ------------------------------------------------------------------ tracks the collection does not hold
+    def identify_tracks(self, tracks, k=10, candidates=None, similarity_types=None, raw=False):
+        """CoverAlgorithm.identify_tracks; tracks: pooled (T, 12) f32 chroma as set_pooled_features takes it, or with
+        raw=True raw (T0, 12) chroma, pooled by downsample_fac on the device (on the host by pool_median above 64)."""
+        return self._identify_tracks(tracks, k, candidates, similarity_types, raw=raw)
+
+    def score_tracks(self, tracks, similarity_types=None, raw=False):
+        return self._score_tracks(tracks, similarity_types, raw=raw)
+
+    def _check_tracks(self, who, tracks, raw=False):
+        """tracks: pooled (T, 12) f32 chroma as set_pooled_features takes it, or with raw=True raw (T0, 12) chroma, pooled
+        by downsample_fac on the device (on the host, here, by pool_median above 64).
+        -> (the tracks, whether the device still has to pool them)."""
+        out = []
+        for i, t in enumerate(tracks):
+            t = np.asarray(t)
+            if t.ndim != 2 or t.shape[1] != 12:
+                raise ValueError("%s: track %d must be (T, 12) chroma, got shape %s" % (who, i, t.shape))
+            if t.dtype.kind != "f":
+                raise ValueError("%s: track %d must be floating-point chroma, got dtype %s" % (who, i, t.dtype))
+            t = np.ascontiguousarray(t, dtype=np.float32)
+            if raw and self.downsample_fac > 64:
+                t = pool_median(t, self.downsample_fac) if len(t) else t
+            out.append(t)
+        return out, bool(raw) and self.downsample_fac <= 64
+
+    def _append_tracks(self, ctx, checked):
+        tracks, pool_on_device = checked
+        offs = np.concatenate([[0], np.cumsum([t.shape[0] for t in tracks])]).astype(np.int64)
+        frames = np.concatenate(tracks, axis=0)
+        if pool_on_device:
+            lens = np.diff(ctx.pool_append_raw(frames, offs, self.downsample_fac))
+        else:
+            ctx.pool_append(frames, offs)
+            lens = np.diff(offs)
+        return np.sqrt(lens.astype(np.float64))
+
     def similarity(self, idxs):
         idxs = np.asarray(idxs).reshape(-1, 2)
         if len(idxs) == 0:

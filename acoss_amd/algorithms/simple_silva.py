@@ -122,6 +122,22 @@ class Simple(CoverAlgorithm):
         ctx.upload_pool_f64(np.concatenate([a, b]), np.array([0, len(a), len(a) + len(b)], np.int64))
         return float(-ctx.simple_pairs(np.array([[0, 1]], np.int32), self.SSLEN, oti=False)[0])
 
+    def _check_tracks(self, who, tracks):
+        out = []
+        for i, t in enumerate(tracks):
+            t = np.asarray(t)
+            if t.ndim != 2 or t.shape[0] != 12:
+                raise ValueError("%s: track %d must be (12, n) features, got shape %s" % (who, i, t.shape))
+            if t.dtype.kind != "f":
+                raise ValueError("%s: track %d must be floating-point features, got dtype %s" % (who, i, t.dtype))
+            out.append(np.ascontiguousarray(t.T, dtype=np.float64))
+        return out
+
+    def _append_tracks(self, ctx, tracks):
+        offs = np.concatenate([[0], np.cumsum([t.shape[0] for t in tracks])]).astype(np.int64)
+        ctx.pool_append_f64(np.concatenate(tracks, axis=0), offs)
+        return None
+
     def _grid(self):
         return self._context(), _lib.ALGO_SIMPLE, _lib.SimpleParams(int(self.SSLEN), 1), ["main"]
 

@@ -94,6 +94,7 @@ struct acx_ctx {
     float *d_normtab = nullptr;   // embedded norms per (track, rotation, frame) for normtab_m / normtab_span
     int64_t *d_noff = nullptr;
     int normtab_m = 0, normtab_span = -1;
+    std::vector<int64_t> h_noff;  // host copy of d_noff (n_tracks + 1 entries; the last one is the table's length)
     int64_t *d_toff = nullptr;
     float *d_gch = nullptr;
     std::vector<int64_t> h_off;
@@ -179,6 +180,14 @@ struct acx_ctx {
                              {"query_topk_kernel", 0, 0, 0}, {"query_rank_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
+    // Appends (acx_pool_append & co.): capacity in elements of every raw-pointer pool block that an append has grown.  0 = the block
+    // is as its upload allocated it, exactly as large as its contents; whoever frees a block resets its entry.
+    struct S09Caps { size_t frames0, toff0, gch, frames, toff, frot, fh, normtab, noff; } s09_cap = {};
+    struct EfCaps { size_t ef[3], efs[3], efn[2], efsc[3], efmed, efoff; } ef_cap = {};
+    size_t ftm_cap = 0;
+    // How many tracks ensure_f16pool's range check saw when it built d_fh (-1: it had no frame to check).  The largest magnitude of
+    // a pool that contains those tracks is at least theirs, so the check's lower bound holds for every such pool.
+    int32_t fh_base_n = -1;
 };
 
 namespace {
@@ -333,10 +342,10 @@ bool launch_band(acx_ctx *c, int m, const PairDesc *dpd, int B, int maxRows, int
 }
 
 template <int M>
-void launch_normtab(acx_ctx *c, int maxM, int span)
+void launch_normtab(acx_ctx *c, int maxM, int span, int first, int count)       // tracks [first, first + count) of the active pool
 {
-    hipLaunchKernelGGL((acx::normtab_kernel<M>), dim3(c->n_tracks, (maxM + 255) / 256, acx::NBIN), dim3(256), 0, c->stream,
-                       c->d_frames, c->d_toff, c->d_noff, c->d_normtab + POOL_SLACK, span);
+    hipLaunchKernelGGL((acx::normtab_kernel<M>), dim3(count, (maxM + 255) / 256, acx::NBIN), dim3(256), 0, c->stream,
+                       c->d_frames, c->d_toff + first, c->d_noff + first, c->d_normtab + POOL_SLACK, span);
 }
 
 #ifdef ACX_FAST_BUILD   /* development builds: only the default stack size */
@@ -371,6 +380,8 @@ int ensure_tau(acx_ctx *c, int tau)
     if (c->d_noff) { ACX_HIP(c, hipFree(c->d_noff)); c->d_noff = nullptr; }
     c->normtab_m = 0; c->normtab_span = -1;
     c->pool_tau = 0;
+    c->s09_cap.frames = c->s09_cap.toff = c->s09_cap.frot = c->s09_cap.fh = c->s09_cap.normtab = c->s09_cap.noff = 0;
+    c->fh_base_n = -1;
     const int n = c->n_tracks;
     DeviceBuffer<float> frames, frot;            // built here and handed to the context when complete: a failure leaves no half-built pool
     DeviceBuffer<int64_t> toff;
@@ -435,9 +446,9 @@ int ensure_f16pool(acx_ctx *c)
     // become inf (NaN distances), features far below 1 lose their second term to fp16's subnormal range -- and the embedded
     // norms, made from the exact f32 values, would no longer match the Gram.  HPCP / CREMA frames are normalised to a
     // maximum of 1; a pool whose largest value lies outside [2^-8, 2^15] is refused (rescale it, or use ACX_ARITH_EXACT).
+    unsigned h_m = 0u;
     if (total > 0) {
         DeviceBuffer<unsigned> d_m;
-        unsigned h_m = 0u;
         ACX_HIP(c, d_m.grow(1));
         ACX_HIP(c, hipMemsetAsync(d_m, 0, sizeof(unsigned), c->stream));
         hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)std::min<int64_t>((total * acx::NBIN + 255) / 256, 4096)), dim3(256), 0, c->stream,
@@ -462,6 +473,8 @@ int ensure_f16pool(acx_ctx *c)
     }
     ACX_HIP(c, hipStreamSynchronize(c->stream));
     c->d_fh = fh.release();
+    c->s09_cap.fh = 0;
+    c->fh_base_n = total > 0 ? c->n_tracks : -1;
     return ACX_OK;
 }
 
@@ -473,7 +486,9 @@ int ensure_normtab(acx_ctx *c, const acx_serra09_params &p)
     if (c->d_normtab) { ACX_HIP(c, hipFree(c->d_normtab)); c->d_normtab = nullptr; }
     if (c->d_noff) { ACX_HIP(c, hipFree(c->d_noff)); c->d_noff = nullptr; }
     c->normtab_m = 0; c->normtab_span = -1;            // (a failure below must not leave the old key on a new, unfinished table)
-    std::vector<int64_t> noff((size_t)c->n_tracks + 1);
+    c->s09_cap.normtab = c->s09_cap.noff = 0;
+    std::vector<int64_t> &noff = c->h_noff;
+    noff.assign((size_t)c->n_tracks + 1, 0);
     int64_t tot = 0;
     int maxM = 1;
     for (int t = 0; t < c->n_tracks; ++t) {
@@ -491,7 +506,7 @@ int ensure_normtab(acx_ctx *c, const acx_serra09_params &p)
     bool handled = true;
     {
         ProfScope ps(c, KS_NORMS, 0);
-#define ACX_CALL(M_) launch_normtab<M_>(c, maxM, span)
+#define ACX_CALL(M_) launch_normtab<M_>(c, maxM, span, 0, c->n_tracks)
         ACX_M_SWITCH(p.m, ACX_CALL)
 #undef ACX_CALL
     }
@@ -1417,6 +1432,8 @@ static void free_pool(acx_ctx *c)
     c->d_noff = nullptr;
     c->normtab_m = 0; c->normtab_span = -1;
     c->pool_tau = 0;
+    c->s09_cap = {};
+    c->fh_base_n = -1;
 }
 
 template <int L>
@@ -2077,6 +2094,7 @@ static void ef_free_pool(acx_ctx *c)
     if (c->d_efoff) { (void)hipFree(c->d_efoff); c->d_efoff = nullptr; }
     c->ef_ntracks = 0;
     c->ef_open = 0;
+    c->ef_cap = {};
 }
 
 // (Re)build the split pools the matrix-pipe GEMMs read from the f32 features: fmt 0 = three bf16 terms, fmt 1 = two
@@ -2518,6 +2536,7 @@ static void ftm2d_free_pool(acx_ctx *c)
 {
     if (c->d_ftm) (void)hipFree(c->d_ftm);
     c->d_ftm = nullptr;
+    c->ftm_cap = 0;
     c->ftm_n = c->ftm_dim = 0;
     c->ftm_open = 0;
     c->ftm_filled.clear();
@@ -3130,6 +3149,536 @@ int acx_snf_fuse_dists(acx_ctx *c, const double *const *Ds, int32_t m, int32_t n
     }
     ACX_HIP(c, e);
     return snf_loop(c, R, niters, reg_diag, out);
+}
+
+// ---------------------------------------------------------------------------------------
+// appends and truncation: tracks behind an uploaded pool in O(new tracks) work
+//
+// An append (1) checks everything, (2) makes room in every block of the pool, derived ones included (grow_keep: the pool is
+// the same pool afterwards), (3) writes the new tracks and their derived data BEHIND the pool's end, where nothing reads, and
+// (4) moves the end: counts and host offsets.  A failure before (4) leaves the pool as it was: (2) carries the slack behind the
+// end into every block it replaces, and after a failure inside (3), which writes over that slack, it is restored (*_seal), which
+// is also all a truncate does besides moving the end back.
+// ---------------------------------------------------------------------------------------
+
+// Grow and keep: the block `p` (capacity `cap` elements; 0 = exactly its `keep` live elements, as an upload leaves it) gets room
+// for `need` elements.  A block that is too small is replaced by one of max(need, 1.5 x capacity): allocated beside the old one,
+// the first `keep` elements copied device to device on the library's stream, then the old one freed.  `keep` counts whatever a
+// reader may touch: the live elements and, where a block has slack behind its end, that slack.  A failure leaves the old block.
+extern "C++" {
+template <typename T>
+static int grow_keep(acx_ctx *c, T *&p, size_t &cap, size_t keep, size_t need)
+{
+    if (cap < keep) cap = keep;
+    if (need <= cap) return ACX_OK;
+    const size_t ncap = std::max(need, cap + cap / 2);
+    DeviceBuffer<T> fresh;
+    const hipError_t e = fresh.grow(ncap);
+    if (e != hipSuccess)
+        return fail(c, ACX_ERR_NOMEM, "append: hipMalloc of " + std::to_string(ncap * sizeof(T)) + " bytes failed: " + hipGetErrorString(e));
+    if (keep) ACX_HIP(c, hipMemcpyAsync(fresh.get(), p, sizeof(T) * keep, hipMemcpyDeviceToDevice, c->stream));
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    if (p) (void)hipFree(p);
+    p = fresh.release();
+    cap = ncap;
+    return ACX_OK;
+}
+
+template <typename T>
+static int grow_keep(acx_ctx *c, DeviceBuffer<T> &b, size_t keep, size_t need)
+{
+    size_t cap = b.capacity();
+    T *p = b.release();
+    const int rc = grow_keep(c, p, cap, keep, need);      // (a failure leaves the old block in p)
+    b.adopt(p, cap);
+    return rc;
+}
+}  // extern "C++"
+
+// What every append checks first: the arguments that all of them share, and the offsets of the new tracks (relative: offsets[0] == 0).
+static int append_check(acx_ctx *c, const char *who, const void *data, const int64_t *offsets, int32_t n_new, int64_t n_old)
+{
+    if (!data) return fail(c, ACX_ERR_INVALID, std::string(who) + ": the feature pointer must not be NULL");
+    if (n_new <= 0) return fail(c, ACX_ERR_INVALID, std::string(who) + ": n_new must be >= 1");
+    if (n_old + n_new > 0x7fffffffLL) return fail(c, ACX_ERR_INVALID, std::string(who) + ": n_new takes the pool beyond 2^31 - 1 tracks");
+    if (!offsets) return ACX_OK;                            // (one row per track)
+    if (offsets[0] != 0) return fail(c, ACX_ERR_INVALID, std::string(who) + ": offsets[0] must be 0 (offsets are relative to the appended tracks)");
+    for (int i = 0; i < n_new; ++i)
+        if (offsets[i + 1] < offsets[i]) return fail(c, ACX_ERR_INVALID, std::string(who) + ": offsets must be non-decreasing");
+    return ACX_OK;
+}
+
+// offsets [n0 + 1, n0 + n_new] of a device offset table from the new tracks' relative ones (entry n0 is the pool's end already)
+static int append_offsets(acx_ctx *c, int64_t *d_off, int64_t n0, int64_t end0, const int64_t *rel, int32_t n_new, std::vector<int64_t> &abs)
+{
+    abs.resize((size_t)n_new + 1);
+    for (int i = 0; i <= n_new; ++i) abs[i] = end0 + rel[i];
+    ACX_HIP(c, hipMemcpyAsync(d_off + n0, abs.data(), sizeof(int64_t) * (n_new + 1), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipStreamSynchronize(c->stream));           // (abs is pageable)
+    return ACX_OK;
+}
+
+static void plan_forget(acx_ctx *c) { c->plan_len.clear(); c->plan_spec.algo = -1; }
+
+// ---- f32 pool (Serra09 / ChenFusion) ----
+
+// The slack behind the pool's end as an upload leaves it: POOL_SLACK zeroed frames behind the rotated and the f16 pool, +inf from the
+// norm table's end up to `norm_hi` + POOL_SLACK (norm_hi: the farthest table end anything was written for).
+static int s09_seal(acx_ctx *c, int64_t norm_hi)
+{
+    if (c->pool_tau < 1) return ACX_OK;
+    const int64_t atotal = c->h_off[c->n_tracks];
+    if (c->d_frot) ACX_HIP(c, hipMemsetAsync(c->d_frot + (POOL_SLACK + atotal) * acx::FROT, 0, sizeof(float) * POOL_SLACK * acx::FROT, c->stream));
+    if (c->d_fh) ACX_HIP(c, hipMemsetAsync(c->d_fh + (POOL_SLACK + atotal) * acx::FH, 0, sizeof(_Float16) * POOL_SLACK * acx::FH, c->stream));
+    if (c->d_normtab && c->normtab_m > 0) {
+        const int64_t tot = c->h_noff[c->n_tracks];
+        if (norm_hi >= tot)
+            ACX_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(c->d_normtab + POOL_SLACK + tot), 0x7f800000, (size_t)(norm_hi - tot + POOL_SLACK), c->stream));
+    }
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
+}
+
+// What an append of `n_new` tracks adds to the f32 pool, worked out on the host before anything is touched.
+struct S09Tail {
+    int n0 = 0, n1 = 0;
+    std::vector<int64_t> off0, aoff, noff;     // n_new + 1 absolute offsets each: uploaded pool, active pool, norm table
+    int maxT = 1, maxM = 1;                    // longest new track of the active pool, in frames / embedded frames
+    bool active = false, table = false;        // the pool has an active copy (dim 12) / a norm table to extend
+};
+
+// Steps (1) and (2) for the f32 pool: on return every block has room for the new tracks and d_toff0's tail is written.
+static int s09_append_begin(acx_ctx *c, const char *who, const int64_t *rel, int32_t n_new, S09Tail &t)
+{
+    quiesce(c);                                 // qstream / qstream2 may still hold sweeps that read the blocks replaced below
+    const int dim = c->dim, tau = c->pool_tau;
+    t.n0 = c->n_tracks; t.n1 = t.n0 + n_new;
+    const int64_t total0 = c->h_off0[t.n0], total1 = total0 + rel[n_new];
+    t.active = dim == acx::NBIN && tau >= 1 && c->d_frames && c->d_toff;
+    t.table = t.active && c->d_normtab && c->d_noff && c->normtab_m > 0;
+    const int64_t atotal0 = t.active ? c->h_off[t.n0] : 0, tot0 = t.table ? c->h_noff[t.n0] : 0;
+    t.off0.resize((size_t)n_new + 1); t.aoff.assign((size_t)n_new + 1, atotal0); t.noff.assign((size_t)n_new + 1, tot0);
+    for (int i = 0; i <= n_new; ++i) t.off0[i] = total0 + rel[i];
+    for (int i = 0; i < n_new && t.active; ++i) {
+        const int64_t T = rel[i + 1] - rel[i], Ta = tau == 1 ? T : (T + tau - 1) / tau;
+        if (Ta > 0x7fffffffLL) return fail(c, ACX_ERR_INVALID, std::string(who) + ": offsets: a track has more than 2^31 - 1 frames");
+        t.aoff[i + 1] = t.aoff[i] + Ta;
+        t.maxT = std::max<int>(t.maxT, (int)Ta);
+        if (t.table) {
+            const int Me = std::max<int>(0, (int)Ta - c->normtab_span);
+            t.maxM = std::max(t.maxM, Me);
+            t.noff[i + 1] = t.noff[i] + (int64_t)acx::NBIN * (Me + acx::NGUARD);
+        }
+    }
+    const int64_t atotal1 = t.aoff[n_new], tot1 = t.noff[n_new];
+    auto &cap = c->s09_cap;
+    int rc;
+    // tau = 1: the active pool IS the uploaded one.  The aliases follow each block at once, whether its call replaced it or failed
+    // (then it is the old block still), so that no return below leaves them on a freed block.
+    const bool alias = t.active && tau == 1;
+    rc = grow_keep(c, c->d_frames0, cap.frames0, (size_t)total0 * dim, (size_t)std::max<int64_t>(1, total1) * dim);
+    if (alias) c->d_frames = c->d_frames0;
+    if (rc != ACX_OK) return rc;
+    rc = grow_keep(c, c->d_toff0, cap.toff0, (size_t)t.n0 + 1, (size_t)t.n1 + 1);
+    if (alias) c->d_toff = c->d_toff0;
+    if (rc != ACX_OK) return rc;
+    if (dim == acx::NBIN && c->d_gch && (rc = grow_keep(c, c->d_gch, cap.gch, (size_t)t.n0 * acx::NBIN, (size_t)t.n1 * acx::NBIN)) != ACX_OK) return rc;
+    if (t.active && tau > 1) {
+        if ((rc = grow_keep(c, c->d_frames, cap.frames, (size_t)atotal0 * acx::NBIN, (size_t)std::max<int64_t>(1, atotal1) * acx::NBIN)) != ACX_OK) return rc;
+        if ((rc = grow_keep(c, c->d_toff, cap.toff, (size_t)t.n0 + 1, (size_t)t.n1 + 1)) != ACX_OK) return rc;
+    }
+    // The rotated pool, the f16 pool and the norm table are kept WITH the slack behind their end (zeros / +inf, which the band
+    // kernel's edge tiles of the last track read): a replaced block is then sealed as the old one was, and an append that fails
+    // before it has written behind the end -- a non-finite value under REJECT, a later allocation -- needs no seal.
+    if (t.active && c->d_frot &&
+        (rc = grow_keep(c, c->d_frot, cap.frot, (size_t)(atotal0 + 2 * POOL_SLACK) * acx::FROT, (size_t)(std::max<int64_t>(1, atotal1) + 2 * POOL_SLACK) * acx::FROT)) != ACX_OK)
+        return rc;
+    if (t.active && c->d_fh &&
+        (rc = grow_keep(c, c->d_fh, cap.fh, (size_t)(atotal0 + 2 * POOL_SLACK) * acx::FH, (size_t)(std::max<int64_t>(1, atotal1) + 2 * POOL_SLACK) * acx::FH)) != ACX_OK)
+        return rc;
+    if (t.table) {
+        if ((rc = grow_keep(c, c->d_normtab, cap.normtab, (size_t)(tot0 + 2 * POOL_SLACK), (size_t)(std::max<int64_t>(1, tot1) + 2 * POOL_SLACK))) != ACX_OK) return rc;
+        if ((rc = grow_keep(c, c->d_noff, cap.noff, (size_t)t.n0 + 1, (size_t)t.n1 + 1)) != ACX_OK) return rc;
+    }
+    ACX_HIP(c, hipMemcpyAsync(c->d_toff0 + t.n0, t.off0.data(), sizeof(int64_t) * (n_new + 1), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
+}
+
+// Step (3) for the derived data -- the new frames are in d_frames0 behind the pool's end, scanned -- and step (4).
+static int s09_append_derived(acx_ctx *c, const S09Tail &t)
+{
+    const int n_new = t.n1 - t.n0, tau = c->pool_tau;
+    if (c->dim == acx::NBIN && c->d_gch) {
+        hipLaunchKernelGGL(acx::chroma_profile_kernel, dim3((unsigned)((n_new + 15) / 16)), dim3(256), 0, c->stream,
+                           c->d_frames0, c->d_toff0 + t.n0, n_new, c->d_gch + (size_t)t.n0 * acx::NBIN);
+        ACX_HIP(c, hipGetLastError());
+    }
+    if (!t.active) return ACX_OK;
+    const int64_t a0 = t.aoff[0], a1 = t.aoff[n_new], nfr = a1 - a0;
+    if (tau > 1) {
+        ACX_HIP(c, hipMemcpyAsync(c->d_toff + t.n0, t.aoff.data(), sizeof(int64_t) * (n_new + 1), hipMemcpyHostToDevice, c->stream));
+        if (nfr > 0) {
+            hipLaunchKernelGGL(acx::decimate_kernel, dim3(n_new, (t.maxT * acx::NBIN + 255) / 256), dim3(256), 0, c->stream,
+                               c->d_frames0, c->d_toff0 + t.n0, c->d_toff + t.n0, c->d_frames, tau);
+            ACX_HIP(c, hipGetLastError());
+        }
+    }
+    const float *tail = c->d_frames + a0 * acx::NBIN;
+    if (c->d_frot) {
+        if (nfr > 0) {
+            hipLaunchKernelGGL(acx::rotpool_kernel, dim3((unsigned)std::min<int64_t>((nfr * acx::FROT + 255) / 256, 1 << 22)), dim3(256), 0, c->stream,
+                               tail, c->d_frot + (POOL_SLACK + a0) * acx::FROT, nfr);
+            ACX_HIP(c, hipGetLastError());
+        }
+        ACX_HIP(c, hipMemsetAsync(c->d_frot + (POOL_SLACK + a1) * acx::FROT, 0, sizeof(float) * POOL_SLACK * acx::FROT, c->stream));
+    }
+    if (c->d_fh) {
+        // ensure_f16pool's range check, on the new frames: they can only take the pool's largest magnitude UP, so the lower bound
+        // holds as it did (fh_base_n) and the upper one is theirs to break.  Beyond the range the operand pool is dropped, so that
+        // the next f16x2 call rebuilds it and refuses the pool in ensure_f16pool's own words.
+        unsigned h_m = 0u;
+        if (nfr > 0) {
+            DeviceBuffer<unsigned> d_m;
+            ACX_HIP(c, d_m.grow(1));
+            ACX_HIP(c, hipMemsetAsync(d_m, 0, sizeof(unsigned), c->stream));
+            hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)std::min<int64_t>((nfr * acx::NBIN + 255) / 256, 4096)), dim3(256), 0, c->stream,
+                               tail, nfr * acx::NBIN, d_m.get());
+            ACX_HIP(c, hipMemcpyAsync(&h_m, d_m, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        float mx;
+        memcpy(&mx, &h_m, sizeof(mx));
+        if (c->fh_base_n < 0 || !(mx <= 32768.0f)) {
+            ACX_HIP(c, hipFree(c->d_fh));
+            c->d_fh = nullptr; c->s09_cap.fh = 0; c->fh_base_n = -1;
+        } else {
+            ACX_HIP(c, hipMemsetAsync(c->d_fh + (POOL_SLACK + a0) * acx::FH, 0, sizeof(_Float16) * (size_t)(nfr + POOL_SLACK) * acx::FH, c->stream));
+            if (nfr > 0) {
+                hipLaunchKernelGGL(acx::rotpool_f16_kernel, dim3((unsigned)std::min<int64_t>((nfr * 12 + 255) / 256, 1 << 22)), dim3(256), 0, c->stream,
+                                   tail, c->d_fh + (POOL_SLACK + a0) * acx::FH, nfr);
+                ACX_HIP(c, hipGetLastError());
+            }
+        }
+    }
+    if (t.table) {
+        // +inf first: the new region with its guard entries, and the slack behind the new end
+        const int64_t tot0 = t.noff[0], tot1 = t.noff[n_new];
+        ACX_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(c->d_normtab + POOL_SLACK + tot0), 0x7f800000, (size_t)(tot1 - tot0 + POOL_SLACK), c->stream));
+        ACX_HIP(c, hipMemcpyAsync(c->d_noff + t.n0, t.noff.data(), sizeof(int64_t) * (n_new + 1), hipMemcpyHostToDevice, c->stream));
+        bool handled = true;
+        {
+            ProfScope ps(c, KS_NORMS, 0);
+#define ACX_CALL(M_) launch_normtab<M_>(c, t.maxM, c->normtab_span, t.n0, n_new)
+            ACX_M_SWITCH(c->normtab_m, ACX_CALL)
+#undef ACX_CALL
+        }
+        if (!handled) return fail(c, ACX_ERR_UNSUPPORTED, "serra09: this build of libacx has no band kernel for the norm table's m");
+        ACX_HIP(c, hipGetLastError());
+    }
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
+}
+
+static int s09_append_finish(acx_ctx *c, const S09Tail &t)
+{
+    const int n_new = t.n1 - t.n0;
+    const int rc = s09_append_derived(c, t);
+    if (rc != ACX_OK) {
+        const std::string first = c->err;
+        (void)s09_seal(c, t.noff[n_new]);
+        c->err = first;
+        return rc;
+    }
+    c->h_off0.insert(c->h_off0.end(), t.off0.begin() + 1, t.off0.end());
+    if (t.active) c->h_off.insert(c->h_off.end(), t.aoff.begin() + 1, t.aoff.end());
+    if (t.table) c->h_noff.insert(c->h_noff.end(), t.noff.begin() + 1, t.noff.end());
+    c->n_tracks = t.n1;
+    plan_forget(c);
+    drain_profile(c);
+    return ACX_OK;
+}
+
+int acx_pool_append(acx_ctx *c, const float *frames, const int64_t *offsets, int32_t n_new, int32_t dim)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!c->d_frames0) return fail(c, ACX_ERR_STATE, "pool_append: feature pool not uploaded (acx_upload_pool)");
+    if (!offsets) return fail(c, ACX_ERR_INVALID, "pool_append: offsets must not be NULL");
+    int rc;
+    if ((rc = append_check(c, "pool_append", frames, offsets, n_new, c->n_tracks)) != ACX_OK) return rc;
+    if (dim != c->dim) return fail(c, ACX_ERR_INVALID, "pool_append: dim is " + std::to_string(dim) + ", the pool's is " + std::to_string(c->dim));
+    ACX_HIP(c, hipSetDevice(c->device));
+    c->nf_zeroed = 0;
+    S09Tail t;
+    if ((rc = s09_append_begin(c, "pool_append", offsets, n_new, t)) != ACX_OK) return rc;
+    const int64_t total0 = t.off0[0], nfr = offsets[n_new];
+    if (nfr > 0) ACX_HIP(c, hipMemcpy(c->d_frames0 + total0 * dim, frames, sizeof(float) * nfr * dim, hipMemcpyHostToDevice));
+    // (track_of over the tail of d_toff0: the track is named by its index in the pool after the append)
+    if ((rc = scan_nonfinite(c, "pool_append", "frames", c->d_frames0 + total0 * dim, nfr * dim, dim, total0, c->d_toff0 + t.n0, n_new, false, t.n0)) != ACX_OK) return rc;
+    return s09_append_finish(c, t);
+}
+
+int acx_pool_append_raw(acx_ctx *c, const float *raw, const int64_t *raw_offsets, int32_t n_new, int32_t dim, int32_t fac,
+                        int64_t *pooled_offsets_out)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!c->d_frames0) return fail(c, ACX_ERR_STATE, "pool_append_raw: feature pool not uploaded (acx_upload_pool / acx_upload_raw_pool)");
+    if (!raw_offsets) return fail(c, ACX_ERR_INVALID, "pool_append_raw: raw_offsets must not be NULL");
+    int rc;
+    if ((rc = append_check(c, "pool_append_raw", raw, raw_offsets, n_new, c->n_tracks)) != ACX_OK) return rc;
+    if (dim != 12 || c->dim != 12) return fail(c, ACX_ERR_INVALID, "pool_append_raw: dim must be 12, and so must the pool's");
+    if (fac < 1) return fail(c, ACX_ERR_INVALID, "pool_append_raw: fac (the downsample factor) must be >= 1");
+    if (fac > acx::POOL_MAXFAC) return fail(c, ACX_ERR_UNSUPPORTED, "pool_append_raw: fac: downsample factors above 64 are not supported on the device");
+    ACX_HIP(c, hipSetDevice(c->device));
+    c->nf_zeroed = 0;
+    std::vector<int64_t> poff((size_t)n_new + 1, 0);
+    for (int i = 0; i < n_new; ++i) poff[i + 1] = poff[i] + (raw_offsets[i + 1] - raw_offsets[i] + fac - 1) / fac;
+    S09Tail t;
+    if ((rc = s09_append_begin(c, "pool_append_raw", poff.data(), n_new, t)) != ACX_OK) return rc;
+    const int64_t total0 = t.off0[0];
+    DeviceBuffer<int64_t> d_roff;
+    DeviceBuffer<float> d_raw;                       // staging of one slice of raw chroma; the medians go straight behind the pool's end
+    ACX_HIP(c, d_roff.grow((size_t)n_new + 1));
+    ACX_HIP(c, hipMemcpy(d_roff, raw_offsets, sizeof(int64_t) * (n_new + 1), hipMemcpyHostToDevice));
+    const int64_t budget = raw_slice_bytes(c);
+    rc = for_track_slices(
+        n_new, n_new, [&](int t0, int t1) { return (raw_offsets[t1] - raw_offsets[t0]) * 12 * (int64_t)sizeof(float) <= budget; },
+        [&](int t0, int t1) -> int {
+            const int64_t nraw = raw_offsets[t1] - raw_offsets[t0], npool = poff[t1] - poff[t0];
+            if (npool <= 0) return ACX_OK;
+            ACX_HIP(c, d_raw.grow((size_t)nraw * 12));
+            ACX_HIP(c, hipMemcpyAsync(d_raw, raw + raw_offsets[t0] * 12, sizeof(float) * nraw * 12, hipMemcpyHostToDevice, c->stream));
+            const int rcs = scan_nonfinite(c, "pool_append_raw", "raw chroma", d_raw.get(), nraw * 12, 12, raw_offsets[t0], d_roff.get(), n_new, false, t.n0);
+            if (rcs != ACX_OK) return rcs;
+            // pooled frames [p0, p1) of the pool after the append, found in the tail of d_toff0
+            const int64_t p0 = total0 + poff[t0], p1 = total0 + poff[t1];
+            hipLaunchKernelGGL(acx::pool_median_kernel, dim3((unsigned)((npool + acx::POOL_FPB - 1) / acx::POOL_FPB)), dim3(256), 0, c->stream,
+                               d_raw.get(), raw_offsets[t0], d_roff.get(), c->d_toff0 + t.n0, n_new, p0, p1, fac, c->d_frames0 + p0 * 12);
+            ACX_HIP(c, hipGetLastError());
+            ACX_HIP(c, hipStreamSynchronize(c->stream));     // (the next slice reuses d_raw)
+            return ACX_OK;
+        });
+    if (rc != ACX_OK) return rc;
+    if ((rc = s09_append_finish(c, t)) != ACX_OK) return rc;
+    if (pooled_offsets_out) memcpy(pooled_offsets_out, poff.data(), sizeof(int64_t) * (n_new + 1));
+    return ACX_OK;
+}
+
+static int s09_truncate(acx_ctx *c, int32_t n)
+{
+    quiesce(c);
+    const bool table = c->d_normtab && c->normtab_m > 0 && c->pool_tau >= 1;
+    const int64_t norm_hi = table ? c->h_noff[c->n_tracks] : 0;
+    c->n_tracks = n;
+    c->h_off0.resize((size_t)n + 1);
+    if (c->pool_tau >= 1) c->h_off.resize((size_t)n + 1);
+    if (table) c->h_noff.resize((size_t)n + 1);
+    // the f16x2 range check must still hold for the tracks that stay: it does while they contain the ones it was made for
+    if (c->d_fh && (c->fh_base_n < 0 || n < c->fh_base_n)) {
+        ACX_HIP(c, hipFree(c->d_fh));
+        c->d_fh = nullptr; c->s09_cap.fh = 0; c->fh_base_n = -1;
+    }
+    plan_forget(c);
+    return s09_seal(c, norm_hi);
+}
+
+// ---- f64 pool (SiMPle) ----
+
+int acx_pool_append_f64(acx_ctx *c, const double *frames, const int64_t *offsets, int32_t n_new, int32_t dim)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!c->d_frames64) return fail(c, ACX_ERR_STATE, "pool_append_f64: f64 feature pool not uploaded (acx_upload_pool_f64)");
+    if (!offsets) return fail(c, ACX_ERR_INVALID, "pool_append_f64: offsets must not be NULL");
+    int rc;
+    if ((rc = append_check(c, "pool_append_f64", frames, offsets, n_new, c->n_tracks64)) != ACX_OK) return rc;
+    if (dim != 12) return fail(c, ACX_ERR_INVALID, "pool_append_f64: dim must be 12");
+    ACX_HIP(c, hipSetDevice(c->device));
+    c->nf_zeroed = 0;
+    quiesce(c);
+    const int n0 = c->n_tracks64, n1 = n0 + n_new;
+    const int64_t total0 = c->h_off64[n0], nfr = offsets[n_new], total1 = total0 + nfr;
+    if ((rc = grow_keep(c, c->d_frames64, (size_t)total0 * 12, (size_t)std::max<int64_t>(1, total1) * 12)) != ACX_OK) return rc;
+    if ((rc = grow_keep(c, c->d_toff64, (size_t)n0 + 1, (size_t)n1 + 1)) != ACX_OK) return rc;
+    if ((rc = grow_keep(c, c->d_prof64, (size_t)n0 * 12, (size_t)n1 * 12)) != ACX_OK) return rc;
+    if (c->d_wn64 && (rc = grow_keep(c, c->d_wn64, (size_t)total0, (size_t)std::max<int64_t>(1, total1))) != ACX_OK) return rc;
+    std::vector<int64_t> abs;
+    if ((rc = append_offsets(c, c->d_toff64, n0, total0, offsets, n_new, abs)) != ACX_OK) return rc;
+    double *tail = c->d_frames64 + total0 * 12;
+    if (nfr > 0) ACX_HIP(c, hipMemcpy(tail, frames, sizeof(double) * nfr * 12, hipMemcpyHostToDevice));
+    if ((rc = scan_nonfinite(c, "pool_append_f64", "frames", tail, nfr * 12, 12, total0, c->d_toff64 + n0, n_new, false, n0)) != ACX_OK) return rc;
+    std::vector<double> cleaned;
+    if (c->nf_zeroed > 0) {                          // policy ZERO: the profile below sums what the device holds
+        cleaned.resize((size_t)nfr * 12);
+        ACX_HIP(c, hipMemcpy(cleaned.data(), tail, sizeof(double) * nfr * 12, hipMemcpyDeviceToHost));
+        frames = cleaned.data();
+    }
+    // per-track chroma profile, as the upload sums it
+    std::vector<double> prof((size_t)n_new * 12, 0.0);
+    int maxn = 1;
+    for (int t = 0; t < n_new; ++t) {
+        maxn = std::max<int>(maxn, (int)std::min<int64_t>(offsets[t + 1] - offsets[t], 0x7fffffff));
+        for (int64_t f = offsets[t]; f < offsets[t + 1]; ++f)
+            for (int b = 0; b < 12; ++b) prof[(size_t)t * 12 + b] += frames[f * 12 + b];
+    }
+    ACX_HIP(c, hipMemcpy(c->d_prof64 + (size_t)n0 * 12, prof.data(), sizeof(double) * prof.size(), hipMemcpyHostToDevice));
+    if (c->d_wn64 && c->wn64_L > 0) {
+        if (nfr > 0) ACX_HIP(c, hipMemsetAsync(c->d_wn64 + total0, 0, sizeof(double) * nfr, c->stream));
+        hipLaunchKernelGGL(acx::simple_winnorm_kernel, dim3(n_new, std::min(64, (maxn + 255) / 256)), dim3(256), 0, c->stream,
+                           c->d_frames64, c->d_toff64 + n0, c->d_wn64, c->wn64_L);
+        ACX_HIP(c, hipGetLastError());
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    c->h_off64.insert(c->h_off64.end(), abs.begin() + 1, abs.end());
+    c->n_tracks64 = n1;
+    plan_forget(c);
+    return ACX_OK;
+}
+
+// ---- EarlyFusion block features ----
+
+// The +32 rows of slack behind d_efn / d_efsc (a group of 16 is read at once), for a pool of nb rows
+static int ef_seal(acx_ctx *c, int64_t nb)
+{
+    for (int k = 0; k < 2; ++k)
+        if (c->d_efn[k]) ACX_HIP(c, hipMemsetAsync(c->d_efn[k] + nb, 0, sizeof(float) * 32, c->stream));
+    for (int k = 0; k < 3; ++k)
+        if (c->d_efsc[k]) ACX_HIP(c, hipMemsetAsync(c->d_efsc[k] + nb, 0, sizeof(float) * 32, c->stream));
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
+}
+
+int acx_ef_pool_append(acx_ctx *c, const float *mfccs, const float *ssms, const float *chromas, const double *chroma_med,
+                       const int64_t *offsets, int32_t n_new)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (c->ef_open) return fail(c, ACX_ERR_STATE, "ef_pool_append: a pool is still being filled (acx_ef_pool_end)");
+    if (!c->d_ef[0] || c->ef_ntracks <= 0) return fail(c, ACX_ERR_STATE, "ef_pool_append: block-feature pool not uploaded (acx_ef_upload_pool)");
+    if (!offsets) return fail(c, ACX_ERR_INVALID, "ef_pool_append: offsets must not be NULL");
+    if (!mfccs || !ssms || !chromas) return fail(c, ACX_ERR_INVALID, "ef_pool_append: mfccs, ssms and chromas must not be NULL");
+    int rc;
+    if ((rc = append_check(c, "ef_pool_append", chroma_med, offsets, n_new, c->ef_ntracks)) != ACX_OK) return rc;
+    ACX_HIP(c, hipSetDevice(c->device));
+    c->nf_zeroed = 0;
+    quiesce(c);
+    const int n0 = c->ef_ntracks, n1 = n0 + n_new, fmt = c->ef_split_fmt, nt = fmt == 1 ? 2 : 3;
+    const int64_t nb0 = c->h_efoff[n0], nbq = offsets[n_new], nb1 = nb0 + nbq;
+    const int32_t *dims = c->ef_dims;
+    auto &cap = c->ef_cap;
+    for (int k = 0; k < 3; ++k) {
+        if ((rc = grow_keep(c, c->d_ef[k], cap.ef[k], (size_t)nb0 * dims[k], (size_t)std::max<int64_t>(1, nb1) * dims[k])) != ACX_OK) return rc;
+        if (c->d_efs[k] && (rc = grow_keep(c, c->d_efs[k], cap.efs[k], (size_t)nb0 * 3 * c->ef_kp[k], (size_t)std::max<int64_t>(1, nb1) * 3 * c->ef_kp[k])) != ACX_OK) return rc;
+        // (kept with their 32 rows of slack: a failure before the row kernels below then leaves nothing to seal)
+        if (c->d_efsc[k] && (rc = grow_keep(c, c->d_efsc[k], cap.efsc[k], (size_t)nb0 + 32, (size_t)nb1 + 32)) != ACX_OK) return rc;
+        if (k < 2 && (rc = grow_keep(c, c->d_efn[k], cap.efn[k], (size_t)nb0 + 32, (size_t)nb1 + 32)) != ACX_OK) return rc;
+    }
+    if ((rc = grow_keep(c, c->d_efmed, cap.efmed, (size_t)12 * n0, (size_t)12 * n1)) != ACX_OK) return rc;
+    if ((rc = grow_keep(c, c->d_efoff, cap.efoff, (size_t)n0 + 1, (size_t)n1 + 1)) != ACX_OK) return rc;
+    std::vector<int64_t> abs;
+    if ((rc = append_offsets(c, c->d_efoff, n0, nb0, offsets, n_new, abs)) != ACX_OK) return rc;
+    const float *src[3] = {mfccs, ssms, chromas};
+    static const char *what[3] = {"mfcc blocks", "ssm blocks", "chroma blocks"};
+    for (int k = 0; k < 3; ++k) {
+        float *tail = c->d_ef[k] + nb0 * dims[k];
+        if (nbq > 0) ACX_HIP(c, hipMemcpy(tail, src[k], sizeof(float) * nbq * dims[k], hipMemcpyDefault));
+        if ((rc = scan_nonfinite(c, "ef_pool_append", what[k], tail, nbq * dims[k], dims[k], nb0, c->d_efoff + n0, n_new, false, n0)) != ACX_OK) return rc;
+    }
+    ACX_HIP(c, hipMemcpy(c->d_efmed + (size_t)12 * n0, chroma_med, sizeof(double) * 12 * n_new, hipMemcpyDefault));
+    if ((rc = scan_nonfinite<double>(c, "ef_pool_append", "chroma median", c->d_efmed + (size_t)12 * n0, (int64_t)12 * n_new, 12, 0, nullptr, n_new, false, n0)) != ACX_OK) return rc;
+    // norms, row scales and splits of rows [nb0, nb1): every one of these kernels works on a row by itself
+    rc = [&]() -> int {
+        if (nbq > 0) {
+            const unsigned g = (unsigned)((nbq + 3) / 4);
+            hipLaunchKernelGGL(acx::ef_rownorm_kernel, dim3(g), dim3(256), 0, c->stream, c->d_ef[2] + nb0 * dims[2], nbq, dims[2], 1, (float *)nullptr);
+            for (int k = 0; k < 2; ++k)
+                hipLaunchKernelGGL(acx::ef_rownorm_kernel, dim3(g), dim3(256), 0, c->stream, c->d_ef[k] + nb0 * dims[k], nbq, dims[k], 0, c->d_efn[k] + nb0);
+            ACX_HIP(c, hipGetLastError());
+            for (int k = 0; k < 3; ++k) {
+                if (c->ef_kp[k] == 0 || !c->d_efs[k]) continue;
+                if (fmt == 1)
+                    hipLaunchKernelGGL(acx::ef_rowscale_kernel, dim3(g), dim3(256), 0, c->stream, c->d_ef[k] + nb0 * dims[k], c->d_efsc[k] + nb0, nbq, dims[k]);
+                const int64_t nthr = nbq * c->ef_kp[k];
+                hipLaunchKernelGGL(acx::ef_split_bf16_kernel, dim3((unsigned)std::min<int64_t>((nthr + 255) / 256, 1 << 22)), dim3(256), 0, c->stream,
+                                   c->d_ef[k] + nb0 * dims[k], c->d_efs[k] + nb0 * nt * c->ef_kp[k], nbq, dims[k], c->ef_kp[k], k == 2 ? 1 : 0,
+                                   fmt == 1 ? c->d_efsc[k] + nb0 : (const float *)nullptr);
+                ACX_HIP(c, hipGetLastError());
+            }
+        }
+        return ef_seal(c, nb1);
+    }();
+    if (rc != ACX_OK) {
+        const std::string first = c->err;
+        (void)ef_seal(c, nb0);
+        c->err = first;
+        return rc;
+    }
+    c->h_efoff.insert(c->h_efoff.end(), abs.begin() + 1, abs.end());
+    c->ef_ntracks = n1;
+    plan_forget(c);
+    return ACX_OK;
+}
+
+// ---- FTM2D shingles ----
+
+int acx_ftm2d_append_shingles(acx_ctx *c, const double *shingles, int32_t n_new, int32_t dim)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (c->ftm_open) return fail(c, ACX_ERR_STATE, "ftm2d_append_shingles: a pool is still being filled (acx_ftm2d_pool_end)");
+    if (!c->d_ftm || c->ftm_n <= 0) return fail(c, ACX_ERR_STATE, "ftm2d_append_shingles: no shingle pool (acx_ftm2d_pool_* or acx_ftm2d_upload_shingles)");
+    int rc;
+    if ((rc = append_check(c, "ftm2d_append_shingles", shingles, nullptr, n_new, c->ftm_n)) != ACX_OK) return rc;
+    if (dim != c->ftm_dim) return fail(c, ACX_ERR_INVALID, "ftm2d_append_shingles: dim is " + std::to_string(dim) + ", the pool's is " + std::to_string(c->ftm_dim));
+    ACX_HIP(c, hipSetDevice(c->device));
+    quiesce(c);
+    const size_t keep = (size_t)c->ftm_n * dim, add = (size_t)n_new * dim;
+    if ((rc = grow_keep(c, c->d_ftm, c->ftm_cap, keep, keep + add)) != ACX_OK) return rc;
+    ACX_HIP(c, hipMemcpy(c->d_ftm + keep, shingles, sizeof(double) * add, hipMemcpyHostToDevice));
+    c->ftm_n += n_new;
+    plan_forget(c);
+    return ACX_OK;
+}
+
+int acx_pool_truncate(acx_ctx *c, int32_t algo, int32_t n_tracks)
+{
+    if (!c) return ACX_ERR_INVALID;
+    int n = 0;
+    switch (algo) {
+    case ACX_ALGO_SERRA09: case ACX_ALGO_CHENFUSION:
+        if (!c->d_frames0) return fail(c, ACX_ERR_STATE, "pool_truncate: feature pool not uploaded (acx_upload_pool)");
+        n = c->n_tracks; break;
+    case ACX_ALGO_SIMPLE:
+        if (!c->d_frames64) return fail(c, ACX_ERR_STATE, "pool_truncate: f64 feature pool not uploaded (acx_upload_pool_f64)");
+        n = c->n_tracks64; break;
+    case ACX_ALGO_EARLYFUSION:
+        if (!c->d_ef[0] || c->ef_open || c->ef_ntracks <= 0) return fail(c, ACX_ERR_STATE, "pool_truncate: no finished block-feature pool (acx_ef_upload_pool / acx_ef_pool_end)");
+        n = c->ef_ntracks; break;
+    case ACX_ALGO_FTM2D:
+        if (!c->d_ftm || c->ftm_open) return fail(c, ACX_ERR_STATE, "pool_truncate: no finished FTM2D shingle pool (acx_ftm2d_pool_end / acx_ftm2d_upload_shingles)");
+        n = c->ftm_n; break;
+    default: return fail(c, ACX_ERR_INVALID, "pool_truncate: algo: unknown algorithm");
+    }
+    if (n_tracks < 1 || n_tracks > n)
+        return fail(c, ACX_ERR_INVALID, "pool_truncate: n_tracks must be in 1.." + std::to_string(n) + " (got " + std::to_string(n_tracks) + ")");
+    if (n_tracks == n) return ACX_OK;
+    ACX_HIP(c, hipSetDevice(c->device));
+    switch (algo) {
+    case ACX_ALGO_SERRA09: case ACX_ALGO_CHENFUSION: return s09_truncate(c, n_tracks);
+    case ACX_ALGO_SIMPLE:
+        quiesce(c);
+        c->n_tracks64 = n_tracks;
+        c->h_off64.resize((size_t)n_tracks + 1);
+        break;
+    case ACX_ALGO_EARLYFUSION:
+        quiesce(c);
+        c->ef_ntracks = n_tracks;
+        c->h_efoff.resize((size_t)n_tracks + 1);
+        plan_forget(c);
+        return ef_seal(c, c->h_efoff.back());
+    default:
+        quiesce(c);
+        c->ftm_n = n_tracks;
+    }
+    plan_forget(c);
+    return ACX_OK;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -42,6 +42,8 @@ public:
         p_ = nullptr; cap_ = 0;
         return p;
     }
+    // takes over a block of `cap` elements that the caller allocated (the buffer must be empty)
+    void adopt(T *p, size_t cap) { p_ = p; cap_ = p ? cap : 0; }
     // a failed allocation leaves the buffer empty and HIP's sticky error cleared
     hipError_t grow(size_t need)
     {

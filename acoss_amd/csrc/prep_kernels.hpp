@@ -109,6 +109,34 @@ __global__ __launch_bounds__(256) void pool_median_kernel(const float *__restric
 }
 
 // ------------------------------------------------------------------------------------
+// P1b: the OTI's global chroma profile of `n_tracks` tracks (appends: the host loop of the upload, on the device).
+// toff holds n_tracks + 1 offsets into `pool`, gch receives 12 floats per track.  16 lanes per track, 12 of them
+// at work: lane b adds the frames' bin b one after the other in frame order (acc = acc + x: no reassociation, and
+// the build keeps contraction off), the 12 sums are compared in bin order for their maximum (first bin, then
+// `v > mx`), and every sum is divided by it when it is positive -- one correctly rounded f32 division (hipcc's
+// default for f32 `/`; the Makefile passes nothing that relaxes it).
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void chroma_profile_kernel(const float *__restrict__ pool, const int64_t *__restrict__ toff,
+                                                             int n_tracks, float *__restrict__ gch)
+{
+    const int bin = threadIdx.x & 15;
+    const int64_t track = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const bool live = track < n_tracks && bin < 12;
+    float acc = 0.0f;
+    if (live) {
+        const int64_t f1 = toff[track + 1];
+        for (int64_t f = toff[track]; f < f1; ++f) acc = acc + pool[f * 12 + bin];
+    }
+    const int base = threadIdx.x & 48;               // first lane of this track's group within the wave
+    float mx = __shfl(acc, base, 64);
+    for (int b = 1; b < 12; ++b) {
+        const float v = __shfl(acc, base + b, 64);
+        if (v > mx) mx = v;
+    }
+    if (live) gch[track * 12 + bin] = (mx > 0.0f) ? acc / mx : acc;
+}
+
+// ------------------------------------------------------------------------------------
 // P2: SiMPle features of one track per workgroup.  Stage 1: pooled[i][c] = mean of raw frames
 // [i skip, i skip + win) clipped to the track (f32, frames added one after the other in time
 // order, then divided by the count -- numpy's reduction order for this strided axis), kept in

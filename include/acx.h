@@ -707,6 +707,48 @@ int acx_query_ranks(acx_ctx *ctx, const acx_query_spec *spec, const void *params
                     const double *col, const int32_t *posn, const int64_t *moff, const int32_t *mates, int32_t *out_pos,
                     uint8_t *out_flag);
 
+/* ---- appends: tracks behind an uploaded pool, and away again ------------- */
+
+/*
+ * The query calls above take their queries from the uploaded pool.  A track the collection does not hold is put BEHIND the
+ * pool -- O(new tracks) work, the collection stays where it is --, asked about as queries n_old .. n_old + n_new - 1 against
+ * the candidates [0, n_old), and taken away again with acx_pool_truncate.
+ *
+ * The rule: after an upload and ANY sequence of appends and truncates, every later call (pairs, debug entry points,
+ * acx_pool_lengths, acx_download_pool*, the pair grid, the query calls) returns the bits it returns after ONE upload of the
+ * same final track list, for every parameter set.  Data derived from the pool (the active copy for tau > 1, the rotated and
+ * f16 operand pools, the norm table, window norms, row norms, row scales and splits) is extended for the new tracks only.
+ *
+ * Arguments are those of the upload call of the same pool; `offsets` (n_new + 1 entries) are relative to the appended
+ * tracks, offsets[0] == 0.  A pool block that is too small is replaced by one of max(need, 1.5 x its capacity) and keeps the
+ * capacity afterwards, so append -> query -> truncate in a loop allocates nothing after the first round.  Errors, all found
+ * before the pool is changed -- unlike an upload, a failed append leaves the pool exactly as it was: no pool of that kind, or
+ * an EarlyFusion / FTM2D pool still open: ACX_ERR_STATE; n_new < 1, offsets that do not start at 0 or decrease, dim / dims
+ * other than the pool's, more than 2^31 - 1 tracks in all: ACX_ERR_INVALID naming the argument; a failed allocation:
+ * ACX_ERR_NOMEM; a non-finite value: as in the upload (acx_set_nonfinite_policy), the track named by its index in the pool
+ * AFTER the append; acx_nonfinite_zeroed counts the values the last upload OR append zeroed.
+ *   acx_pool_append            pooled f32 frames behind the pool of acx_upload_pool / acx_upload_raw_pool
+ *   acx_pool_append_raw        raw chroma: block medians of `fac` frames written straight behind the pool's end, the OTI's
+ *                              chroma profile summed on the device (same bits as the upload's host loop); pooled_offsets_out
+ *                              (n_new + 1 entries, may be NULL) receives the new tracks' relative pooled offsets
+ *   acx_pool_append_f64        SiMPle features behind the pool of acx_upload_pool_f64
+ *   acx_ef_pool_append         block features of n_new tracks behind a finished EarlyFusion pool.  The call takes no dims: rows
+ *                              have the widths the pool was begun / uploaded with, and offsets[n_new] rows of exactly those
+ *                              widths are read from each array.  THE WIDTHS ARE THE CALLER'S RESPONSIBILITY: the library
+ *                              cannot check them, and narrower rows make it read past the end of the host arrays
+ *   acx_ftm2d_append_shingles  (n_new, dim) f64 shingles behind a finished FTM2D pool; dim = the pool's
+ *   acx_pool_truncate          keep the first n_tracks tracks of the pool of `algo` (ACX_ALGO_*; Serra09 and ChenFusion share
+ *                              one), 1 <= n_tracks <= the current count (equal: nothing happens); the capacity is kept
+ */
+int acx_pool_append(acx_ctx *ctx, const float *frames, const int64_t *offsets, int32_t n_new, int32_t dim);
+int acx_pool_append_raw(acx_ctx *ctx, const float *raw, const int64_t *raw_offsets, int32_t n_new, int32_t dim, int32_t fac,
+                        int64_t *pooled_offsets_out);
+int acx_pool_append_f64(acx_ctx *ctx, const double *frames, const int64_t *offsets, int32_t n_new, int32_t dim);
+int acx_ef_pool_append(acx_ctx *ctx, const float *mfccs, const float *ssms, const float *chromas, const double *chroma_med,
+                       const int64_t *offsets, int32_t n_new);
+int acx_ftm2d_append_shingles(acx_ctx *ctx, const double *shingles, int32_t n_new, int32_t dim);
+int acx_pool_truncate(acx_ctx *ctx, int32_t algo, int32_t n_tracks);
+
 /* ---- multi-GPU inside the library: RCCL over xGMI, no Python ------------- */
 
 /*
