@@ -36,7 +36,7 @@ EXPORTS = [
     "acx_ftm2d_default_params", "acx_ftm2d_pool_begin", "acx_ftm2d_pool_tracks", "acx_ftm2d_pool_end",
     "acx_ftm2d_upload_shingles", "acx_ftm2d_download_shingles", "acx_ftm2d_debug_track", "acx_ftm2d_pairs",
     "acx_rank_columns", "acx_topk_rows",
-    "acx_query_scores", "acx_query_topk", "acx_query_ranks",
+    "acx_query_scores", "acx_query_topk", "acx_query_ranks", "acx_query_topk_lists",
     "acx_serra09_debug_bits", "acx_serra09_plan", "acx_serra09_family_name",
     "acx_pool_append", "acx_pool_append_raw", "acx_pool_append_f64", "acx_ef_pool_append", "acx_ftm2d_append_shingles",
     "acx_pool_truncate",
@@ -274,6 +274,7 @@ def load():
     qp = ctypes.POINTER(QuerySpec)
     L.acx_query_scores.argtypes = [vp, qp, vp, ip, ctypes.c_int32, dp, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64]
     L.acx_query_topk.argtypes = [vp, qp, vp, ip, ctypes.c_int32, ip, ctypes.c_int32, dp, ctypes.c_int32, ip, fp]
+    L.acx_query_topk_lists.argtypes = [vp, qp, vp, ip, ctypes.c_int32, ip, ctypes.c_int32, dp, ctypes.c_int32, ip, fp]
     L.acx_query_ranks.argtypes = [vp, qp, vp, ip, ctypes.c_int32, dp, ip, lp, ip, ip, ctypes.POINTER(ctypes.c_uint8)]
     L.acx_pool_append.argtypes = [vp, fp, lp, ctypes.c_int32, ctypes.c_int32]
     L.acx_pool_append_raw.argtypes = [vp, fp, lp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, lp]
@@ -1134,6 +1135,24 @@ class Context(object):
         self._check(self._L.acx_query_topk(self._h, ctypes.byref(spec), _params_ptr(params), _iptr(queries), len(queries),
                                            cptr, 0 if cands is None else len(cands), None if col is None else _dptr(col), k,
                                            _iptr(idx), _fptr(score)))
+        return idx, score
+
+    def query_topk_lists(self, algo, symmetric, params, queries, lists, k, col=None, col_mode=0):
+        """acx_query_topk_lists: query_topk with a candidate list PER QUERY -- (idx (Q, planes, k) int32, score (Q, planes, k)
+        float32).  lists: (Q, L) integers, a track index or -1 (an empty slot) per entry, any order, no track twice in a
+        row; the query's own track is skipped.  Row i is query_topk(queries[i:i + 1], candidates=sorted valid entries of
+        lists[i]) in indices and score bits; only the listed cells are computed."""
+        spec, queries, col = self._query_args(algo, symmetric, queries, col, col_mode)
+        w = GRID_PLANES[int(algo)]
+        k = int(k)
+        lists = np.ascontiguousarray(lists, dtype=np.int32)
+        if lists.ndim != 2 or lists.shape[0] != len(queries):
+            raise ValueError("query_topk_lists: lists must be (len(queries), L) = (%d, L), got shape %s" % (len(queries), lists.shape))
+        idx = np.full((len(queries), w, max(k, 0)), -1, np.int32)
+        score = np.full((len(queries), w, max(k, 0)), np.nan, np.float32)
+        self._check(self._L.acx_query_topk_lists(self._h, ctypes.byref(spec), _params_ptr(params), _iptr(queries), len(queries),
+                                                 _iptr(lists), lists.shape[1], None if col is None else _dptr(col), k,
+                                                 _iptr(idx), _fptr(score)))
         return idx, score
 
     def query_ranks(self, algo, symmetric, params, queries, moff, mates, posn=None, col=None, col_mode=0):

@@ -432,6 +432,78 @@ class CoverAlgorithm(object):
         planes = list(self._identify_planes)
         return {t: np.ascontiguousarray(rows[planes.index(t)][:, :N]) for t in types}
 
+    # ------------------------------------------------------------------ reranking: a shortlist per query
+    def _check_shortlists(self, who, shortlists, Q):
+        """The shortlists of rerank() / rerank_tracks() without touching the library: a (Q, L) integer array, or a
+        sequence of Q integer sequences of any lengths -- padded with -1 behind their last entry --, every entry a track
+        of the collection in [0, N) or -1 (an empty slot), no track twice in a row.  -> (Q, L) int32."""
+        lists = shortlists_to_array(who, shortlists)
+        if lists.shape[0] != Q:
+            raise ValueError("%s: shortlists must hold one row per query (%d), got %d" % (who, Q, lists.shape[0]))
+        if lists.size and (lists.min() < -1 or lists.max() >= self.N):
+            raise ValueError("%s: shortlist entries must be track indices in [0, %d) or -1" % (who, self.N))
+        srt = np.sort(lists, axis=1)
+        dup = (srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)
+        if dup.any():
+            r, j = np.argwhere(dup)[0]
+            raise ValueError("%s: shortlists row %d lists track %d twice" % (who, r, srt[r, j + 1]))
+        return lists.astype(np.int32)
+
+    def _by_type(self, idx, score, types):
+        planes = list(self._identify_planes)
+        return {t: (np.ascontiguousarray(idx[:, planes.index(t)]), np.ascontiguousarray(score[:, planes.index(t)])) for t in types}
+
+    def rerank(self, queries, shortlists, k=10, similarity_types=None):
+        """identify() with a shortlist PER QUERY: the second stage of a cascade, whose first stage (a cheap index) left
+        every query a few hundred candidates.  shortlists: a (Q, L) integer array, or a sequence of Q integer sequences
+        of any lengths (padded with -1); an entry is a track index or -1, an empty slot; the order within a row is free,
+        no track twice in a row; a query's own track is skipped.  Returns what identify() returns, and row i holds
+        exactly identify([queries[i]], k, candidates=sorted(valid entries of shortlists[i])): only the Q x L listed cells
+        are computed (acx_query_topk_lists), in bands that are not limited to 128 rows.  `Ds` is not written.  Not a
+        collective."""
+        q, types = self._query_setup("rerank", queries, similarity_types)
+        k = int(k)
+        if k < 1:
+            raise ValueError("rerank: k must be >= 1 (got %d)" % k)
+        lists = self._check_shortlists("rerank", shortlists, len(q))
+        ctx, algo, params, mode, col = self._query_call()
+        idx, score = ctx.query_topk_lists(algo, self._identify_symmetric, params, q, lists, k, col=col, col_mode=mode)
+        return self._by_type(idx, score, types)
+
+    def identify_cascade(self, first, queries, k=10, shortlist=200, first_type=None, similarity_types=None):
+        """Two stages: `first` -- another device-backed algorithm object over the SAME collection, the cheap one (FTM2D) --
+        shortlists `shortlist` (1 .. 1024) tracks per query by its similarity type `first_type` (None: its first plane),
+        and this object reranks them: self.rerank(queries, first.identify(queries, k=shortlist)[first_type][0], k)."""
+        if getattr(first, "N", None) != self.N:
+            raise ValueError("identify_cascade: first holds %s tracks, this collection %d" % (getattr(first, "N", None), self.N))
+        shortlist = int(shortlist)
+        if shortlist < 1 or shortlist > 1024:
+            raise ValueError("identify_cascade: shortlist must be in 1..1024 (got %d)" % shortlist)
+        k = int(k)
+        if k < 1:
+            raise ValueError("identify_cascade: k must be >= 1 (got %d)" % k)
+        q, _ = self._query_setup("identify_cascade", queries, similarity_types)
+        first_type = first._identify_planes[0] if first_type is None else first_type
+        first._query_setup("identify_cascade", q, [first_type])
+        lists = first.identify(q, k=shortlist, similarity_types=[first_type])[first_type][0]
+        return self.rerank(q, lists, k=k, similarity_types=similarity_types)
+
+    def rerank_tracks(self, tracks, shortlists, k=10, similarity_types=None):
+        """rerank() for tracks the collection does NOT hold (tracks as identify_tracks() takes them): they are appended
+        behind the uploaded pool, asked about as queries N .. N + Q - 1 with their shortlists -- entries in [0, N) or
+        -1 --, and taken away again; `Ds`, N, the cliques and the pool are as identify_tracks() leaves them."""
+        return self._rerank_tracks(tracks, shortlists, k, similarity_types)
+
+    def _rerank_tracks(self, tracks, shortlists, k, similarity_types, **how):
+        k = int(k)
+        if k < 1:
+            raise ValueError("rerank_tracks: k must be >= 1 (got %d)" % k)
+        checked, Q, types, _ = self._tracks_setup("rerank_tracks", tracks, similarity_types, None, how)
+        lists = self._check_shortlists("rerank_tracks", shortlists, Q)
+        idx, score = self._with_appended(checked, Q, lambda ctx, algo, params, mode, col, q: ctx.query_topk_lists(
+            algo, self._identify_symmetric, params, q, lists, k, col=col, col_mode=mode))
+        return self._by_type(idx, score, types)
+
     def evaluate(self, queries=None, similarity_types=None, topsidx=[1, 10, 100, 1000], report=False, info=None, row_block=1024):
         """MR, MRR, MDR, MAP and Top-k of a query set against the collection without an N x N matrix:
         {type: (MR, MRR, MDR, MAP, tops)} for the similarity types the device computes (similarity_types: a subset,
@@ -551,6 +623,30 @@ class CoverAlgorithm(object):
             for t in tops:
                 fout.write(", %.3g" % t)
             fout.write("\n")
+
+
+def shortlists_to_array(who, shortlists):
+    """The shortlists of rerank() as one (Q, L) int64 array: a 2-D integer array as it is; a sequence of Q integer
+    sequences of any lengths with every row padded with -1 (an empty slot) to the longest, L = 0 when all are empty."""
+    if isinstance(shortlists, np.ndarray):
+        if shortlists.ndim != 2:
+            raise ValueError("%s: a shortlist array must be (Q, L), got shape %s" % (who, shortlists.shape))
+        if shortlists.size and not np.issubdtype(shortlists.dtype, np.integer):
+            raise ValueError("%s: shortlists must hold integer track indices" % who)
+        return shortlists.astype(np.int64)
+    try:
+        rows = [np.asarray(r) for r in shortlists]
+    except TypeError:
+        raise ValueError("%s: shortlists must be a (Q, L) array or a sequence of sequences" % who)
+    for i, r in enumerate(rows):
+        if r.ndim != 1:
+            raise ValueError("%s: shortlists[%d] must be a flat sequence of track indices, got shape %s" % (who, i, r.shape))
+        if r.size and not np.issubdtype(r.dtype, np.integer):
+            raise ValueError("%s: shortlists must hold integer track indices (row %d)" % (who, i))
+    out = np.full((len(rows), max([len(r) for r in rows], default=0)), -1, np.int64)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = r
+    return out
 
 
 def _clique_order(cliques):

@@ -166,6 +166,10 @@ class Serra09(CoverAlgorithm):
     def score_tracks(self, tracks, similarity_types=None, raw=False):
         return self._score_tracks(tracks, similarity_types, raw=raw)
 
+    def rerank_tracks(self, tracks, shortlists, k=10, similarity_types=None, raw=False):
+        """CoverAlgorithm.rerank_tracks; tracks and raw as in identify_tracks."""
+        return self._rerank_tracks(tracks, shortlists, k, similarity_types, raw=raw)
+
     def _check_tracks(self, who, tracks, raw=False):
         """tracks: pooled (T, 12) f32 chroma as set_pooled_features takes it, or with raw=True raw (T0, 12) chroma, pooled
         by downsample_fac on the device (on the host, here, by pool_median above 64).

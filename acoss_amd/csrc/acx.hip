@@ -48,7 +48,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -135,6 +135,7 @@ struct acx_ctx {
     bool rank_attr = false;
     bool query_attr = false;                          // query_topk_kernel's dynamic LDS limit is raised (acx_query_topk)
     bool query_rank_attr = false;                     // query_rank_kernel's (acx_query_ranks)
+    bool query_lists_attr = false;                    // query_topk_lists_kernel's (acx_query_topk_lists)
     // multi-GPU inside the library (acx_comm_*): one RCCL communicator rank per context
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -177,7 +178,8 @@ struct acx_ctx {
                              {"simple_kernel", 0, 0, 0}, {"ef_gemm_kernel", 0, 0, 0}, {"ef_rowstat_kernel", 0, 0, 0},
                              {"ef_fuse_kernel", 0, 0, 0}, {"sw_kernel", 0, 0, 0}, {"rank_columns_kernel", 0, 0, 0},
                              {"topk_rows_kernel", 0, 0, 0}, {"ftm2d_tile_kernel", 0, 0, 0}, {"query_rows_kernel", 0, 0, 0},
-                             {"query_topk_kernel", 0, 0, 0}, {"query_rank_kernel", 0, 0, 0}};
+                             {"query_topk_kernel", 0, 0, 0}, {"query_rank_kernel", 0, 0, 0}, {"query_topk_lists_kernel", 0, 0, 0},
+                             {"ftm2d_pairs_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
     // Appends (acx_pool_append & co.): capacity in elements of every raw-pointer pool block that an append has grown.  0 = the block
@@ -4371,6 +4373,179 @@ int acx_query_ranks(acx_ctx *c, const acx_query_spec *spec, const void *params, 
                 ACX_HIP(c, hipMemcpyAsync(out_flag + (size_t)r0 * Q.w, d_flag, (size_t)nr * Q.w, hipMemcpyDeviceToHost, c->stream));
                 return ACX_OK;
             });
+    });
+}
+
+// ---- list bands: every query brings its own candidate list (acx_query_topk_lists) ------------------------------
+// A list band is R query rows x L list positions x planes floats (slab[(r L + j) W + e]): only the listed cells exist.
+// Its rows are not capped at QUERY_BAND_ROWS -- that cap makes a dense EarlyFusion rectangle of R x 128 tracks, and with
+// lists of a few hundred entries it would hand Serra09 a fraction of one 65535-pair batch per band.  A band is bounded by
+// memory (half of the scratch limit, as every band) and by QUERY_LIST_BAND_CELLS cells: four full Serra09 batches, so
+// that the two result slots of run_serra09 overlap within a band, while the host's pair list and destinations of a band
+// stay at 4 MB.  A design parameter: no measurement rests on it.
+static const int64_t QUERY_LIST_BAND_CELLS = (int64_t)1 << 18;
+
+// Everything acx_query_topk_lists checks of its lists, before anything is allocated or launched.
+static int query_check_lists(acx_ctx *c, const char *who, int n, int32_t n_queries, const int32_t *lists, int32_t list_len)
+{
+    const std::string w(who);
+    if (list_len < 0) return fail(c, ACX_ERR_INVALID, w + ": list_len must be >= 0 (got " + std::to_string(list_len) + ")");
+    if (n_queries > 0 && list_len > 0 && !lists) return fail(c, ACX_ERR_INVALID, w + ": lists must not be NULL when list_len > 0");
+    std::vector<std::pair<int32_t, int32_t>> seen;
+    for (int32_t i = 0; i < n_queries; ++i) {
+        const int32_t *row = lists + (size_t)i * list_len;
+        seen.clear();
+        for (int32_t j = 0; j < list_len; ++j) {
+            if (row[j] < -1 || row[j] >= n)
+                return fail(c, ACX_ERR_INVALID, w + ": lists[" + std::to_string(i) + "][" + std::to_string(j) + "] = " + std::to_string(row[j]) +
+                                                    " is neither a track in [0, " + std::to_string(n) + ") nor -1");
+            if (row[j] >= 0) seen.push_back({row[j], j});
+        }
+        std::sort(seen.begin(), seen.end());
+        for (size_t s = 1; s < seen.size(); ++s)
+            if (seen[s].first == seen[s - 1].first)
+                return fail(c, ACX_ERR_INVALID, w + ": lists row " + std::to_string(i) + " holds track " + std::to_string(seen[s].first) +
+                                                    " twice (positions " + std::to_string(seen[s - 1].second) + " and " + std::to_string(seen[s].second) + ")");
+    }
+    return ACX_OK;
+}
+
+// The cells of a list band -- rows q[0 .. nr) with their lists -- as pairs and slab destinations.  Cell (r, j) with
+// c = lists[r][j], c >= 0, c != q[r] is the pair (min, max) of a symmetric call, (q, c) of an ordered one; a pair two rows
+// want is computed twice.  The cells are enumerated grouped by the pair's second track (then by its first): neighbouring
+// pairs share a track (what simple_kernel wants), and the queries of one work share shortlist entries.  No pair kernel's
+// score depends on its place in the list.
+static void query_list_pairs(const int32_t *q, int nr, const int32_t *lists, int L, int w, int symmetric, std::vector<int32_t> &pairs,
+                             std::vector<int64_t> &idx)
+{
+    struct Cell { int32_t a, b; int64_t at; };
+    std::vector<Cell> cells;
+    for (int r = 0; r < nr; ++r)
+        for (int j = 0; j < L; ++j) {
+            const int32_t cnd = lists[(size_t)r * L + j];
+            if (cnd < 0 || cnd == q[r]) continue;
+            const bool swap = symmetric && cnd < q[r];
+            cells.push_back({swap ? cnd : q[r], swap ? q[r] : cnd, ((int64_t)r * L + j) * w});
+        }
+    std::sort(cells.begin(), cells.end(), [](const Cell &x, const Cell &y) {
+        return x.b != y.b ? x.b < y.b : x.a != y.a ? x.a < y.a : x.at < y.at;
+    });
+    pairs.resize(2 * cells.size()); idx.resize(cells.size());
+    for (size_t k = 0; k < cells.size(); ++k) { pairs[2 * k] = cells[k].a; pairs[2 * k + 1] = cells[k].b; idx[k] = cells[k].at; }
+}
+
+// FTM2D over a pair list whose scores stay on the device: ftm2d_pairs_kernel as acx_ftm2d_pairs launches it (the same
+// accumulation, the same bits), then the scatter of the grid path.
+static int run_ftm2d_list(acx_ctx *c, const int32_t *pairs, const int64_t *idx, int64_t K, float *d_scores)
+{
+    const int64_t CH = (int64_t)1 << 22;
+    int rc;
+    if ((rc = ensure(c, c->d_pairs, (size_t)2 * std::min(K, CH))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_out, (size_t)std::min(K, CH))) != ACX_OK) return rc;
+    for (int64_t k0 = 0; k0 < K; k0 += CH) {
+        const int64_t n = std::min(CH, K - k0);
+        ACX_HIP(c, hipMemcpyAsync(c->d_pairs, pairs + 2 * k0, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
+        if ((rc = stage_idx(c, idx + k0, n)) != ACX_OK) return rc;
+        {
+            ProfScope ps(c, KS_FTMPAIRS, n);
+            hipLaunchKernelGGL(acx::ftm2d_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_ftm, c->ftm_dim,
+                               c->d_pairs, n, c->d_out);
+        }
+        hipLaunchKernelGGL(scatter_scores_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_out, c->d_idx, d_scores, (int)n, 1);
+        ACX_LAUNCHES_OK(c);
+        ACX_HIP(c, hipStreamSynchronize(c->stream));      // (the pinned staging of the destinations is reused by the next chunk)
+    }
+    return ACX_OK;
+}
+
+// One list band through the pair kernels: on return every listed cell's score lies in d_slab.
+static int query_run_list_band(acx_ctx *c, const QueryCall &Q, const int32_t *q, int nr, const int32_t *lists, int L, float *d_slab,
+                               int64_t band_bytes, std::vector<int32_t> &pairs, std::vector<int64_t> &idx)
+{
+    if (L > 0) ACX_HIP(c, hipMemsetAsync(d_slab, 0, sizeof(float) * (size_t)nr * L * Q.w, c->stream));
+    query_list_pairs(q, nr, lists, L, Q.w, Q.symmetric, pairs, idx);
+    const int64_t K = (int64_t)idx.size();
+    int rc = ACX_OK;
+    if (K == 0) {
+    } else if (Q.algo == ACX_ALGO_FTM2D) {
+        rc = run_ftm2d_list(c, pairs.data(), idx.data(), K, d_slab);
+    } else if (Q.algo == ACX_ALGO_SIMPLE) {
+        rc = run_simple_list(c, pairs.data(), idx.data(), K, *static_cast<const acx_simple_params *>(Q.params), d_slab);
+    } else {
+        // a limit the caller set covers the band too: the pair kernels batch within what the band leaves of it
+        const int64_t saved = c->scratch_limit;
+        if (saved > 0) c->scratch_limit = std::max<int64_t>(1, saved - band_bytes);
+        DevDst dd{d_slab, idx.data()};
+        if (Q.algo == ACX_ALGO_EARLYFUSION)
+            rc = run_ef(c, pairs.data(), K, *static_cast<const acx_ef_params *>(Q.params), nullptr, nullptr, nullptr, 0, 0, &dd);
+        else
+            rc = run_serra09(c, pairs.data(), K, *static_cast<const acx_serra09_params *>(Q.params), nullptr, nullptr,
+                             Q.algo == ACX_ALGO_CHENFUSION, &dd);
+        c->scratch_limit = saved;
+    }
+    if (rc != ACX_OK) return rc;
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
+}
+
+int acx_query_topk_lists(acx_ctx *c, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
+                         const int32_t *lists, int32_t list_len, const double *col, int32_t k, int32_t *out_idx, float *out_score)
+{
+    if (!c) return ACX_ERR_INVALID;
+    QueryCall Q;
+    int rc = query_check(c, "query_topk_lists", spec, params, queries, n_queries, nullptr, 0, col, Q);
+    if (rc != ACX_OK) return rc;
+    if ((rc = rank_check_k(c, "query_topk_lists", k, n_queries, out_idx, out_score)) != ACX_OK) return rc;
+    if ((rc = query_check_lists(c, "query_topk_lists", Q.n, n_queries, lists, list_len)) != ACX_OK) return rc;
+    if (n_queries == 0) return ACX_OK;
+    const int L = list_len;
+    const int64_t per_row = (int64_t)L * Q.w * 4 + 8 * (int64_t)Q.w * k;        // the slab row and its results
+    const int64_t half = scratch_limit_bytes(c) / 2;
+    if (half < per_row)
+        return fail(c, ACX_ERR_NOMEM, "query_topk_lists: one query row (" + std::to_string(per_row) + " bytes of scores and results) does not fit half of the scratch limit");
+    const int R = (int)std::min<int64_t>(std::min<int64_t>(n_queries, half / per_row), std::max<int64_t>(1, QUERY_LIST_BAND_CELLS / std::max(L, 1)));
+    ACX_HIP(c, hipSetDevice(c->device));
+    if (!c->query_lists_attr) {
+        ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::query_topk_lists_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       4 * acx::RANK_ROW_LDS + 12 * acx::RANK_KMAX + acx::RANK_SELECT_LDS_FIXED + 16));
+        c->query_lists_attr = true;
+    }
+    int P = 4;
+    while (P < std::min<int>(k, L)) P <<= 1;
+    // slab | col | queries | lists | the band's results (indices, scores)
+    const size_t slab_floats = (size_t)R * L * Q.w, res = (size_t)R * Q.w * k, nl = (size_t)n_queries * L;
+    const size_t o_col = (slab_floats * 4 + 7) & ~(size_t)7, o_q = o_col + (col ? 8 * (size_t)Q.n : 0), o_l = o_q + 4 * (size_t)n_queries,
+                 o_res = o_l + 4 * nl, total = o_res + 8 * res;
+    return with_device_block(c, "query_topk_lists", total, [&](char *d_mem) -> int {
+        float *d_slab = reinterpret_cast<float *>(d_mem);
+        const double *d_col = col ? reinterpret_cast<const double *>(d_mem + o_col) : nullptr;
+        int32_t *d_q = reinterpret_cast<int32_t *>(d_mem + o_q);
+        const int32_t *d_l = reinterpret_cast<const int32_t *>(d_mem + o_l);
+        int32_t *d_idx = reinterpret_cast<int32_t *>(d_mem + o_res);
+        float *d_sc = reinterpret_cast<float *>(d_idx + res);
+        if (col) ACX_HIP(c, hipMemcpyAsync(d_mem + o_col, col, 8 * (size_t)Q.n, hipMemcpyHostToDevice, c->stream));
+        ACX_HIP(c, hipMemcpyAsync(d_q, queries, 4 * (size_t)n_queries, hipMemcpyHostToDevice, c->stream));
+        if (nl > 0) ACX_HIP(c, hipMemcpyAsync(d_mem + o_l, lists, 4 * nl, hipMemcpyHostToDevice, c->stream));
+        const bool in_lds = L <= acx::RANK_ROW_LDS;
+        const size_t lds = 12 * (size_t)P + acx::RANK_SELECT_LDS_FIXED + 16 + (in_lds ? 4 * (size_t)L : 0);
+        std::vector<int32_t> pairs;
+        std::vector<int64_t> idx;
+        for (int r0 = 0; r0 < n_queries; r0 += R) {
+            const int nr = std::min(R, n_queries - r0);
+            int rc2 = query_run_list_band(c, Q, queries + r0, nr, lists + (size_t)r0 * L, L, d_slab, (int64_t)R * per_row, pairs, idx);
+            if (rc2 != ACX_OK) return rc2;
+            {
+                ProfScope ps(c, KS_QTOPKL, (int64_t)nr * L * Q.w);
+                ACX_LAUNCH_IN_LDS(query_topk_lists_kernel, in_lds, dim3((unsigned)nr, (unsigned)Q.w), lds, d_slab, L, Q.w, d_q + r0, d_l + (size_t)r0 * L,
+                                  d_col, Q.mode, (int)k, P, d_idx, d_sc);
+            }
+            ACX_LAUNCHES_OK(c);
+            const size_t nres = (size_t)nr * Q.w * k;
+            ACX_HIP(c, hipMemcpyAsync(out_idx + (size_t)r0 * Q.w * k, d_idx, 4 * nres, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(out_score + (size_t)r0 * Q.w * k, d_sc, 4 * nres, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        return ACX_OK;
     });
 }
 

@@ -22,6 +22,10 @@
 //                           comparison counts it); a NaN or a -inf anywhere else flags the (row, plane) and its positions
 //                           are -1.  Up to RANK_ROW_LDS tracks keep their finished values in LDS; more are re-read -- and
 //                           re-finished, the same operations on the same bits -- per pass.
+//   Q4  query_topk_lists_kernel   Q2 for a band whose rows each bring their own candidate list (acx_query_topk_lists): the
+//                           slab is R x L x W by list position, candidates are positions, empty slots and the own
+//                           track are skipped and the valid entries are counted.  Up to RANK_ROW_LDS positions keep
+//                           their finished values in LDS; more are re-read and re-finished per pass.
 // Every store is a plain C++ store.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -124,6 +128,66 @@ __global__ __launch_bounds__(RANK_THREADS) void query_rank_kernel(const float *_
         [&](int q) { return IN_LDS ? lrow4[q] : make_float4(value_of(4 * q), value_of(4 * q + 1), value_of(4 * q + 2), value_of(4 * q + 3)); },
         value_of, posn, mates, moff[r] - mate_base, moff[r + 1] - mate_base, out_pos + (int64_t)e * plane_stride,
         out_flag + (int64_t)r * W + e);
+}
+
+// Q4.  grid: (R, W).  The band of acx_query_topk_lists: every row has its OWN candidate list, lists[r L .. r L + L) --
+// tracks in any order, -1 = an empty slot, no track twice (checked by the host) --, and the slab is laid out by list
+// POSITION: slab[(r L + j) W + e] = plane e of the pair {query r, lists[r L + j]}.  Candidate j is position j; empty slots
+// and the row's own track take no part.  The select carries the POSITION where the other kernels carry the column (the
+// key holds the track: rank_key64(value, track), the order of Q2), so that a listed track's score is read back at its
+// position and nothing here is N wide.
+// out_idx / out_score: R x W x k.  P = the power of two >= max(4, min(k, L)) (<= RANK_KMAX).
+// Dynamic LDS: 12 P + RANK_SELECT_LDS_FIXED + 16 (the count of a row's valid entries) + IN_LDS ? 4 L : 0.
+template <bool IN_LDS>
+__global__ __launch_bounds__(RANK_THREADS) void query_topk_lists_kernel(const float *__restrict__ slab, int L, int W,
+                                                                         const int32_t *__restrict__ self_of,
+                                                                         const int32_t *__restrict__ lists,
+                                                                         const double *__restrict__ col, int mode, int k, int P,
+                                                                         int32_t *__restrict__ out_idx, float *__restrict__ out_score)
+{
+    extern __shared__ float4 rank_lds4[];
+    int *cnt = reinterpret_cast<int *>(rank_select_row(rank_lds4, P));      // 16 bytes in front of the row: the valid entries
+    float *lrow = reinterpret_cast<float *>(cnt + 4);
+    const int r = blockIdx.x, e = blockIdx.y, tid = threadIdx.x;
+    const float *row = slab + (int64_t)r * L * W + e;
+    const int32_t *list = lists + (int64_t)r * L;
+    const int self = self_of[r];
+    // query_value's bits with ONE division for both col_modes (a single path through the re-finishing of a pass)
+    auto value_at = [&](int j, int c) {
+        const float s = row[(int64_t)j * W];
+        if (mode == 0) return s;
+        const double d = col[c];
+        const float q = (float)((mode == 1 ? (double)s : d) / (mode == 1 ? d : (double)s));
+        return mode == 1 ? q : -q;
+    };
+    if (tid == 0) *cnt = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int j = tid; j < L; j += RANK_THREADS) {
+        const int c = list[j];
+        if (c < 0 || c == self) continue;
+        ++mine;
+        if (IN_LDS) lrow[j] = value_at(j, c);
+    }
+    mine = rank_wave_sum(mine);
+    if ((tid & 63) == 0 && mine) atomicAdd(cnt, mine);
+    __syncthreads();
+    const int nvalid = *cnt;                              // candidates there are to list: counted, a list may hold any number
+    rank_select_sort(rank_lds4, L, nvalid, k, P, [&](int j, int &pos, uint64_t &key) {
+        const int c = list[j];
+        if (c < 0 || c == self) return false;
+        pos = j;
+        key = rank_key64(IN_LDS ? lrow[j] : value_at(j, c), (uint32_t)c);    // (no track twice in a row: the keys are distinct)
+        return true;
+    });
+    const int32_t *spos = rank_select_columns(rank_lds4, P);
+    const int64_t o = ((int64_t)r * W + e) * k;
+    for (int p = tid; p < k; p += RANK_THREADS) {
+        const int j = p < P ? spos[p] : -1;
+        const int c = j >= 0 ? list[j] : -1;
+        out_idx[o + p] = c;
+        out_score[o + p] = j >= 0 ? value_at(j, c) : __builtin_nanf("");
+    }
 }
 
 }  // namespace acx

@@ -707,6 +707,26 @@ int acx_query_ranks(acx_ctx *ctx, const acx_query_spec *spec, const void *params
                     const double *col, const int32_t *posn, const int64_t *moff, const int32_t *mates, int32_t *out_pos,
                     uint8_t *out_flag);
 
+/* Reranking: a candidate list PER QUERY -- the second stage of a cascade, whose first stage (a cheap index, acx_query_topk
+ * with FTM2D) left every query its own shortlist.  lists: n_queries x list_len int32, row-major; lists[i * list_len + j] is
+ * a track in [0, n_tracks) or -1, an empty slot at any position; the entries of a row may be in any order.  A query's own
+ * track may be listed and is skipped.  A track listed twice in one row is ACX_ERR_INVALID (the message names the row and
+ * both positions); duplicate queries with different lists are fine.
+ *   values   raw score, orientation (`symmetric`), col_mode, order, ties, NaN / -inf, k <= 1024 and the -1 / NaN tail are
+ *            those of acx_query_topk: row i holds exactly what acx_query_topk(queries = {queries[i]}, cands = the valid
+ *            entries of row i, sorted) returns, in indices and score bits
+ *   band     rows x list_len x planes floats, laid out by list position -- only the listed cells are computed, a pair two
+ *            rows want is computed twice.  Memory per row: 4 list_len planes + 8 planes k bytes within half of
+ *            acx_set_scratch_limit (one row that does not fit: ACX_ERR_NOMEM); the rows of a band are bounded by that and
+ *            by 2^18 cells, not by 128
+ *   errors   the whole argument list is validated before anything is allocated or launched: the common rules above, k,
+ *            then the lists (list_len >= 0, lists not NULL when list_len > 0, every entry a track or -1, no track twice
+ *            in a row); a failure after that (a listed track shorter than the delay-embedding stack ...) leaves nothing
+ *            in flight
+ * list_len == 0 or a row of empty slots: all -1 / NaN.  n_queries == 0: ACX_OK. */
+int acx_query_topk_lists(acx_ctx *ctx, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
+                         const int32_t *lists, int32_t list_len, const double *col, int32_t k, int32_t *out_idx, float *out_score);
+
 /* ---- appends: tracks behind an uploaded pool, and away again ------------- */
 
 /*
