@@ -40,6 +40,7 @@ EXPORTS = [
     "acx_serra09_debug_bits", "acx_serra09_plan", "acx_serra09_family_name",
     "acx_pool_append", "acx_pool_append_raw", "acx_pool_append_f64", "acx_ef_pool_append", "acx_ftm2d_append_shingles",
     "acx_pool_truncate",
+    "acx_serra09_align", "acx_qmax_locate_binary",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -50,6 +51,10 @@ GRID_PLANES = {ALGO_SERRA09: 1, ALGO_CHENFUSION: 2, ALGO_SIMPLE: 1, ALGO_EARLYFU
 
 class AcxError(RuntimeError):
     """A libacx call failed (HIP error, missing device, out of device memory ...)."""
+
+
+# acx_alignment (include/acx.h): max Q, the path's start (q0, r0) and end (q1, r1) in plot rows / columns; -1: no match
+ALIGNMENT_DTYPE = np.dtype([("score", np.float32), ("q0", np.int32), ("r0", np.int32), ("q1", np.int32), ("r1", np.int32)])
 
 
 class EfParams(ctypes.Structure):
@@ -247,6 +252,8 @@ def load():
                                      ctypes.POINTER(ctypes.c_void_p)]
     L.acx_csm_binary_sw.argtypes = [vp, fp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, fp]
     L.acx_qmax_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, pp, fp]
+    L.acx_serra09_align.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.c_void_p]
+    L.acx_qmax_locate_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, pp, ctypes.c_void_p]
     epp = ctypes.POINTER(EfPrepParams)
     L.acx_ef_block_features.argtypes = [vp, fp, ctypes.c_int64, fp, ctypes.c_int64, ctypes.c_int32, lp, ctypes.c_int32, epp,
                                         fp, fp, fp, dp]
@@ -902,6 +909,27 @@ class Context(object):
         self._check(self._L.acx_qmax_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                                             R.shape[0], R.shape[1], ctypes.byref(p), ctypes.byref(score)))
         return float(score.value)
+
+    def serra09_align(self, pairs, params=None):
+        """WHERE the Qmax alignment of every (query, reference) pair lies (acx_serra09_align): a (K,) structured array
+        (ALIGNMENT_DTYPE) -- score = what serra09_pairs returns, (q0, r0) the start and (q1, r1) the end of the path in
+        embedded frames (rows / columns of the recurrence plot); a pair without a match: score 0 and -1 four times."""
+        p = params or serra09_params()
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
+        self._check(self._L.acx_serra09_align(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), out.ctypes.data))
+        return out
+
+    def qmax_locate_binary(self, R, params=None):
+        """The same for a given binary (M, N) cross recurrence plot (acx_qmax_locate_binary): a (1,) structured array."""
+        p = params or serra09_params()
+        R = np.ascontiguousarray(R, dtype=np.uint8)
+        if R.ndim != 2:
+            raise ValueError("qmax_locate_binary: R must be (M, N), got shape %s" % (R.shape,))
+        out = np.zeros(1, ALIGNMENT_DTYPE)
+        self._check(self._L.acx_qmax_locate_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                                   R.shape[0], R.shape[1], ctypes.byref(p), out.ctypes.data))
+        return out
 
     # ------------------------------------------------------------------ FTM2D
     def ftm2d_pool_begin(self, n_tracks, pwr=1.96, win=75, c=5):

@@ -206,6 +206,77 @@ class Serra09(CoverAlgorithm):
         for key in self.Ds.keys():
             self.Ds[key][idxs[:, 0], idxs[:, 1]] = scores
 
+    # ------------------------------------------------------------------ where the alignment lies
+    # align() / align_matches(): acx_alignment's fields and the spans in POOLED frames, [first, last] inclusive
+    ALIGN_DTYPE = np.dtype(_lib.ALIGNMENT_DTYPE.descr + [("q_span", np.int32, (2,)), ("r_span", np.int32, (2,))])
+
+    def _check_align(self, who, idxs):
+        if self._engine.get("dmax"):
+            raise ValueError("%s: the Qmax alignment only (engine dmax must be 0)" % who)
+        a = np.asarray(idxs)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("%s: track indices must be integers, got dtype %s" % (who, a.dtype))
+        return a
+
+    def _align_pairs(self, pairs):
+        """(K, 2) checked int32 pairs -> (K,) ALIGN_DTYPE."""
+        out = np.zeros(len(pairs), self.ALIGN_DTYPE)
+        out["score"] = 0.0
+        for f in ("q0", "r0", "q1", "r1", "q_span", "r_span"):
+            out[f] = -1
+        if len(pairs) == 0:
+            return out
+        al = self._context().serra09_align(pairs, self._params())
+        for f in _lib.ALIGNMENT_DTYPE.names:
+            out[f] = al[f]
+        hit = al["q0"] >= 0
+        T = self._pooled_lengths()
+        tau, m = int(self.tau), int(self.m)
+        for side, col in (("q", 0), ("r", 1)):
+            last = T[pairs[:, col]] - 1
+            span = np.stack([tau * al[side + "0"].astype(np.int64), np.minimum(tau * (al[side + "1"].astype(np.int64) + m - 1), last)], axis=1)
+            out[side + "_span"][hit] = span[hit]
+        return out
+
+    def align(self, idxs):
+        """WHERE in the two recordings does the Qmax alignment lie?  idxs: (K, 2) (query, reference) track indices over
+        the uploaded collection.  Returns a (K,) structured array: score (the value similarity() stores, before
+        normalize_by_length), the path's start (q0, r0) and end (q1, r1) in EMBEDDED frames -- rows (query) and columns
+        (reference) of the cross recurrence plot; the end is the row-major first maximum of Qmax, the start is found by
+        following the recursion's predecessors back (include/acx.h acx_alignment) -- and q_span / r_span, [first, last]
+        inclusive in POOLED frames of each track.  The device decimates the pooled track by tau and embeds it with stride
+        1 (DESIGN.md sections 2 and 3: the stack at base frame e tau holds frames (e + k) tau, k < m), so embedded frame e
+        covers pooled frames tau e .. tau (e + m - 1) and a span is [tau q0, tau (q1 + m - 1)], clipped to the track.  A pair
+        without a match (score 0) has -1 everywhere.  `Ds` is not written; not a collective."""
+        a = self._check_align("align", idxs)
+        if a.size == 0:
+            a = a.reshape(0, 2)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("align: idxs must be (K, 2) (query, reference) track indices, got shape %s" % (a.shape,))
+        if a.size and (a.min() < 0 or a.max() >= self.N):
+            raise ValueError("align: idxs must be track indices in [0, %d)" % self.N)
+        return self._align_pairs(np.ascontiguousarray(a, dtype=np.int32))
+
+    def align_matches(self, queries, indices):
+        """align() for the hits of identify() / rerank(): queries (Q,) track indices, indices the (Q, k) int array
+        either returned (-1: an empty slot).  Returns a (Q, k) structured array as align() does, row i slot s being the
+        alignment of (queries[i], indices[i, s]); an empty slot comes back as a no-match row."""
+        q = self._check_align("align_matches", queries).reshape(-1)
+        idx = self._check_align("align_matches", indices)
+        if idx.ndim != 2 or idx.shape[0] != len(q):
+            raise ValueError("align_matches: indices must be (Q, k) with one row per query (%d), got shape %s" % (len(q), idx.shape))
+        if q.size and (q.min() < 0 or q.max() >= self.N):
+            raise ValueError("align_matches: queries must be track indices in [0, %d)" % self.N)
+        if idx.size and (idx.min() < -1 or idx.max() >= self.N):
+            raise ValueError("align_matches: indices must be track indices in [0, %d) or -1" % self.N)
+        out = np.zeros(idx.shape, self.ALIGN_DTYPE)
+        for f in ("q0", "r0", "q1", "r1", "q_span", "r_span"):
+            out[f] = -1
+        rows, slots = np.nonzero(idx >= 0)
+        pairs = np.stack([q[rows], idx[rows, slots]], axis=1).astype(np.int32).reshape(-1, 2)
+        out[rows, slots] = self._align_pairs(np.ascontiguousarray(pairs))
+        return out
+
     def normalize_by_length(self):
         """Non-symmetric normalisation: D[i, j] /= sqrt(T_j), T_j the pooled length
         (rqa_serra09.py:71-83; the reciprocal of the paper's distance, so larger = closer)."""

@@ -20,6 +20,7 @@
 #include "../../include/acx.h"
 #include "serra09_kernels.hpp"
 #include "serra09_long_kernels.hpp"
+#include "serra09_locate_kernels.hpp"
 #include "prep_kernels.hpp"
 #include "snf_kernels.hpp"
 #include "simple_kernels.hpp"
@@ -48,7 +49,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -71,6 +72,12 @@ struct Serra09Slot {
     bool on_q = false;                               // its alignment sweeps run on the context's second stream
     int B = 0, w = 1;
     int64_t k0 = 0;
+    // acx_serra09_align: the batch's records instead of scores, and where each pair's strip seam records start in d_seam
+    DeviceBuffer<acx_alignment> d_al;
+    PinnedBuffer<acx_alignment> h_al;
+    std::vector<int64_t> seam_off;
+    DeviceBuffer<int64_t> d_seam_off;
+    bool al = false;
 };
 
 }  // namespace
@@ -159,6 +166,7 @@ struct acx_ctx {
     Serra09Slot slot[2];
     DeviceBuffer<float> d_out;
     DeviceBuffer<unsigned long long> d_bits;              // recurrence bitmaps (u64 words)
+    DeviceBuffer<acx::LocSeam> d_seam;                    // qmax_locate_kernel's strip seam records (pairs wider than one strip only)
     int64_t scratch_limit = 0;                            // bytes
     size_t total_mem = 0;
     // the pair grid: last plan (a pure function of lengths and spec; sorting 10^4 tiles per call is what the cache saves)
@@ -179,7 +187,7 @@ struct acx_ctx {
                              {"ef_fuse_kernel", 0, 0, 0}, {"sw_kernel", 0, 0, 0}, {"rank_columns_kernel", 0, 0, 0},
                              {"topk_rows_kernel", 0, 0, 0}, {"ftm2d_tile_kernel", 0, 0, 0}, {"query_rows_kernel", 0, 0, 0},
                              {"query_topk_kernel", 0, 0, 0}, {"query_rank_kernel", 0, 0, 0}, {"query_topk_lists_kernel", 0, 0, 0},
-                             {"ftm2d_pairs_kernel", 0, 0, 0}};
+                             {"ftm2d_pairs_kernel", 0, 0, 0}, {"qmax_locate_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
     // Appends (acx_pool_append & co.): capacity in elements of every raw-pointer pool block that an append has grown.  0 = the block
@@ -535,11 +543,12 @@ int64_t scratch_limit_bytes(const acx_ctx *c)
 
 // Results of one batch come back through a pinned staging slot; two slots, so that the host packs
 // batch b + 1 (descriptors, size classes) while the device works on batch b.
-int collect_slot(acx_ctx *c, Serra09Slot &s, float *out)
+int collect_slot(acx_ctx *c, Serra09Slot &s, float *out, acx_alignment *al = nullptr)
 {
     if (!s.busy) return ACX_OK;
     ACX_HIP(c, hipEventSynchronize(s.done));
-    for (int k2 = 0; out && k2 < s.B; ++k2)
+    for (int k2 = 0; s.al && al && k2 < s.B; ++k2) al[s.k0 + s.perm[k2]] = s.h_al[(size_t)k2];
+    for (int k2 = 0; !s.al && out && k2 < s.B; ++k2)
         for (int e = 0; e < s.w; ++e) out[(size_t)s.w * (s.k0 + s.perm[k2]) + e] = s.h_out[(size_t)s.w * k2 + e];
     s.busy = false;
     drain_profile(c);
@@ -665,6 +674,17 @@ void launch_qmax_sweep(hipStream_t st, const PairDesc *pd, int B, const unsigned
 #undef ACX_QB3
 }
 
+// The locating sweep (serra09_locate_kernels.hpp) over the recurrence bitmaps of B pairs, one wave per pair of any shape: pair k's
+// record goes to dst[k]; seam_off[k] = first of its strip seam records in `seam` (read for pairs wider than one strip only).
+void launch_qmax_locate(hipStream_t st, const PairDesc *pd, int B, const unsigned long long *bits, acx::LocSeam *seam, const int64_t *seam_off,
+                        acx_alignment *dst, float gamma_o, float gamma_e, int dp_start)
+{
+    if (gamma_o == gamma_e)
+        hipLaunchKernelGGL((acx::qmax_locate_kernel<true>), dim3(B), dim3(64), 0, st, pd, bits, seam, seam_off, dst, gamma_o, gamma_e, dp_start);
+    else
+        hipLaunchKernelGGL((acx::qmax_locate_kernel<false>), dim3(B), dim3(64), 0, st, pd, bits, seam, seam_off, dst, gamma_o, gamma_e, dp_start);
+}
+
 // The streaming class (a side beyond the last band class, or m > MAX_M) up to its recurrence bitmap, on the main stream: `B` pairs
 // whose descriptors are `dpd` on the device and `pd` on the host, spanning `e`.
 void launch_streaming_class(acx_ctx *c, const PairDesc *dpd, const PairDesc *pd, int B, const acx::Serra09Extent &e, const acx_serra09_params &p)
@@ -687,19 +707,20 @@ void launch_streaming_class(acx_ctx *c, const PairDesc *dpd, const PairDesc *pd,
 }
 
 int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
-                     const DebugOut *dbg, bool both, const DevDst *dd);
+                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al);
 
-// Runs the chain over `K` pairs in scratch-sized batches.
+// Runs the chain over `K` pairs in scratch-sized batches.  `al` (acx_serra09_align): the sweep is qmax_locate_kernel and pair k's
+// record goes to al[k]; no scores are written.
 int run_serra09(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
-                const DebugOut *dbg, bool both = false, const DevDst *dd = nullptr)
+                const DebugOut *dbg, bool both = false, const DevDst *dd = nullptr, acx_alignment *al = nullptr)
 {
-    const int rc = run_serra09_impl(c, pairs, K, p_in, out, dbg, both, dd);
+    const int rc = run_serra09_impl(c, pairs, K, p_in, out, dbg, both, dd, al);
     if (rc != ACX_OK) quiesce(c);                // (c->err keeps the first failure's text)
     return rc;
 }
 
 int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
-                     const DebugOut *dbg, bool both, const DevDst *dd)
+                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al)
 {
     if (!c->d_frames0) return fail(c, ACX_ERR_STATE, "serra09: feature pool not uploaded (acx_upload_pool)");
     if (c->dim != acx::NBIN) return fail(c, ACX_ERR_INVALID, "serra09: pool dim must be 12");
@@ -714,6 +735,15 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
     constexpr int NC = acx::SERRA09_NC;          // band size classes; class NC: the streaming kernels
     const int w = both ? 2 : 1;
     if ((rc = validate_serra09_pairs(c, len, pairs, K, p, dbg != nullptr, limit_floats)) != ACX_OK) return rc;
+    if (al) {      // the path start of a cell is ONE u32, row * Mr + column (the scratch limit refuses such a pair long before)
+        PairDesc d;
+        acx::Serra09Need need;
+        for (int64_t k = 0; k < K; ++k) {
+            (void)acx::serra09_size_pair(len, pairs[2 * k], pairs[2 * k + 1], p, false, d, need);
+            if ((int64_t)d.Mq * d.Mr + acx::LOC_STRIP >= ((int64_t)1 << 32))      // (+ a strip: the wave indexes the columns right of the matrix too)
+                return fail(c, ACX_ERR_UNSUPPORTED, "serra09_align: pair " + std::to_string(k) + " has 2^32 cells or more");
+        }
+    }
     for (int s = 0; s < 2; ++s) {
         if (!c->slot[s].done) ACX_HIP(c, hipEventCreateWithFlags(&c->slot[s].done, hipEventDisableTiming));
         // (a slot is never marked free without its work being waited for: a failed call drains the streams, quiesce())
@@ -723,7 +753,7 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
     int64_t k0 = 0;
     for (int batch = 0; k0 < K; ++batch) {
         Serra09Slot &S = c->slot[batch & 1];
-        if ((rc = collect_slot(c, S, out)) != ACX_OK) return rc;
+        if ((rc = collect_slot(c, S, out, al)) != ACX_OK) return rc;
         // the plan of the batch (serra09_plan.hpp): its pairs and their arena offsets, then the sort by size-class key --
         // `S.perm[k]` = position in the batch of sorted pair k
         std::vector<PairDesc> &pd = S.pd;
@@ -745,6 +775,16 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         if ((rc = ensure(c, S.d_out, (size_t)2 * B)) != ACX_OK) return rc;
         if ((rc = ensure(c, S.h_out, (size_t)2 * B)) != ACX_OK) return rc;
         ACX_HIP(c, hipMemcpyAsync(S.d_pd, pd.data(), sizeof(PairDesc) * B, hipMemcpyHostToDevice, c->stream));
+        if (al) {     // the locating sweep's records, and the seam records of the batch's pairs wider than one strip
+            int64_t seams = 0;
+            S.seam_off.resize((size_t)B);
+            for (int k2 = 0; k2 < B; ++k2) { S.seam_off[(size_t)k2] = seams; seams += acx::loc_seam_records(pd[k2].Mq, pd[k2].Mr, p.dp_start); }
+            if ((rc = ensure(c, S.d_al, (size_t)B)) != ACX_OK) return rc;
+            if ((rc = ensure(c, S.h_al, (size_t)B)) != ACX_OK) return rc;
+            if ((rc = ensure(c, S.d_seam_off, (size_t)B)) != ACX_OK) return rc;
+            if ((rc = ensure(c, c->d_seam, (size_t)std::max<int64_t>(seams, 1))) != ACX_OK) return rc;
+            ACX_HIP(c, hipMemcpyAsync(S.d_seam_off, S.seam_off.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, c->stream));
+        }
         if (dd) {     // destinations of the batch's scores (staged here: the scatter may run on the second stream)
             if ((rc = ensure(c, S.h_idx, (size_t)B)) != ACX_OK) return rc;
             if ((rc = ensure(c, S.d_idx, (size_t)B)) != ACX_OK) return rc;
@@ -759,7 +799,8 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         // Not for batches with long pairs (their sweep's strip records live in the shared scratch), the debug entry point, or while
         // the per-kernel event clocks are on (acx_profile_enable: a kernel's time is then its time ALONE, not beside another launch).
         // (ACX_QMAX_STREAM=0 keeps them on the main stream.)
-        const bool use_q = acx::serra09_switches().qstream && !dbg && !c->prof && cls_begin[NC + 1] == cls_begin[NC];
+        // (nor for acx_serra09_align: one seam buffer serves both slots, and its lists are thousands of pairs, not millions)
+        const bool use_q = acx::serra09_switches().qstream && !dbg && !al && !c->prof && cls_begin[NC + 1] == cls_begin[NC];
         if (use_q && !c->qstream) ACX_HIP(c, hipStreamCreateWithFlags(&c->qstream, hipStreamNonBlocking));
         if (use_q && both && !c->qstream2) {
             ACX_HIP(c, hipStreamCreateWithFlags(&c->qstream2, hipStreamNonBlocking));
@@ -822,7 +863,10 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
                                       sw.cols, sw.pack);
                 }
             };
-            if (both && use_q) {      // the two alignments of a pair read the same bitmap and write different halves of d_out: side by side
+            if (al) {                 // WHERE the alignment lies: one launch for the batch, every class the same kernel
+                ProfScope ps(c, KS_LOCATE, acx::serra09_extent(pd, 0, B).cells, qs);
+                launch_qmax_locate(qs, S.d_pd, B, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, p.gamma_o, p.gamma_e, p.dp_start);
+            } else if (both && use_q) {      // the two alignments of a pair read the same bitmap and write different halves of d_out: side by side
                 sweep(false, S.d_out, qs);
                 sweep(true, S.d_out + 1, c->qstream2);
                 ACX_HIP(c, hipEventRecord(c->q2_done, c->qstream2));
@@ -832,7 +876,9 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
             ACX_HIP(c, wait_err);
         }
         ACX_LAUNCHES_OK(c);
-        if (dd) {
+        if (al) {
+            ACX_HIP(c, hipMemcpyAsync(S.h_al, S.d_al, sizeof(acx_alignment) * B, hipMemcpyDeviceToHost, qs));
+        } else if (dd) {
             hipLaunchKernelGGL(scatter_scores_kernel, dim3((B + 255) / 256), dim3(256), 0, qs,
                                S.d_out, S.d_idx, dd->base, B, w);
             ACX_HIP(c, hipGetLastError());
@@ -840,7 +886,7 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
             ACX_HIP(c, hipMemcpyAsync(S.h_out, S.d_out, sizeof(float) * B * w, hipMemcpyDeviceToHost, qs));
         }
         ACX_HIP(c, hipEventRecord(S.done, qs));
-        S.busy = true; S.on_q = use_q; S.B = B; S.w = w; S.k0 = k0;
+        S.busy = true; S.on_q = use_q; S.B = B; S.w = w; S.k0 = k0; S.al = al != nullptr;
 
         if (dbg && B >= 1) {
             if ((rc = collect_slot(c, S, out)) != ACX_OK) return rc;
@@ -860,7 +906,7 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         k0 = k;
     }
     for (int s = 0; s < 2; ++s)
-        if ((rc = collect_slot(c, c->slot[s], out)) != ACX_OK) return rc;
+        if ((rc = collect_slot(c, c->slot[s], out, al)) != ACX_OK) return rc;
     return ACX_OK;
 }
 
@@ -1908,6 +1954,57 @@ int acx_qmax_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const ac
                       params->dmax != 0, acx::serra09_sweep(acx::serra09_row_class(std::max(M, N))).cols, 1);
     ACX_HIP(c, hipGetLastError());
     ACX_HIP(c, hipMemcpyAsync(score, S.d_out, sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
+}
+
+int acx_serra09_align(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, acx_alignment *out)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (K < 0 || (K > 0 && (!pairs || !out)) || !params) return fail(c, ACX_ERR_INVALID, "serra09_align: bad argument");
+    if (params->dmax != 0) return fail(c, ACX_ERR_UNSUPPORTED, "serra09_align: the Qmax alignment only (params->dmax must be 0)");
+    if (K == 0) return ACX_OK;
+    return run_serra09(c, pairs, K, *params, nullptr, nullptr, false, nullptr, out);
+}
+
+int acx_qmax_locate_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!R || !params || !out || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "qmax_locate_binary: bad argument");
+    if (params->dmax != 0) return fail(c, ACX_ERR_UNSUPPORTED, "qmax_locate_binary: the Qmax alignment only (params->dmax must be 0)");
+    if (params->dp_start != 2 && params->dp_start != 3) return fail(c, ACX_ERR_INVALID, "qmax_locate_binary: dp_start must be 2 or 3");
+    if (!(params->gamma_o >= 0.0f) || !(params->gamma_e >= 0.0f)) return fail(c, ACX_ERR_INVALID, "qmax_locate_binary: gammas must be >= 0");
+    if ((int64_t)M * N + acx::LOC_STRIP >= ((int64_t)1 << 32)) return fail(c, ACX_ERR_UNSUPPORTED, "qmax_locate_binary: the plot has 2^32 cells or more");
+    ACX_HIP(c, hipSetDevice(c->device));
+    // the recurrence plot in the pipeline's bitmap layout (acx_qmax_binary): word t of row i = columns [64 t - 7 + (i & 7), +64)
+    PairDesc d;
+    memset(&d, 0, sizeof(d));
+    d.Mq = M; d.Mr = N; d.Tq = M; d.Tr = N;
+    d.pitchD = round_up(N, 64); d.pitchT = 0;
+    d.nw = acx::serra09_tiles(N);
+    std::vector<unsigned long long> words((size_t)M * d.nw, 0ull);
+    for (int i = 0; i < M; ++i) {
+        const int c0 = (i & (acx::BAND - 1)) - (acx::BAND - 1);
+        for (int j = 0; j < N; ++j) {
+            const uint8_t v = R[(size_t)i * N + j];
+            if (v > 1) return fail(c, ACX_ERR_INVALID, "qmax_locate_binary: non-binary elements found in input");
+            if (v) { const int pos = j - c0; words[(size_t)i * d.nw + (pos >> 6)] |= 1ull << (pos & 63); }
+        }
+    }
+    int rc;
+    Serra09Slot &S = c->slot[0];
+    const int64_t seam_off = 0;
+    if ((rc = ensure(c, c->d_bits, words.size())) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_seam, (size_t)std::max<int64_t>(acx::loc_seam_records(M, N, params->dp_start), 1))) != ACX_OK) return rc;
+    if ((rc = ensure(c, S.d_pd, (size_t)1)) != ACX_OK) return rc;
+    if ((rc = ensure(c, S.d_al, (size_t)1)) != ACX_OK) return rc;
+    if ((rc = ensure(c, S.d_seam_off, (size_t)1)) != ACX_OK) return rc;
+    ACX_HIP(c, hipMemcpyAsync(c->d_bits, words.data(), sizeof(unsigned long long) * words.size(), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(S.d_pd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(S.d_seam_off, &seam_off, sizeof(seam_off), hipMemcpyHostToDevice, c->stream));
+    launch_qmax_locate(c->stream, S.d_pd, 1, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, params->gamma_o, params->gamma_e, params->dp_start);
+    ACX_HIP(c, hipGetLastError());
+    ACX_HIP(c, hipMemcpyAsync(out, S.d_al, sizeof(acx_alignment), hipMemcpyDeviceToHost, c->stream));
     ACX_HIP(c, hipStreamSynchronize(c->stream));
     return ACX_OK;
 }

@@ -219,6 +219,33 @@ int acx_serra09_debug_bits(acx_ctx *ctx, const int32_t *pairs, int64_t K,
 int acx_qmax_binary(acx_ctx *ctx, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params,
                     float *score);
 
+/*
+ * WHERE the Qmax alignment lies.  Q is the matrix whose maximum acx_serra09_pairs returns.
+ *   score      max Q: the bits acx_serra09_pairs returns for the pair
+ *   (q1, r1)   end: the first cell in row-major order (smallest row, then smallest column) at which Q attains it
+ *   (q0, r0)   start: follow predecessors from the end until a cell has none.  Predecessor of a match cell: the first of
+ *              Q[i-1][j-1], Q[i-2][j-1], Q[i-1][j-2] equal to their maximum, none when that maximum is 0; of a gap cell
+ *              with Q > 0: the first of the three penalised values equal to their maximum.
+ * Coordinates are rows (query) and columns (reference) of the recurrence plot, i.e. EMBEDDED frames (with dp_start == 3 the
+ * oracle's DP cell (i, j) reads R[i-1][j-1]: reported is the R index).  score == 0: no match, all four are -1.
+ * Qmax only: params->dmax != 0 -> ACX_ERR_UNSUPPORTED before any launch.
+ */
+typedef struct { float score; int32_t q0, r0, q1, r1; } acx_alignment;
+
+/*
+ * The alignments of K (query, reference) pairs over the uploaded pool: the chain of acx_serra09_pairs (the same validation
+ * of the whole list before the first launch, batch plan, class sort and band / streaming kernels under params->arith), with
+ * qmax_locate_kernel as the sweep of every class, one wave per pair.  out: K records in the order of `pairs`.
+ */
+int acx_serra09_align(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_serra09_params *params, acx_alignment *out);
+
+/*
+ * The same DP alone on a given binary (M, N) uint8 plot, like acx_qmax_binary: uses params->gamma_o, gamma_e, dp_start;
+ * any M, N.  Non-{0,1} input -> ACX_ERR_INVALID; params->dmax != 0 -> ACX_ERR_UNSUPPORTED.
+ */
+int acx_qmax_locate_binary(acx_ctx *ctx, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params,
+                           acx_alignment *out);
+
 /* Number of embedded frames for a pooled length T (0 if too short). */
 int32_t acx_serra09_embed_len(int32_t T, const acx_serra09_params *params);
 
