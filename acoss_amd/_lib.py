@@ -41,6 +41,7 @@ EXPORTS = [
     "acx_pool_append", "acx_pool_append_raw", "acx_pool_append_f64", "acx_ef_pool_append", "acx_ftm2d_append_shingles",
     "acx_pool_truncate",
     "acx_serra09_align", "acx_qmax_locate_binary",
+    "acx_serra09_align_paths", "acx_qmax_path_binary",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -254,6 +255,9 @@ def load():
     L.acx_qmax_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, pp, fp]
     L.acx_serra09_align.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.c_void_p]
     L.acx_qmax_locate_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, pp, ctypes.c_void_p]
+    L.acx_serra09_align_paths.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+    L.acx_qmax_path_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, pp, ctypes.c_void_p,
+                                       ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_int64]
     epp = ctypes.POINTER(EfPrepParams)
     L.acx_ef_block_features.argtypes = [vp, fp, ctypes.c_int64, fp, ctypes.c_int64, ctypes.c_int32, lp, ctypes.c_int32, epp,
                                         fp, fp, fp, dp]
@@ -930,6 +934,40 @@ class Context(object):
         self._check(self._L.acx_qmax_locate_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                                                    R.shape[0], R.shape[1], ctypes.byref(p), out.ctypes.data))
         return out
+
+    def serra09_align_paths(self, pairs, params=None, cap=None):
+        """The alignments AND their paths (acx_serra09_align_paths): (records, offsets, cells) -- records as serra09_align
+        returns them, offsets (K + 1,) int64 and cells (offsets[-1], 2) int32: pair k's path is cells[offsets[k]:offsets[k + 1]],
+        (row, column) of the recurrence plot from the start to the end; a pair without a match has none.  cap: cells the buffer
+        holds; default the bound the library checks, the sum of min(Mq_k, Mr_k) over the list (acx_serra09_embed_len)."""
+        p = params or serra09_params()
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        if cap is None:
+            # (a list the library refuses -- an index out of range -- is refused before it looks at cap)
+            Ms = {t: max(self.serra09_embed_len(self.lengths[t], p), 0) for t in {int(t) for t in pairs.ravel()} if 0 <= t < len(self.lengths)}
+            cap = sum(min(Ms.get(int(i), 0), Ms.get(int(j), 0)) for i, j in pairs)
+        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
+        off = np.zeros(len(pairs) + 1, np.int64)
+        cells = np.zeros((max(int(cap), 1), 2), np.int32)
+        self._check(self._L.acx_serra09_align_paths(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), out.ctypes.data,
+                                                    off.ctypes.data, cells.ctypes.data, int(cap)))
+        return out, off, cells[:off[-1]].copy()
+
+    def qmax_path_binary(self, R, params=None, cap=None):
+        """The same DP alone on a given binary (M, N) plot (acx_qmax_path_binary): (record (1,) as qmax_locate_binary returns it,
+        cells (L, 2) int32 from the start to the end; L == 0: no match).  cap: default min(M, N)."""
+        p = params or serra09_params()
+        R = np.ascontiguousarray(R, dtype=np.uint8)
+        if R.ndim != 2:
+            raise ValueError("qmax_path_binary: R must be (M, N), got shape %s" % (R.shape,))
+        if cap is None:
+            cap = min(R.shape)
+        out = np.zeros(1, ALIGNMENT_DTYPE)
+        n = ctypes.c_int64(0)
+        cells = np.zeros((max(int(cap), 1), 2), np.int32)
+        self._check(self._L.acx_qmax_path_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), R.shape[0], R.shape[1],
+                                                 ctypes.byref(p), out.ctypes.data, ctypes.byref(n), cells.ctypes.data, int(cap)))
+        return out, cells[:n.value].copy()
 
     # ------------------------------------------------------------------ FTM2D
     def ftm2d_pool_begin(self, n_tracks, pwr=1.96, win=75, c=5):

@@ -218,15 +218,19 @@ class Serra09(CoverAlgorithm):
             raise ValueError("%s: track indices must be integers, got dtype %s" % (who, a.dtype))
         return a
 
-    def _align_pairs(self, pairs):
-        """(K, 2) checked int32 pairs -> (K,) ALIGN_DTYPE."""
+    def _align_pairs(self, pairs, paths=None):
+        """(K, 2) checked int32 pairs -> (K,) ALIGN_DTYPE.  paths: a list that receives the K (L_k, 2) int32 paths as well."""
         out = np.zeros(len(pairs), self.ALIGN_DTYPE)
         out["score"] = 0.0
         for f in ("q0", "r0", "q1", "r1", "q_span", "r_span"):
             out[f] = -1
         if len(pairs) == 0:
             return out
-        al = self._context().serra09_align(pairs, self._params())
+        if paths is None:
+            al = self._context().serra09_align(pairs, self._params())
+        else:
+            al, off, cells = self._context().serra09_align_paths(pairs, self._params())
+            paths.extend(cells[off[k]:off[k + 1]] for k in range(len(pairs)))
         for f in _lib.ALIGNMENT_DTYPE.names:
             out[f] = al[f]
         hit = al["q0"] >= 0
@@ -248,34 +252,70 @@ class Serra09(CoverAlgorithm):
         1 (DESIGN.md sections 2 and 3: the stack at base frame e tau holds frames (e + k) tau, k < m), so embedded frame e
         covers pooled frames tau e .. tau (e + m - 1) and a span is [tau q0, tau (q1 + m - 1)], clipped to the track.  A pair
         without a match (score 0) has -1 everywhere.  `Ds` is not written; not a collective."""
-        a = self._check_align("align", idxs)
+        return self._align_pairs(self._check_align_pairs("align", idxs))
+
+    def _check_align_pairs(self, who, idxs):
+        """align() / align_paths(): idxs -> (K, 2) int32, every check before the first library call."""
+        a = self._check_align(who, idxs)
         if a.size == 0:
             a = a.reshape(0, 2)
         if a.ndim != 2 or a.shape[1] != 2:
-            raise ValueError("align: idxs must be (K, 2) (query, reference) track indices, got shape %s" % (a.shape,))
+            raise ValueError("%s: idxs must be (K, 2) (query, reference) track indices, got shape %s" % (who, a.shape))
         if a.size and (a.min() < 0 or a.max() >= self.N):
-            raise ValueError("align: idxs must be track indices in [0, %d)" % self.N)
-        return self._align_pairs(np.ascontiguousarray(a, dtype=np.int32))
+            raise ValueError("%s: idxs must be track indices in [0, %d)" % (who, self.N))
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def _check_align_matches(self, who, queries, indices):
+        """align_matches() / align_match_paths(): -> (the (Q, k) index array, rows and slots of its filled slots, their (P, 2) pairs)."""
+        q = self._check_align(who, queries).reshape(-1)
+        idx = self._check_align(who, indices)
+        if idx.ndim != 2 or idx.shape[0] != len(q):
+            raise ValueError("%s: indices must be (Q, k) with one row per query (%d), got shape %s" % (who, len(q), idx.shape))
+        if q.size and (q.min() < 0 or q.max() >= self.N):
+            raise ValueError("%s: queries must be track indices in [0, %d)" % (who, self.N))
+        if idx.size and (idx.min() < -1 or idx.max() >= self.N):
+            raise ValueError("%s: indices must be track indices in [0, %d) or -1" % (who, self.N))
+        rows, slots = np.nonzero(idx >= 0)
+        pairs = np.stack([q[rows], idx[rows, slots]], axis=1).astype(np.int32).reshape(-1, 2)
+        return idx, rows, slots, np.ascontiguousarray(pairs)
+
+    def _no_match_rows(self, shape):
+        out = np.zeros(shape, self.ALIGN_DTYPE)
+        for f in ("q0", "r0", "q1", "r1", "q_span", "r_span"):
+            out[f] = -1
+        return out
 
     def align_matches(self, queries, indices):
         """align() for the hits of identify() / rerank(): queries (Q,) track indices, indices the (Q, k) int array
         either returned (-1: an empty slot).  Returns a (Q, k) structured array as align() does, row i slot s being the
         alignment of (queries[i], indices[i, s]); an empty slot comes back as a no-match row."""
-        q = self._check_align("align_matches", queries).reshape(-1)
-        idx = self._check_align("align_matches", indices)
-        if idx.ndim != 2 or idx.shape[0] != len(q):
-            raise ValueError("align_matches: indices must be (Q, k) with one row per query (%d), got shape %s" % (len(q), idx.shape))
-        if q.size and (q.min() < 0 or q.max() >= self.N):
-            raise ValueError("align_matches: queries must be track indices in [0, %d)" % self.N)
-        if idx.size and (idx.min() < -1 or idx.max() >= self.N):
-            raise ValueError("align_matches: indices must be track indices in [0, %d) or -1" % self.N)
-        out = np.zeros(idx.shape, self.ALIGN_DTYPE)
-        for f in ("q0", "r0", "q1", "r1", "q_span", "r_span"):
-            out[f] = -1
-        rows, slots = np.nonzero(idx >= 0)
-        pairs = np.stack([q[rows], idx[rows, slots]], axis=1).astype(np.int32).reshape(-1, 2)
-        out[rows, slots] = self._align_pairs(np.ascontiguousarray(pairs))
+        idx, rows, slots, pairs = self._check_align_matches("align_matches", queries, indices)
+        out = self._no_match_rows(idx.shape)
+        out[rows, slots] = self._align_pairs(pairs)
         return out
+
+    def align_paths(self, idxs):
+        """align() and, for every pair, the PATH of its alignment: (al, paths).  al is exactly what align(idxs) returns; paths is a
+        list of K (L_k, 2) int32 arrays, the cells (q, r) of the cross recurrence plot that the recursion's predecessors visit
+        between the start and the end, both included, listed from (q0, r0) to (q1, r1) -- which frame of the query corresponds to
+        which frame of the reference.  Consecutive cells differ by (1, 1), (2, 1) or (1, 2); a pair without a match has an empty
+        (0, 2) path.  Cells are EMBEDDED frames: embedded frame e starts at pooled frame tau * e (and stacks pooled frames
+        tau e .. tau (e + m - 1), as in align()).  `Ds` is not written; not a collective."""
+        paths = []
+        al = self._align_pairs(self._check_align_pairs("align_paths", idxs), paths)
+        return al, (paths if len(al) else [])
+
+    def align_match_paths(self, queries, indices):
+        """align_matches() with the paths: (the (Q, k) array align_matches returns, a Q-list of k-lists of (L, 2) int32 paths as
+        align_paths lists them); an empty slot (-1) has an empty path."""
+        idx, rows, slots, pairs = self._check_align_matches("align_match_paths", queries, indices)
+        out = self._no_match_rows(idx.shape)
+        got = []
+        out[rows, slots] = self._align_pairs(pairs, got)
+        paths = [[np.zeros((0, 2), np.int32) for _ in range(idx.shape[1])] for _ in range(idx.shape[0])]
+        for r, s, p in zip(rows, slots, got):
+            paths[r][s] = p
+        return out, paths
 
     def normalize_by_length(self):
         """Non-symmetric normalisation: D[i, j] /= sqrt(T_j), T_j the pooled length

@@ -21,6 +21,7 @@
 #include "serra09_kernels.hpp"
 #include "serra09_long_kernels.hpp"
 #include "serra09_locate_kernels.hpp"
+#include "serra09_path_kernels.hpp"
 #include "prep_kernels.hpp"
 #include "snf_kernels.hpp"
 #include "simple_kernels.hpp"
@@ -49,7 +50,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -167,6 +168,12 @@ struct acx_ctx {
     DeviceBuffer<float> d_out;
     DeviceBuffer<unsigned long long> d_bits;              // recurrence bitmaps (u64 words)
     DeviceBuffer<acx::LocSeam> d_seam;                    // qmax_locate_kernel's strip seam records (pairs wider than one strip only)
+    // qmax_path_kernel, per chunk of boxes: the direction plane (2 bits per box cell), the strip seam records of
+    // boxes wider than one strip, the boxes, and the cells and their number as the traceback left them
+    DeviceBuffer<unsigned long long> d_dir;
+    DeviceBuffer<acx::PathSeam> d_pseam;
+    DeviceBuffer<acx::PathBox> d_pbox;
+    DeviceBuffer<int32_t> d_pcells, d_pn;
     int64_t scratch_limit = 0;                            // bytes
     size_t total_mem = 0;
     // the pair grid: last plan (a pure function of lengths and spec; sorting 10^4 tiles per call is what the cache saves)
@@ -187,7 +194,7 @@ struct acx_ctx {
                              {"ef_fuse_kernel", 0, 0, 0}, {"sw_kernel", 0, 0, 0}, {"rank_columns_kernel", 0, 0, 0},
                              {"topk_rows_kernel", 0, 0, 0}, {"ftm2d_tile_kernel", 0, 0, 0}, {"query_rows_kernel", 0, 0, 0},
                              {"query_topk_kernel", 0, 0, 0}, {"query_rank_kernel", 0, 0, 0}, {"query_topk_lists_kernel", 0, 0, 0},
-                             {"ftm2d_pairs_kernel", 0, 0, 0}, {"qmax_locate_kernel", 0, 0, 0}};
+                             {"ftm2d_pairs_kernel", 0, 0, 0}, {"qmax_locate_kernel", 0, 0, 0}, {"qmax_path_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
     // Appends (acx_pool_append & co.): capacity in elements of every raw-pointer pool block that an append has grown.  0 = the block
@@ -685,6 +692,86 @@ void launch_qmax_locate(hipStream_t st, const PairDesc *pd, int B, const unsigne
         hipLaunchKernelGGL((acx::qmax_locate_kernel<false>), dim3(B), dim3(64), 0, st, pd, bits, seam, seam_off, dst, gamma_o, gamma_e, dp_start);
 }
 
+// The path pass (serra09_path_kernels.hpp) behind a locating sweep, while c->d_bits still holds the bitmaps of the B pairs whose
+// descriptors are `dpd` on the device: recs[k2] is pair k2's record ON THE HOST (the caller has waited for it), and pair k2's cells
+// go to dst(k2) as (q, r) from start to end; a pair without a match gets none.  The boxes run in CHUNKS: as many consecutive boxes as
+// fit path_budget_bytes (direction planes + seam records) and one launch's grid; a single box beyond it is ACX_ERR_NOMEM (`name(k2)`
+// says which pair).  Runs on the main stream and returns with it idle.
+int64_t path_budget_bytes(const acx_ctx *c) { return scratch_limit_bytes(c) / 2; }
+
+template <typename Dst, typename Name>
+int run_qmax_paths(acx_ctx *c, const PairDesc *dpd, const acx_alignment *recs, int B, float gamma_o, float gamma_e, Dst dst, Name name)
+{
+    const int64_t budget = path_budget_bytes(c);
+    std::vector<acx::PathBox> boxes;
+    std::vector<int> owner;
+    std::vector<int32_t> h_n, h_cells;
+    int k2 = 0;
+    while (k2 < B) {
+        boxes.clear(); owner.clear();
+        int64_t words = 0, seams = 0, ncell = 0, bytes = 0, area = 0;
+        for (; k2 < B && boxes.size() < 65535; ++k2) {
+            const acx_alignment &a = recs[k2];
+            dst(k2).clear();
+            if (!(a.score > 0.0f) || a.q0 < 0) continue;
+            const int rows = a.q1 - a.q0 + 1, width = a.r1 - a.r0 + 1;
+            if (rows < 1 || width < 1 || a.r0 < 0) return fail(c, ACX_ERR_STATE, "qmax_path: pair " + name(k2) + " has a malformed alignment record");
+            const int64_t need = acx::path_box_bytes(rows, width);
+            if (need > budget)
+                return fail(c, ACX_ERR_NOMEM, "qmax_path: the " + std::to_string(rows) + " x " + std::to_string(width) + " box of pair " + name(k2) +
+                                                  " takes " + std::to_string(need) + " bytes, beyond the path budget of " + std::to_string(budget) +
+                                                  " (half the scratch limit)");
+            if (bytes + need > budget) break;
+            acx::PathBox bx;
+            bx.pair = k2; bx.q0 = a.q0; bx.r0 = a.r0; bx.q1 = a.q1; bx.r1 = a.r1;
+            bx.max_cells = std::min(rows, width);
+            bx.dir_off = words; bx.seam_off = seams; bx.cell_off = ncell;
+            words += (int64_t)rows * acx::path_words(width);
+            if (acx::path_strips(width) > 1) seams += 2 * (int64_t)rows;
+            ncell += bx.max_cells;
+            bytes += need;
+            area += (int64_t)rows * width;
+            boxes.push_back(bx); owner.push_back(k2);
+        }
+        const int nb = (int)boxes.size();
+        if (nb == 0) continue;
+        int rc;
+        if ((rc = ensure(c, c->d_dir, (size_t)words)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_pseam, (size_t)std::max<int64_t>(seams, 1))) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_pbox, (size_t)nb)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_pcells, (size_t)(2 * ncell))) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_pn, (size_t)nb)) != ACX_OK) return rc;
+        ACX_HIP(c, hipMemcpyAsync(c->d_pbox, boxes.data(), sizeof(acx::PathBox) * nb, hipMemcpyHostToDevice, c->stream));
+        {
+            ProfScope ps(c, KS_PATH, area);
+            if (gamma_o == gamma_e)
+                hipLaunchKernelGGL((acx::qmax_path_kernel<true>), dim3(nb), dim3(64), 0, c->stream, dpd, c->d_pbox, c->d_bits, c->d_dir, c->d_pseam,
+                                   c->d_pcells, c->d_pn, gamma_o, gamma_e);
+            else
+                hipLaunchKernelGGL((acx::qmax_path_kernel<false>), dim3(nb), dim3(64), 0, c->stream, dpd, c->d_pbox, c->d_bits, c->d_dir, c->d_pseam,
+                                   c->d_pcells, c->d_pn, gamma_o, gamma_e);
+        }
+        ACX_HIP(c, hipGetLastError());
+        h_n.resize((size_t)nb);
+        h_cells.resize((size_t)(2 * ncell));
+        ACX_HIP(c, hipMemcpyAsync(h_n.data(), c->d_pn, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipMemcpyAsync(h_cells.data(), c->d_pcells, sizeof(int32_t) * 2 * ncell, hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        for (int b = 0; b < nb; ++b) {      // the traceback wrote the cells end first
+            const acx::PathBox &bx = boxes[(size_t)b];
+            const int n = h_n[(size_t)b];
+            const int32_t *src = h_cells.data() + 2 * bx.cell_off;
+            if (n < 1 || n > bx.max_cells || src[2 * (n - 1)] != bx.q0 || src[2 * (n - 1) + 1] != bx.r0)
+                return fail(c, ACX_ERR_STATE, "qmax_path: the traceback of pair " + name(owner[(size_t)b]) + " does not end at the reported start");
+            std::vector<int32_t> &out = dst(owner[(size_t)b]);
+            out.resize((size_t)(2 * n));
+            for (int t = 0; t < n; ++t) { out[2 * (size_t)t] = src[2 * (n - 1 - t)]; out[2 * (size_t)t + 1] = src[2 * (n - 1 - t) + 1]; }
+        }
+    }
+    drain_profile(c);
+    return ACX_OK;
+}
+
 // The streaming class (a side beyond the last band class, or m > MAX_M) up to its recurrence bitmap, on the main stream: `B` pairs
 // whose descriptors are `dpd` on the device and `pd` on the host, spanning `e`.
 void launch_streaming_class(acx_ctx *c, const PairDesc *dpd, const PairDesc *pd, int B, const acx::Serra09Extent &e, const acx_serra09_params &p)
@@ -707,20 +794,22 @@ void launch_streaming_class(acx_ctx *c, const PairDesc *dpd, const PairDesc *pd,
 }
 
 int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
-                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al);
+                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al, std::vector<std::vector<int32_t>> *paths);
 
 // Runs the chain over `K` pairs in scratch-sized batches.  `al` (acx_serra09_align): the sweep is qmax_locate_kernel and pair k's
-// record goes to al[k]; no scores are written.
+// record goes to al[k]; no scores are written.  `paths` (acx_serra09_align_paths, with `al`; K vectors): the path pass runs behind the
+// locating sweep of every batch, and pair k's cells go to (*paths)[k].
 int run_serra09(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
-                const DebugOut *dbg, bool both = false, const DevDst *dd = nullptr, acx_alignment *al = nullptr)
+                const DebugOut *dbg, bool both = false, const DevDst *dd = nullptr, acx_alignment *al = nullptr,
+                std::vector<std::vector<int32_t>> *paths = nullptr)
 {
-    const int rc = run_serra09_impl(c, pairs, K, p_in, out, dbg, both, dd, al);
+    const int rc = run_serra09_impl(c, pairs, K, p_in, out, dbg, both, dd, al, paths);
     if (rc != ACX_OK) quiesce(c);                // (c->err keeps the first failure's text)
     return rc;
 }
 
 int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
-                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al)
+                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al, std::vector<std::vector<int32_t>> *paths)
 {
     if (!c->d_frames0) return fail(c, ACX_ERR_STATE, "serra09: feature pool not uploaded (acx_upload_pool)");
     if (c->dim != acx::NBIN) return fail(c, ACX_ERR_INVALID, "serra09: pool dim must be 12");
@@ -887,6 +976,12 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         }
         ACX_HIP(c, hipEventRecord(S.done, qs));
         S.busy = true; S.on_q = use_q; S.B = B; S.w = w; S.k0 = k0; S.al = al != nullptr;
+        if (al && paths) {     // the paths, while d_bits holds this batch: the boxes come from the batch's records, so the host waits here
+            ACX_HIP(c, hipEventSynchronize(S.done));
+            if ((rc = run_qmax_paths(c, S.d_pd, S.h_al, B, p.gamma_o, p.gamma_e,
+                                     [&](int k2) -> std::vector<int32_t> & { return (*paths)[(size_t)(k0 + perm[k2])]; },
+                                     [&](int k2) { return std::to_string(k0 + perm[k2]); })) != ACX_OK) return rc;
+        }
 
         if (dbg && B >= 1) {
             if ((rc = collect_slot(c, S, out)) != ACX_OK) return rc;
@@ -2006,6 +2101,66 @@ int acx_qmax_locate_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, c
     ACX_HIP(c, hipGetLastError());
     ACX_HIP(c, hipMemcpyAsync(out, S.d_al, sizeof(acx_alignment), hipMemcpyDeviceToHost, c->stream));
     ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
+}
+
+int acx_serra09_align_paths(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, acx_alignment *out,
+                            int64_t *path_off, int32_t *cells, int64_t cap)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (params && params->dmax != 0) return fail(c, ACX_ERR_UNSUPPORTED, "serra09_align_paths: the Qmax alignment only (params->dmax must be 0)");
+    if (K < 0 || (K > 0 && (!pairs || !out)) || !params || !path_off || cap < 0 || (cap > 0 && !cells))
+        return fail(c, ACX_ERR_INVALID, "serra09_align_paths: bad argument");
+    path_off[0] = 0;
+    if (K == 0) return ACX_OK;
+    // the run's own checks of the list, in its order, so that the bound on the cells is known before the first launch
+    if (!c->d_frames0) return fail(c, ACX_ERR_STATE, "serra09: feature pool not uploaded (acx_upload_pool)");
+    if (c->dim != acx::NBIN) return fail(c, ACX_ERR_INVALID, "serra09: pool dim must be 12");
+    int rc = check_params(c, *params);
+    if (rc != ACX_OK) return rc;
+    const acx::Serra09Lengths len{c->h_off0.data(), c->n_tracks, params->tau};
+    if ((rc = validate_serra09_pairs(c, len, pairs, K, *params, false, scratch_limit_bytes(c) / 4)) != ACX_OK) return rc;
+    int64_t bound = 0;                           // no path has more cells than its plot's shorter side
+    for (int64_t k = 0; k < K; ++k) {
+        PairDesc d;
+        acx::Serra09Need need;
+        (void)acx::serra09_size_pair(len, pairs[2 * k], pairs[2 * k + 1], *params, false, d, need);
+        bound += std::min(d.Mq, d.Mr);
+    }
+    if (cap < bound)
+        return fail(c, ACX_ERR_INVALID, "serra09_align_paths: cap " + std::to_string(cap) + " is too small: " + std::to_string(bound) +
+                                            " cells required (the sum of min(Mq, Mr) over the list)");
+    std::vector<std::vector<int32_t>> paths((size_t)K);
+    if ((rc = run_serra09(c, pairs, K, *params, nullptr, nullptr, false, nullptr, out, &paths)) != ACX_OK) return rc;
+    int64_t n = 0;
+    for (int64_t k = 0; k < K; ++k) {
+        const std::vector<int32_t> &pk = paths[(size_t)k];
+        if (!pk.empty()) memcpy(cells + 2 * n, pk.data(), sizeof(int32_t) * pk.size());
+        n += (int64_t)pk.size() / 2;
+        path_off[k + 1] = n;
+    }
+    return ACX_OK;
+}
+
+int acx_qmax_path_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out,
+                         int64_t *n_cells, int32_t *cells, int64_t cap)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (params && params->dmax != 0) return fail(c, ACX_ERR_UNSUPPORTED, "qmax_path_binary: the Qmax alignment only (params->dmax must be 0)");
+    if (!R || !params || !out || !n_cells || M < 1 || N < 1 || cap < 0 || (cap > 0 && !cells)) return fail(c, ACX_ERR_INVALID, "qmax_path_binary: bad argument");
+    if (cap < std::min(M, N))
+        return fail(c, ACX_ERR_INVALID, "qmax_path_binary: cap " + std::to_string(cap) + " is too small: " + std::to_string(std::min(M, N)) +
+                                            " cells required (min(M, N))");
+    *n_cells = 0;
+    // the locating sweep on the plot: it leaves the plot's bitmap in d_bits and its descriptor in slot 0, and the record is the box
+    int rc = acx_qmax_locate_binary(c, R, M, N, params, out);
+    if (rc != ACX_OK) return rc;
+    std::vector<int32_t> path;
+    rc = run_qmax_paths(c, c->slot[0].d_pd, out, 1, params->gamma_o, params->gamma_e,
+                        [&](int) -> std::vector<int32_t> & { return path; }, [](int) { return std::string("0"); });
+    if (rc != ACX_OK) { quiesce(c); return rc; }
+    if (!path.empty()) memcpy(cells, path.data(), sizeof(int32_t) * path.size());
+    *n_cells = (int64_t)path.size() / 2;
     return ACX_OK;
 }
 

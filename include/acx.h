@@ -246,6 +246,32 @@ int acx_serra09_align(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_s
 int acx_qmax_locate_binary(acx_ctx *ctx, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params,
                            acx_alignment *out);
 
+/*
+ * The PATH of the Qmax alignment: the cells from the start (q0, r0) to the end (q1, r1), both included, that
+ * the predecessor chain from the end visits -- rows and columns of the recurrence plot, the coordinates of acx_alignment, listed from
+ * start to end; consecutive cells differ by (1, 1), (2, 1) or (1, 2); a pair without a match has an empty path.  A second pass behind
+ * the locating sweep of every batch (qmax_path_kernel): the Qmax recursion over the cells of the reported box only, one 2-bit
+ * predecessor code per cell, and a traceback over the codes.
+ *   out       K records, bit for bit what acx_serra09_align returns for the same arguments
+ *   path_off  K + 1 entries: pair k's cells are cells[2 * path_off[k] .. 2 * path_off[k + 1]), (q, r) interleaved
+ *   cells     cap x 2 int32
+ *   cap       checked before the first launch against the bound the host knows then, the sum over the list of min(Mq_k, Mr_k) in
+ *             embedded frames (no path has more cells than its plot's shorter side): too small -> ACX_ERR_INVALID with the required
+ *             number in the message, nothing launched
+ * The boxes of a batch run in chunks whose direction planes (2 bits per box cell) and seam records fit HALF the scratch limit
+ * (acx_set_scratch_limit); a single box beyond that: ACX_ERR_NOMEM, nothing left in flight.  All other errors are those of
+ * acx_serra09_align with the same codes; params->dmax != 0 -> ACX_ERR_UNSUPPORTED before anything else.
+ */
+int acx_serra09_align_paths(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_serra09_params *params,
+                            acx_alignment *out, int64_t *path_off /* K + 1 */, int32_t *cells /* cap x 2: (q, r) */, int64_t cap);
+
+/*
+ * The same DP alone on a given binary (M, N) uint8 plot, as acx_qmax_locate_binary is for the endpoints: `out` is its record,
+ * *n_cells the number of cells written to `cells` (cap x 2 int32; cap >= min(M, N), else ACX_ERR_INVALID and nothing launched).
+ */
+int acx_qmax_path_binary(acx_ctx *ctx, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params,
+                         acx_alignment *out, int64_t *n_cells, int32_t *cells, int64_t cap);
+
 /* Number of embedded frames for a pooled length T (0 if too short). */
 int32_t acx_serra09_embed_len(int32_t T, const acx_serra09_params *params);
 
