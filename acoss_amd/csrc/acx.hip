@@ -90,22 +90,26 @@ struct acx_ctx {
     hipStream_t qstream2 = nullptr;                  // ... and the second alignment (Dmax) of LateFusionChen beside the first
     hipEvent_t q2_done = nullptr;
     std::string err;
-    // pool as uploaded (d_frames0 / d_toff0 / h_off0) and the ACTIVE pool: the upload decimated by the
-    // stack stride tau of the last Serra09 call (tau == 1: the same buffers)
-    float *d_frames0 = nullptr;
-    int64_t *d_toff0 = nullptr;
+    // pool as uploaded (d_frames0 / d_toff0 / h_off0) and the ACTIVE pool: the upload decimated by the stack stride tau of
+    // the last Serra09 call.  d_frames / d_toff hold the decimated copy and are EMPTY at tau == 1, where the active pool is
+    // the uploaded one: readers go through active_frames() / active_toff().  Invariant, kept by ensure_tau and free_pool (the
+    // only writers of pool_tau): d_frames and d_toff are non-empty exactly when pool_tau > 1, so the accessors may decide by the block.
+    DeviceBuffer<float> d_frames0;
+    DeviceBuffer<int64_t> d_toff0;
     std::vector<int64_t> h_off0;
     int pool_tau = 0;
-    float *d_frames = nullptr;
-    float *d_frot = nullptr;      // rotated frame pool (band kernel MFMA operands), 36 floats per frame
-    _Float16 *d_fh = nullptr;     // the f16 operand pool of the opt-in f16x2 Gram (acx::FH halfs per frame), built on first use
-    float *d_normtab = nullptr;   // embedded norms per (track, rotation, frame) for normtab_m / normtab_span
-    int64_t *d_noff = nullptr;
+    DeviceBuffer<float> d_frames;
+    DeviceBuffer<float> d_frot;       // rotated frame pool (band kernel MFMA operands), 36 floats per frame
+    DeviceBuffer<_Float16> d_fh;      // the f16 operand pool of the opt-in f16x2 Gram (acx::FH halfs per frame), built on first use
+    DeviceBuffer<float> d_normtab;    // embedded norms per (track, rotation, frame) for normtab_m / normtab_span
+    DeviceBuffer<int64_t> d_noff;
     int normtab_m = 0, normtab_span = -1;
     std::vector<int64_t> h_noff;  // host copy of d_noff (n_tracks + 1 entries; the last one is the table's length)
-    int64_t *d_toff = nullptr;
-    float *d_gch = nullptr;
+    DeviceBuffer<int64_t> d_toff;
+    DeviceBuffer<float> d_gch;
     std::vector<int64_t> h_off;
+    const float *active_frames() const { return d_frames ? d_frames.get() : d_frames0.get(); }
+    const int64_t *active_toff() const { return d_toff ? d_toff.get() : d_toff0.get(); }
     int32_t n_tracks = 0, dim = 0;
     // f64 pool (SiMPle)
     DeviceBuffer<double> d_frames64;
@@ -118,12 +122,12 @@ struct acx_ctx {
     DeviceBuffer<int32_t> d_pairs;
     DeviceBuffer<double> d_out64;
     // EarlyFusion pool
-    float *d_ef[3] = {nullptr, nullptr, nullptr};
-    unsigned short *d_efs[3] = {nullptr, nullptr, nullptr};   // mfcc / ssm / chroma block features as three-term bf16 splits
+    DeviceBuffer<float> d_ef[3];
+    DeviceBuffer<unsigned short> d_efs[3];            // mfcc / ssm / chroma block features as three-term bf16 splits
     int ef_kp[3] = {0, 0, 0};                         // their row length (K rounded up to 32); chroma: bin-major, 0 = no split (f32 kernel)
-    float *d_efn[2] = {nullptr, nullptr};
-    double *d_efmed = nullptr;
-    int64_t *d_efoff = nullptr;
+    DeviceBuffer<float> d_efn[2];
+    DeviceBuffer<double> d_efmed;
+    DeviceBuffer<int64_t> d_efoff;
     std::vector<int64_t> h_efoff;
     int32_t ef_ntracks = 0;
     int32_t ef_gemm = ACX_EF_GEMM_DEFAULT;            // arithmetic of the three cross-similarity GEMMs
@@ -131,7 +135,7 @@ struct acx_ctx {
     int32_t ef_open = 0;                              // > 0: a pool of that many tracks is being filled (acx_ef_pool_begin .. _end)
     std::vector<uint8_t> ef_filled;                   // per track of the open pool: handed over by acx_ef_pool_tracks yet?
     // FTM2D shingle pool: (ftm_n, ftm_dim) f64, one row per track
-    double *d_ftm = nullptr;
+    DeviceBuffer<double> d_ftm;
     int32_t ftm_n = 0, ftm_dim = 0;
     int32_t ftm_open = 0;                             // > 0: a pool of that many tracks is being filled (acx_ftm2d_pool_begin .. _end)
     std::vector<uint8_t> ftm_filled;                  // per track of the open pool: handed over by acx_ftm2d_pool_tracks yet?
@@ -160,7 +164,7 @@ struct acx_ctx {
     DeviceBuffer<unsigned> d_efctr;                    // tile counters of the persistent rectangle GEMMs (one per launch of a batch)
     int n_cu = 0;
     int ef_split_fmt = 0;                             // what d_efs holds: 0 three bf16 terms, 1 two fp16 terms of x / d_efsc[row]
-    float *d_efsc[3] = {nullptr, nullptr, nullptr};   // fmt 1: the power-of-two scale of every pool row (ef_rowscale_kernel)
+    DeviceBuffer<float> d_efsc[3];                    // fmt 1: the power-of-two scale of every pool row (ef_rowscale_kernel)
     // scratch (grow-only)
     DeviceBuffer<float> d_scratch, d_thr;
     DeviceBuffer<unsigned> d_efbits;                         // EarlyFusion: the binarised matrices of a batch (ef_rowstat_kernel -> sw_bits_kernel)
@@ -197,11 +201,6 @@ struct acx_ctx {
                              {"ftm2d_pairs_kernel", 0, 0, 0}, {"qmax_locate_kernel", 0, 0, 0}, {"qmax_path_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
-    // Appends (acx_pool_append & co.): capacity in elements of every raw-pointer pool block that an append has grown.  0 = the block
-    // is as its upload allocated it, exactly as large as its contents; whoever frees a block resets its entry.
-    struct S09Caps { size_t frames0, toff0, gch, frames, toff, frot, fh, normtab, noff; } s09_cap = {};
-    struct EfCaps { size_t ef[3], efs[3], efn[2], efsc[3], efmed, efoff; } ef_cap = {};
-    size_t ftm_cap = 0;
     // How many tracks ensure_f16pool's range check saw when it built d_fh (-1: it had no frame to check).  The largest magnitude of
     // a pool that contains those tracks is at least theirs, so the check's lower bound holds for every such pool.
     int32_t fh_base_n = -1;
@@ -353,7 +352,7 @@ bool launch_band(acx_ctx *c, int m, const PairDesc *dpd, int B, int maxRows, int
                  int want_eps)
 {
     const float *operands = p.arith == ACX_ARITH_F16X2 ? reinterpret_cast<const float *>(c->d_fh + POOL_SLACK * acx::FH) : c->d_frot + POOL_SLACK * acx::FROT;
-    acx::BandLaunch L{c->stream, operands, c->d_toff, c->d_normtab + POOL_SLACK, c->d_noff, c->d_scratch, c->d_thr,
+    acx::BandLaunch L{c->stream, operands, c->active_toff(), c->d_normtab + POOL_SLACK, c->d_noff, c->d_scratch, c->d_thr,
                       c->d_bits, p.kappa, p.pct_mode, p.inclusive, p.oti_target};
     return acx::launch_band_kernel(L, m, dpd, B, maxRows, acx::serra09_band_family(cls, m, p.arith), role, write_d2, want_eps, p.arith);
 }
@@ -362,7 +361,7 @@ template <int M>
 void launch_normtab(acx_ctx *c, int maxM, int span, int first, int count)       // tracks [first, first + count) of the active pool
 {
     hipLaunchKernelGGL((acx::normtab_kernel<M>), dim3(count, (maxM + 255) / 256, acx::NBIN), dim3(256), 0, c->stream,
-                       c->d_frames, c->d_toff + first, c->d_noff + first, c->d_normtab + POOL_SLACK, span);
+                       c->active_frames(), c->active_toff() + first, c->d_noff + first, c->d_normtab + POOL_SLACK, span);
 }
 
 #ifdef ACX_FAST_BUILD   /* development builds: only the default stack size */
@@ -384,23 +383,21 @@ void launch_normtab(acx_ctx *c, int maxM, int span, int first, int count)       
 // The active pool is the uploaded one decimated by the stack stride: the stack at base frame e tau
 // holds frames (e + k) tau, so with X'[t] = X[t tau] it is the tau = 1 stack of X' (same frames,
 // same order, same count: ceil(T / tau) - m = ceil((T - m tau) / tau)).  The OTI's global chroma
-// stays the one of the complete track.  Rebuilt when tau changes; tau = 1 aliases the upload.
+// stays the one of the complete track.  Rebuilt when tau changes; at tau = 1 the upload is the active pool.
 int ensure_tau(acx_ctx *c, int tau)
 {
     if (c->pool_tau == tau) return ACX_OK;
-    if (c->d_frames && c->d_frames != c->d_frames0) { ACX_HIP(c, hipFree(c->d_frames)); }
-    if (c->d_toff && c->d_toff != c->d_toff0) { ACX_HIP(c, hipFree(c->d_toff)); }
-    c->d_frames = nullptr; c->d_toff = nullptr;
-    if (c->d_frot) { ACX_HIP(c, hipFree(c->d_frot)); c->d_frot = nullptr; }
-    if (c->d_fh) { ACX_HIP(c, hipFree(c->d_fh)); c->d_fh = nullptr; }
-    if (c->d_normtab) { ACX_HIP(c, hipFree(c->d_normtab)); c->d_normtab = nullptr; }
-    if (c->d_noff) { ACX_HIP(c, hipFree(c->d_noff)); c->d_noff = nullptr; }
-    c->normtab_m = 0; c->normtab_span = -1;
+    c->normtab_m = 0; c->normtab_span = -1;      // the keys first: a reset that fails below leaves no key on an emptied block
     c->pool_tau = 0;
-    c->s09_cap.frames = c->s09_cap.toff = c->s09_cap.frot = c->s09_cap.fh = c->s09_cap.normtab = c->s09_cap.noff = 0;
     c->fh_base_n = -1;
+    ACX_HIP(c, c->d_frames.reset());
+    ACX_HIP(c, c->d_toff.reset());
+    ACX_HIP(c, c->d_frot.reset());
+    ACX_HIP(c, c->d_fh.reset());
+    ACX_HIP(c, c->d_normtab.reset());
+    ACX_HIP(c, c->d_noff.reset());
     const int n = c->n_tracks;
-    DeviceBuffer<float> frames, frot;            // built here and handed to the context when complete: a failure leaves no half-built pool
+    DeviceBuffer<float> frames, frot;            // built here and moved into the context when complete: a failure leaves no half-built pool
     DeviceBuffer<int64_t> toff;
     if (tau == 1) {
         c->h_off = c->h_off0;
@@ -419,12 +416,12 @@ int ensure_tau(acx_ctx *c, int tau)
         ACX_HIP(c, hipMemcpy(toff, c->h_off.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
         if (total > 0) {
             hipLaunchKernelGGL(acx::decimate_kernel, dim3(n, (maxT * acx::NBIN + 255) / 256), dim3(256), 0, c->stream,
-                               c->d_frames0, c->d_toff0, toff.get(), frames.get(), tau);
+                               c->d_frames0.get(), c->d_toff0.get(), toff.get(), frames.get(), tau);
             ACX_HIP(c, hipGetLastError());
         }
     }
     const int64_t total = c->h_off[n];
-    const float *active = tau == 1 ? c->d_frames0 : frames.get();
+    const float *active = tau == 1 ? c->d_frames0.get() : frames.get();
     // rotated copy of the active pool: the band kernel loads its MFMA operands from it (12 bytes per
     // lane per 16-frame tile, already in the rotated chain order) -- 144 B per frame
     ACX_HIP(c, frot.grow((size_t)(std::max<int64_t>(1, total) + 2 * POOL_SLACK) * acx::FROT));
@@ -437,9 +434,9 @@ int ensure_tau(acx_ctx *c, int tau)
         ACX_HIP(c, hipGetLastError());
     }
     ACX_HIP(c, hipStreamSynchronize(c->stream));
-    c->d_frames = tau == 1 ? c->d_frames0 : frames.release();
-    c->d_toff = tau == 1 ? c->d_toff0 : toff.release();
-    c->d_frot = frot.release();
+    c->d_frames = std::move(frames);             // (both empty at tau == 1)
+    c->d_toff = std::move(toff);
+    c->d_frot = std::move(frot);
     c->pool_tau = tau;
     return ACX_OK;
 }
@@ -469,7 +466,7 @@ int ensure_f16pool(acx_ctx *c)
         ACX_HIP(c, d_m.grow(1));
         ACX_HIP(c, hipMemsetAsync(d_m, 0, sizeof(unsigned), c->stream));
         hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)std::min<int64_t>((total * acx::NBIN + 255) / 256, 4096)), dim3(256), 0, c->stream,
-                           c->d_frames, total * acx::NBIN, d_m.get());
+                           c->active_frames(), total * acx::NBIN, d_m.get());
         ACX_HIP(c, hipMemcpyAsync(&h_m, d_m, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
         ACX_HIP(c, hipStreamSynchronize(c->stream));
         float mx;
@@ -485,12 +482,11 @@ int ensure_f16pool(acx_ctx *c)
     ACX_HIP(c, hipMemsetAsync(fh, 0, sizeof(_Float16) * halfs, c->stream));
     if (total > 0) {
         hipLaunchKernelGGL(acx::rotpool_f16_kernel, dim3((unsigned)std::min<int64_t>((total * 12 + 255) / 256, 1 << 22)), dim3(256), 0, c->stream,
-                           c->d_frames, fh + POOL_SLACK * acx::FH, total);
+                           c->active_frames(), fh + POOL_SLACK * acx::FH, total);
         ACX_HIP(c, hipGetLastError());
     }
     ACX_HIP(c, hipStreamSynchronize(c->stream));
-    c->d_fh = fh.release();
-    c->s09_cap.fh = 0;
+    c->d_fh = std::move(fh);
     c->fh_base_n = total > 0 ? c->n_tracks : -1;
     return ACX_OK;
 }
@@ -500,10 +496,9 @@ int ensure_normtab(acx_ctx *c, const acx_serra09_params &p)
 {
     const int span = p.embed_full ? (p.m - 1) : p.m;           // (active pool: tau == 1)
     if (c->d_normtab && c->normtab_m == p.m && c->normtab_span == span) return ACX_OK;
-    if (c->d_normtab) { ACX_HIP(c, hipFree(c->d_normtab)); c->d_normtab = nullptr; }
-    if (c->d_noff) { ACX_HIP(c, hipFree(c->d_noff)); c->d_noff = nullptr; }
+    ACX_HIP(c, c->d_normtab.reset());
+    ACX_HIP(c, c->d_noff.reset());
     c->normtab_m = 0; c->normtab_span = -1;            // (a failure below must not leave the old key on a new, unfinished table)
-    c->s09_cap.normtab = c->s09_cap.noff = 0;
     std::vector<int64_t> &noff = c->h_noff;
     noff.assign((size_t)c->n_tracks + 1, 0);
     int64_t tot = 0;
@@ -515,10 +510,10 @@ int ensure_normtab(acx_ctx *c, const acx_serra09_params &p)
         tot += (int64_t)acx::NBIN * (Me + acx::NGUARD);      // + the +inf guard entries behind every rotation's row
     }
     noff[c->n_tracks] = tot;
-    ACX_HIP(c, hipMalloc((void **)&c->d_normtab, sizeof(float) * (std::max<int64_t>(1, tot) + 2 * POOL_SLACK)));
+    ACX_HIP(c, c->d_normtab.grow((size_t)(std::max<int64_t>(1, tot) + 2 * POOL_SLACK)));
     // +inf everywhere first: the guard entries and the slack are what the band kernel reads for columns outside a matrix
     ACX_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_normtab, 0x7f800000, (size_t)(std::max<int64_t>(1, tot) + 2 * POOL_SLACK), c->stream));
-    ACX_HIP(c, hipMalloc((void **)&c->d_noff, sizeof(int64_t) * noff.size()));
+    ACX_HIP(c, c->d_noff.grow(noff.size()));
     ACX_HIP(c, hipMemcpy(c->d_noff, noff.data(), sizeof(int64_t) * noff.size(), hipMemcpyHostToDevice));
     bool handled = true;
     {
@@ -780,7 +775,7 @@ void launch_streaming_class(acx_ctx *c, const PairDesc *dpd, const PairDesc *pd,
         const int tiles_x = (e.Mr + acx::LT - 1) / acx::LT, tiles_y = (e.Mq + acx::LT - 1) / acx::LT;
         ProfScope ps(c, KS_CSM, e.cells);
         hipLaunchKernelGGL(acx::csm_long_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, c->stream,
-                           c->d_frames, c->d_toff, dpd, c->d_scratch, tiles_x, p.oti_target, p.m);
+                           c->active_frames(), c->active_toff(), dpd, c->d_scratch, tiles_x, p.oti_target, p.m);
     }
     {   // L2: thresholds of every row and column;  L3: recurrence bitmap
         int maxRows = 0;
@@ -905,7 +900,7 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         {   // K0
             ProfScope ps(c, KS_OTI, acx::serra09_extent(pd, 0, B).cells);
             hipLaunchKernelGGL(acx::oti_kernel, dim3((B + 255) / 256), dim3(256), 0, c->stream,
-                               S.d_pd, B, c->d_gch, p.oti, p.oti_target, c->d_toff, c->d_noff);
+                               S.d_pd, B, c->d_gch, p.oti, p.oti_target, c->active_toff(), c->d_noff);
         }
         int64_t cls_cells[NC + 1];
         for (int cl = 0; cl <= NC; ++cl) {
@@ -1555,27 +1550,13 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
     return ACX_OK;
 }
 
-static void ef_free_pool(acx_ctx *c);
-
 static void free_pool(acx_ctx *c)
 {
-    if (c->d_frames && c->d_frames != c->d_frames0) (void)hipFree(c->d_frames);
-    if (c->d_toff && c->d_toff != c->d_toff0) (void)hipFree(c->d_toff);
-    if (c->d_frames0) (void)hipFree(c->d_frames0);
-    if (c->d_toff0) (void)hipFree(c->d_toff0);
-    if (c->d_frot) (void)hipFree(c->d_frot);
-    if (c->d_fh) (void)hipFree(c->d_fh);
-    c->d_fh = nullptr;
-    if (c->d_normtab) (void)hipFree(c->d_normtab);
-    if (c->d_noff) (void)hipFree(c->d_noff);
-    if (c->d_gch) (void)hipFree(c->d_gch);
-    c->d_frames = c->d_frames0 = nullptr;
-    c->d_toff = c->d_toff0 = nullptr;
-    c->d_frot = c->d_normtab = c->d_gch = nullptr;
-    c->d_noff = nullptr;
+    for (DeviceBuffer<float> *b : {&c->d_frames0, &c->d_frames, &c->d_frot, &c->d_normtab, &c->d_gch}) (void)b->reset();
+    for (DeviceBuffer<int64_t> *b : {&c->d_toff0, &c->d_toff, &c->d_noff}) (void)b->reset();
+    (void)c->d_fh.reset();
     c->normtab_m = 0; c->normtab_span = -1;
     c->pool_tau = 0;
-    c->s09_cap = {};
     c->fh_base_n = -1;
 }
 
@@ -1697,7 +1678,6 @@ acx_ctx *acx_create(int device, int *err)
 }
 
 static void comm_release(acx_ctx *c);
-static void ftm2d_free_pool(acx_ctx *c);
 
 void acx_destroy(acx_ctx *c)
 {
@@ -1720,11 +1700,7 @@ void acx_destroy(acx_ctx *c)
     if (c->qstream) (void)hipStreamDestroy(c->qstream);
     if (c->qstream2) (void)hipStreamDestroy(c->qstream2);
     (void)hipStreamDestroy(c->stream);
-    // the pools that are raw pointers (an active pool may alias the upload); every other buffer frees itself with the context
-    free_pool(c);
-    ef_free_pool(c);
-    ftm2d_free_pool(c);
-    delete c;
+    delete c;                                    // (every device and pinned buffer frees itself with the context)
 }
 
 #ifdef ACX_EF_TIMING
@@ -1788,12 +1764,12 @@ static int fill_pool(acx_ctx *c, const float *frames, const int64_t *offsets, in
     c->h_off0.assign(offsets, offsets + n_tracks + 1);
     c->n_tracks = n_tracks;
     c->dim = dim;
-    ACX_HIP(c, hipMalloc((void **)&c->d_frames0, sizeof(float) * std::max<int64_t>(1, total) * dim));
-    ACX_HIP(c, hipMalloc((void **)&c->d_toff0, sizeof(int64_t) * (n_tracks + 1)));
+    ACX_HIP(c, c->d_frames0.grow((size_t)std::max<int64_t>(1, total) * dim));
+    ACX_HIP(c, c->d_toff0.grow((size_t)n_tracks + 1));
     ACX_HIP(c, hipMemcpy(c->d_frames0, frames, sizeof(float) * total * dim, hipMemcpyHostToDevice));
     ACX_HIP(c, hipMemcpy(c->d_toff0, offsets, sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
     {
-        const int rc = scan_nonfinite(c, "upload_pool", "frames", c->d_frames0, total * dim, dim, 0, c->d_toff0, n_tracks);
+        const int rc = scan_nonfinite(c, "upload_pool", "frames", c->d_frames0.get(), total * dim, dim, 0, c->d_toff0.get(), n_tracks);
         if (rc != ACX_OK) return rc;
     }
     std::vector<float> cleaned;                     // policy ZERO and something was zeroed: the host-side sums below see what the device holds
@@ -1820,7 +1796,7 @@ static int fill_pool(acx_ctx *c, const float *frames, const int64_t *offsets, in
             for (int b = 1; b < acx::NBIN; ++b) if (acc[b] > mx) mx = acc[b];
             for (int b = 0; b < acx::NBIN; ++b) g[(size_t)t * acx::NBIN + b] = (mx > 0.0f) ? acc[b] / mx : acc[b];
         }
-        ACX_HIP(c, hipMalloc((void **)&c->d_gch, sizeof(float) * g.size()));
+        ACX_HIP(c, c->d_gch.grow(g.size()));
         ACX_HIP(c, hipMemcpy(c->d_gch, g.data(), sizeof(float) * g.size(), hipMemcpyHostToDevice));
     }
     return ACX_OK;
@@ -2340,15 +2316,12 @@ int acx_simple_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, int32_t sslen,
 
 static void ef_free_pool(acx_ctx *c)
 {
-    for (int k = 0; k < 3; ++k) if (c->d_ef[k]) { (void)hipFree(c->d_ef[k]); c->d_ef[k] = nullptr; }
-    for (int k = 0; k < 2; ++k) if (c->d_efn[k]) { (void)hipFree(c->d_efn[k]); c->d_efn[k] = nullptr; }
-    for (int k = 0; k < 3; ++k) if (c->d_efs[k]) { (void)hipFree(c->d_efs[k]); c->d_efs[k] = nullptr; }
-    for (int k = 0; k < 3; ++k) if (c->d_efsc[k]) { (void)hipFree(c->d_efsc[k]); c->d_efsc[k] = nullptr; }
-    if (c->d_efmed) { (void)hipFree(c->d_efmed); c->d_efmed = nullptr; }
-    if (c->d_efoff) { (void)hipFree(c->d_efoff); c->d_efoff = nullptr; }
+    for (int k = 0; k < 3; ++k) { (void)c->d_ef[k].reset(); (void)c->d_efs[k].reset(); (void)c->d_efsc[k].reset(); }
+    for (int k = 0; k < 2; ++k) (void)c->d_efn[k].reset();
+    (void)c->d_efmed.reset();
+    (void)c->d_efoff.reset();
     c->ef_ntracks = 0;
     c->ef_open = 0;
-    c->ef_cap = {};
 }
 
 // (Re)build the split pools the matrix-pipe GEMMs read from the f32 features: fmt 0 = three bf16 terms, fmt 1 = two
@@ -2361,7 +2334,7 @@ static int ef_build_splits(acx_ctx *c, int fmt)
         if (c->ef_kp[k] == 0 || !c->d_efs[k]) continue;
         if (fmt == 1) {
             if (!c->d_efsc[k]) {
-                ACX_HIP(c, hipMalloc((void **)&c->d_efsc[k], sizeof(float) * (nb + 32)));      // (+ slack: a group of 16 scales is read at once)
+                ACX_HIP(c, c->d_efsc[k].grow((size_t)nb + 32));      // (+ slack: a group of 16 scales is read at once)
                 ACX_HIP(c, hipMemsetAsync(c->d_efsc[k], 0, sizeof(float) * (nb + 32), c->stream));
             }
             hipLaunchKernelGGL(acx::ef_rowscale_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, c->stream, c->d_ef[k], c->d_efsc[k], nb, c->ef_dims[k]);
@@ -2393,17 +2366,17 @@ static int ef_norms_and_splits(acx_ctx *c, const int64_t *offsets, int32_t n_tra
     c->h_efoff.assign(offsets, offsets + n_tracks + 1);
     c->ef_ntracks = n_tracks;
     for (int k = 0; k < 3; ++k) c->ef_dims[k] = dims[k];
-    ACX_HIP(c, hipMalloc((void **)&c->d_efoff, sizeof(int64_t) * (n_tracks + 1)));
+    ACX_HIP(c, c->d_efoff.grow((size_t)n_tracks + 1));
     ACX_HIP(c, hipMemcpy(c->d_efoff, offsets, sizeof(int64_t) * (n_tracks + 1), hipMemcpyHostToDevice));
     {
         static const char *what[3] = {"mfcc blocks", "ssm blocks", "chroma blocks"};
         for (int k = 0; k < 3; ++k) {
-            const int rc = scan_nonfinite(c, "ef pool", what[k], c->d_ef[k], nb * dims[k], dims[k], 0, c->d_efoff, n_tracks);
+            const int rc = scan_nonfinite(c, "ef pool", what[k], c->d_ef[k].get(), nb * dims[k], dims[k], 0, c->d_efoff.get(), n_tracks);
             if (rc != ACX_OK) return rc;
         }
     }
     for (int k = 0; k < 2; ++k)
-        ACX_HIP(c, hipMalloc((void **)&c->d_efn[k], sizeof(float) * (nb + 32)));      // (+ slack: the rectangle GEMM reads a whole group of 16 norms)
+        ACX_HIP(c, c->d_efn[k].grow((size_t)nb + 32));      // (+ slack: the rectangle GEMM reads a whole group of 16 norms)
     if (nb > 0) {
         const unsigned g = (unsigned)((nb + 3) / 4);
         hipLaunchKernelGGL(acx::ef_rownorm_kernel, dim3(g), dim3(256), 0, c->stream, c->d_ef[2], nb, dims[2], 1, (float *)nullptr);
@@ -2417,7 +2390,7 @@ static int ef_norms_and_splits(acx_ctx *c, const int64_t *offsets, int32_t n_tra
         c->ef_kp[k] = (dims[k] + acx::EFB_BK - 1) / acx::EFB_BK * acx::EFB_BK;
         if (k == 2 && dims[2] % 96 != 0) { c->ef_kp[2] = 0; continue; }
         const int64_t nel = std::max<int64_t>(1, nb) * 3 * c->ef_kp[k];
-        ACX_HIP(c, hipMalloc((void **)&c->d_efs[k], sizeof(unsigned short) * nel));
+        ACX_HIP(c, c->d_efs[k].grow((size_t)nel));
     }
     {
         const int rc = ef_build_splits(c, c->ef_gemm == ACX_EF_GEMM_F16X2 ? 1 : 0);
@@ -2464,11 +2437,11 @@ int acx_ef_pool_begin(acx_ctx *c, const int64_t *offsets, int32_t n_tracks, cons
     c->nf_zeroed = 0;
     const int64_t nb = offsets[n_tracks];
     for (int k = 0; k < 3; ++k) {
-        const hipError_t e = hipMalloc((void **)&c->d_ef[k], sizeof(float) * std::max<int64_t>(1, nb) * dims[k]);
+        const hipError_t e = c->d_ef[k].grow((size_t)std::max<int64_t>(1, nb) * dims[k]);
         if (e != hipSuccess) { ef_free_pool(c); return fail(c, ACX_ERR_NOMEM, std::string("ef_pool_begin: the block features do not fit the device: ") + hipGetErrorString(e)); }
     }
     {
-        const hipError_t e = hipMalloc((void **)&c->d_efmed, sizeof(double) * 12 * n_tracks);
+        const hipError_t e = c->d_efmed.grow((size_t)12 * n_tracks);
         if (e != hipSuccess) { ef_free_pool(c); ACX_HIP(c, e); }
     }
     c->h_efoff.assign(offsets, offsets + n_tracks + 1);
@@ -2516,7 +2489,7 @@ int acx_ef_pool_end(acx_ctx *c)
     c->ef_filled.clear();
     ACX_HIP(c, hipSetDevice(c->device));
     {   // the chroma medians: one row of 12 per track
-        const int rc = scan_nonfinite<double>(c, "ef pool", "chroma median", c->d_efmed, (int64_t)12 * n_tracks, 12, 0, nullptr, n_tracks);
+        const int rc = scan_nonfinite<double>(c, "ef pool", "chroma median", c->d_efmed.get(), (int64_t)12 * n_tracks, 12, 0, nullptr, n_tracks);
         if (rc != ACX_OK) { ef_free_pool(c); return rc; }
     }
     const std::vector<int64_t> off = c->h_efoff;
@@ -2537,7 +2510,7 @@ int acx_ef_upload_pool(acx_ctx *c, const float *mfccs, const float *ssms, const 
     return rc;
 }
 
-// Block features of tracks [0, n_tracks) into fresh device arrays: the caller's, to adopt (release()) or to let drop.
+// Block features of tracks [0, n_tracks) into fresh device arrays: the caller's, to move into the context or to let drop.
 struct EfBlocks {
     DeviceBuffer<float> feat[3];         // mfcc / ssm / chroma block features
     DeviceBuffer<double> med;            // chroma median, 12 per track
@@ -2651,8 +2624,8 @@ int acx_ef_upload_raw_pool(acx_ctx *c, const float *chroma, const int64_t *chrom
     EfBlocks blocks;
     if ((rc = ef_build_blocks(c, chroma, chroma_offsets, mfcc, mfcc_offsets, ncoef, onsets, onset_offsets, n_tracks, *prep, boff,
                               blocks)) != ACX_OK) return rc;
-    for (int k = 0; k < 3; ++k) c->d_ef[k] = blocks.feat[k].release();
-    c->d_efmed = blocks.med.release();
+    for (int k = 0; k < 3; ++k) c->d_ef[k] = std::move(blocks.feat[k]);
+    c->d_efmed = std::move(blocks.med);
     const int32_t dims[3] = {prep->mfccs_per_block * ncoef, prep->mfccs_per_block * (prep->mfccs_per_block - 1) / 2, prep->chromas_per_block * 12};
     if (block_offsets_out) memcpy(block_offsets_out, boff.data(), sizeof(int64_t) * (n_tracks + 1));
     return ef_finish_pool(c, boff.data(), n_tracks, dims);
@@ -2788,9 +2761,7 @@ static int ftm2d_check_params(acx_ctx *c, const char *who, const acx_ftm2d_param
 
 static void ftm2d_free_pool(acx_ctx *c)
 {
-    if (c->d_ftm) (void)hipFree(c->d_ftm);
-    c->d_ftm = nullptr;
-    c->ftm_cap = 0;
+    (void)c->d_ftm.reset();
     c->ftm_n = c->ftm_dim = 0;
     c->ftm_open = 0;
     c->ftm_filled.clear();
@@ -2929,8 +2900,8 @@ int acx_ftm2d_pool_begin(acx_ctx *c, int32_t n_tracks, const acx_ftm2d_params *p
     ACX_HIP(c, hipSetDevice(c->device));
     ftm2d_free_pool(c);
     const int D = 12 * params->win;
-    const hipError_t e = hipMalloc((void **)&c->d_ftm, sizeof(double) * (size_t)n_tracks * D);
-    if (e != hipSuccess) { c->d_ftm = nullptr; return fail(c, ACX_ERR_NOMEM, std::string("ftm2d_pool_begin: ") + hipGetErrorString(e)); }
+    const hipError_t e = c->d_ftm.grow((size_t)n_tracks * D);
+    if (e != hipSuccess) return fail(c, ACX_ERR_NOMEM, std::string("ftm2d_pool_begin: ") + hipGetErrorString(e));
     c->ftm_n = n_tracks;
     c->ftm_dim = D;
     c->ftm_open = n_tracks;
@@ -2973,8 +2944,8 @@ int acx_ftm2d_upload_shingles(acx_ctx *c, const double *shingles, int32_t n_trac
     ACX_HIP(c, hipSetDevice(c->device));
     ftm2d_free_pool(c);
     const size_t n = (size_t)n_tracks * dim;
-    const hipError_t e = hipMalloc((void **)&c->d_ftm, sizeof(double) * n);
-    if (e != hipSuccess) { c->d_ftm = nullptr; return fail(c, ACX_ERR_NOMEM, std::string("ftm2d_upload_shingles: ") + hipGetErrorString(e)); }
+    const hipError_t e = c->d_ftm.grow(n);
+    if (e != hipSuccess) return fail(c, ACX_ERR_NOMEM, std::string("ftm2d_upload_shingles: ") + hipGetErrorString(e));
     ACX_HIP(c, hipMemcpy(c->d_ftm, shingles, sizeof(double) * n, hipMemcpyHostToDevice));
     c->ftm_n = n_tracks;
     c->ftm_dim = dim;
@@ -3415,37 +3386,24 @@ int acx_snf_fuse_dists(acx_ctx *c, const double *const *Ds, int32_t m, int32_t n
 // is also all a truncate does besides moving the end back.
 // ---------------------------------------------------------------------------------------
 
-// Grow and keep: the block `p` (capacity `cap` elements; 0 = exactly its `keep` live elements, as an upload leaves it) gets room
-// for `need` elements.  A block that is too small is replaced by one of max(need, 1.5 x capacity): allocated beside the old one,
-// the first `keep` elements copied device to device on the library's stream, then the old one freed.  `keep` counts whatever a
-// reader may touch: the live elements and, where a block has slack behind its end, that slack.  A failure leaves the old block.
+// Grow and keep: the block `b` gets room for `need` elements.  A block that is too small is replaced by one of max(need, 1.5 x capacity):
+// allocated beside the old one, the first `keep` elements copied device to device on the library's stream, then the old one freed.
+// `keep` counts whatever a reader may touch: the live elements and, where a block has slack behind its end, that slack.  A failure
+// leaves the old block.
 extern "C++" {
 template <typename T>
-static int grow_keep(acx_ctx *c, T *&p, size_t &cap, size_t keep, size_t need)
+static int grow_keep(acx_ctx *c, DeviceBuffer<T> &b, size_t keep, size_t need)
 {
-    if (cap < keep) cap = keep;
-    if (need <= cap) return ACX_OK;
-    const size_t ncap = std::max(need, cap + cap / 2);
+    if (need <= b.capacity()) return ACX_OK;
+    const size_t ncap = std::max(need, b.capacity() + b.capacity() / 2);
     DeviceBuffer<T> fresh;
     const hipError_t e = fresh.grow(ncap);
     if (e != hipSuccess)
         return fail(c, ACX_ERR_NOMEM, "append: hipMalloc of " + std::to_string(ncap * sizeof(T)) + " bytes failed: " + hipGetErrorString(e));
-    if (keep) ACX_HIP(c, hipMemcpyAsync(fresh.get(), p, sizeof(T) * keep, hipMemcpyDeviceToDevice, c->stream));
+    if (keep) ACX_HIP(c, hipMemcpyAsync(fresh.get(), b.get(), sizeof(T) * keep, hipMemcpyDeviceToDevice, c->stream));
     ACX_HIP(c, hipStreamSynchronize(c->stream));
-    if (p) (void)hipFree(p);
-    p = fresh.release();
-    cap = ncap;
+    b = std::move(fresh);                                   // (frees the old block)
     return ACX_OK;
-}
-
-template <typename T>
-static int grow_keep(acx_ctx *c, DeviceBuffer<T> &b, size_t keep, size_t need)
-{
-    size_t cap = b.capacity();
-    T *p = b.release();
-    const int rc = grow_keep(c, p, cap, keep, need);      // (a failure leaves the old block in p)
-    b.adopt(p, cap);
-    return rc;
 }
 }  // extern "C++"
 
@@ -3508,7 +3466,7 @@ static int s09_append_begin(acx_ctx *c, const char *who, const int64_t *rel, int
     const int dim = c->dim, tau = c->pool_tau;
     t.n0 = c->n_tracks; t.n1 = t.n0 + n_new;
     const int64_t total0 = c->h_off0[t.n0], total1 = total0 + rel[n_new];
-    t.active = dim == acx::NBIN && tau >= 1 && c->d_frames && c->d_toff;
+    t.active = dim == acx::NBIN && tau >= 1 && c->d_frames0 && c->d_toff0;
     t.table = t.active && c->d_normtab && c->d_noff && c->normtab_m > 0;
     const int64_t atotal0 = t.active ? c->h_off[t.n0] : 0, tot0 = t.table ? c->h_noff[t.n0] : 0;
     t.off0.resize((size_t)n_new + 1); t.aoff.assign((size_t)n_new + 1, atotal0); t.noff.assign((size_t)n_new + 1, tot0);
@@ -3525,34 +3483,26 @@ static int s09_append_begin(acx_ctx *c, const char *who, const int64_t *rel, int
         }
     }
     const int64_t atotal1 = t.aoff[n_new], tot1 = t.noff[n_new];
-    auto &cap = c->s09_cap;
     int rc;
-    // tau = 1: the active pool IS the uploaded one.  The aliases follow each block at once, whether its call replaced it or failed
-    // (then it is the old block still), so that no return below leaves them on a freed block.
-    const bool alias = t.active && tau == 1;
-    rc = grow_keep(c, c->d_frames0, cap.frames0, (size_t)total0 * dim, (size_t)std::max<int64_t>(1, total1) * dim);
-    if (alias) c->d_frames = c->d_frames0;
-    if (rc != ACX_OK) return rc;
-    rc = grow_keep(c, c->d_toff0, cap.toff0, (size_t)t.n0 + 1, (size_t)t.n1 + 1);
-    if (alias) c->d_toff = c->d_toff0;
-    if (rc != ACX_OK) return rc;
-    if (dim == acx::NBIN && c->d_gch && (rc = grow_keep(c, c->d_gch, cap.gch, (size_t)t.n0 * acx::NBIN, (size_t)t.n1 * acx::NBIN)) != ACX_OK) return rc;
-    if (t.active && tau > 1) {
-        if ((rc = grow_keep(c, c->d_frames, cap.frames, (size_t)atotal0 * acx::NBIN, (size_t)std::max<int64_t>(1, atotal1) * acx::NBIN)) != ACX_OK) return rc;
-        if ((rc = grow_keep(c, c->d_toff, cap.toff, (size_t)t.n0 + 1, (size_t)t.n1 + 1)) != ACX_OK) return rc;
+    if ((rc = grow_keep(c, c->d_frames0, (size_t)total0 * dim, (size_t)std::max<int64_t>(1, total1) * dim)) != ACX_OK) return rc;
+    if ((rc = grow_keep(c, c->d_toff0, (size_t)t.n0 + 1, (size_t)t.n1 + 1)) != ACX_OK) return rc;
+    if (dim == acx::NBIN && c->d_gch && (rc = grow_keep(c, c->d_gch, (size_t)t.n0 * acx::NBIN, (size_t)t.n1 * acx::NBIN)) != ACX_OK) return rc;
+    if (t.active && tau > 1) {                  // the decimated copy
+        if ((rc = grow_keep(c, c->d_frames, (size_t)atotal0 * acx::NBIN, (size_t)std::max<int64_t>(1, atotal1) * acx::NBIN)) != ACX_OK) return rc;
+        if ((rc = grow_keep(c, c->d_toff, (size_t)t.n0 + 1, (size_t)t.n1 + 1)) != ACX_OK) return rc;
     }
     // The rotated pool, the f16 pool and the norm table are kept WITH the slack behind their end (zeros / +inf, which the band
     // kernel's edge tiles of the last track read): a replaced block is then sealed as the old one was, and an append that fails
     // before it has written behind the end -- a non-finite value under REJECT, a later allocation -- needs no seal.
     if (t.active && c->d_frot &&
-        (rc = grow_keep(c, c->d_frot, cap.frot, (size_t)(atotal0 + 2 * POOL_SLACK) * acx::FROT, (size_t)(std::max<int64_t>(1, atotal1) + 2 * POOL_SLACK) * acx::FROT)) != ACX_OK)
+        (rc = grow_keep(c, c->d_frot, (size_t)(atotal0 + 2 * POOL_SLACK) * acx::FROT, (size_t)(std::max<int64_t>(1, atotal1) + 2 * POOL_SLACK) * acx::FROT)) != ACX_OK)
         return rc;
     if (t.active && c->d_fh &&
-        (rc = grow_keep(c, c->d_fh, cap.fh, (size_t)(atotal0 + 2 * POOL_SLACK) * acx::FH, (size_t)(std::max<int64_t>(1, atotal1) + 2 * POOL_SLACK) * acx::FH)) != ACX_OK)
+        (rc = grow_keep(c, c->d_fh, (size_t)(atotal0 + 2 * POOL_SLACK) * acx::FH, (size_t)(std::max<int64_t>(1, atotal1) + 2 * POOL_SLACK) * acx::FH)) != ACX_OK)
         return rc;
     if (t.table) {
-        if ((rc = grow_keep(c, c->d_normtab, cap.normtab, (size_t)(tot0 + 2 * POOL_SLACK), (size_t)(std::max<int64_t>(1, tot1) + 2 * POOL_SLACK))) != ACX_OK) return rc;
-        if ((rc = grow_keep(c, c->d_noff, cap.noff, (size_t)t.n0 + 1, (size_t)t.n1 + 1)) != ACX_OK) return rc;
+        if ((rc = grow_keep(c, c->d_normtab, (size_t)(tot0 + 2 * POOL_SLACK), (size_t)(std::max<int64_t>(1, tot1) + 2 * POOL_SLACK))) != ACX_OK) return rc;
+        if ((rc = grow_keep(c, c->d_noff, (size_t)t.n0 + 1, (size_t)t.n1 + 1)) != ACX_OK) return rc;
     }
     ACX_HIP(c, hipMemcpyAsync(c->d_toff0 + t.n0, t.off0.data(), sizeof(int64_t) * (n_new + 1), hipMemcpyHostToDevice, c->stream));
     ACX_HIP(c, hipStreamSynchronize(c->stream));
@@ -3565,7 +3515,7 @@ static int s09_append_derived(acx_ctx *c, const S09Tail &t)
     const int n_new = t.n1 - t.n0, tau = c->pool_tau;
     if (c->dim == acx::NBIN && c->d_gch) {
         hipLaunchKernelGGL(acx::chroma_profile_kernel, dim3((unsigned)((n_new + 15) / 16)), dim3(256), 0, c->stream,
-                           c->d_frames0, c->d_toff0 + t.n0, n_new, c->d_gch + (size_t)t.n0 * acx::NBIN);
+                           c->d_frames0.get(), c->d_toff0 + t.n0, n_new, c->d_gch + (size_t)t.n0 * acx::NBIN);
         ACX_HIP(c, hipGetLastError());
     }
     if (!t.active) return ACX_OK;
@@ -3574,11 +3524,11 @@ static int s09_append_derived(acx_ctx *c, const S09Tail &t)
         ACX_HIP(c, hipMemcpyAsync(c->d_toff + t.n0, t.aoff.data(), sizeof(int64_t) * (n_new + 1), hipMemcpyHostToDevice, c->stream));
         if (nfr > 0) {
             hipLaunchKernelGGL(acx::decimate_kernel, dim3(n_new, (t.maxT * acx::NBIN + 255) / 256), dim3(256), 0, c->stream,
-                               c->d_frames0, c->d_toff0 + t.n0, c->d_toff + t.n0, c->d_frames, tau);
+                               c->d_frames0.get(), c->d_toff0 + t.n0, c->d_toff + t.n0, c->d_frames.get(), tau);
             ACX_HIP(c, hipGetLastError());
         }
     }
-    const float *tail = c->d_frames + a0 * acx::NBIN;
+    const float *tail = c->active_frames() + a0 * acx::NBIN;
     if (c->d_frot) {
         if (nfr > 0) {
             hipLaunchKernelGGL(acx::rotpool_kernel, dim3((unsigned)std::min<int64_t>((nfr * acx::FROT + 255) / 256, 1 << 22)), dim3(256), 0, c->stream,
@@ -3604,8 +3554,8 @@ static int s09_append_derived(acx_ctx *c, const S09Tail &t)
         float mx;
         memcpy(&mx, &h_m, sizeof(mx));
         if (c->fh_base_n < 0 || !(mx <= 32768.0f)) {
-            ACX_HIP(c, hipFree(c->d_fh));
-            c->d_fh = nullptr; c->s09_cap.fh = 0; c->fh_base_n = -1;
+            ACX_HIP(c, c->d_fh.reset());
+            c->fh_base_n = -1;
         } else {
             ACX_HIP(c, hipMemsetAsync(c->d_fh + (POOL_SLACK + a0) * acx::FH, 0, sizeof(_Float16) * (size_t)(nfr + POOL_SLACK) * acx::FH, c->stream));
             if (nfr > 0) {
@@ -3729,8 +3679,8 @@ static int s09_truncate(acx_ctx *c, int32_t n)
     if (table) c->h_noff.resize((size_t)n + 1);
     // the f16x2 range check must still hold for the tracks that stay: it does while they contain the ones it was made for
     if (c->d_fh && (c->fh_base_n < 0 || n < c->fh_base_n)) {
-        ACX_HIP(c, hipFree(c->d_fh));
-        c->d_fh = nullptr; c->s09_cap.fh = 0; c->fh_base_n = -1;
+        ACX_HIP(c, c->d_fh.reset());
+        c->fh_base_n = -1;
     }
     plan_forget(c);
     return s09_seal(c, norm_hi);
@@ -3817,16 +3767,15 @@ int acx_ef_pool_append(acx_ctx *c, const float *mfccs, const float *ssms, const 
     const int n0 = c->ef_ntracks, n1 = n0 + n_new, fmt = c->ef_split_fmt, nt = fmt == 1 ? 2 : 3;
     const int64_t nb0 = c->h_efoff[n0], nbq = offsets[n_new], nb1 = nb0 + nbq;
     const int32_t *dims = c->ef_dims;
-    auto &cap = c->ef_cap;
     for (int k = 0; k < 3; ++k) {
-        if ((rc = grow_keep(c, c->d_ef[k], cap.ef[k], (size_t)nb0 * dims[k], (size_t)std::max<int64_t>(1, nb1) * dims[k])) != ACX_OK) return rc;
-        if (c->d_efs[k] && (rc = grow_keep(c, c->d_efs[k], cap.efs[k], (size_t)nb0 * 3 * c->ef_kp[k], (size_t)std::max<int64_t>(1, nb1) * 3 * c->ef_kp[k])) != ACX_OK) return rc;
+        if ((rc = grow_keep(c, c->d_ef[k], (size_t)nb0 * dims[k], (size_t)std::max<int64_t>(1, nb1) * dims[k])) != ACX_OK) return rc;
+        if (c->d_efs[k] && (rc = grow_keep(c, c->d_efs[k], (size_t)nb0 * 3 * c->ef_kp[k], (size_t)std::max<int64_t>(1, nb1) * 3 * c->ef_kp[k])) != ACX_OK) return rc;
         // (kept with their 32 rows of slack: a failure before the row kernels below then leaves nothing to seal)
-        if (c->d_efsc[k] && (rc = grow_keep(c, c->d_efsc[k], cap.efsc[k], (size_t)nb0 + 32, (size_t)nb1 + 32)) != ACX_OK) return rc;
-        if (k < 2 && (rc = grow_keep(c, c->d_efn[k], cap.efn[k], (size_t)nb0 + 32, (size_t)nb1 + 32)) != ACX_OK) return rc;
+        if (c->d_efsc[k] && (rc = grow_keep(c, c->d_efsc[k], (size_t)nb0 + 32, (size_t)nb1 + 32)) != ACX_OK) return rc;
+        if (k < 2 && (rc = grow_keep(c, c->d_efn[k], (size_t)nb0 + 32, (size_t)nb1 + 32)) != ACX_OK) return rc;
     }
-    if ((rc = grow_keep(c, c->d_efmed, cap.efmed, (size_t)12 * n0, (size_t)12 * n1)) != ACX_OK) return rc;
-    if ((rc = grow_keep(c, c->d_efoff, cap.efoff, (size_t)n0 + 1, (size_t)n1 + 1)) != ACX_OK) return rc;
+    if ((rc = grow_keep(c, c->d_efmed, (size_t)12 * n0, (size_t)12 * n1)) != ACX_OK) return rc;
+    if ((rc = grow_keep(c, c->d_efoff, (size_t)n0 + 1, (size_t)n1 + 1)) != ACX_OK) return rc;
     std::vector<int64_t> abs;
     if ((rc = append_offsets(c, c->d_efoff, n0, nb0, offsets, n_new, abs)) != ACX_OK) return rc;
     const float *src[3] = {mfccs, ssms, chromas};
@@ -3884,7 +3833,7 @@ int acx_ftm2d_append_shingles(acx_ctx *c, const double *shingles, int32_t n_new,
     ACX_HIP(c, hipSetDevice(c->device));
     quiesce(c);
     const size_t keep = (size_t)c->ftm_n * dim, add = (size_t)n_new * dim;
-    if ((rc = grow_keep(c, c->d_ftm, c->ftm_cap, keep, keep + add)) != ACX_OK) return rc;
+    if ((rc = grow_keep(c, c->d_ftm, keep, keep + add)) != ACX_OK) return rc;
     ACX_HIP(c, hipMemcpy(c->d_ftm + keep, shingles, sizeof(double) * add, hipMemcpyHostToDevice));
     c->ftm_n += n_new;
     plan_forget(c);

@@ -31,19 +31,11 @@ public:
 
     hipError_t reset()
     {
-        T *p = release();
+        T *p = p_;
+        p_ = nullptr; cap_ = 0;
         if (!p) return hipSuccess;
         return PINNED ? hipHostFree(p) : hipFree(p);
     }
-    // hands the block to the caller, who frees it
-    T *release()
-    {
-        T *p = p_;
-        p_ = nullptr; cap_ = 0;
-        return p;
-    }
-    // takes over a block of `cap` elements that the caller allocated (the buffer must be empty)
-    void adopt(T *p, size_t cap) { p_ = p; cap_ = p ? cap : 0; }
     // a failed allocation leaves the buffer empty and HIP's sticky error cleared
     hipError_t grow(size_t need)
     {

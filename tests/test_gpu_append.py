@@ -324,6 +324,52 @@ def test_truncate(name):
         ctx.close()
 
 
+@pytest.mark.parametrize("name", ALGOS)
+def test_upload_over_grown_pool(name):
+    """A new upload into a context whose pool has been grown (every block at 1.5 x its capacity, derived data included) and
+    truncated: the pool is the new list's alone, its blocks are exactly as large as their contents again -- so the first
+    append behind it reallocates -- and, Serra09, an upload that fails over a grown pool leaves no pool."""
+    from acoss_amd import _lib
+    P = _Pool(name)
+    T, n0 = P.tracks, _first(name)
+    few = P.all_pairs(n0)[:4]
+    prepare, tag = None, "default"
+    ctx = _context()
+    try:
+        if name == "earlyfusion":
+            prepare, tag = (lambda c: c.set_ef_gemm("f16x2")), "f16x2"
+            prepare(ctx)
+        P.upload(ctx, T[:n0])
+        if name in ("serra09", "chenfusion"):                     # decimated pool, norm table and (Serra09) f16 operand pool exist
+            P.pairs(ctx, few, _lib.serra09_params(tau=2))
+        if name == "serra09":
+            P.pairs(ctx, few, _lib.serra09_params(tau=2, arith="f16x2"))
+        if name == "earlyfusion":                                 # row scales and two-term splits exist
+            P.pairs(ctx, few)
+        P.append(ctx, T[n0:])
+        ctx.pool_truncate(P.algo, n0 + 1)
+        assert len(ctx.pool_lengths(P.algo)) == n0 + 1
+        P.upload(ctx, T[3:9])
+        _same_state(P.snapshot(ctx, T[3:9]), _fresh(name, ("reupload", tag, "3:9"), T[3:9], prepare=prepare))
+        P.append(ctx, T[9:12])
+        _same_state(P.snapshot(ctx, T[3:12]), _fresh(name, ("reupload", tag, "3:12"), T[3:12], prepare=prepare))
+        if name == "serra09":
+            # the decimated copy in the same lifecycle: rebuilt over the new pool (exact again), grown by an append, truncated
+            p2 = _lib.serra09_params(tau=2)
+            ctx.pool_truncate(P.algo, 6)
+            _same_state(P.snapshot(ctx, T[3:9], p2), _fresh(name, ("reupload", "tau2", "3:9"), T[3:9], params=p2))
+            P.append(ctx, T[9:12])
+            _same_state(P.snapshot(ctx, T[3:12], p2), _fresh(name, ("reupload", "tau2", "3:12"), T[3:12], params=p2))
+            bad = [T[0], T[1].copy(), T[2]]
+            bad[1][3, 5] = np.nan
+            with pytest.raises(ValueError, match=r"track 1 holds a non-finite value"):
+                P.upload(ctx, bad)
+            with pytest.raises(_lib.AcxError, match="not uploaded"):
+                ctx.serra09_pairs(P.all_pairs(3))
+    finally:
+        ctx.close()
+
+
 def _raw_tracks():
     """Raw chroma for fac = 4: lengths that are and are not multiples of 4, and one track whose bins b and b + 6 are equal --
     its chroma profile has period 6, so two transpositions tie in every OTI it takes part in, bit for bit."""
