@@ -304,7 +304,9 @@ ARITH = {"exact": 0, "f16x2": 1}
 def serra09_params(m=9, tau=1, kappa=0.095, oti=True, gamma_o=0.5, gamma_e=0.5, embed_full=0,
                    pct_mode=0, oti_target=0, dp_start=2, inclusive=1, dmax=0, arith="exact"):
     """acx_serra09_params.  arith: "exact" (default: the f32 Gram of the arithmetic spec) or "f16x2" (opt-in, m = 9:
-    two-term fp16 splits on the f16 matrix pipe -- f32-accurate, not bit-identical; include/acx.h ACX_ARITH_F16X2)."""
+    two-term fp16 splits on the f16 matrix pipe -- f32-accurate, not bit-identical; include/acx.h ACX_ARITH_F16X2).  "f16x2" accepts
+    pools whose largest feature magnitude lies in [2^-1, 2^15] (frame-max-normalised chroma: 1) and refuses others with
+    NotImplementedError: below 2^-1 the second fp16 term sinks into the subnormal step and the distances lose their accuracy."""
     return Serra09Params(int(m), int(tau), float(kappa), int(bool(oti)), float(gamma_o), float(gamma_e),
                          int(embed_full), int(pct_mode), int(oti_target), int(dp_start), int(inclusive), int(dmax),
                          int(ARITH.get(arith, arith)))

@@ -452,14 +452,20 @@ static __global__ void absmax_kernel(const float *__restrict__ v, int64_t n, uns
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
 
+constexpr float F16X2_MIN_MAX = 0.5f, F16X2_MAX_MAX = 32768.0f;     // the range of a pool's largest magnitude, here and in s09_append_derived's copy of the check
+
 int ensure_f16pool(acx_ctx *c)
 {
     if (c->d_fh) return ACX_OK;
     const int64_t total = c->h_off[c->n_tracks];
-    // The two-term fp16 split x = h1 + h2 carries 22 bits only while h1 is a NORMAL fp16 and finite: features above 65504 would
-    // become inf (NaN distances), features far below 1 lose their second term to fp16's subnormal range -- and the embedded
-    // norms, made from the exact f32 values, would no longer match the Gram.  HPCP / CREMA frames are normalised to a
-    // maximum of 1; a pool whose largest value lies outside [2^-8, 2^15] is refused (rescale it, or use ACX_ARITH_EXACT).
+    // The two-term fp16 split x = h1 + h2 carries 22 bits only while h1 is finite and h2 keeps its bits: features above 65504 would
+    // become inf (NaN distances), and h2 = fp16(x - h1) is rounded to fp16's subnormal step of 2^-24 -- an ABSOLUTE error, so every
+    // halving of the features doubles the error of 2 xy relative to them, while the embedded norms, made from the exact f32
+    // values, no longer match the Gram.  At a largest value of 1 that step is the smaller part of the error; from 2^-2 down it
+    // dominates (2 xy of frame-max-normalised chroma: 1.95e-6 at 1, 2.6e-6 at 2^-1, 5.3e-6 at 2^-2, 2.8e-4 at 2^-8, which was the
+    // limit once; tests/test_serra09_f64_ref.py derives it, tests/test_gpu_serra09_f16x2.py holds d2 to 3e-5 over the whole range).
+    // HPCP / CREMA frames are normalised to a maximum of 1; a pool whose largest value lies outside [2^-1, 2^15] is refused
+    // (rescale it by a power of two, or use ACX_ARITH_EXACT).
     unsigned h_m = 0u;
     if (total > 0) {
         DeviceBuffer<unsigned> d_m;
@@ -471,9 +477,10 @@ int ensure_f16pool(acx_ctx *c)
         ACX_HIP(c, hipStreamSynchronize(c->stream));
         float mx;
         memcpy(&mx, &h_m, sizeof(mx));
-        if (!(mx >= 0.00390625f && mx <= 32768.0f))
-            return fail(c, ACX_ERR_UNSUPPORTED, "serra09: arith = f16x2 needs features whose largest magnitude lies in [2^-8, 2^15] (this pool: " +
-                                                    std::to_string(mx) + "): rescale the pool or use the exact arithmetic");
+        if (!(mx >= F16X2_MIN_MAX && mx <= F16X2_MAX_MAX))
+            return fail(c, ACX_ERR_UNSUPPORTED, "serra09: arith = f16x2 needs features whose largest magnitude lies in [2^-1, 2^15] (this pool: " +
+                                                    std::to_string(mx) + "; below 2^-1 the second fp16 term loses its bits to the subnormal "
+                                                    "step and the distances their accuracy): rescale the pool by a power of two or use the exact arithmetic");
     }
     const size_t halfs = (size_t)(std::max<int64_t>(1, total) + 2 * POOL_SLACK) * acx::FH;
     DeviceBuffer<_Float16> fh;                         // the context's once it is complete
@@ -3553,7 +3560,7 @@ static int s09_append_derived(acx_ctx *c, const S09Tail &t)
         }
         float mx;
         memcpy(&mx, &h_m, sizeof(mx));
-        if (c->fh_base_n < 0 || !(mx <= 32768.0f)) {
+        if (c->fh_base_n < 0 || !(mx <= F16X2_MAX_MAX)) {
             ACX_HIP(c, c->d_fh.reset());
             c->fh_base_n = -1;
         } else {

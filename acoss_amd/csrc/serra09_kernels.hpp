@@ -1175,7 +1175,13 @@ __device__ __forceinline__ void band_row_bits(const float (&xr)[NV], const TCG (
 #define ACX_STAMP_PARM
 #define ACX_STAMP_ARG
 #endif
-template <int NV, int ROLE>
+// SNAP: the d2-domain threshold may be an order statistic of the row itself (thr = slo, below).  That holds only where every pass
+// that compares against it computes the SAME bits for a cell.  The exact Gram is bit-symmetric in its two tracks; the f16x2 Gram is
+// not (the two passes put x1 y2 and x2 y1 into different k-slots and instructions, so their d2 differ in the last bits), and a
+// column threshold snapped to the column pass's cell lost that very cell -- the last recurrent one of the column -- in the row pass
+// whenever its d2 there came out one ulp higher.  The f16x2 column pass therefore stores the closed form (the largest f32 whose
+// root is <= eps), which separates the cells of ANY pass the way `sqrtf(d2) <= eps` does.
+template <int NV, int ROLE, bool SNAP = true>
 __device__ __forceinline__ void band_row_tail(float (&xr)[NV], float *smem, int wave, int lane, int row, int MA, int MB,
                                               int cshift, const PairDesc &P, float *__restrict__ thr,
                                               unsigned long long *__restrict__ bits, const PctPos &pp, int pct_mode,
@@ -1249,7 +1255,7 @@ __device__ __forceinline__ void band_row_tail(float (&xr)[NV], float *smem, int 
     // products, the sum and the two correctly rounded roots can move (each <= 2^-24 relative).  Then thr = slo (see below) and
     // neither sqrtf expansion nor eps is evaluated -- unless the caller wants eps itself (the debug entry point).
     const bool weights_ok = interp && ihi == ilo + 1 && inclusive && fl >= 1.0f && (ce - kf) >= 0.00390625f && (kf - fl) >= 0.00390625f;
-    if (!want_eps && weights_ok && shi < INF && (shi - slo) > shi * 0.000244140625f) {
+    if (SNAP && !want_eps && weights_ok && shi < INF && (shi - slo) > shi * 0.000244140625f) {
         ACX_STAMP(6);
         ACX_ABL_EXIT(4, slo);
         if (lane == 0) (thr + P.offX)[role ? P.pitchT + row : row] = slo;
@@ -1267,7 +1273,7 @@ __device__ __forceinline__ void band_row_tail(float (&xr)[NV], float *smem, int 
     // interpolation collapsed (eps == dhi: ties, an exact-integer position, adjacent roots), eps outside [dlo, dhi) (pct_mode 1
     // at an exact-integer position), the exclusive comparison -- takes the closed form; the branch is wave-uniform.
     float thr_row;
-    if (inclusive && dlo <= eps && eps < dhi) thr_row = slo;
+    if (SNAP && inclusive && dlo <= eps && eps < dhi) thr_row = slo;
     else thr_row = d2_threshold(eps, inclusive);
     ACX_STAMP(6);        // eps + threshold
     float *X = thr + P.offX;
@@ -1673,7 +1679,7 @@ __global__ __launch_bounds__(BAND_THREADS, band_waves_per_simd(M, V4, ARITH)) vo
       for (int t = 0; t < NV; ++t) keep_ += xr[t];
       ACX_ABL_EXIT(2, keep_); }
 #endif
-    band_row_tail<NV, ROLE>(xr, smem, wave, lane, i0 + wave, MA, MB, (BAND - 1) - wave, P, thr, role == 0 ? bits : nullptr,
+    band_row_tail<NV, ROLE, ARITH == 0 || ROLE == 0>(xr, smem, wave, lane, i0 + wave, MA, MB, (BAND - 1) - wave, P, thr, role == 0 ? bits : nullptr,
                             pp, pct_mode, inclusive, want_eps ACX_STAMP_ARG);
 }
 

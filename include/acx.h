@@ -143,14 +143,18 @@ typedef struct {
  * Arithmetic of the frame Gram behind the distance matrix (everything else is the same code in both):
  *   ACX_ARITH_EXACT  v_mfma_f32_16x16x4_f32 chains: the f32 spec the oracle reproduces bit for bit
  *   ACX_ARITH_F16X2  opt-in, m = 9 only: every bin value as two fp16 terms x = h1 + h2 (22-23 significant bits; the matrix pipe
- *                    keeps fp16 subnormals), products x1 y1 + x1 y2 + x2 y1 on v_mfma_f32_16x16x32_f16 + 16x16x16_f16, which run
+ *                    keeps fp16 subnormals), products x1 y1 + x1 y2 + x2 y1 + x2 y2 on two v_mfma_f32_16x16x32_f16, which run
  *                    beside other waves' VALU work where an f32 MFMA blocks the SIMD.  As accurate as the f32 chain against f64
  *                    (2e-7 relative, scripts/ubench/mfma_f16_probe.hip) but NOT the same bits: scores are graded by north_star's
  *                    tolerance (|score difference| <= 2.0, identical MAP / MR on cover sets; tests/test_gpu_serra09.py), the
  *                    default and bench.py's headline stay exact.  Pairs beyond the band kernel (rows of more than 2041 cells)
- *                    take the exact streaming kernels in either mode.  INPUT RANGE: the split keeps its 22 bits only while the
- *                    first term is a normal, finite fp16 -- a pool whose largest magnitude lies outside [2^-8, 2^15] is
- *                    refused with ACX_ERR_UNSUPPORTED (HPCP / CREMA frames are normalised to a maximum of 1).
+ *                    take the exact streaming kernels in either mode.  INPUT RANGE: the first term must be finite, and the
+ *                    second is rounded to fp16's subnormal step of 2^-24, an absolute error that doubles relative to the
+ *                    features with every halving of them -- a pool whose largest magnitude lies outside [2^-1, 2^15] is
+ *                    refused with ACX_ERR_UNSUPPORTED (HPCP / CREMA frames are normalised to a maximum of 1; rescale anything
+ *                    else by a power of two).  Inside that range squared distances of frame-max-normalised features lie within
+ *                    3e-5 x (largest magnitude)^2 of f64 (1.3e-5 measured; the exact chain: 1.2e-5), and the recurrence plot is
+ *                    the f64 plot on every cell those distances decide (tests/test_gpu_serra09_f16x2.py).
  */
 enum { ACX_ARITH_EXACT = 0, ACX_ARITH_F16X2 = 1 };
 
