@@ -37,7 +37,7 @@ EXPORTS = [
     "acx_ftm2d_upload_shingles", "acx_ftm2d_download_shingles", "acx_ftm2d_debug_track", "acx_ftm2d_pairs",
     "acx_rank_columns", "acx_topk_rows",
     "acx_query_scores", "acx_query_topk", "acx_query_ranks", "acx_query_topk_lists",
-    "acx_serra09_debug_bits", "acx_serra09_plan", "acx_serra09_family_name",
+    "acx_serra09_debug_bits", "acx_serra09_plan", "acx_serra09_family_name", "acx_serra09_fast_tail", "acx_serra09_fast_tail_launches",
     "acx_pool_append", "acx_pool_append_raw", "acx_pool_append_f64", "acx_ef_pool_append", "acx_ftm2d_append_shingles",
     "acx_pool_truncate",
     "acx_serra09_align", "acx_qmax_locate_binary",
@@ -219,6 +219,9 @@ def load():
     L.acx_serra09_plan.argtypes = [lp, ctypes.c_int32, ip, ctypes.c_int64, pp, ctypes.c_int64, ctypes.POINTER(Serra09PlanRec)]
     L.acx_serra09_family_name.restype = ctypes.c_char_p
     L.acx_serra09_family_name.argtypes = [ctypes.c_int32, ctypes.c_int32]
+    L.acx_serra09_fast_tail.argtypes = [pp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+    L.acx_serra09_fast_tail_launches.restype = ctypes.c_int64
+    L.acx_serra09_fast_tail_launches.argtypes = []
     L.acx_serra09_embed_len.restype = ctypes.c_int32
     L.acx_serra09_embed_len.argtypes = [ctypes.c_int32, pp]
     L.acx_profile_enable.argtypes = [vp, ctypes.c_int]
@@ -408,6 +411,22 @@ def serra09_plan(lengths, pairs, params=None, scratch_limit=0):
         err.code = rc
         raise err
     return out
+
+
+def serra09_fast_tail(n_cells, role, params=None, debug=False):
+    """acx_serra09_fast_tail: whether a band pass with rows of n_cells cells (role 1: column pass, role 0: row pass) may take the
+    product-path copy of the band kernel's row tail -- a pure host function, no GPU needed."""
+    L = load()
+    params = params if params is not None else serra09_params()
+    rc = L.acx_serra09_fast_tail(ctypes.byref(params), int(n_cells), int(role), int(bool(debug)))
+    if rc < 0:
+        raise ValueError("acx_serra09_fast_tail: bad argument")
+    return bool(rc)
+
+
+def serra09_fast_tail_launches():
+    """acx_serra09_fast_tail_launches: band passes of this process that launched the product-path copy of the wide kernel so far."""
+    return int(load().acx_serra09_fast_tail_launches())
 
 
 def serra09_family_name(family, m):

@@ -348,13 +348,20 @@ int check_params(acx_ctx *c, const acx_serra09_params &p)
 constexpr int64_t POOL_SLACK = 96;      // frames (rotated pool) / floats (norm table) on either side
 
 // band_kernel is launched from its own translation unit (acx_band.hip)
-bool launch_band(acx_ctx *c, int m, const PairDesc *dpd, int B, int maxRows, int cls, const acx_serra09_params &p, int role, int write_d2,
-                 int want_eps)
+// (hpd: the host's copy of the same B descriptors, for the plan's per-launch decisions)
+bool launch_band(acx_ctx *c, int m, const PairDesc *dpd, const std::vector<PairDesc> &hpd, int b0, int B, int maxRows, int cls,
+                 const acx_serra09_params &p, int role, int write_d2, int want_eps)
 {
     const float *operands = p.arith == ACX_ARITH_F16X2 ? reinterpret_cast<const float *>(c->d_fh + POOL_SLACK * acx::FH) : c->d_frot + POOL_SLACK * acx::FROT;
     acx::BandLaunch L{c->stream, operands, c->active_toff(), c->d_normtab + POOL_SLACK, c->d_noff, c->d_scratch, c->d_thr,
-                      c->d_bits, p.kappa, p.pct_mode, p.inclusive, p.oti_target};
-    return acx::launch_band_kernel(L, m, dpd, B, maxRows, acx::serra09_band_family(cls, m, p.arith), role, write_d2, want_eps, p.arith);
+                      c->d_bits, p.kappa, p.pct_mode, p.inclusive, p.oti_target, 0};
+    const int family = acx::serra09_band_family(cls, m, p.arith);
+    bool ok = true;
+    for (const acx::Serra09Run &r : acx::serra09_fast_tail_runs(p, family, role, write_d2 != 0, want_eps != 0, c->d_bits != nullptr, hpd, b0, b0 + B)) {
+        L.fast_tail = r.fast ? 1 : 0;
+        ok = ok && acx::launch_band_kernel(L, m, dpd + (r.begin - b0), r.end - r.begin, maxRows, family, role, write_d2, want_eps, p.arith);
+    }
+    return ok;
 }
 
 template <int M>
@@ -924,12 +931,12 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
                     if (Bq <= 0) continue;
                     const acx::Serra09Extent qe = acx::serra09_extent(pd, q0, q0 + Bq);
                     ProfScope ps(c, KS_BAND, qe.cells);
-                    ok = ok && launch_band(c, p.m, S.d_pd + q0, Bq, qe.Mr, cq, p, 1, 0, dbg ? 1 : 0);
+                    ok = ok && launch_band(c, p.m, S.d_pd + q0, pd, q0, Bq, qe.Mr, cq, p, 1, 0, dbg ? 1 : 0);
                 }
                 if (!bits_free) { ACX_HIP(c, hipStreamWaitEvent(c->stream, Sprev.done, 0)); bits_free = true; }
                 {   // K1' role 0: rows = query frames (Mr cells each) -> row thresholds + recurrence bitmap (needs role 1)
                     ProfScope ps(c, KS_BAND, ce.cells);
-                    ok = ok && launch_band(c, p.m, S.d_pd + b0, Bc, ce.Mq, cl, p, 0, dbg ? 1 : 0, dbg ? 1 : 0);
+                    ok = ok && launch_band(c, p.m, S.d_pd + b0, pd, b0, Bc, ce.Mq, cl, p, 0, dbg ? 1 : 0, dbg ? 1 : 0);
                 }
                 if (use_q) ACX_HIP(c, hipEventRecord(S.cls_ev[cl], c->stream));
                 if (!ok) return fail(c, ACX_ERR_UNSUPPORTED, "serra09: this build of libacx has no band kernel for the requested m");
@@ -3981,6 +3988,18 @@ int acx_serra09_plan(const int64_t *lengths, int32_t n_tracks, const int32_t *pa
 }
 
 const char *acx_serra09_family_name(int32_t family, int32_t m) { return acx::serra09_family_name(family, m); }
+
+int64_t acx_serra09_fast_tail_launches(void) { return (int64_t)acx::fast_tail_launches(); }
+
+int acx_serra09_fast_tail(const acx_serra09_params *params, int32_t n_cells, int32_t role, int32_t debug)
+{
+    if (!params || n_cells < 1 || check_params(nullptr, *params) != ACX_OK) return ACX_ERR_INVALID;
+    const int cl = acx::serra09_row_class(n_cells);
+    if (cl >= acx::SERRA09_NC || params->m > acx::MAX_M) return 0;      // the streaming kernels
+    const bool dbg = debug != 0;
+    return acx::serra09_fast_tail_params(*params, acx::serra09_band_family(cl, params->m, params->arith), role, dbg && role == 0, dbg, true) &&
+           acx::serra09_fast_tail_row(acx::pct_position(n_cells, params->kappa, params->pct_mode), n_cells) ? 1 : 0;
+}
 
 int acx_pool_lengths(acx_ctx *c, int32_t algo, int64_t *lengths, int32_t capacity, int32_t *n_tracks)
 {

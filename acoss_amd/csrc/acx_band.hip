@@ -5,6 +5,9 @@
 // ACX_BAND2 switch; the launcher receives the family and maps it onto the instantiations.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <cassert>
+
 #include "serra09_kernels.hpp"
 #include "serra09_band2_kernels.hpp"
 #include "serra09_plan.hpp"
@@ -13,17 +16,27 @@ namespace acx {
 
 namespace {
 
+std::atomic<long long> g_fast_tail_launches{0};      // band passes of this process that took the FAST copy (fast_tail_launches)
+
 // `family`: the plan's answer for the pass's size class (serra09_band_family, serra09_plan.hpp -- the class limits, the choice
 // per stack size and arithmetic, and ACX_BAND2 live there); this switch only maps it onto the instantiations.
 template <int M>
 bool launch_band_m(const BandLaunch &L, const PairDesc *dpd, int B, int maxRows, int family, int role, int write_d2, int want_eps, int arith)
 {
     const dim3 grid((maxRows + BAND - 1) / BAND, B, 1);
-#define ACX_BAND_K(V4_, R_, W_, A_) hipLaunchKernelGGL((band_kernel<M, V4_, R_, W_, A_>), grid, dim3(BAND_THREADS), 0, L.stream, \
+#define ACX_BAND_K(V4_, R_, W_, A_, F_) hipLaunchKernelGGL((band_kernel<M, V4_, R_, W_, A_, F_>), grid, dim3(BAND_THREADS), 0, L.stream, \
                                                   L.frot, L.toff, L.normtab, L.noff, dpd, L.scratch, L.thr, L.bits, L.kappa, \
                                                   L.pct_mode, L.inclusive, L.oti_target, want_eps)
     // (the variant that also writes D2 exists for the row pass only: the debug entry point)
-#define ACX_BAND_A(V4_, A_) do { if (role) ACX_BAND_K(V4_, 1, false, A_); else if (write_d2) ACX_BAND_K(V4_, 0, true, A_); else ACX_BAND_K(V4_, 0, false, A_); } while (0)
+#define ACX_BAND_A(V4_, A_) do { if (role) ACX_BAND_K(V4_, 1, false, A_, false); else if (write_d2) ACX_BAND_K(V4_, 0, true, A_, false); else ACX_BAND_K(V4_, 0, false, A_, false); } while (0)
+    // the product-path tail (band_row_tail's FAST copy): the plan found its conditions to hold for the pass and for every pair of the
+    // launch (serra09_fast_tail_runs, serra09_plan.hpp: wide class, exact arithmetic, no D2, no eps, a bitmap in the row pass)
+    if (L.fast_tail) {
+        assert(family == ACX_SERRA09_FAMILY_BAND_8 && arith == ACX_ARITH_EXACT && !write_d2 && !want_eps);    // (serra09_fast_tail_params)
+        if (role) ACX_BAND_K(8, 1, false, 0, true); else ACX_BAND_K(8, 0, false, 0, true);
+        g_fast_tail_launches.fetch_add(1, std::memory_order_relaxed);
+        return true;
+    }
     // the opt-in f16x2 Gram: the default stack size only
 #define ACX_BAND(V4_) do { if (arith == ACX_ARITH_EXACT) ACX_BAND_A(V4_, 0); else if constexpr (M == 9) ACX_BAND_A(V4_, 1); else return false; return true; } while (0)
     // the kernels of two and four rows per wave (serra09_band2_kernels.hpp): m <= 9, the exact arithmetic
@@ -69,6 +82,7 @@ bool launch_band_kernel(const BandLaunch &L, int m, const PairDesc *dpd, int B, 
     return false;
 }
 
+long long fast_tail_launches() { return g_fast_tail_launches.load(std::memory_order_relaxed); }
 
 }  // namespace acx
 

@@ -990,6 +990,7 @@ struct BandLaunch {
     unsigned long long *bits;
     float kappa;
     int pct_mode, inclusive, oti_target;
+    int fast_tail;                  // the pass may take the product-path tail (serra09_fast_tail_runs, serra09_plan.hpp: every pair of this launch qualifies)
 };
 // role 1 / 0 over B pairs of one size class; false when the stack size m has no instantiation of `family`
 // (family: ACX_SERRA09_FAMILY_* as serra09_band_family (serra09_plan.hpp) chose it for the pass's class, m and arith)
@@ -997,6 +998,8 @@ struct BandLaunch {
 // (arith: 0 = the exact f32 Gram, 1 = the opt-in f16x2 Gram, m = 9 only; L.frot then points at the f16 operand pool)
 bool launch_band_kernel(const BandLaunch &L, int m, const struct PairDesc *dpd, int B, int maxRows, int family, int role,
                         int write_d2, int want_eps, int arith);
+// band passes of this process that launched the FAST copy of the wide kernel so far (tests observe the dispatch through it)
+long long fast_tail_launches();
 
 // development builds only (scripts/ab_build.sh ablN -DACX_ABL=N): the band kernel stops behind stage N -- 1 sweep, 2 exchange +
 // row read, 3 selection, 4 eps / threshold -- so that instruction counters (rocprofv3 --pmc SQ_INSTS_*) can be read per stage
@@ -1087,7 +1090,10 @@ struct RowGeom {
 };
 
 // The bitmap step of band_row_tail (row pass only): the row in registers against min(row threshold, column thresholds).
-template <int NV, int ROLE, bool TC_VIA_LDS, typename TCG>
+// FAST (the product-path tail, see band_row_tail): a bitmap is known to be wanted.  MASK = false: the caller knows thr_row < +inf, and
+// then the `valid` mask is redundant -- a slot without a column holds +inf (the guard norms, see band_kernel), min(column threshold,
+// thr_row) is finite or NaN whatever the arena holds beside the pair's columns, and +inf <= that is false: the bit is 0 by itself.
+template <int NV, int ROLE, bool TC_VIA_LDS, bool FAST = false, bool MASK = true, typename TCG>
 __device__ __forceinline__ void band_row_bits(const float (&xr)[NV], const TCG (&tcg)[NV / 4], float thr_row, float *myrow, int lane,
                                               int row, int MB, int cshift, const PairDesc &P, float *__restrict__ thr,
                                               unsigned long long *__restrict__ bits)
@@ -1100,7 +1106,7 @@ __device__ __forceinline__ void band_row_bits(const float (&xr)[NV], const TCG (
     // wave still holds in registers and emit it as a bitmap.  256 bytes per row instead of 8 KB of f32.
     // A lane owns NV consecutive slots, i.e. NV consecutive bits: R = [d2 <= min(thr_row, thr_col)] is
     // shifted into the lane's own word bit by bit (compare -> carry -> add-with-carry), no cross-lane traffic.
-    if (ROLE == 0 && bits) {
+    if (ROLE == 0 && (FAST || bits)) {
         // column thresholds (d2 domain) of the lane's NV slots.  In the wide class, read straight from memory, they
         // are 128 contiguous bytes per lane -- every load instruction would touch 64 different lines, and those eight
         // loads measured 4.5 of the band kernels' 47.8 ms.  So the wave reads the row's thresholds
@@ -1129,11 +1135,13 @@ __device__ __forceinline__ void band_row_bits(const float (&xr)[NV], const TCG (
             }
         }
         // slots of this lane whose column exists: t in [lo, hi)
-        int lo = cshift - lane * NV, hi = MB + cshift - lane * NV;
-        lo = lo < 0 ? 0 : lo;
-        hi = hi > NV ? NV : hi;
         unsigned valid = 0u;
-        if (hi > lo) valid = (hi - lo >= 32 ? ~0u : ((1u << (hi - lo)) - 1u)) << lo;
+        if constexpr (MASK) {
+            int lo = cshift - lane * NV, hi = MB + cshift - lane * NV;
+            lo = lo < 0 ? 0 : lo;
+            hi = hi > NV ? NV : hi;
+            if (hi > lo) valid = (hi - lo >= 32 ? ~0u : ((1u << (hi - lo)) - 1u)) << lo;
+        }
         unsigned acc = 0u;
 #pragma unroll
         for (int t = NV - 1; t >= 0; --t) {
@@ -1141,7 +1149,7 @@ __device__ __forceinline__ void band_row_bits(const float (&xr)[NV], const TCG (
             asm("v_min_f32 %0, %1, %2" : "=v"(mthr) : "v"(tcv[t]), "v"(thr_row));
             asm("v_cmp_le_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(acc) : "v"(xr[t]), "v"(mthr) : "vcc");
         }
-        acc &= valid;
+        if constexpr (MASK) acc &= valid;
         // NV < 32: neighbouring lanes complete a dword
         // (the lanes that store -- every second / fourth -- take their neighbours' bits inside their quad: DPP quad_perm
         //  [1,1,3,3] / [1,2,3,3], [2,3,3,3] instead of ds_bpermute round trips)
@@ -1155,7 +1163,8 @@ __device__ __forceinline__ void band_row_bits(const float (&xr)[NV], const TCG (
         unsigned *rowbits = reinterpret_cast<unsigned *>(bits + P.offT + (size_t)row * P.nw);
         const int ndw = 2 * P.nw, d = lane / LPD;
         if ((lane & (LPD - 1)) == 0 && d < ndw) rowbits[d] = acc;
-        for (int z = 2 * NV + lane; z < ndw; z += 64) rowbits[z] = 0u;  // words beyond this size class
+        if constexpr (!(FAST && NV == 32))                              // (a wide-class row has at most 2 NV = 64 dwords: nothing beyond)
+            for (int z = 2 * NV + lane; z < ndw; z += 64) rowbits[z] = 0u;  // words beyond this size class
     }
 }
 
@@ -1181,7 +1190,13 @@ __device__ __forceinline__ void band_row_bits(const float (&xr)[NV], const TCG (
 // column threshold snapped to the column pass's cell lost that very cell -- the last recurrent one of the column -- in the row pass
 // whenever its d2 there came out one ulp higher.  The f16x2 column pass therefore stores the closed form (the largest f32 whose
 // root is <= eps), which separates the cells of ANY pass the way `sqrtf(d2) <= eps` does.
-template <int NV, int ROLE, bool SNAP = true>
+// FAST: the product-path tail (wide class, exact arithmetic; serra09_fast_tail_runs in serra09_plan.hpp decides on the host, per launch):
+// pct_mode 0 with ihi == ilo + 1, the inclusive comparison, no eps wanted, the weight conditions of `weights_ok`, use_pivot for every
+// row length of the launch and, in the row pass, a bitmap.  Those tests are constants here, so the path row read -> pivot selection ->
+// gap test -> threshold -> bitmap is straight-line code; what remains are the selection's data-dependent exits and the gap test, which
+// fall into the same generic continuation as ever (unfiltered histogram, narrowing selection, closed-form threshold).  Same
+// instructions on the same values: thresholds and bitmaps are bit-identical to the generic copy's.
+template <int NV, int ROLE, bool SNAP = true, bool FAST = false>
 __device__ __forceinline__ void band_row_tail(float (&xr)[NV], float *smem, int wave, int lane, int row, int MA, int MB,
                                               int cshift, const PairDesc &P, float *__restrict__ thr,
                                               unsigned long long *__restrict__ bits, const PctPos &pp, int pct_mode,
@@ -1195,18 +1210,20 @@ __device__ __forceinline__ void band_row_tail(float (&xr)[NV], float *smem, int 
     constexpr int role = ROLE;
     const float INF = __builtin_inff();
     const int hist_off = RG::hist_off(wave);
+    static_assert(!FAST || SNAP, "the product-path tail snaps its thresholds");
     if (row >= MA) return;
     const int n = MB;
     const float kf = pp.kf, fl = pp.fl, ce = pp.ce;
     const int ilo = pp.ilo, ihi = pp.ihi, k = pp.k;
-    const bool interp = (pct_mode == 0 || pct_mode == 1);
+    if constexpr (FAST) { pct_mode = 0; inclusive = 1; want_eps = 0; }
+    const bool interp = FAST || (pct_mode == 0 || pct_mode == 1);
     float *myrow = smem + wave * ROWP;
     float slo, shi;
     typedef __attribute__((address_space(3))) void lds_void;
     const unsigned hist_addr = (unsigned)(uintptr_t)(lds_void *)(smem + hist_off);
     // Small kappa (the default 0.095): the pivot-filtered histogram first (wave_select_pivot); it gives up
     // when fewer than k + 2 cells lie below its pivot, and the unfiltered pass takes over.
-    const bool use_pivot = (ihi + 2) * 9 <= n;
+    const bool use_pivot = FAST || (ihi + 2) * 9 <= n;
     auto zero_hist = [&](int bins) {
         float *h = smem + hist_off;
         for (int q = 0; q < bins / 256; ++q) *reinterpret_cast<float4 *>(h + 256 * q + 4 * lane) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1219,18 +1236,19 @@ __device__ __forceinline__ void band_row_tail(float (&xr)[NV], float *smem, int 
     if (use_pivot) {
         const int g0 = (lane & ~(PGRP - 1)) * NV;                       // first slot of the lane's group
         const bool group_full = g0 >= cshift && g0 + PGRP * NV <= end_valid;
-        done = wave_select_pivot<NV, PBINS, PGRP>(xr, k, interp && ihi != ilo, hist_addr, myrow, lane, slo, shi,
+        done = wave_select_pivot<NV, PBINS, PGRP>(xr, k, FAST || (interp && ihi != ilo), hist_addr, myrow, lane, slo, shi,
                                                   lane_has_data, group_full, PDELTA);
+        if constexpr (FAST) done = __builtin_expect(done, true);        // (the exits below are the cold continuation)
         if (!done) zero_hist(FBINS);
     }
     if (!done)
-        done = wave_select_fast<NV, FBINS, FCOPIES>(xr, k, interp && ihi != ilo, hist_addr, myrow, lane, slo, shi, lane_has_data);
+        done = wave_select_fast<NV, FBINS, FCOPIES>(xr, k, FAST || (interp && ihi != ilo), hist_addr, myrow, lane, slo, shi, lane_has_data);
     if (!done) {
         unsigned *ghist = reinterpret_cast<unsigned *>(myrow) + 64;
         unsigned *counter = reinterpret_cast<unsigned *>(myrow) + 64 + SelGeom<GBINS>::SLOTS;
         const SelectResult sr = wave_select_regs<NV, GBINS>(xr, k, ghist, myrow, counter, lane, interp);
         slo = sr.value;
-        shi = (interp && ihi != ilo && sr.cnt_le <= ihi) ? sr.next : sr.value;     // rank ihi is the next distinct value
+        shi = ((FAST || (interp && ihi != ilo)) && sr.cnt_le <= ihi) ? sr.next : sr.value;     // rank ihi is the next distinct value
     }
     ACX_STAMP(5);        // selection
     ACX_ABL_EXIT(3, slo + shi);
@@ -1241,7 +1259,7 @@ __device__ __forceinline__ void band_row_tail(float (&xr)[NV], float *smem, int 
     constexpr bool TC_VIA_LDS = NV >= 32;       // (the narrower classes measure 2 % faster with direct loads)
     f32x4_u tcg[CH];
     if constexpr (TC_VIA_LDS) {
-        if (role == 0 && bits) {
+        if (role == 0 && (FAST || bits)) {
             asm volatile("" ::: "memory");
             const float *tc = thr + P.offX + P.pitchT - cshift + 4 * lane;
 #pragma unroll
@@ -1254,12 +1272,15 @@ __device__ __forceinline__ void band_row_tail(float (&xr)[NV], float *smem, int 
     // 2^-13 - 2^-23 > 2^-14, so w0 (dhi - dlo) and w1 (dhi - dlo) exceed 2^-22 dhi, four times what the roundings of the two
     // products, the sum and the two correctly rounded roots can move (each <= 2^-24 relative).  Then thr = slo (see below) and
     // neither sqrtf expansion nor eps is evaluated -- unless the caller wants eps itself (the debug entry point).
-    const bool weights_ok = interp && ihi == ilo + 1 && inclusive && fl >= 1.0f && (ce - kf) >= 0.00390625f && (kf - fl) >= 0.00390625f;
-    if (SNAP && !want_eps && weights_ok && shi < INF && (shi - slo) > shi * 0.000244140625f) {
+    const bool weights_ok = FAST || (interp && ihi == ilo + 1 && inclusive && fl >= 1.0f && (ce - kf) >= 0.00390625f && (kf - fl) >= 0.00390625f);
+    bool easy = SNAP && !want_eps && weights_ok && shi < INF && (shi - slo) > shi * 0.000244140625f;
+    if constexpr (FAST) easy = __builtin_expect(easy, true);
+    if (easy) {
         ACX_STAMP(6);
         ACX_ABL_EXIT(4, slo);
         if (lane == 0) (thr + P.offX)[role ? P.pitchT + row : row] = slo;
-        band_row_bits<NV, ROLE, TC_VIA_LDS>(xr, tcg, slo, myrow, lane, row, MB, cshift, P, thr, bits);
+        // (slo < shi < +inf here: the FAST copy's bitmap needs no mask, see band_row_bits)
+        band_row_bits<NV, ROLE, TC_VIA_LDS, FAST, !FAST>(xr, tcg, slo, myrow, lane, row, MB, cshift, P, thr, bits);
         ACX_STAMP(7);
         return;
     }
@@ -1282,7 +1303,7 @@ __device__ __forceinline__ void band_row_tail(float (&xr)[NV], float *smem, int 
         X[o] = thr_row;
         X[P.pitchT + P.pitchD + o] = eps;
     }
-    band_row_bits<NV, ROLE, TC_VIA_LDS>(xr, tcg, thr_row, myrow, lane, row, MB, cshift, P, thr, bits);
+    band_row_bits<NV, ROLE, TC_VIA_LDS, FAST>(xr, tcg, thr_row, myrow, lane, row, MB, cshift, P, thr, bits);
     ACX_STAMP(7);        // threshold store + bitmap
 }
 
@@ -1291,7 +1312,10 @@ constexpr int band_waves_per_simd(int m, int v4, int arith = 0) { return (v4 <= 
 // WD2: the debug entry point's variant, which also writes the band's distances to HBM (D2, query-major) -- a
 // template parameter, not a flag: as a run-time flag hipcc folds it into the per-cell store predicates and every
 // tile of the production kernel pays 24 VALU + 40 SALU instructions for stores that never happen.
-template <int M, int V4, int ROLE, bool WD2 = false, int ARITH = 0>
+// FAST: the product-path tail (band_row_tail), wide class and exact arithmetic only.
+// (Reading the pair's descriptor again behind the second barrier instead of keeping it across the sweep removes the last SGPR spills
+// of the row pass and was a measured negative -- profiles/r07_wide_tail.md.)
+template <int M, int V4, int ROLE, bool WD2 = false, int ARITH = 0, bool FAST = false>
 __global__ __launch_bounds__(BAND_THREADS, band_waves_per_simd(M, V4, ARITH)) void band_kernel(const float *__restrict__ frot,
                                                             const int64_t *__restrict__ toff,
                                                             const float *__restrict__ normtab,
@@ -1303,6 +1327,7 @@ __global__ __launch_bounds__(BAND_THREADS, band_waves_per_simd(M, V4, ARITH)) vo
                                                             float kappa, int pct_mode, int inclusive, int oti_target, int want_eps)
 {
     constexpr bool write_d2 = WD2;
+    static_assert(!FAST || (V4 == 8 && ARITH == 0 && !WD2), "the product-path tail exists for the wide class of the exact arithmetic");
     using G = BandGeom<M, V4, ARITH>;
     constexpr int role = ROLE;           // 1: rows = reference frames (column thresholds); 0: rows = query frames
     constexpr int NV = 4 * V4;           // values per lane of a complete row
@@ -1679,7 +1704,7 @@ __global__ __launch_bounds__(BAND_THREADS, band_waves_per_simd(M, V4, ARITH)) vo
       for (int t = 0; t < NV; ++t) keep_ += xr[t];
       ACX_ABL_EXIT(2, keep_); }
 #endif
-    band_row_tail<NV, ROLE, ARITH == 0 || ROLE == 0>(xr, smem, wave, lane, i0 + wave, MA, MB, (BAND - 1) - wave, P, thr, role == 0 ? bits : nullptr,
+    band_row_tail<NV, ROLE, ARITH == 0 || ROLE == 0, FAST>(xr, smem, wave, lane, i0 + wave, MA, MB, (BAND - 1) - wave, P, thr, role == 0 ? bits : nullptr,
                             pp, pct_mode, inclusive, want_eps ACX_STAMP_ARG);
 }
 

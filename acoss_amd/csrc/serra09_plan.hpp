@@ -250,6 +250,44 @@ inline Serra09Sort serra09_sort_batch(std::vector<PairDesc> &pd, std::vector<Pai
     return s;
 }
 
+// ---- the product-path tail -------------------------------------------------------------------
+// band_kernel<M, 8> has a second copy of its row tail (band_row_tail's FAST flag, serra09_kernels.hpp) in which everything the
+// host knows about a pass is a constant.  It is taken when ALL of this holds: the wide class of the exact arithmetic; pct_mode 0 (the
+// interpolating percentile) with the inclusive comparison; no eps and no D2 wanted (the debug entry point wants both); the row pass
+// writes a bitmap; and for every row length n of the launch, i.e. for every pair of it: the position falls strictly between two
+// ranks (ihi == ilo + 1) with both interpolation weights at least 2^-8 and at least one full rank below (band_row_tail's
+// `weights_ok`), and the pivot-filtered selection applies ((ihi + 2) * 9 <= n: its `use_pivot`).  A length whose position is an
+// integer ((n - 1) kappa: every 200th length at the default 0.095) does not qualify; serra09_fast_tail_runs cuts the pass around it.
+inline bool serra09_fast_tail_row(const PctPos &pp, int n)
+{
+    return pp.ihi == pp.ilo + 1 && pp.fl >= 1.0f && (pp.ce - pp.kf) >= 0.00390625f && (pp.kf - pp.fl) >= 0.00390625f && (pp.ihi + 2) * 9 <= n;
+}
+// (role 1: the column pass, rows of Mq cells; role 0: the row pass, rows of Mr cells, `have_bits`: it writes the bitmap)
+inline bool serra09_fast_tail_params(const acx_serra09_params &p, int family, int role, bool write_d2, bool want_eps, bool have_bits)
+{
+    return family == ACX_SERRA09_FAMILY_BAND_8 && p.arith == ACX_ARITH_EXACT && p.pct_mode == 0 && p.inclusive != 0 && !write_d2 && !want_eps &&
+           (role != 0 || have_bits);
+}
+// One band pass over sorted pairs [b0, b1) as launches: maximal runs of neighbouring pairs that all qualify (fast) or all do not, so
+// that a pair of an odd length sends only its own run through the generic copy, not the whole class.  Pairs are independent (one
+// grid row each), so the cut changes no result.  More than 2 + B / 32 runs (lengths that alternate): one generic launch, as before.
+struct Serra09Run { int begin, end; bool fast; };
+inline std::vector<Serra09Run> serra09_fast_tail_runs(const acx_serra09_params &p, int family, int role, bool write_d2, bool want_eps,
+                                                       bool have_bits, const std::vector<PairDesc> &pd, int b0, int b1)
+{
+    std::vector<Serra09Run> runs;
+    if (b1 <= b0) return runs;
+    if (!serra09_fast_tail_params(p, family, role, write_d2, want_eps, have_bits)) return {Serra09Run{b0, b1, false}};
+    auto ok = [&](int k2) { return role ? serra09_fast_tail_row(pd[k2].pos_q, pd[k2].Mq) : serra09_fast_tail_row(pd[k2].pos_r, pd[k2].Mr); };
+    for (int k2 = b0; k2 < b1; ++k2) {
+        const bool f = ok(k2);
+        if (!runs.empty() && runs.back().fast == f) runs.back().end = k2 + 1;
+        else runs.push_back(Serra09Run{k2, k2 + 1, f});
+    }
+    if ((int)runs.size() > 2 + (b1 - b0) / 32) return {Serra09Run{b0, b1, false}};
+    return runs;
+}
+
 // what one launch over sorted pairs [b0, b1) spans: the longest side each way (its grid) and the cells (its profile record)
 struct Serra09Extent { int Mq = 0, Mr = 0; int64_t cells = 0; };
 inline Serra09Extent serra09_extent(const std::vector<PairDesc> &pd, int b0, int b1)

@@ -318,6 +318,18 @@ int acx_serra09_plan(const int64_t *lengths, int32_t n_tracks, const int32_t *pa
 /* Printable name of a family for stack size m (band_kernel's names tell m <= 9 from m >= 10: the same limits, another
  * kernel beside it); NULL for an unknown family.  The string is static. */
 const char *acx_serra09_family_name(int32_t family, int32_t m);
+/* Whether a band pass whose rows hold n_cells cells may take the product-path copy of the band kernel's row tail (1) or runs
+ * the generic one (0); a pure host function.  role 1: the column pass, role 0: the row pass (which writes the bitmap);
+ * debug != 0: as the debug entry point acx_serra09_debug_pair launches it (eps and, in the row pass, D2 wanted).  A launch
+ * takes the copy only if this holds for every pair of it.  The conditions: the wide class (rows of 1018 .. 2041 cells) of
+ * the exact arithmetic, pct_mode 0, the inclusive comparison, no debug outputs, and a percentile position (n_cells - 1) kappa
+ * that lies at least 2^-8 away from the two ranks around it, the lower of them >= 1, with (upper rank + 2) * 9 <= n_cells.
+ * Negative: ACX_ERR_INVALID (the parameters). */
+int acx_serra09_fast_tail(const acx_serra09_params *params, int32_t n_cells, int32_t role, int32_t debug);
+/* TESTING AND DIAGNOSTICS, not part of the API proper: how many band passes of this process have launched the product-path copy
+ * so far (a process-wide counter: every context, every thread) -- what the launcher did, as opposed to what the predicate above
+ * says it would do.  The tests observe the dispatch through it; nothing else should depend on it. */
+int64_t acx_serra09_fast_tail_launches(void);
 
 /* ---- SiMPle (similarity matrix profile) ---------------------------------- */
 
