@@ -42,6 +42,7 @@ EXPORTS = [
     "acx_pool_truncate",
     "acx_serra09_align", "acx_qmax_locate_binary",
     "acx_serra09_align_paths", "acx_qmax_path_binary",
+    "acx_ef_debug_bits", "acx_csm_debug_bits", "acx_sw_bits_binary",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -248,6 +249,10 @@ def load():
     L.acx_ef_debug_pair.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ep, fp, fp, fp, ip]
     L.acx_ef_debug_pairs.argtypes = [vp, ip, ctypes.c_int64, ep, ctypes.c_int64, fp, fp, fp, ip]
     L.acx_sw_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, fp]
+    L.acx_sw_bits_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, fp]
+    up = ctypes.POINTER(ctypes.c_uint32)
+    L.acx_ef_debug_bits.argtypes = [vp, ip, ctypes.c_int64, ep, ctypes.c_int64, up, fp, ip, fp, fp, fp]
+    L.acx_csm_debug_bits.argtypes = [vp, fp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, up, fp, ip, fp, fp]
     L.acx_snf_fuse.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                ctypes.c_int32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]
@@ -753,6 +758,57 @@ class Context(object):
         self._check(self._L.acx_ef_debug_pairs(self._h, pairs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(pairs), ctypes.byref(p),
                                                int(which), _fptr(csm), _fptr(fused), _fptr(sc), ctypes.byref(oti)))
         return dict(csm=csm, fused=fused, scores=sc, oti=int(oti.value))
+
+    def ef_debug_bits(self, pairs, which, kappa=0.1, K=10):
+        """What the back end of the product call left behind for pair `which` of a sorted list that runs as ONE batch
+        (acx_ef_debug_bits; the fused matrix is not stored): bits (4, M, pitch / 32) uint32 or None when a track of the list has
+        more than 1024 blocks (the float path keeps no bitmaps), t / jcut (4, M), r (3, M), c (3, N), scores (n, 4)."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        if not 0 <= int(which) < len(pairs):
+            raise ValueError("ef_debug_bits: `which` = %d is not a pair of the list (%d pairs)" % (which, len(pairs)))
+        if pairs.min() < 0 or pairs.max() >= len(self.ef_blocks):
+            raise ValueError("ef_debug_bits: track index out of range")
+        i, j = (int(v) for v in pairs[which])
+        M, N = int(self.ef_blocks[i]), int(self.ef_blocks[j])
+        bits = np.zeros((4, M, (N + 63) // 64 * 2), np.uint32) if int(self.ef_blocks[np.unique(pairs)].max()) <= 1024 else None
+        t = np.empty((4, M), np.float32)
+        jcut = np.empty((4, M), np.int32)
+        r = np.empty((3, M), np.float32)
+        c = np.empty((3, N), np.float32)
+        sc = np.empty((len(pairs), 4), np.float32)
+        p = EfParams(float(kappa), int(K))
+        self._check(self._L.acx_ef_debug_bits(
+            self._h, pairs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(pairs), ctypes.byref(p), int(which),
+            bits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if bits is not None else None, _fptr(t),
+            jcut.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(r), _fptr(c), _fptr(sc)))
+        return dict(bits=bits, t=t, jcut=jcut, r=r, c=c, scores=sc)
+
+    def csm_debug_bits(self, D, kappa=0.1, K=1):
+        """The run of csm_binary_sw with neighbourhood size K, and what it left behind (acx_csm_debug_bits): bits (M, pitch / 32)
+        uint32 (None beyond 1024 rows or columns), t, jcut, r (M) and the score."""
+        D = np.ascontiguousarray(D, dtype=np.float32)
+        M, N = D.shape
+        bits = np.zeros((M, (N + 63) // 64 * 2), np.uint32) if max(M, N) <= 1024 else None
+        t = np.empty(M, np.float32)
+        jcut = np.empty(M, np.int32)
+        r = np.empty(M, np.float32)
+        sc = ctypes.c_float(0)
+        self._check(self._L.acx_csm_debug_bits(
+            self._h, _fptr(D), M, N, ctypes.c_double(kappa), int(K),
+            bits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if bits is not None else None, _fptr(t),
+            jcut.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(r), ctypes.byref(sc)))
+        return dict(bits=bits, t=t, jcut=jcut, r=r, score=float(sc.value))
+
+    def sw_bits_binary(self, B):
+        """sw_binary on the bit kernel of the product path (acx_sw_bits_binary): at most 1024 rows and columns."""
+        B = np.ascontiguousarray(B, dtype=np.uint8)
+        sc = ctypes.c_float(0)
+        rc = self._L.acx_sw_bits_binary(self._h, B.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), B.shape[0], B.shape[1],
+                                        ctypes.byref(sc))
+        if rc == ACX_ERR_INVALID and b"Non-binary" in (self._L.acx_last_error(self._h) or b""):
+            raise IOError("Non-binary elements found in input")       # alignment_tools.py:23
+        self._check(rc)
+        return float(sc.value)
 
     def sw_binary(self, B):
         B = np.ascontiguousarray(B, dtype=np.uint8)

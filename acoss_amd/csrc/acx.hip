@@ -167,7 +167,7 @@ struct acx_ctx {
     DeviceBuffer<float> d_efsc[3];                    // fmt 1: the power-of-two scale of every pool row (ef_rowscale_kernel)
     // scratch (grow-only)
     DeviceBuffer<float> d_scratch, d_thr;
-    DeviceBuffer<unsigned> d_efbits;                         // EarlyFusion: the binarised matrices of a batch (ef_rowstat_kernel -> sw_bits_kernel)
+    DeviceBuffer<unsigned> d_efbits;                         // EarlyFusion: the binarised matrices of a batch (ef_rowstat_kernel -> sw_bits_h16_kernel)
     Serra09Slot slot[2];
     DeviceBuffer<float> d_out;
     DeviceBuffer<unsigned long long> d_bits;              // recurrence bitmaps (u64 words)
@@ -1020,7 +1020,9 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
 // ---------------------------------------------------------------------------------------
 // EarlyFusion driver
 // ---------------------------------------------------------------------------------------
-struct EfDebug { float *csm, *fused; int32_t *oti; int64_t which = 0; };      // which: the pair of the (one-batch) list whose intermediates are wanted
+// what the selection kernels left behind for one pair (acx_ef_debug_bits / acx_csm_debug_bits); any pointer may be null
+struct EfStats { uint32_t *bits; float *t; int32_t *jcut; float *r; float *c; };
+struct EfDebug { float *csm, *fused; int32_t *oti; int64_t which = 0; const EfStats *stats = nullptr; };      // which: the pair of the (one-batch) list whose intermediates are wanted
 
 // pinned host staging + device copy of `n` score destinations idx[0 .. n)
 static int stage_idx(acx_ctx *c, const int64_t *idx, int64_t n)
@@ -1335,6 +1337,8 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
             if (c->h_efoff[q + 1] - c->h_efoff[q] > acx::EF_MAXNB || c->h_efoff[r + 1] - c->h_efoff[r] > acx::EF_MAXNB) bits_path = false;
         }
     const bool keep_f = !bits_path || (dbg && dbg->fused);
+    if (dbg && dbg->stats && dbg->stats->bits && !bits_path)
+        return fail(c, ACX_ERR_INVALID, "ef debug: a track of more than 1024 blocks takes the float path, which leaves no bitmaps (pass a null bitmap pointer)");
     if (!ext_matrix)                              // (the last of the up-front checks: a pair that cannot fit the scratch limit on its own)
         for (int64_t k = 0; k < K; ++k) {
             const int64_t M = c->h_efoff[pairs[2 * k] + 1] - c->h_efoff[pairs[2 * k]], N = c->h_efoff[pairs[2 * k + 1] + 1] - c->h_efoff[pairs[2 * k + 1]];
@@ -1430,6 +1434,8 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
         return ACX_OK;
     };
     if ((rc = prepare(hbs[0], 0)) != ACX_OK) return rc;
+    if (dbg && !ext_matrix && hbs[0].k_end < K)          // the debug entries show one batch: refused before the first launch
+        return fail(c, ACX_ERR_UNSUPPORTED, "ef debug: the list does not fit one batch");
     for (int bi = 0; hbs[bi & 1].k_begin < K; ++bi) {
         HostBatch &hb = hbs[bi & 1];
         std::vector<EfPair> &pd = hb.pd;
@@ -1537,8 +1543,6 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
         ht[3] += now() - t_w;
         drain_profile(c);
         if (rc_next != ACX_OK) return rc_next;
-        if (dbg && !ext_matrix && k < K)
-            return fail(c, ACX_ERR_UNSUPPORTED, "ef_debug_pairs: the list does not fit one batch");
         if (dbg && B >= 1) {
             EfPair d;
             ACX_HIP(c, hipMemcpy(&d, c->d_efpd + (dbg->which - k0), sizeof(EfPair), hipMemcpyDeviceToHost));
@@ -1551,6 +1555,22 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
                 ACX_HIP(c, hipMemcpy2D(dbg->fused, sizeof(float) * d.N,
                                        c->d_scratch + d.offC + (int64_t)3 * d.M * d.pitchC + (int64_t)3 * d.ctN * d.pitchT,
                                        sizeof(float) * d.pitchC, sizeof(float) * d.N, d.M, hipMemcpyDeviceToHost));
+            if (const EfStats *st = dbg->stats) {
+                // the vectors of d_thr (layout: ef_kernels.hpp, EfPair::offS) and the words of d_efbits as the kernels wrote them;
+                // the caller's matrix has one slot, a pair three features and the fused slot
+                const int nf = ext_matrix ? 1 : 3, nslots = ext_matrix ? 1 : 4;
+                const int64_t stride = acx::ef_s_stride(d);
+                if (st->bits)
+                    ACX_HIP(c, hipMemcpy(st->bits, c->d_efbits + d.offB, sizeof(uint32_t) * (size_t)nslots * d.M * (d.pitchC / 32), hipMemcpyDeviceToHost));
+                for (int sl = 0; sl < nslots; ++sl) {
+                    const float *S = c->d_thr + d.offS + sl * stride;
+                    if (st->t) ACX_HIP(c, hipMemcpy(st->t + (size_t)sl * d.M, S, sizeof(float) * d.M, hipMemcpyDeviceToHost));
+                    if (st->jcut) ACX_HIP(c, hipMemcpy(st->jcut + (size_t)sl * d.M, S + acx::ef_jcut_off(d, sl), sizeof(int32_t) * d.M, hipMemcpyDeviceToHost));
+                    if (sl >= nf) continue;
+                    if (st->r) ACX_HIP(c, hipMemcpy(st->r + (size_t)sl * d.M, S + d.pitchT, sizeof(float) * d.M, hipMemcpyDeviceToHost));
+                    if (st->c && !ext_matrix) ACX_HIP(c, hipMemcpy(st->c + (size_t)sl * d.N, S + 2 * d.pitchT, sizeof(float) * d.N, hipMemcpyDeviceToHost));
+                }
+            }
         }
         if (ext_matrix) break;
     }
@@ -2703,6 +2723,37 @@ int acx_ef_debug_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
     return rc;
 }
 
+int acx_ef_debug_bits(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params *params, int64_t which,
+                      uint32_t *bits, float *t, int32_t *jcut, float *r, float *cm, float *scores)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!params || !pairs || K < 1 || which < 0 || which >= K) return fail(c, ACX_ERR_INVALID, "ef_debug_bits: bad argument");
+    // the list as acx_earlyfusion_pairs hands it to run_ef: sorted, the fused matrix not stored
+    for (int64_t k = 1; k < K; ++k)
+        if (!(pairs[2 * k - 2] < pairs[2 * k] || (pairs[2 * k - 2] == pairs[2 * k] && pairs[2 * k - 1] <= pairs[2 * k + 1])))
+            return fail(c, ACX_ERR_INVALID, "ef_debug_bits: the pair list must be sorted by (first track, second track)");
+    std::vector<float> sc((size_t)4 * K);
+    const EfStats st{bits, t, jcut, r, cm};
+    EfDebug dbg{nullptr, nullptr, nullptr, which, &st};
+    const int rc = run_ef(c, pairs, K, *params, sc.data(), &dbg, nullptr, 0, 0);
+    if (rc == ACX_OK && scores) memcpy(scores, sc.data(), sizeof(float) * 4 * (size_t)K);
+    return rc;
+}
+
+int acx_csm_debug_bits(acx_ctx *c, const float *D, int32_t M, int32_t N, double kappa, int32_t K,
+                       uint32_t *bits, float *t, int32_t *jcut, float *r, float *score)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!D || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "csm_debug_bits: bad argument");
+    acx_ef_params p{kappa, K};
+    float sc[4] = {0, 0, 0, 0};
+    const EfStats st{bits, t, jcut, r, nullptr};
+    EfDebug dbg{nullptr, nullptr, nullptr, 0, &st};
+    const int rc = run_ef(c, nullptr, 1, p, sc, &dbg, D, M, N);
+    if (rc == ACX_OK && score) *score = sc[0];
+    return rc;
+}
+
 int acx_csm_binary_sw(acx_ctx *c, const float *D, int32_t M, int32_t N, double kappa, float *score)
 {
     if (!c) return ACX_ERR_INVALID;
@@ -2748,6 +2799,49 @@ int acx_sw_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, float *sco
     ACX_HIP(c, hipMemcpyAsync(sc, c->d_out, sizeof(float) * 4, hipMemcpyDeviceToHost, c->stream));
     ACX_HIP(c, hipStreamSynchronize(c->stream));
     (void)p;
+    *score = sc[0];
+    return ACX_OK;
+}
+
+static int sw_bits_binary_impl(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, float *score);
+
+int acx_sw_bits_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, float *score)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const int rc = sw_bits_binary_impl(c, B, M, N, score);
+    if (rc != ACX_OK) quiesce(c);                // the queued copies read this call's host buffers: none stays in flight behind an error
+    return rc;
+}
+
+static int sw_bits_binary_impl(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, float *score)
+{
+    if (!B || !score || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "sw_bits_binary: bad argument");
+    if (M > acx::EF_MAXNB || N > acx::EF_MAXNB) return fail(c, ACX_ERR_INVALID, "sw_bits_binary: more than 1024 rows or columns (the bit kernels hold a row in one wave)");
+    acx::EfPair d;
+    d.q = d.r = 0; d.M = M; d.N = N; d.oti = 0; d.pitchC = round_up(N, 64); d.pitchT = round_up(M, 64); d.kbin = 0;
+    d.ctN = 0; d.pad = 0; d.offB = 0; d.offC = 0; d.offS = 0;
+    // the layout the selection kernels leave in d_efbits: bit j % 32 of word j / 32, M rows of pitchC / 32 words, pads zero
+    const int words = d.pitchC / 32;
+    std::vector<uint32_t> W((size_t)M * words, 0u);
+    for (int i = 0; i < M; ++i)
+        for (int j = 0; j < N; ++j) {
+            const uint8_t b = B[(size_t)i * N + j];
+            if (b > 1) return fail(c, ACX_ERR_INVALID, "Non-binary elements found in input");
+            W[(size_t)i * words + (j >> 5)] |= (uint32_t)b << (j & 31);
+        }
+    float sc[4] = {0, 0, 0, 0};
+    int rc;
+    ACX_HIP(c, hipSetDevice(c->device));
+    if ((rc = ensure(c, c->d_efbits, W.size())) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efpd, (size_t)1)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_out, (size_t)4)) != ACX_OK) return rc;
+    ACX_HIP(c, hipMemcpyAsync(c->d_efpd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(c->d_efbits, W.data(), sizeof(uint32_t) * W.size(), hipMemcpyHostToDevice, c->stream));
+    if (N > 512) hipLaunchKernelGGL((acx::sw_bits_h16_kernel<16>), dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_efbits, c->d_out, 0);
+    else hipLaunchKernelGGL((acx::sw_bits_h16_kernel<8>), dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_efbits, c->d_out, 0);
+    ACX_HIP(c, hipGetLastError());
+    ACX_HIP(c, hipMemcpyAsync(sc, c->d_out, sizeof(float) * 4, hipMemcpyDeviceToHost, c->stream));
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
     *score = sc[0];
     return ACX_OK;
 }

@@ -1794,95 +1794,13 @@ __global__ __launch_bounds__(64) void sw_kernel(const EfPair *__restrict__ pd, c
 // E4b: the same recursion on the BINARISED rows the selection kernels leave behind (round 3): a lane's CPL columns of a
 // row are CPL bits -- one byte (CPL = 8) or two (16) -- instead of CPL floats, a threshold and a tie column; the four
 // matrices of a pair in one launch.  out[pair * 4 + src].
-// ------------------------------------------------------------------------------------
-template <int CPL>
-#ifndef ACX_SW_BITS_WAVES
-#define ACX_SW_BITS_WAVES 1
-#endif
-__global__ __launch_bounds__(64, ACX_SW_BITS_WAVES) void sw_bits_kernel(const EfPair *__restrict__ pd, const unsigned *__restrict__ bits,
-                                                     float *__restrict__ out, int src_base)
-{
-    const int lane = threadIdx.x;
-    const EfPair P = pd[blockIdx.x];
-    const int src = src_base + blockIdx.y;
-    const int M = P.M, N = P.N, pitch = P.pitchC;
-    float result = 0.0f;
-    if (M >= 4 && N >= 4) {
-        typedef unsigned short bits_t;                               // (CPL = 8 uses the low byte)
-        const unsigned char *rows = reinterpret_cast<const unsigned char *>(bits + P.offB + (int64_t)src * M * (pitch >> 5));
-        const int rowbytes = pitch >> 3;
-        const int j0 = CPL * lane;
-        const bool inrow = j0 < pitch;
-        auto load = [&](int row) -> unsigned {
-            const int r = row < M ? row : M - 1;                     // (rows past the last one: a valid address, never used)
-            if (!inrow) return 0u;
-            if (CPL == 8) return rows[(size_t)r * rowbytes + lane];
-            return *reinterpret_cast<const bits_t *>(rows + (size_t)r * rowbytes + 2 * lane);
-        };
-        int U1[CPL], U2[CPL];      // U of rows i-1, i-2
-        const int prev = (lane + 63) & 63;
-        unsigned w = load(0);
-#pragma unroll
-        for (int e = 0; e < CPL; ++e) U2[e] = ((w >> e) & 1u) ? 0 : -7;
-        w = load(1);
-#pragma unroll
-        for (int e = 0; e < CPL; ++e) U1[e] = ((w >> e) & 1u) ? 0 : -7;
-        int best = 0;
-        constexpr int SW_PF = 8;
-        unsigned ring[SW_PF];
-#pragma unroll
-        for (int sl = 0; sl < SW_PF; ++sl) ring[sl] = load(2 + sl);
-        for (int i0 = 2; i0 <= M - 2; i0 += SW_PF) {
-#pragma unroll
-            for (int sl = 0; sl < SW_PF; ++sl) {
-                const int i = i0 + sl;
-                if (i <= M - 2) {                            // wave-uniform
-                    const unsigned wb = ring[sl];
-                    ring[sl] = load(i + SW_PF);
-                    bool b[CPL];
-#pragma unroll
-                    for (int e = 0; e < CPL; ++e) b[e] = ((wb >> e) & 1u) != 0u;
-                    const int l1a = lane_prev_i(U1[CPL - 1]), l1b = lane_prev_i(U1[CPL - 2]), l2a = lane_prev_i(U2[CPL - 1]);
-                    int Tn[CPL];
-#pragma unroll
-                    for (int e = 0; e < CPL; ++e) {
-                        const int c2 = (e >= 1) ? U1[e - 1] : l1a;                        // U[i-1][j-1]
-                        const int c3 = (e >= 1) ? U2[e - 1] : l2a;                        // U[i-2][j-1]
-                        const int c4 = (e >= 2) ? U1[e - 2] : (e == 1 ? l1a : l1b);       // U[i-1][j-2]
-                        int mx = c2 > c3 ? c2 : c3;
-                        mx = mx > c4 ? mx : c4;
-                        int t = (b[e] ? 10 : -10) + mx;
-                        t = t > 0 ? t : 0;
-                        const int j = j0 + e;
-                        if (j < 2) t = 0;                  // columns 0, 1 (lane 0 only; its shuffled inputs are unused)
-                        Tn[e] = t;
-                        if (j <= N - 2) best = best > t ? best : t;
-                    }
-#pragma unroll
-                    for (int e = 0; e < CPL; ++e) {
-                        U2[e] = U1[e];
-                        U1[e] = Tn[e] + (b[e] ? 0 : -7);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const int t = __shfl_xor(best, o, 64);
-            best = best > t ? best : t;
-        }
-        result = (float)best / 10.0f;
-    }
-    if (lane == 0) out[(size_t)blockIdx.x * 4 + src] = result;
-}
-
-// ------------------------------------------------------------------------------------
-// E4c: E4b in PACKED 16-bit integers (round 4; the pattern of qmax_bits_h16_kernel): scores are tenths, at most 10 min(M, N)
+// In PACKED 16-bit integers (round 4; the pattern of qmax_bits_h16_kernel): scores are tenths, at most 10 min(M, N)
 // <= 10 240 for rows of <= 1024 cells, and U >= -7, so V = U + 7 fits the unsigned half of a register and one v_pk_* instruction
 // updates two cells.  Register k of a lane holds its columns k (low half) and k + CPL / 2 (high half): the (i-1, j-1), (i-2, j-1),
 // (i-1, j-2) predecessors of register k are registers k - 1 / k - 2 of the two previous rows (the first two stitched from the
 // left neighbour lane by DPP + one funnel shift).  With the bias, T = max(max(U) +- 10, 0) = sat_sub(max(V) + 20 bit, 17) (an
-// unsigned saturating subtract) and the new V = T + 7 bit: 11 packed instructions per two cells.  The same integers as E4b.
+// unsigned saturating subtract) and the new V = T + 7 bit: 11 packed instructions per two cells.  The same integers as E4
+// (acx_sw_bits_binary: tests/test_gpu_ef_backend.py).
 // ------------------------------------------------------------------------------------
 template <int CPL>
 __global__ __launch_bounds__(64) void sw_bits_h16_kernel(const EfPair *__restrict__ pd, const unsigned *__restrict__ bits,

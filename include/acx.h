@@ -507,6 +507,26 @@ int acx_ef_debug_pair(acx_ctx *ctx, int32_t i, int32_t j, const acx_ef_params *p
 int acx_ef_debug_pairs(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_ef_params *params, int64_t which,
                        float *csm, float *fused, float *scores, int32_t *oti);
 
+/* What the EarlyFusion back end leaves behind for pair `which` of a SORTED list of K pairs that runs as ONE batch (tests): the
+ * call acx_earlyfusion_pairs makes for that list -- the fused matrix made and binarised in registers, never stored, the same
+ * kernel choices -- and then, copied from the device:
+ *   bits  (4, M, pitch / 32) uint32, pitch = N rounded up to 64: the binarised matrices (mfccs, ssms, chromas, fused) as the
+ *         selection kernels wrote them, bit j % 32 of word j / 32 = B[i][j], pad bits 0
+ *   t     (4, M) thresholds, jcut (4, M) tie columns: B_ij = C_ij < t_i, or C_ij == t_i and j <= jcut_i (0x7fffffff: every tie)
+ *   r     (3, M) row and c (3, N) column neighbourhood means of getWCSM (similarity_fusion.py:38-54)
+ *   scores (K, 4), all pairs.
+ * Any output may be NULL.  A list with a track of more than 1024 blocks takes the float-matrix kernels and leaves no bitmaps:
+ * `bits` must then be NULL (else ACX_ERR_INVALID); the vectors are returned all the same.  An unsorted list: ACX_ERR_INVALID;
+ * a list that needs more than one batch: ACX_ERR_UNSUPPORTED, before any launch (acx_ef_debug_pairs likewise). */
+int acx_ef_debug_bits(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_ef_params *params, int64_t which,
+                      uint32_t *bits, float *t, int32_t *jcut, float *r, float *c, float *scores);
+
+/* The run of acx_csm_binary_sw for one (M, N) f32 matrix with the caller's neighbourhood size K, and what it left behind (tests):
+ * bits (M, pitch / 32), t (M), jcut (M), r (M) as above, and the Smith-Waterman score.  Any output may be NULL; M or N above 1024:
+ * `bits` must be NULL. */
+int acx_csm_debug_bits(acx_ctx *ctx, const float *D, int32_t M, int32_t N, double kappa, int32_t K,
+                       uint32_t *bits, float *t, int32_t *jcut, float *r, float *score);
+
 /* csm_to_binary(D, kappa) (cross_recurrence.py:136-161: exactly k = round(kappa N) cells per row;
  * ties at the k-th value are taken in column order) followed by smith_waterman_constrained, for
  * one (M, N) f32 matrix -- the tail of every feature's chain in earlyfusion_traile.py:165-197
@@ -517,6 +537,11 @@ int acx_csm_binary_sw(acx_ctx *ctx, const float *D, int32_t M, int32_t N, double
  * the device DP (tests against the reference goldens).  Non-{0,1} input -> ACX_ERR_INVALID
  * (the reference raises IOError). */
 int acx_sw_binary(acx_ctx *ctx, const uint8_t *B, int32_t M, int32_t N, float *score);
+
+/* The same on the BIT kernel every ordinary EarlyFusion call runs (tests): B is packed on the host into the layout of the
+ * binarised matrices (see acx_ef_debug_bits) and aligned by the packed 16-bit Smith-Waterman, N <= 512 and N <= 1024 columns
+ * in the variants the product launches.  M or N above 1024: ACX_ERR_INVALID; non-{0,1} input as acx_sw_binary. */
+int acx_sw_bits_binary(acx_ctx *ctx, const uint8_t *B, int32_t M, int32_t N, float *score);
 
 /* ---- FTM2D (2D Fourier transform magnitudes, Bertin-Mahieux & Ellis) ------ */
 
