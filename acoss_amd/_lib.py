@@ -43,6 +43,7 @@ EXPORTS = [
     "acx_serra09_align", "acx_qmax_locate_binary",
     "acx_serra09_align_paths", "acx_qmax_path_binary",
     "acx_ef_debug_bits", "acx_csm_debug_bits", "acx_sw_bits_binary",
+    "acx_ef_align", "acx_sw_align_binary",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -266,6 +267,9 @@ def load():
     L.acx_serra09_align_paths.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
     L.acx_qmax_path_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, pp, ctypes.c_void_p,
                                        ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_int64]
+    L.acx_ef_align.argtypes = [vp, ip, ctypes.c_int64, ep, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+    L.acx_sw_align_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     epp = ctypes.POINTER(EfPrepParams)
     L.acx_ef_block_features.argtypes = [vp, fp, ctypes.c_int64, fp, ctypes.c_int64, ctypes.c_int32, lp, ctypes.c_int32, epp,
                                         fp, fp, fp, dp]
@@ -809,6 +813,54 @@ class Context(object):
             raise IOError("Non-binary elements found in input")       # alignment_tools.py:23
         self._check(rc)
         return float(sc.value)
+
+    def ef_align(self, pairs, kappa=0.1, K=10, plane=3, paths=False, cap=None):
+        """WHERE the Smith-Waterman alignment of every (query, reference) pair lies in one binarised matrix (acx_ef_align; plane
+        0 mfccs, 1 ssms, 2 chromas, 3 early): a (K,) structured array (ALIGNMENT_DTYPE) -- score = earlyfusion_pairs' value for
+        that pair and plane, (q0, r0) the start and (q1, r1) the end of the path in blocks of the query / the reference; a pair
+        without a match: score 0 and -1 four times.  paths=True: (records, offsets (K + 1,) int64, cells (offsets[-1], 2) int32),
+        pair k's path being cells[offsets[k]:offsets[k + 1]] from the start to the end.  cap: cells the buffer holds; default
+        the bound the library checks, the sum of min(M_k, N_k) over the list."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        p = EfParams(float(kappa), int(K))
+        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
+        if not paths:
+            self._check(self._L.acx_ef_align(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), out.ctypes.data, None, None, 0))
+            return out
+        if cap is None:
+            # (a list the library refuses -- an index out of range -- is refused before it looks at cap)
+            nb = getattr(self, "ef_blocks", None)
+            if nb is None:
+                # a pool this object did not see uploaded: the bound of any list the library accepts (at most 1024 blocks a track)
+                cap = 1024 * len(pairs)
+            else:
+                nb = np.asarray(nb, dtype=np.int64)
+                ok = np.all((pairs >= 0) & (pairs < len(nb)), axis=1) if len(pairs) else np.zeros(0, bool)
+                cap = int(np.minimum(nb[pairs[ok, 0]], nb[pairs[ok, 1]]).sum())
+        off = np.zeros(len(pairs) + 1, np.int64)
+        cells = np.zeros((max(int(cap), 1), 2), np.int32)
+        self._check(self._L.acx_ef_align(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), out.ctypes.data,
+                                         off.ctypes.data, cells.ctypes.data, int(cap)))
+        return out, off, cells[:off[-1]].copy()
+
+    def sw_align_binary(self, B, paths=True, cap=None):
+        """The same DP alone on a binary (M, N) plot (acx_sw_align_binary): (record (1,), cells (L, 2) int32 from the start to the
+        end; L == 0: no match), or the record alone with paths=False.  At most 1024 rows and columns.  cap: default min(M, N)."""
+        B = np.ascontiguousarray(B, dtype=np.uint8)
+        if B.ndim != 2:
+            raise ValueError("sw_align_binary: B must be (M, N), got shape %s" % (B.shape,))
+        out = np.zeros(1, ALIGNMENT_DTYPE)
+        bp = B.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+        if not paths:
+            self._check(self._L.acx_sw_align_binary(self._h, bp, B.shape[0], B.shape[1], out.ctypes.data, None, 0, None))
+            return out
+        if cap is None:
+            cap = min(B.shape)
+        n = ctypes.c_int64(0)
+        cells = np.zeros((max(int(cap), 1), 2), np.int32)
+        self._check(self._L.acx_sw_align_binary(self._h, bp, B.shape[0], B.shape[1], out.ctypes.data, cells.ctypes.data, int(cap),
+                                                ctypes.byref(n)))
+        return out, cells[:n.value].copy()
 
     def sw_binary(self, B):
         B = np.ascontiguousarray(B, dtype=np.uint8)

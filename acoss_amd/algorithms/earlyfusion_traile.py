@@ -21,6 +21,7 @@ import os
 import numpy as np
 
 from .. import _lib
+from . import _align
 from .algorithm_template import CoverAlgorithm
 from .similarity_fusion import doSimilarityFusion
 
@@ -151,6 +152,88 @@ class EarlyFusion(CoverAlgorithm):
         sc = self._context().earlyfusion_pairs(idxs.astype(np.int32), kappa=self.kappa, K=self.K)
         for c, s in enumerate(("mfccs", "ssms", "chromas", "early")):
             self.Ds[s][idxs[:, 0], idxs[:, 1]] = sc[:, c]
+
+    # ------------------------------------------------------------------ where the alignment lies
+    # align() / align_matches(): acx_alignment's fields in BLOCKS and the spans in BEATS, [first, last] inclusive
+    ALIGN_DTYPE = np.dtype(_lib.ALIGNMENT_DTYPE.descr + [("q_span", np.int32, (2,)), ("r_span", np.int32, (2,))])
+
+    def _align_plane(self, who, similarity_type):
+        """The device plane of a similarity type; checked before anything else."""
+        if similarity_type in self._identify_fused:
+            raise ValueError("%s: '%s' is fused from whole score matrices and has no alignment of its own; similarity_type must be one of %s"
+                             % (who, similarity_type, list(self._identify_planes)))
+        if similarity_type not in self._identify_planes:
+            raise ValueError("%s: unknown similarity type %r; similarity_type must be one of %s" % (who, similarity_type, list(self._identify_planes)))
+        return self._identify_planes.index(similarity_type)
+
+    def _align_pairs(self, pairs, plane, paths=None):
+        """(K, 2) checked int32 pairs -> (K,) ALIGN_DTYPE.  paths: a list that receives the K (L_k, 2) int32 paths as well."""
+        out = _align.no_match_rows(len(pairs), self.ALIGN_DTYPE)
+        if len(pairs) == 0:
+            return out
+        if paths is None:
+            al = self._context().ef_align(pairs, self.kappa, self.K, plane)
+        else:
+            al, off, cells = self._context().ef_align(pairs, self.kappa, self.K, plane, paths=True)
+            paths.extend(cells[off[k]:off[k + 1]] for k in range(len(pairs)))
+        for f in _lib.ALIGNMENT_DTYPE.names:
+            out[f] = al[f]
+        hit = al["q0"] >= 0
+        for side in ("q", "r"):
+            span = np.stack([al[side + "0"], al[side + "1"] + int(self.blocksize) - 1], axis=1)
+            out[side + "_span"][hit] = span[hit]
+        return out
+
+    def align(self, idxs, similarity_type="early"):
+        """WHERE in the two recordings does the Smith-Waterman alignment lie?  idxs: (K, 2) (query, reference) track indices
+        over the uploaded collection; similarity_type: one of the four matrices the device binarises, 'mfccs', 'ssms',
+        'chromas' or 'early' ('late' and 'early+late' are fused from whole score matrices: ValueError).  Returns a (K,)
+        structured array: score (the value similarity() stores for that ordered pair and type), the path's start (q0, r0) and
+        end (q1, r1) in BLOCKS -- rows (query) and columns (reference) of the binarised cross-similarity matrix; the end is
+        the row-major first maximum of the score matrix, the start is found by following the recursion's predecessors back
+        (include/acx.h acx_ef_align) -- and q_span / r_span, [first, last] inclusive in BEATS of each track: block b starts
+        at beat b and spans `blocksize` beats, so a span is [q0, q1 + blocksize - 1] (a track of n beats has n - blocksize
+        blocks: no clipping).  A pair without a match (score 0) has -1 everywhere.  Tracks of at most 1024 blocks.  `Ds` is
+        not written; not a collective."""
+        plane = self._align_plane("align", similarity_type)
+        return self._align_pairs(_align.check_pairs("align", _align.check_indices("align", idxs), self.N), plane)
+
+    def align_paths(self, idxs, similarity_type="early"):
+        """align() and, for every pair, the PATH of its alignment: (al, paths).  al is exactly what align(idxs, similarity_type)
+        returns; paths is a list of K (L_k, 2) int32 arrays, the cells (q, r) in blocks that the recursion's predecessors visit
+        between the start and the end, both included, listed from (q0, r0) to (q1, r1) -- which block of the query corresponds
+        to which block of the reference.  Consecutive cells differ by (1, 1), (2, 1) or (1, 2); a pair without a match has an
+        empty (0, 2) path.  `Ds` is not written; not a collective."""
+        plane = self._align_plane("align_paths", similarity_type)
+        paths = []
+        al = self._align_pairs(_align.check_pairs("align_paths", _align.check_indices("align_paths", idxs), self.N), plane, paths)
+        return al, (paths if len(al) else [])
+
+    def _check_align_matches(self, who, queries, indices):
+        return _align.check_matches(who, _align.check_indices(who, queries), _align.check_indices(who, indices), self.N)
+
+    def align_matches(self, queries, indices, similarity_type="early"):
+        """align() for the hits of identify() / rerank(): queries (Q,) track indices, indices the (Q, k) int array either
+        returned (-1: an empty slot).  Returns a (Q, k) structured array as align() does, row i slot s being the alignment of the
+        ORDERED pair (queries[i], indices[i, s]); an empty slot comes back as a no-match row.  identify() of this symmetric
+        class scored the cell (min, max) of the two indices: the score listed there is that of the pair (min(queries[i],
+        indices[i, s]), max(...)), and passing THAT pair to align() gives the alignment behind the listed score; where the query
+        has the larger index the row here is the alignment of the transposed matrix, whose score may differ."""
+        plane = self._align_plane("align_matches", similarity_type)
+        idx, rows, slots, pairs = self._check_align_matches("align_matches", queries, indices)
+        out = _align.no_match_rows(idx.shape, self.ALIGN_DTYPE)
+        out[rows, slots] = self._align_pairs(pairs, plane)
+        return out
+
+    def align_match_paths(self, queries, indices, similarity_type="early"):
+        """align_matches() with the paths: (the (Q, k) array align_matches returns, a Q-list of k-lists of (L, 2) int32 paths as
+        align_paths lists them); an empty slot (-1) has an empty path."""
+        plane = self._align_plane("align_match_paths", similarity_type)
+        idx, rows, slots, pairs = self._check_align_matches("align_match_paths", queries, indices)
+        out = _align.no_match_rows(idx.shape, self.ALIGN_DTYPE)
+        got = []
+        out[rows, slots] = self._align_pairs(pairs, plane, got)
+        return out, _align.scatter_paths(idx, rows, slots, got)
 
     def _fusion_context(self):
         """The GPU context of the pair grid, or a fresh one (scores loaded with precomputed=True)."""

@@ -8,6 +8,7 @@ runs in libacx's HIP kernels for ALL rows of `idxs` in one call.
 import numpy as np
 
 from .. import _lib
+from . import _align
 from .algorithm_template import CoverAlgorithm
 
 __all__ = ["Serra09", "pool_median"]
@@ -213,10 +214,7 @@ class Serra09(CoverAlgorithm):
     def _check_align(self, who, idxs):
         if self._engine.get("dmax"):
             raise ValueError("%s: the Qmax alignment only (engine dmax must be 0)" % who)
-        a = np.asarray(idxs)
-        if a.size and not np.issubdtype(a.dtype, np.integer):
-            raise ValueError("%s: track indices must be integers, got dtype %s" % (who, a.dtype))
-        return a
+        return _align.check_indices(who, idxs)
 
     def _align_pairs(self, pairs, paths=None):
         """(K, 2) checked int32 pairs -> (K,) ALIGN_DTYPE.  paths: a list that receives the K (L_k, 2) int32 paths as well."""
@@ -256,34 +254,14 @@ class Serra09(CoverAlgorithm):
 
     def _check_align_pairs(self, who, idxs):
         """align() / align_paths(): idxs -> (K, 2) int32, every check before the first library call."""
-        a = self._check_align(who, idxs)
-        if a.size == 0:
-            a = a.reshape(0, 2)
-        if a.ndim != 2 or a.shape[1] != 2:
-            raise ValueError("%s: idxs must be (K, 2) (query, reference) track indices, got shape %s" % (who, a.shape))
-        if a.size and (a.min() < 0 or a.max() >= self.N):
-            raise ValueError("%s: idxs must be track indices in [0, %d)" % (who, self.N))
-        return np.ascontiguousarray(a, dtype=np.int32)
+        return _align.check_pairs(who, self._check_align(who, idxs), self.N)
 
     def _check_align_matches(self, who, queries, indices):
         """align_matches() / align_match_paths(): -> (the (Q, k) index array, rows and slots of its filled slots, their (P, 2) pairs)."""
-        q = self._check_align(who, queries).reshape(-1)
-        idx = self._check_align(who, indices)
-        if idx.ndim != 2 or idx.shape[0] != len(q):
-            raise ValueError("%s: indices must be (Q, k) with one row per query (%d), got shape %s" % (who, len(q), idx.shape))
-        if q.size and (q.min() < 0 or q.max() >= self.N):
-            raise ValueError("%s: queries must be track indices in [0, %d)" % (who, self.N))
-        if idx.size and (idx.min() < -1 or idx.max() >= self.N):
-            raise ValueError("%s: indices must be track indices in [0, %d) or -1" % (who, self.N))
-        rows, slots = np.nonzero(idx >= 0)
-        pairs = np.stack([q[rows], idx[rows, slots]], axis=1).astype(np.int32).reshape(-1, 2)
-        return idx, rows, slots, np.ascontiguousarray(pairs)
+        return _align.check_matches(who, self._check_align(who, queries), self._check_align(who, indices), self.N)
 
     def _no_match_rows(self, shape):
-        out = np.zeros(shape, self.ALIGN_DTYPE)
-        for f in ("q0", "r0", "q1", "r1", "q_span", "r_span"):
-            out[f] = -1
-        return out
+        return _align.no_match_rows(shape, self.ALIGN_DTYPE)
 
     def align_matches(self, queries, indices):
         """align() for the hits of identify() / rerank(): queries (Q,) track indices, indices the (Q, k) int array
@@ -312,10 +290,7 @@ class Serra09(CoverAlgorithm):
         out = self._no_match_rows(idx.shape)
         got = []
         out[rows, slots] = self._align_pairs(pairs, got)
-        paths = [[np.zeros((0, 2), np.int32) for _ in range(idx.shape[1])] for _ in range(idx.shape[0])]
-        for r, s, p in zip(rows, slots, got):
-            paths[r][s] = p
-        return out, paths
+        return out, _align.scatter_paths(idx, rows, slots, got)
 
     def normalize_by_length(self):
         """Non-symmetric normalisation: D[i, j] /= sqrt(T_j), T_j the pooled length

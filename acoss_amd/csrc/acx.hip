@@ -27,6 +27,7 @@
 #include "simple_kernels.hpp"
 #include "ef_kernels.hpp"
 #include "ef_rowstat2_kernels.hpp"
+#include "ef_align_kernels.hpp"
 #include "ef_gemm_dma_kernels.hpp"
 #include "ef_prep_kernels.hpp"
 #include "ftm2d_kernels.hpp"
@@ -50,7 +51,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_EFALIGN, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -178,6 +179,11 @@ struct acx_ctx {
     DeviceBuffer<acx::PathSeam> d_pseam;
     DeviceBuffer<acx::PathBox> d_pbox;
     DeviceBuffer<int32_t> d_pcells, d_pn;
+    // ef_align_kernel, per chunk of a batch's pairs: the direction planes (2 bits per cell), the jobs, and the
+    // records, cell counts and cells as the kernel left them (one block: one copy per chunk)
+    DeviceBuffer<unsigned> d_efdir;
+    DeviceBuffer<acx::EfAlignJob> d_efjob;
+    DeviceBuffer<int32_t> d_efres;
     int64_t scratch_limit = 0;                            // bytes
     size_t total_mem = 0;
     // the pair grid: last plan (a pure function of lengths and spec; sorting 10^4 tiles per call is what the cache saves)
@@ -198,7 +204,8 @@ struct acx_ctx {
                              {"ef_fuse_kernel", 0, 0, 0}, {"sw_kernel", 0, 0, 0}, {"rank_columns_kernel", 0, 0, 0},
                              {"topk_rows_kernel", 0, 0, 0}, {"ftm2d_tile_kernel", 0, 0, 0}, {"query_rows_kernel", 0, 0, 0},
                              {"query_topk_kernel", 0, 0, 0}, {"query_rank_kernel", 0, 0, 0}, {"query_topk_lists_kernel", 0, 0, 0},
-                             {"ftm2d_pairs_kernel", 0, 0, 0}, {"qmax_locate_kernel", 0, 0, 0}, {"qmax_path_kernel", 0, 0, 0}};
+                             {"ftm2d_pairs_kernel", 0, 0, 0}, {"qmax_locate_kernel", 0, 0, 0}, {"qmax_path_kernel", 0, 0, 0},
+                             {"ef_align_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
     // How many tracks ensure_f16pool's range check saw when it built d_fh (-1: it had no frame to check).  The largest magnitude of
@@ -1024,6 +1031,10 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
 struct EfStats { uint32_t *bits; float *t; int32_t *jcut; float *r; float *c; };
 struct EfDebug { float *csm, *fused; int32_t *oti; int64_t which = 0; const EfStats *stats = nullptr; };      // which: the pair of the (one-batch) list whose intermediates are wanted
 
+// acx_ef_align: what a run adds to the scores -- for every pair the record of ONE plane (0..3: mfccs, ssms, chromas, early) and,
+// when `paths` is given (K vectors), the cells (q, r) of its path from start to end.  Pair k of the run's list -> al[k], (*paths)[k].
+struct EfAlign { int plane; acx_alignment *al; std::vector<std::vector<int32_t>> *paths; };
+
 // pinned host staging + device copy of `n` score destinations idx[0 .. n)
 static int stage_idx(acx_ctx *c, const int64_t *idx, int64_t n)
 {
@@ -1282,19 +1293,99 @@ static int launch_ef_gemms(acx_ctx *c, const SegBatch &seg, int B, int tiles_x, 
 }
 
 static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params &p, float *out, const EfDebug *dbg,
-                       const float *ext_matrix, int extM, int extN, const DevDst *dd);
+                       const float *ext_matrix, int extM, int extN, const DevDst *dd, const EfAlign *aln);
+
+// The alignment pass (ef_align_kernels.hpp) behind a batch's Smith-Waterman launch, while d_efbits and d_efpd
+// still hold the batch: `pd` are the batch's descriptors on the host, pair b of the batch is pair k0 + b of the run, `scores` its
+// four scores (queued behind the batch's kernels: valid after a wait).  The batch's pairs run in CHUNKS: as many consecutive pairs
+// as fit `budget` bytes of direction planes (M * pitch / 4 bytes a pair; the first pair of a chunk is always taken -- a pair's
+// plane is 1 / 48 of the three float matrices the same pair holds in the batch, so it fits half of any limit the batch fits) and
+// one launch's grid; one launch, one copy and one wait per chunk.  Returns with the stream idle.
+static int64_t ef_align_wave_cap()
+{
+    // development aid (ACX_EF_ALIGN_WAVES=n, read per call): fewer waves per chunk than a launch's 65535, so that a short list runs
+    // in several chunks
+    const char *e = getenv("ACX_EF_ALIGN_WAVES");
+    const long v = e ? atol(e) : 0;
+    return v >= 1 && v < 65535 ? v : 65535;
+}
+
+static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, int64_t k0, int64_t budget, const EfAlign &aln, const float *scores)
+{
+    const int B = (int)pd.size();
+    const int64_t wave_cap = ef_align_wave_cap();
+    std::vector<acx::EfAlignJob> jobs;
+    std::vector<int32_t> h_res;
+    int b = 0;
+    while (b < B) {
+        jobs.clear();
+        int64_t words = 0, ncell = 0, area = 0;
+        const int b0 = b;
+        for (; b < B && (int64_t)jobs.size() < wave_cap; ++b) {
+            const acx::EfPair &d = pd[(size_t)b];
+            const int64_t w = acx::ef_align_dir_words(d.M, d.pitchC);
+            if (!jobs.empty() && 4 * (words + w) > budget) break;
+            acx::EfAlignJob j;
+            j.pair = b; j.max_cells = std::min(d.M, d.N); j.dir_off = words; j.cell_off = ncell;
+            words += w;
+            ncell += j.max_cells;
+            area += (int64_t)d.M * d.N;
+            jobs.push_back(j);
+        }
+        const int nb = (int)jobs.size();
+        const size_t nrec = (size_t)acx::EFA_REC * nb, nres = nrec + 2 * (size_t)ncell;
+        int rc;
+        if ((rc = ensure(c, c->d_efdir, (size_t)words)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_efjob, (size_t)nb)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_efres, nres)) != ACX_OK) return rc;
+        ACX_HIP(c, hipMemcpyAsync(c->d_efjob, jobs.data(), sizeof(acx::EfAlignJob) * nb, hipMemcpyHostToDevice, c->stream));
+        {
+            ProfScope ps(c, KS_EFALIGN, area);
+            hipLaunchKernelGGL(acx::ef_align_kernel, dim3(nb), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, aln.plane);
+        }
+        ACX_HIP(c, hipGetLastError());
+        const size_t ncopy = aln.paths ? nres : nrec;                // (records and counts alone when no path is wanted)
+        h_res.resize(ncopy);
+        ACX_HIP(c, hipMemcpyAsync(h_res.data(), c->d_efres, sizeof(int32_t) * ncopy, hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        for (int t = 0; t < nb; ++t) {
+            const int32_t *rec = h_res.data() + (size_t)acx::EFA_REC * t;
+            const acx::EfAlignJob &j = jobs[(size_t)t];
+            const int64_t k = k0 + b0 + t;
+            acx_alignment a;
+            memcpy(&a.score, rec, sizeof(float));
+            a.q0 = rec[1]; a.r0 = rec[2]; a.q1 = rec[3]; a.r1 = rec[4];
+            const int n = rec[5];
+            // the score is the one the batch's Smith-Waterman launch left for this pair and plane, and a match has its cells
+            if (memcmp(&a.score, scores + 4 * (size_t)(b0 + t) + aln.plane, sizeof(float)) != 0)
+                return fail(c, ACX_ERR_STATE, "ef_align: the alignment of pair " + std::to_string(k) + " does not reach the pair's score");
+            if (n < 0 || n > j.max_cells || (a.score > 0.0f) != (n >= 1))
+                return fail(c, ACX_ERR_STATE, "ef_align: the traceback of pair " + std::to_string(k) + " returned " + std::to_string(n) + " cells");
+            aln.al[k] = a;
+            if (!aln.paths) continue;
+            std::vector<int32_t> &dst = (*aln.paths)[(size_t)k];
+            dst.resize(2 * (size_t)n);
+            const int32_t *src = h_res.data() + nrec + 2 * (size_t)j.cell_off;      // the traceback wrote the cells end first
+            if (n >= 1 && (src[0] != a.q1 || src[1] != a.r1 || src[2 * (n - 1)] != a.q0 || src[2 * (n - 1) + 1] != a.r0))
+                return fail(c, ACX_ERR_STATE, "ef_align: the traceback of pair " + std::to_string(k) + " does not run from the reported end to the reported start");
+            for (int e = 0; e < n; ++e) { dst[2 * (size_t)e] = src[2 * (n - 1 - e)]; dst[2 * (size_t)e + 1] = src[2 * (n - 1 - e) + 1]; }
+        }
+    }
+    drain_profile(c);
+    return ACX_OK;
+}
 
 // `dd` (grid runs): the four scores of pair k go to dd->base[dd->idx[k] .. + 4) on the DEVICE instead of out[4 k ..].
 int run_ef(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params &p, float *out, const EfDebug *dbg,
-           const float *ext_matrix, int extM, int extN, const DevDst *dd = nullptr)
+           const float *ext_matrix, int extM, int extN, const DevDst *dd = nullptr, const EfAlign *aln = nullptr)
 {
-    const int rc = run_ef_impl(c, pairs, K, p, out, dbg, ext_matrix, extM, extN, dd);
+    const int rc = run_ef_impl(c, pairs, K, p, out, dbg, ext_matrix, extM, extN, dd, aln);
     if (rc != ACX_OK) quiesce(c);                // nothing of a failed call stays in flight behind its error code
     return rc;
 }
 
 static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params &p, float *out, const EfDebug *dbg,
-                       const float *ext_matrix, int extM, int extN, const DevDst *dd)
+                       const float *ext_matrix, int extM, int extN, const DevDst *dd, const EfAlign *aln)
 {
     using acx::EfPair;
     if (!ext_matrix && (!c->d_ef[0] || c->ef_open)) return fail(c, ACX_ERR_STATE, "earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)");
@@ -1337,6 +1428,10 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
             if (c->h_efoff[q + 1] - c->h_efoff[q] > acx::EF_MAXNB || c->h_efoff[r + 1] - c->h_efoff[r] > acx::EF_MAXNB) bits_path = false;
         }
     const bool keep_f = !bits_path || (dbg && dbg->fused);
+    if (aln && (ext_matrix || dd || !out))          // (no export gets here: acx_ef_align passes the pool's pairs and a host buffer)
+        return fail(c, ACX_ERR_STATE, "ef_align: the alignment option takes pairs of the pool and scores on the host");
+    if (aln && !bits_path)
+        return fail(c, ACX_ERR_UNSUPPORTED, "ef_align: alignment needs the bit path: at most 1024 blocks");
     if (dbg && dbg->stats && dbg->stats->bits && !bits_path)
         return fail(c, ACX_ERR_INVALID, "ef debug: a track of more than 1024 blocks takes the float path, which leaves no bitmaps (pass a null bitmap pointer)");
     if (!ext_matrix)                              // (the last of the up-front checks: a pair that cannot fit the scratch limit on its own)
@@ -1531,6 +1626,8 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
         } else {
             ACX_HIP(c, hipMemcpyAsync(out + 4 * k0, c->d_out, sizeof(float) * 4 * B, hipMemcpyDeviceToHost, c->stream));
         }
+        // acx_ef_align: the records (and paths) of this batch, while d_efbits still holds it
+        if (aln && (rc = run_ef_align_batch(c, pd, k0, limit / 2, *aln, out + 4 * k0)) != ACX_OK) return rc;
         const double t_s = now();
         ht[2] += t_s - t_b;
         // the next batch's descriptors and rectangles, while the device works on this one
@@ -2844,6 +2941,140 @@ static int sw_bits_binary_impl(acx_ctx *c, const uint8_t *B, int32_t M, int32_t 
     ACX_HIP(c, hipStreamSynchronize(c->stream));
     *score = sc[0];
     return ACX_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// EarlyFusion: where the Smith-Waterman alignment lies, and its path
+// ---------------------------------------------------------------------------------------
+static const char *const EF_ALIGN_TOO_LONG = "alignment needs the bit path: at most 1024 blocks";
+
+static int ef_align_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params *params, int32_t plane, acx_alignment *out,
+                         int64_t *path_off, int32_t *cells, int64_t cap)
+{
+    if (K < 0 || (K > 0 && (!pairs || !out)) || !params || cap < 0) return fail(c, ACX_ERR_INVALID, "ef_align: bad argument");
+    if ((path_off == nullptr) != (cells == nullptr))
+        return fail(c, ACX_ERR_INVALID, "ef_align: path_off and cells must both be given (the paths) or both be NULL (the records alone)");
+    if (plane < 0 || plane > 3) return fail(c, ACX_ERR_INVALID, "ef_align: plane must be 0..3 (mfccs, ssms, chromas, early), got " + std::to_string(plane));
+    if (path_off) path_off[0] = 0;
+    if (K == 0) return ACX_OK;
+    // the whole list before the first launch, on the caller's list (the sorted copy below would name a pair by its sorted position)
+    const bool pool = c->d_ef[0] && !c->ef_open;
+    for (int64_t k = 0; k < K; ++k)
+        if (pairs[2 * k] < 0 || pairs[2 * k + 1] < 0 || pairs[2 * k] >= c->ef_ntracks || pairs[2 * k + 1] >= c->ef_ntracks)
+            return fail(c, pool ? ACX_ERR_INVALID : ACX_ERR_STATE,
+                        pool ? "earlyfusion: track index out of range in pair " + std::to_string(k)
+                             : std::string("earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)"));
+    if (!pool) return fail(c, ACX_ERR_STATE, "earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)");
+    int64_t bound = 0;                           // no path has more cells than its matrix's shorter side
+    for (int64_t k = 0; k < K; ++k) {
+        const int64_t M = c->h_efoff[pairs[2 * k] + 1] - c->h_efoff[pairs[2 * k]], N = c->h_efoff[pairs[2 * k + 1] + 1] - c->h_efoff[pairs[2 * k + 1]];
+        if (M < 1 || N < 1) return fail(c, ACX_ERR_SHORT, "earlyfusion: track without blocks (pair " + std::to_string(k) + ")");
+        if (M > acx::EF_MAXNB || N > acx::EF_MAXNB)
+            return fail(c, ACX_ERR_UNSUPPORTED, std::string("ef_align: ") + EF_ALIGN_TOO_LONG + " (pair " + std::to_string(k) + ": " + std::to_string(M) + " x " + std::to_string(N) + ")");
+        bound += std::min(M, N);
+    }
+    if (path_off && cap < bound)
+        return fail(c, ACX_ERR_INVALID, "ef_align: cap " + std::to_string(cap) + " is too small: " + std::to_string(bound) +
+                                            " cells required (the sum of min(M, N) over the list)");
+    // the list runs sorted by (first track, second track), as acx_earlyfusion_pairs runs it; results go back in the caller's order
+    std::vector<int64_t> order((size_t)K);
+    for (int64_t k = 0; k < K; ++k) order[(size_t)k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+        return pairs[2 * a] != pairs[2 * b] ? pairs[2 * a] < pairs[2 * b] : pairs[2 * a + 1] < pairs[2 * b + 1];
+    });
+    std::vector<int32_t> sp((size_t)2 * K);
+    for (int64_t k = 0; k < K; ++k) { sp[(size_t)2 * k] = pairs[2 * order[(size_t)k]]; sp[(size_t)2 * k + 1] = pairs[2 * order[(size_t)k] + 1]; }
+    std::vector<float> so((size_t)4 * K);
+    std::vector<acx_alignment> sal((size_t)K);
+    std::vector<std::vector<int32_t>> paths(path_off ? (size_t)K : 0);
+    const EfAlign aln{plane, sal.data(), path_off ? &paths : nullptr};
+    const int rc = run_ef(c, sp.data(), K, *params, so.data(), nullptr, nullptr, 0, 0, nullptr, &aln);
+    if (rc != ACX_OK) return rc;
+    for (int64_t k = 0; k < K; ++k) out[order[(size_t)k]] = sal[(size_t)k];
+    if (path_off) {
+        std::vector<int64_t> where((size_t)K);                       // caller's pair -> its position in the run
+        for (int64_t k = 0; k < K; ++k) where[(size_t)order[(size_t)k]] = k;
+        int64_t n = 0;
+        for (int64_t k = 0; k < K; ++k) {
+            const std::vector<int32_t> &pk = paths[(size_t)where[(size_t)k]];
+            if (!pk.empty()) memcpy(cells + 2 * n, pk.data(), sizeof(int32_t) * pk.size());
+            n += (int64_t)pk.size() / 2;
+            path_off[k + 1] = n;
+        }
+    }
+    return ACX_OK;
+}
+
+int acx_ef_align(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params *params, int32_t plane, acx_alignment *out,
+                 int64_t *path_off, int32_t *cells, int64_t cap)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const int rc = ef_align_impl(c, pairs, K, params, plane, out, path_off, cells, cap);
+    if (rc != ACX_OK) quiesce(c);                // nothing of a failed call stays in flight behind its error code
+    return rc;
+}
+
+static int sw_align_binary_impl(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out, int32_t *cells, int64_t cap, int64_t *n_cells)
+{
+    if (!B || !out || M < 1 || N < 1 || cap < 0 || (cells != nullptr) != (n_cells != nullptr)) return fail(c, ACX_ERR_INVALID, "sw_align_binary: bad argument");
+    if (M > acx::EF_MAXNB || N > acx::EF_MAXNB) return fail(c, ACX_ERR_UNSUPPORTED, std::string("sw_align_binary: ") + EF_ALIGN_TOO_LONG);
+    if (cells && cap < std::min(M, N))
+        return fail(c, ACX_ERR_INVALID, "sw_align_binary: cap " + std::to_string(cap) + " is too small: " + std::to_string(std::min(M, N)) +
+                                            " cells required (min(M, N))");
+    if (n_cells) *n_cells = 0;
+    acx::EfPair d;
+    d.q = d.r = 0; d.M = M; d.N = N; d.oti = 0; d.pitchC = round_up(N, 64); d.pitchT = round_up(M, 64); d.kbin = 0;
+    d.ctN = 0; d.pad = 0; d.offB = 0; d.offC = 0; d.offS = 0;
+    // the layout the selection kernels leave in d_efbits: bit j % 32 of word j / 32, M rows of pitchC / 32 words, pads zero
+    const int words = d.pitchC / 32;
+    std::vector<uint32_t> W((size_t)M * words, 0u);
+    for (int i = 0; i < M; ++i)
+        for (int j = 0; j < N; ++j) {
+            const uint8_t b = B[(size_t)i * N + j];
+            if (b > 1) return fail(c, ACX_ERR_INVALID, "sw_align_binary: non-binary elements found in input");
+            W[(size_t)i * words + (j >> 5)] |= (uint32_t)b << (j & 31);
+        }
+    acx::EfAlignJob job;
+    job.pair = 0; job.max_cells = std::min(M, N); job.dir_off = 0; job.cell_off = 0;
+    const size_t nres = (size_t)acx::EFA_REC + 2 * (size_t)job.max_cells;
+    std::vector<int32_t> res(nres);
+    int rc;
+    ACX_HIP(c, hipSetDevice(c->device));
+    if ((rc = ensure(c, c->d_efbits, W.size())) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efpd, (size_t)1)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efjob, (size_t)1)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efdir, (size_t)acx::ef_align_dir_words(M, d.pitchC))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efres, nres)) != ACX_OK) return rc;
+    ACX_HIP(c, hipMemcpyAsync(c->d_efpd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(c->d_efjob, &job, sizeof(job), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(c->d_efbits, W.data(), sizeof(uint32_t) * W.size(), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(acx::ef_align_kernel, dim3(1), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, 0);
+    ACX_HIP(c, hipGetLastError());
+    ACX_HIP(c, hipMemcpyAsync(res.data(), c->d_efres, sizeof(int32_t) * (cells ? nres : (size_t)acx::EFA_REC), hipMemcpyDeviceToHost, c->stream));
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    acx_alignment a;
+    memcpy(&a.score, res.data(), sizeof(float));
+    a.q0 = res[1]; a.r0 = res[2]; a.q1 = res[3]; a.r1 = res[4];
+    const int n = res[5];
+    if (n < 0 || n > job.max_cells || (a.score > 0.0f) != (n >= 1))
+        return fail(c, ACX_ERR_STATE, "sw_align_binary: the traceback returned " + std::to_string(n) + " cells");
+    *out = a;
+    if (cells) {
+        const int32_t *src = res.data() + acx::EFA_REC;             // the traceback wrote the cells end first
+        if (n >= 1 && (src[0] != a.q1 || src[1] != a.r1 || src[2 * (n - 1)] != a.q0 || src[2 * (n - 1) + 1] != a.r0))
+            return fail(c, ACX_ERR_STATE, "sw_align_binary: the traceback does not run from the reported end to the reported start");
+        for (int e = 0; e < n; ++e) { cells[2 * (size_t)e] = src[2 * (n - 1 - e)]; cells[2 * (size_t)e + 1] = src[2 * (n - 1 - e) + 1]; }
+        *n_cells = n;
+    }
+    return ACX_OK;
+}
+
+int acx_sw_align_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out, int32_t *cells, int64_t cap, int64_t *n_cells)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const int rc = sw_align_binary_impl(c, B, M, N, out, cells, cap, n_cells);
+    if (rc != ACX_OK) quiesce(c);                // the queued copies read this call's host buffers: none stays in flight behind an error
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -1,0 +1,171 @@
+// EarlyFusion: WHERE the constrained Smith-Waterman alignment of a binarised matrix lies, and its path.
+//
+// The recursion is E4's (ef_kernels.hpp), in integer tenths on the bitmaps the selection kernels leave in d_efbits:
+//   T[i][j] = max(0, (B[i][j] ? 10 : -10) + max(U[i-1][j-1], U[i-2][j-1], U[i-1][j-2])),  U = T + (B ? 0 : -7),
+//   T = 0 in rows / columns 0, 1;  the cells 2 <= i <= M-2, 2 <= j <= N-2 count.
+// Reported in this T frame (rows = blocks of the query, columns = blocks of the reference):
+//   end    the counted cell, first in row-major order, at which T attains its maximum
+//   pred   of a cell with T > 0: the first of (i-1, j-1), (i-2, j-1), (i-1, j-2) whose U equals the maximum of the three
+//   start  the last cell with T > 0 on the chain of predecessors from the end (its chosen predecessor has T == 0)
+//   path   the cells from start to end; at most min(M, N) (every step lowers row and column by at least one)
+//
+// One wave per job (pair), ONE width for every class: a lane owns 16 contiguous columns, 64 lanes cover the 1024 a row may have.
+// Rows i-1 and i-2 are plain i32 registers (sw_kernel<16>), the left neighbour's edge values come by DPP.  Every cell gets two
+// bits of direction code -- 0: T == 0 (or not counted), 1 / 2 / 3: which predecessor -- so a lane's row is one u32, stored into
+// the job's direction plane: M rows of pitch / 16 words (pitch / 4 bytes a row, at most 256 bytes).  A lane's running
+// maximum is ONE packed integer -- the value, then the earlier row, then the smaller column -- updated by a plain max, so that an
+// earlier row keeps a tie and within a row the smallest column wins; the wave reduction compares the value, then the cell index.  Behind a __threadfence lane 0 walks the codes back from the end
+// (qmax_path_kernel's way): cells are written END FIRST, the driver reverses them.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "../../include/acx.h"
+#include "ef_kernels.hpp"      // EfPair, lane_prev_i
+
+namespace acx {
+
+constexpr int EFA_CPL = 16;                       // columns per lane: 64 lanes x 16 = EF_MAXNB
+constexpr int EFA_REC = 6;                        // int32 words of a job's result: acx_alignment's five fields and the cell count
+static_assert(64 * EFA_CPL == EF_MAXNB, "a wave covers the longest row of the bit path");
+
+struct EfAlignJob {
+    int32_t pair;          // index into the batch's EfPair descriptors
+    int32_t max_cells;     // min(M, N): the room of this job in `cells`
+    int64_t dir_off;       // first u32 word of the job's direction plane
+    int64_t cell_off;      // first cell (x 2 int32) of the job in `cells`
+};
+
+__host__ __device__ __forceinline__ int64_t ef_align_dir_words(int M, int pitch) { return (int64_t)M * (pitch / EFA_CPL); }
+
+__global__ __launch_bounds__(64) void ef_align_kernel(const EfPair *__restrict__ pd, const EfAlignJob *__restrict__ jobs,
+                                                      const unsigned *__restrict__ bits, unsigned *dir,
+                                                      int32_t *__restrict__ res, int plane)
+{
+    // res: EFA_REC words per job -- the acx_alignment record (score's bits, q0, r0, q1, r1) and the number of cells -- then the
+    // cells of all jobs (job.cell_off), so that one copy brings a chunk's results back
+    int32_t *cells = res + (size_t)EFA_REC * gridDim.x;
+    constexpr int CPL = EFA_CPL;
+    const int lane = threadIdx.x;
+    const EfAlignJob job = jobs[blockIdx.x];
+    const EfPair P = pd[job.pair];
+    const int M = P.M, N = P.N, pitch = P.pitchC;
+    acx_alignment a;
+    a.score = 0.0f; a.q0 = a.r0 = a.q1 = a.r1 = -1;
+    int n = 0;
+    if (M >= 4 && N >= 4) {
+        const unsigned char *rows = reinterpret_cast<const unsigned char *>(bits + P.offB + (int64_t)plane * M * (pitch >> 5));
+        const int rowbytes = pitch >> 3, wpr = pitch / CPL;
+        unsigned *my_dir = dir + job.dir_off;
+        const int j0 = CPL * lane;
+        const bool inrow = j0 < pitch;
+        auto load = [&](int row) -> unsigned {
+            const int r = row < M ? row : M - 1;                     // (rows past the last one: a valid address, never used)
+            return inrow ? (unsigned)*reinterpret_cast<const unsigned short *>(rows + (size_t)r * rowbytes + 2 * lane) : 0u;
+        };
+        // A cell is held as V = 4 (U + 8) (U >= -7: positive; the two low bits are free), so that the maximum of the three
+        // predecessors AND which one it is come from one v_max3 of V + 2, V + 1, V + 0 in the order (i-1, j-1), (i-2, j-1),
+        // (i-1, j-2): equal U's leave the first with the largest key.  With base = key & ~3 = 4 (max U + 8):
+        //   4 T = max(0, base - 32 +- 40),  new V = 4 T + (B ? 32 : 4),  code = 3 - (key & 3) where T > 0.
+        // valid: bit e = column j0 + e is counted (2 <= j <= N - 2).  T is forced to 0 elsewhere: columns 0, 1 by the recursion's
+        // definition, columns right of N - 2 because they feed only columns further right -- so a cell with T > 0 is a counted one.
+        unsigned valid = 0u;
+#pragma unroll
+        for (int e = 0; e < CPL; ++e) valid |= (j0 + e >= 2 && j0 + e <= N - 2) ? (1u << e) : 0u;
+        int V1[CPL], V2[CPL];                                        // rows i-1, i-2
+        {
+            const unsigned w0 = load(0), w1 = load(1);               // rows 0 and 1: T = 0, U = delta(B)
+#pragma unroll
+            for (int e = 0; e < CPL; ++e) {
+                V2[e] = 4 + 28 * (int)((w0 >> e) & 1u);
+                V1[e] = 4 + 28 * (int)((w1 >> e) & 1u);
+            }
+        }
+        // The running maximum of a lane as ONE integer, (4 T) << 14 | (1023 - i) << 4 | (15 - e): larger T first, then the earlier
+        // row, then the smaller column (4 T <= 40 960 < 2^16: 30 bits).
+        int best_key = 0;
+        // one row: VA = row i-1, VB = row i-2 (overwritten with row i, from the right: cell e reads VB[e - 1] before it is replaced)
+        auto dp_row = [&](int i, unsigned wb, int (&VA)[CPL], int (&VB)[CPL]) {
+            const int a1 = lane_prev_i(VA[CPL - 1]), a2 = lane_prev_i(VA[CPL - 2]), b1 = lane_prev_i(VB[CPL - 1]);
+            const int row_key = (EF_MAXNB - 1 - i) << 4;
+            unsigned codes = 0u;
+            // (opaque per row: sixteen loop-invariant lane masks hoisted out of the row loop would take 32 SGPRs and spill)
+            int vm = (int)valid;
+            asm volatile("" : "+v"(vm));
+#pragma unroll
+            for (int e = CPL - 1; e >= 0; --e) {
+                const int k2 = ((e >= 1) ? VA[e - 1] : a1) + 2;                           // (i-1, j-1)
+                const int k3 = ((e >= 1) ? VB[e - 1] : b1) + 1;                           // (i-2, j-1)
+                const int k4 = (e >= 2) ? VA[e - 2] : (e == 1 ? a1 : a2);                 // (i-1, j-2)
+                const int key = max(max(k2, k3), k4);
+                const int bit = (int)((wb >> e) & 1u);
+                int t4 = (key & ~3) - 72 + 80 * bit;
+                t4 = max(t4, 0) & __builtin_amdgcn_sbfe(vm, e, 1);                // (sbfe of one bit: 0 or -1)
+                VB[e] = t4 + 4 + 28 * bit;
+                const unsigned code = t4 > 0 ? 3u - (unsigned)(key & 3) : 0u;
+                codes |= code << (2 * e);
+                best_key = max(best_key, ((t4 << 14) | (15 - e)) | row_key);
+            }
+            if (inrow) my_dir[(size_t)i * wpr + lane] = codes;
+        };
+        constexpr int SW_PF = 8;                                     // rows in flight ahead of the recursion, as in sw_bits_h16_kernel
+        unsigned ring[SW_PF];
+#pragma unroll
+        for (int sl = 0; sl < SW_PF; ++sl) ring[sl] = load(2 + sl);
+        for (int i0 = 2; i0 <= M - 2; i0 += SW_PF) {
+#pragma unroll
+            for (int sl = 0; sl < SW_PF; ++sl) {
+                const int i = i0 + sl;
+                if (i <= M - 2) {                                    // wave-uniform
+                    const unsigned wb = ring[sl];
+                    ring[sl] = load(i + SW_PF);
+                    if (sl & 1) dp_row(i, wb, V2, V1); else dp_row(i, wb, V1, V2);      // (i0 and SW_PF are even: row i-1 is V1 for even sl)
+                }
+            }
+        }
+        // the maximum and, among equal maxima, the smallest cell index (a plain maximum would lose which lane's cell comes first)
+        int best = best_key >> 16;                                   // tenths: (4 T) >> 2
+        int best_cell = best > 0 ? (EF_MAXNB - 1 - ((best_key >> 4) & (EF_MAXNB - 1))) * EF_MAXNB + j0 + 15 - (best_key & 15) : 0x7fffffff;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const int ob = __shfl_xor(best, o, 64), oc = __shfl_xor(best_cell, o, 64);
+            if (ob > best || (ob == best && oc < best_cell)) { best = ob; best_cell = oc; }
+        }
+        // the traceback reads the whole plane: same wave, but other lanes' stores, through memory
+        __threadfence();
+        if (lane == 0 && best > 0) {
+            int y = best_cell / EF_MAXNB, x = best_cell % EF_MAXNB;
+            int32_t *dst = cells + 2 * job.cell_off;
+            // It stays inside the counted rectangle (every step lowers row and column; a predecessor outside rows [2, M-2] x
+            // columns [2, N-2] has T = 0 and ends the path), and the bounds keep a plane that broke that promise from being read
+            // or written outside.
+            auto code_at = [&](int yy, int xx) -> unsigned {
+                const unsigned wd = __hip_atomic_load(my_dir + (size_t)yy * wpr + (xx >> 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return (wd >> (2 * (xx & 15))) & 3u;
+            };
+            if (y >= 2 && y <= M - 2 && x >= 2 && x <= N - 2) {
+                unsigned code = code_at(y, x);
+                while (code != 0u && n < job.max_cells) {
+                    dst[2 * n] = y; dst[2 * n + 1] = x;
+                    ++n;
+                    const int py = y - (code == 2u ? 2 : 1), px = x - (code == 3u ? 2 : 1);
+                    if (py < 2 || px < 2) break;                     // rows / columns 0, 1: T = 0
+                    code = code_at(py, px);                          // 0: T == 0 there, (y, x) was the start
+                    if (code != 0u) { y = py; x = px; }
+                }
+            }
+            a.score = (float)best / 10.0f;                           // (a positive score without a cell: the driver reports it)
+            if (n > 0) {
+                a.q1 = best_cell / EF_MAXNB; a.r1 = best_cell % EF_MAXNB;
+                a.q0 = y; a.r0 = x;
+            }
+        }
+    }
+    if (lane == 0) {
+        int32_t *rec = res + (size_t)EFA_REC * blockIdx.x;
+        rec[0] = __float_as_int(a.score); rec[1] = a.q0; rec[2] = a.r0; rec[3] = a.q1; rec[4] = a.r1; rec[5] = n;
+    }
+}
+
+}  // namespace acx

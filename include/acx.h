@@ -543,6 +543,36 @@ int acx_sw_binary(acx_ctx *ctx, const uint8_t *B, int32_t M, int32_t N, float *s
  * in the variants the product launches.  M or N above 1024: ACX_ERR_INVALID; non-{0,1} input as acx_sw_binary. */
 int acx_sw_bits_binary(acx_ctx *ctx, const uint8_t *B, int32_t M, int32_t N, float *score);
 
+/* WHERE the constrained Smith-Waterman alignment of every listed pair lies in ONE of the four binarised matrices, and optionally its
+ * path (ABI 4, additive).  plane: 0 mfccs, 1 ssms, 2 chromas, 3 early (the fused matrix).  With T[i][j] = S[i+1][j+1] of
+ * smith_waterman_constrained (alignment_tools.py:26-46), in integer tenths,
+ *   T[i][j] = max(0, (B[i][j] ? 10 : -10) + max(U[i-1][j-1], U[i-2][j-1], U[i-1][j-2])),  U = T + (B ? 0 : -7),
+ * T = 0 in rows and columns 0, 1, and only the cells 2 <= i <= M-2, 2 <= j <= N-2 count.  Everything is reported in this T frame:
+ * rows are block indices of the query (pairs[2 k]), columns block indices of the reference (pairs[2 k + 1]).
+ *   out[k].score     max T / 10: the bits acx_earlyfusion_pairs returns for that ordered pair and plane
+ *   (q1, r1)         the end: the counted cell, first in row-major order, at which T attains the maximum
+ *   (q0, r0)         the start: follow predecessors from the end -- the predecessor of a cell with T > 0 is the first of
+ *                    (i-1, j-1), (i-2, j-1), (i-1, j-2) whose U equals the maximum of the three -- to the last cell with T > 0
+ *   no match         (score 0; M < 4 or N < 4): the four coordinates are -1
+ *   path_off, cells  both NULL: the records alone.  Both given: pair k's path is cells[2 path_off[k] .. 2 path_off[k + 1]), the
+ *                    (q, r) of every cell from the start to the end, both included; consecutive cells differ by (1, 1), (2, 1) or
+ *                    (1, 2); a pair without a match has none.  Exactly one of the two NULL: ACX_ERR_INVALID.
+ *   cap              cells the buffer holds: at least the sum of min(M_k, N_k) over the list, checked before the first launch;
+ *                    too small -> ACX_ERR_INVALID with the required number in the message
+ * Results come back in the order of the caller's list (the run sorts it as acx_earlyfusion_pairs does).  The whole list is checked
+ * before the first launch: a track of more than 1024 blocks anywhere in it -> ACX_ERR_UNSUPPORTED ("alignment needs the bit
+ * path: at most 1024 blocks"); plane outside 0..3 -> ACX_ERR_INVALID; an index out of range, a track without blocks, no pool:
+ * the codes and messages of acx_earlyfusion_pairs.  A failed call leaves nothing in flight, and a valid call after it succeeds. */
+int acx_ef_align(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_ef_params *params, int32_t plane /* 0..3 */,
+                 acx_alignment *out /* K */, int64_t *path_off /* K + 1 or NULL */, int32_t *cells /* cap x 2 or NULL */, int64_t cap);
+
+/* The same DP alone on a caller's binary (M, N) uint8 plot (tests), packed on the host as acx_sw_bits_binary packs it.  cells and
+ * n_cells both NULL: the record alone; both given: cap >= min(M, N) (else ACX_ERR_INVALID, nothing launched), the path goes to
+ * cells (cap x 2 int32) from the start to the end and *n_cells is its length.  M or N above 1024: ACX_ERR_UNSUPPORTED; a value
+ * above 1 in B: ACX_ERR_INVALID. */
+int acx_sw_align_binary(acx_ctx *ctx, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out, int32_t *cells, int64_t cap,
+                        int64_t *n_cells);
+
 /* ---- FTM2D (2D Fourier transform magnitudes, Bertin-Mahieux & Ellis) ------ */
 
 /* Constructor arguments of FTM2D (ftm2d.py:23): defaults PWR 1.96, WIN 75, C 5. */
