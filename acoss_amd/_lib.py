@@ -44,6 +44,7 @@ EXPORTS = [
     "acx_serra09_align_paths", "acx_qmax_path_binary",
     "acx_ef_debug_bits", "acx_csm_debug_bits", "acx_sw_bits_binary",
     "acx_ef_align", "acx_sw_align_binary",
+    "acx_simple_profile",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -58,6 +59,13 @@ class AcxError(RuntimeError):
 
 # acx_alignment (include/acx.h): max Q, the path's start (q0, r0) and end (q1, r1) in plot rows / columns; -1: no match
 ALIGNMENT_DTYPE = np.dtype([("score", np.float32), ("q0", np.int32), ("r0", np.int32), ("q1", np.int32), ("r1", np.int32)])
+
+
+# acx_simple_alignment (include/acx.h): the score, the profile's smallest value and where it lies, and the matched section
+SIMPLE_ALIGNMENT_DTYPE = np.dtype([("score", np.float64), ("best_dist", np.float64), ("shift", np.int32), ("best_q", np.int32),
+                                   ("best_r", np.int32), ("q0", np.int32), ("r0", np.int32), ("q1", np.int32), ("r1", np.int32),
+                                   ("q_span", np.int32, (2,)), ("r_span", np.int32, (2,)), ("run_len", np.int32)])
+assert SIMPLE_ALIGNMENT_DTYPE.itemsize == 64
 
 
 class EfParams(ctypes.Structure):
@@ -239,6 +247,8 @@ def load():
                                              ctypes.c_int32, lp]
     L.acx_download_pool_f64.argtypes = [vp, dp, ctypes.c_int64]
     L.acx_simple_pairs.argtypes = [vp, ip, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, dp]
+    L.acx_simple_profile.argtypes = [vp, ip, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
     ep = ctypes.POINTER(EfParams)
     L.acx_ef_upload_pool.argtypes = [vp, fp, fp, fp, dp, lp, ctypes.c_int32, ip]
     L.acx_ef_pool_begin.argtypes = [vp, lp, ctypes.c_int32, ip]
@@ -623,6 +633,34 @@ class Context(object):
                                              len(pairs), int(sslen), int(bool(oti)),
                                              out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
         return out
+
+    def simple_profile(self, pairs, sslen=10, oti=True, profiles=False, cap=None):
+        """The matrix profile behind simple_pairs' score (acx_simple_profile): a (K,) structured array (SIMPLE_ALIGNMENT_DTYPE)
+        -- score = simple_pairs' value, the OTI shift, where the profile is smallest (best_q, best_r, best_dist) and the
+        matched section, the longest run of rows whose nearest neighbours are consecutive columns (q0, r0) .. (q1, r1), spans in
+        pooled frames, run_len.  profiles=True: (records, offsets (K + 1,) int64, mp (offsets[-1],) f64, mpi (offsets[-1],)
+        int32), pair k's profile and index being [offsets[k]:offsets[k + 1]].  cap: elements the buffers hold; default the
+        number the library requires, the sum of ma over the list."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros(len(pairs), SIMPLE_ALIGNMENT_DTYPE)
+        if not profiles:
+            self._check(self._L.acx_simple_profile(self._h, _iptr(pairs), len(pairs), int(sslen), int(bool(oti)), out.ctypes.data,
+                                                   None, None, None, 0))
+            return out
+        if cap is None:
+            # (a list the library refuses -- no pool, an index out of range, a short track -- is refused before it looks at cap)
+            try:
+                n = self.pool_lengths(ALGO_SIMPLE)
+            except AcxError:
+                n = np.zeros(0, np.int64)
+            ok = np.all((pairs >= 0) & (pairs < len(n)), axis=1) if len(pairs) else np.zeros(0, bool)
+            cap = int(np.maximum(n[pairs[ok, 0]] - int(sslen) + 1, 0).sum())
+        off = np.zeros(len(pairs) + 1, np.int64)
+        mp = np.zeros(max(int(cap), 1), np.float64)
+        mpi = np.zeros(max(int(cap), 1), np.int32)
+        self._check(self._L.acx_simple_profile(self._h, _iptr(pairs), len(pairs), int(sslen), int(bool(oti)), out.ctypes.data,
+                                               off.ctypes.data, mp.ctypes.data, mpi.ctypes.data, int(cap)))
+        return out, off, mp[:off[-1]].copy(), mpi[:off[-1]].copy()
 
     def ef_upload_pool(self, tracks, slice_bytes=1 << 30):
         """tracks: list of dicts with mfccs (nb,650), ssms (nb,1225), chromas (nb,480) f32 and

@@ -10,6 +10,7 @@ run in libacx's HIP kernel, in f64 like the reference.
 import numpy as np
 
 from .. import _lib
+from . import _align
 from .algorithm_template import CoverAlgorithm
 
 __all__ = ["Simple"]
@@ -140,6 +141,58 @@ class Simple(CoverAlgorithm):
 
     def _grid(self):
         return self._context(), _lib.ALGO_SIMPLE, _lib.SimpleParams(int(self.SSLEN), 1), ["main"]
+
+    # ------------------------------------------------------------------ where the match lies
+    # align() / profile() / align_matches(): acx_simple_alignment (include/acx.h).  Rows and columns are subsequence starts in
+    # POOLED frames of the query / the reference; the spans are [first, last] inclusive pooled frames
+    ALIGN_DTYPE = _lib.SIMPLE_ALIGNMENT_DTYPE
+
+    def _no_match_rows(self, shape):
+        """An empty slot of align_matches: -1 in every position, run_len 0, score and best_dist NaN."""
+        out = _align.no_match_rows(shape, self.ALIGN_DTYPE)
+        for f in ("best_q", "best_r"):
+            out[f] = -1
+        for f in ("score", "best_dist"):
+            out[f] = np.nan
+        return out
+
+    def align(self, idxs):
+        """WHICH part of the reference did the query match?  idxs: (K, 2) (query, reference) track indices over the uploaded
+        collection, ORDERED pairs as similarity() scores them.  Returns a (K,) structured array: score (the f64 value
+        similarity() computes for the pair, before Ds['main'] rounds it to f32), shift (the OTI shift applied to the
+        reference), best_q / best_r / best_dist (the subsequence of the query that lies closest to the reference, its nearest
+        neighbour there and their squared distance: the smallest value of the matrix profile, first row on ties), and the
+        matched section: the longest run of consecutive query subsequences q0 .. q1 whose nearest neighbours r0 .. r1 are
+        consecutive too (run_len of them; of several longest the first), with q_span = [q0, q1 + SSLEN - 1] and r_span =
+        [r0, r1 + SSLEN - 1] in pooled frames.  A pair always has a match (run_len >= 1).  `Ds` is not written; not a
+        collective."""
+        pairs = _align.check_pairs("align", _align.check_indices("align", idxs), self.N)
+        if len(pairs) == 0:
+            return np.zeros(0, self.ALIGN_DTYPE)
+        return self._context().simple_profile(pairs, self.SSLEN)
+
+    def profile(self, idxs):
+        """align() and the matrix profiles themselves: (al, mps, mpis).  al is exactly what align(idxs) returns; mps[k] is the
+        (ma_k,) f64 profile of pair k -- for every subsequence of the query (ma_k = n_query - SSLEN + 1 of them) the squared
+        distance to its nearest subsequence of the reference -- and mpis[k] the (ma_k,) int32 index, which subsequence that is
+        (the first of equally near ones).  -median(mps[k]) is al['score'][k]."""
+        pairs = _align.check_pairs("profile", _align.check_indices("profile", idxs), self.N)
+        if len(pairs) == 0:
+            return np.zeros(0, self.ALIGN_DTYPE), [], []
+        al, off, mp, mpi = self._context().simple_profile(pairs, self.SSLEN, profiles=True)
+        return al, [mp[off[k]:off[k + 1]] for k in range(len(pairs))], [mpi[off[k]:off[k + 1]] for k in range(len(pairs))]
+
+    def align_matches(self, queries, indices):
+        """align() for the hits of identify() / rerank(): queries (Q,) track indices, indices the (Q, k) int array either
+        returned (-1: an empty slot).  Returns a (Q, k) structured array as align() does, row i slot s being the ORDERED pair
+        (queries[i], indices[i, s]) -- the pair identify() scored.  An empty slot comes back as a no-match row: -1 in every
+        position, run_len 0, score and best_dist NaN."""
+        who = "align_matches"
+        idx, rows, slots, pairs = _align.check_matches(who, _align.check_indices(who, queries), _align.check_indices(who, indices), self.N)
+        out = self._no_match_rows(idx.shape)
+        if len(pairs):
+            out[rows, slots] = self._context().simple_profile(pairs, self.SSLEN)
+        return out
 
     def similarity(self, idxs):
         idxs = np.asarray(idxs).reshape(-1, 2)

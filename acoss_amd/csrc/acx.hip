@@ -25,6 +25,7 @@
 #include "prep_kernels.hpp"
 #include "snf_kernels.hpp"
 #include "simple_kernels.hpp"
+#include "simple_profile_kernels.hpp"
 #include "ef_kernels.hpp"
 #include "ef_rowstat2_kernels.hpp"
 #include "ef_align_kernels.hpp"
@@ -51,7 +52,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_EFALIGN, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_SIMPLEPROF, KS_EFALIGN, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -122,6 +123,12 @@ struct acx_ctx {
     int32_t n_tracks64 = 0;
     DeviceBuffer<int32_t> d_pairs;
     DeviceBuffer<double> d_out64;
+    // simple_profile_kernel, per chunk of pairs: the records, where each pair's profile starts, the profiles
+    // and their indices
+    DeviceBuffer<acx::SimpleProfileRec> d_sprec;
+    DeviceBuffer<int64_t> d_spoff;
+    DeviceBuffer<double> d_spmp;
+    DeviceBuffer<int32_t> d_spmpi;
     // EarlyFusion pool
     DeviceBuffer<float> d_ef[3];
     DeviceBuffer<unsigned short> d_efs[3];            // mfcc / ssm / chroma block features as three-term bf16 splits
@@ -205,7 +212,7 @@ struct acx_ctx {
                              {"topk_rows_kernel", 0, 0, 0}, {"ftm2d_tile_kernel", 0, 0, 0}, {"query_rows_kernel", 0, 0, 0},
                              {"query_topk_kernel", 0, 0, 0}, {"query_rank_kernel", 0, 0, 0}, {"query_topk_lists_kernel", 0, 0, 0},
                              {"ftm2d_pairs_kernel", 0, 0, 0}, {"qmax_locate_kernel", 0, 0, 0}, {"qmax_path_kernel", 0, 0, 0},
-                             {"ef_align_kernel", 0, 0, 0}};
+                             {"simple_profile_kernel", 0, 0, 0}, {"ef_align_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
     // How many tracks ensure_f16pool's range check saw when it built d_fh (-1: it had no frame to check).  The largest magnitude of
@@ -1718,6 +1725,33 @@ static int launch_simple_sslen(acx_ctx *c, int sslen, int n, size_t smem, int ot
     return fail(c, ACX_ERR_UNSUPPORTED, "simple: SSLEN must be in 1..16 on the device");
 }
 
+// simple_profile_kernel's LDS per wave: simple_kernel's + the profile's index (4 bytes per row, kept a multiple of 16)
+static size_t simple_profile_smem(int maxn) { return simple_smem(maxn) + (4 * (size_t)maxn + 15) / 16 * 16; }
+
+// d_poff: where each pair's profile starts in d_mp / d_mpi; nullptr: the records alone
+template <int L>
+int launch_simple_profile(acx_ctx *c, int n, size_t smem, int oti, const int64_t *d_poff)
+{
+    auto kern = acx::simple_profile_kernel<L>;
+    int wpb = acx::SIMPLE_WPB;                        // the step-down of launch_simple
+    while (wpb > 1 && smem * wpb > 160 * 1024) --wpb;
+    ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(smem * wpb)));
+    hipLaunchKernelGGL(kern, dim3((n + wpb - 1) / wpb), dim3(64 * wpb), smem * wpb, c->stream, c->d_frames64, c->d_toff64,
+                       c->d_prof64, c->d_wn64, c->d_pairs, c->d_sprec, d_poff, c->d_spmp, c->d_spmpi, oti, n, (int)smem);
+    return ACX_OK;
+}
+
+static int launch_simple_profile_sslen(acx_ctx *c, int sslen, int n, size_t smem, int oti, const int64_t *d_poff)
+{
+    switch (sslen) {
+#define ACX_L(L_) case L_: return launch_simple_profile<L_>(c, n, smem, oti, d_poff);
+        ACX_L(1) ACX_L(2) ACX_L(3) ACX_L(4) ACX_L(5) ACX_L(6) ACX_L(7) ACX_L(8)
+        ACX_L(9) ACX_L(10) ACX_L(11) ACX_L(12) ACX_L(13) ACX_L(14) ACX_L(15) ACX_L(16)
+#undef ACX_L
+    }
+    return fail(c, ACX_ERR_UNSUPPORTED, "simple_profile: SSLEN must be in 1..16 on the device");
+}
+
 // |x_t|^2 summed over every window of `sslen` frames of the f64 pool: built on first use per (pool, SSLEN)
 static int ensure_winnorm(acx_ctx *c, int sslen)
 {
@@ -2441,6 +2475,101 @@ int acx_simple_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, int32_t sslen,
         ACX_HIP(c, hipStreamSynchronize(c->stream));
         for (int k = 0; k < n; ++k) out[k0 + order[k]] = tmp[k];
         drain_profile(c);
+    }
+    return ACX_OK;
+}
+
+static_assert(sizeof(acx_simple_alignment) == sizeof(acx::SimpleProfileRec) && offsetof(acx_simple_alignment, run_len) == offsetof(acx::SimpleProfileRec, run_len) &&
+              offsetof(acx_simple_alignment, q_span) == offsetof(acx::SimpleProfileRec, q_span), "simple_profile_kernel writes acx_simple_alignment");
+
+int acx_simple_profile(acx_ctx *c, const int32_t *pairs, int64_t K, int32_t sslen, int32_t oti, acx_simple_alignment *out,
+                       int64_t *offsets, double *mp, int32_t *mpi, int64_t cap)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (K < 0 || (K > 0 && (!pairs || !out)) || cap < 0) return fail(c, ACX_ERR_INVALID, "simple_profile: bad argument");
+    const bool want = offsets || mp || mpi;
+    if (want && !(offsets && mp && mpi))
+        return fail(c, ACX_ERR_INVALID, "simple_profile: offsets, mp and mpi must all be given (the profiles) or all be NULL (the records alone)");
+    if (K == 0) { if (want) offsets[0] = 0; return ACX_OK; }
+    if (!c->d_frames64) return fail(c, ACX_ERR_STATE, "simple_profile: f64 feature pool not uploaded (acx_upload_pool_f64)");
+    if (sslen < 1 || sslen > acx::SIMPLE_MAXL) return fail(c, ACX_ERR_UNSUPPORTED, "simple_profile: SSLEN must be in 1..16 on the device");
+    ACX_HIP(c, hipSetDevice(c->device));
+    int maxn = 0;
+    for (int64_t k = 0; k < K; ++k) {
+        for (int s = 0; s < 2; ++s) {
+            const int t = pairs[2 * k + s];
+            if (t < 0 || t >= c->n_tracks64) return fail(c, ACX_ERR_INVALID, "simple_profile: track index out of range in pair " + std::to_string(k));
+            const int n = (int)(c->h_off64[t + 1] - c->h_off64[t]);
+            if (n < sslen) return fail(c, ACX_ERR_SHORT, "simple_profile: track shorter than SSLEN (pair " + std::to_string(k) + ")");
+            if (n > acx::SIMPLE_MAXN) return fail(c, ACX_ERR_UNSUPPORTED, "simple_profile: tracks with more than 6000 pooled frames are not supported on the device");
+            maxn = std::max(maxn, n);
+        }
+    }
+    auto rows = [&](int64_t k) { const int t = pairs[2 * k]; return (int64_t)(c->h_off64[t + 1] - c->h_off64[t]) - sslen + 1; };
+    // a chunk's device profiles: 12 bytes per row (f64 value + int32 index), inside the scratch limit
+    const int64_t row_limit = want ? scratch_limit_bytes(c) / 12 : 0;
+    if (want) {
+        int64_t need = 0;
+        for (int64_t k = 0; k < K; ++k) need += rows(k);
+        if (cap < need)
+            return fail(c, ACX_ERR_INVALID, "simple_profile: cap " + std::to_string(cap) + " is too small: " + std::to_string(need) +
+                                                " elements are required (the sum of ma over the list)");
+        for (int64_t k = 0; k < K; ++k)
+            if (rows(k) > row_limit)
+                return fail(c, ACX_ERR_NOMEM, "simple_profile: the profile of pair " + std::to_string(k) + " (" + std::to_string(rows(k)) +
+                                                  " rows) does not fit the scratch limit (acx_set_scratch_limit)");
+    }
+    const size_t smem = simple_profile_smem(maxn);
+    int rc = ensure_winnorm(c, sslen);
+    if (rc != ACX_OK) return rc;
+    if (want) { offsets[0] = 0; for (int64_t k = 0; k < K; ++k) offsets[k + 1] = offsets[k] + rows(k); }
+    const int64_t chunk = 1 << 22;
+    std::vector<int32_t> order, sorted, bucket;
+    std::vector<int64_t> poff;
+    std::vector<acx::SimpleProfileRec> tmp;
+    for (int64_t k0 = 0; k0 < K;) {
+        // the caller's pairs k0 .. k0 + n - 1: as many as the pair limit and the profile buffer take (at least one: checked above)
+        int n = 0;
+        int64_t nrows = 0;
+        while (k0 + n < K && n < chunk && (!want || nrows + rows(k0 + n) <= row_limit)) { nrows += rows(k0 + n); ++n; }
+        if ((rc = ensure(c, c->d_pairs, (size_t)2 * n)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_sprec, (size_t)n)) != ACX_OK) return rc;
+        if (want) {
+            if ((rc = ensure(c, c->d_spoff, (size_t)n)) != ACX_OK) return rc;
+            if ((rc = ensure(c, c->d_spmp, (size_t)std::max<int64_t>(1, nrows))) != ACX_OK) return rc;
+            if ((rc = ensure(c, c->d_spmpi, (size_t)std::max<int64_t>(1, nrows))) != ACX_OK) return rc;
+        }
+        // sorted by the second track as acx_simple_pairs sorts (stable counting sort); a pair's profile keeps its place in the
+        // CALLER's order, so the chunk's buffer is a slice of the caller's and comes back in one copy
+        order.resize(n);
+        const int32_t *pp = pairs + 2 * k0;
+        bucket.assign((size_t)c->n_tracks64 + 1, 0);
+        for (int k = 0; k < n; ++k) ++bucket[(size_t)pp[2 * k + 1] + 1];
+        for (int t = 0; t < c->n_tracks64; ++t) bucket[t + 1] += bucket[t];
+        for (int k = 0; k < n; ++k) order[bucket[pp[2 * k + 1]]++] = k;
+        sorted.resize((size_t)2 * n);
+        for (int k = 0; k < n; ++k) { sorted[2 * k] = pp[2 * order[k]]; sorted[2 * k + 1] = pp[2 * order[k] + 1]; }
+        ACX_HIP(c, hipMemcpyAsync(c->d_pairs, sorted.data(), sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
+        if (want) {
+            poff.resize(n);
+            for (int k = 0; k < n; ++k) poff[k] = offsets[k0 + order[k]] - offsets[k0];
+            ACX_HIP(c, hipMemcpyAsync(c->d_spoff, poff.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, c->stream));
+        }
+        {
+            ProfScope ps(c, KS_SIMPLEPROF, n);
+            if ((rc = launch_simple_profile_sslen(c, sslen, n, smem, oti, want ? c->d_spoff.get() : nullptr)) != ACX_OK) return rc;
+        }
+        ACX_LAUNCHES_OK(c);
+        tmp.resize(n);
+        ACX_HIP(c, hipMemcpyAsync(tmp.data(), c->d_sprec, sizeof(acx::SimpleProfileRec) * n, hipMemcpyDeviceToHost, c->stream));
+        if (want && nrows > 0) {
+            ACX_HIP(c, hipMemcpyAsync(mp + offsets[k0], c->d_spmp, sizeof(double) * nrows, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(mpi + offsets[k0], c->d_spmpi, sizeof(int32_t) * nrows, hipMemcpyDeviceToHost, c->stream));
+        }
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        for (int k = 0; k < n; ++k) memcpy(&out[k0 + order[k]], &tmp[k], sizeof(acx_simple_alignment));
+        drain_profile(c);
+        k0 += n;
     }
     return ACX_OK;
 }

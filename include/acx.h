@@ -368,6 +368,41 @@ int acx_download_pool_f64(acx_ctx *ctx, double *frames, int64_t capacity);
 int acx_simple_pairs(acx_ctx *ctx, const int32_t *pairs, int64_t K, int32_t sslen, int32_t oti,
                      double *out);
 
+/*
+ * The matrix profile behind acx_simple_pairs' score, its index, and the matched section (ABI 4, additive).  For the ORDERED
+ * pair (q, r) = (pairs[2k], pairs[2k+1]): A = track q (na frames), B' = track r rolled by the OTI shift (nb frames), L = sslen,
+ * ma = na - L + 1 rows, mb = nb - L + 1 columns, D[a][b] the distance acx_simple_pairs' kernel computes for that cell (the same
+ * operations in the same order).
+ *   MP[a]       min over b of D[a][b]
+ *   MPI[a]      the SMALLEST b with D[a][b] == MP[a] (the first minimum)
+ *   score       -median(MP): the f64 bits acx_simple_pairs returns for the pair;  shift: the OTI shift used (0 with oti = 0)
+ *   best_q      the smallest a with MP[a] == min MP;  best_r = MPI[best_q];  best_dist = MP[best_q]
+ *   section     the longest maximal run of consecutive rows a0 .. a0 + n - 1 with MPI[a + 1] == MPI[a] + 1 (of several longest
+ *               the one with the smallest a0; n >= 1 always: a SiMPle pair always has a match):
+ *               q0 = a0, r0 = MPI[a0], q1 = a0 + n - 1, r1 = r0 + n - 1, run_len = n,
+ *               q_span = [q0, q1 + L - 1], r_span = [r0, r1 + L - 1]: [first, last] inclusive in pooled frames
+ */
+typedef struct {
+    double score, best_dist;
+    int32_t shift, best_q, best_r;
+    int32_t q0, r0, q1, r1;
+    int32_t q_span[2], r_span[2];
+    int32_t run_len;
+} acx_simple_alignment;
+
+/*
+ * out: K records.  offsets, mp and mpi all NULL: the records alone.  All three given: offsets has K + 1 entries, offsets[0] = 0
+ * and offsets[k + 1] - offsets[k] = ma_k; pair k's profile is mp[offsets[k] ..] (f64) and its index mpi[offsets[k] ..] (int32);
+ * cap = the number of elements mp and mpi each hold, at least offsets[K]: too small -> ACX_ERR_INVALID with the required number
+ * in the message.  Some but not all of the three NULL: ACX_ERR_INVALID.  The whole list is checked before the first launch with
+ * the codes of acx_simple_pairs (index out of range ACX_ERR_INVALID, a track shorter than sslen ACX_ERR_SHORT, sslen outside
+ * 1..16 or a track above 6000 frames ACX_ERR_UNSUPPORTED, no f64 pool ACX_ERR_STATE).  The pairs run sorted by their second
+ * track, in chunks whose device profile buffer stays inside acx_set_scratch_limit (one pair whose profile does not fit:
+ * ACX_ERR_NOMEM); results come back in the order of the caller's list.
+ */
+int acx_simple_profile(acx_ctx *ctx, const int32_t *pairs, int64_t K, int32_t sslen, int32_t oti,
+                       acx_simple_alignment *out, int64_t *offsets, double *mp, int32_t *mpi, int64_t cap);
+
 /* ---- EarlyFusion (Tralie 2017) per-pair chain ---------------------------- */
 
 /*
