@@ -1981,16 +1981,22 @@ __global__ __launch_bounds__(256) void ef_rowstat_long_kernel(const EfPair *__re
     if (mode != 2) {
         const int kk = kw < n ? kw : n;
         const float vk = ef_select_stream(v, n, kk - 1, lane);
+        // in the ORDER of the register kernels (mean_k_smallest + ef_wave_sum_f: a lane adds columns 256 q + 4 lane + e, q then e, a
+        // cell not below vk adding 0.0f): a batch whose longest track has more than 1024 blocks runs this kernel for ALL its pairs,
+        // and a short pair's r must not depend on what shares its batch.  Rows of more than 1024 cells: the same order, carried on.
         float acc = 0.0f;
         int cnt = 0;
-        for (int j = lane; j < n; j += 64) {
-            const float x = v[j];
-            if (x < vk) { acc += x; ++cnt; }
+        for (int j0 = 4 * lane; j0 < n; j0 += 256) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float x = j0 + e < n ? v[j0 + e] : INF;
+                const bool lt = x < vk;
+                acc += lt ? x : 0.0f;
+                cnt += lt ? 1 : 0;
+            }
         }
         const int tot = wave_sum_i(cnt);
-        float sm = acc;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) sm += __shfl_xor(sm, o, 64);
+        const float sm = ef_wave_sum_f(acc);
         const float m = (sm + (float)(kk - tot) * vk) / (float)kk;
         if (lane == 0) S[(mode == 0 ? P.pitchT : 2 * P.pitchT) + row] = m;
     }
