@@ -42,6 +42,7 @@ EXPORTS = [
     "acx_pool_truncate",
     "acx_serra09_align", "acx_qmax_locate_binary",
     "acx_serra09_align_paths", "acx_qmax_path_binary",
+    "acx_chenfusion_align", "acx_chenfusion_align_paths", "acx_dmax_locate_binary", "acx_dmax_path_binary",
     "acx_ef_debug_bits", "acx_csm_debug_bits", "acx_sw_bits_binary",
     "acx_ef_align", "acx_sw_align_binary",
     "acx_simple_profile",
@@ -277,6 +278,11 @@ def load():
     L.acx_serra09_align_paths.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
     L.acx_qmax_path_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, pp, ctypes.c_void_p,
                                        ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_int64]
+    L.acx_chenfusion_align.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.c_int32, ctypes.c_void_p]
+    L.acx_chenfusion_align_paths.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int64]
+    L.acx_dmax_locate_binary.argtypes = L.acx_qmax_locate_binary.argtypes
+    L.acx_dmax_path_binary.argtypes = L.acx_qmax_path_binary.argtypes
     L.acx_ef_align.argtypes = [vp, ip, ctypes.c_int64, ep, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
     L.acx_sw_align_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
@@ -1133,6 +1139,58 @@ class Context(object):
         n = ctypes.c_int64(0)
         cells = np.zeros((max(int(cap), 1), 2), np.int32)
         self._check(self._L.acx_qmax_path_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), R.shape[0], R.shape[1],
+                                                 ctypes.byref(p), out.ctypes.data, ctypes.byref(n), cells.ctypes.data, int(cap)))
+        return out, cells[:n.value].copy()
+
+    def chenfusion_align(self, pairs, params=None, plane=0):
+        """WHERE the alignment of one plane of chenfusion_pairs lies (acx_chenfusion_align): plane 0 Qmax -- serra09_align itself --,
+        plane 1 Dmax (score = chenfusion_pairs' column 1).  A (K,) structured array as serra09_align returns it.  The Dmax start need
+        not hold Q = 1 and can be a gap cell beside the recurrence the alignment begins at."""
+        p = params or serra09_params()
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
+        self._check(self._L.acx_chenfusion_align(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), out.ctypes.data))
+        return out
+
+    def chenfusion_align_paths(self, pairs, params=None, plane=0, cap=None):
+        """The alignments of one plane AND their paths (acx_chenfusion_align_paths): (records, offsets, cells) as serra09_align_paths
+        returns them, `cap` as there."""
+        p = params or serra09_params()
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        if cap is None:
+            Ms = {t: max(self.serra09_embed_len(self.lengths[t], p), 0) for t in {int(t) for t in pairs.ravel()} if 0 <= t < len(self.lengths)}
+            cap = sum(min(Ms.get(int(i), 0), Ms.get(int(j), 0)) for i, j in pairs)
+        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
+        off = np.zeros(len(pairs) + 1, np.int64)
+        cells = np.zeros((max(int(cap), 1), 2), np.int32)
+        self._check(self._L.acx_chenfusion_align_paths(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), out.ctypes.data,
+                                                       off.ctypes.data, cells.ctypes.data, int(cap)))
+        return out, off, cells[:off[-1]].copy()
+
+    def dmax_locate_binary(self, R, params=None):
+        """The Dmax alignment of a given binary (M, N) cross recurrence plot (acx_dmax_locate_binary): a (1,) structured array."""
+        p = params or serra09_params()
+        R = np.ascontiguousarray(R, dtype=np.uint8)
+        if R.ndim != 2:
+            raise ValueError("dmax_locate_binary: R must be (M, N), got shape %s" % (R.shape,))
+        out = np.zeros(1, ALIGNMENT_DTYPE)
+        self._check(self._L.acx_dmax_locate_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                                   R.shape[0], R.shape[1], ctypes.byref(p), out.ctypes.data))
+        return out
+
+    def dmax_path_binary(self, R, params=None, cap=None):
+        """The same with its path (acx_dmax_path_binary): (record (1,), cells (L, 2) int32 from the start to the end; L == 0: no
+        match).  cap: default min(M, N)."""
+        p = params or serra09_params()
+        R = np.ascontiguousarray(R, dtype=np.uint8)
+        if R.ndim != 2:
+            raise ValueError("dmax_path_binary: R must be (M, N), got shape %s" % (R.shape,))
+        if cap is None:
+            cap = min(R.shape)
+        out = np.zeros(1, ALIGNMENT_DTYPE)
+        n = ctypes.c_int64(0)
+        cells = np.zeros((max(int(cap), 1), 2), np.int32)
+        self._check(self._L.acx_dmax_path_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), R.shape[0], R.shape[1],
                                                  ctypes.byref(p), out.ctypes.data, ctypes.byref(n), cells.ctypes.data, int(cap)))
         return out, cells[:n.value].copy()
 

@@ -216,18 +216,23 @@ class Serra09(CoverAlgorithm):
             raise ValueError("%s: the Qmax alignment only (engine dmax must be 0)" % who)
         return _align.check_indices(who, idxs)
 
-    def _align_pairs(self, pairs, paths=None):
-        """(K, 2) checked int32 pairs -> (K,) ALIGN_DTYPE.  paths: a list that receives the K (L_k, 2) int32 paths as well."""
+    def _align_call(self, pairs, want_paths, plane=0):
+        """The library call behind _align_pairs: (records, offsets, cells), the last two None without paths."""
+        if not want_paths:
+            return self._context().serra09_align(pairs, self._params()), None, None
+        return self._context().serra09_align_paths(pairs, self._params())
+
+    def _align_pairs(self, pairs, paths=None, plane=0):
+        """(K, 2) checked int32 pairs -> (K,) ALIGN_DTYPE.  paths: a list that receives the K (L_k, 2) int32 paths as well.
+        plane: what a subclass with more than one alignment hands to its _align_call."""
         out = np.zeros(len(pairs), self.ALIGN_DTYPE)
         out["score"] = 0.0
         for f in ("q0", "r0", "q1", "r1", "q_span", "r_span"):
             out[f] = -1
         if len(pairs) == 0:
             return out
-        if paths is None:
-            al = self._context().serra09_align(pairs, self._params())
-        else:
-            al, off, cells = self._context().serra09_align_paths(pairs, self._params())
+        al, off, cells = self._align_call(pairs, paths is not None, plane)
+        if paths is not None:
             paths.extend(cells[off[k]:off[k + 1]] for k in range(len(pairs)))
         for f in _lib.ALIGNMENT_DTYPE.names:
             out[f] = al[f]

@@ -22,6 +22,7 @@
 #include "serra09_long_kernels.hpp"
 #include "serra09_locate_kernels.hpp"
 #include "serra09_path_kernels.hpp"
+#include "chen_align_kernels.hpp"
 #include "prep_kernels.hpp"
 #include "snf_kernels.hpp"
 #include "simple_kernels.hpp"
@@ -52,7 +53,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_SIMPLEPROF, KS_EFALIGN, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_DLOCATE, KS_DPATH, KS_SIMPLEPROF, KS_EFALIGN, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -212,6 +213,7 @@ struct acx_ctx {
                              {"topk_rows_kernel", 0, 0, 0}, {"ftm2d_tile_kernel", 0, 0, 0}, {"query_rows_kernel", 0, 0, 0},
                              {"query_topk_kernel", 0, 0, 0}, {"query_rank_kernel", 0, 0, 0}, {"query_topk_lists_kernel", 0, 0, 0},
                              {"ftm2d_pairs_kernel", 0, 0, 0}, {"qmax_locate_kernel", 0, 0, 0}, {"qmax_path_kernel", 0, 0, 0},
+                             {"dmax_locate_kernel", 0, 0, 0}, {"dmax_path_kernel", 0, 0, 0},
                              {"simple_profile_kernel", 0, 0, 0}, {"ef_align_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
@@ -715,16 +717,29 @@ void launch_qmax_locate(hipStream_t st, const PairDesc *pd, int B, const unsigne
         hipLaunchKernelGGL((acx::qmax_locate_kernel<false>), dim3(B), dim3(64), 0, st, pd, bits, seam, seam_off, dst, gamma_o, gamma_e, dp_start);
 }
 
+// The same for the Dmax alignment (chen_align_kernels.hpp): same records, same seam buffer.
+void launch_dmax_locate(hipStream_t st, const PairDesc *pd, int B, const unsigned long long *bits, acx::LocSeam *seam, const int64_t *seam_off,
+                        acx_alignment *dst, float gamma_o, float gamma_e, int dp_start)
+{
+    if (gamma_o == gamma_e)
+        hipLaunchKernelGGL((acx::dmax_locate_kernel<true>), dim3(B), dim3(64), 0, st, pd, bits, seam, seam_off, dst, gamma_o, gamma_e, dp_start);
+    else
+        hipLaunchKernelGGL((acx::dmax_locate_kernel<false>), dim3(B), dim3(64), 0, st, pd, bits, seam, seam_off, dst, gamma_o, gamma_e, dp_start);
+}
+
 // The path pass (serra09_path_kernels.hpp) behind a locating sweep, while c->d_bits still holds the bitmaps of the B pairs whose
 // descriptors are `dpd` on the device: recs[k2] is pair k2's record ON THE HOST (the caller has waited for it), and pair k2's cells
 // go to dst(k2) as (q, r) from start to end; a pair without a match gets none.  The boxes run in CHUNKS: as many consecutive boxes as
 // fit path_budget_bytes (direction planes + seam records) and one launch's grid; a single box beyond it is ACX_ERR_NOMEM (`name(k2)`
-// says which pair).  Runs on the main stream and returns with it idle.
+// says which pair).  Runs on the main stream and returns with it idle.  `dmax`: the records are a Dmax locating sweep's and the pass is
+// dmax_path_kernel (same boxes, planes, records and budget).
 int64_t path_budget_bytes(const acx_ctx *c) { return scratch_limit_bytes(c) / 2; }
 
 template <typename Dst, typename Name>
-int run_qmax_paths(acx_ctx *c, const PairDesc *dpd, const acx_alignment *recs, int B, float gamma_o, float gamma_e, Dst dst, Name name)
+int run_qmax_paths(acx_ctx *c, const PairDesc *dpd, const acx_alignment *recs, int B, float gamma_o, float gamma_e, Dst dst, Name name,
+                   bool dmax = false)
 {
+    const std::string who = dmax ? "dmax_path: " : "qmax_path: ";
     const int64_t budget = path_budget_bytes(c);
     std::vector<acx::PathBox> boxes;
     std::vector<int> owner;
@@ -738,10 +753,10 @@ int run_qmax_paths(acx_ctx *c, const PairDesc *dpd, const acx_alignment *recs, i
             dst(k2).clear();
             if (!(a.score > 0.0f) || a.q0 < 0) continue;
             const int rows = a.q1 - a.q0 + 1, width = a.r1 - a.r0 + 1;
-            if (rows < 1 || width < 1 || a.r0 < 0) return fail(c, ACX_ERR_STATE, "qmax_path: pair " + name(k2) + " has a malformed alignment record");
+            if (rows < 1 || width < 1 || a.r0 < 0) return fail(c, ACX_ERR_STATE, who + "pair " + name(k2) + " has a malformed alignment record");
             const int64_t need = acx::path_box_bytes(rows, width);
             if (need > budget)
-                return fail(c, ACX_ERR_NOMEM, "qmax_path: the " + std::to_string(rows) + " x " + std::to_string(width) + " box of pair " + name(k2) +
+                return fail(c, ACX_ERR_NOMEM, who + "the " + std::to_string(rows) + " x " + std::to_string(width) + " box of pair " + name(k2) +
                                                   " takes " + std::to_string(need) + " bytes, beyond the path budget of " + std::to_string(budget) +
                                                   " (half the scratch limit)");
             if (bytes + need > budget) break;
@@ -766,8 +781,14 @@ int run_qmax_paths(acx_ctx *c, const PairDesc *dpd, const acx_alignment *recs, i
         if ((rc = ensure(c, c->d_pn, (size_t)nb)) != ACX_OK) return rc;
         ACX_HIP(c, hipMemcpyAsync(c->d_pbox, boxes.data(), sizeof(acx::PathBox) * nb, hipMemcpyHostToDevice, c->stream));
         {
-            ProfScope ps(c, KS_PATH, area);
-            if (gamma_o == gamma_e)
+            ProfScope ps(c, dmax ? KS_DPATH : KS_PATH, area);
+            if (dmax && gamma_o == gamma_e)
+                hipLaunchKernelGGL((acx::dmax_path_kernel<true>), dim3(nb), dim3(64), 0, c->stream, dpd, c->d_pbox, c->d_bits, c->d_dir, c->d_pseam,
+                                   c->d_pcells, c->d_pn, gamma_o, gamma_e);
+            else if (dmax)
+                hipLaunchKernelGGL((acx::dmax_path_kernel<false>), dim3(nb), dim3(64), 0, c->stream, dpd, c->d_pbox, c->d_bits, c->d_dir, c->d_pseam,
+                                   c->d_pcells, c->d_pn, gamma_o, gamma_e);
+            else if (gamma_o == gamma_e)
                 hipLaunchKernelGGL((acx::qmax_path_kernel<true>), dim3(nb), dim3(64), 0, c->stream, dpd, c->d_pbox, c->d_bits, c->d_dir, c->d_pseam,
                                    c->d_pcells, c->d_pn, gamma_o, gamma_e);
             else
@@ -785,7 +806,7 @@ int run_qmax_paths(acx_ctx *c, const PairDesc *dpd, const acx_alignment *recs, i
             const int n = h_n[(size_t)b];
             const int32_t *src = h_cells.data() + 2 * bx.cell_off;
             if (n < 1 || n > bx.max_cells || src[2 * (n - 1)] != bx.q0 || src[2 * (n - 1) + 1] != bx.r0)
-                return fail(c, ACX_ERR_STATE, "qmax_path: the traceback of pair " + name(owner[(size_t)b]) + " does not end at the reported start");
+                return fail(c, ACX_ERR_STATE, who + "the traceback of pair " + name(owner[(size_t)b]) + " does not end at the reported start");
             std::vector<int32_t> &out = dst(owner[(size_t)b]);
             out.resize((size_t)(2 * n));
             for (int t = 0; t < n; ++t) { out[2 * (size_t)t] = src[2 * (n - 1 - t)]; out[2 * (size_t)t + 1] = src[2 * (n - 1 - t) + 1]; }
@@ -817,22 +838,23 @@ void launch_streaming_class(acx_ctx *c, const PairDesc *dpd, const PairDesc *pd,
 }
 
 int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
-                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al, std::vector<std::vector<int32_t>> *paths);
+                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al, std::vector<std::vector<int32_t>> *paths, bool al_dmax);
 
 // Runs the chain over `K` pairs in scratch-sized batches.  `al` (acx_serra09_align): the sweep is qmax_locate_kernel and pair k's
 // record goes to al[k]; no scores are written.  `paths` (acx_serra09_align_paths, with `al`; K vectors): the path pass runs behind the
-// locating sweep of every batch, and pair k's cells go to (*paths)[k].
+// locating sweep of every batch, and pair k's cells go to (*paths)[k].  `al_dmax` (acx_chenfusion_align*, plane 1; with `al`): the
+// locating sweep and the path pass are the Dmax ones.
 int run_serra09(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
                 const DebugOut *dbg, bool both = false, const DevDst *dd = nullptr, acx_alignment *al = nullptr,
-                std::vector<std::vector<int32_t>> *paths = nullptr)
+                std::vector<std::vector<int32_t>> *paths = nullptr, bool al_dmax = false)
 {
-    const int rc = run_serra09_impl(c, pairs, K, p_in, out, dbg, both, dd, al, paths);
+    const int rc = run_serra09_impl(c, pairs, K, p_in, out, dbg, both, dd, al, paths, al_dmax);
     if (rc != ACX_OK) quiesce(c);                // (c->err keeps the first failure's text)
     return rc;
 }
 
 int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
-                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al, std::vector<std::vector<int32_t>> *paths)
+                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al, std::vector<std::vector<int32_t>> *paths, bool al_dmax)
 {
     if (!c->d_frames0) return fail(c, ACX_ERR_STATE, "serra09: feature pool not uploaded (acx_upload_pool)");
     if (c->dim != acx::NBIN) return fail(c, ACX_ERR_INVALID, "serra09: pool dim must be 12");
@@ -853,7 +875,8 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         for (int64_t k = 0; k < K; ++k) {
             (void)acx::serra09_size_pair(len, pairs[2 * k], pairs[2 * k + 1], p, false, d, need);
             if ((int64_t)d.Mq * d.Mr + acx::LOC_STRIP >= ((int64_t)1 << 32))      // (+ a strip: the wave indexes the columns right of the matrix too)
-                return fail(c, ACX_ERR_UNSUPPORTED, "serra09_align: pair " + std::to_string(k) + " has 2^32 cells or more");
+                return fail(c, ACX_ERR_UNSUPPORTED, std::string(al_dmax ? "chenfusion_align" : "serra09_align") + ": pair " + std::to_string(k) +
+                                                        " has 2^32 cells or more");
         }
     }
     for (int s = 0; s < 2; ++s) {
@@ -976,8 +999,9 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
                 }
             };
             if (al) {                 // WHERE the alignment lies: one launch for the batch, every class the same kernel
-                ProfScope ps(c, KS_LOCATE, acx::serra09_extent(pd, 0, B).cells, qs);
-                launch_qmax_locate(qs, S.d_pd, B, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, p.gamma_o, p.gamma_e, p.dp_start);
+                ProfScope ps(c, al_dmax ? KS_DLOCATE : KS_LOCATE, acx::serra09_extent(pd, 0, B).cells, qs);
+                if (al_dmax) launch_dmax_locate(qs, S.d_pd, B, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, p.gamma_o, p.gamma_e, p.dp_start);
+                else launch_qmax_locate(qs, S.d_pd, B, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, p.gamma_o, p.gamma_e, p.dp_start);
             } else if (both && use_q) {      // the two alignments of a pair read the same bitmap and write different halves of d_out: side by side
                 sweep(false, S.d_out, qs);
                 sweep(true, S.d_out + 1, c->qstream2);
@@ -1003,7 +1027,7 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
             ACX_HIP(c, hipEventSynchronize(S.done));
             if ((rc = run_qmax_paths(c, S.d_pd, S.h_al, B, p.gamma_o, p.gamma_e,
                                      [&](int k2) -> std::vector<int32_t> & { return (*paths)[(size_t)(k0 + perm[k2])]; },
-                                     [&](int k2) { return std::to_string(k0 + perm[k2]); })) != ACX_OK) return rc;
+                                     [&](int k2) { return std::to_string(k0 + perm[k2]); }, al_dmax)) != ACX_OK) return rc;
         }
 
         if (dbg && B >= 1) {
@@ -2203,14 +2227,13 @@ int acx_serra09_align(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ser
     return run_serra09(c, pairs, K, *params, nullptr, nullptr, false, nullptr, out);
 }
 
-int acx_qmax_locate_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out)
+// The locating sweep alone on a given plot (acx_qmax_locate_binary; `dmax`: acx_dmax_locate_binary); `who` names the entry point in errors.
+static int locate_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out, bool dmax,
+                         const std::string &who)
 {
-    if (!c) return ACX_ERR_INVALID;
-    if (!R || !params || !out || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "qmax_locate_binary: bad argument");
-    if (params->dmax != 0) return fail(c, ACX_ERR_UNSUPPORTED, "qmax_locate_binary: the Qmax alignment only (params->dmax must be 0)");
-    if (params->dp_start != 2 && params->dp_start != 3) return fail(c, ACX_ERR_INVALID, "qmax_locate_binary: dp_start must be 2 or 3");
-    if (!(params->gamma_o >= 0.0f) || !(params->gamma_e >= 0.0f)) return fail(c, ACX_ERR_INVALID, "qmax_locate_binary: gammas must be >= 0");
-    if ((int64_t)M * N + acx::LOC_STRIP >= ((int64_t)1 << 32)) return fail(c, ACX_ERR_UNSUPPORTED, "qmax_locate_binary: the plot has 2^32 cells or more");
+    if (params->dp_start != 2 && params->dp_start != 3) return fail(c, ACX_ERR_INVALID, who + ": dp_start must be 2 or 3");
+    if (!(params->gamma_o >= 0.0f) || !(params->gamma_e >= 0.0f)) return fail(c, ACX_ERR_INVALID, who + ": gammas must be >= 0");
+    if ((int64_t)M * N + acx::LOC_STRIP >= ((int64_t)1 << 32)) return fail(c, ACX_ERR_UNSUPPORTED, who + ": the plot has 2^32 cells or more");
     ACX_HIP(c, hipSetDevice(c->device));
     // the recurrence plot in the pipeline's bitmap layout (acx_qmax_binary): word t of row i = columns [64 t - 7 + (i & 7), +64)
     PairDesc d;
@@ -2223,7 +2246,7 @@ int acx_qmax_locate_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, c
         const int c0 = (i & (acx::BAND - 1)) - (acx::BAND - 1);
         for (int j = 0; j < N; ++j) {
             const uint8_t v = R[(size_t)i * N + j];
-            if (v > 1) return fail(c, ACX_ERR_INVALID, "qmax_locate_binary: non-binary elements found in input");
+            if (v > 1) return fail(c, ACX_ERR_INVALID, who + ": non-binary elements found in input");
             if (v) { const int pos = j - c0; words[(size_t)i * d.nw + (pos >> 6)] |= 1ull << (pos & 63); }
         }
     }
@@ -2238,20 +2261,35 @@ int acx_qmax_locate_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, c
     ACX_HIP(c, hipMemcpyAsync(c->d_bits, words.data(), sizeof(unsigned long long) * words.size(), hipMemcpyHostToDevice, c->stream));
     ACX_HIP(c, hipMemcpyAsync(S.d_pd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
     ACX_HIP(c, hipMemcpyAsync(S.d_seam_off, &seam_off, sizeof(seam_off), hipMemcpyHostToDevice, c->stream));
-    launch_qmax_locate(c->stream, S.d_pd, 1, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, params->gamma_o, params->gamma_e, params->dp_start);
+    if (dmax) launch_dmax_locate(c->stream, S.d_pd, 1, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, params->gamma_o, params->gamma_e, params->dp_start);
+    else launch_qmax_locate(c->stream, S.d_pd, 1, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, params->gamma_o, params->gamma_e, params->dp_start);
     ACX_HIP(c, hipGetLastError());
     ACX_HIP(c, hipMemcpyAsync(out, S.d_al, sizeof(acx_alignment), hipMemcpyDeviceToHost, c->stream));
     ACX_HIP(c, hipStreamSynchronize(c->stream));
     return ACX_OK;
 }
 
-int acx_serra09_align_paths(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, acx_alignment *out,
-                            int64_t *path_off, int32_t *cells, int64_t cap)
+int acx_qmax_locate_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out)
 {
     if (!c) return ACX_ERR_INVALID;
-    if (params && params->dmax != 0) return fail(c, ACX_ERR_UNSUPPORTED, "serra09_align_paths: the Qmax alignment only (params->dmax must be 0)");
+    if (!R || !params || !out || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "qmax_locate_binary: bad argument");
+    if (params->dmax != 0) return fail(c, ACX_ERR_UNSUPPORTED, "qmax_locate_binary: the Qmax alignment only (params->dmax must be 0)");
+    return locate_binary(c, R, M, N, params, out, false, "qmax_locate_binary");
+}
+
+int acx_dmax_locate_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!R || !params || !out || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "dmax_locate_binary: bad argument");
+    return locate_binary(c, R, M, N, params, out, true, "dmax_locate_binary");
+}
+
+// acx_serra09_align_paths, and (`al_dmax`) plane 1 of acx_chenfusion_align_paths; `who` names the entry point in errors.
+static int align_paths(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, acx_alignment *out,
+                       int64_t *path_off, int32_t *cells, int64_t cap, bool al_dmax, const std::string &who)
+{
     if (K < 0 || (K > 0 && (!pairs || !out)) || !params || !path_off || cap < 0 || (cap > 0 && !cells))
-        return fail(c, ACX_ERR_INVALID, "serra09_align_paths: bad argument");
+        return fail(c, ACX_ERR_INVALID, who + ": bad argument");
     path_off[0] = 0;
     if (K == 0) return ACX_OK;
     // the run's own checks of the list, in its order, so that the bound on the cells is known before the first launch
@@ -2269,10 +2307,10 @@ int acx_serra09_align_paths(acx_ctx *c, const int32_t *pairs, int64_t K, const a
         bound += std::min(d.Mq, d.Mr);
     }
     if (cap < bound)
-        return fail(c, ACX_ERR_INVALID, "serra09_align_paths: cap " + std::to_string(cap) + " is too small: " + std::to_string(bound) +
+        return fail(c, ACX_ERR_INVALID, who + ": cap " + std::to_string(cap) + " is too small: " + std::to_string(bound) +
                                             " cells required (the sum of min(Mq, Mr) over the list)");
     std::vector<std::vector<int32_t>> paths((size_t)K);
-    if ((rc = run_serra09(c, pairs, K, *params, nullptr, nullptr, false, nullptr, out, &paths)) != ACX_OK) return rc;
+    if ((rc = run_serra09(c, pairs, K, *params, nullptr, nullptr, false, nullptr, out, &paths, al_dmax)) != ACX_OK) return rc;
     int64_t n = 0;
     for (int64_t k = 0; k < K; ++k) {
         const std::vector<int32_t> &pk = paths[(size_t)k];
@@ -2283,26 +2321,74 @@ int acx_serra09_align_paths(acx_ctx *c, const int32_t *pairs, int64_t K, const a
     return ACX_OK;
 }
 
+int acx_serra09_align_paths(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, acx_alignment *out,
+                            int64_t *path_off, int32_t *cells, int64_t cap)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (params && params->dmax != 0) return fail(c, ACX_ERR_UNSUPPORTED, "serra09_align_paths: the Qmax alignment only (params->dmax must be 0)");
+    return align_paths(c, pairs, K, params, out, path_off, cells, cap, false, "serra09_align_paths");
+}
+
+// LateFusionChen: the alignment of one of the two planes acx_chenfusion_pairs scores.  params->dmax is ignored,
+// as there; plane 0 is acx_serra09_align* itself.
+int acx_chenfusion_align(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, int32_t plane, acx_alignment *out)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (plane != 0 && plane != 1) return fail(c, ACX_ERR_INVALID, "chenfusion_align: plane must be 0 (qmax) or 1 (dmax)");
+    if (K < 0 || (K > 0 && (!pairs || !out)) || !params) return fail(c, ACX_ERR_INVALID, "chenfusion_align: bad argument");
+    acx_serra09_params p = *params;
+    p.dmax = 0;
+    if (plane == 0) return acx_serra09_align(c, pairs, K, &p, out);
+    if (K == 0) return ACX_OK;
+    return run_serra09(c, pairs, K, p, nullptr, nullptr, false, nullptr, out, nullptr, true);
+}
+
+int acx_chenfusion_align_paths(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, int32_t plane, acx_alignment *out,
+                               int64_t *path_off, int32_t *cells, int64_t cap)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (plane != 0 && plane != 1) return fail(c, ACX_ERR_INVALID, "chenfusion_align_paths: plane must be 0 (qmax) or 1 (dmax)");
+    if (!params) return fail(c, ACX_ERR_INVALID, "chenfusion_align_paths: bad argument");
+    acx_serra09_params p = *params;
+    p.dmax = 0;
+    if (plane == 0) return acx_serra09_align_paths(c, pairs, K, &p, out, path_off, cells, cap);
+    return align_paths(c, pairs, K, &p, out, path_off, cells, cap, true, "chenfusion_align_paths");
+}
+
+// acx_qmax_path_binary, and (`dmax`) acx_dmax_path_binary; `who` names the entry point in errors.
+static int path_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out,
+                       int64_t *n_cells, int32_t *cells, int64_t cap, bool dmax, const std::string &who)
+{
+    if (!R || !params || !out || !n_cells || M < 1 || N < 1 || cap < 0 || (cap > 0 && !cells)) return fail(c, ACX_ERR_INVALID, who + ": bad argument");
+    if (cap < std::min(M, N))
+        return fail(c, ACX_ERR_INVALID, who + ": cap " + std::to_string(cap) + " is too small: " + std::to_string(std::min(M, N)) +
+                                            " cells required (min(M, N))");
+    *n_cells = 0;
+    // the locating sweep on the plot: it leaves the plot's bitmap in d_bits and its descriptor in slot 0, and the record is the box
+    int rc = dmax ? acx_dmax_locate_binary(c, R, M, N, params, out) : acx_qmax_locate_binary(c, R, M, N, params, out);
+    if (rc != ACX_OK) return rc;
+    std::vector<int32_t> path;
+    rc = run_qmax_paths(c, c->slot[0].d_pd, out, 1, params->gamma_o, params->gamma_e,
+                        [&](int) -> std::vector<int32_t> & { return path; }, [](int) { return std::string("0"); }, dmax);
+    if (rc != ACX_OK) { quiesce(c); return rc; }
+    if (!path.empty()) memcpy(cells, path.data(), sizeof(int32_t) * path.size());
+    *n_cells = (int64_t)path.size() / 2;
+    return ACX_OK;
+}
+
 int acx_qmax_path_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out,
                          int64_t *n_cells, int32_t *cells, int64_t cap)
 {
     if (!c) return ACX_ERR_INVALID;
     if (params && params->dmax != 0) return fail(c, ACX_ERR_UNSUPPORTED, "qmax_path_binary: the Qmax alignment only (params->dmax must be 0)");
-    if (!R || !params || !out || !n_cells || M < 1 || N < 1 || cap < 0 || (cap > 0 && !cells)) return fail(c, ACX_ERR_INVALID, "qmax_path_binary: bad argument");
-    if (cap < std::min(M, N))
-        return fail(c, ACX_ERR_INVALID, "qmax_path_binary: cap " + std::to_string(cap) + " is too small: " + std::to_string(std::min(M, N)) +
-                                            " cells required (min(M, N))");
-    *n_cells = 0;
-    // the locating sweep on the plot: it leaves the plot's bitmap in d_bits and its descriptor in slot 0, and the record is the box
-    int rc = acx_qmax_locate_binary(c, R, M, N, params, out);
-    if (rc != ACX_OK) return rc;
-    std::vector<int32_t> path;
-    rc = run_qmax_paths(c, c->slot[0].d_pd, out, 1, params->gamma_o, params->gamma_e,
-                        [&](int) -> std::vector<int32_t> & { return path; }, [](int) { return std::string("0"); });
-    if (rc != ACX_OK) { quiesce(c); return rc; }
-    if (!path.empty()) memcpy(cells, path.data(), sizeof(int32_t) * path.size());
-    *n_cells = (int64_t)path.size() / 2;
-    return ACX_OK;
+    return path_binary(c, R, M, N, params, out, n_cells, cells, cap, false, "qmax_path_binary");
+}
+
+int acx_dmax_path_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out,
+                         int64_t *n_cells, int32_t *cells, int64_t cap)
+{
+    if (!c) return ACX_ERR_INVALID;
+    return path_binary(c, R, M, N, params, out, n_cells, cells, cap, true, "dmax_path_binary");
 }
 
 int acx_upload_pool_f64(acx_ctx *c, const double *frames, const int64_t *offsets, int32_t n_tracks, int32_t dim)

@@ -276,6 +276,33 @@ int acx_serra09_align_paths(acx_ctx *ctx, const int32_t *pairs, int64_t K, const
 int acx_qmax_path_binary(acx_ctx *ctx, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params,
                          acx_alignment *out, int64_t *n_cells, int32_t *cells, int64_t cap);
 
+/*
+ * LateFusionChen: where the alignment of ONE of the two planes of acx_chenfusion_pairs lies, and its path.
+ * plane 0: Qmax -- byte for byte acx_serra09_align / acx_serra09_align_paths; plane 1: Dmax (dmax_locate_kernel, dmax_path_kernel);
+ * any other value -> ACX_ERR_INVALID before any launch.  params->dmax is ignored, as in acx_chenfusion_pairs.
+ * Dmax: Q is the oracle's matrix with dmax = 1 -- c3 = Q[i-2][j-1] + R[i-1][j], c4 = Q[i-1][j-2] + R[i][j-1] -- and
+ *   score      max Q: the bits acx_chenfusion_pairs returns in column 1
+ *   (q1, r1)   the row-major first cell that attains it
+ *   (q0, r0)   follow predecessors from the end: the cell of the first candidate (bonus included; penalised in a gap cell) equal to the
+ *              maximum of the three; a cell has none, and the path starts there, when Q of THAT cell (without its bonus) is 0.
+ * The start cell's Q need not be 1, and the start can be a GAP cell whose bonus neighbour (q0 - 1, r0) or (q0, r0 - 1) is the recurrence
+ * at which the alignment really begins: the span can begin one frame late.  Paths, steps, `cap`, chunks, budget and error codes are those
+ * of acx_serra09_align_paths.
+ */
+int acx_chenfusion_align(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_serra09_params *params, int32_t plane,
+                         acx_alignment *out);
+int acx_chenfusion_align_paths(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_serra09_params *params, int32_t plane,
+                               acx_alignment *out, int64_t *path_off /* K + 1 */, int32_t *cells /* cap x 2: (q, r) */, int64_t cap);
+
+/*
+ * The Dmax DP alone on a given binary (M, N) uint8 plot, as acx_qmax_locate_binary / acx_qmax_path_binary are for Qmax: uses
+ * params->gamma_o, gamma_e, dp_start (params->dmax is ignored); any M, N.  Non-{0,1} input -> ACX_ERR_INVALID.
+ */
+int acx_dmax_locate_binary(acx_ctx *ctx, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params,
+                           acx_alignment *out);
+int acx_dmax_path_binary(acx_ctx *ctx, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params,
+                         acx_alignment *out, int64_t *n_cells, int32_t *cells, int64_t cap);
+
 /* Number of embedded frames for a pooled length T (0 if too short). */
 int32_t acx_serra09_embed_len(int32_t T, const acx_serra09_params *params);
 
