@@ -46,6 +46,7 @@ EXPORTS = [
     "acx_ef_debug_bits", "acx_csm_debug_bits", "acx_sw_bits_binary",
     "acx_ef_align", "acx_sw_align_binary",
     "acx_simple_profile",
+    "acx_snf_debug_stages", "acx_snf_debug_update",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -271,6 +272,9 @@ def load():
     L.acx_snf_fuse_dists.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                                      ctypes.POINTER(ctypes.c_void_p)]
+    L.acx_snf_debug_stages.argtypes = [vp, dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, dp, dp, dp, ip, dp, dp]
+    L.acx_snf_debug_update.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_double, ip, dp, ctypes.c_double, ctypes.c_int32, ip, ctypes.c_int32, dp, dp, dp]
     L.acx_csm_binary_sw.argtypes = [vp, fp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, fp]
     L.acx_qmax_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, pp, fp]
     L.acx_serra09_align.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.c_void_p]
@@ -937,6 +941,40 @@ class Context(object):
         self._check(self._L.acx_snf_fuse(self._h, arr(Ws), arr(Js), arr(Vs), m, n, K, int(niters), float(reg_diag),
                                          out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
         return out
+
+    def snf_debug_stages(self, M, K, mu=0.5, from_stage=0):
+        """What the kernels of snf_fuse_dists leave behind for one (n, n) matrix (acx_snf_debug_stages): a dict with S (n, n), md (n,),
+        W (n, n), J (n, K) int32, V (n, K), P (n, n).  from_stage = 1: M is already the affinity matrix; S and md are None and
+        W is M as the device holds it."""
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        n = M.shape[0]
+        if M.shape != (n, n):
+            raise ValueError("snf_debug_stages: the matrix must be square")
+        K = int(K)
+        first = int(from_stage) == 0
+        out = {"S": np.empty((n, n)) if first else None, "md": np.empty(n) if first else None, "W": np.empty((n, n)),
+               "J": np.empty((n, max(K, 0)), np.int32), "V": np.empty((n, max(K, 0))), "P": np.empty((n, n))}
+        self._check(self._L.acx_snf_debug_stages(self._h, _dptr(M), n, K, float(mu), int(from_stage),
+                                                 _dptr(out["S"]) if first else None, _dptr(out["md"]) if first else None,
+                                                 _dptr(out["W"]), _iptr(out["J"]), _dptr(out["V"]), _dptr(out["P"])))
+        return out
+
+    def snf_debug_update(self, srcs, scale, J, V, reg_diag=1.0, variant=0, rows=None):
+        """One update of the cross-diffusion as snf_fuse launches it (acx_snf_debug_update): acc = sum(srcs) * scale, UT = acc S^T,
+        P = S UT + reg_diag I with S = (J, V) (n, K).  variant: 0 the product's choice of gather kernel, 1 the row in LDS,
+        2 gathers from global memory.  Returns the rows `rows` (default: all) of (acc, UT, P), each (len(rows), n)."""
+        srcs = [np.ascontiguousarray(A, dtype=np.float64) for A in srcs]
+        J = np.ascontiguousarray(J, dtype=np.int32)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        n, K = J.shape
+        if V.shape != (n, K) or any(A.shape != (n, n) for A in srcs):
+            raise ValueError("snf_debug_update: srcs must be (n, n) and V (n, K) like J")
+        rows = np.arange(n, dtype=np.int32) if rows is None else np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        acc, ut, p = (np.empty((len(rows), n)) for _ in range(3))
+        ptrs = (ctypes.c_void_p * max(len(srcs), 1))(*[A.ctypes.data for A in srcs])
+        self._check(self._L.acx_snf_debug_update(self._h, ptrs, len(srcs), n, K, float(scale), _iptr(J), _dptr(V), float(reg_diag),
+                                                 int(variant), _iptr(rows), len(rows), _dptr(acc), _dptr(ut), _dptr(p)))
+        return acc, ut, p
 
     # ------------------------------------------------------------------ device buffers without torch
     def dev_alloc(self, nbytes):

@@ -3826,16 +3826,72 @@ static int snf_alloc(acx_ctx *c, SnfRun &R, int m, int n, int K)
     return ACX_OK;
 }
 
+// snf_ast_kernel<true> keeps one row of n doubles in LDS; beyond that the gathers go to global memory
+static bool snf_row_fits_lds(int n) { return (size_t)n * sizeof(double) <= 160 * 1024 - 1024; }
+static hipError_t snf_lds_optin(int n)
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(acx::snf_ast_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)((size_t)n * sizeof(double)));
+}
+
+// One update of the cross-diffusion:  acc = (sum of sp) * scale,  ut = acc S^T,  nxt = S ut (+ reg_diag on the diagonal),
+// S = (dJ, dV).  The loop below and acx_snf_debug_update both launch it here, so that the tests see the product's launches.
+static void snf_update(acx_ctx *c, const acx::SnfSrc &sp, double scale, double *acc, const int32_t *dJ, const double *dV, double *ut,
+                       double *nxt, int n, int K, double reg_diag, bool ldsrow)
+{
+    const size_t nn = (size_t)n * n;
+    hipLaunchKernelGGL(acx::snf_mean_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, c->stream, sp, scale, acc, (int64_t)nn);
+    if (ldsrow)
+        hipLaunchKernelGGL((acx::snf_ast_kernel<true>), dim3(n), dim3(256), (size_t)n * sizeof(double), c->stream, acc, dJ, dV, ut, n, K);
+    else
+        hipLaunchKernelGGL((acx::snf_ast_kernel<false>), dim3(n), dim3(256), 0, c->stream, acc, dJ, dV, ut, n, K);
+    hipLaunchKernelGGL(acx::snf_sut_kernel, dim3(n), dim3(256), 0, c->stream, ut, dJ, dV, nxt, n, K, reg_diag);
+}
+
+// Where the stages of one matrix go on the host, as each kernel leaves them (any may be null): the product asks for W only
+struct SnfTaps {
+    double *S = nullptr, *md = nullptr, *W = nullptr;
+    int32_t *J = nullptr;
+    double *V = nullptr, *P = nullptr;
+};
+
+// One matrix of acx_snf_fuse_dists, from the host matrix `M` to P = row-normalised W in `cur` and the kNN kernel in (dJ, dV):
+// getW (similarity_fusion.py:15-36: symmetrise, local scale from the K + 1 nearest, Gaussian kernel), getS (:124-144) as
+// neighbour lists, getP (:101-122).  from_stage = 1 (tests): M is already the affinity matrix, getW is skipped.  `acc` is the
+// staging buffer, `ut` holds S and then W.  The product entry point and acx_snf_debug_stages both launch the kernels here.
+static hipError_t snf_prepare(acx_ctx *c, const double *M, double *acc, double *ut, double *md, int32_t *dJ, double *dV, double *cur,
+                              int n, int K, double mu, int from_stage, const SnfTaps &tap)
+{
+    const size_t nn = (size_t)n * n;
+    const dim3 tg((n + 31) / 32, (n + 31) / 32);
+    const unsigned rows4 = (unsigned)((n + 3) / 4);
+    hipError_t e = hipMemcpyAsync(from_stage == 0 ? acc : ut, M, nn * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return e;
+    if (from_stage == 0) {
+        hipLaunchKernelGGL(acx::snf_sym_kernel, tg, dim3(256), 0, c->stream, acc, ut, n);
+        if (tap.S) e = hipMemcpyAsync(tap.S, ut, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        hipLaunchKernelGGL(acx::snf_localscale_kernel, dim3(rows4), dim3(256), 0, c->stream, ut, md, n, K);
+        if (tap.md && e == hipSuccess) e = hipMemcpyAsync(tap.md, md, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        hipLaunchKernelGGL(acx::snf_affinity_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, c->stream, ut, md, n, mu);
+    }
+    if (tap.W && e == hipSuccess) e = hipMemcpyAsync(tap.W, ut, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    hipLaunchKernelGGL(acx::snf_knn_kernel, dim3(rows4), dim3(256), 0, c->stream, ut, dJ, dV, n, K);
+    hipLaunchKernelGGL(acx::snf_rownorm_kernel, dim3(n), dim3(256), 0, c->stream, ut, cur, n);
+    if (tap.J && e == hipSuccess) e = hipMemcpyAsync(tap.J, dJ, (size_t)n * K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+    if (tap.V && e == hipSuccess) e = hipMemcpyAsync(tap.V, dV, (size_t)n * K * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (tap.P && e == hipSuccess) e = hipMemcpyAsync(tap.P, cur, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    return e;
+}
+
 // The cross-diffusion loop of doSimilarityFusionWs (similarity_fusion.py:146-186) on matrices that are
 // already on the device: cur[i] = row-normalised W_i, (dJ[i], dV[i]) = its kNN kernel.
 static int snf_loop(acx_ctx *c, SnfRun &R, int niters, double reg_diag, double *out)
 {
     const int m = R.m, n = R.n, K = R.K;
     const size_t nn = (size_t)n * n;
-    const bool ldsrow = (size_t)n * sizeof(double) <= 160 * 1024 - 1024;
-    if (ldsrow)
-        ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::snf_ast_kernel<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)n * sizeof(double))));
+    const bool ldsrow = snf_row_fits_lds(n);
+    if (ldsrow) ACX_HIP(c, snf_lds_optin(n));
     for (int it = 0; it < niters; ++it) {
         // from the second sweep on the reference's two work lists alias: a matrix updated earlier in the
         // sweep is already seen by the later ones (similarity_fusion.py:179)
@@ -3845,14 +3901,7 @@ static int snf_loop(acx_ctx *c, SnfRun &R, int niters, double reg_diag, double *
             sp.count = 0;
             for (int k = 0; k < m; ++k)
                 if (k != i) sp.p[sp.count++] = src[k];
-            hipLaunchKernelGGL(acx::snf_mean_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, c->stream,
-                               sp, 1.0 / (double)(m - 1), R.acc, (int64_t)nn);
-            if (ldsrow)
-                hipLaunchKernelGGL((acx::snf_ast_kernel<true>), dim3(n), dim3(256), (size_t)n * sizeof(double), c->stream,
-                                   R.acc, R.dJ[i], R.dV[i], R.ut, n, K);
-            else
-                hipLaunchKernelGGL((acx::snf_ast_kernel<false>), dim3(n), dim3(256), 0, c->stream, R.acc, R.dJ[i], R.dV[i], R.ut, n, K);
-            hipLaunchKernelGGL(acx::snf_sut_kernel, dim3(n), dim3(256), 0, c->stream, R.ut, R.dJ[i], R.dV[i], R.nxt[i], n, K, reg_diag);
+            snf_update(c, sp, 1.0 / (double)(m - 1), R.acc, R.dJ[i], R.dV[i], R.ut, R.nxt[i], n, K, reg_diag, ldsrow);
         }
     }
     {
@@ -3909,25 +3958,89 @@ int acx_snf_fuse_dists(acx_ctx *c, const double *const *Ds, int32_t m, int32_t n
     SnfRun R;
     int rc = snf_alloc(c, R, m, n, K);
     if (rc != ACX_OK) return rc;
-    const size_t nn = (size_t)n * n;
     hipError_t e = hipSuccess;
-    const dim3 tg((n + 31) / 32, (n + 31) / 32);
-    const unsigned rows4 = (unsigned)((n + 3) / 4);
     for (int i = 0; i < m && e == hipSuccess; ++i) {
-        e = hipMemcpyAsync(R.acc, Ds[i], nn * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) break;
-        // getW (similarity_fusion.py:15-36): symmetrise, local scale from the K + 1 nearest, Gaussian kernel
-        hipLaunchKernelGGL(acx::snf_sym_kernel, tg, dim3(256), 0, c->stream, R.acc, R.ut, n);
-        hipLaunchKernelGGL(acx::snf_localscale_kernel, dim3(rows4), dim3(256), 0, c->stream, R.ut, R.md, n, K);
-        hipLaunchKernelGGL(acx::snf_affinity_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, c->stream, R.ut, R.md, n, mu);
-        if (Ws_out && Ws_out[i]) e = hipMemcpyAsync(Ws_out[i], R.ut, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        // getS (:124-144) as neighbour lists, getP (:101-122)
-        hipLaunchKernelGGL(acx::snf_knn_kernel, dim3(rows4), dim3(256), 0, c->stream, R.ut, R.dJ[i], R.dV[i], n, K);
-        hipLaunchKernelGGL(acx::snf_rownorm_kernel, dim3(n), dim3(256), 0, c->stream, R.ut, R.cur[i], n);
-        if (e == hipSuccess) e = hipGetLastError();
+        SnfTaps tap;
+        tap.W = Ws_out ? Ws_out[i] : nullptr;
+        e = snf_prepare(c, Ds[i], R.acc, R.ut, R.md, R.dJ[i], R.dV[i], R.cur[i], n, K, mu, 0, tap);
     }
     ACX_HIP(c, e);
     return snf_loop(c, R, niters, reg_diag, out);
+}
+
+int acx_snf_debug_stages(acx_ctx *c, const double *M, int32_t n, int32_t K, double mu, int32_t from_stage, double *S, double *md,
+                         double *W, int32_t *J, double *V, double *P)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!M || n < 1 || K < 1 || K > n || !(mu > 0.0) || from_stage < 0 || from_stage > 1)
+        return fail(c, ACX_ERR_INVALID, "snf_debug_stages: bad argument (1 <= K <= n, mu > 0, from_stage 0 or 1)");
+    if (K > 64) return fail(c, ACX_ERR_UNSUPPORTED, "snf_debug_stages: more than 64 neighbours are not supported on the device");
+    ACX_HIP(c, hipSetDevice(c->device));
+    SnfRun R;
+    int rc = snf_alloc(c, R, 1, n, K);
+    if (rc != ACX_OK) return rc;
+    SnfTaps tap;
+    if (from_stage == 0) { tap.S = S; tap.md = md; }
+    tap.W = W; tap.J = J; tap.V = V; tap.P = P;
+    // a slot of the lists that no lane writes shows as column -1 (and a NaN weight), not as whatever the block held before
+    ACX_HIP(c, hipMemsetAsync(R.dJ[0], 0xff, (size_t)n * K * sizeof(int32_t), c->stream));
+    ACX_HIP(c, hipMemsetAsync(R.dV[0], 0xff, (size_t)n * K * sizeof(double), c->stream));
+    ACX_HIP(c, snf_prepare(c, M, R.acc, R.ut, R.md, R.dJ[0], R.dV[0], R.cur[0], n, K, mu, from_stage, tap));
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
+}
+
+int acx_snf_debug_update(acx_ctx *c, const double *const *srcs, int32_t m_src, int32_t n, int32_t K, double scale, const int32_t *J,
+                         const double *V, double reg_diag, int32_t variant, const int32_t *rows, int32_t n_rows, double *acc_rows,
+                         double *ut_rows, double *p_rows)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!srcs || !J || !V || m_src < 1 || m_src > 8 || n < 1 || K < 1 || K > n || variant < 0 || variant > 2 || n_rows < 0 ||
+        (n_rows > 0 && !rows))
+        return fail(c, ACX_ERR_INVALID, "snf_debug_update: bad argument (1 <= m_src <= 8, 1 <= K <= n, variant 0..2)");
+    // (before anything of size n is read: the refusal needs no matrix)
+    if (variant == 1 && !snf_row_fits_lds(n))
+        return fail(c, ACX_ERR_UNSUPPORTED, "snf_debug_update: a row of n doubles does not fit the LDS");
+    if (n > 65535) return fail(c, ACX_ERR_UNSUPPORTED, "snf_debug_update: more than 65535 tracks are not supported on the device");
+    for (int k = 0; k < m_src; ++k)
+        if (!srcs[k]) return fail(c, ACX_ERR_INVALID, "snf_debug_update: null matrix");
+    for (int r = 0; r < n_rows; ++r)
+        if (rows[r] < 0 || rows[r] >= n) return fail(c, ACX_ERR_INVALID, "snf_debug_update: row index out of range");
+    for (int64_t e = 0; e < (int64_t)n * K; ++e)
+        if (J[e] < 0 || J[e] >= n) return fail(c, ACX_ERR_INVALID, "snf_debug_update: neighbour index out of range");
+    ACX_HIP(c, hipSetDevice(c->device));
+    const size_t nn = (size_t)n * n;
+    const size_t need = ((size_t)m_src + 3) * nn * sizeof(double) + (size_t)n * K * (sizeof(double) + sizeof(int32_t));
+    if (need > (size_t)(0.8 * (double)c->total_mem)) return fail(c, ACX_ERR_NOMEM, "snf_debug_update: matrices do not fit the device");
+    std::vector<DeviceBuffer<double>> src(m_src);
+    DeviceBuffer<double> acc, ut, nxt, dV;
+    DeviceBuffer<int32_t> dJ;
+    ACX_HIP(c, acc.grow(nn));
+    ACX_HIP(c, ut.grow(nn));
+    ACX_HIP(c, nxt.grow(nn));
+    ACX_HIP(c, dV.grow((size_t)n * K));
+    ACX_HIP(c, dJ.grow((size_t)n * K));
+    acx::SnfSrc sp;
+    sp.count = m_src;
+    for (int k = 0; k < m_src; ++k) {
+        ACX_HIP(c, src[k].grow(nn));
+        ACX_HIP(c, hipMemcpyAsync(src[k], srcs[k], nn * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        sp.p[k] = src[k];
+    }
+    ACX_HIP(c, hipMemcpyAsync(dV, V, (size_t)n * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(dJ, J, (size_t)n * K * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    const bool ldsrow = variant == 0 ? snf_row_fits_lds(n) : variant == 1;
+    if (ldsrow) ACX_HIP(c, snf_lds_optin(n));
+    snf_update(c, sp, scale, acc, dJ, dV, ut, nxt, n, K, reg_diag, ldsrow);
+    ACX_HIP(c, hipGetLastError());
+    for (int r = 0; r < n_rows; ++r) {
+        const size_t at = (size_t)rows[r] * n, to = (size_t)r * n;
+        if (acc_rows) ACX_HIP(c, hipMemcpyAsync(acc_rows + to, acc.get() + at, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (ut_rows) ACX_HIP(c, hipMemcpyAsync(ut_rows + to, ut.get() + at, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (p_rows) ACX_HIP(c, hipMemcpyAsync(p_rows + to, nxt.get() + at, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -211,15 +211,25 @@ __global__ __launch_bounds__(256) void snf_knn_kernel(const double *__restrict__
     __builtin_amdgcn_wave_barrier();
     const double v = lane < K ? cv[wv][lane] : 0.0;
     const int jj = lane < K ? cj[wv][lane] : 0;
+    // Ranked by KEY, the total order the selection above used.  Compared as doubles (before), a NaN -- W is NaN where a
+    // distance is +inf, which ChenFusion.normalize_by_length writes for a score of 0 -- was neither above nor below anything:
+    // it took rank 0 beside the row's largest value and slot K - 1 of J and V stayed unwritten, an uninitialised column
+    // index for the gathers of snf_ast_kernel.  With keys the K ranks are a permutation whatever the values are; for rows
+    // without NaN and without -0.0 (W is an exp) the order is the same.
+    const unsigned long long kv = snf_key(v);
     int rank = 0;
     for (int t = 0; t < K; ++t) {
-        const double o = cv[wv][t];
+        const unsigned long long ko = snf_key(cv[wv][t]);
         const int oj = cj[wv][t];
-        rank += (o > v || (o == v && oj < jj)) ? 1 : 0;
+        rank += (ko > kv || (ko == kv && oj < jj)) ? 1 : 0;
     }
     __builtin_amdgcn_wave_barrier();
     double sum = 0.0;
-    for (int t = 0; t < K; ++t) sum += cv[wv][t];     // (any order of the K terms: the same values)
+    // Every lane adds the K weights in SLOT order (ascending column), so all lanes divide by the same sum.  The reference adds
+    // them in RANK order (numpy's pairwise sum of the sorted weights): the same terms, another rounding.  Both lie within
+    // (K - 1) 2^-53 of the exact sum of these non-negative terms, which is what tests/test_gpu_snf_stages.py holds V to
+    // ((K + 1) 2^-53 with the division; DESIGN.md section 23 has the measured share of it).
+    for (int t = 0; t < K; ++t) sum += cv[wv][t];
     if (sum == 0.0) sum = 1.0;
     if (lane < K) {
         J[(size_t)i * K + rank] = jj;

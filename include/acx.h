@@ -727,6 +727,30 @@ int acx_snf_fuse(acx_ctx *ctx, const double *const *Ws, const int32_t *const *Js
 int acx_snf_fuse_dists(acx_ctx *ctx, const double *const *Ds, int32_t m, int32_t n, int32_t K, int32_t niters,
                        double reg_diag, double mu, double *out, double *const *Ws_out);
 
+/*
+ * What the kernels of acx_snf_fuse_dists leave behind for ONE matrix (tests): the same host function launches them for
+ * the product and for this call.  M (n, n) f64 row-major.  from_stage = 0: M is a distance matrix, all five kernels
+ * run; from_stage = 1: M is already an affinity matrix, only the neighbour lists and the row normalisation run on it
+ * (S and md are not written).  Outputs, any may be NULL: S (n, n) the symmetrised matrix with its zero diagonal,
+ * md (n) the local scale, W (n, n) the affinity matrix, J (n, K) int32 / V (n, K) the kNN kernel, P (n, n) the
+ * row-normalised W.  1 <= K <= min(n, 64).  J and V are filled with -1 / NaN before the launch: a slot that no lane
+ * wrote shows as such.
+ */
+int acx_snf_debug_stages(acx_ctx *ctx, const double *M, int32_t n, int32_t K, double mu, int32_t from_stage,
+                         double *S, double *md, double *W, int32_t *J, double *V, double *P);
+
+/*
+ * ONE update of the cross-diffusion loop as acx_snf_fuse launches it (tests; the same host function):
+ * acc = (srcs[0] + ... + srcs[m_src - 1]) * scale, UT = acc S^T, P = S UT + reg_diag I, with S = (J, V) (n, K) as in
+ * acx_snf_fuse, any 1 <= K <= n, 1 <= m_src <= 8.  variant: 0 = the gather kernel the product chooses for this n,
+ * 1 = the row of acc in LDS (ACX_ERR_UNSUPPORTED when n doubles do not fit; refused before any array is read),
+ * 2 = gathers from global memory.  Only the rows `rows[0 .. n_rows)` are copied back: acc_rows, ut_rows, p_rows
+ * (n_rows, n) f64, any may be NULL.
+ */
+int acx_snf_debug_update(acx_ctx *ctx, const double *const *srcs, int32_t m_src, int32_t n, int32_t K, double scale,
+                         const int32_t *J, const double *V, double reg_diag, int32_t variant, const int32_t *rows,
+                         int32_t n_rows, double *acc_rows, double *ut_rows, double *p_rows);
+
 /* ---- the N x N pair grid -------------------------------------------------- */
 
 /*
