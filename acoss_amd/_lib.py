@@ -47,6 +47,7 @@ EXPORTS = [
     "acx_ef_align", "acx_sw_align_binary",
     "acx_simple_profile",
     "acx_snf_debug_stages", "acx_snf_debug_update",
+    "acx_ef_crossfusion_pairs", "acx_ef_crossfusion_debug", "acx_crossfusion_matrices", "acx_xsel_binary_sw",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -275,6 +276,11 @@ def load():
     L.acx_snf_debug_stages.argtypes = [vp, dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, dp, dp, dp, ip, dp, dp]
     L.acx_snf_debug_update.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                        ctypes.c_double, ip, dp, ctypes.c_double, ctypes.c_int32, ip, ctypes.c_int32, dp, dp, dp]
+    L.acx_ef_crossfusion_pairs.argtypes = [vp, ip, ctypes.c_int64, ep, ctypes.c_int32, ctypes.c_double, fp]
+    L.acx_ef_crossfusion_debug.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ep, ctypes.c_int32, ctypes.c_double, fp, fp, fp, dp, dp, dp, up, fp]
+    L.acx_crossfusion_matrices.argtypes = [vp, fp, fp, fp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_double, dp, dp, dp, dp, dp, up, fp]
+    L.acx_xsel_binary_sw.argtypes = [vp, dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, up, fp]
     L.acx_csm_binary_sw.argtypes = [vp, fp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, fp]
     L.acx_qmax_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, pp, fp]
     L.acx_serra09_align.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.c_void_p]
@@ -861,6 +867,66 @@ class Context(object):
             raise IOError("Non-binary elements found in input")       # alignment_tools.py:23
         self._check(rc)
         return float(sc.value)
+
+    # ------------------------------------------------------------------ the full cross-diffusion fusion
+    def ef_crossfusion(self, pairs, kappa=0.1, K=10, niters=5, reg_diag=1.0):
+        """(n,) float32: the Smith-Waterman score of the full early fusion of every ordered pair of the uploaded EarlyFusion
+        pool (acx_ef_crossfusion_pairs): per feature the (M + N) x (M + N) affinity matrix of getWCSMSSM, the three cross-diffused
+        by similarity network fusion, the cross blocks of the result summed, binarised (the round(kappa N) largest of a row) and aligned."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        out = np.empty(len(pairs), np.float32)
+        p = EfParams(float(kappa), int(K))
+        self._check(self._L.acx_ef_crossfusion_pairs(self._h, pairs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(pairs),
+                                                     ctypes.byref(p), int(niters), float(reg_diag), _fptr(out)))
+        return out
+
+    def ef_crossfusion_debug(self, i, j, kappa=0.1, K=10, niters=5, reg_diag=1.0):
+        """One pair of the pool through the host function of ef_crossfusion, every intermediate copied back (acx_ef_crossfusion_debug):
+        ssm_a (3, M, M), ssm_b (3, N, N), csm (3, M, N) f32; W (3, n, n), D (n, n), X (M, N) f64; bits (M, pitch / 32) uint32; score."""
+        if not (0 <= int(i) < len(self.ef_blocks) and 0 <= int(j) < len(self.ef_blocks)):
+            raise ValueError("ef_crossfusion_debug: track index out of range")
+        M, N = int(self.ef_blocks[i]), int(self.ef_blocks[j])
+        n = M + N
+        out = dict(ssm_a=np.empty((3, M, M), np.float32), ssm_b=np.empty((3, N, N), np.float32), csm=np.empty((3, M, N), np.float32),
+                   W=np.empty((3, n, n)), D=np.empty((n, n)), X=np.empty((M, N)), bits=np.zeros((M, (N + 63) // 64 * 2), np.uint32))
+        sc = ctypes.c_float(0)
+        p = EfParams(float(kappa), int(K))
+        self._check(self._L.acx_ef_crossfusion_debug(
+            self._h, int(i), int(j), ctypes.byref(p), int(niters), float(reg_diag), _fptr(out["ssm_a"]), _fptr(out["ssm_b"]), _fptr(out["csm"]),
+            _dptr(out["W"]), _dptr(out["D"]), _dptr(out["X"]), out["bits"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(sc)))
+        out["score"] = float(sc.value)
+        return out
+
+    def crossfusion_matrices(self, SA, SB, C, kappa=0.1, K=10, niters=5, reg_diag=1.0):
+        """The chain of ef_crossfusion behind the GEMMs on a caller's matrices (acx_crossfusion_matrices): SA (3, M, M), SB (3, N, N),
+        C (3, M, N) f32.  A dict with r (3, M), c (3, N), W (3, n, n), D (n, n), X (M, N) f64, bits (M, pitch / 32) uint32, score."""
+        SA = np.ascontiguousarray(SA, dtype=np.float32)
+        SB = np.ascontiguousarray(SB, dtype=np.float32)
+        C = np.ascontiguousarray(C, dtype=np.float32)
+        if C.ndim != 3 or C.shape[0] != 3 or SA.shape != (3, C.shape[1], C.shape[1]) or SB.shape != (3, C.shape[2], C.shape[2]):
+            raise ValueError("crossfusion_matrices: SA must be (3, M, M), SB (3, N, N) and C (3, M, N)")
+        M, N = C.shape[1:]
+        n = M + N
+        out = dict(r=np.empty((3, M)), c=np.empty((3, N)), W=np.empty((3, n, n)), D=np.empty((n, n)), X=np.empty((M, N)),
+                   bits=np.zeros((M, (N + 63) // 64 * 2), np.uint32))
+        sc = ctypes.c_float(0)
+        self._check(self._L.acx_crossfusion_matrices(
+            self._h, _fptr(SA), _fptr(SB), _fptr(C), M, N, float(kappa), int(K), int(niters), float(reg_diag), _dptr(out["r"]), _dptr(out["c"]),
+            _dptr(out["W"]), _dptr(out["D"]), _dptr(out["X"]), out["bits"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(sc)))
+        out["score"] = float(sc.value)
+        return out
+
+    def xsel_binary_sw(self, X, kappa=0.1):
+        """The selection and the Smith-Waterman of ef_crossfusion alone on an (M, N) f64 matrix (acx_xsel_binary_sw): (bits, score)."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise ValueError("xsel_binary_sw: X must be (M, N)")
+        M, N = X.shape
+        bits = np.zeros((M, (N + 63) // 64 * 2), np.uint32)
+        sc = ctypes.c_float(0)
+        self._check(self._L.acx_xsel_binary_sw(self._h, _dptr(X), M, N, float(kappa), bits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                               ctypes.byref(sc)))
+        return bits, float(sc.value)
 
     def ef_align(self, pairs, kappa=0.1, K=10, plane=3, paths=False, cap=None):
         """WHERE the Smith-Waterman alignment of every (query, reference) pair lies in one binarised matrix (acx_ef_align; plane

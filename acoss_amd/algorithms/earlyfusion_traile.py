@@ -153,6 +153,61 @@ class EarlyFusion(CoverAlgorithm):
         for c, s in enumerate(("mfccs", "ssms", "chromas", "early")):
             self.Ds[s][idxs[:, 0], idxs[:, 1]] = sc[:, c]
 
+    # ------------------------------------------------------------------ the full cross-diffusion fusion for listed pairs
+    def _check_full_fusion(self, who):
+        """The class's own arguments as the library will refuse them, before the first library call."""
+        if int(self.niters) < 1:
+            raise ValueError("%s: niters must be >= 1 (got %d)" % (who, int(self.niters)))
+        if int(self.K) < 1:
+            raise ValueError("%s: K must be >= 1 (got %d)" % (who, int(self.K)))
+        if int(self.K) > 64:
+            raise NotImplementedError("%s: more than 64 neighbours are not supported on the device (K = %d)" % (who, int(self.K)))
+
+    def full_fusion(self, idxs):
+        """The score of the PUBLISHED early fusion (Tralie, ISMIR 2017), the "Step 3" the reference disables
+        (earlyfusion_traile.py:142-148) because it was too slow in numpy: idxs (K, 2) ordered (A, B) track indices -> (K,)
+        float32.  Per feature the self-similarity matrices of A and B and their cross-similarity matrix become one
+        (M + N) x (M + N) affinity matrix (getWCSMSSM, K neighbours split between the blocks); the three are cross-diffused by
+        similarity network fusion (doSimilarityFusionWs, K, niters, reg_diag = 1); the two cross blocks of the result are summed,
+        binarised (the round(kappa N) largest of every row) and aligned by Smith-Waterman.  The stages are the reference's
+        functions, the composition is the method's (include/acx.h acx_ef_crossfusion_pairs).  Tracks of at most 1024 blocks; a
+        pair whose k1 = int(K M / (M + N)) or k2 = K - k1 leaves np.partition no room is refused (NotImplementedError naming
+        the pair).  `Ds` is not written: this score is not one of similarity_types.  Not a collective."""
+        self._check_full_fusion("full_fusion")
+        pairs = _align.check_pairs("full_fusion", _align.check_indices("full_fusion", idxs), self.N)
+        if len(pairs) == 0:
+            return np.zeros(0, np.float32)
+        return self._context().ef_crossfusion(pairs, self.kappa, self.K, self.niters, 1.0)
+
+    def rerank_full(self, queries, shortlists, k=10):
+        """rerank() by the full-fusion score: queries (Q,) track indices, shortlists as rerank() takes them ((Q, L) integers or
+        Q sequences, -1 an empty slot, no track twice in a row) -> (indices (Q, k) int32, scores (Q, k) float32), the k best
+        candidates of every query by score descending, then smaller track index; slots beyond a query's candidates hold -1 and
+        NaN.  The cell of (query, candidate) is the pair (min, max) of the two indices, as identify() scores this symmetric class;
+        a query's own track is skipped.  Only the listed cells are computed.  `Ds` is not written.  Not a collective."""
+        self._check_full_fusion("rerank_full")
+        q, _ = self._query_setup("rerank_full", queries, None)
+        k = int(k)
+        if k < 1:
+            raise ValueError("rerank_full: k must be >= 1 (got %d)" % k)
+        lists = self._check_shortlists("rerank_full", shortlists, len(q))
+        idx = np.full((len(q), k), -1, np.int32)
+        score = np.full((len(q), k), np.nan, np.float32)
+        rows, slots = np.nonzero((lists >= 0) & (lists != q[:, None]))
+        if len(rows) == 0:
+            return idx, score
+        cand = lists[rows, slots]
+        pairs = np.stack([np.minimum(q[rows], cand), np.maximum(q[rows], cand)], axis=1).astype(np.int32)
+        uniq, inv = np.unique(pairs, axis=0, return_inverse=True)
+        sc = self._context().ef_crossfusion(uniq, self.kappa, self.K, self.niters, 1.0)[np.asarray(inv).reshape(-1)]
+        for i in range(len(q)):
+            mine = rows == i
+            c_i, s_i = cand[mine], sc[mine]
+            order = np.lexsort((c_i, -s_i.astype(np.float64)))[:k]
+            idx[i, :len(order)] = c_i[order]
+            score[i, :len(order)] = s_i[order]
+        return idx, score
+
     # ------------------------------------------------------------------ where the alignment lies
     # align() / align_matches(): acx_alignment's fields in BLOCKS and the spans in BEATS, [first, last] inclusive
     ALIGN_DTYPE = np.dtype(_lib.ALIGNMENT_DTYPE.descr + [("q_span", np.int32, (2,)), ("r_span", np.int32, (2,))])

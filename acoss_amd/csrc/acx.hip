@@ -25,6 +25,7 @@
 #include "chen_align_kernels.hpp"
 #include "prep_kernels.hpp"
 #include "snf_kernels.hpp"
+#include "ef_crossfusion_kernels.hpp"
 #include "simple_kernels.hpp"
 #include "simple_profile_kernels.hpp"
 #include "ef_kernels.hpp"
@@ -53,7 +54,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_DLOCATE, KS_DPATH, KS_SIMPLEPROF, KS_EFALIGN, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_DLOCATE, KS_DPATH, KS_SIMPLEPROF, KS_XFMEANS, KS_XFAFFINITY, KS_XFSNF, KS_XFX, KS_XFSELECT, KS_EFALIGN, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -214,7 +215,9 @@ struct acx_ctx {
                              {"query_topk_kernel", 0, 0, 0}, {"query_rank_kernel", 0, 0, 0}, {"query_topk_lists_kernel", 0, 0, 0},
                              {"ftm2d_pairs_kernel", 0, 0, 0}, {"qmax_locate_kernel", 0, 0, 0}, {"qmax_path_kernel", 0, 0, 0},
                              {"dmax_locate_kernel", 0, 0, 0}, {"dmax_path_kernel", 0, 0, 0},
-                             {"simple_profile_kernel", 0, 0, 0}, {"ef_align_kernel", 0, 0, 0}};
+                             {"simple_profile_kernel", 0, 0, 0}, {"xf_means_kernel", 0, 0, 0}, {"xf_affinity_kernels", 0, 0, 0},
+                             {"xf_snf_kernels", 0, 0, 0}, {"xf_x_kernel", 0, 0, 0}, {"xf_select_kernel", 0, 0, 0},
+                             {"ef_align_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
     // How many tracks ensure_f16pool's range check saw when it built d_fh (-1: it had no frame to check).  The largest magnitude of
@@ -1324,7 +1327,7 @@ static int launch_ef_gemms(acx_ctx *c, const SegBatch &seg, int B, int tiles_x, 
 }
 
 static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params &p, float *out, const EfDebug *dbg,
-                       const float *ext_matrix, int extM, int extN, const DevDst *dd, const EfAlign *aln);
+                       const float *ext_matrix, int extM, int extN, const DevDst *dd, const EfAlign *aln, std::vector<acx::EfPair> *pd_out);
 
 // The alignment pass (ef_align_kernels.hpp) behind a batch's Smith-Waterman launch, while d_efbits and d_efpd
 // still hold the batch: `pd` are the batch's descriptors on the host, pair b of the batch is pair k0 + b of the run, `scores` its
@@ -1408,15 +1411,16 @@ static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, in
 
 // `dd` (grid runs): the four scores of pair k go to dd->base[dd->idx[k] .. + 4) on the DEVICE instead of out[4 k ..].
 int run_ef(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params &p, float *out, const EfDebug *dbg,
-           const float *ext_matrix, int extM, int extN, const DevDst *dd = nullptr, const EfAlign *aln = nullptr)
+           const float *ext_matrix, int extM, int extN, const DevDst *dd = nullptr, const EfAlign *aln = nullptr,
+           std::vector<acx::EfPair> *pd_out = nullptr)
 {
-    const int rc = run_ef_impl(c, pairs, K, p, out, dbg, ext_matrix, extM, extN, dd, aln);
+    const int rc = run_ef_impl(c, pairs, K, p, out, dbg, ext_matrix, extM, extN, dd, aln, pd_out);
     if (rc != ACX_OK) quiesce(c);                // nothing of a failed call stays in flight behind its error code
     return rc;
 }
 
 static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params &p, float *out, const EfDebug *dbg,
-                       const float *ext_matrix, int extM, int extN, const DevDst *dd, const EfAlign *aln)
+                       const float *ext_matrix, int extM, int extN, const DevDst *dd, const EfAlign *aln, std::vector<acx::EfPair> *pd_out)
 {
     using acx::EfPair;
     if (!ext_matrix && (!c->d_ef[0] || c->ef_open)) return fail(c, ACX_ERR_STATE, "earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)");
@@ -1562,6 +1566,9 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
     if ((rc = prepare(hbs[0], 0)) != ACX_OK) return rc;
     if (dbg && !ext_matrix && hbs[0].k_end < K)          // the debug entries show one batch: refused before the first launch
         return fail(c, ACX_ERR_UNSUPPORTED, "ef debug: the list does not fit one batch");
+    // pd_out (the cross-diffusion fusion): the caller goes on with the matrices this call leaves in d_scratch, where the
+    // descriptors of its ONE batch say
+    if (pd_out && hbs[0].k_end < K) return fail(c, ACX_ERR_NOMEM, "earlyfusion: the pair and its two self pairs do not fit the scratch limit");
     for (int bi = 0; hbs[bi & 1].k_begin < K; ++bi) {
         HostBatch &hb = hbs[bi & 1];
         std::vector<EfPair> &pd = hb.pd;
@@ -1671,6 +1678,7 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
         ht[3] += now() - t_w;
         drain_profile(c);
         if (rc_next != ACX_OK) return rc_next;
+        if (pd_out) *pd_out = pd;
         if (dbg && B >= 1) {
             EfPair d;
             ACX_HIP(c, hipMemcpy(&d, c->d_efpd + (dbg->which - k0), sizeof(EfPair), hipMemcpyDeviceToHost));
@@ -3859,14 +3867,27 @@ struct SnfTaps {
 // getW (similarity_fusion.py:15-36: symmetrise, local scale from the K + 1 nearest, Gaussian kernel), getS (:124-144) as
 // neighbour lists, getP (:101-122).  from_stage = 1 (tests): M is already the affinity matrix, getW is skipped.  `acc` is the
 // staging buffer, `ut` holds S and then W.  The product entry point and acx_snf_debug_stages both launch the kernels here.
+static hipError_t snf_prepare_dev(acx_ctx *c, double *acc, double *ut, double *md, int32_t *dJ, double *dV, double *cur, int n, int K,
+                                  double mu, int from_stage, const SnfTaps &tap, bool lists = true);
+
 static hipError_t snf_prepare(acx_ctx *c, const double *M, double *acc, double *ut, double *md, int32_t *dJ, double *dV, double *cur,
                               int n, int K, double mu, int from_stage, const SnfTaps &tap)
 {
     const size_t nn = (size_t)n * n;
-    const dim3 tg((n + 31) / 32, (n + 31) / 32);
-    const unsigned rows4 = (unsigned)((n + 3) / 4);
     hipError_t e = hipMemcpyAsync(from_stage == 0 ? acc : ut, M, nn * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) return e;
+    return snf_prepare_dev(c, acc, ut, md, dJ, dV, cur, n, K, mu, from_stage, tap);
+}
+
+// The same behind the copy, for a matrix that is on the device already: in `acc` (from_stage = 0) or in `ut` (from_stage = 1).
+// lists = false stops behind getW (the diagonal blocks of the cross-diffusion fusion, which take their lists from the whole W).
+static hipError_t snf_prepare_dev(acx_ctx *c, double *acc, double *ut, double *md, int32_t *dJ, double *dV, double *cur, int n, int K,
+                                  double mu, int from_stage, const SnfTaps &tap, bool lists)
+{
+    const size_t nn = (size_t)n * n;
+    const dim3 tg((n + 31) / 32, (n + 31) / 32);
+    const unsigned rows4 = (unsigned)((n + 3) / 4);
+    hipError_t e = hipSuccess;
     if (from_stage == 0) {
         hipLaunchKernelGGL(acx::snf_sym_kernel, tg, dim3(256), 0, c->stream, acc, ut, n);
         if (tap.S) e = hipMemcpyAsync(tap.S, ut, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
@@ -3875,17 +3896,20 @@ static hipError_t snf_prepare(acx_ctx *c, const double *M, double *acc, double *
         hipLaunchKernelGGL(acx::snf_affinity_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, c->stream, ut, md, n, mu);
     }
     if (tap.W && e == hipSuccess) e = hipMemcpyAsync(tap.W, ut, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    hipLaunchKernelGGL(acx::snf_knn_kernel, dim3(rows4), dim3(256), 0, c->stream, ut, dJ, dV, n, K);
-    hipLaunchKernelGGL(acx::snf_rownorm_kernel, dim3(n), dim3(256), 0, c->stream, ut, cur, n);
-    if (tap.J && e == hipSuccess) e = hipMemcpyAsync(tap.J, dJ, (size_t)n * K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
-    if (tap.V && e == hipSuccess) e = hipMemcpyAsync(tap.V, dV, (size_t)n * K * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (tap.P && e == hipSuccess) e = hipMemcpyAsync(tap.P, cur, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (lists) {
+        hipLaunchKernelGGL(acx::snf_knn_kernel, dim3(rows4), dim3(256), 0, c->stream, ut, dJ, dV, n, K);
+        hipLaunchKernelGGL(acx::snf_rownorm_kernel, dim3(n), dim3(256), 0, c->stream, ut, cur, n);
+        if (tap.J && e == hipSuccess) e = hipMemcpyAsync(tap.J, dJ, (size_t)n * K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+        if (tap.V && e == hipSuccess) e = hipMemcpyAsync(tap.V, dV, (size_t)n * K * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (tap.P && e == hipSuccess) e = hipMemcpyAsync(tap.P, cur, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    }
     if (e == hipSuccess) e = hipGetLastError();
     return e;
 }
 
 // The cross-diffusion loop of doSimilarityFusionWs (similarity_fusion.py:146-186) on matrices that are
-// already on the device: cur[i] = row-normalised W_i, (dJ[i], dV[i]) = its kNN kernel.
+// already on the device: cur[i] = row-normalised W_i, (dJ[i], dV[i]) = its kNN kernel.  out = nullptr: the result stays in
+// R.acc and the launches stay queued (the caller goes on with it on the device).
 static int snf_loop(acx_ctx *c, SnfRun &R, int niters, double reg_diag, double *out)
 {
     const int m = R.m, n = R.n, K = R.K;
@@ -3912,6 +3936,7 @@ static int snf_loop(acx_ctx *c, SnfRun &R, int niters, double reg_diag, double *
                            sp, 1.0 / (double)m, R.acc, (int64_t)nn);
     }
     ACX_HIP(c, hipGetLastError());
+    if (!out) return ACX_OK;
     ACX_HIP(c, hipMemcpyAsync(out, R.acc, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     ACX_HIP(c, hipStreamSynchronize(c->stream));
     return ACX_OK;
@@ -4041,6 +4066,310 @@ int acx_snf_debug_update(acx_ctx *c, const double *const *srcs, int32_t m_src, i
     }
     ACX_HIP(c, hipStreamSynchronize(c->stream));
     return ACX_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// EarlyFusion: the full cross-diffusion fusion for listed pairs (ef_crossfusion_kernels.hpp)
+// ---------------------------------------------------------------------------------------
+// Device state of a list: one SnfRun sized for the largest n of the list, the means of the three cross blocks, X.
+struct XfRun {
+    SnfRun R;
+    DeviceBuffer<double> rc, X;          // [r x3 (M each)][c x3 (N each)];  X (M, N)
+    acx::EfPair desc;                    // the plot's descriptor: the source of a queued copy, so it lives as long as the run
+};
+
+// the three triples of one pair on the device: f32, row pitches in floats
+struct XfSrc {
+    const float *SA[3], *SB[3], *C[3];
+    int64_t ldA, ldB, ldC;
+};
+
+// where the intermediates of one pair go on the host (any may be null)
+struct XfTaps {
+    double *r = nullptr, *c = nullptr, *W = nullptr, *D = nullptr, *X = nullptr;
+    uint32_t *bits = nullptr;
+};
+
+// k1 = int(K M / (M + N)), k2 = K - k1 (similarity_fusion.py:93-94); what np.partition refuses or divides by zero on is refused
+static bool xf_split(int M, int N, int K, int &k1, int &k2)
+{
+    k1 = (int)((double)K * (double)M / (double)(M + N));
+    k2 = K - k1;
+    return k1 >= 1 && k2 >= 1 && k1 + 1 < M && k2 + 1 < N;
+}
+
+static std::string xf_split_text(int M, int N, int K)
+{
+    int k1, k2;
+    (void)xf_split(M, N, K, k1, k2);
+    return std::to_string(M) + " x " + std::to_string(N) + " blocks with K = " + std::to_string(K) + " give k1 = " + std::to_string(k1) + ", k2 = " +
+           std::to_string(k2) + "; needed: 1 <= k1 < M - 1 and 1 <= k2 < N - 1";
+}
+
+// csm_to_binary's neighbours per row (cross_recurrence.py:149-154), as run_ef sets EfPair::kbin
+static int xf_kbin(double kappa, int N)
+{
+    if (kappa == 0.0) return N;
+    if (kappa < 1.0) return (int)std::nearbyint(kappa * (double)N);
+    return (int)kappa;
+}
+
+static int xf_alloc(acx_ctx *c, XfRun &xr, int maxM, int maxN, int maxn, int K)
+{
+    int rc = snf_alloc(c, xr.R, 3, maxn, K);
+    if (rc != ACX_OK) return rc;
+    if ((rc = ensure(c, xr.rc, (size_t)3 * (maxM + maxN))) != ACX_OK) return rc;
+    if ((rc = ensure(c, xr.X, (size_t)maxM * maxN)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efbits, (size_t)maxM * (round_up(maxN, 64) / 32))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efpd, (size_t)1)) != ACX_OK) return rc;
+    return ensure(c, c->d_out, (size_t)4);
+}
+
+// Selection on X (xr.X, or the caller's matrix when the test entry put it there) and the Smith-Waterman on the bitmap: d_efbits
+// holds the plot from word 0 on in the layout of a batch's plane, descriptor 0 of d_efpd says so; the score waits in d_out[0].
+static int xf_select_sw(acx_ctx *c, XfRun &xr, int M, int N, int kbin, const XfTaps &tap)
+{
+    acx::EfPair &d = xr.desc;
+    d.q = d.r = 0; d.M = M; d.N = N; d.oti = 0; d.pitchC = round_up(N, 64); d.pitchT = round_up(M, 64); d.kbin = kbin;
+    d.ctN = 0; d.pad = 0; d.offB = 0; d.offC = 0; d.offS = 0;
+    ACX_HIP(c, hipMemcpyAsync(c->d_efpd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
+    {
+        ProfScope ps(c, KS_XFSELECT, (int64_t)M * N);
+        hipLaunchKernelGGL(acx::xf_select_kernel, dim3((M + 3) / 4), dim3(256), 0, c->stream, xr.X, M, N, kbin, c->d_efbits);
+    }
+    if (tap.bits) ACX_HIP(c, hipMemcpyAsync(tap.bits, c->d_efbits, sizeof(uint32_t) * (size_t)M * (d.pitchC / 32), hipMemcpyDeviceToHost, c->stream));
+    {
+        ProfScope ps(c, KS_EFSW, (int64_t)M * N);
+        if (N > 512) hipLaunchKernelGGL((acx::sw_bits_h16_kernel<16>), dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_efbits, c->d_out, 0);
+        else hipLaunchKernelGGL((acx::sw_bits_h16_kernel<8>), dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_efbits, c->d_out, 0);
+    }
+    ACX_LAUNCHES_OK(c);
+    return ACX_OK;
+}
+
+// One pair behind its GEMMs: W per feature (in R.nxt[f], which the loop only writes later), the lists and P of each, the loop,
+// X, the bitmap and the score (queued; `score` is valid after the wait at the end).  The shape has passed xf_split.
+static int xf_chain(acx_ctx *c, XfRun &xr, const XfSrc &s, int M, int N, int K, int kbin, int niters, double reg_diag,
+                    const XfTaps &tap, float *score)
+{
+    SnfRun &R = xr.R;
+    const int n = M + N;
+    const double mu = 0.5;
+    int k1, k2;
+    (void)xf_split(M, N, K, k1, k2);
+    R.n = n;
+    const size_t nn = (size_t)n * n;
+    double *r = xr.rc, *cm = xr.rc.get() + (size_t)3 * M;
+    for (int f = 0; f < 3; ++f) {
+        {
+            ProfScope ps(c, KS_XFMEANS, (int64_t)M * N);
+            hipLaunchKernelGGL(acx::xf_means_kernel, dim3((n + 3) / 4), dim3(256), 0, c->stream, s.C[f], M, N, s.ldC, k2, k1,
+                               r + (size_t)f * M, cm + (size_t)f * N);
+        }
+        ProfScope ps(c, KS_XFAFFINITY, (int64_t)n * n);
+        hipLaunchKernelGGL(acx::xf_cross_affinity_kernel, dim3((N + 31) / 32, (M + 31) / 32), dim3(256), 0, c->stream, s.C[f], M, N, s.ldC,
+                           r + (size_t)f * M, cm + (size_t)f * N, mu, R.nxt[f].get());
+        // the diagonal blocks: getW(S^A, k1) and getW(S^B, k2) on the three stage kernels of snf_prepare, then into place
+        for (int side = 0; side < 2; ++side) {
+            const int m = side ? N : M, kk = side ? k2 : k1;
+            const unsigned g = (unsigned)(((size_t)m * m + 255) / 256);
+            hipLaunchKernelGGL(acx::xf_widen_kernel, dim3(g), dim3(256), 0, c->stream, side ? s.SB[f] : s.SA[f], side ? s.ldB : s.ldA, m, R.acc.get());
+            ACX_HIP(c, snf_prepare_dev(c, R.acc, R.ut, R.md, nullptr, nullptr, nullptr, m, kk, mu, 0, SnfTaps(), false));
+            hipLaunchKernelGGL(acx::xf_place_kernel, dim3(g), dim3(256), 0, c->stream, R.ut.get(), m, R.nxt[f].get(), n, side ? M : 0);
+        }
+        if (tap.W) ACX_HIP(c, hipMemcpyAsync(tap.W + (size_t)f * nn, R.nxt[f], nn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    {
+        // doSimilarityFusionWs: getS and getP of every W (from_stage = 1 of snf_prepare, W where it is), then the loop
+        ProfScope ps(c, KS_XFSNF, (int64_t)n * n);
+        for (int f = 0; f < 3; ++f)
+            ACX_HIP(c, snf_prepare_dev(c, nullptr, R.nxt[f], R.md, R.dJ[f], R.dV[f], R.cur[f], n, K, mu, 1, SnfTaps()));
+        const int rc = snf_loop(c, R, niters, reg_diag, nullptr);
+        if (rc != ACX_OK) return rc;
+    }
+    if (tap.D) ACX_HIP(c, hipMemcpyAsync(tap.D, R.acc, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    {
+        ProfScope ps(c, KS_XFX, (int64_t)M * N);
+        hipLaunchKernelGGL(acx::xf_x_kernel, dim3((N + 31) / 32, (M + 31) / 32), dim3(256), 0, c->stream, R.acc.get(), M, N, xr.X.get());
+    }
+    if (tap.r) ACX_HIP(c, hipMemcpyAsync(tap.r, r, sizeof(double) * 3 * M, hipMemcpyDeviceToHost, c->stream));
+    if (tap.c) ACX_HIP(c, hipMemcpyAsync(tap.c, cm, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
+    if (tap.X) ACX_HIP(c, hipMemcpyAsync(tap.X, xr.X, sizeof(double) * (size_t)M * N, hipMemcpyDeviceToHost, c->stream));
+    const int rc = xf_select_sw(c, xr, M, N, kbin, tap);
+    if (rc != ACX_OK) return rc;
+    ACX_HIP(c, hipMemcpyAsync(score, c->d_out, sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    drain_profile(c);
+    return ACX_OK;
+}
+
+static int xf_check_params(acx_ctx *c, const char *who, double kappa, int K, int niters)
+{
+    if (niters < 1) return fail(c, ACX_ERR_INVALID, std::string(who) + ": niters must be >= 1");
+    if (K < 1) return fail(c, ACX_ERR_INVALID, std::string(who) + ": K must be >= 1");
+    if (!(kappa >= 0.0)) return fail(c, ACX_ERR_INVALID, std::string(who) + ": kappa must be >= 0");
+    if (K > 64) return fail(c, ACX_ERR_UNSUPPORTED, std::string(who) + ": more than 64 neighbours are not supported on the device");
+    return ACX_OK;
+}
+
+// where the intermediates of the product path's one debug pair go (acx_ef_crossfusion_debug)
+struct XfPairDebug {
+    float *ssm_a, *ssm_b, *csm;
+    XfTaps tap;
+};
+
+static int xf_pairs_impl(acx_ctx *c, const int32_t *pairs, int64_t Kp, const acx_ef_params *params, int32_t niters, double reg_diag,
+                         float *out, const XfPairDebug *dbg)
+{
+    if (Kp < 0 || (Kp > 0 && (!pairs || !out)) || !params) return fail(c, ACX_ERR_INVALID, "ef_crossfusion: bad argument");
+    int rc = xf_check_params(c, "ef_crossfusion", params->kappa, params->K, niters);
+    if (rc != ACX_OK) return rc;
+    if (Kp == 0) return ACX_OK;
+    // the whole list before the first launch, on the caller's list
+    const bool pool = c->d_ef[0] && !c->ef_open;
+    for (int64_t k = 0; k < Kp; ++k)
+        if (pairs[2 * k] < 0 || pairs[2 * k + 1] < 0 || pairs[2 * k] >= c->ef_ntracks || pairs[2 * k + 1] >= c->ef_ntracks)
+            return fail(c, pool ? ACX_ERR_INVALID : ACX_ERR_STATE,
+                        pool ? "earlyfusion: track index out of range in pair " + std::to_string(k)
+                             : std::string("earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)"));
+    if (!pool) return fail(c, ACX_ERR_STATE, "earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)");
+    int maxM = 0, maxN = 0, maxn = 0;
+    for (int64_t k = 0; k < Kp; ++k) {
+        const int64_t M = c->h_efoff[pairs[2 * k] + 1] - c->h_efoff[pairs[2 * k]], N = c->h_efoff[pairs[2 * k + 1] + 1] - c->h_efoff[pairs[2 * k + 1]];
+        if (M < 1 || N < 1) return fail(c, ACX_ERR_SHORT, "earlyfusion: track without blocks (pair " + std::to_string(k) + ")");
+        if (M > acx::XF_MAXN || N > acx::XF_MAXN)
+            return fail(c, ACX_ERR_UNSUPPORTED, "ef_crossfusion: the fusion needs the bit path: at most 1024 blocks (pair " + std::to_string(k) + ": " +
+                                                    std::to_string(M) + " x " + std::to_string(N) + ")");
+        int k1, k2;
+        if (!xf_split((int)M, (int)N, params->K, k1, k2))
+            return fail(c, ACX_ERR_UNSUPPORTED, "ef_crossfusion: pair " + std::to_string(k) + ": " + xf_split_text((int)M, (int)N, params->K));
+        maxM = std::max(maxM, (int)M); maxN = std::max(maxN, (int)N); maxn = std::max(maxn, (int)(M + N));
+    }
+    ACX_HIP(c, hipSetDevice(c->device));
+    XfRun xr;
+    if ((rc = xf_alloc(c, xr, maxM, maxN, maxn, params->K)) != ACX_OK) return rc;
+    // the distances come from the product's own GEMM path: the pair and the two self pairs as one list of run_ef, whose
+    // matrices stay in d_scratch (its statistics and scores are not used: K = 1 keeps them cheap, the GEMMs do not read K)
+    const acx_ef_params gp{params->kappa, 1};
+    std::vector<acx::EfPair> pd;
+    for (int64_t k = 0; k < Kp; ++k) {
+        const int32_t a = pairs[2 * k], b = pairs[2 * k + 1];
+        const int32_t three[6] = {a, b, a, a, b, b};
+        float sc[12];
+        if ((rc = run_ef(c, three, 3, gp, sc, nullptr, nullptr, 0, 0, nullptr, nullptr, &pd)) != ACX_OK) return rc;
+        if (pd.size() != 3) return fail(c, ACX_ERR_STATE, "ef_crossfusion: the GEMM batch returned " + std::to_string(pd.size()) + " descriptors");
+        const int M = pd[0].M, N = pd[0].N;
+        XfSrc s;
+        s.ldC = pd[0].pitchC; s.ldA = pd[1].pitchC; s.ldB = pd[2].pitchC;
+        for (int f = 0; f < 3; ++f) {
+            s.C[f] = c->d_scratch + pd[0].offC + (int64_t)f * M * pd[0].pitchC;
+            s.SA[f] = c->d_scratch + pd[1].offC + (int64_t)f * M * pd[1].pitchC;
+            s.SB[f] = c->d_scratch + pd[2].offC + (int64_t)f * N * pd[2].pitchC;
+        }
+        if (dbg)
+            for (int f = 0; f < 3; ++f) {
+                if (dbg->csm) ACX_HIP(c, hipMemcpy2DAsync(dbg->csm + (size_t)f * M * N, sizeof(float) * N, s.C[f], sizeof(float) * s.ldC, sizeof(float) * N, M, hipMemcpyDeviceToHost, c->stream));
+                if (dbg->ssm_a) ACX_HIP(c, hipMemcpy2DAsync(dbg->ssm_a + (size_t)f * M * M, sizeof(float) * M, s.SA[f], sizeof(float) * s.ldA, sizeof(float) * M, M, hipMemcpyDeviceToHost, c->stream));
+                if (dbg->ssm_b) ACX_HIP(c, hipMemcpy2DAsync(dbg->ssm_b + (size_t)f * N * N, sizeof(float) * N, s.SB[f], sizeof(float) * s.ldB, sizeof(float) * N, N, hipMemcpyDeviceToHost, c->stream));
+            }
+        if ((rc = xf_chain(c, xr, s, M, N, params->K, xf_kbin(params->kappa, N), niters, reg_diag, dbg ? dbg->tap : XfTaps(), out + k)) != ACX_OK) return rc;
+    }
+    return ACX_OK;
+}
+
+int acx_ef_crossfusion_pairs(acx_ctx *c, const int32_t *pairs, int64_t K_pairs, const acx_ef_params *params, int32_t niters,
+                             double reg_diag, float *out)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const int rc = xf_pairs_impl(c, pairs, K_pairs, params, niters, reg_diag, out, nullptr);
+    if (rc != ACX_OK) quiesce(c);                // nothing of a failed call stays in flight behind its error code
+    return rc;
+}
+
+int acx_ef_crossfusion_debug(acx_ctx *c, int32_t i, int32_t j, const acx_ef_params *params, int32_t niters, double reg_diag,
+                             float *ssm_a, float *ssm_b, float *csm, double *W, double *D, double *X, uint32_t *bits, float *score)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const int32_t pr[2] = {i, j};
+    float sc = 0.0f;
+    XfPairDebug dbg{ssm_a, ssm_b, csm, XfTaps()};
+    dbg.tap.W = W; dbg.tap.D = D; dbg.tap.X = X; dbg.tap.bits = bits;
+    const int rc = xf_pairs_impl(c, pr, 1, params, niters, reg_diag, &sc, &dbg);
+    if (rc != ACX_OK) quiesce(c);
+    else if (score) *score = sc;
+    return rc;
+}
+
+static int xf_matrices_impl(acx_ctx *c, const float *SA, const float *SB, const float *C, int32_t M, int32_t N, double kappa, int32_t K,
+                            int32_t niters, double reg_diag, const XfTaps &tap, float *score)
+{
+    if (!SA || !SB || !C || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "crossfusion_matrices: bad argument");
+    int rc = xf_check_params(c, "crossfusion_matrices", kappa, K, niters);
+    if (rc != ACX_OK) return rc;
+    if (M > acx::XF_MAXN || N > acx::XF_MAXN)
+        return fail(c, ACX_ERR_UNSUPPORTED, "crossfusion_matrices: more than 1024 rows or columns (the kernels hold a row in one wave)");
+    int k1, k2;
+    if (!xf_split(M, N, K, k1, k2)) return fail(c, ACX_ERR_UNSUPPORTED, "crossfusion_matrices: " + xf_split_text(M, N, K));
+    ACX_HIP(c, hipSetDevice(c->device));
+    XfRun xr;
+    if ((rc = xf_alloc(c, xr, M, N, M + N, K)) != ACX_OK) return rc;
+    const size_t na = (size_t)M * M, nb = (size_t)N * N, nc = (size_t)M * N;
+    if ((rc = ensure(c, c->d_scratch, 3 * (na + nb + nc))) != ACX_OK) return rc;
+    float *dA = c->d_scratch, *dB = dA + 3 * na, *dC = dB + 3 * nb;
+    ACX_HIP(c, hipMemcpyAsync(dA, SA, sizeof(float) * 3 * na, hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(dB, SB, sizeof(float) * 3 * nb, hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(dC, C, sizeof(float) * 3 * nc, hipMemcpyHostToDevice, c->stream));
+    XfSrc s;
+    s.ldA = M; s.ldB = N; s.ldC = N;
+    for (int f = 0; f < 3; ++f) { s.SA[f] = dA + f * na; s.SB[f] = dB + f * nb; s.C[f] = dC + f * nc; }
+    float sc = 0.0f;
+    if ((rc = xf_chain(c, xr, s, M, N, K, xf_kbin(kappa, N), niters, reg_diag, tap, &sc)) != ACX_OK) return rc;
+    if (score) *score = sc;
+    return ACX_OK;
+}
+
+int acx_crossfusion_matrices(acx_ctx *c, const float *SA, const float *SB, const float *C, int32_t M, int32_t N, double kappa,
+                             int32_t K, int32_t niters, double reg_diag, double *r, double *cm, double *W, double *D, double *X,
+                             uint32_t *bits, float *score)
+{
+    if (!c) return ACX_ERR_INVALID;
+    XfTaps tap;
+    tap.r = r; tap.c = cm; tap.W = W; tap.D = D; tap.X = X; tap.bits = bits;
+    const int rc = xf_matrices_impl(c, SA, SB, C, M, N, kappa, K, niters, reg_diag, tap, score);
+    if (rc != ACX_OK) quiesce(c);
+    return rc;
+}
+
+static int xf_xsel_impl(acx_ctx *c, const double *X, int32_t M, int32_t N, double kappa, uint32_t *bits, float *score)
+{
+    if (!X || M < 1 || N < 1 || !(kappa >= 0.0)) return fail(c, ACX_ERR_INVALID, "xsel_binary_sw: bad argument");
+    if (M > acx::XF_MAXN || N > acx::XF_MAXN)
+        return fail(c, ACX_ERR_UNSUPPORTED, "xsel_binary_sw: more than 1024 rows or columns (the kernels hold a row in one wave)");
+    ACX_HIP(c, hipSetDevice(c->device));
+    XfRun xr;
+    int rc;
+    if ((rc = ensure(c, xr.X, (size_t)M * N)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efbits, (size_t)M * (round_up(N, 64) / 32))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efpd, (size_t)1)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_out, (size_t)4)) != ACX_OK) return rc;
+    ACX_HIP(c, hipMemcpyAsync(xr.X, X, sizeof(double) * (size_t)M * N, hipMemcpyHostToDevice, c->stream));
+    XfTaps tap;
+    tap.bits = bits;
+    if ((rc = xf_select_sw(c, xr, M, N, xf_kbin(kappa, N), tap)) != ACX_OK) return rc;
+    float sc = 0.0f;
+    ACX_HIP(c, hipMemcpyAsync(&sc, c->d_out, sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    drain_profile(c);
+    if (score) *score = sc;
+    return ACX_OK;
+}
+
+int acx_xsel_binary_sw(acx_ctx *c, const double *X, int32_t M, int32_t N, double kappa, uint32_t *bits, float *score)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const int rc = xf_xsel_impl(c, X, M, N, kappa, bits, score);
+    if (rc != ACX_OK) quiesce(c);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------

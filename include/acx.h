@@ -751,6 +751,46 @@ int acx_snf_debug_update(acx_ctx *ctx, const double *const *srcs, int32_t m_src,
                          const int32_t *J, const double *V, double reg_diag, int32_t variant, const int32_t *rows,
                          int32_t n_rows, double *acc_rows, double *ut_rows, double *p_rows);
 
+/* ---- EarlyFusion: the full cross-diffusion fusion for listed pairs ---------- */
+
+/*
+ * The early fusion of Tralie's ISMIR 2017 paper, the "Step 3" that earlyfusion_traile.py:142-148 disables, for ordered
+ * pairs of the uploaded EarlyFusion pool.  Per pair (A of M blocks, B of N, n = M + N) and per feature (mfccs, ssms,
+ * chromas): W = getWCSMSSM(S^A, S^B, C, K, mu = 0.5) (similarity_fusion.py:76-99) from the f32 matrices of the pairs
+ * (A, A), (B, B), (A, B) under the current acx_set_ef_gemm mode, in f64; D = doSimilarityFusionWs of the three W
+ * (:146-186; params->K neighbours, niters sweeps); X = D[0:M, M:] + D[M:, 0:M]^T; row i of the plot holds the
+ * round(kappa N) columns with the largest X[i, :] (csm_to_binary(exp(-X), kappa) without the exponential; ties at the
+ * cut in column order); out[k] = smith_waterman_constrained of the plot (alignment_tools.py:26-46), one f32 per pair in
+ * the caller's order.  The stages restate reference functions; the composition is the method's, not the reference's.
+ * The whole list is checked before the first launch.  ACX_ERR_UNSUPPORTED: a pair with k1 = int(K M / (M + N)) < 1,
+ * k2 = K - k1 < 1, k1 + 1 >= M or k2 + 1 >= N (np.partition raises or divides by zero there; the message names the
+ * pair's position), a track of more than 1024 blocks, K > 64.  ACX_ERR_INVALID: niters < 1.  Indices, tracks without
+ * blocks and a missing pool: as acx_earlyfusion_pairs.
+ */
+int acx_ef_crossfusion_pairs(acx_ctx *ctx, const int32_t *pairs, int64_t K_pairs, const acx_ef_params *params,
+                             int32_t niters, double reg_diag, float *out);
+
+/*
+ * ONE pair of the pool through the same host function, every intermediate copied back (tests; any output may be NULL):
+ * ssm_a (3, M, M), ssm_b (3, N, N), csm (3, M, N) f32; W (3, n, n), D (n, n), X (M, N) f64; bits (M, pitch / 32) uint32,
+ * pitch = N rounded up to 64, bit j % 32 of word j / 32, pad bits zero; score.
+ */
+int acx_ef_crossfusion_debug(acx_ctx *ctx, int32_t i, int32_t j, const acx_ef_params *params, int32_t niters,
+                             double reg_diag, float *ssm_a, float *ssm_b, float *csm, double *W, double *D, double *X,
+                             uint32_t *bits, float *score);
+
+/*
+ * The same chain behind the GEMMs for a caller's three triples of f32 matrices (tests): SA (3, M, M), SB (3, N, N),
+ * C (3, M, N).  Also returns r (3, M) and c (3, N), the means of the k2 smallest cells of every row and of the k1
+ * smallest of every column of C (getWCSM, similarity_fusion.py:47-51).  M, N <= 1024; the refusals of the call above.
+ */
+int acx_crossfusion_matrices(acx_ctx *ctx, const float *SA, const float *SB, const float *C, int32_t M, int32_t N,
+                             double kappa, int32_t K, int32_t niters, double reg_diag, double *r, double *c, double *W,
+                             double *D, double *X, uint32_t *bits, float *score);
+
+/* The selection and the Smith-Waterman alone on a caller's f64 (M, N) matrix (tests).  M, N <= 1024. */
+int acx_xsel_binary_sw(acx_ctx *ctx, const double *X, int32_t M, int32_t N, double kappa, uint32_t *bits, float *score);
+
 /* ---- the N x N pair grid -------------------------------------------------- */
 
 /*
