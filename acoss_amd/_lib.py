@@ -48,6 +48,7 @@ EXPORTS = [
     "acx_simple_profile",
     "acx_snf_debug_stages", "acx_snf_debug_update",
     "acx_ef_crossfusion_pairs", "acx_ef_crossfusion_debug", "acx_crossfusion_matrices", "acx_xsel_binary_sw",
+    "acx_ef_download_pool",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -300,6 +301,7 @@ def load():
     L.acx_ef_block_features.argtypes = [vp, fp, ctypes.c_int64, fp, ctypes.c_int64, ctypes.c_int32, lp, ctypes.c_int32, epp,
                                         fp, fp, fp, dp]
     L.acx_ef_upload_raw_pool.argtypes = [vp, fp, lp, fp, lp, ctypes.c_int32, lp, lp, ctypes.c_int32, epp, lp]
+    L.acx_ef_download_pool.argtypes = [vp, fp, fp, fp, fp, fp, dp, lp, ip, ip]
     gp = ctypes.POINTER(GridSpec)
     L.acx_grid_plan.argtypes = [lp, ctypes.c_int32, gp, ctypes.POINTER(GridTile), ctypes.c_int64, lp, lp, dp]
     L.acx_pool_lengths.argtypes = [vp, ctypes.c_int32, lp, ctypes.c_int32, ip]
@@ -778,6 +780,24 @@ class Context(object):
         self.ef_blocks = np.diff(boff)
         self._ef_dims = (int(mfccs_per_block) * int(ncoef), int(mfccs_per_block) * (int(mfccs_per_block) - 1) // 2, int(chromas_per_block) * 12)
         return boff
+
+    def ef_download_pool(self):
+        """The block-feature pool as the device holds it (acx_ef_download_pool): dict of mfccs, ssms, chromas (f32, one row
+        per block; the chroma rows are already unit-normalised), mfcc_sq, ssm_sq (the squared row norms, f32), chroma_med
+        (n_tracks, 12) f64 and offsets (n_tracks + 1) int64.  AcxError when no finished pool is up."""
+        nt = ctypes.c_int32(0)
+        dims = (ctypes.c_int32 * 3)()
+        self._check(self._L.acx_ef_download_pool(self._h, None, None, None, None, None, None, None, ctypes.byref(nt), dims))
+        offsets = np.zeros(nt.value + 1, np.int64)
+        self._check(self._L.acx_ef_download_pool(self._h, None, None, None, None, None, None, _lptr(offsets), None, None))
+        nb = int(offsets[-1])
+        out = dict(mfccs=np.zeros((nb, dims[0]), np.float32), ssms=np.zeros((nb, dims[1]), np.float32),
+                   chromas=np.zeros((nb, dims[2]), np.float32), mfcc_sq=np.zeros(nb, np.float32), ssm_sq=np.zeros(nb, np.float32),
+                   chroma_med=np.zeros((nt.value, 12), np.float64), offsets=offsets)
+        self._check(self._L.acx_ef_download_pool(
+            self._h, _fptr(out["mfccs"]), _fptr(out["ssms"]), _fptr(out["chromas"]), _fptr(out["mfcc_sq"]), _fptr(out["ssm_sq"]),
+            out["chroma_med"].ctypes.data_as(ctypes.POINTER(ctypes.c_double)), None, None, None))
+        return out
 
     def earlyfusion_pairs(self, pairs, kappa=0.1, K=10):
         """(n, 4) scores: mfccs, ssms, chromas, early."""

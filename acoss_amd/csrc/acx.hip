@@ -2870,9 +2870,12 @@ struct EfBlocks {
     DeviceBuffer<double> med;            // chroma median, 12 per track
 };
 
-static int ef_build_blocks(acx_ctx *c, const float *chroma, const int64_t *coff, const float *mfcc, const int64_t *moff,
-                           int32_t ncoef, const int64_t *onsets, const int64_t *ooff, int32_t n_tracks,
-                           const acx_ef_prep_params &pp, std::vector<int64_t> &boff, EfBlocks &out)
+// Everything about a raw-feature upload that the host can refuse, before anything is allocated or a pool dropped: the
+// parameters, the offsets, negative onsets (numpy's slice would count them from the end; the device clamps) and blocks
+// whose resize needs a wider Gaussian than ef_blocks_kernel holds (radius as efp_resize computes it).  Fills the
+// block offsets.
+static int ef_plan_blocks(acx_ctx *c, const char *who, const int64_t *coff, const int64_t *moff, int32_t ncoef, const int64_t *onsets,
+                          const int64_t *ooff, int32_t n_tracks, const acx_ef_prep_params &pp, std::vector<int64_t> &boff)
 {
     if (pp.blocksize < 1 || pp.mfccs_per_block < 2 || pp.chromas_per_block < 1 || ncoef < 1)
         return fail(c, ACX_ERR_INVALID, "ef block features: bad parameter");
@@ -2885,7 +2888,33 @@ static int ef_build_blocks(acx_ctx *c, const float *chroma, const int64_t *coff,
             return fail(c, ACX_ERR_INVALID, "ef block features: offsets must be non-decreasing");
         const int64_t nbeat = ooff[t + 1] - ooff[t];
         boff[t + 1] = boff[t] + std::max<int64_t>(0, nbeat - pp.blocksize);
+        const int64_t *on = onsets + ooff[t];
+        for (int64_t k = 0; k < nbeat; ++k)
+            if (on[k] < 0)
+                return fail(c, ACX_ERR_INVALID, std::string(who) + ": track " + std::to_string(t) + " has a negative onset (" +
+                            std::to_string(on[k]) + "); numpy's slice would count it from the end");
+        const int64_t len[2] = {moff[t + 1] - moff[t], coff[t + 1] - coff[t]};
+        const int rows[2] = {pp.mfccs_per_block, pp.chromas_per_block}, last[2] = {pp.blocksize - 1, pp.blocksize};
+        static const char *what[2] = {"MFCCs", "chroma"};
+        for (int64_t b = 0; b < boff[t + 1] - boff[t]; ++b)
+            for (int k = 0; k < 2; ++k) {
+                const int64_t i1 = std::min(on[b], len[k]), i2 = std::min(on[b + last[k]], len[k]), n = std::max<int64_t>(0, i2 - i1);
+                const double factor = (double)n / (double)rows[k], sigma = factor > 1.0 ? (factor - 1.0) * 0.5 : 0.0;
+                if (4.0 * sigma + 0.5 >= (double)(acx::EFP_MAXRAD + 1))
+                    return fail(c, ACX_ERR_UNSUPPORTED, "ef block features: block " + std::to_string(b) + " of track " + std::to_string(t) + " spans " +
+                                std::to_string(n) + " frames of " + what[k] + ": its resize to " + std::to_string(rows[k]) +
+                                " rows needs a Gaussian of radius " + std::to_string((int64_t)(4.0 * sigma + 0.5)) + ", at most " +
+                                std::to_string(acx::EFP_MAXRAD) + " on the device");
+            }
     }
+    return ACX_OK;
+}
+
+// `boff`: the block offsets of ef_plan_blocks, which has passed.
+static int ef_build_blocks(acx_ctx *c, const float *chroma, const int64_t *coff, const float *mfcc, const int64_t *moff,
+                           int32_t ncoef, const int64_t *onsets, const int64_t *ooff, int32_t n_tracks,
+                           const acx_ef_prep_params &pp, const std::vector<int64_t> &boff, EfBlocks &out)
+{
     const int64_t nb = boff[n_tracks];
     const int dims[3] = {pp.mfccs_per_block * ncoef, pp.mfccs_per_block * (pp.mfccs_per_block - 1) / 2, pp.chromas_per_block * 12};
     for (int k = 0; k < 3; ++k) ACX_HIP(c, out.feat[k].grow((size_t)std::max<int64_t>(1, nb) * dims[k]));
@@ -2948,10 +2977,11 @@ int acx_ef_block_features(acx_ctx *c, const float *chroma, int64_t n_chroma, con
     int rc = ef_check_raw(c, "ef_block_features", chroma, mfcc, onsets, prep);
     if (rc != ACX_OK) return rc;
     if (n_chroma < 0 || n_mfcc < 0 || n_beats < 0) return fail(c, ACX_ERR_INVALID, "ef_block_features: bad argument");
-    ACX_HIP(c, hipSetDevice(c->device));
-    c->nf_zeroed = 0;
     const int64_t coff[2] = {0, n_chroma}, moff[2] = {0, n_mfcc}, ooff[2] = {0, n_beats};
     std::vector<int64_t> boff;
+    if ((rc = ef_plan_blocks(c, "ef_block_features", coff, moff, ncoef, onsets, ooff, 1, *prep, boff)) != ACX_OK) return rc;
+    ACX_HIP(c, hipSetDevice(c->device));
+    c->nf_zeroed = 0;
     EfBlocks blocks;
     if ((rc = ef_build_blocks(c, chroma, coff, mfcc, moff, ncoef, onsets, ooff, 1, *prep, boff, blocks)) != ACX_OK) return rc;
     const int64_t nb = boff[1];
@@ -2971,10 +3001,12 @@ int acx_ef_upload_raw_pool(acx_ctx *c, const float *chroma, const int64_t *chrom
     int rc = ef_check_raw(c, "ef_upload_raw_pool", chroma, mfcc, onsets, prep);
     if (rc != ACX_OK) return rc;
     if (!chroma_offsets || !mfcc_offsets || !onset_offsets || n_tracks <= 0) return fail(c, ACX_ERR_INVALID, "ef_upload_raw_pool: bad argument");
+    std::vector<int64_t> boff;
+    if ((rc = ef_plan_blocks(c, "ef_upload_raw_pool", chroma_offsets, mfcc_offsets, ncoef, onsets, onset_offsets, n_tracks, *prep, boff)) != ACX_OK)
+        return rc;                                    // (the pool that is up stays as it is)
     ACX_HIP(c, hipSetDevice(c->device));
     ef_free_pool(c);
     c->nf_zeroed = 0;
-    std::vector<int64_t> boff;
     EfBlocks blocks;
     if ((rc = ef_build_blocks(c, chroma, chroma_offsets, mfcc, mfcc_offsets, ncoef, onsets, onset_offsets, n_tracks, *prep, boff,
                               blocks)) != ACX_OK) return rc;
@@ -2983,6 +3015,26 @@ int acx_ef_upload_raw_pool(acx_ctx *c, const float *chroma, const int64_t *chrom
     const int32_t dims[3] = {prep->mfccs_per_block * ncoef, prep->mfccs_per_block * (prep->mfccs_per_block - 1) / 2, prep->chromas_per_block * 12};
     if (block_offsets_out) memcpy(block_offsets_out, boff.data(), sizeof(int64_t) * (n_tracks + 1));
     return ef_finish_pool(c, boff.data(), n_tracks, dims);
+}
+
+int acx_ef_download_pool(acx_ctx *c, float *mfccs, float *ssms, float *chromas, float *mfcc_sq, float *ssm_sq, double *chroma_med,
+                         int64_t *offsets, int32_t *n_tracks, int32_t *dims)
+{
+    if (!c) return ACX_ERR_INVALID;
+    if (!c->d_ef[0] || c->ef_open || c->ef_ntracks <= 0)
+        return fail(c, ACX_ERR_STATE, "ef_download_pool: no finished block-feature pool (acx_ef_upload_pool / acx_ef_upload_raw_pool / acx_ef_pool_end)");
+    const int64_t nb = c->h_efoff[(size_t)c->ef_ntracks];
+    if (n_tracks) *n_tracks = c->ef_ntracks;
+    if (dims) for (int k = 0; k < 3; ++k) dims[k] = c->ef_dims[k];
+    if (offsets) memcpy(offsets, c->h_efoff.data(), sizeof(int64_t) * ((size_t)c->ef_ntracks + 1));
+    ACX_HIP(c, hipSetDevice(c->device));
+    float *dst[3] = {mfccs, ssms, chromas}, *sq[2] = {mfcc_sq, ssm_sq};
+    for (int k = 0; k < 3; ++k)
+        if (dst[k] && nb > 0) ACX_HIP(c, hipMemcpy(dst[k], c->d_ef[k], sizeof(float) * nb * c->ef_dims[k], hipMemcpyDeviceToHost));
+    for (int k = 0; k < 2; ++k)
+        if (sq[k] && nb > 0) ACX_HIP(c, hipMemcpy(sq[k], c->d_efn[k], sizeof(float) * nb, hipMemcpyDeviceToHost));
+    if (chroma_med) ACX_HIP(c, hipMemcpy(chroma_med, c->d_efmed, sizeof(double) * 12 * c->ef_ntracks, hipMemcpyDeviceToHost));
+    return ACX_OK;
 }
 
 int acx_earlyfusion_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params *params, float *out)

@@ -83,7 +83,7 @@ __device__ __forceinline__ void efp_resize(const float *__restrict__ X, int64_t 
     const double factor = (double)n / (double)rows;
     const double sigma = factor > 1.0 ? (factor - 1.0) * 0.5 : 0.0;
     int r = sigma > 0.0 ? (int)(4.0 * sigma + 0.5) : 0;
-    r = r > EFP_MAXRAD ? EFP_MAXRAD : r;
+    r = r > EFP_MAXRAD ? EFP_MAXRAD : r;      // (never taken: the host refuses such a block, ef_plan_blocks; it keeps w in bounds)
     if (r > 0) {
         for (int k = tid; k <= 2 * r; k += nthreads) {
             const double xx = (double)(k - r);

@@ -481,6 +481,10 @@ typedef struct {
  *   chromas (n_blocks, chromas_per_block * 12)  f32 row-major, chroma_med (12) f64
  * into host buffers (any may be NULL).  The anti-aliased resize restates skimage.transform.resize
  * (see acoss_amd/csrc/ef_prep_kernels.hpp; unpinned: skimage is absent from the reference's tree).
+ * Refused before anything is allocated (here and in acx_ef_upload_raw_pool, whose pool then stays as it is):
+ * a negative onset -> ACX_ERR_INVALID naming the track (numpy's slice would count it from the end); a block
+ * whose resize needs a Gaussian of radius int(4 sigma + 0.5) > 512, sigma = (frames / rows - 1) / 2, i.e. of
+ * more than about 257 frames per row -> ACX_ERR_UNSUPPORTED naming the track and the block.
  */
 int acx_ef_block_features(acx_ctx *ctx, const float *chroma, int64_t n_chroma, const float *mfcc, int64_t n_mfcc,
                           int32_t ncoef, const int64_t *onsets, int32_t n_beats, const acx_ef_prep_params *prep,
@@ -498,6 +502,17 @@ int acx_ef_upload_raw_pool(acx_ctx *ctx, const float *chroma, const int64_t *chr
                            const int64_t *mfcc_offsets, int32_t ncoef, const int64_t *onsets,
                            const int64_t *onset_offsets, int32_t n_tracks, const acx_ef_prep_params *prep,
                            int64_t *block_offsets_out);
+
+/*
+ * The block-feature pool read back as the device holds it (host-side copies only; tests and inspection):
+ * mfccs (n_blocks, dims[0]), ssms (n_blocks, dims[1]), chromas (n_blocks, dims[2]) -- the chroma rows are
+ * ALREADY unit-normalised (a row of zeros stays zero) --, mfcc_sq / ssm_sq (n_blocks) the squared row norms
+ * of the two Euclidean features, chroma_med (n_tracks, 12), offsets (n_tracks + 1) the block offsets,
+ * *n_tracks and dims[3].  Any pointer may be NULL (a first call may ask for *n_tracks and dims alone, a
+ * second for the offsets).  No finished pool (none uploaded, or one still open): ACX_ERR_STATE.
+ */
+int acx_ef_download_pool(acx_ctx *ctx, float *mfccs, float *ssms, float *chromas, float *mfcc_sq, float *ssm_sq,
+                         double *chroma_med, int64_t *offsets, int32_t *n_tracks, int32_t *dims);
 
 typedef struct {
     double kappa;     /* csm_to_binary neighbourhood (EarlyFusion ctor kappa = 0.1)  */
