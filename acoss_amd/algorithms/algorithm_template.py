@@ -22,6 +22,8 @@ Differences from the reference, all deliberate:
   * under torch.distributed rank 0 owns the result: it alone holds the filled matrices, writes
     the cache / results files and computes the statistics, which are broadcast to the others.
 """
+import contextlib
+import functools
 import os
 import warnings
 
@@ -31,8 +33,33 @@ from .. import _lib
 from .. import dist as _dist
 from ..featurestore import load_track, load_matrices_h5, save_matrices_h5
 from ..utils import create_dataset_filepaths
+from . import _align
 
-__all__ = ["CoverAlgorithm"]
+__all__ = ["CoverAlgorithm", "AppendedSession", "refused_in_session"]
+
+
+class AppendedSession(object):
+    """What `with algo.appended(tracks) as s` yields: the Q appended tracks are tracks first .. total - 1 of the pool while the
+    block runs.  indices: np.arange(first, total) int32; first == algo.N; count == Q; total == N + Q; labels: the clique
+    labels given for the new tracks (None: evaluate() is refused)."""
+
+    def __init__(self, first, count, labels=None):
+        self.first, self.count, self.total = int(first), int(count), int(first) + int(count)
+        self.indices = np.arange(self.first, self.total, dtype=np.int32)
+        self.labels = labels
+        self.col_tail = None            # _identify_norm's column values of the new tracks (_append_tracks returns them)
+
+
+def refused_in_session(method):
+    """Marks a method that writes `Ds`, assumes an N x N result, or changes the pool or the feature caches: inside an
+    appended() session it raises a RuntimeError naming itself, before anything else happens."""
+    @functools.wraps(method)
+    def guarded(self, *args, **kwargs):
+        if getattr(self, "_session", None) is not None:
+            raise RuntimeError("%s: refused inside an appended() session (the pool holds %d tracks behind the collection's %d); "
+                               "leave the `with` block first" % (method.__name__, self._session.count, self.N))
+        return method(self, *args, **kwargs)
+    return guarded
 
 
 class CoverAlgorithm(object):
@@ -147,6 +174,7 @@ class CoverAlgorithm(object):
             self._register_label(int(i), label)
 
     # ------------------------------------------------------------------ pairwise
+    @refused_in_session
     def similarity(self, idxs):
         """idxs: (K,2) int array.  Writes Ds[type][i, j] for every row; the return value is
         ignored.  The base class stores zeros."""
@@ -163,6 +191,7 @@ class CoverAlgorithm(object):
             i, j = np.nonzero(~np.eye(N, dtype=bool))
         return np.stack([i, j], axis=1).astype(np.int64)
 
+    @refused_in_session
     def all_pairwise(self, parallel=0, n_cores=12, symmetric=False, precomputed=False):
         """All pairwise comparisons.  Device-backed classes ignore `parallel` / `n_cores`: their fan-out unit is the GPU
         (one process per GPU under torch.distributed).  User subclasses that bring their own CPU `similarity()` get the
@@ -278,9 +307,17 @@ class CoverAlgorithm(object):
     _identify_fused = ()
     _identify_symmetric = True
 
+    # the open appended() session (an AppendedSession), None outside one
+    _session = None
+
+    def _n_tracks(self):
+        """How many tracks may an index name right now: N, and N + Q inside an appended() session.  Every index check of
+        the read-only methods takes its bound from here; `self.N` is the collection's count throughout."""
+        return self.N if self._session is None else self._session.total
+
     def _identify_norm(self):
         """(col_mode, col) of the class's normalize_by_length as acx_query_spec states it (include/acx.h): (0, None) for
-        a class without one."""
+        a class without one.  col holds the collection's N values; _query_call adds a session's tail."""
         return 0, None
 
     def _query_setup(self, who, queries, similarity_types):
@@ -300,8 +337,8 @@ class CoverAlgorithm(object):
         if q.size and not np.issubdtype(q.dtype, np.integer):
             raise ValueError("%s: queries must be integer track indices" % who)
         q = q.reshape(-1).astype(np.int64)
-        if q.size and (q.min() < 0 or q.max() >= self.N):
-            raise ValueError("%s: queries must be track indices in [0, %d)" % (who, self.N))
+        if q.size and (q.min() < 0 or q.max() >= self._n_tracks()):
+            raise ValueError("%s: queries must be track indices in [0, %d)" % (who, self._n_tracks()))
         return q.astype(np.int32), types
 
     def _check_candidates(self, who, candidates, what):
@@ -312,8 +349,8 @@ class CoverAlgorithm(object):
         if cands.size and not np.issubdtype(cands.dtype, np.integer):
             raise ValueError("%s: candidates must be integer track indices" % who)
         cands = cands.reshape(-1).astype(np.int64)
-        if cands.size and (cands.min() < 0 or cands.max() >= self.N):
-            raise ValueError("%s: candidates must be %s in [0, %d)" % (who, what, self.N))
+        if cands.size and (cands.min() < 0 or cands.max() >= self._n_tracks()):
+            raise ValueError("%s: candidates must be %s in [0, %d)" % (who, what, self._n_tracks()))
         if np.any(np.diff(cands) <= 0):
             raise ValueError("%s: candidates must be strictly ascending" % who)
         return cands.astype(np.int32)
@@ -323,6 +360,8 @@ class CoverAlgorithm(object):
         if tuple(keys) != tuple(self._identify_planes):
             raise RuntimeError("%s: _grid() planes %s differ from _identify_planes %s" % (type(self).__name__, keys, self._identify_planes))
         mode, col = self._identify_norm()
+        if col is not None and self._session is not None:
+            col = np.concatenate([np.asarray(col, np.float64).reshape(-1), np.asarray(self._session.col_tail, np.float64).reshape(-1)])
         return ctx, algo, params, mode, col
 
     def identify(self, queries, k=10, candidates=None, similarity_types=None):
@@ -380,20 +419,162 @@ class CoverAlgorithm(object):
         checked = self._check_tracks(who, tracks, **how)
         return checked, len(tracks), types, self._check_candidates(who, candidates, "tracks of the collection, indices")
 
+    def _append_session(self, ctx, checked, s):
+        """Entering a session: the one append.  A class with more per-track side data than _identify_norm's column (Serra09:
+        the pooled lengths) overrides this and keeps the tail on the session object."""
+        s.col_tail = self._append_tracks(ctx, checked)
+
+    @contextlib.contextmanager
+    def _appended(self, checked, Q, labels=None):
+        """The session itself, for tracks that _check_tracks has passed: one append on the way in, one pool_truncate(algo, N)
+        on the way out -- after the block, after an exception in it and after a library error alike."""
+        if self._session is not None:
+            raise RuntimeError("appended: a session is already open on this object (sessions do not nest)")
+        ctx, algo = self._query_call()[:2]              # (uploads the collection's pool first where that has not happened)
+        N = self.N
+        s = AppendedSession(N, Q, labels)
+        try:
+            self._append_session(ctx, checked, s)
+            self._session = s
+            yield s
+        finally:
+            self._session = None
+            ctx.pool_truncate(algo, N)
+
+    def _session_setup(self, who, tracks, labels, how):
+        """Argument checks of appended() and the one-call forms, all before the first library call:
+        -> (what _check_tracks returned, the number of tracks, the labels as a list or None)."""
+        if self._session is not None:
+            raise RuntimeError("%s: a session is already open on this object (sessions do not nest)" % who)
+        checked, Q, _, _ = self._tracks_setup(who, tracks, None, None, how)
+        if labels is not None:
+            try:
+                labels = list(labels)
+            except TypeError:
+                raise ValueError("%s: labels must be a sequence of one clique label per track" % who)
+            if len(labels) != Q:
+                raise ValueError("%s: labels must hold one clique label per track (%d), got %d" % (who, Q, len(labels)))
+        return checked, Q, labels
+
+    def appended(self, tracks, labels=None, **how):
+        """A session over tracks the collection does NOT hold: `with algo.appended(tracks) as s:` appends them behind the
+        uploaded pool ONCE (tracks and `how` as identify_tracks() takes them: Serra09 / ChenFusion raw=True), keeps them
+        there while the block runs, and takes them away again when it ends -- on a normal exit, on an exception raised in
+        the block (it propagates) and on a library error alike.  s: an AppendedSession -- s.indices = arange(N, N + Q)
+        int32, s.first == N, s.count == Q, s.total == N + Q.
+        Inside the block every read-only, index-taking method of the class treats the collection as the N + Q tracks:
+        identify, query_rows, rerank, evaluate, align, align_paths, align_matches, align_match_paths (with the class's
+        similarity_type), Simple.profile, EarlyFusion.full_fusion / rerank_full accept indices in [0, N + Q) wherever they
+        accept [0, N) outside -- queries, candidates, shortlists, pairs -- and return, bit for bit, what the same call
+        returns on an object built over the N + Q tracks in one upload.  `algo.N` keeps reading N; s.total is the other
+        number.  labels: Q clique labels for the new tracks, used by evaluate() only: the mates of a query are all tracks
+        of the N + Q with its label; without labels evaluate() raises a ValueError.
+        Refused inside the block with a RuntimeError naming the method, before any library call: what writes `Ds` or assumes
+        an N x N result (similarity, all_pairwise, normalize_by_length, do_late_fusion, getEvalStatistics, top_matches),
+        what changes the pool or the feature caches (set_pooled_features / set_features / set_block_features,
+        identify_tracks, score_tracks, rerank_tracks, the one-call forms) and a nested appended().
+        Afterwards `Ds`, N, filepaths, the cliques, the cached features, the pooled lengths and the pool are exactly as
+        before.  Every argument check comes before the first library call.  Not a collective: under a process group each
+        rank that opens a session works on its own GPU."""
+        checked, Q, labels = self._session_setup("appended", tracks, labels, how)
+        return self._appended(checked, Q, labels)
+
     def _with_appended(self, checked, Q, call):
         """call(ctx, algo, params, mode, col, queries) with the Q tracks behind the collection's pool as tracks N .. N + Q - 1;
         whatever happens, the pool holds the N tracks of the collection again afterwards."""
-        ctx, algo, params, mode, col = self._query_call()
-        N = self.N
-        try:
-            tail = self._append_tracks(ctx, checked)
-            if col is not None:
-                col = np.concatenate([np.asarray(col, np.float64).reshape(-1), np.asarray(tail, np.float64).reshape(-1)])
-            return call(ctx, algo, params, mode, col, np.arange(N, N + Q, dtype=np.int32))
-        finally:
-            if len(ctx.pool_lengths(algo)) > N:
-                ctx.pool_truncate(algo, N)
+        with self._appended(checked, Q) as s:
+            ctx, algo, params, mode, col = self._query_call()
+            return call(ctx, algo, params, mode, col, s.indices)
 
+    def _cliques_now(self):
+        """The cliques as lists of sorted track indices: the collection's, and inside a session (opened with labels) the same
+        cliques extended by them -- a new label opens a clique behind the collection's, in the order of the new tracks, as
+        _register_label would over the N + Q tracks.  `self.cliques` is not touched."""
+        s = self._session
+        if s is None:
+            return [sorted(self.cliques[c]) for c in self.cliques]
+        cliques = {c: set(m) for c, m in self.cliques.items()}
+        for i, label in zip(s.indices, s.labels):
+            cliques.setdefault(label, set()).add(int(i))
+        return [sorted(cliques[c]) for c in cliques]
+
+    # ------------------------------------------------------------------ one-call forms: one append, one question
+    # what locate_tracks() aligns by when similarity_type is None (None here: the class's first device plane), and whether the
+    # listed score of identify() belongs to the pair (hit, new track) -- a symmetric class whose alignment of the transposed pair
+    # can score differently (EarlyFusion)
+    _locate_type = None
+    _locate_hit_first = False
+
+    def _align_kw(self, who, similarity_type):
+        """Per class with align_matches(): similarity_type checked (the class's own errors, before any library call) ->
+        the keywords its align methods take."""
+        raise NotImplementedError("%s: %s has no alignment (align_matches)" % (who, type(self).__name__))
+
+    def _align_tracks_setup(self, who, tracks, indices, similarity_type, how, paths):
+        kw = self._align_kw(who, similarity_type)
+        if paths and not hasattr(self, "align_match_paths"):
+            raise NotImplementedError("%s: %s returns no alignment paths" % (who, type(self).__name__))
+        checked, Q, _ = self._session_setup(who, tracks, None, how)
+        _align.check_matches(who, np.arange(self.N, self.N + Q), _align.check_indices(who, indices), self.N + Q)
+        return kw, checked, Q
+
+    def align_tracks(self, tracks, indices, similarity_type=None, **how):
+        """align_matches() for tracks the collection does NOT hold, in ONE append: tracks (and how: Serra09 / ChenFusion
+        raw=True) as identify_tracks() takes them, indices the (Q, k) array identify_tracks() / rerank_tracks() returned
+        for them (-1: an empty slot).  Row i, slot s is the alignment of the ORDERED pair (new track i, indices[i, s]):
+        exactly align_matches(s.indices, indices) inside `with self.appended(tracks) as s`.  similarity_type: ChenFusion
+        ('qmax', the default, or 'dmax') and EarlyFusion ('early' by default); for EarlyFusion read align_matches() on which
+        pair a listed score belongs to -- locate_tracks() aligns that one."""
+        kw, checked, Q = self._align_tracks_setup("align_tracks", tracks, indices, similarity_type, how, False)
+        with self._appended(checked, Q) as s:
+            return self.align_matches(s.indices, indices, **kw)
+
+    def align_track_paths(self, tracks, indices, similarity_type=None, **how):
+        """align_tracks() with the paths: exactly align_match_paths(s.indices, indices) inside a session."""
+        kw, checked, Q = self._align_tracks_setup("align_track_paths", tracks, indices, similarity_type, how, True)
+        with self._appended(checked, Q) as s:
+            return self.align_match_paths(s.indices, indices, **kw)
+
+    def locate_tracks(self, tracks, k=10, candidates=None, similarity_type=None, paths=False, **how):
+        """WHICH tracks of the collection are the covers of these new tracks, and WHERE do they match -- identify_tracks()
+        and align_tracks() in ONE append.  Returns (idx (Q, k) int32, score (Q, k) float32, al (Q, k) records) or, with
+        paths=True, (idx, score, al, paths) for ONE similarity type: the class's first device plane by default (ChenFusion
+        'qmax', Serra09 / SiMPle 'main'), EarlyFusion 'early'; a fused type has no alignment: ValueError.  candidates: as in
+        identify_tracks(), [0, N) by default.  idx / score are identify_tracks(tracks, k, candidates, [similarity_type])'s;
+        al (and paths) are align_tracks(tracks, idx, similarity_type)'s (align_track_paths'): row i, slot s is the ordered
+        pair (new track i, idx[i, s]), an empty slot a no-match row.
+        EarlyFusion alone differs: identify() of that symmetric class lists the score of the cell (min, max) of the two
+        indices, and the alignment of the transposed pair may score differently, so locate_tracks() aligns the pair the
+        listed score belongs to, (hit, new track) = (idx[i, s], N + i): in al and paths the QUERY side (q0, q1, q_span, path
+        column 0) is the hit and the REFERENCE side the new track, and al['score'] has the bits of score."""
+        who = "locate_tracks"
+        k = int(k)
+        if k < 1:
+            raise ValueError("%s: k must be >= 1 (got %d)" % (who, k))
+        t = (self._locate_type or self._identify_planes[0]) if similarity_type is None else similarity_type
+        kw = self._align_kw(who, t)
+        if paths and not hasattr(self, "align_match_paths"):
+            raise NotImplementedError("%s: %s returns no alignment paths" % (who, type(self).__name__))
+        checked, Q, _ = self._session_setup(who, tracks, None, how)
+        self._query_setup(who, [], [t])
+        cands = self._check_candidates(who, candidates, "tracks of the collection, indices")
+        if cands is None:
+            cands = np.arange(self.N, dtype=np.int32)
+        with self._appended(checked, Q) as s:
+            idx, score = self.identify(s.indices, k=k, candidates=cands, similarity_types=[t])[t]
+            if not self._locate_hit_first:
+                got = self.align_match_paths(s.indices, idx, **kw) if paths else (self.align_matches(s.indices, idx, **kw),)
+                return (idx, score) + tuple(got)
+            rows, slots = np.nonzero(idx >= 0)
+            pairs = np.stack([idx[rows, slots], s.indices[rows]], axis=1)
+            al = self._no_match_rows(idx.shape)
+            if not paths:
+                al[rows, slots] = self.align(pairs, **kw)
+                return idx, score, al
+            al[rows, slots], got = self.align_paths(pairs, **kw)
+            return idx, score, al, _align.scatter_paths(idx, rows, slots, got)
+
+    @refused_in_session
     def identify_tracks(self, tracks, k=10, candidates=None, similarity_types=None):
         """identify() for tracks the collection does NOT hold.  tracks: a list in the format of the class's injection
         method (Serra09 / ChenFusion: pooled (T, 12) f32 chroma, or with raw=True raw (T0, 12) chroma, pooled by
@@ -419,6 +600,7 @@ class CoverAlgorithm(object):
         planes = list(self._identify_planes)
         return {t: (np.ascontiguousarray(idx[:, planes.index(t)]), np.ascontiguousarray(score[:, planes.index(t)])) for t in types}
 
+    @refused_in_session
     def score_tracks(self, tracks, similarity_types=None):
         """query_rows() for tracks the collection does not hold: {type: (Q, N) float32}, the finished scores of every new
         track against every track of the collection, as identify_tracks() ranks them."""
@@ -440,8 +622,8 @@ class CoverAlgorithm(object):
         lists = shortlists_to_array(who, shortlists)
         if lists.shape[0] != Q:
             raise ValueError("%s: shortlists must hold one row per query (%d), got %d" % (who, Q, lists.shape[0]))
-        if lists.size and (lists.min() < -1 or lists.max() >= self.N):
-            raise ValueError("%s: shortlist entries must be track indices in [0, %d) or -1" % (who, self.N))
+        if lists.size and (lists.min() < -1 or lists.max() >= self._n_tracks()):
+            raise ValueError("%s: shortlist entries must be track indices in [0, %d) or -1" % (who, self._n_tracks()))
         srt = np.sort(lists, axis=1)
         dup = (srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)
         if dup.any():
@@ -488,6 +670,7 @@ class CoverAlgorithm(object):
         lists = first.identify(q, k=shortlist, similarity_types=[first_type])[first_type][0]
         return self.rerank(q, lists, k=k, similarity_types=similarity_types)
 
+    @refused_in_session
     def rerank_tracks(self, tracks, shortlists, k=10, similarity_types=None):
         """rerank() for tracks the collection does NOT hold (tracks as identify_tracks() takes them): they are appended
         behind the uploaded pool, asked about as queries N .. N + Q - 1 with their shortlists -- entries in [0, N) or
@@ -521,12 +704,16 @@ class CoverAlgorithm(object):
         info: a dict that receives {type: {"device_rows", "host_rows"}}.  report=True prints and appends the lines
         getEvalStatistics writes.  Fused types need the whole matrix: NotImplementedError.  Not a collective: under a
         process group every rank that calls it computes on its own GPU."""
-        q, types = self._query_setup("evaluate", np.arange(self.N) if queries is None else queries, similarity_types)
+        n = self._n_tracks()
+        q, types = self._query_setup("evaluate", np.arange(n) if queries is None else queries, similarity_types)
         if len(np.unique(q)) != len(q):
             raise ValueError("evaluate: queries must be distinct track indices")
+        if self._session is not None and self._session.labels is None:
+            raise ValueError("evaluate: the session was opened without labels; evaluate() needs a clique label for every "
+                             "appended track (appended(tracks, labels=...))")
         if not self.cliques and _dist.single():
             self.get_all_clique_ids()
-        plan = evaluate_plan([sorted(self.cliques[s]) for s in self.cliques], self.N, None if queries is None else q)
+        plan = evaluate_plan(self._cliques_now(), n, None if queries is None else q)
         ctx, algo, params, mode, col = self._query_call()
         pos, flag = ctx.query_ranks(algo, self._identify_symmetric, params, plan["rows"], plan["moff"], plan["mates"],
                                     posn=plan["posn"], col=col, col_mode=mode)
@@ -571,12 +758,14 @@ class CoverAlgorithm(object):
             self._rank_ctx = _lib.Context(int(os.environ.get("LOCAL_RANK", "0")) if dev is None else int(dev))
         return self._rank_ctx
 
+    @refused_in_session
     def top_matches(self, similarity_type, k=10, rows=None):
         """The k best other tracks of every track (or of `rows`) by Ds[similarity_type], best first, ties in index order:
         (idx (R, k) int32, score (R, k) float32) = np.argsort(-row, kind="stable")[:k] with the track itself removed,
         computed on the device (acx_topk_rows).  Fewer than k other tracks: the tail is index -1, score NaN."""
         return self._rank_context().topk_rows(self.Ds[similarity_type], k, rows=rows)
 
+    @refused_in_session
     def getEvalStatistics(self, similarity_type, topsidx=[1, 10, 100, 1000], engine=None):
         """MR, MRR, MDR, MAP and Top-k of one similarity matrix; appends a row to
         results_<shortname>_<name>.csv.  Same definitions as the reference (:205-290),

@@ -22,7 +22,7 @@ import numpy as np
 
 from .. import _lib
 from . import _align
-from .algorithm_template import CoverAlgorithm
+from .algorithm_template import CoverAlgorithm, refused_in_session
 from .similarity_fusion import doSimilarityFusion
 
 __all__ = ["EarlyFusion"]
@@ -90,6 +90,7 @@ class EarlyFusion(CoverAlgorithm):
                     mfcc=np.ascontiguousarray(np.asarray(feats["mfcc_htk"], dtype=np.float32).T),
                     onsets=np.asarray(feats["madmom_features"]["onsets"]).astype(np.int64))
 
+    @refused_in_session
     def set_block_features(self, tracks, labels=None):
         assert len(tracks) == self.N
         self.all_block_feats = dict(enumerate(tracks))
@@ -145,6 +146,7 @@ class EarlyFusion(CoverAlgorithm):
         return (self._context(), _lib.ALGO_EARLYFUSION, _lib.EfParams(float(self.kappa), int(self.K)),
                 ["mfccs", "ssms", "chromas", "early"])
 
+    @refused_in_session
     def similarity(self, idxs, do_plot=False):
         idxs = np.asarray(idxs).reshape(-1, 2)
         if len(idxs) == 0:
@@ -174,7 +176,7 @@ class EarlyFusion(CoverAlgorithm):
         pair whose k1 = int(K M / (M + N)) or k2 = K - k1 leaves np.partition no room is refused (NotImplementedError naming
         the pair).  `Ds` is not written: this score is not one of similarity_types.  Not a collective."""
         self._check_full_fusion("full_fusion")
-        pairs = _align.check_pairs("full_fusion", _align.check_indices("full_fusion", idxs), self.N)
+        pairs = _align.check_pairs("full_fusion", _align.check_indices("full_fusion", idxs), self._n_tracks())
         if len(pairs) == 0:
             return np.zeros(0, np.float32)
         return self._context().ef_crossfusion(pairs, self.kappa, self.K, self.niters, 1.0)
@@ -221,6 +223,18 @@ class EarlyFusion(CoverAlgorithm):
             raise ValueError("%s: unknown similarity type %r; similarity_type must be one of %s" % (who, similarity_type, list(self._identify_planes)))
         return self._identify_planes.index(similarity_type)
 
+    # locate_tracks(): 'early' unless asked otherwise, and the pair the listed score belongs to, (hit, new track)
+    _locate_type = "early"
+    _locate_hit_first = True
+
+    def _align_kw(self, who, similarity_type):
+        st = "early" if similarity_type is None else similarity_type
+        self._align_plane(who, st)
+        return {"similarity_type": st}
+
+    def _no_match_rows(self, shape):
+        return _align.no_match_rows(shape, self.ALIGN_DTYPE)
+
     def _align_pairs(self, pairs, plane, paths=None):
         """(K, 2) checked int32 pairs -> (K,) ALIGN_DTYPE.  paths: a list that receives the K (L_k, 2) int32 paths as well."""
         out = _align.no_match_rows(len(pairs), self.ALIGN_DTYPE)
@@ -251,7 +265,7 @@ class EarlyFusion(CoverAlgorithm):
         blocks: no clipping).  A pair without a match (score 0) has -1 everywhere.  Tracks of at most 1024 blocks.  `Ds` is
         not written; not a collective."""
         plane = self._align_plane("align", similarity_type)
-        return self._align_pairs(_align.check_pairs("align", _align.check_indices("align", idxs), self.N), plane)
+        return self._align_pairs(_align.check_pairs("align", _align.check_indices("align", idxs), self._n_tracks()), plane)
 
     def align_paths(self, idxs, similarity_type="early"):
         """align() and, for every pair, the PATH of its alignment: (al, paths).  al is exactly what align(idxs, similarity_type)
@@ -261,11 +275,11 @@ class EarlyFusion(CoverAlgorithm):
         empty (0, 2) path.  `Ds` is not written; not a collective."""
         plane = self._align_plane("align_paths", similarity_type)
         paths = []
-        al = self._align_pairs(_align.check_pairs("align_paths", _align.check_indices("align_paths", idxs), self.N), plane, paths)
+        al = self._align_pairs(_align.check_pairs("align_paths", _align.check_indices("align_paths", idxs), self._n_tracks()), plane, paths)
         return al, (paths if len(al) else [])
 
     def _check_align_matches(self, who, queries, indices):
-        return _align.check_matches(who, _align.check_indices(who, queries), _align.check_indices(who, indices), self.N)
+        return _align.check_matches(who, _align.check_indices(who, queries), _align.check_indices(who, indices), self._n_tracks())
 
     def align_matches(self, queries, indices, similarity_type="early"):
         """align() for the hits of identify() / rerank(): queries (Q,) track indices, indices the (Q, k) int array either
@@ -302,6 +316,7 @@ class EarlyFusion(CoverAlgorithm):
                 self._ctx.set_ef_fuse(eng["fuse"])
         return self._ctx
 
+    @refused_in_session
     def do_late_fusion(self):
         """SNF of 1/(1+D) over the three / four score matrices (earlyfusion_traile.py:200-206), on the
         GPU (acx_snf_fuse_dists; no device -> the call fails) of the rank that owns the matrices."""

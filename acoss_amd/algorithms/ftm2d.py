@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from .. import _lib
-from .algorithm_template import CoverAlgorithm
+from .algorithm_template import CoverAlgorithm, refused_in_session
 
 __all__ = ["FTM2D"]
 
@@ -90,6 +90,7 @@ class FTM2D(CoverAlgorithm):
         self.shingles[i] = self._aux_ctx.ftm2d_debug_track(raw["chroma"], raw["onsets"], self.PWR, self.WIN, self.C)["shingle"]
         return self.shingles[i]
 
+    @refused_in_session
     def set_features(self, shingles, labels=None):
         """Inject ready (12 WIN,) f64 shingles for every track (synthetic benchmarks)."""
         assert len(shingles) == self.N
@@ -133,6 +134,7 @@ class FTM2D(CoverAlgorithm):
     def _grid(self):
         return self._context(), _lib.ALGO_FTM2D, None, ["main"]
 
+    @refused_in_session
     def similarity(self, idxs):
         idxs = np.asarray(idxs).reshape(-1, 2)
         if len(idxs) == 0:

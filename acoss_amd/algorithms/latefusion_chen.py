@@ -11,7 +11,7 @@ import numpy as np
 from .. import _lib
 from . import _align
 from .rqa_serra09 import Serra09
-from .algorithm_template import CoverAlgorithm
+from .algorithm_template import CoverAlgorithm, refused_in_session
 from .similarity_fusion import doSimilarityFusion
 
 __all__ = ["ChenFusion"]
@@ -47,6 +47,7 @@ class ChenFusion(Serra09):
     def _grid(self):
         return self._context(), _lib.ALGO_CHENFUSION, self._params(), ["qmax", "dmax"]
 
+    @refused_in_session
     def similarity(self, idxs):
         idxs = np.asarray(idxs).reshape(-1, 2)
         if len(idxs) == 0:
@@ -72,6 +73,11 @@ class ChenFusion(Serra09):
         # (the Dmax alignment does not read the engine's dmax switch, as acx_chenfusion_pairs does not)
         return Serra09._check_align(self, who, idxs) if plane == 0 else _align.check_indices(who, idxs)
 
+    def _align_kw(self, who, similarity_type):
+        st = "qmax" if similarity_type is None else similarity_type
+        self._check_align(who, np.zeros((0, 2), np.int32), self._align_plane(who, st))
+        return {"similarity_type": st}
+
     def _align_call(self, pairs, want_paths, plane=0):
         if plane == 0:
             return Serra09._align_call(self, pairs, want_paths)
@@ -86,17 +92,17 @@ class ChenFusion(Serra09):
         and the start can be a gap cell whose neighbour (q0 - 1, r0) or (q0, r0 - 1) is the recurrence at which the alignment really
         begins: q_span / r_span can begin one embedded frame late.  'Late' has no alignment of its own: ValueError."""
         plane = self._align_plane("align", similarity_type)
-        return self._align_pairs(_align.check_pairs("align", self._check_align("align", idxs, plane), self.N), None, plane)
+        return self._align_pairs(_align.check_pairs("align", self._check_align("align", idxs, plane), self._n_tracks()), None, plane)
 
     def align_paths(self, idxs, similarity_type="qmax"):
         """Serra09.align_paths() for 'qmax' (the default) or 'dmax': (al, paths), al exactly what align(idxs, similarity_type) returns."""
         plane = self._align_plane("align_paths", similarity_type)
         paths = []
-        al = self._align_pairs(_align.check_pairs("align_paths", self._check_align("align_paths", idxs, plane), self.N), paths, plane)
+        al = self._align_pairs(_align.check_pairs("align_paths", self._check_align("align_paths", idxs, plane), self._n_tracks()), paths, plane)
         return al, (paths if len(al) else [])
 
     def _check_plane_matches(self, who, queries, indices, plane):
-        return _align.check_matches(who, self._check_align(who, queries, plane), self._check_align(who, indices, plane), self.N)
+        return _align.check_matches(who, self._check_align(who, queries, plane), self._check_align(who, indices, plane), self._n_tracks())
 
     def align_matches(self, queries, indices, similarity_type="qmax"):
         """Serra09.align_matches() for the hits identify() / rerank() list under similarity_type ('qmax', the default, or 'dmax')."""
@@ -115,6 +121,7 @@ class ChenFusion(Serra09):
         out[rows, slots] = self._align_pairs(pairs, got, plane)
         return out, _align.scatter_paths(idx, rows, slots, got)
 
+    @refused_in_session
     def normalize_by_length(self):
         """D[i, j] = sqrt(T_j) / D[i, j] (latefusion_chen.py:75-85): a DISTANCE, smaller =
         closer; unfilled cells (the diagonal) become +inf exactly as in the reference."""
@@ -128,6 +135,7 @@ class ChenFusion(Serra09):
                     j1 = min(self.N, j0 + 2048)
                     D[:, j0:j1] = (norm[None, j0:j1] / D[:, j0:j1]).astype(np.float32)
 
+    @refused_in_session
     def do_late_fusion(self):
         """SNF of the two distance matrices (latefusion_chen.py:87-91): Ds["Late"] = fused
         similarity; the two inputs are negated so that larger = closer everywhere.  Runs on the GPU

@@ -9,7 +9,7 @@ import numpy as np
 
 from .. import _lib
 from . import _align
-from .algorithm_template import CoverAlgorithm
+from .algorithm_template import CoverAlgorithm, refused_in_session
 
 __all__ = ["Serra09", "pool_median"]
 
@@ -82,6 +82,7 @@ class Serra09(CoverAlgorithm):
             self.all_feats[i] = pool_median(feats[self.chroma_type], self.downsample_fac)
         return self.all_feats[i]
 
+    @refused_in_session
     def set_pooled_features(self, tracks, labels=None):
         """Inject already-pooled (T_i, 12) chroma for every track (synthetic benchmarks,
         or features prepared elsewhere) instead of reading feature files."""
@@ -159,14 +160,17 @@ class Serra09(CoverAlgorithm):
         return 1, np.sqrt(self._pooled_lengths().astype(np.float64))
 
     # ------------------------------------------------------------------ tracks the collection does not hold
+    @refused_in_session
     def identify_tracks(self, tracks, k=10, candidates=None, similarity_types=None, raw=False):
         """CoverAlgorithm.identify_tracks; tracks: pooled (T, 12) f32 chroma as set_pooled_features takes it, or with
         raw=True raw (T0, 12) chroma, pooled by downsample_fac on the device (on the host by pool_median above 64)."""
         return self._identify_tracks(tracks, k, candidates, similarity_types, raw=raw)
 
+    @refused_in_session
     def score_tracks(self, tracks, similarity_types=None, raw=False):
         return self._score_tracks(tracks, similarity_types, raw=raw)
 
+    @refused_in_session
     def rerank_tracks(self, tracks, shortlists, k=10, similarity_types=None, raw=False):
         """CoverAlgorithm.rerank_tracks; tracks and raw as in identify_tracks."""
         return self._rerank_tracks(tracks, shortlists, k, similarity_types, raw=raw)
@@ -188,17 +192,36 @@ class Serra09(CoverAlgorithm):
             out.append(t)
         return out, bool(raw) and self.downsample_fac <= 64
 
-    def _append_tracks(self, ctx, checked):
+    def _append_pooled(self, ctx, checked):
+        """The append itself -> the pooled lengths of the new tracks (raw tracks: as the library pooled them)."""
         tracks, pool_on_device = checked
         offs = np.concatenate([[0], np.cumsum([t.shape[0] for t in tracks])]).astype(np.int64)
         frames = np.concatenate(tracks, axis=0)
         if pool_on_device:
-            lens = np.diff(ctx.pool_append_raw(frames, offs, self.downsample_fac))
-        else:
-            ctx.pool_append(frames, offs)
-            lens = np.diff(offs)
-        return np.sqrt(lens.astype(np.float64))
+            return np.diff(ctx.pool_append_raw(frames, offs, self.downsample_fac)).astype(np.int64)
+        ctx.pool_append(frames, offs)
+        return np.diff(offs)
 
+    def _append_tracks(self, ctx, checked):
+        return np.sqrt(self._append_pooled(ctx, checked).astype(np.float64))
+
+    def _append_session(self, ctx, checked, s):
+        """A session keeps the pooled lengths of its tracks as well: align()'s spans clip to them."""
+        s.pooled_len = self._append_pooled(ctx, checked)
+        s.col_tail = np.sqrt(s.pooled_len.astype(np.float64))
+
+    def _track_lengths(self):
+        """Pooled lengths of every track an index may name right now: the collection's, and a session's behind them."""
+        T = self._pooled_lengths()
+        return T if self._session is None else np.concatenate([T, self._session.pooled_len])
+
+    def _align_kw(self, who, similarity_type):
+        if similarity_type not in (None, "main"):
+            raise ValueError("%s: unknown similarity type %r; similarity_type must be one of %s" % (who, similarity_type, list(self._identify_planes)))
+        self._check_align(who, np.zeros((0, 2), np.int32))
+        return {}
+
+    @refused_in_session
     def similarity(self, idxs):
         idxs = np.asarray(idxs).reshape(-1, 2)
         if len(idxs) == 0:
@@ -237,7 +260,7 @@ class Serra09(CoverAlgorithm):
         for f in _lib.ALIGNMENT_DTYPE.names:
             out[f] = al[f]
         hit = al["q0"] >= 0
-        T = self._pooled_lengths()
+        T = self._track_lengths()
         tau, m = int(self.tau), int(self.m)
         for side, col in (("q", 0), ("r", 1)):
             last = T[pairs[:, col]] - 1
@@ -259,11 +282,11 @@ class Serra09(CoverAlgorithm):
 
     def _check_align_pairs(self, who, idxs):
         """align() / align_paths(): idxs -> (K, 2) int32, every check before the first library call."""
-        return _align.check_pairs(who, self._check_align(who, idxs), self.N)
+        return _align.check_pairs(who, self._check_align(who, idxs), self._n_tracks())
 
     def _check_align_matches(self, who, queries, indices):
         """align_matches() / align_match_paths(): -> (the (Q, k) index array, rows and slots of its filled slots, their (P, 2) pairs)."""
-        return _align.check_matches(who, self._check_align(who, queries), self._check_align(who, indices), self.N)
+        return _align.check_matches(who, self._check_align(who, queries), self._check_align(who, indices), self._n_tracks())
 
     def _no_match_rows(self, shape):
         return _align.no_match_rows(shape, self.ALIGN_DTYPE)
@@ -297,6 +320,7 @@ class Serra09(CoverAlgorithm):
         out[rows, slots] = self._align_pairs(pairs, got)
         return out, _align.scatter_paths(idx, rows, slots, got)
 
+    @refused_in_session
     def normalize_by_length(self):
         """Non-symmetric normalisation: D[i, j] /= sqrt(T_j), T_j the pooled length
         (rqa_serra09.py:71-83; the reciprocal of the paper's distance, so larger = closer)."""

@@ -11,7 +11,7 @@ import numpy as np
 
 from .. import _lib
 from . import _align
-from .algorithm_template import CoverAlgorithm
+from .algorithm_template import CoverAlgorithm, refused_in_session
 
 __all__ = ["Simple"]
 
@@ -57,6 +57,7 @@ class Simple(CoverAlgorithm):
             self.all_feats[i] = self.smooth(pooled)
         return self.all_feats[i]
 
+    @refused_in_session
     def set_features(self, feats, labels=None):
         """Inject ready (12, n_i) f64 features for every track (synthetic benchmarks)."""
         assert len(feats) == self.N
@@ -156,6 +157,11 @@ class Simple(CoverAlgorithm):
             out[f] = np.nan
         return out
 
+    def _align_kw(self, who, similarity_type):
+        if similarity_type not in (None, "main"):
+            raise ValueError("%s: unknown similarity type %r; similarity_type must be one of %s" % (who, similarity_type, list(self._identify_planes)))
+        return {}
+
     def align(self, idxs):
         """WHICH part of the reference did the query match?  idxs: (K, 2) (query, reference) track indices over the uploaded
         collection, ORDERED pairs as similarity() scores them.  Returns a (K,) structured array: score (the f64 value
@@ -166,7 +172,7 @@ class Simple(CoverAlgorithm):
         consecutive too (run_len of them; of several longest the first), with q_span = [q0, q1 + SSLEN - 1] and r_span =
         [r0, r1 + SSLEN - 1] in pooled frames.  A pair always has a match (run_len >= 1).  `Ds` is not written; not a
         collective."""
-        pairs = _align.check_pairs("align", _align.check_indices("align", idxs), self.N)
+        pairs = _align.check_pairs("align", _align.check_indices("align", idxs), self._n_tracks())
         if len(pairs) == 0:
             return np.zeros(0, self.ALIGN_DTYPE)
         return self._context().simple_profile(pairs, self.SSLEN)
@@ -176,7 +182,7 @@ class Simple(CoverAlgorithm):
         (ma_k,) f64 profile of pair k -- for every subsequence of the query (ma_k = n_query - SSLEN + 1 of them) the squared
         distance to its nearest subsequence of the reference -- and mpis[k] the (ma_k,) int32 index, which subsequence that is
         (the first of equally near ones).  -median(mps[k]) is al['score'][k]."""
-        pairs = _align.check_pairs("profile", _align.check_indices("profile", idxs), self.N)
+        pairs = _align.check_pairs("profile", _align.check_indices("profile", idxs), self._n_tracks())
         if len(pairs) == 0:
             return np.zeros(0, self.ALIGN_DTYPE), [], []
         al, off, mp, mpi = self._context().simple_profile(pairs, self.SSLEN, profiles=True)
@@ -188,12 +194,13 @@ class Simple(CoverAlgorithm):
         (queries[i], indices[i, s]) -- the pair identify() scored.  An empty slot comes back as a no-match row: -1 in every
         position, run_len 0, score and best_dist NaN."""
         who = "align_matches"
-        idx, rows, slots, pairs = _align.check_matches(who, _align.check_indices(who, queries), _align.check_indices(who, indices), self.N)
+        idx, rows, slots, pairs = _align.check_matches(who, _align.check_indices(who, queries), _align.check_indices(who, indices), self._n_tracks())
         out = self._no_match_rows(idx.shape)
         if len(pairs):
             out[rows, slots] = self._context().simple_profile(pairs, self.SSLEN)
         return out
 
+    @refused_in_session
     def similarity(self, idxs):
         idxs = np.asarray(idxs).reshape(-1, 2)
         if len(idxs) == 0:
