@@ -38,6 +38,7 @@ EXPORTS = [
     "acx_rank_columns", "acx_topk_rows",
     "acx_query_scores", "acx_query_topk", "acx_query_ranks", "acx_query_topk_lists",
     "acx_serra09_debug_bits", "acx_serra09_plan", "acx_serra09_family_name", "acx_serra09_fast_tail", "acx_serra09_fast_tail_launches",
+    "acx_serra09_plane_launches",
     "acx_pool_append", "acx_pool_append_raw", "acx_pool_append_f64", "acx_ef_pool_append", "acx_ftm2d_append_shingles",
     "acx_pool_truncate",
     "acx_serra09_align", "acx_qmax_locate_binary",
@@ -236,6 +237,8 @@ def load():
     L.acx_serra09_fast_tail.argtypes = [pp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     L.acx_serra09_fast_tail_launches.restype = ctypes.c_int64
     L.acx_serra09_fast_tail_launches.argtypes = []
+    L.acx_serra09_plane_launches.restype = ctypes.c_int64
+    L.acx_serra09_plane_launches.argtypes = []
     L.acx_serra09_embed_len.restype = ctypes.c_int32
     L.acx_serra09_embed_len.argtypes = [ctypes.c_int32, pp]
     L.acx_profile_enable.argtypes = [vp, ctypes.c_int]
@@ -464,6 +467,11 @@ def serra09_fast_tail(n_cells, role, params=None, debug=False):
 def serra09_fast_tail_launches():
     """acx_serra09_fast_tail_launches: band passes of this process that launched the product-path copy of the wide kernel so far."""
     return int(load().acx_serra09_fast_tail_launches())
+
+
+def serra09_plane_launches():
+    """acx_serra09_plane_launches: band passes of this process whose wide kernel read its column operands from the per-rotation planes."""
+    return int(load().acx_serra09_plane_launches())
 
 
 def serra09_family_name(family, m):

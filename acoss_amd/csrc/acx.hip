@@ -105,6 +105,10 @@ struct acx_ctx {
     DeviceBuffer<float> d_frames;
     DeviceBuffer<float> d_frot;       // rotated frame pool (band kernel MFMA operands), 36 floats per frame
     DeviceBuffer<_Float16> d_fh;      // the f16 operand pool of the opt-in f16x2 Gram (acx::FH halfs per frame), built on first use
+    // the wide class's operand planes (acx::planepool_kernel: 12 planes of acx::FPLANE floats per frame of the ACTIVE pool, each with
+    // the pool's slack on both sides), built on first use by ensure_planes and dropped whenever the pool changes
+    DeviceBuffer<float> d_planes;
+    int64_t plane_floats = 0;         // floats from one plane to the next
     DeviceBuffer<float> d_normtab;    // embedded norms per (track, rotation, frame) for normtab_m / normtab_span
     DeviceBuffer<int64_t> d_noff;
     int normtab_m = 0, normtab_span = -1;
@@ -373,7 +377,8 @@ bool launch_band(acx_ctx *c, int m, const PairDesc *dpd, const std::vector<PairD
 {
     const float *operands = p.arith == ACX_ARITH_F16X2 ? reinterpret_cast<const float *>(c->d_fh + POOL_SLACK * acx::FH) : c->d_frot + POOL_SLACK * acx::FROT;
     acx::BandLaunch L{c->stream, operands, c->active_toff(), c->d_normtab + POOL_SLACK, c->d_noff, c->d_scratch, c->d_thr,
-                      c->d_bits, p.kappa, p.pct_mode, p.inclusive, p.oti_target, 0};
+                      c->d_bits, p.kappa, p.pct_mode, p.inclusive, p.oti_target,
+                      c->d_planes ? c->d_planes + POOL_SLACK * acx::FPLANE : nullptr, c->plane_floats, 0};
     const int family = acx::serra09_band_family(cls, m, p.arith);
     bool ok = true;
     for (const acx::Serra09Run &r : acx::serra09_fast_tail_runs(p, family, role, write_d2 != 0, want_eps != 0, c->d_bits != nullptr, hpd, b0, b0 + B)) {
@@ -420,6 +425,7 @@ int ensure_tau(acx_ctx *c, int tau)
     ACX_HIP(c, c->d_toff.reset());
     ACX_HIP(c, c->d_frot.reset());
     ACX_HIP(c, c->d_fh.reset());
+    ACX_HIP(c, c->d_planes.reset());
     ACX_HIP(c, c->d_normtab.reset());
     ACX_HIP(c, c->d_noff.reset());
     const int n = c->n_tracks;
@@ -524,6 +530,34 @@ int ensure_f16pool(acx_ctx *c)
     return ACX_OK;
 }
 
+// The operand planes of the wide class (exact arithmetic): 12 x 48 B per frame of the ACTIVE pool on top of the rotated pool's 144 B,
+// so they are built on the first batch that launches that class, from the rotated pool, and only while ACX_PLANES is not 0.  A plane
+// carries the pool's slack on both sides (zeroed: what the edge tiles of the first and the last track read).  The distance between
+// planes depends on the pool's length, so every change of the pool (ensure_tau, append, truncate, a new upload) drops them and the
+// next wide batch builds them again.
+int ensure_planes(acx_ctx *c)
+{
+    if (c->d_planes || !acx::serra09_switches().planes) return ACX_OK;
+    const int64_t total = c->h_off[c->n_tracks];
+    const int64_t plane_floats = (std::max<int64_t>(1, total) + 2 * POOL_SLACK) * acx::FPLANE;
+    DeviceBuffer<float> planes;                        // the context's once it is complete
+    const hipError_t e = planes.grow((size_t)plane_floats * acx::NBIN);
+    if (e != hipSuccess)
+        return fail(c, ACX_ERR_NOMEM, std::string("serra09: the wide class's operand planes (576 bytes per pooled frame) do not fit the device: ") +
+                                          hipGetErrorString(e) + "; ACX_PLANES=0 runs that class from the rotated pool");
+    ACX_HIP(c, hipMemsetAsync(planes, 0, sizeof(float) * (size_t)plane_floats * acx::NBIN, c->stream));
+    if (total > 0) {
+        const int64_t nout = total * acx::FPLANE * acx::NBIN;
+        hipLaunchKernelGGL(acx::planepool_kernel, dim3((unsigned)std::min<int64_t>((nout + 255) / 256, 1 << 22)), dim3(256), 0, c->stream,
+                           c->d_frot + POOL_SLACK * acx::FROT, planes + POOL_SLACK * acx::FPLANE, total, plane_floats);
+        ACX_HIP(c, hipGetLastError());
+    }
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    c->d_planes = std::move(planes);
+    c->plane_floats = plane_floats;
+    return ACX_OK;
+}
+
 // The table of embedded norms depends on the pool and on (m, embedded length): built on first use.
 int ensure_normtab(acx_ctx *c, const acx_serra09_params &p)
 {
@@ -573,7 +607,9 @@ int64_t scratch_limit_bytes(const acx_ctx *c)
     if (c->scratch_limit > 0) return c->scratch_limit;
     const char *env = getenv("ACX_SCRATCH_GB");
     if (env && atof(env) > 0) return (int64_t)(atof(env) * (double)(1ull << 30));
-    return (int64_t)(0.40 * (double)c->total_mem);
+    // (the wide class's operand planes are the one derived pool larger than the features themselves -- 17 GB for 15 000 tracks of
+    // 2000 frames: the default share is taken of what they leave)
+    return (int64_t)(0.40 * (double)(c->total_mem - (int64_t)(c->d_planes.capacity() * sizeof(float))));
 }
 
 // Results of one batch come back through a pinned staging slot; two slots, so that the host packs
@@ -904,6 +940,11 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         const std::vector<int> &perm = S.perm;
         if (cls_begin[NC] > 0 && (rc = ensure_normtab(c, p)) != ACX_OK) return rc;
         if (cls_begin[NC] > 0 && p.arith == ACX_ARITH_F16X2 && (rc = ensure_f16pool(c)) != ACX_OK) return rc;
+        {   // a pass of the wide class (its row pass, or a column pass whose rows are of that class) in the exact arithmetic
+            bool wide = cls_begin[NC] > cls_begin[NC - 1];
+            for (int cl = 0; cl < NC; ++cl) wide = wide || key_begin[NC * cl + NC] > key_begin[NC * cl + NC - 1];
+            if (wide && p.arith == ACX_ARITH_EXACT && (rc = ensure_planes(c)) != ACX_OK) return rc;
+        }
         // (the band kernel reads its column thresholds 16 bytes at a time without a bounds check, up to
         // 64 x 32 floats behind a pair's column-threshold row: the arena carries that much slack)
         if ((rc = ensure(c, c->d_scratch, (size_t)std::max<int64_t>(used.scratch, 1))) != ACX_OK) return rc;
@@ -1725,6 +1766,7 @@ static void free_pool(acx_ctx *c)
     for (DeviceBuffer<float> *b : {&c->d_frames0, &c->d_frames, &c->d_frot, &c->d_normtab, &c->d_gch}) (void)b->reset();
     for (DeviceBuffer<int64_t> *b : {&c->d_toff0, &c->d_toff, &c->d_noff}) (void)b->reset();
     (void)c->d_fh.reset();
+    (void)c->d_planes.reset();
     c->normtab_m = 0; c->normtab_span = -1;
     c->pool_tau = 0;
     c->fh_base_n = -1;
@@ -4513,6 +4555,7 @@ static int s09_append_begin(acx_ctx *c, const char *who, const int64_t *rel, int
     quiesce(c);                                 // qstream / qstream2 may still hold sweeps that read the blocks replaced below
     const int dim = c->dim, tau = c->pool_tau;
     t.n0 = c->n_tracks; t.n1 = t.n0 + n_new;
+    ACX_HIP(c, c->d_planes.reset());            // (the planes' pitch is the pool's length: rebuilt by the next wide batch, ensure_planes)
     const int64_t total0 = c->h_off0[t.n0], total1 = total0 + rel[n_new];
     t.active = dim == acx::NBIN && tau >= 1 && c->d_frames0 && c->d_toff0;
     t.table = t.active && c->d_normtab && c->d_noff && c->normtab_m > 0;
@@ -4725,6 +4768,7 @@ static int s09_truncate(acx_ctx *c, int32_t n)
     c->h_off0.resize((size_t)n + 1);
     if (c->pool_tau >= 1) c->h_off.resize((size_t)n + 1);
     if (table) c->h_noff.resize((size_t)n + 1);
+    ACX_HIP(c, c->d_planes.reset());            // (ensure_planes rebuilds them for the shorter pool)
     // the f16x2 range check must still hold for the tracks that stay: it does while they contain the ones it was made for
     if (c->d_fh && (c->fh_base_n < 0 || n < c->fh_base_n)) {
         ACX_HIP(c, c->d_fh.reset());
@@ -5024,6 +5068,7 @@ int acx_serra09_plan(const int64_t *lengths, int32_t n_tracks, const int32_t *pa
 const char *acx_serra09_family_name(int32_t family, int32_t m) { return acx::serra09_family_name(family, m); }
 
 int64_t acx_serra09_fast_tail_launches(void) { return (int64_t)acx::fast_tail_launches(); }
+int64_t acx_serra09_plane_launches(void) { return (int64_t)acx::plane_launches(); }
 
 int acx_serra09_fast_tail(const acx_serra09_params *params, int32_t n_cells, int32_t role, int32_t debug)
 {

@@ -17,6 +17,7 @@ namespace acx {
 namespace {
 
 std::atomic<long long> g_fast_tail_launches{0};      // band passes of this process that took the FAST copy (fast_tail_launches)
+std::atomic<long long> g_plane_launches{0};          // ... that read their column operands from the per-rotation planes (plane_launches)
 
 // `family`: the plan's answer for the pass's size class (serra09_band_family, serra09_plan.hpp -- the class limits, the choice
 // per stack size and arithmetic, and ACX_BAND2 live there); this switch only maps it onto the instantiations.
@@ -24,9 +25,14 @@ template <int M>
 bool launch_band_m(const BandLaunch &L, const PairDesc *dpd, int B, int maxRows, int family, int role, int write_d2, int want_eps, int arith)
 {
     const dim3 grid((maxRows + BAND - 1) / BAND, B, 1);
-#define ACX_BAND_K(V4_, R_, W_, A_, F_) hipLaunchKernelGGL((band_kernel<M, V4_, R_, W_, A_, F_>), grid, dim3(BAND_THREADS), 0, L.stream, \
+#define ACX_BAND_KP(V4_, R_, W_, A_, F_, P_) hipLaunchKernelGGL((band_kernel<M, V4_, R_, W_, A_, F_, P_>), grid, dim3(BAND_THREADS), 0, L.stream, \
                                                   L.frot, L.toff, L.normtab, L.noff, dpd, L.scratch, L.thr, L.bits, L.kappa, \
-                                                  L.pct_mode, L.inclusive, L.oti_target, want_eps)
+                                                  L.pct_mode, L.inclusive, L.oti_target, want_eps, L.planes, L.plane_floats)
+    // the wide class of the exact arithmetic takes its column operands from the per-rotation planes when the context built them
+#define ACX_BAND_K(V4_, R_, W_, A_, F_) do { if constexpr (V4_ == 8 && A_ == 0) { \
+                                                 if (L.planes) { ACX_BAND_KP(V4_, R_, W_, A_, F_, true); g_plane_launches.fetch_add(1, std::memory_order_relaxed); } \
+                                                 else ACX_BAND_KP(V4_, R_, W_, A_, F_, false); } \
+                                             else ACX_BAND_KP(V4_, R_, W_, A_, F_, false); } while (0)
     // (the variant that also writes D2 exists for the row pass only: the debug entry point)
 #define ACX_BAND_A(V4_, A_) do { if (role) ACX_BAND_K(V4_, 1, false, A_, false); else if (write_d2) ACX_BAND_K(V4_, 0, true, A_, false); else ACX_BAND_K(V4_, 0, false, A_, false); } while (0)
     // the product-path tail (band_row_tail's FAST copy): the plan found its conditions to hold for the pass and for every pair of the
@@ -60,6 +66,7 @@ bool launch_band_m(const BandLaunch &L, const PairDesc *dpd, int B, int maxRows,
 #undef ACX_BAND
 #undef ACX_BAND_A
 #undef ACX_BAND_K
+#undef ACX_BAND_KP
 }
 
 }  // namespace
@@ -83,6 +90,7 @@ bool launch_band_kernel(const BandLaunch &L, int m, const PairDesc *dpd, int B, 
 }
 
 long long fast_tail_launches() { return g_fast_tail_launches.load(std::memory_order_relaxed); }
+long long plane_launches() { return g_plane_launches.load(std::memory_order_relaxed); }
 
 }  // namespace acx
 

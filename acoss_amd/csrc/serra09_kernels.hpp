@@ -7,6 +7,7 @@
 //   K0  oti_kernel        12-bin optimal transposition index per pair
 //   K0b normtab_kernel    embedded norms per (track, rotation, frame), once per (pool, m)
 //       rotpool_kernel    rotated frame pool (MFMA operands in chain order), once per upload
+//       planepool_kernel  the wide class's column operands as one plane per rotation, on the first wide batch of a pool
 //   K1' band_kernel       role 1 then role 0: frame Gram on the matrix cores
 //                         (v_mfma_f32_16x16x4_f32, K = 12 = 3 k-steps, exact f32 == fmaf chain),
 //                         diagonal doubling-tree window sums, exact kappa-percentile thresholds
@@ -939,6 +940,29 @@ static __global__ void rotpool_kernel(const float *__restrict__ pool, float *__r
     }
 }
 
+// Per-rotation operand planes for the wide class of the exact arithmetic (built on first use from the rotated pool): plane
+// rot = 0..11 holds, per frame, the four triples that the lanes lk = 0..3 of a pair of rotation rot load -- (r, cls) of
+// c0 = (lk - rot) mod 12 -- in lk order, 48 bytes per frame, frames consecutive.  One buffer_load_dwordx3 of a wave (16 frames x
+// 4 lk) then covers 768 contiguous bytes = 6 cache lines; in the rotated pool the same 768 bytes lie in 16 frames of 144 bytes
+// = 18 lines.  planes[rot * plane_floats + f * FPLANE + 3 lk + kb] = frame[f][(4 kb + lk - rot) mod 12].
+constexpr int FPLANE = NBIN;       // floats per frame of one plane (4 lk x 3 kb)
+__host__ __device__ constexpr int plane_src(int rot, int e)     // rotated-pool float (of FROT) behind float e = 3 lk + kb of a plane's frame
+{
+    const int lk = e / 3, kb = e - 3 * lk;
+    const int c0 = (lk - rot + NBIN) % NBIN;
+    return (c0 >> 2) * NBIN + (c0 & 3) * 3 + kb;
+}
+static __global__ void planepool_kernel(const float *__restrict__ frot, float *__restrict__ planes, int64_t nframes, int64_t plane_floats)
+{
+    const int64_t per = nframes * FPLANE, total = per * NBIN, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {     // one output float each
+        const int rot = (int)(idx / per);
+        const int64_t w = idx - rot * per, f = w / FPLANE;
+        const int e = (int)(w - f * FPLANE);
+        planes[rot * plane_floats + w] = frot[f * FROT + plane_src(rot, e)];
+    }
+}
+
 // The same pool for the opt-in f16x2 Gram (acx_serra09_params.arith = ACX_ARITH_F16X2): every bin value as TWO fp16 terms
 // x = h1 + h2 (h1 = fp16(x), h2 = fp16(x - h1): 22-23 significant bits, fp16 subnormals are kept by the matrix pipe), and per
 // (frame, r, cls) the 8 halfs [h1(b0) h1(b1) h1(b2) h2(b0) h2(b1) h2(b2) h1(b0) h1(b1)], b_j = cls + 4 ((r + j) mod 3): exactly the
@@ -990,6 +1014,8 @@ struct BandLaunch {
     unsigned long long *bits;
     float kappa;
     int pct_mode, inclusive, oti_target;
+    const float *planes;            // the wide class's operand planes (planepool_kernel; frame 0 of plane 0), or nullptr: the rotated pool
+    int64_t plane_floats;           // floats from one plane to the next
     int fast_tail;                  // the pass may take the product-path tail (serra09_fast_tail_runs, serra09_plan.hpp: every pair of this launch qualifies)
 };
 // role 1 / 0 over B pairs of one size class; false when the stack size m has no instantiation of `family`
@@ -1000,6 +1026,8 @@ bool launch_band_kernel(const BandLaunch &L, int m, const struct PairDesc *dpd, 
                         int write_d2, int want_eps, int arith);
 // band passes of this process that launched the FAST copy of the wide kernel so far (tests observe the dispatch through it)
 long long fast_tail_launches();
+// ... that launched a wide kernel reading its column operands from the per-rotation planes (planepool_kernel)
+long long plane_launches();
 
 // development builds only (scripts/ab_build.sh ablN -DACX_ABL=N): the band kernel stops behind stage N -- 1 sweep, 2 exchange +
 // row read, 3 selection, 4 eps / threshold -- so that instruction counters (rocprofv3 --pmc SQ_INSTS_*) can be read per stage
@@ -1315,7 +1343,8 @@ constexpr int band_waves_per_simd(int m, int v4, int arith = 0) { return (v4 <= 
 // FAST: the product-path tail (band_row_tail), wide class and exact arithmetic only.
 // (Reading the pair's descriptor again behind the second barrier instead of keeping it across the sweep removes the last SGPR spills
 // of the row pass and was a measured negative -- profiles/r07_wide_tail.md.)
-template <int M, int V4, int ROLE, bool WD2 = false, int ARITH = 0, bool FAST = false>
+// PLANES: the column-frame operands come from the per-rotation planes (planepool_kernel), wide class and exact arithmetic only.
+template <int M, int V4, int ROLE, bool WD2 = false, int ARITH = 0, bool FAST = false, bool PLANES = false>
 __global__ __launch_bounds__(BAND_THREADS, band_waves_per_simd(M, V4, ARITH)) void band_kernel(const float *__restrict__ frot,
                                                             const int64_t *__restrict__ toff,
                                                             const float *__restrict__ normtab,
@@ -1324,9 +1353,11 @@ __global__ __launch_bounds__(BAND_THREADS, band_waves_per_simd(M, V4, ARITH)) vo
                                                             float *__restrict__ scratch,
                                                             float *__restrict__ thr,
                                                             unsigned long long *__restrict__ bits,
-                                                            float kappa, int pct_mode, int inclusive, int oti_target, int want_eps)
+                                                            float kappa, int pct_mode, int inclusive, int oti_target, int want_eps,
+                                                            const float *__restrict__ planes, int64_t plane_floats)
 {
     constexpr bool write_d2 = WD2;
+    static_assert(!PLANES || (V4 == 8 && ARITH == 0), "the operand planes exist for the wide class of the exact arithmetic");
     static_assert(!FAST || (V4 == 8 && ARITH == 0 && !WD2), "the product-path tail exists for the wide class of the exact arithmetic");
     using G = BandGeom<M, V4, ARITH>;
     constexpr int role = ROLE;           // 1: rows = reference frames (column thresholds); 0: rows = query frames
@@ -1340,11 +1371,25 @@ __global__ __launch_bounds__(BAND_THREADS, band_waves_per_simd(M, V4, ARITH)) vo
     __shared__ __attribute__((aligned(4096))) float smem[LDS_FLOATS];
 
     const int bid_x = blockIdx.x, bid_y = blockIdx.y;
-    const PairDesc P = pd[bid_y];
+    // The wide class of the exact arithmetic (8-row workgroups, 249 of them per 2000-frame pair) asks for its scalars in TWO dependent
+    // round trips: the arguments in one clause, then every descriptor field that the operand and norm addresses need in one clause,
+    // and only then the exit test.  Left to itself the compiler reads the descriptor's address, then Mq / Mr, takes the exit, and
+    // requests the other arguments and fields behind it: three round trips before the first operand load (-1.2 % of the kernel,
+    // profiles/r08_operand_planes.md).
+    // (The statements are empty and NOT volatile -- a volatile one counts as a store, and every load behind it would leave the scalar
+    // cache's path -- and order by data: the descriptor's index passes through the first together with the arguments, the exit
+    // test's bound through the second together with the fields.  The tail's fields are requested behind the exit and not waited
+    // for before the first tile: taking them here as well costs the row pass five VGPRs and a spill.)
+    constexpr bool EAGER_HEAD = V4 == 8 && ARITH == 0;
+    int pd_idx = bid_y;
+    if constexpr (EAGER_HEAD) asm("" : "+s"(pd_idx) : "s"(frot), "s"(normtab), "s"(oti_target), "s"(planes), "s"(plane_floats));
+    const PairDesc P = pd[pd_idx];
     const int MA = role ? P.Mr : P.Mq, MB = role ? P.Mq : P.Mr;
     const int TA = role ? P.Tr : P.Tq, TB = role ? P.Tq : P.Tr;
     const int i0 = bid_x * BAND;
-    if (i0 >= MA) return;     // block-uniform
+    int ma_exit = MA;
+    if constexpr (EAGER_HEAD) asm("" : "+s"(ma_exit) : "s"(P.Tq), "s"(P.Tr), "s"(P.Mq), "s"(P.Mr), "s"(P.oti), "s"(P.fq), "s"(P.fr), "s"(P.nq), "s"(P.nr));
+    if (i0 >= ma_exit) return;     // block-uniform
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // SGPR: everything derived from it is scalar
     const bool rows_are_ref = role == 1;
@@ -1373,6 +1418,8 @@ __global__ __launch_bounds__(BAND_THREADS, band_waves_per_simd(M, V4, ARITH)) vo
     // frame, 8 halfs per (r, cls) entry) -- `frot` then points at that pool.  PB = bytes per frame, offA / offB = byte offset of the
     // lane's (r, cls) entry inside a frame.
     constexpr unsigned PB = ARITH ? (unsigned)FH * 2u : (unsigned)FROT * 4u;
+    // PLANES: the column frames come from plane rotb, PBB = 48 bytes per frame, the lane's triple at 12 lk
+    constexpr unsigned PBB = PLANES ? (unsigned)FPLANE * 4u : PB;
     const unsigned offA = ARITH ? (unsigned)(((c0a >> 2) * 4 + (c0a & 3)) * 16) : (unsigned)(((c0a >> 2) * NBIN + (c0a & 3) * 3) * 4);
     const unsigned offB = ARITH ? (unsigned)(((c0b >> 2) * 4 + (c0b & 3)) * 16) : (unsigned)(((c0b >> 2) * NBIN + (c0b & 3) * 3) * 4);
     const char *pool_b = reinterpret_cast<const char *>(frot);
@@ -1380,9 +1427,10 @@ __global__ __launch_bounds__(BAND_THREADS, band_waves_per_simd(M, V4, ARITH)) vo
     // column-frame operands go through a buffer descriptor: scalar base + scalar offset (the tile) + one 32-bit
     // lane offset -- no 64-bit VALU address arithmetic in the tile loop.  The descriptor starts 8 frames before
     // the track (a tile reaches back 7 frames: pool slack / the neighbouring track), no range check.
+    const char *col_b = PLANES ? reinterpret_cast<const char *>(planes + rotb * plane_floats) : pool_b;
     const __amdgpu_buffer_rsrc_t rsB =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(pool_b + ((role ? P.fq : P.fr) - 8) * (int64_t)PB), 0, -1, 0x00020000);
-    const unsigned voffB = offB + (unsigned)lr * PB;              // this lane's byte offset inside a 16-frame block
+        __builtin_amdgcn_make_buffer_rsrc((void *)(col_b + ((role ? P.fq : P.fr) - 8) * (int64_t)PBB), 0, -1, 0x00020000);
+    const unsigned voffB = (PLANES ? 12u * (unsigned)lk : offB) + (unsigned)lr * PBB;     // this lane's byte offset inside a 16-frame block
     const char *frb = pool_b + (role ? P.fq : P.fr) * (int64_t)PB + offB;   // (short-row classes: per-lane pointer, plain global loads)
     typedef float f32x3 __attribute__((ext_vector_type(3)));
     typedef f32x3 f32x3_u __attribute__((aligned(4)));
@@ -1413,7 +1461,13 @@ __global__ __launch_bounds__(BAND_THREADS, band_waves_per_simd(M, V4, ARITH)) vo
     }
     float xrow[BAND];
 #pragma unroll
-    for (int a = 0; a < BAND; ++a) xrow[a] = (i0 + a < MA) ? nrow[i0 + a] : INF;       // rows past the matrix: +inf cells
+    for (int a = 0; a < BAND; ++a) {
+        // rows past the matrix: +inf cells.  (wide class, exact arithmetic: read from the table without the test -- i0 < MA, so these
+        // are the first of the NGUARD +inf entries behind the rotation's row: the same bits in one scalar load, no branch per row)
+        if constexpr (EAGER_HEAD) xrow[a] = nrow[i0 + a];
+        else xrow[a] = (i0 + a < MA) ? nrow[i0 + a] : INF;
+    }
+    static_assert(BAND - 1 <= NGUARD, "the band's rows past the matrix read guard entries");
     float *Sw = smem + wave * (G::AROWS * G::SP);               // this wave's Gram tile, [row frame][column frame]
     const PctPos pp = role ? P.pos_q : P.pos_r;                 // rows of MB cells (worked out on the host)
 #ifdef ACX_TIMING
@@ -1434,11 +1488,11 @@ __global__ __launch_bounds__(BAND_THREADS, band_waves_per_simd(M, V4, ARITH)) vo
         const int base = 64 * tile - (BAND - 1);
         if constexpr (V4 >= 8) {
             // wide rows (four tiles per wave): buffer loads, scalar tile offset + 32-bit lane offset (-1.7 % at T = 2000)
-            const unsigned so = (unsigned)(base + 8) * PB;                        // wave-uniform byte offset of the tile
+            const unsigned so = (unsigned)(base + 8) * PBB;                       // wave-uniform byte offset of the tile
 #pragma unroll
             for (int tb = tb0; tb < G::NCT; ++tb) {
                 if constexpr (ARITH == 0) {
-                    const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(rsB, voffB, so + 16u * PB * tb, 0);
+                    const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(rsB, voffB, so + 16u * PBB * tb, 0);
                     bv[tb][0] = v.x; bv[tb][1] = v.y; bv[tb][2] = v.z;
                 } else {
                     const u32x4v v = __builtin_amdgcn_raw_buffer_load_b128(rsB, voffB, so + 16u * PB * tb, 0);
@@ -1667,6 +1721,8 @@ __global__ __launch_bounds__(BAND_THREADS, band_waves_per_simd(M, V4, ARITH)) vo
     static_assert(NV == 8 || NV == 16 || NV == 32, "row owners hold 8, 16 or 32 consecutive positions");
     {
         const int wl = lane + 4 * (lane / NV);           // position 64 T + lane -> float T * (LPT * LNP) + wl
+        // (a copy of these stores for cpw == NSTEP, where tile_of(st) = NSTEP wave + st needs no select: measured +0.2 .. 0.6 %,
+        // profiles/r08_operand_planes.md)
 #pragma unroll
         for (int st = 0; st < NSTEP; ++st) {
             float *dst = smem + tile_of(st) * (LPT * LNP) + wl;

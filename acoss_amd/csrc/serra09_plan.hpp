@@ -65,16 +65,17 @@ inline int serra09_row_class(int M)
 //                         24-position class onto band_kernel<M, 4>; also the two-row classes onto band_kernel<M, 2>
 //   ACX_QMAX_MULTI=0      one wave per pair in every sweep
 //   ACX_QMAX_STREAM=0     the sweeps run on the main stream
+//   ACX_PLANES=0          the wide class reads its column operands from the rotated pool: no per-rotation planes (576 B per frame)
 struct Serra09Switches {
     int band2;          // band2 classes kept: 3 (default) .. 0
-    bool multi, qstream;
+    bool multi, qstream, planes;
 };
 inline const Serra09Switches &serra09_switches()
 {
     static const Serra09Switches s = [] {
         auto off = [](const char *name) { const char *e = getenv(name); return e && e[0] == '0'; };
         const char *b = getenv("ACX_BAND2");
-        return Serra09Switches{(b && b[0] >= '0' && b[0] <= '2') ? b[0] - '0' : 3, !off("ACX_QMAX_MULTI"), !off("ACX_QMAX_STREAM")};
+        return Serra09Switches{(b && b[0] >= '0' && b[0] <= '2') ? b[0] - '0' : 3, !off("ACX_QMAX_MULTI"), !off("ACX_QMAX_STREAM"), !off("ACX_PLANES")};
     }();
     return s;
 }

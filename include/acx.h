@@ -357,6 +357,10 @@ int acx_serra09_fast_tail(const acx_serra09_params *params, int32_t n_cells, int
  * so far (a process-wide counter: every context, every thread) -- what the launcher did, as opposed to what the predicate above
  * says it would do.  The tests observe the dispatch through it; nothing else should depend on it. */
 int64_t acx_serra09_fast_tail_launches(void);
+/* The same kind of counter for the wide class's per-rotation operand planes: band passes of this process whose kernel read its
+ * column operands from the planes (built on the first wide batch of the exact arithmetic, 576 bytes per pooled frame; the
+ * environment switch ACX_PLANES=0, read once per process, keeps the class on the rotated pool and this counter where it is). */
+int64_t acx_serra09_plane_launches(void);
 
 /* ---- SiMPle (similarity matrix profile) ---------------------------------- */
 
