@@ -50,6 +50,7 @@ EXPORTS = [
     "acx_snf_debug_stages", "acx_snf_debug_update",
     "acx_ef_crossfusion_pairs", "acx_ef_crossfusion_debug", "acx_crossfusion_matrices", "acx_xsel_binary_sw",
     "acx_ef_download_pool",
+    "acx_ef_align_long", "acx_sw_align_long_binary",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -300,6 +301,8 @@ def load():
     L.acx_ef_align.argtypes = [vp, ip, ctypes.c_int64, ep, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
     L.acx_sw_align_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    L.acx_ef_align_long.argtypes = L.acx_ef_align.argtypes
+    L.acx_sw_align_long_binary.argtypes = L.acx_sw_align_binary.argtypes
     epp = ctypes.POINTER(EfPrepParams)
     L.acx_ef_block_features.argtypes = [vp, fp, ctypes.c_int64, fp, ctypes.c_int64, ctypes.c_int32, lp, ctypes.c_int32, epp,
                                         fp, fp, fp, dp]
@@ -1002,6 +1005,62 @@ class Context(object):
         cells = np.zeros((max(int(cap), 1), 2), np.int32)
         self._check(self._L.acx_sw_align_binary(self._h, bp, B.shape[0], B.shape[1], out.ctypes.data, cells.ctypes.data, int(cap),
                                                 ctypes.byref(n)))
+        return out, cells[:n.value].copy()
+
+    def ef_has_long_track(self, pairs):
+        """Whether a track of the list has more than 1024 blocks, so that its alignments take ef_align_long.  A pool this object
+        did not see uploaded has no block counts here: True -- ef_align_long serves every list, a short one exactly as ef_align
+        does, and says so itself when it needs a `cap` it cannot work out."""
+        nb = getattr(self, "ef_blocks", None)
+        if nb is None:
+            return True
+        nb = np.asarray(nb, dtype=np.int64)
+        idx = np.unique(np.asarray(pairs, dtype=np.int64))
+        idx = idx[(idx >= 0) & (idx < len(nb))]            # (an index out of range is the library's to refuse)
+        return bool(len(idx)) and int(nb[idx].max()) > 1024
+
+    def ef_align_long(self, pairs, kappa=0.1, K=10, plane=3, paths=False, cap=None):
+        """ef_align() for tracks of ANY length (acx_ef_align_long): the same arguments and return values.  A list without a track
+        of more than 1024 blocks runs as ef_align() runs it; any other list takes the float path, and the strip-wise kernel aligns
+        all its pairs.  cap: default the sum of min(M_k, N_k) from the block counts of the pool this object uploaded; for a pool it
+        did not see uploaded, cap must be given."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        p = EfParams(float(kappa), int(K))
+        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
+        if not paths:
+            self._check(self._L.acx_ef_align_long(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), out.ctypes.data, None, None, 0))
+            return out
+        if cap is None:
+            nb = getattr(self, "ef_blocks", None)
+            if nb is None:
+                raise ValueError("ef_align_long: this object did not see the pool uploaded and cannot bound the paths: cap must be given")
+            # (a list the library refuses -- an index out of range -- is refused before it looks at cap)
+            nb = np.asarray(nb, dtype=np.int64)
+            ok = np.all((pairs >= 0) & (pairs < len(nb)), axis=1) if len(pairs) else np.zeros(0, bool)
+            cap = int(np.minimum(nb[pairs[ok, 0]], nb[pairs[ok, 1]]).sum())
+        off = np.zeros(len(pairs) + 1, np.int64)
+        cells = np.zeros((max(int(cap), 1), 2), np.int32)
+        self._check(self._L.acx_ef_align_long(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), out.ctypes.data,
+                                              off.ctypes.data, cells.ctypes.data, int(cap)))
+        return out, off, cells[:off[-1]].copy()
+
+    def sw_align_long_binary(self, B, paths=True, cap=None):
+        """sw_align_binary() on a plot of ANY size (acx_sw_align_long_binary): the strip-wise kernel of ef_align_long's float path,
+        whatever the size.  cap: default min(M, N)."""
+        B = np.ascontiguousarray(B, dtype=np.uint8)
+        if B.ndim != 2:
+            raise ValueError("sw_align_long_binary: B must be (M, N), got shape %s" % (B.shape,))
+        out = np.zeros(1, ALIGNMENT_DTYPE)
+        bp = B.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+        if not paths:
+            self._check(self._L.acx_sw_align_long_binary(self._h, bp, B.shape[0], B.shape[1], out.ctypes.data, None, 0, None))
+            return out
+        if cap is None:
+            cap = min(B.shape)
+        n = ctypes.c_int64(0)
+        cells = np.zeros((max(int(cap), 1), 2), np.int32)
+        self._check(self._L.acx_sw_align_long_binary(self._h, bp, B.shape[0], B.shape[1], out.ctypes.data, cells.ctypes.data, int(cap),
+                                                     ctypes.byref(n)))
         return out, cells[:n.value].copy()
 
     def sw_binary(self, B):

@@ -240,10 +240,14 @@ class EarlyFusion(CoverAlgorithm):
         out = _align.no_match_rows(len(pairs), self.ALIGN_DTYPE)
         if len(pairs) == 0:
             return out
+        ctx = self._context()
+        # a listed track of more than 1024 blocks: the strip-wise alignment of the float path (ef_align_long); else ef_align, with the
+        # launches it always had
+        fn = ctx.ef_align_long if ctx.ef_has_long_track(pairs) else ctx.ef_align
         if paths is None:
-            al = self._context().ef_align(pairs, self.kappa, self.K, plane)
+            al = fn(pairs, self.kappa, self.K, plane)
         else:
-            al, off, cells = self._context().ef_align(pairs, self.kappa, self.K, plane, paths=True)
+            al, off, cells = fn(pairs, self.kappa, self.K, plane, paths=True)
             paths.extend(cells[off[k]:off[k + 1]] for k in range(len(pairs)))
         for f in _lib.ALIGNMENT_DTYPE.names:
             out[f] = al[f]
@@ -262,8 +266,8 @@ class EarlyFusion(CoverAlgorithm):
         the row-major first maximum of the score matrix, the start is found by following the recursion's predecessors back
         (include/acx.h acx_ef_align) -- and q_span / r_span, [first, last] inclusive in BEATS of each track: block b starts
         at beat b and spans `blocksize` beats, so a span is [q0, q1 + blocksize - 1] (a track of n beats has n - blocksize
-        blocks: no clipping).  A pair without a match (score 0) has -1 everywhere.  Tracks of at most 1024 blocks.  `Ds` is
-        not written; not a collective."""
+        blocks: no clipping).  A pair without a match (score 0) has -1 everywhere.  `Ds` is not written; not a
+        collective."""
         plane = self._align_plane("align", similarity_type)
         return self._align_pairs(_align.check_pairs("align", _align.check_indices("align", idxs), self._n_tracks()), plane)
 

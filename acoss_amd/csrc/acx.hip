@@ -54,7 +54,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_DLOCATE, KS_DPATH, KS_SIMPLEPROF, KS_XFMEANS, KS_XFAFFINITY, KS_XFSNF, KS_XFX, KS_XFSELECT, KS_EFALIGN, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_DLOCATE, KS_DPATH, KS_SIMPLEPROF, KS_XFMEANS, KS_XFAFFINITY, KS_XFSNF, KS_XFX, KS_XFSELECT, KS_EFALIGNLONG, KS_EFALIGN, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -221,6 +221,7 @@ struct acx_ctx {
                              {"dmax_locate_kernel", 0, 0, 0}, {"dmax_path_kernel", 0, 0, 0},
                              {"simple_profile_kernel", 0, 0, 0}, {"xf_means_kernel", 0, 0, 0}, {"xf_affinity_kernels", 0, 0, 0},
                              {"xf_snf_kernels", 0, 0, 0}, {"xf_x_kernel", 0, 0, 0}, {"xf_select_kernel", 0, 0, 0},
+                             {"ef_align_long_kernel", 0, 0, 0},
                              {"ef_align_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
@@ -1108,7 +1109,9 @@ struct EfDebug { float *csm, *fused; int32_t *oti; int64_t which = 0; const EfSt
 
 // acx_ef_align: what a run adds to the scores -- for every pair the record of ONE plane (0..3: mfccs, ssms, chromas, early) and,
 // when `paths` is given (K vectors), the cells (q, r) of its path from start to end.  Pair k of the run's list -> al[k], (*paths)[k].
-struct EfAlign { int plane; acx_alignment *al; std::vector<std::vector<int32_t>> *paths; };
+// any_length (acx_ef_align_long): a list with a track of more than 1024 blocks is not refused -- its batches take the float path, and
+// ef_align_long_kernel reads the plot off the float matrices.
+struct EfAlign { int plane; acx_alignment *al; std::vector<std::vector<int32_t>> *paths; bool any_length; };
 
 // pinned host staging + device copy of `n` score destinations idx[0 .. n)
 static int stage_idx(acx_ctx *c, const int64_t *idx, int64_t n)
@@ -1385,7 +1388,8 @@ static int64_t ef_align_wave_cap()
     return v >= 1 && v < 65535 ? v : 65535;
 }
 
-static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, int64_t k0, int64_t budget, const EfAlign &aln, const float *scores)
+static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, int64_t k0, int64_t budget, const EfAlign &aln, const float *scores,
+                              bool float_path)
 {
     const int B = (int)pd.size();
     const int64_t wave_cap = ef_align_wave_cap();
@@ -1398,7 +1402,7 @@ static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, in
         const int b0 = b;
         for (; b < B && (int64_t)jobs.size() < wave_cap; ++b) {
             const acx::EfPair &d = pd[(size_t)b];
-            const int64_t w = acx::ef_align_dir_words(d.M, d.pitchC);
+            const int64_t w = float_path ? acx::ef_align_long_dir_words(d.M, d.N) : acx::ef_align_dir_words(d.M, d.pitchC);
             if (!jobs.empty() && 4 * (words + w) > budget) break;
             acx::EfAlignJob j;
             j.pair = b; j.max_cells = std::min(d.M, d.N); j.dir_off = words; j.cell_off = ncell;
@@ -1414,7 +1418,12 @@ static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, in
         if ((rc = ensure(c, c->d_efjob, (size_t)nb)) != ACX_OK) return rc;
         if ((rc = ensure(c, c->d_efres, nres)) != ACX_OK) return rc;
         ACX_HIP(c, hipMemcpyAsync(c->d_efjob, jobs.data(), sizeof(acx::EfAlignJob) * nb, hipMemcpyHostToDevice, c->stream));
-        {
+        if (float_path) {
+            // (the batch keeps no bitmaps: the plot from its float matrices, thresholds and tie columns; the pairs' record areas are
+            // free behind the batch's Smith-Waterman launches on this stream)
+            ProfScope ps(c, KS_EFALIGNLONG, area);
+            hipLaunchKernelGGL(acx::ef_align_long_kernel, dim3(nb), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_scratch, c->d_thr, c->d_efdir, c->d_efres, aln.plane);
+        } else {
             ProfScope ps(c, KS_EFALIGN, area);
             hipLaunchKernelGGL(acx::ef_align_kernel, dim3(nb), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, aln.plane);
         }
@@ -1506,7 +1515,7 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
     const bool keep_f = !bits_path || (dbg && dbg->fused);
     if (aln && (ext_matrix || dd || !out))          // (no export gets here: acx_ef_align passes the pool's pairs and a host buffer)
         return fail(c, ACX_ERR_STATE, "ef_align: the alignment option takes pairs of the pool and scores on the host");
-    if (aln && !bits_path)
+    if (aln && !bits_path && !aln->any_length)
         return fail(c, ACX_ERR_UNSUPPORTED, "ef_align: alignment needs the bit path: at most 1024 blocks");
     if (dbg && dbg->stats && dbg->stats->bits && !bits_path)
         return fail(c, ACX_ERR_INVALID, "ef debug: a track of more than 1024 blocks takes the float path, which leaves no bitmaps (pass a null bitmap pointer)");
@@ -1705,8 +1714,9 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
         } else {
             ACX_HIP(c, hipMemcpyAsync(out + 4 * k0, c->d_out, sizeof(float) * 4 * B, hipMemcpyDeviceToHost, c->stream));
         }
-        // acx_ef_align: the records (and paths) of this batch, while d_efbits still holds it
-        if (aln && (rc = run_ef_align_batch(c, pd, k0, limit / 2, *aln, out + 4 * k0)) != ACX_OK) return rc;
+        // acx_ef_align / acx_ef_align_long: the records (and paths) of this batch, while d_efbits (the float path: d_scratch and d_thr)
+        // still holds it
+        if (aln && (rc = run_ef_align_batch(c, pd, k0, limit / 2, *aln, out + 4 * k0, !bits_path)) != ACX_OK) return rc;
         const double t_s = now();
         ht[2] += t_s - t_b;
         // the next batch's descriptors and rectangles, while the device works on this one
@@ -3266,7 +3276,7 @@ static int sw_bits_binary_impl(acx_ctx *c, const uint8_t *B, int32_t M, int32_t 
 static const char *const EF_ALIGN_TOO_LONG = "alignment needs the bit path: at most 1024 blocks";
 
 static int ef_align_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params *params, int32_t plane, acx_alignment *out,
-                         int64_t *path_off, int32_t *cells, int64_t cap)
+                         int64_t *path_off, int32_t *cells, int64_t cap, bool any_length)
 {
     if (K < 0 || (K > 0 && (!pairs || !out)) || !params || cap < 0) return fail(c, ACX_ERR_INVALID, "ef_align: bad argument");
     if ((path_off == nullptr) != (cells == nullptr))
@@ -3286,7 +3296,7 @@ static int ef_align_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_
     for (int64_t k = 0; k < K; ++k) {
         const int64_t M = c->h_efoff[pairs[2 * k] + 1] - c->h_efoff[pairs[2 * k]], N = c->h_efoff[pairs[2 * k + 1] + 1] - c->h_efoff[pairs[2 * k + 1]];
         if (M < 1 || N < 1) return fail(c, ACX_ERR_SHORT, "earlyfusion: track without blocks (pair " + std::to_string(k) + ")");
-        if (M > acx::EF_MAXNB || N > acx::EF_MAXNB)
+        if (!any_length && (M > acx::EF_MAXNB || N > acx::EF_MAXNB))
             return fail(c, ACX_ERR_UNSUPPORTED, std::string("ef_align: ") + EF_ALIGN_TOO_LONG + " (pair " + std::to_string(k) + ": " + std::to_string(M) + " x " + std::to_string(N) + ")");
         bound += std::min(M, N);
     }
@@ -3304,7 +3314,7 @@ static int ef_align_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_
     std::vector<float> so((size_t)4 * K);
     std::vector<acx_alignment> sal((size_t)K);
     std::vector<std::vector<int32_t>> paths(path_off ? (size_t)K : 0);
-    const EfAlign aln{plane, sal.data(), path_off ? &paths : nullptr};
+    const EfAlign aln{plane, sal.data(), path_off ? &paths : nullptr, any_length};
     const int rc = run_ef(c, sp.data(), K, *params, so.data(), nullptr, nullptr, 0, 0, nullptr, &aln);
     if (rc != ACX_OK) return rc;
     for (int64_t k = 0; k < K; ++k) out[order[(size_t)k]] = sal[(size_t)k];
@@ -3326,7 +3336,18 @@ int acx_ef_align(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_param
                  int64_t *path_off, int32_t *cells, int64_t cap)
 {
     if (!c) return ACX_ERR_INVALID;
-    const int rc = ef_align_impl(c, pairs, K, params, plane, out, path_off, cells, cap);
+    const int rc = ef_align_impl(c, pairs, K, params, plane, out, path_off, cells, cap, false);
+    if (rc != ACX_OK) quiesce(c);                // nothing of a failed call stays in flight behind its error code
+    return rc;
+}
+
+// The same for tracks of any length: a list without a track of more than 1024 blocks runs exactly as above; any
+// other takes the float path, and ef_align_long_kernel aligns ALL its pairs.
+int acx_ef_align_long(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params *params, int32_t plane, acx_alignment *out,
+                      int64_t *path_off, int32_t *cells, int64_t cap)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const int rc = ef_align_impl(c, pairs, K, params, plane, out, path_off, cells, cap, true);
     if (rc != ACX_OK) quiesce(c);                // nothing of a failed call stays in flight behind its error code
     return rc;
 }
@@ -3390,6 +3411,70 @@ int acx_sw_align_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, acx_
 {
     if (!c) return ACX_ERR_INVALID;
     const int rc = sw_align_binary_impl(c, B, M, N, out, cells, cap, n_cells);
+    if (rc != ACX_OK) quiesce(c);                // the queued copies read this call's host buffers: none stays in flight behind an error
+    return rc;
+}
+
+// ef_align_long_kernel alone on a caller's plot of ANY size, set up as acx_sw_binary sets up sw_long_kernel: the plot as a 0 / 1 float
+// matrix (1 - B), thresholds 0, every tie counted.
+static int sw_align_long_binary_impl(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out, int32_t *cells, int64_t cap, int64_t *n_cells)
+{
+    if (!B || !out || M < 1 || N < 1 || cap < 0 || (cells != nullptr) != (n_cells != nullptr)) return fail(c, ACX_ERR_INVALID, "sw_align_long_binary: bad argument");
+    if (cells && cap < std::min(M, N))
+        return fail(c, ACX_ERR_INVALID, "sw_align_long_binary: cap " + std::to_string(cap) + " is too small: " + std::to_string(std::min(M, N)) +
+                                            " cells required (min(M, N))");
+    if (n_cells) *n_cells = 0;
+    std::vector<float> Cm((size_t)M * N);
+    for (size_t k = 0; k < Cm.size(); ++k) {
+        if (B[k] > 1) return fail(c, ACX_ERR_INVALID, "sw_align_long_binary: non-binary elements found in input");
+        Cm[k] = B[k] ? 0.0f : 1.0f;         // B = [C <= threshold] with threshold 0
+    }
+    acx::EfPair d;
+    d.q = d.r = 0; d.M = M; d.N = N; d.oti = 0; d.pitchC = round_up(N, 64); d.pitchT = round_up(M, 64); d.kbin = 0;
+    d.ctN = 0; d.pad = 0; d.offB = 0; d.offC = 0; d.offS = 0;
+    acx::EfAlignJob job;
+    job.pair = 0; job.max_cells = std::min(M, N); job.dir_off = 0; job.cell_off = 0;
+    const size_t nres = (size_t)acx::EFA_REC + 2 * (size_t)job.max_cells;
+    std::vector<int32_t> res(nres);
+    int rc;
+    ACX_HIP(c, hipSetDevice(c->device));
+    if ((rc = ensure(c, c->d_scratch, (size_t)M * d.pitchC)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_thr, (size_t)acx::ef_s_total(d))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efpd, (size_t)1)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efjob, (size_t)1)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efdir, (size_t)acx::ef_align_long_dir_words(M, N))) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efres, nres)) != ACX_OK) return rc;
+    ACX_HIP(c, hipMemcpyAsync(c->d_efpd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(c->d_efjob, &job, sizeof(job), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpy2DAsync(c->d_scratch, sizeof(float) * d.pitchC, Cm.data(), sizeof(float) * N, sizeof(float) * N, M,
+                                hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemsetAsync(c->d_thr, 0, sizeof(float) * M, c->stream));
+    ACX_HIP(c, hipMemsetAsync(c->d_thr + acx::ef_jcut_off(d, 0), 0x7f, sizeof(int) * M, c->stream));   // every tie counts
+    hipLaunchKernelGGL(acx::ef_align_long_kernel, dim3(1), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_scratch, c->d_thr, c->d_efdir, c->d_efres, 0);
+    ACX_HIP(c, hipGetLastError());
+    ACX_HIP(c, hipMemcpyAsync(res.data(), c->d_efres, sizeof(int32_t) * (cells ? nres : (size_t)acx::EFA_REC), hipMemcpyDeviceToHost, c->stream));
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    acx_alignment a;
+    memcpy(&a.score, res.data(), sizeof(float));
+    a.q0 = res[1]; a.r0 = res[2]; a.q1 = res[3]; a.r1 = res[4];
+    const int n = res[5];
+    if (n < 0 || n > job.max_cells || (a.score > 0.0f) != (n >= 1))
+        return fail(c, ACX_ERR_STATE, "sw_align_long_binary: the traceback returned " + std::to_string(n) + " cells");
+    *out = a;
+    if (cells) {
+        const int32_t *src = res.data() + acx::EFA_REC;             // the traceback wrote the cells end first
+        if (n >= 1 && (src[0] != a.q1 || src[1] != a.r1 || src[2 * (n - 1)] != a.q0 || src[2 * (n - 1) + 1] != a.r0))
+            return fail(c, ACX_ERR_STATE, "sw_align_long_binary: the traceback does not run from the reported end to the reported start");
+        for (int e = 0; e < n; ++e) { cells[2 * (size_t)e] = src[2 * (n - 1 - e)]; cells[2 * (size_t)e + 1] = src[2 * (n - 1 - e) + 1]; }
+        *n_cells = n;
+    }
+    return ACX_OK;
+}
+
+int acx_sw_align_long_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out, int32_t *cells, int64_t cap, int64_t *n_cells)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const int rc = sw_align_long_binary_impl(c, B, M, N, out, cells, cap, n_cells);
     if (rc != ACX_OK) quiesce(c);                // the queued copies read this call's host buffers: none stays in flight behind an error
     return rc;
 }

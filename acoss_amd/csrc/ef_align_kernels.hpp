@@ -168,4 +168,169 @@ __global__ __launch_bounds__(64) void ef_align_kernel(const EfPair *__restrict__
     }
 }
 
+// The same alignment on the FLOAT path, for plots of any size: a batch that holds a track of more than
+// EF_MAXNB blocks keeps no bitmaps, so a cell of the plot is what sw_long_kernel::load_b reads off the pair's float matrix, its row's
+// threshold t and tie column jcut.  One wave per job again, a lane owns 16 contiguous columns, and a plot of N columns runs in
+// ceil(N / 1024) STRIPS as sw_long_kernel's does: for every row lane 63 leaves U[i][c-1], U[i][c-2] (c: the next strip's first column)
+// in the pair's record area -- sw_long_kernel's own records, free once the batch's score launch has finished on the stream -- double
+// buffered by strip, and lane 0 of the next strip reads them in place of its left neighbour.  A strip ends in __threadfence().
+//   direction plane   M rows of 64 * nstrips words (word j / 16 of a row holds column j); EVERY word of rows 2 .. M-2 is written in
+//                     every strip, zeros included: the traceback stops on a 0, and the plane is reused between calls
+//   running best      T, row and column as three integers per lane (T passes 16 bits and rows pass 1023 here; a pair may hold more
+//                     than 2^32 cells): replaced by a larger T, or by an equal T in an EARLIER row -- strip 2 meets row 3 after
+//                     strip 1 met row 300 -- and within a row by the smaller column; the wave reduction compares T, row, column
+//   traceback         lane 0, behind the last strip's fence, bounded by min(M, N) cells and by the counted rectangle
+constexpr int EFA_STRIP = 64 * EFA_CPL;           // columns of one strip
+
+__host__ __device__ __forceinline__ int ef_align_long_strips(int N) { return (N + EFA_STRIP - 1) / EFA_STRIP; }
+__host__ __device__ __forceinline__ int64_t ef_align_long_dir_words(int M, int N) { return (int64_t)M * 64 * ef_align_long_strips(N); }
+
+__global__ __launch_bounds__(64) void ef_align_long_kernel(const EfPair *__restrict__ pd, const EfAlignJob *__restrict__ jobs,
+                                                           const float *__restrict__ scratch, float *stat, unsigned *dir,
+                                                           int32_t *__restrict__ res, int plane)
+{
+    int32_t *cells = res + (size_t)EFA_REC * gridDim.x;              // the result block of ef_align_kernel
+    constexpr int CPL = EFA_CPL;
+    const int lane = threadIdx.x;
+    const EfAlignJob job = jobs[blockIdx.x];
+    const EfPair P = pd[job.pair];
+    const int M = P.M, N = P.N, pitch = P.pitchC;
+    acx_alignment a;
+    a.score = 0.0f; a.q0 = a.r0 = a.q1 = a.r1 = -1;
+    int n = 0;
+    if (M >= 4 && N >= 4) {
+        const float *C = scratch + (plane < 3 ? ef_c_off(P, plane) : ef_f_off(P));
+        const float *thr = stat + P.offS + plane * ef_s_stride(P);
+        const int *jcut = reinterpret_cast<const int *>(thr) + ef_jcut_off(P, plane);
+        unsigned long long *rec = reinterpret_cast<unsigned long long *>(stat + P.offS + ef_rec_off(P, plane));     // int2 {U[c-1], U[c-2]}
+        const int nstrips = ef_align_long_strips(N);
+        const int64_t wpr = 64 * (int64_t)nstrips;
+        unsigned *my_dir = dir + job.dir_off;
+        int bT = 0, bRow = 0, bCol = 0;                              // the lane's running best (bT == 0: none yet)
+        for (int st = 0; st < nstrips; ++st) {
+            const int j0 = st * EFA_STRIP + CPL * lane;
+            const unsigned long long *rin = rec + (size_t)((st + 1) & 1) * P.pitchT;
+            unsigned long long *rout = rec + (size_t)(st & 1) * P.pitchT;
+            const bool more = st + 1 < nstrips, seam = st > 0;
+            // the plot's row as 16 bits: sw_long_kernel::load_b.  j >= N reads no memory and is 0: such a column reads column N - 1
+            // in its place, and `have` drops its bit
+            const int nv = min(max(N - j0, 0), CPL);
+            const unsigned have = (1u << nv) - 1u;
+            auto load_b = [&](int row) -> unsigned {
+                const int r = row < M ? row : M - 1;                 // (rows past the last one: a valid address, never used)
+                const float t = thr[r];
+                const int jc = jcut[r];
+                const float *Cr = C + (size_t)r * pitch;
+                float d[CPL];
+#pragma unroll
+                for (int e = 0; e < CPL; ++e) d[e] = Cr[(unsigned)min(j0 + e, N - 1)];
+                // ties: bit e = column j0 + e <= jcut.  jcut is clamped into [j0 - 1, j0 + 15] BEFORE the subtraction: the selection
+                // kernels write 0x7fffffff for a row whose every tie counts, and jcut - j0 + 1 would overflow in lane 0 of strip 0
+                const int ec = min(max(jc, j0 - 1), j0 + CPL - 1) - j0 + 1;
+                const unsigned tie = (1u << ec) - 1u;
+                unsigned w = 0u;
+#pragma unroll
+                for (int e = 0; e < CPL; ++e) w |= (d[e] < t ? 1u : (d[e] == t ? ((tie >> e) & 1u) : 0u)) << e;
+                return w & have;
+            };
+            // a record: the two values as one 8-byte word, so that a row's record is one store and one load (relaxed, agent scope:
+            // the other lanes' stores of the strip before, read through memory behind its fence)
+            auto put_rec = [&](int row, int u1, int u2) {
+                if (more && lane == 63) rout[row] = (unsigned long long)(unsigned)u1 | ((unsigned long long)(unsigned)u2 << 32);
+            };
+            auto get_rec = [&](int row) -> unsigned long long {
+                return seam ? __hip_atomic_load(rin + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+            };
+            // valid: bit e = column j0 + e is counted (2 <= j <= N - 2); T is forced to 0 elsewhere, as in ef_align_kernel
+            unsigned valid = 0u;
+#pragma unroll
+            for (int e = 0; e < CPL; ++e) valid |= (j0 + e >= 2 && j0 + e <= N - 2) ? (1u << e) : 0u;
+            int U1[CPL], U2[CPL];                                    // rows i-1, i-2
+            {
+                const unsigned w0 = load_b(0), w1 = load_b(1);       // rows 0 and 1: T = 0, U = delta(B)
+#pragma unroll
+                for (int e = 0; e < CPL; ++e) {
+                    U2[e] = ((w0 >> e) & 1u) ? 0 : -7;
+                    U1[e] = ((w1 >> e) & 1u) ? 0 : -7;
+                }
+                put_rec(0, U2[CPL - 1], U2[CPL - 2]);
+                put_rec(1, U1[CPL - 1], U1[CPL - 2]);
+            }
+            unsigned long long recB = get_rec(0), recA = get_rec(1); // records of rows i-2, i-1
+            // one row: UA = row i-1, UB = row i-2 (overwritten with row i, from the right: cell e reads UB[e - 1] before it is replaced)
+            auto dp_row = [&](int i, unsigned wb, int (&UA)[CPL], int (&UB)[CPL]) {
+                int a1 = lane_prev_i(UA[CPL - 1]), a2 = lane_prev_i(UA[CPL - 2]), b1 = lane_prev_i(UB[CPL - 1]);
+                if (lane == 0) { a1 = (int)(unsigned)recA; a2 = (int)(unsigned)(recA >> 32); b1 = (int)(unsigned)recB; }
+                unsigned codes = 0u;
+                int rT = 0, rE = 0;                                  // the row's maximum in this lane, at its smallest column
+#pragma unroll
+                for (int e = CPL - 1; e >= 0; --e) {
+                    const int c2 = (e >= 1) ? UA[e - 1] : a1;                             // (i-1, j-1)
+                    const int c3 = (e >= 1) ? UB[e - 1] : b1;                             // (i-2, j-1)
+                    const int c4 = (e >= 2) ? UA[e - 2] : (e == 1 ? a1 : a2);             // (i-1, j-2)
+                    int mx = c2;
+                    unsigned code = 1u;
+                    if (c3 > mx) { mx = c3; code = 2u; }
+                    if (c4 > mx) { mx = c4; code = 3u; }
+                    const int bit = (int)((wb >> e) & 1u);
+                    int t = mx - 10 + 20 * bit;
+                    t = max(t, 0) & __builtin_amdgcn_sbfe((int)valid, e, 1);              // (sbfe of one bit: 0 or -1)
+                    UB[e] = t - 7 + 7 * bit;
+                    codes |= (t > 0 ? code : 0u) << (2 * e);
+                    if (t >= rT) { rT = t; rE = e; }                 // (from the right: an equal value further left wins)
+                }
+                my_dir[i * wpr + 64 * st + lane] = codes;
+                put_rec(i, UB[CPL - 1], UB[CPL - 2]);
+                if (rT > bT || (rT == bT && rT > 0 && i < bRow)) { bT = rT; bRow = i; bCol = j0 + rE; }
+            };
+            unsigned wb = load_b(2);
+            for (int i = 2; i <= M - 2; ++i) {
+                const unsigned wn = load_b(i + 1);                   // the next row and its record, ahead of their use
+                const unsigned long long recN = get_rec(i);
+                dp_row(i, wb, U1, U2);
+#pragma unroll
+                for (int e = 0; e < CPL; ++e) { const int u = U1[e]; U1[e] = U2[e]; U2[e] = u; }
+                wb = wn;
+                recB = recA; recA = recN;
+            }
+            __threadfence();                                         // the next strip reads this one's records, the traceback every strip's codes
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const int oT = __shfl_xor(bT, o, 64), oR = __shfl_xor(bRow, o, 64), oC = __shfl_xor(bCol, o, 64);
+            if (oT > bT || (oT == bT && (oR < bRow || (oR == bRow && oC < bCol)))) { bT = oT; bRow = oR; bCol = oC; }
+        }
+        if (lane == 0 && bT > 0) {
+            int y = bRow, x = bCol;
+            int32_t *dst = cells + 2 * job.cell_off;
+            // as in ef_align_kernel: every step lowers row and column, a predecessor outside rows [2, M-2] x columns [2, N-2] ends
+            // the path, and the bounds keep a wrong code from reading outside the plane or writing outside the job's cells
+            auto code_at = [&](int yy, int xx) -> unsigned {
+                const unsigned wd = __hip_atomic_load(my_dir + yy * wpr + (xx >> 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return (wd >> (2 * (xx & 15))) & 3u;
+            };
+            if (y >= 2 && y <= M - 2 && x >= 2 && x <= N - 2) {
+                unsigned code = code_at(y, x);
+                while (code != 0u && n < job.max_cells) {
+                    dst[2 * n] = y; dst[2 * n + 1] = x;
+                    ++n;
+                    const int py = y - (code == 2u ? 2 : 1), px = x - (code == 3u ? 2 : 1);
+                    if (py < 2 || px < 2) break;                     // rows / columns 0, 1: T = 0
+                    code = code_at(py, px);                          // 0: T == 0 there, (y, x) was the start
+                    if (code != 0u) { y = py; x = px; }
+                }
+            }
+            a.score = (float)bT / 10.0f;                             // sw_long_kernel's expression: the same bits
+            if (n > 0) {
+                a.q1 = bRow; a.r1 = bCol;
+                a.q0 = y; a.r0 = x;
+            }
+        }
+    }
+    if (lane == 0) {
+        int32_t *out = res + (size_t)EFA_REC * blockIdx.x;
+        out[0] = __float_as_int(a.score); out[1] = a.q0; out[2] = a.r0; out[3] = a.q1; out[4] = a.r1; out[5] = n;
+    }
+}
+
 }  // namespace acx

@@ -654,6 +654,23 @@ int acx_ef_align(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_ef_par
 int acx_sw_align_binary(acx_ctx *ctx, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out, int32_t *cells, int64_t cap,
                         int64_t *n_cells);
 
+/* acx_ef_align for tracks of ANY length (ABI 4, additive): the same arguments, contract, cap rule, sort and output order, without the
+ * refusal of tracks of more than 1024 blocks.  A list without such a track runs exactly as acx_ef_align runs it.  Any other list takes
+ * the float path of acx_earlyfusion_pairs, and the alignment of ALL its pairs, short ones included, is read off the float matrices,
+ * row thresholds and tie columns that path leaves on the device, in strips of 1024 columns: B[i][j] = C[i][j] < t_i, or
+ * C[i][j] == t_i and j <= jcut_i (the plot the scores of that path are taken from; out[k].score has their bits).  The whole list is
+ * checked before the first launch: the codes and messages of acx_ef_align minus the length refusal; a pair that does not fit the
+ * scratch limit -> ACX_ERR_NOMEM, as in acx_earlyfusion_pairs.  A failed call leaves nothing in flight, and a valid call after it
+ * succeeds. */
+int acx_ef_align_long(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_ef_params *params, int32_t plane /* 0..3 */,
+                      acx_alignment *out /* K */, int64_t *path_off /* K + 1 or NULL */, int32_t *cells /* cap x 2 or NULL */, int64_t cap);
+
+/* The strip-wise DP alone on a caller's binary (M, N) uint8 plot of any size (tests), set up as acx_sw_binary sets up its long case
+ * (the plot as a 0 / 1 float matrix, thresholds 0).  The arguments of acx_sw_align_binary; every size, 4 x 4 included, runs the kernel
+ * of acx_ef_align_long's float path.  A value above 1 in B: ACX_ERR_INVALID. */
+int acx_sw_align_long_binary(acx_ctx *ctx, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out, int32_t *cells, int64_t cap,
+                             int64_t *n_cells);
+
 /* ---- FTM2D (2D Fourier transform magnitudes, Bertin-Mahieux & Ellis) ------ */
 
 /* Constructor arguments of FTM2D (ftm2d.py:23): defaults PWR 1.96, WIN 75, C 5. */
