@@ -959,53 +959,75 @@ class Context(object):
                                                ctypes.byref(sc)))
         return bits, float(sc.value)
 
+    def _align_list(self, export, pairs, extra, paths, cap, cap_rule):
+        """A list call of the align family: export(ctx, pairs, K, *extra, out, path_off, cells, cap).  The records alone (NULL path
+        pointers), or with paths=True (records, offsets (K + 1,) int64, cells (offsets[-1], 2) int32); cap None: cap_rule(pairs)."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
+        if paths and cap is None:
+            cap = cap_rule(pairs)                   # (may refuse: before the library is touched)
+        head = (self._h, _iptr(pairs), len(pairs)) + tuple(extra) + (out.ctypes.data,)
+        if not paths:
+            self._check(getattr(self._L, export)(*head, None, None, 0))
+            return out
+        off = np.zeros(len(pairs) + 1, np.int64)
+        cells = np.zeros((max(int(cap), 1), 2), np.int32)
+        self._check(getattr(self._L, export)(*head, off.ctypes.data, cells.ctypes.data, int(cap)))
+        return out, off, cells[:off[-1]].copy()
+
+    def _align_plot(self, export, P, what, extra=(), paths=True, cap=None, n_first=False):
+        """A plot call of the align family on a binary (M, N) plot `P` (`what`: its name in the method's signature):
+        export(ctx, P, M, N, *extra, out, ...).  paths None: the export takes the record alone; False: NULL path pointers and cap 0;
+        True: (record (1,), cells (L, 2) int32), the tail being (n_cells, cells, cap) with n_first, else (cells, cap, n_cells).
+        cap: default min(M, N)."""
+        P = np.ascontiguousarray(P, dtype=np.uint8)
+        if P.ndim != 2:
+            raise ValueError("%s: %s must be (M, N), got shape %s" % (export[len("acx_"):], what, P.shape,))
+        out = np.zeros(1, ALIGNMENT_DTYPE)
+        args = (self._h, P.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), P.shape[0], P.shape[1]) + tuple(extra) + (out.ctypes.data,)
+        fn = getattr(self._L, export)
+        if not paths:
+            self._check(fn(*args) if paths is None else fn(*args, None, 0, None))
+            return out
+        if cap is None:
+            cap = min(P.shape)
+        n = ctypes.c_int64(0)
+        cells = np.zeros((max(int(cap), 1), 2), np.int32)
+        tail = (ctypes.byref(n), cells.ctypes.data, int(cap)) if n_first else (cells.ctypes.data, int(cap), ctypes.byref(n))
+        self._check(fn(*(args + tail)))
+        return out, cells[:n.value].copy()
+
+    def _ef_cap(self, pairs, unseen):
+        """The sum of min(M_k, N_k) over the list from the block counts of the pool this object uploaded; unseen(pairs) for a pool it
+        did not see.  (A list the library refuses -- an index out of range -- is refused before it looks at cap.)"""
+        nb = getattr(self, "ef_blocks", None)
+        if nb is None:
+            return unseen(pairs)
+        nb = np.asarray(nb, dtype=np.int64)
+        ok = np.all((pairs >= 0) & (pairs < len(nb)), axis=1) if len(pairs) else np.zeros(0, bool)
+        return int(np.minimum(nb[pairs[ok, 0]], nb[pairs[ok, 1]]).sum())
+
+    def _serra09_cap(self, pairs, p):
+        """The sum of min(Mq_k, Mr_k) over the list (acx_serra09_embed_len); an index out of range counts nothing, as in _ef_cap."""
+        Ms = {t: max(self.serra09_embed_len(self.lengths[t], p), 0) for t in {int(t) for t in pairs.ravel()} if 0 <= t < len(self.lengths)}
+        return sum(min(Ms.get(int(i), 0), Ms.get(int(j), 0)) for i, j in pairs)
+
     def ef_align(self, pairs, kappa=0.1, K=10, plane=3, paths=False, cap=None):
         """WHERE the Smith-Waterman alignment of every (query, reference) pair lies in one binarised matrix (acx_ef_align; plane
         0 mfccs, 1 ssms, 2 chromas, 3 early): a (K,) structured array (ALIGNMENT_DTYPE) -- score = earlyfusion_pairs' value for
         that pair and plane, (q0, r0) the start and (q1, r1) the end of the path in blocks of the query / the reference; a pair
         without a match: score 0 and -1 four times.  paths=True: (records, offsets (K + 1,) int64, cells (offsets[-1], 2) int32),
         pair k's path being cells[offsets[k]:offsets[k + 1]] from the start to the end.  cap: cells the buffer holds; default
-        the bound the library checks, the sum of min(M_k, N_k) over the list."""
-        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        the bound the library checks, the sum of min(M_k, N_k) over the list; for a pool this object did not see uploaded, the
+        bound of any list the library accepts (at most 1024 blocks a track)."""
         p = EfParams(float(kappa), int(K))
-        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
-        if not paths:
-            self._check(self._L.acx_ef_align(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), out.ctypes.data, None, None, 0))
-            return out
-        if cap is None:
-            # (a list the library refuses -- an index out of range -- is refused before it looks at cap)
-            nb = getattr(self, "ef_blocks", None)
-            if nb is None:
-                # a pool this object did not see uploaded: the bound of any list the library accepts (at most 1024 blocks a track)
-                cap = 1024 * len(pairs)
-            else:
-                nb = np.asarray(nb, dtype=np.int64)
-                ok = np.all((pairs >= 0) & (pairs < len(nb)), axis=1) if len(pairs) else np.zeros(0, bool)
-                cap = int(np.minimum(nb[pairs[ok, 0]], nb[pairs[ok, 1]]).sum())
-        off = np.zeros(len(pairs) + 1, np.int64)
-        cells = np.zeros((max(int(cap), 1), 2), np.int32)
-        self._check(self._L.acx_ef_align(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), out.ctypes.data,
-                                         off.ctypes.data, cells.ctypes.data, int(cap)))
-        return out, off, cells[:off[-1]].copy()
+        return self._align_list("acx_ef_align", pairs, (ctypes.byref(p), int(plane)), paths, cap,
+                                lambda pr: self._ef_cap(pr, lambda q: 1024 * len(q)))
 
     def sw_align_binary(self, B, paths=True, cap=None):
         """The same DP alone on a binary (M, N) plot (acx_sw_align_binary): (record (1,), cells (L, 2) int32 from the start to the
         end; L == 0: no match), or the record alone with paths=False.  At most 1024 rows and columns.  cap: default min(M, N)."""
-        B = np.ascontiguousarray(B, dtype=np.uint8)
-        if B.ndim != 2:
-            raise ValueError("sw_align_binary: B must be (M, N), got shape %s" % (B.shape,))
-        out = np.zeros(1, ALIGNMENT_DTYPE)
-        bp = B.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
-        if not paths:
-            self._check(self._L.acx_sw_align_binary(self._h, bp, B.shape[0], B.shape[1], out.ctypes.data, None, 0, None))
-            return out
-        if cap is None:
-            cap = min(B.shape)
-        n = ctypes.c_int64(0)
-        cells = np.zeros((max(int(cap), 1), 2), np.int32)
-        self._check(self._L.acx_sw_align_binary(self._h, bp, B.shape[0], B.shape[1], out.ctypes.data, cells.ctypes.data, int(cap),
-                                                ctypes.byref(n)))
-        return out, cells[:n.value].copy()
+        return self._align_plot("acx_sw_align_binary", B, "B", paths=bool(paths), cap=cap)
 
     def ef_has_long_track(self, pairs):
         """Whether a track of the list has more than 1024 blocks, so that its alignments take ef_align_long.  A pool this object
@@ -1024,44 +1046,15 @@ class Context(object):
         of more than 1024 blocks runs as ef_align() runs it; any other list takes the float path, and the strip-wise kernel aligns
         all its pairs.  cap: default the sum of min(M_k, N_k) from the block counts of the pool this object uploaded; for a pool it
         did not see uploaded, cap must be given."""
-        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        def unseen(_):
+            raise ValueError("ef_align_long: this object did not see the pool uploaded and cannot bound the paths: cap must be given")
         p = EfParams(float(kappa), int(K))
-        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
-        if not paths:
-            self._check(self._L.acx_ef_align_long(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), out.ctypes.data, None, None, 0))
-            return out
-        if cap is None:
-            nb = getattr(self, "ef_blocks", None)
-            if nb is None:
-                raise ValueError("ef_align_long: this object did not see the pool uploaded and cannot bound the paths: cap must be given")
-            # (a list the library refuses -- an index out of range -- is refused before it looks at cap)
-            nb = np.asarray(nb, dtype=np.int64)
-            ok = np.all((pairs >= 0) & (pairs < len(nb)), axis=1) if len(pairs) else np.zeros(0, bool)
-            cap = int(np.minimum(nb[pairs[ok, 0]], nb[pairs[ok, 1]]).sum())
-        off = np.zeros(len(pairs) + 1, np.int64)
-        cells = np.zeros((max(int(cap), 1), 2), np.int32)
-        self._check(self._L.acx_ef_align_long(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), out.ctypes.data,
-                                              off.ctypes.data, cells.ctypes.data, int(cap)))
-        return out, off, cells[:off[-1]].copy()
+        return self._align_list("acx_ef_align_long", pairs, (ctypes.byref(p), int(plane)), paths, cap, lambda pr: self._ef_cap(pr, unseen))
 
     def sw_align_long_binary(self, B, paths=True, cap=None):
         """sw_align_binary() on a plot of ANY size (acx_sw_align_long_binary): the strip-wise kernel of ef_align_long's float path,
         whatever the size.  cap: default min(M, N)."""
-        B = np.ascontiguousarray(B, dtype=np.uint8)
-        if B.ndim != 2:
-            raise ValueError("sw_align_long_binary: B must be (M, N), got shape %s" % (B.shape,))
-        out = np.zeros(1, ALIGNMENT_DTYPE)
-        bp = B.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
-        if not paths:
-            self._check(self._L.acx_sw_align_long_binary(self._h, bp, B.shape[0], B.shape[1], out.ctypes.data, None, 0, None))
-            return out
-        if cap is None:
-            cap = min(B.shape)
-        n = ctypes.c_int64(0)
-        cells = np.zeros((max(int(cap), 1), 2), np.int32)
-        self._check(self._L.acx_sw_align_long_binary(self._h, bp, B.shape[0], B.shape[1], out.ctypes.data, cells.ctypes.data, int(cap),
-                                                     ctypes.byref(n)))
-        return out, cells[:n.value].copy()
+        return self._align_plot("acx_sw_align_long_binary", B, "B", paths=bool(paths), cap=cap)
 
     def sw_binary(self, B):
         B = np.ascontiguousarray(B, dtype=np.uint8)
@@ -1291,13 +1284,7 @@ class Context(object):
     def qmax_locate_binary(self, R, params=None):
         """The same for a given binary (M, N) cross recurrence plot (acx_qmax_locate_binary): a (1,) structured array."""
         p = params or serra09_params()
-        R = np.ascontiguousarray(R, dtype=np.uint8)
-        if R.ndim != 2:
-            raise ValueError("qmax_locate_binary: R must be (M, N), got shape %s" % (R.shape,))
-        out = np.zeros(1, ALIGNMENT_DTYPE)
-        self._check(self._L.acx_qmax_locate_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                                   R.shape[0], R.shape[1], ctypes.byref(p), out.ctypes.data))
-        return out
+        return self._align_plot("acx_qmax_locate_binary", R, "R", (ctypes.byref(p),), paths=None)
 
     def serra09_align_paths(self, pairs, params=None, cap=None):
         """The alignments AND their paths (acx_serra09_align_paths): (records, offsets, cells) -- records as serra09_align
@@ -1305,33 +1292,13 @@ class Context(object):
         (row, column) of the recurrence plot from the start to the end; a pair without a match has none.  cap: cells the buffer
         holds; default the bound the library checks, the sum of min(Mq_k, Mr_k) over the list (acx_serra09_embed_len)."""
         p = params or serra09_params()
-        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        if cap is None:
-            # (a list the library refuses -- an index out of range -- is refused before it looks at cap)
-            Ms = {t: max(self.serra09_embed_len(self.lengths[t], p), 0) for t in {int(t) for t in pairs.ravel()} if 0 <= t < len(self.lengths)}
-            cap = sum(min(Ms.get(int(i), 0), Ms.get(int(j), 0)) for i, j in pairs)
-        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
-        off = np.zeros(len(pairs) + 1, np.int64)
-        cells = np.zeros((max(int(cap), 1), 2), np.int32)
-        self._check(self._L.acx_serra09_align_paths(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), out.ctypes.data,
-                                                    off.ctypes.data, cells.ctypes.data, int(cap)))
-        return out, off, cells[:off[-1]].copy()
+        return self._align_list("acx_serra09_align_paths", pairs, (ctypes.byref(p),), True, cap, lambda pr: self._serra09_cap(pr, p))
 
     def qmax_path_binary(self, R, params=None, cap=None):
         """The same DP alone on a given binary (M, N) plot (acx_qmax_path_binary): (record (1,) as qmax_locate_binary returns it,
         cells (L, 2) int32 from the start to the end; L == 0: no match).  cap: default min(M, N)."""
         p = params or serra09_params()
-        R = np.ascontiguousarray(R, dtype=np.uint8)
-        if R.ndim != 2:
-            raise ValueError("qmax_path_binary: R must be (M, N), got shape %s" % (R.shape,))
-        if cap is None:
-            cap = min(R.shape)
-        out = np.zeros(1, ALIGNMENT_DTYPE)
-        n = ctypes.c_int64(0)
-        cells = np.zeros((max(int(cap), 1), 2), np.int32)
-        self._check(self._L.acx_qmax_path_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), R.shape[0], R.shape[1],
-                                                 ctypes.byref(p), out.ctypes.data, ctypes.byref(n), cells.ctypes.data, int(cap)))
-        return out, cells[:n.value].copy()
+        return self._align_plot("acx_qmax_path_binary", R, "R", (ctypes.byref(p),), cap=cap, n_first=True)
 
     def chenfusion_align(self, pairs, params=None, plane=0):
         """WHERE the alignment of one plane of chenfusion_pairs lies (acx_chenfusion_align): plane 0 Qmax -- serra09_align itself --,
@@ -1347,43 +1314,19 @@ class Context(object):
         """The alignments of one plane AND their paths (acx_chenfusion_align_paths): (records, offsets, cells) as serra09_align_paths
         returns them, `cap` as there."""
         p = params or serra09_params()
-        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        if cap is None:
-            Ms = {t: max(self.serra09_embed_len(self.lengths[t], p), 0) for t in {int(t) for t in pairs.ravel()} if 0 <= t < len(self.lengths)}
-            cap = sum(min(Ms.get(int(i), 0), Ms.get(int(j), 0)) for i, j in pairs)
-        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
-        off = np.zeros(len(pairs) + 1, np.int64)
-        cells = np.zeros((max(int(cap), 1), 2), np.int32)
-        self._check(self._L.acx_chenfusion_align_paths(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), out.ctypes.data,
-                                                       off.ctypes.data, cells.ctypes.data, int(cap)))
-        return out, off, cells[:off[-1]].copy()
+        return self._align_list("acx_chenfusion_align_paths", pairs, (ctypes.byref(p), int(plane)), True, cap,
+                                lambda pr: self._serra09_cap(pr, p))
 
     def dmax_locate_binary(self, R, params=None):
         """The Dmax alignment of a given binary (M, N) cross recurrence plot (acx_dmax_locate_binary): a (1,) structured array."""
         p = params or serra09_params()
-        R = np.ascontiguousarray(R, dtype=np.uint8)
-        if R.ndim != 2:
-            raise ValueError("dmax_locate_binary: R must be (M, N), got shape %s" % (R.shape,))
-        out = np.zeros(1, ALIGNMENT_DTYPE)
-        self._check(self._L.acx_dmax_locate_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                                   R.shape[0], R.shape[1], ctypes.byref(p), out.ctypes.data))
-        return out
+        return self._align_plot("acx_dmax_locate_binary", R, "R", (ctypes.byref(p),), paths=None)
 
     def dmax_path_binary(self, R, params=None, cap=None):
         """The same with its path (acx_dmax_path_binary): (record (1,), cells (L, 2) int32 from the start to the end; L == 0: no
         match).  cap: default min(M, N)."""
         p = params or serra09_params()
-        R = np.ascontiguousarray(R, dtype=np.uint8)
-        if R.ndim != 2:
-            raise ValueError("dmax_path_binary: R must be (M, N), got shape %s" % (R.shape,))
-        if cap is None:
-            cap = min(R.shape)
-        out = np.zeros(1, ALIGNMENT_DTYPE)
-        n = ctypes.c_int64(0)
-        cells = np.zeros((max(int(cap), 1), 2), np.int32)
-        self._check(self._L.acx_dmax_path_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), R.shape[0], R.shape[1],
-                                                 ctypes.byref(p), out.ctypes.data, ctypes.byref(n), cells.ctypes.data, int(cap)))
-        return out, cells[:n.value].copy()
+        return self._align_plot("acx_dmax_path_binary", R, "R", (ctypes.byref(p),), cap=cap, n_first=True)
 
     # ------------------------------------------------------------------ FTM2D
     def ftm2d_pool_begin(self, n_tracks, pwr=1.96, win=75, c=5):

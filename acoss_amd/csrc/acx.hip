@@ -701,6 +701,22 @@ void quiesce(acx_ctx *c)
     drain_profile(c);
 }
 
+// The guard of every entry point that queues work: body() returns an ACX code, and any code but ACX_OK is returned with the streams
+// idle -- no queued copy still reads a host buffer of the call that is about to go out of scope, or still writes the caller's.
+template <typename Body>
+int guarded(acx_ctx *c, Body body)
+{
+    const int rc = body();
+    if (rc != ACX_OK) quiesce(c);                // (c->err keeps the first failure's text)
+    return rc;
+}
+
+// The tracebacks on the device wrote the cells end first: the n cells of `src`, from the start to the end, into dst.
+void reverse_cells(const int32_t *src, int n, int32_t *dst)
+{
+    for (int t = 0; t < n; ++t) { dst[2 * (size_t)t] = src[2 * (n - 1 - t)]; dst[2 * (size_t)t + 1] = src[2 * (n - 1 - t) + 1]; }
+}
+
 // The WHOLE pair list is checked before the first launch: indices, tracks shorter than the stack, pairs that cannot fit the
 // scratch limit on their own.  (The batch loop used to find these when it reached them -- with earlier batches in flight.)
 int validate_serra09_pairs(acx_ctx *c, const acx::Serra09Lengths &len, const int32_t *pairs, int64_t K, const acx_serra09_params &p, bool dbg,
@@ -841,7 +857,7 @@ int run_qmax_paths(acx_ctx *c, const PairDesc *dpd, const acx_alignment *recs, i
         ACX_HIP(c, hipMemcpyAsync(h_n.data(), c->d_pn, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, c->stream));
         ACX_HIP(c, hipMemcpyAsync(h_cells.data(), c->d_pcells, sizeof(int32_t) * 2 * ncell, hipMemcpyDeviceToHost, c->stream));
         ACX_HIP(c, hipStreamSynchronize(c->stream));
-        for (int b = 0; b < nb; ++b) {      // the traceback wrote the cells end first
+        for (int b = 0; b < nb; ++b) {
             const acx::PathBox &bx = boxes[(size_t)b];
             const int n = h_n[(size_t)b];
             const int32_t *src = h_cells.data() + 2 * bx.cell_off;
@@ -849,7 +865,7 @@ int run_qmax_paths(acx_ctx *c, const PairDesc *dpd, const acx_alignment *recs, i
                 return fail(c, ACX_ERR_STATE, who + "the traceback of pair " + name(owner[(size_t)b]) + " does not end at the reported start");
             std::vector<int32_t> &out = dst(owner[(size_t)b]);
             out.resize((size_t)(2 * n));
-            for (int t = 0; t < n; ++t) { out[2 * (size_t)t] = src[2 * (n - 1 - t)]; out[2 * (size_t)t + 1] = src[2 * (n - 1 - t) + 1]; }
+            reverse_cells(src, n, out.data());
         }
     }
     drain_profile(c);
@@ -877,22 +893,10 @@ void launch_streaming_class(acx_ctx *c, const PairDesc *dpd, const PairDesc *pd,
     }
 }
 
-int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
-                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al, std::vector<std::vector<int32_t>> *paths, bool al_dmax);
-
-// Runs the chain over `K` pairs in scratch-sized batches.  `al` (acx_serra09_align): the sweep is qmax_locate_kernel and pair k's
-// record goes to al[k]; no scores are written.  `paths` (acx_serra09_align_paths, with `al`; K vectors): the path pass runs behind the
-// locating sweep of every batch, and pair k's cells go to (*paths)[k].  `al_dmax` (acx_chenfusion_align*, plane 1; with `al`): the
-// locating sweep and the path pass are the Dmax ones.
-int run_serra09(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
-                const DebugOut *dbg, bool both = false, const DevDst *dd = nullptr, acx_alignment *al = nullptr,
-                std::vector<std::vector<int32_t>> *paths = nullptr, bool al_dmax = false)
-{
-    const int rc = run_serra09_impl(c, pairs, K, p_in, out, dbg, both, dd, al, paths, al_dmax);
-    if (rc != ACX_OK) quiesce(c);                // (c->err keeps the first failure's text)
-    return rc;
-}
-
+// Runs the chain over `K` pairs in scratch-sized batches (behind run_serra09's guard, below).  `al` (acx_serra09_align): the sweep is
+// qmax_locate_kernel and pair k's record goes to al[k]; no scores are written.  `paths` (acx_serra09_align_paths, with `al`; K vectors):
+// the path pass runs behind the locating sweep of every batch, and pair k's cells go to (*paths)[k].  `al_dmax` (acx_chenfusion_align*,
+// plane 1; with `al`): the locating sweep and the path pass are the Dmax ones.
 int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
                      const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al, std::vector<std::vector<int32_t>> *paths, bool al_dmax)
 {
@@ -1095,6 +1099,13 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
     for (int s = 0; s < 2; ++s)
         if ((rc = collect_slot(c, c->slot[s], out, al)) != ACX_OK) return rc;
     return ACX_OK;
+}
+
+int run_serra09(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
+                const DebugOut *dbg, bool both = false, const DevDst *dd = nullptr, acx_alignment *al = nullptr,
+                std::vector<std::vector<int32_t>> *paths = nullptr, bool al_dmax = false)
+{
+    return guarded(c, [&] { return run_serra09_impl(c, pairs, K, p_in, out, dbg, both, dd, al, paths, al_dmax); });
 }
 
 }  // namespace
@@ -1370,8 +1381,38 @@ static int launch_ef_gemms(acx_ctx *c, const SegBatch &seg, int B, int tiles_x, 
     return f32_chroma();
 }
 
-static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params &p, float *out, const EfDebug *dbg,
-                       const float *ext_matrix, int extM, int extN, const DevDst *dd, const EfAlign *aln, std::vector<acx::EfPair> *pd_out);
+// One pair of M x N at offset 0 of every arena: a caller's matrix or plot as a batch of its own.
+static acx::EfPair ef_one_pair(int M, int N, int kbin = 0)
+{
+    acx::EfPair d;
+    d.q = d.r = 0; d.M = M; d.N = N; d.oti = 0; d.pitchC = round_up(N, 64); d.pitchT = round_up(M, 64); d.kbin = kbin;
+    d.ctN = 0; d.pad = 0; d.offB = 0; d.offC = 0; d.offS = 0;
+    return d;
+}
+
+// One job's result of ef_align_kernel / ef_align_long_kernel on the host: `rec` its EFA_REC words, `src` its cells as the traceback left
+// them, read only where `path` is given; the record goes to `out`, the cells from the start to the end to `path`.  The errors read
+// who + ": the traceback" + of + ...; `score` (or nullptr): the bits the record's score must have.
+static int decode_ef_alignment(acx_ctx *c, const std::string &who, const std::string &of, const int32_t *rec, const int32_t *src, int max_cells,
+                               const float *score, acx_alignment &out, std::vector<int32_t> *path)
+{
+    acx_alignment a;
+    memcpy(&a.score, rec, sizeof(float));
+    a.q0 = rec[1]; a.r0 = rec[2]; a.q1 = rec[3]; a.r1 = rec[4];
+    const int n = rec[5];
+    // the score is the one the batch's Smith-Waterman launch left for this pair and plane, and a match has its cells
+    if (score && memcmp(&a.score, score, sizeof(float)) != 0)
+        return fail(c, ACX_ERR_STATE, who + ": the alignment" + of + " does not reach the pair's score");
+    if (n < 0 || n > max_cells || (a.score > 0.0f) != (n >= 1))
+        return fail(c, ACX_ERR_STATE, who + ": the traceback" + of + " returned " + std::to_string(n) + " cells");
+    out = a;
+    if (!path) return ACX_OK;
+    if (n >= 1 && (src[0] != a.q1 || src[1] != a.r1 || src[2 * (n - 1)] != a.q0 || src[2 * (n - 1) + 1] != a.r0))
+        return fail(c, ACX_ERR_STATE, who + ": the traceback" + of + " does not run from the reported end to the reported start");
+    path->resize(2 * (size_t)n);
+    reverse_cells(src, n, path->data());
+    return ACX_OK;
+}
 
 // The alignment pass (ef_align_kernels.hpp) behind a batch's Smith-Waterman launch, while d_efbits and d_efpd
 // still hold the batch: `pd` are the batch's descriptors on the host, pair b of the batch is pair k0 + b of the run, `scores` its
@@ -1433,42 +1474,20 @@ static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, in
         ACX_HIP(c, hipMemcpyAsync(h_res.data(), c->d_efres, sizeof(int32_t) * ncopy, hipMemcpyDeviceToHost, c->stream));
         ACX_HIP(c, hipStreamSynchronize(c->stream));
         for (int t = 0; t < nb; ++t) {
-            const int32_t *rec = h_res.data() + (size_t)acx::EFA_REC * t;
             const acx::EfAlignJob &j = jobs[(size_t)t];
             const int64_t k = k0 + b0 + t;
-            acx_alignment a;
-            memcpy(&a.score, rec, sizeof(float));
-            a.q0 = rec[1]; a.r0 = rec[2]; a.q1 = rec[3]; a.r1 = rec[4];
-            const int n = rec[5];
-            // the score is the one the batch's Smith-Waterman launch left for this pair and plane, and a match has its cells
-            if (memcmp(&a.score, scores + 4 * (size_t)(b0 + t) + aln.plane, sizeof(float)) != 0)
-                return fail(c, ACX_ERR_STATE, "ef_align: the alignment of pair " + std::to_string(k) + " does not reach the pair's score");
-            if (n < 0 || n > j.max_cells || (a.score > 0.0f) != (n >= 1))
-                return fail(c, ACX_ERR_STATE, "ef_align: the traceback of pair " + std::to_string(k) + " returned " + std::to_string(n) + " cells");
-            aln.al[k] = a;
-            if (!aln.paths) continue;
-            std::vector<int32_t> &dst = (*aln.paths)[(size_t)k];
-            dst.resize(2 * (size_t)n);
-            const int32_t *src = h_res.data() + nrec + 2 * (size_t)j.cell_off;      // the traceback wrote the cells end first
-            if (n >= 1 && (src[0] != a.q1 || src[1] != a.r1 || src[2 * (n - 1)] != a.q0 || src[2 * (n - 1) + 1] != a.r0))
-                return fail(c, ACX_ERR_STATE, "ef_align: the traceback of pair " + std::to_string(k) + " does not run from the reported end to the reported start");
-            for (int e = 0; e < n; ++e) { dst[2 * (size_t)e] = src[2 * (n - 1 - e)]; dst[2 * (size_t)e + 1] = src[2 * (n - 1 - e) + 1]; }
+            const int32_t *src = aln.paths ? h_res.data() + nrec + 2 * (size_t)j.cell_off : nullptr;
+            if ((rc = decode_ef_alignment(c, "ef_align", " of pair " + std::to_string(k), h_res.data() + (size_t)acx::EFA_REC * t, src, j.max_cells,
+                                          scores + 4 * (size_t)(b0 + t) + aln.plane, aln.al[k], aln.paths ? &(*aln.paths)[(size_t)k] : nullptr)) != ACX_OK)
+                return rc;
         }
     }
     drain_profile(c);
     return ACX_OK;
 }
 
-// `dd` (grid runs): the four scores of pair k go to dd->base[dd->idx[k] .. + 4) on the DEVICE instead of out[4 k ..].
-int run_ef(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params &p, float *out, const EfDebug *dbg,
-           const float *ext_matrix, int extM, int extN, const DevDst *dd = nullptr, const EfAlign *aln = nullptr,
-           std::vector<acx::EfPair> *pd_out = nullptr)
-{
-    const int rc = run_ef_impl(c, pairs, K, p, out, dbg, ext_matrix, extM, extN, dd, aln, pd_out);
-    if (rc != ACX_OK) quiesce(c);                // nothing of a failed call stays in flight behind its error code
-    return rc;
-}
-
+// `dd` (grid runs): the four scores of pair k go to dd->base[dd->idx[k] .. + 4) on the DEVICE instead of out[4 k ..].  (Behind
+// run_ef's guard, below.)
 static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params &p, float *out, const EfDebug *dbg,
                        const float *ext_matrix, int extM, int extN, const DevDst *dd, const EfAlign *aln, std::vector<acx::EfPair> *pd_out)
 {
@@ -1571,7 +1590,7 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
         for (; k < K && pd.size() < 65535; ++k) {
             EfPair d;
             if (ext_matrix) {
-                d.q = d.r = 0; d.M = extM; d.N = extN;
+                d = ef_one_pair(extM, extN);
             } else {
                 d.q = pairs[2 * k]; d.r = pairs[2 * k + 1];
                 if (d.q < 0 || d.r < 0 || d.q >= c->ef_ntracks || d.r >= c->ef_ntracks)
@@ -1769,6 +1788,13 @@ static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef
         fprintf(stderr, "[acx ef host] %lld pairs in %d batches, %.1f ms: preamble %.1f, descriptors %.1f, rectangles %.1f, enqueue %.1f, waiting for the device %.1f\n",
                 (long long)K, nbatches, 1e3 * (now() - t_call), 1e3 * ht[4], 1e3 * ht[0], 1e3 * ht[1], 1e3 * ht[2], 1e3 * ht[3]);
     return ACX_OK;
+}
+
+int run_ef(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params &p, float *out, const EfDebug *dbg,
+           const float *ext_matrix, int extM, int extN, const DevDst *dd = nullptr, const EfAlign *aln = nullptr,
+           std::vector<acx::EfPair> *pd_out = nullptr)
+{
+    return guarded(c, [&] { return run_ef_impl(c, pairs, K, p, out, dbg, ext_matrix, extM, extN, dd, aln, pd_out); });
 }
 
 static void free_pool(acx_ctx *c)
@@ -2239,43 +2265,55 @@ int acx_serra09_debug_bits(acx_ctx *c, const int32_t *pairs, int64_t K, const ac
     return ACX_OK;
 }
 
-int acx_qmax_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, float *score)
+// A caller's binary M x N recurrence plot as the one pair of a Serra09 batch: checked (`who` names the entry point), packed into `words`
+// in the pipeline's bitmap layout -- word t of row i = columns [64 t - 7 + (i & 7), +64) -- and queued for d_bits, with its descriptor
+// `d` for slot 0.  The queued copies read `d` and `words`: both are the caller's, to keep until the stream is idle.
+static int stage_serra09_plot(acx_ctx *c, const std::string &who, const uint8_t *R, int M, int N, PairDesc &d, std::vector<unsigned long long> &words)
 {
-    if (!c) return ACX_ERR_INVALID;
-    if (!R || !params || !score || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "qmax_binary: bad argument");
-    if (params->dp_start != 2 && params->dp_start != 3) return fail(c, ACX_ERR_INVALID, "qmax_binary: dp_start must be 2 or 3");
-    if (!(params->gamma_o >= 0.0f) || !(params->gamma_e >= 0.0f)) return fail(c, ACX_ERR_INVALID, "qmax_binary: gammas must be >= 0");
-    ACX_HIP(c, hipSetDevice(c->device));
-    // the recurrence plot in the pipeline's bitmap layout: word t of row i = columns [64 t - 7 + (i & 7), +64)
-    PairDesc d;
     memset(&d, 0, sizeof(d));
     d.Mq = M; d.Mr = N; d.Tq = M; d.Tr = N;
     d.pitchD = round_up(N, 64); d.pitchT = 0;
     d.nw = acx::serra09_tiles(N);
-    std::vector<unsigned long long> words((size_t)M * d.nw, 0ull);
+    words.assign((size_t)M * d.nw, 0ull);
     for (int i = 0; i < M; ++i) {
         const int c0 = (i & (acx::BAND - 1)) - (acx::BAND - 1);
         for (int j = 0; j < N; ++j) {
             const uint8_t v = R[(size_t)i * N + j];
-            if (v > 1) return fail(c, ACX_ERR_INVALID, "qmax_binary: non-binary elements found in input");
+            if (v > 1) return fail(c, ACX_ERR_INVALID, who + ": non-binary elements found in input");
             if (v) { const int pos = j - c0; words[(size_t)i * d.nw + (pos >> 6)] |= 1ull << (pos & 63); }
         }
     }
     int rc;
-    Serra09Slot &S = c->slot[0];
     if ((rc = ensure(c, c->d_bits, words.size())) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_scratch, (size_t)8 * M + 16)) != ACX_OK) return rc;     // strip records of the long DP
-    if ((rc = ensure(c, S.d_pd, (size_t)1)) != ACX_OK) return rc;
-    if ((rc = ensure(c, S.d_out, (size_t)2)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->slot[0].d_pd, (size_t)1)) != ACX_OK) return rc;
     ACX_HIP(c, hipMemcpyAsync(c->d_bits, words.data(), sizeof(unsigned long long) * words.size(), hipMemcpyHostToDevice, c->stream));
-    ACX_HIP(c, hipMemcpyAsync(S.d_pd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
-    // (one pair of any shape: the class of its longer side, never packed)
-    launch_qmax_sweep(c->stream, S.d_pd, 1, c->d_bits, c->d_scratch, S.d_out, 1, params->gamma_o, params->gamma_e, params->dp_start,
-                      params->dmax != 0, acx::serra09_sweep(acx::serra09_row_class(std::max(M, N))).cols, 1);
-    ACX_HIP(c, hipGetLastError());
-    ACX_HIP(c, hipMemcpyAsync(score, S.d_out, sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    ACX_HIP(c, hipMemcpyAsync(c->slot[0].d_pd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
     return ACX_OK;
+}
+
+int acx_qmax_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, float *score)
+{
+    if (!c) return ACX_ERR_INVALID;
+    PairDesc d;
+    std::vector<unsigned long long> words;
+    return guarded(c, [&]() -> int {
+        if (!R || !params || !score || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "qmax_binary: bad argument");
+        if (params->dp_start != 2 && params->dp_start != 3) return fail(c, ACX_ERR_INVALID, "qmax_binary: dp_start must be 2 or 3");
+        if (!(params->gamma_o >= 0.0f) || !(params->gamma_e >= 0.0f)) return fail(c, ACX_ERR_INVALID, "qmax_binary: gammas must be >= 0");
+        ACX_HIP(c, hipSetDevice(c->device));
+        int rc;
+        Serra09Slot &S = c->slot[0];
+        if ((rc = stage_serra09_plot(c, "qmax_binary", R, M, N, d, words)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_scratch, (size_t)8 * M + 16)) != ACX_OK) return rc;     // strip records of the long DP
+        if ((rc = ensure(c, S.d_out, (size_t)2)) != ACX_OK) return rc;
+        // (one pair of any shape: the class of its longer side, never packed)
+        launch_qmax_sweep(c->stream, S.d_pd, 1, c->d_bits, c->d_scratch, S.d_out, 1, params->gamma_o, params->gamma_e, params->dp_start,
+                          params->dmax != 0, acx::serra09_sweep(acx::serra09_row_class(std::max(M, N))).cols, 1);
+        ACX_HIP(c, hipGetLastError());
+        ACX_HIP(c, hipMemcpyAsync(score, S.d_out, sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        return ACX_OK;
+    });
 }
 
 int acx_serra09_align(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, acx_alignment *out)
@@ -2291,42 +2329,28 @@ int acx_serra09_align(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ser
 static int locate_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out, bool dmax,
                          const std::string &who)
 {
-    if (params->dp_start != 2 && params->dp_start != 3) return fail(c, ACX_ERR_INVALID, who + ": dp_start must be 2 or 3");
-    if (!(params->gamma_o >= 0.0f) || !(params->gamma_e >= 0.0f)) return fail(c, ACX_ERR_INVALID, who + ": gammas must be >= 0");
-    if ((int64_t)M * N + acx::LOC_STRIP >= ((int64_t)1 << 32)) return fail(c, ACX_ERR_UNSUPPORTED, who + ": the plot has 2^32 cells or more");
-    ACX_HIP(c, hipSetDevice(c->device));
-    // the recurrence plot in the pipeline's bitmap layout (acx_qmax_binary): word t of row i = columns [64 t - 7 + (i & 7), +64)
     PairDesc d;
-    memset(&d, 0, sizeof(d));
-    d.Mq = M; d.Mr = N; d.Tq = M; d.Tr = N;
-    d.pitchD = round_up(N, 64); d.pitchT = 0;
-    d.nw = acx::serra09_tiles(N);
-    std::vector<unsigned long long> words((size_t)M * d.nw, 0ull);
-    for (int i = 0; i < M; ++i) {
-        const int c0 = (i & (acx::BAND - 1)) - (acx::BAND - 1);
-        for (int j = 0; j < N; ++j) {
-            const uint8_t v = R[(size_t)i * N + j];
-            if (v > 1) return fail(c, ACX_ERR_INVALID, who + ": non-binary elements found in input");
-            if (v) { const int pos = j - c0; words[(size_t)i * d.nw + (pos >> 6)] |= 1ull << (pos & 63); }
-        }
-    }
-    int rc;
-    Serra09Slot &S = c->slot[0];
-    const int64_t seam_off = 0;
-    if ((rc = ensure(c, c->d_bits, words.size())) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_seam, (size_t)std::max<int64_t>(acx::loc_seam_records(M, N, params->dp_start), 1))) != ACX_OK) return rc;
-    if ((rc = ensure(c, S.d_pd, (size_t)1)) != ACX_OK) return rc;
-    if ((rc = ensure(c, S.d_al, (size_t)1)) != ACX_OK) return rc;
-    if ((rc = ensure(c, S.d_seam_off, (size_t)1)) != ACX_OK) return rc;
-    ACX_HIP(c, hipMemcpyAsync(c->d_bits, words.data(), sizeof(unsigned long long) * words.size(), hipMemcpyHostToDevice, c->stream));
-    ACX_HIP(c, hipMemcpyAsync(S.d_pd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
-    ACX_HIP(c, hipMemcpyAsync(S.d_seam_off, &seam_off, sizeof(seam_off), hipMemcpyHostToDevice, c->stream));
-    if (dmax) launch_dmax_locate(c->stream, S.d_pd, 1, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, params->gamma_o, params->gamma_e, params->dp_start);
-    else launch_qmax_locate(c->stream, S.d_pd, 1, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, params->gamma_o, params->gamma_e, params->dp_start);
-    ACX_HIP(c, hipGetLastError());
-    ACX_HIP(c, hipMemcpyAsync(out, S.d_al, sizeof(acx_alignment), hipMemcpyDeviceToHost, c->stream));
-    ACX_HIP(c, hipStreamSynchronize(c->stream));
-    return ACX_OK;
+    std::vector<unsigned long long> words;
+    static const int64_t seam_off = 0;
+    return guarded(c, [&]() -> int {
+        if (params->dp_start != 2 && params->dp_start != 3) return fail(c, ACX_ERR_INVALID, who + ": dp_start must be 2 or 3");
+        if (!(params->gamma_o >= 0.0f) || !(params->gamma_e >= 0.0f)) return fail(c, ACX_ERR_INVALID, who + ": gammas must be >= 0");
+        if ((int64_t)M * N + acx::LOC_STRIP >= ((int64_t)1 << 32)) return fail(c, ACX_ERR_UNSUPPORTED, who + ": the plot has 2^32 cells or more");
+        ACX_HIP(c, hipSetDevice(c->device));
+        int rc;
+        Serra09Slot &S = c->slot[0];
+        if ((rc = stage_serra09_plot(c, who, R, M, N, d, words)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_seam, (size_t)std::max<int64_t>(acx::loc_seam_records(M, N, params->dp_start), 1))) != ACX_OK) return rc;
+        if ((rc = ensure(c, S.d_al, (size_t)1)) != ACX_OK) return rc;
+        if ((rc = ensure(c, S.d_seam_off, (size_t)1)) != ACX_OK) return rc;
+        ACX_HIP(c, hipMemcpyAsync(S.d_seam_off, &seam_off, sizeof(seam_off), hipMemcpyHostToDevice, c->stream));
+        if (dmax) launch_dmax_locate(c->stream, S.d_pd, 1, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, params->gamma_o, params->gamma_e, params->dp_start);
+        else launch_qmax_locate(c->stream, S.d_pd, 1, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, params->gamma_o, params->gamma_e, params->dp_start);
+        ACX_HIP(c, hipGetLastError());
+        ACX_HIP(c, hipMemcpyAsync(out, S.d_al, sizeof(acx_alignment), hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        return ACX_OK;
+    });
 }
 
 int acx_qmax_locate_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out)
@@ -2419,21 +2443,23 @@ int acx_chenfusion_align_paths(acx_ctx *c, const int32_t *pairs, int64_t K, cons
 static int path_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out,
                        int64_t *n_cells, int32_t *cells, int64_t cap, bool dmax, const std::string &who)
 {
-    if (!R || !params || !out || !n_cells || M < 1 || N < 1 || cap < 0 || (cap > 0 && !cells)) return fail(c, ACX_ERR_INVALID, who + ": bad argument");
-    if (cap < std::min(M, N))
-        return fail(c, ACX_ERR_INVALID, who + ": cap " + std::to_string(cap) + " is too small: " + std::to_string(std::min(M, N)) +
-                                            " cells required (min(M, N))");
-    *n_cells = 0;
-    // the locating sweep on the plot: it leaves the plot's bitmap in d_bits and its descriptor in slot 0, and the record is the box
-    int rc = dmax ? acx_dmax_locate_binary(c, R, M, N, params, out) : acx_qmax_locate_binary(c, R, M, N, params, out);
-    if (rc != ACX_OK) return rc;
-    std::vector<int32_t> path;
-    rc = run_qmax_paths(c, c->slot[0].d_pd, out, 1, params->gamma_o, params->gamma_e,
-                        [&](int) -> std::vector<int32_t> & { return path; }, [](int) { return std::string("0"); }, dmax);
-    if (rc != ACX_OK) { quiesce(c); return rc; }
-    if (!path.empty()) memcpy(cells, path.data(), sizeof(int32_t) * path.size());
-    *n_cells = (int64_t)path.size() / 2;
-    return ACX_OK;
+    return guarded(c, [&]() -> int {
+        if (!R || !params || !out || !n_cells || M < 1 || N < 1 || cap < 0 || (cap > 0 && !cells)) return fail(c, ACX_ERR_INVALID, who + ": bad argument");
+        if (cap < std::min(M, N))
+            return fail(c, ACX_ERR_INVALID, who + ": cap " + std::to_string(cap) + " is too small: " + std::to_string(std::min(M, N)) +
+                                                " cells required (min(M, N))");
+        *n_cells = 0;
+        // the locating sweep on the plot: it leaves the plot's bitmap in d_bits and its descriptor in slot 0, and the record is the box
+        int rc = dmax ? acx_dmax_locate_binary(c, R, M, N, params, out) : acx_qmax_locate_binary(c, R, M, N, params, out);
+        if (rc != ACX_OK) return rc;
+        std::vector<int32_t> path;
+        rc = run_qmax_paths(c, c->slot[0].d_pd, out, 1, params->gamma_o, params->gamma_e,
+                            [&](int) -> std::vector<int32_t> & { return path; }, [](int) { return std::string("0"); }, dmax);
+        if (rc != ACX_OK) return rc;
+        if (!path.empty()) memcpy(cells, path.data(), sizeof(int32_t) * path.size());
+        *n_cells = (int64_t)path.size() / 2;
+        return ACX_OK;
+    });
 }
 
 int acx_qmax_path_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out,
@@ -3189,85 +3215,101 @@ int acx_csm_binary_sw(acx_ctx *c, const float *D, int32_t M, int32_t N, double k
     return rc;
 }
 
-int acx_sw_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, float *score)
+// A caller's binary M x N plot as the one pair `d` of an EarlyFusion batch, in one of the two layouts the kernels read.  `who` names the
+// entry point where a value is neither 0 nor 1; empty: the reference's own text (alignment_tools.py:23), which acx_sw_binary and
+// acx_sw_bits_binary report.  The queued copies read `d` and the host copy of the plot (`W` / `Cm`): both are the caller's, to keep
+// until the stream is idle.
+static int nonbinary(acx_ctx *c, const std::string &who)
 {
-    if (!c) return ACX_ERR_INVALID;
-    if (!B || !score || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "sw_binary: bad argument");
-    std::vector<float> Cm((size_t)M * N);
+    return fail(c, ACX_ERR_INVALID, who.empty() ? std::string("Non-binary elements found in input") : who + ": non-binary elements found in input");
+}
+
+// the bit words the selection kernels leave in d_efbits: bit j % 32 of word j / 32, M rows of pitchC / 32 words, pads zero
+static int stage_ef_bit_plot(acx_ctx *c, const std::string &who, const uint8_t *B, int M, int N, acx::EfPair &d, std::vector<uint32_t> &W)
+{
+    d = ef_one_pair(M, N);
+    const int words = d.pitchC / 32;
+    W.assign((size_t)M * words, 0u);
+    for (int i = 0; i < M; ++i)
+        for (int j = 0; j < N; ++j) {
+            const uint8_t b = B[(size_t)i * N + j];
+            if (b > 1) return nonbinary(c, who);
+            W[(size_t)i * words + (j >> 5)] |= (uint32_t)b << (j & 31);
+        }
+    int rc;
+    ACX_HIP(c, hipSetDevice(c->device));
+    if ((rc = ensure(c, c->d_efbits, W.size())) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efpd, (size_t)1)) != ACX_OK) return rc;
+    ACX_HIP(c, hipMemcpyAsync(c->d_efpd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(c->d_efbits, W.data(), sizeof(uint32_t) * W.size(), hipMemcpyHostToDevice, c->stream));
+    return ACX_OK;
+}
+
+// the float path's matrix, thresholds and tie columns: B = [C <= threshold] with C = 1 - B and threshold 0 in every row (written
+// directly: the row-stat kernel would select by rank), every tie counted
+static int stage_ef_float_plot(acx_ctx *c, const std::string &who, const uint8_t *B, int M, int N, acx::EfPair &d, std::vector<float> &Cm)
+{
+    d = ef_one_pair(M, N);
+    Cm.resize((size_t)M * N);
     for (size_t k = 0; k < Cm.size(); ++k) {
-        if (B[k] > 1) return fail(c, ACX_ERR_INVALID, "Non-binary elements found in input");
-        Cm[k] = B[k] ? 0.0f : 1.0f;         // B = [C <= threshold] with threshold 0
+        if (B[k] > 1) return nonbinary(c, who);
+        Cm[k] = B[k] ? 0.0f : 1.0f;
     }
-    // run the DP on this matrix with per-row thresholds 0: the row-stat kernel would select by
-    // rank, so the thresholds are written directly
-    acx_ef_params p{1.0, 1};
-    float sc[4] = {0, 0, 0, 0};
-    acx::EfPair d;
-    d.q = d.r = 0; d.M = M; d.N = N; d.oti = 0; d.pitchC = round_up(N, 64); d.pitchT = round_up(M, 64); d.kbin = 0;
-    d.ctN = 0; d.pad = 0; d.offB = 0; d.offC = 0; d.offS = 0;
     int rc;
     ACX_HIP(c, hipSetDevice(c->device));
     if ((rc = ensure(c, c->d_scratch, (size_t)M * d.pitchC)) != ACX_OK) return rc;
     if ((rc = ensure(c, c->d_thr, (size_t)acx::ef_s_total(d))) != ACX_OK) return rc;
     if ((rc = ensure(c, c->d_efpd, (size_t)1)) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_out, (size_t)4)) != ACX_OK) return rc;
     ACX_HIP(c, hipMemcpyAsync(c->d_efpd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
     ACX_HIP(c, hipMemcpy2DAsync(c->d_scratch, sizeof(float) * d.pitchC, Cm.data(), sizeof(float) * N, sizeof(float) * N, M,
                                 hipMemcpyHostToDevice, c->stream));
     ACX_HIP(c, hipMemsetAsync(c->d_thr, 0, sizeof(float) * M, c->stream));
     ACX_HIP(c, hipMemsetAsync(c->d_thr + acx::ef_jcut_off(d, 0), 0x7f, sizeof(int) * M, c->stream));   // every tie counts
-    if (N > acx::EF_MAXNB) hipLaunchKernelGGL(acx::sw_long_kernel, dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_out, 0);
-    else if (N > 512) hipLaunchKernelGGL((acx::sw_kernel<16>), dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_out, 0);
-    else hipLaunchKernelGGL((acx::sw_kernel<8>), dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_out, 0);
-    ACX_HIP(c, hipGetLastError());
-    ACX_HIP(c, hipMemcpyAsync(sc, c->d_out, sizeof(float) * 4, hipMemcpyDeviceToHost, c->stream));
-    ACX_HIP(c, hipStreamSynchronize(c->stream));
-    (void)p;
-    *score = sc[0];
     return ACX_OK;
 }
 
-static int sw_bits_binary_impl(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, float *score);
+int acx_sw_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, float *score)
+{
+    if (!c) return ACX_ERR_INVALID;
+    acx::EfPair d;
+    std::vector<float> Cm;
+    float sc[4] = {0, 0, 0, 0};
+    return guarded(c, [&]() -> int {
+        if (!B || !score || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "sw_binary: bad argument");
+        int rc;
+        if ((rc = stage_ef_float_plot(c, "", B, M, N, d, Cm)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_out, (size_t)4)) != ACX_OK) return rc;
+        if (N > acx::EF_MAXNB) hipLaunchKernelGGL(acx::sw_long_kernel, dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_out, 0);
+        else if (N > 512) hipLaunchKernelGGL((acx::sw_kernel<16>), dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_out, 0);
+        else hipLaunchKernelGGL((acx::sw_kernel<8>), dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_out, 0);
+        ACX_HIP(c, hipGetLastError());
+        ACX_HIP(c, hipMemcpyAsync(sc, c->d_out, sizeof(float) * 4, hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        *score = sc[0];
+        return ACX_OK;
+    });
+}
 
 int acx_sw_bits_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, float *score)
 {
     if (!c) return ACX_ERR_INVALID;
-    const int rc = sw_bits_binary_impl(c, B, M, N, score);
-    if (rc != ACX_OK) quiesce(c);                // the queued copies read this call's host buffers: none stays in flight behind an error
-    return rc;
-}
-
-static int sw_bits_binary_impl(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, float *score)
-{
-    if (!B || !score || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "sw_bits_binary: bad argument");
-    if (M > acx::EF_MAXNB || N > acx::EF_MAXNB) return fail(c, ACX_ERR_INVALID, "sw_bits_binary: more than 1024 rows or columns (the bit kernels hold a row in one wave)");
     acx::EfPair d;
-    d.q = d.r = 0; d.M = M; d.N = N; d.oti = 0; d.pitchC = round_up(N, 64); d.pitchT = round_up(M, 64); d.kbin = 0;
-    d.ctN = 0; d.pad = 0; d.offB = 0; d.offC = 0; d.offS = 0;
-    // the layout the selection kernels leave in d_efbits: bit j % 32 of word j / 32, M rows of pitchC / 32 words, pads zero
-    const int words = d.pitchC / 32;
-    std::vector<uint32_t> W((size_t)M * words, 0u);
-    for (int i = 0; i < M; ++i)
-        for (int j = 0; j < N; ++j) {
-            const uint8_t b = B[(size_t)i * N + j];
-            if (b > 1) return fail(c, ACX_ERR_INVALID, "Non-binary elements found in input");
-            W[(size_t)i * words + (j >> 5)] |= (uint32_t)b << (j & 31);
-        }
+    std::vector<uint32_t> W;
     float sc[4] = {0, 0, 0, 0};
-    int rc;
-    ACX_HIP(c, hipSetDevice(c->device));
-    if ((rc = ensure(c, c->d_efbits, W.size())) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_efpd, (size_t)1)) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_out, (size_t)4)) != ACX_OK) return rc;
-    ACX_HIP(c, hipMemcpyAsync(c->d_efpd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
-    ACX_HIP(c, hipMemcpyAsync(c->d_efbits, W.data(), sizeof(uint32_t) * W.size(), hipMemcpyHostToDevice, c->stream));
-    if (N > 512) hipLaunchKernelGGL((acx::sw_bits_h16_kernel<16>), dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_efbits, c->d_out, 0);
-    else hipLaunchKernelGGL((acx::sw_bits_h16_kernel<8>), dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_efbits, c->d_out, 0);
-    ACX_HIP(c, hipGetLastError());
-    ACX_HIP(c, hipMemcpyAsync(sc, c->d_out, sizeof(float) * 4, hipMemcpyDeviceToHost, c->stream));
-    ACX_HIP(c, hipStreamSynchronize(c->stream));
-    *score = sc[0];
-    return ACX_OK;
+    return guarded(c, [&]() -> int {
+        if (!B || !score || M < 1 || N < 1) return fail(c, ACX_ERR_INVALID, "sw_bits_binary: bad argument");
+        if (M > acx::EF_MAXNB || N > acx::EF_MAXNB) return fail(c, ACX_ERR_INVALID, "sw_bits_binary: more than 1024 rows or columns (the bit kernels hold a row in one wave)");
+        int rc;
+        if ((rc = stage_ef_bit_plot(c, "", B, M, N, d, W)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_out, (size_t)4)) != ACX_OK) return rc;
+        if (N > 512) hipLaunchKernelGGL((acx::sw_bits_h16_kernel<16>), dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_efbits, c->d_out, 0);
+        else hipLaunchKernelGGL((acx::sw_bits_h16_kernel<8>), dim3(1, 1), dim3(64), 0, c->stream, c->d_efpd, c->d_efbits, c->d_out, 0);
+        ACX_HIP(c, hipGetLastError());
+        ACX_HIP(c, hipMemcpyAsync(sc, c->d_out, sizeof(float) * 4, hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        *score = sc[0];
+        return ACX_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3336,9 +3378,7 @@ int acx_ef_align(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_param
                  int64_t *path_off, int32_t *cells, int64_t cap)
 {
     if (!c) return ACX_ERR_INVALID;
-    const int rc = ef_align_impl(c, pairs, K, params, plane, out, path_off, cells, cap, false);
-    if (rc != ACX_OK) quiesce(c);                // nothing of a failed call stays in flight behind its error code
-    return rc;
+    return guarded(c, [&] { return ef_align_impl(c, pairs, K, params, plane, out, path_off, cells, cap, false); });
 }
 
 // The same for tracks of any length: a list without a track of more than 1024 blocks runs exactly as above; any
@@ -3347,136 +3387,64 @@ int acx_ef_align_long(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_
                       int64_t *path_off, int32_t *cells, int64_t cap)
 {
     if (!c) return ACX_ERR_INVALID;
-    const int rc = ef_align_impl(c, pairs, K, params, plane, out, path_off, cells, cap, true);
-    if (rc != ACX_OK) quiesce(c);                // nothing of a failed call stays in flight behind its error code
-    return rc;
+    return guarded(c, [&] { return ef_align_impl(c, pairs, K, params, plane, out, path_off, cells, cap, true); });
 }
 
-static int sw_align_binary_impl(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out, int32_t *cells, int64_t cap, int64_t *n_cells)
+// ef_align_kernel (acx_sw_align_binary: the plot as bit words, at most 1024 rows and columns) or ef_align_long_kernel
+// (acx_sw_align_long_binary, `any_size`: the plot as acx_sw_binary sets it up for sw_long_kernel) alone on a caller's plot: one job, no
+// profile entry; `who` names the entry point in errors.
+static int sw_align_plot(acx_ctx *c, const std::string &who, bool any_size, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out,
+                         int32_t *cells, int64_t cap, int64_t *n_cells)
 {
-    if (!B || !out || M < 1 || N < 1 || cap < 0 || (cells != nullptr) != (n_cells != nullptr)) return fail(c, ACX_ERR_INVALID, "sw_align_binary: bad argument");
-    if (M > acx::EF_MAXNB || N > acx::EF_MAXNB) return fail(c, ACX_ERR_UNSUPPORTED, std::string("sw_align_binary: ") + EF_ALIGN_TOO_LONG);
-    if (cells && cap < std::min(M, N))
-        return fail(c, ACX_ERR_INVALID, "sw_align_binary: cap " + std::to_string(cap) + " is too small: " + std::to_string(std::min(M, N)) +
-                                            " cells required (min(M, N))");
-    if (n_cells) *n_cells = 0;
     acx::EfPair d;
-    d.q = d.r = 0; d.M = M; d.N = N; d.oti = 0; d.pitchC = round_up(N, 64); d.pitchT = round_up(M, 64); d.kbin = 0;
-    d.ctN = 0; d.pad = 0; d.offB = 0; d.offC = 0; d.offS = 0;
-    // the layout the selection kernels leave in d_efbits: bit j % 32 of word j / 32, M rows of pitchC / 32 words, pads zero
-    const int words = d.pitchC / 32;
-    std::vector<uint32_t> W((size_t)M * words, 0u);
-    for (int i = 0; i < M; ++i)
-        for (int j = 0; j < N; ++j) {
-            const uint8_t b = B[(size_t)i * N + j];
-            if (b > 1) return fail(c, ACX_ERR_INVALID, "sw_align_binary: non-binary elements found in input");
-            W[(size_t)i * words + (j >> 5)] |= (uint32_t)b << (j & 31);
-        }
     acx::EfAlignJob job;
-    job.pair = 0; job.max_cells = std::min(M, N); job.dir_off = 0; job.cell_off = 0;
-    const size_t nres = (size_t)acx::EFA_REC + 2 * (size_t)job.max_cells;
-    std::vector<int32_t> res(nres);
-    int rc;
-    ACX_HIP(c, hipSetDevice(c->device));
-    if ((rc = ensure(c, c->d_efbits, W.size())) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_efpd, (size_t)1)) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_efjob, (size_t)1)) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_efdir, (size_t)acx::ef_align_dir_words(M, d.pitchC))) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_efres, nres)) != ACX_OK) return rc;
-    ACX_HIP(c, hipMemcpyAsync(c->d_efpd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
-    ACX_HIP(c, hipMemcpyAsync(c->d_efjob, &job, sizeof(job), hipMemcpyHostToDevice, c->stream));
-    ACX_HIP(c, hipMemcpyAsync(c->d_efbits, W.data(), sizeof(uint32_t) * W.size(), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(acx::ef_align_kernel, dim3(1), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, 0);
-    ACX_HIP(c, hipGetLastError());
-    ACX_HIP(c, hipMemcpyAsync(res.data(), c->d_efres, sizeof(int32_t) * (cells ? nres : (size_t)acx::EFA_REC), hipMemcpyDeviceToHost, c->stream));
-    ACX_HIP(c, hipStreamSynchronize(c->stream));
-    acx_alignment a;
-    memcpy(&a.score, res.data(), sizeof(float));
-    a.q0 = res[1]; a.r0 = res[2]; a.q1 = res[3]; a.r1 = res[4];
-    const int n = res[5];
-    if (n < 0 || n > job.max_cells || (a.score > 0.0f) != (n >= 1))
-        return fail(c, ACX_ERR_STATE, "sw_align_binary: the traceback returned " + std::to_string(n) + " cells");
-    *out = a;
-    if (cells) {
-        const int32_t *src = res.data() + acx::EFA_REC;             // the traceback wrote the cells end first
-        if (n >= 1 && (src[0] != a.q1 || src[1] != a.r1 || src[2 * (n - 1)] != a.q0 || src[2 * (n - 1) + 1] != a.r0))
-            return fail(c, ACX_ERR_STATE, "sw_align_binary: the traceback does not run from the reported end to the reported start");
-        for (int e = 0; e < n; ++e) { cells[2 * (size_t)e] = src[2 * (n - 1 - e)]; cells[2 * (size_t)e + 1] = src[2 * (n - 1 - e) + 1]; }
-        *n_cells = n;
-    }
-    return ACX_OK;
+    std::vector<uint32_t> W;
+    std::vector<float> Cm;
+    std::vector<int32_t> res;
+    return guarded(c, [&]() -> int {
+        if (!B || !out || M < 1 || N < 1 || cap < 0 || (cells != nullptr) != (n_cells != nullptr)) return fail(c, ACX_ERR_INVALID, who + ": bad argument");
+        if (!any_size && (M > acx::EF_MAXNB || N > acx::EF_MAXNB)) return fail(c, ACX_ERR_UNSUPPORTED, who + ": " + EF_ALIGN_TOO_LONG);
+        if (cells && cap < std::min(M, N))
+            return fail(c, ACX_ERR_INVALID, who + ": cap " + std::to_string(cap) + " is too small: " + std::to_string(std::min(M, N)) +
+                                                " cells required (min(M, N))");
+        if (n_cells) *n_cells = 0;
+        int rc = any_size ? stage_ef_float_plot(c, who, B, M, N, d, Cm) : stage_ef_bit_plot(c, who, B, M, N, d, W);
+        if (rc != ACX_OK) return rc;
+        job.pair = 0; job.max_cells = std::min(M, N); job.dir_off = 0; job.cell_off = 0;
+        const size_t nres = (size_t)acx::EFA_REC + 2 * (size_t)job.max_cells;
+        res.resize(nres);
+        if ((rc = ensure(c, c->d_efjob, (size_t)1)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_efdir, (size_t)(any_size ? acx::ef_align_long_dir_words(M, N) : acx::ef_align_dir_words(M, d.pitchC)))) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_efres, nres)) != ACX_OK) return rc;
+        ACX_HIP(c, hipMemcpyAsync(c->d_efjob, &job, sizeof(job), hipMemcpyHostToDevice, c->stream));
+        if (any_size)
+            hipLaunchKernelGGL(acx::ef_align_long_kernel, dim3(1), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_scratch, c->d_thr, c->d_efdir, c->d_efres, 0);
+        else
+            hipLaunchKernelGGL(acx::ef_align_kernel, dim3(1), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, 0);
+        ACX_HIP(c, hipGetLastError());
+        ACX_HIP(c, hipMemcpyAsync(res.data(), c->d_efres, sizeof(int32_t) * (cells ? nres : (size_t)acx::EFA_REC), hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        std::vector<int32_t> path;
+        if ((rc = decode_ef_alignment(c, who, "", res.data(), res.data() + acx::EFA_REC, job.max_cells, nullptr, *out, cells ? &path : nullptr)) != ACX_OK)
+            return rc;
+        if (cells) {
+            if (!path.empty()) memcpy(cells, path.data(), sizeof(int32_t) * path.size());
+            *n_cells = (int64_t)path.size() / 2;
+        }
+        return ACX_OK;
+    });
 }
 
 int acx_sw_align_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out, int32_t *cells, int64_t cap, int64_t *n_cells)
 {
     if (!c) return ACX_ERR_INVALID;
-    const int rc = sw_align_binary_impl(c, B, M, N, out, cells, cap, n_cells);
-    if (rc != ACX_OK) quiesce(c);                // the queued copies read this call's host buffers: none stays in flight behind an error
-    return rc;
-}
-
-// ef_align_long_kernel alone on a caller's plot of ANY size, set up as acx_sw_binary sets up sw_long_kernel: the plot as a 0 / 1 float
-// matrix (1 - B), thresholds 0, every tie counted.
-static int sw_align_long_binary_impl(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out, int32_t *cells, int64_t cap, int64_t *n_cells)
-{
-    if (!B || !out || M < 1 || N < 1 || cap < 0 || (cells != nullptr) != (n_cells != nullptr)) return fail(c, ACX_ERR_INVALID, "sw_align_long_binary: bad argument");
-    if (cells && cap < std::min(M, N))
-        return fail(c, ACX_ERR_INVALID, "sw_align_long_binary: cap " + std::to_string(cap) + " is too small: " + std::to_string(std::min(M, N)) +
-                                            " cells required (min(M, N))");
-    if (n_cells) *n_cells = 0;
-    std::vector<float> Cm((size_t)M * N);
-    for (size_t k = 0; k < Cm.size(); ++k) {
-        if (B[k] > 1) return fail(c, ACX_ERR_INVALID, "sw_align_long_binary: non-binary elements found in input");
-        Cm[k] = B[k] ? 0.0f : 1.0f;         // B = [C <= threshold] with threshold 0
-    }
-    acx::EfPair d;
-    d.q = d.r = 0; d.M = M; d.N = N; d.oti = 0; d.pitchC = round_up(N, 64); d.pitchT = round_up(M, 64); d.kbin = 0;
-    d.ctN = 0; d.pad = 0; d.offB = 0; d.offC = 0; d.offS = 0;
-    acx::EfAlignJob job;
-    job.pair = 0; job.max_cells = std::min(M, N); job.dir_off = 0; job.cell_off = 0;
-    const size_t nres = (size_t)acx::EFA_REC + 2 * (size_t)job.max_cells;
-    std::vector<int32_t> res(nres);
-    int rc;
-    ACX_HIP(c, hipSetDevice(c->device));
-    if ((rc = ensure(c, c->d_scratch, (size_t)M * d.pitchC)) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_thr, (size_t)acx::ef_s_total(d))) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_efpd, (size_t)1)) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_efjob, (size_t)1)) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_efdir, (size_t)acx::ef_align_long_dir_words(M, N))) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_efres, nres)) != ACX_OK) return rc;
-    ACX_HIP(c, hipMemcpyAsync(c->d_efpd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
-    ACX_HIP(c, hipMemcpyAsync(c->d_efjob, &job, sizeof(job), hipMemcpyHostToDevice, c->stream));
-    ACX_HIP(c, hipMemcpy2DAsync(c->d_scratch, sizeof(float) * d.pitchC, Cm.data(), sizeof(float) * N, sizeof(float) * N, M,
-                                hipMemcpyHostToDevice, c->stream));
-    ACX_HIP(c, hipMemsetAsync(c->d_thr, 0, sizeof(float) * M, c->stream));
-    ACX_HIP(c, hipMemsetAsync(c->d_thr + acx::ef_jcut_off(d, 0), 0x7f, sizeof(int) * M, c->stream));   // every tie counts
-    hipLaunchKernelGGL(acx::ef_align_long_kernel, dim3(1), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_scratch, c->d_thr, c->d_efdir, c->d_efres, 0);
-    ACX_HIP(c, hipGetLastError());
-    ACX_HIP(c, hipMemcpyAsync(res.data(), c->d_efres, sizeof(int32_t) * (cells ? nres : (size_t)acx::EFA_REC), hipMemcpyDeviceToHost, c->stream));
-    ACX_HIP(c, hipStreamSynchronize(c->stream));
-    acx_alignment a;
-    memcpy(&a.score, res.data(), sizeof(float));
-    a.q0 = res[1]; a.r0 = res[2]; a.q1 = res[3]; a.r1 = res[4];
-    const int n = res[5];
-    if (n < 0 || n > job.max_cells || (a.score > 0.0f) != (n >= 1))
-        return fail(c, ACX_ERR_STATE, "sw_align_long_binary: the traceback returned " + std::to_string(n) + " cells");
-    *out = a;
-    if (cells) {
-        const int32_t *src = res.data() + acx::EFA_REC;             // the traceback wrote the cells end first
-        if (n >= 1 && (src[0] != a.q1 || src[1] != a.r1 || src[2 * (n - 1)] != a.q0 || src[2 * (n - 1) + 1] != a.r0))
-            return fail(c, ACX_ERR_STATE, "sw_align_long_binary: the traceback does not run from the reported end to the reported start");
-        for (int e = 0; e < n; ++e) { cells[2 * (size_t)e] = src[2 * (n - 1 - e)]; cells[2 * (size_t)e + 1] = src[2 * (n - 1 - e) + 1]; }
-        *n_cells = n;
-    }
-    return ACX_OK;
+    return sw_align_plot(c, "sw_align_binary", false, B, M, N, out, cells, cap, n_cells);
 }
 
 int acx_sw_align_long_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out, int32_t *cells, int64_t cap, int64_t *n_cells)
 {
     if (!c) return ACX_ERR_INVALID;
-    const int rc = sw_align_long_binary_impl(c, B, M, N, out, cells, cap, n_cells);
-    if (rc != ACX_OK) quiesce(c);                // the queued copies read this call's host buffers: none stays in flight behind an error
-    return rc;
+    return sw_align_plot(c, "sw_align_long_binary", true, B, M, N, out, cells, cap, n_cells);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3826,8 +3794,8 @@ static int with_device_block(acx_ctx *c, const char *who, size_t total, F body)
     DeviceBuffer<char> d_mem;
     const hipError_t e = d_mem.grow(total);
     if (e != hipSuccess) return fail(c, ACX_ERR_NOMEM, std::string(who) + ": " + hipGetErrorString(e));
-    const int rc = body(d_mem.get());
-    if (rc != ACX_OK) quiesce(c); else drain_profile(c);
+    const int rc = guarded(c, [&] { return body(d_mem.get()); });
+    if (rc == ACX_OK) drain_profile(c);
     return rc;
 }
 }  // extern "C++"
@@ -4309,8 +4277,7 @@ static int xf_alloc(acx_ctx *c, XfRun &xr, int maxM, int maxN, int maxn, int K)
 static int xf_select_sw(acx_ctx *c, XfRun &xr, int M, int N, int kbin, const XfTaps &tap)
 {
     acx::EfPair &d = xr.desc;
-    d.q = d.r = 0; d.M = M; d.N = N; d.oti = 0; d.pitchC = round_up(N, 64); d.pitchT = round_up(M, 64); d.kbin = kbin;
-    d.ctN = 0; d.pad = 0; d.offB = 0; d.offC = 0; d.offS = 0;
+    d = ef_one_pair(M, N, kbin);
     ACX_HIP(c, hipMemcpyAsync(c->d_efpd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
     {
         ProfScope ps(c, KS_XFSELECT, (int64_t)M * N);
@@ -4460,9 +4427,7 @@ int acx_ef_crossfusion_pairs(acx_ctx *c, const int32_t *pairs, int64_t K_pairs, 
                              double reg_diag, float *out)
 {
     if (!c) return ACX_ERR_INVALID;
-    const int rc = xf_pairs_impl(c, pairs, K_pairs, params, niters, reg_diag, out, nullptr);
-    if (rc != ACX_OK) quiesce(c);                // nothing of a failed call stays in flight behind its error code
-    return rc;
+    return guarded(c, [&] { return xf_pairs_impl(c, pairs, K_pairs, params, niters, reg_diag, out, nullptr); });
 }
 
 int acx_ef_crossfusion_debug(acx_ctx *c, int32_t i, int32_t j, const acx_ef_params *params, int32_t niters, double reg_diag,
@@ -4473,9 +4438,8 @@ int acx_ef_crossfusion_debug(acx_ctx *c, int32_t i, int32_t j, const acx_ef_para
     float sc = 0.0f;
     XfPairDebug dbg{ssm_a, ssm_b, csm, XfTaps()};
     dbg.tap.W = W; dbg.tap.D = D; dbg.tap.X = X; dbg.tap.bits = bits;
-    const int rc = xf_pairs_impl(c, pr, 1, params, niters, reg_diag, &sc, &dbg);
-    if (rc != ACX_OK) quiesce(c);
-    else if (score) *score = sc;
+    const int rc = guarded(c, [&] { return xf_pairs_impl(c, pr, 1, params, niters, reg_diag, &sc, &dbg); });
+    if (rc == ACX_OK && score) *score = sc;
     return rc;
 }
 
@@ -4514,9 +4478,7 @@ int acx_crossfusion_matrices(acx_ctx *c, const float *SA, const float *SB, const
     if (!c) return ACX_ERR_INVALID;
     XfTaps tap;
     tap.r = r; tap.c = cm; tap.W = W; tap.D = D; tap.X = X; tap.bits = bits;
-    const int rc = xf_matrices_impl(c, SA, SB, C, M, N, kappa, K, niters, reg_diag, tap, score);
-    if (rc != ACX_OK) quiesce(c);
-    return rc;
+    return guarded(c, [&] { return xf_matrices_impl(c, SA, SB, C, M, N, kappa, K, niters, reg_diag, tap, score); });
 }
 
 static int xf_xsel_impl(acx_ctx *c, const double *X, int32_t M, int32_t N, double kappa, uint32_t *bits, float *score)
@@ -4546,9 +4508,7 @@ static int xf_xsel_impl(acx_ctx *c, const double *X, int32_t M, int32_t N, doubl
 int acx_xsel_binary_sw(acx_ctx *c, const double *X, int32_t M, int32_t N, double kappa, uint32_t *bits, float *score)
 {
     if (!c) return ACX_ERR_INVALID;
-    const int rc = xf_xsel_impl(c, X, M, N, kappa, bits, score);
-    if (rc != ACX_OK) quiesce(c);
-    return rc;
+    return guarded(c, [&] { return xf_xsel_impl(c, X, M, N, kappa, bits, score); });
 }
 
 // ---------------------------------------------------------------------------------------

@@ -393,13 +393,8 @@ __global__ __launch_bounds__(64) void dmax_path_kernel(const PairDesc *__restric
                 if (e >= 16) hi |= code << (2 * (e - 16)); else lo |= code << (2 * e);
             }
             wprev = wraw;
-            if (has_word) plane[(size_t)y * nwords + word] = ((unsigned long long)hi << 32) | lo;
-            if (more && lane == 63) {
-                PathSeam o;
-                o.q1 = QB[CPL - 1]; o.q2 = QB[CPL - 2];
-                o.p1 = EQG ? 0.0f : PB[NP - 1]; o.p2 = EQG ? 0.0f : PB[EQG ? 0 : NP - 2];
-                bout[y] = o;
-            }
+            if (has_word) path_store_codes(plane, y, nwords, word, lo, hi);
+            if (more && lane == 63) path_store_seam<EQG>(bout, y, QB, PB);
             recB = recA; recA = recN;
         };
 
@@ -419,21 +414,7 @@ __global__ __launch_bounds__(64) void dmax_path_kernel(const PairDesc *__restric
         __threadfence();       // the next strip reads this one's records, the traceback the whole plane: same wave, but through memory
     }
 
-    // The traceback (qmax_path_kernel's): from the box's last cell along the codes until a cell has none, the cells written end first.
-    if (lane == 0) {
-        int y = H - 1, x = Wd - 1, n = 0;
-        int32_t *out = cells + 2 * bx.cell_off;
-        while (n < bx.max_cells && y >= 0 && x >= 0) {
-            out[2 * n] = bx.q0 + y; out[2 * n + 1] = bx.r0 + x;
-            ++n;
-            const unsigned long long wd = __hip_atomic_load(plane + (size_t)y * nwords + (x >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned code = (unsigned)(wd >> (2 * (x & 31))) & 3u;
-            if (code == 0u) break;
-            y -= (code == 2u) ? 2 : 1;
-            x -= (code == 3u) ? 2 : 1;
-        }
-        n_cells[blockIdx.x] = n;
-    }
+    if (lane == 0) n_cells[blockIdx.x] = path_traceback(plane, nwords, bx, H, Wd, cells + 2 * bx.cell_off);
 }
 
 }  // namespace acx

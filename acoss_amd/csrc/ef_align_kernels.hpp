@@ -39,6 +39,42 @@ struct EfAlignJob {
 
 __host__ __device__ __forceinline__ int64_t ef_align_dir_words(int M, int pitch) { return (int64_t)M * (pitch / EFA_CPL); }
 
+// The traceback of both kernels, on ONE lane behind the fence that makes the other lanes' codes visible: from the end cell (y1, x1)
+// along the codes of `plane` (wpr words a row, word j / 16 of a row holds column j) while a cell has one, at most max_cells cells,
+// written to dst END FIRST.  Returns the number of cells and the start in (y0, x0).  The path stays inside the counted rectangle
+// (every step lowers row and column; a predecessor outside rows [2, M-2] x columns [2, N-2] has T = 0 and ends it), and the bounds
+// keep a plane that broke that promise from being read outside, or the job's cells from being written outside.
+// (The listings of both kernels are held instruction for instruction: they follow the order in which x, y and n are declared here, and
+// the record's passing by value below.)
+__device__ __forceinline__ int ef_align_traceback(const unsigned *plane, int64_t wpr, int M, int N, int y1, int x1, int max_cells, int32_t *dst,
+                                                  int &y0, int &x0)
+{
+    auto code_at = [&](int yy, int xx) -> unsigned {
+        const unsigned wd = __hip_atomic_load(plane + (size_t)yy * wpr + (xx >> 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return (wd >> (2 * (xx & 15))) & 3u;
+    };
+    int x = x1, y = y1, n = 0;
+    if (y >= 2 && y <= M - 2 && x >= 2 && x <= N - 2) {
+        unsigned code = code_at(y, x);
+        while (code != 0u && n < max_cells) {
+            dst[2 * n] = y; dst[2 * n + 1] = x;
+            ++n;
+            const int py = y - (code == 2u ? 2 : 1), px = x - (code == 3u ? 2 : 1);
+            if (py < 2 || px < 2) break;                             // rows / columns 0, 1: T = 0
+            code = code_at(py, px);                                  // 0: T == 0 there, (y, x) was the start
+            if (code != 0u) { y = py; x = px; }
+        }
+    }
+    y0 = y; x0 = x;
+    return n;
+}
+
+// A job's result: the acx_alignment record (score's bits, q0, r0, q1, r1) and the number of cells.
+__device__ __forceinline__ void ef_align_store(int32_t *rec, const acx_alignment a, int n)
+{
+    rec[0] = __float_as_int(a.score); rec[1] = a.q0; rec[2] = a.r0; rec[3] = a.q1; rec[4] = a.r1; rec[5] = n;
+}
+
 __global__ __launch_bounds__(64) void ef_align_kernel(const EfPair *__restrict__ pd, const EfAlignJob *__restrict__ jobs,
                                                       const unsigned *__restrict__ bits, unsigned *dir,
                                                       int32_t *__restrict__ res, int plane)
@@ -136,25 +172,7 @@ __global__ __launch_bounds__(64) void ef_align_kernel(const EfPair *__restrict__
         __threadfence();
         if (lane == 0 && best > 0) {
             int y = best_cell / EF_MAXNB, x = best_cell % EF_MAXNB;
-            int32_t *dst = cells + 2 * job.cell_off;
-            // It stays inside the counted rectangle (every step lowers row and column; a predecessor outside rows [2, M-2] x
-            // columns [2, N-2] has T = 0 and ends the path), and the bounds keep a plane that broke that promise from being read
-            // or written outside.
-            auto code_at = [&](int yy, int xx) -> unsigned {
-                const unsigned wd = __hip_atomic_load(my_dir + (size_t)yy * wpr + (xx >> 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return (wd >> (2 * (xx & 15))) & 3u;
-            };
-            if (y >= 2 && y <= M - 2 && x >= 2 && x <= N - 2) {
-                unsigned code = code_at(y, x);
-                while (code != 0u && n < job.max_cells) {
-                    dst[2 * n] = y; dst[2 * n + 1] = x;
-                    ++n;
-                    const int py = y - (code == 2u ? 2 : 1), px = x - (code == 3u ? 2 : 1);
-                    if (py < 2 || px < 2) break;                     // rows / columns 0, 1: T = 0
-                    code = code_at(py, px);                          // 0: T == 0 there, (y, x) was the start
-                    if (code != 0u) { y = py; x = px; }
-                }
-            }
+            n = ef_align_traceback(my_dir, wpr, M, N, y, x, job.max_cells, cells + 2 * job.cell_off, y, x);
             a.score = (float)best / 10.0f;                           // (a positive score without a cell: the driver reports it)
             if (n > 0) {
                 a.q1 = best_cell / EF_MAXNB; a.r1 = best_cell % EF_MAXNB;
@@ -162,10 +180,7 @@ __global__ __launch_bounds__(64) void ef_align_kernel(const EfPair *__restrict__
             }
         }
     }
-    if (lane == 0) {
-        int32_t *rec = res + (size_t)EFA_REC * blockIdx.x;
-        rec[0] = __float_as_int(a.score); rec[1] = a.q0; rec[2] = a.r0; rec[3] = a.q1; rec[4] = a.r1; rec[5] = n;
-    }
+    if (lane == 0) ef_align_store(res + (size_t)EFA_REC * blockIdx.x, a, n);
 }
 
 // The same alignment on the FLOAT path, for plots of any size: a batch that holds a track of more than
@@ -302,24 +317,7 @@ __global__ __launch_bounds__(64) void ef_align_long_kernel(const EfPair *__restr
         }
         if (lane == 0 && bT > 0) {
             int y = bRow, x = bCol;
-            int32_t *dst = cells + 2 * job.cell_off;
-            // as in ef_align_kernel: every step lowers row and column, a predecessor outside rows [2, M-2] x columns [2, N-2] ends
-            // the path, and the bounds keep a wrong code from reading outside the plane or writing outside the job's cells
-            auto code_at = [&](int yy, int xx) -> unsigned {
-                const unsigned wd = __hip_atomic_load(my_dir + yy * wpr + (xx >> 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return (wd >> (2 * (xx & 15))) & 3u;
-            };
-            if (y >= 2 && y <= M - 2 && x >= 2 && x <= N - 2) {
-                unsigned code = code_at(y, x);
-                while (code != 0u && n < job.max_cells) {
-                    dst[2 * n] = y; dst[2 * n + 1] = x;
-                    ++n;
-                    const int py = y - (code == 2u ? 2 : 1), px = x - (code == 3u ? 2 : 1);
-                    if (py < 2 || px < 2) break;                     // rows / columns 0, 1: T = 0
-                    code = code_at(py, px);                          // 0: T == 0 there, (y, x) was the start
-                    if (code != 0u) { y = py; x = px; }
-                }
-            }
+            n = ef_align_traceback(my_dir, wpr, M, N, y, x, job.max_cells, cells + 2 * job.cell_off, y, x);
             a.score = (float)bT / 10.0f;                             // sw_long_kernel's expression: the same bits
             if (n > 0) {
                 a.q1 = bRow; a.r1 = bCol;
@@ -327,10 +325,7 @@ __global__ __launch_bounds__(64) void ef_align_long_kernel(const EfPair *__restr
             }
         }
     }
-    if (lane == 0) {
-        int32_t *out = res + (size_t)EFA_REC * blockIdx.x;
-        out[0] = __float_as_int(a.score); out[1] = a.q0; out[2] = a.r0; out[3] = a.q1; out[4] = a.r1; out[5] = n;
-    }
+    if (lane == 0) ef_align_store(res + (size_t)EFA_REC * blockIdx.x, a, n);
 }
 
 }  // namespace acx

@@ -46,6 +46,41 @@ inline int64_t path_box_bytes(int rows, int width)
     return (int64_t)rows * path_words(width) * 8 + (path_strips(width) > 1 ? 2 * (int64_t)rows * (int64_t)sizeof(PathSeam) : 0);
 }
 
+// A lane's codes of box row y (column e at bits [2 e, 2 e + 2) of hi : lo), as one word of the row's plane.
+__device__ __forceinline__ void path_store_codes(unsigned long long *plane, int y, int nwords, int word, unsigned lo, unsigned hi)
+{
+    plane[(size_t)y * nwords + word] = ((unsigned long long)hi << 32) | lo;
+}
+
+// What lane 63 leaves of box row y for the next strip (EQG: no penalised values, PB has one element that is not read).
+template <bool EQG, int NP>
+__device__ __forceinline__ void path_store_seam(PathSeam *bout, int y, const float (&QB)[PATH_CPL], const float (&PB)[NP])
+{
+    PathSeam o;
+    o.q1 = QB[PATH_CPL - 1]; o.q2 = QB[PATH_CPL - 2];
+    o.p1 = EQG ? 0.0f : PB[NP - 1]; o.p2 = EQG ? 0.0f : PB[EQG ? 0 : NP - 2];
+    bout[y] = o;
+}
+
+// The traceback of a box of H rows and Wd columns, on one lane behind the last strip's fence: from the box's last cell along the codes
+// until a cell has none; the cells are written END FIRST, their number is returned.  It never leaves the box (every step lowers row and
+// column, and a cell of the path has its predecessor in the box: the box property); the bounds keep a plane that broke that promise
+// from being read or written outside.  (n, x, y are declared in this order: the four kernels' listings follow it.)
+__device__ __forceinline__ int path_traceback(const unsigned long long *plane, int nwords, const PathBox &bx, int H, int Wd, int32_t *out)
+{
+    int n = 0, x = Wd - 1, y = H - 1;
+    while (n < bx.max_cells && y >= 0 && x >= 0) {
+        out[2 * n] = bx.q0 + y; out[2 * n + 1] = bx.r0 + x;
+        ++n;
+        const unsigned long long wd = __hip_atomic_load(plane + (size_t)y * nwords + (x >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned code = (unsigned)(wd >> (2 * (x & 31))) & 3u;
+        if (code == 0u) break;
+        y -= (code == 2u) ? 2 : 1;
+        x -= (code == 3u) ? 2 : 1;
+    }
+    return n;
+}
+
 template <bool EQG>
 __global__ __launch_bounds__(64) void qmax_path_kernel(const PairDesc *__restrict__ pd, const PathBox *__restrict__ boxes,
                                                        const unsigned long long *__restrict__ bits,
@@ -153,13 +188,8 @@ __global__ __launch_bounds__(64) void qmax_path_kernel(const PairDesc *__restric
                 if constexpr (!EQG) PB[e] = q - (r ? go : ge);
                 if (e >= 16) hi |= code << (2 * (e - 16)); else lo |= code << (2 * e);
             }
-            if (has_word) plane[(size_t)y * nwords + word] = ((unsigned long long)hi << 32) | lo;
-            if (more && lane == 63) {
-                PathSeam o;
-                o.q1 = QB[CPL - 1]; o.q2 = QB[CPL - 2];
-                o.p1 = EQG ? 0.0f : PB[NP - 1]; o.p2 = EQG ? 0.0f : PB[EQG ? 0 : NP - 2];
-                bout[y] = o;
-            }
+            if (has_word) path_store_codes(plane, y, nwords, word, lo, hi);
+            if (more && lane == 63) path_store_seam<EQG>(bout, y, QB, PB);
             recB = recA; recA = recN;
         };
 
@@ -180,23 +210,7 @@ __global__ __launch_bounds__(64) void qmax_path_kernel(const PairDesc *__restric
         __threadfence();
     }
 
-    // The traceback, on one lane: from the box's last cell along the codes until a cell has none.  The cells are written end first.
-    // It never leaves the box (every step lowers row and column, and a cell of the path has its predecessor in the box: the box
-    // property); the bounds below keep a plane that broke that promise from being read or written outside.
-    if (lane == 0) {
-        int y = H - 1, x = Wd - 1, n = 0;
-        int32_t *out = cells + 2 * bx.cell_off;
-        while (n < bx.max_cells && y >= 0 && x >= 0) {
-            out[2 * n] = bx.q0 + y; out[2 * n + 1] = bx.r0 + x;
-            ++n;
-            const unsigned long long wd = __hip_atomic_load(plane + (size_t)y * nwords + (x >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned code = (unsigned)(wd >> (2 * (x & 31))) & 3u;
-            if (code == 0u) break;
-            y -= (code == 2u) ? 2 : 1;
-            x -= (code == 3u) ? 2 : 1;
-        }
-        n_cells[blockIdx.x] = n;
-    }
+    if (lane == 0) n_cells[blockIdx.x] = path_traceback(plane, nwords, bx, H, Wd, cells + 2 * bx.cell_off);
 }
 
 }  // namespace acx

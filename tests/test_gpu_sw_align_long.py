@@ -136,6 +136,32 @@ def test_refusals_leave_the_context_usable(ctx):
     _check_dp(ctx, B, "after the refusals")
 
 
+def test_stand_alone_exports_share_the_decode_and_record_no_profile(ctx):
+    """acx_sw_align_binary and acx_sw_align_long_binary are one driver function over the batch path's decode: the records and cells
+    are the reference's with and without paths, and no profile entry counts a launch (the batch path's bookkeeping is not shared)."""
+    small = np.zeros((6, 7), np.uint8)
+    small[np.arange(6), np.arange(6)] = 1                     # counted rows 2..4: (2, 2), (3, 3), (4, 4), 10 tenths a cell
+    wide = np.zeros((5, 1030), np.uint8)
+    wide[np.arange(5), 1021 + np.arange(5)] = 1               # counted rows 2..3: (2, 1023), (3, 1024), across the two strips
+    assert ref.align_forward(small)[0] == (np.float32(3.0), 2, 2, 4, 4) and ref.align_forward(small)[1].tolist() == [[2, 2], [3, 3], [4, 4]]
+    assert ref.align_forward(wide)[1].tolist() == [[2, 1023], [3, 1024]]
+    ctx.profile_enable(True)
+    try:
+        ctx.profile_reset()
+        for name, call, B in (("bits 6 x 7", ctx.sw_align_binary, small), ("long 6 x 7", ctx.sw_align_long_binary, small),
+                              ("long 5 x 1030", ctx.sw_align_long_binary, wide)):
+            wrec, wcells = ref.align_forward(B)
+            al, cells = call(B)
+            assert _same(_rec(al[0]), wrec) and np.array_equal(cells, wcells), (name, _rec(al[0]), wrec, cells.tolist(), wcells.tolist())
+            assert cells.dtype == np.int32 and cells.shape == (len(wcells), 2), name
+            alone = call(B, paths=False)
+            assert alone.shape == (1,) and alone.tobytes() == al.tobytes(), (name, "record alone")
+        prof = ctx.profile()
+        assert len(prof) > 0 and all(v["launches"] == 0 for v in prof.values()), prof
+    finally:
+        ctx.profile_enable(False)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # b. the product path
 # ------------------------------------------------------------------------------------------------------------------
