@@ -376,14 +376,11 @@ class CoverAlgorithm(object):
         Fused types need the whole matrix: NotImplementedError.  Not a collective: under a process group every rank
         that calls it computes on its own GPU."""
         q, types = self._query_setup("identify", queries, similarity_types)
-        k = int(k)
-        if k < 1:
-            raise ValueError("identify: k must be >= 1 (got %d)" % k)
+        k = self._check_k("identify", k)
         cands = self._check_candidates("identify", candidates, "track indices")
         ctx, algo, params, mode, col = self._query_call()
         idx, score = ctx.query_topk(algo, self._identify_symmetric, params, q, k, candidates=cands, col=col, col_mode=mode)
-        planes = list(self._identify_planes)
-        return {t: (np.ascontiguousarray(idx[:, planes.index(t)]), np.ascontiguousarray(score[:, planes.index(t)])) for t in types}
+        return self._by_type(idx, score, types)
 
     def query_rows(self, queries, similarity_types=None):
         """The same rows in full: {type: (Q, N) float32}, the finished scores of every query against every track (its
@@ -548,9 +545,7 @@ class CoverAlgorithm(object):
         listed score belongs to, (hit, new track) = (idx[i, s], N + i): in al and paths the QUERY side (q0, q1, q_span, path
         column 0) is the hit and the REFERENCE side the new track, and al['score'] has the bits of score."""
         who = "locate_tracks"
-        k = int(k)
-        if k < 1:
-            raise ValueError("%s: k must be >= 1 (got %d)" % (who, k))
+        k = self._check_k(who, k)
         t = (self._locate_type or self._identify_planes[0]) if similarity_type is None else similarity_type
         kw = self._align_kw(who, t)
         if paths and not hasattr(self, "align_match_paths"):
@@ -589,16 +584,13 @@ class CoverAlgorithm(object):
 
     def _identify_tracks(self, tracks, k, candidates, similarity_types, **how):
         """identify_tracks(); how: the options of the class's own track format, handed to its _check_tracks."""
-        k = int(k)
-        if k < 1:
-            raise ValueError("identify_tracks: k must be >= 1 (got %d)" % k)
+        k = self._check_k("identify_tracks", k)
         checked, Q, types, cands = self._tracks_setup("identify_tracks", tracks, similarity_types, candidates, how)
         if cands is None:
             cands = np.arange(self.N, dtype=np.int32)
         idx, score = self._with_appended(checked, Q, lambda ctx, algo, params, mode, col, q: ctx.query_topk(
             algo, self._identify_symmetric, params, q, k, candidates=cands, col=col, col_mode=mode))
-        planes = list(self._identify_planes)
-        return {t: (np.ascontiguousarray(idx[:, planes.index(t)]), np.ascontiguousarray(score[:, planes.index(t)])) for t in types}
+        return self._by_type(idx, score, types)
 
     @refused_in_session
     def score_tracks(self, tracks, similarity_types=None):
@@ -631,6 +623,13 @@ class CoverAlgorithm(object):
             raise ValueError("%s: shortlists row %d lists track %d twice" % (who, r, srt[r, j + 1]))
         return lists.astype(np.int32)
 
+    @staticmethod
+    def _check_k(who, k):
+        k = int(k)
+        if k < 1:
+            raise ValueError("%s: k must be >= 1 (got %d)" % (who, k))
+        return k
+
     def _by_type(self, idx, score, types):
         planes = list(self._identify_planes)
         return {t: (np.ascontiguousarray(idx[:, planes.index(t)]), np.ascontiguousarray(score[:, planes.index(t)])) for t in types}
@@ -644,9 +643,7 @@ class CoverAlgorithm(object):
         are computed (acx_query_topk_lists), in bands that are not limited to 128 rows.  `Ds` is not written.  Not a
         collective."""
         q, types = self._query_setup("rerank", queries, similarity_types)
-        k = int(k)
-        if k < 1:
-            raise ValueError("rerank: k must be >= 1 (got %d)" % k)
+        k = self._check_k("rerank", k)
         lists = self._check_shortlists("rerank", shortlists, len(q))
         ctx, algo, params, mode, col = self._query_call()
         idx, score = ctx.query_topk_lists(algo, self._identify_symmetric, params, q, lists, k, col=col, col_mode=mode)
@@ -661,9 +658,7 @@ class CoverAlgorithm(object):
         shortlist = int(shortlist)
         if shortlist < 1 or shortlist > 1024:
             raise ValueError("identify_cascade: shortlist must be in 1..1024 (got %d)" % shortlist)
-        k = int(k)
-        if k < 1:
-            raise ValueError("identify_cascade: k must be >= 1 (got %d)" % k)
+        k = self._check_k("identify_cascade", k)
         q, _ = self._query_setup("identify_cascade", queries, similarity_types)
         first_type = first._identify_planes[0] if first_type is None else first_type
         first._query_setup("identify_cascade", q, [first_type])
@@ -678,9 +673,7 @@ class CoverAlgorithm(object):
         return self._rerank_tracks(tracks, shortlists, k, similarity_types)
 
     def _rerank_tracks(self, tracks, shortlists, k, similarity_types, **how):
-        k = int(k)
-        if k < 1:
-            raise ValueError("rerank_tracks: k must be >= 1 (got %d)" % k)
+        k = self._check_k("rerank_tracks", k)
         checked, Q, types, _ = self._tracks_setup("rerank_tracks", tracks, similarity_types, None, how)
         lists = self._check_shortlists("rerank_tracks", shortlists, Q)
         idx, score = self._with_appended(checked, Q, lambda ctx, algo, params, mode, col, q: ctx.query_topk_lists(

@@ -189,9 +189,7 @@ class EarlyFusion(CoverAlgorithm):
         a query's own track is skipped.  Only the listed cells are computed.  `Ds` is not written.  Not a collective."""
         self._check_full_fusion("rerank_full")
         q, _ = self._query_setup("rerank_full", queries, None)
-        k = int(k)
-        if k < 1:
-            raise ValueError("rerank_full: k must be >= 1 (got %d)" % k)
+        k = self._check_k("rerank_full", k)
         lists = self._check_shortlists("rerank_full", shortlists, len(q))
         idx = np.full((len(q), k), -1, np.int32)
         score = np.full((len(q), k), np.nan, np.float32)

@@ -37,6 +37,7 @@
 #include "rank_kernels.hpp"
 #include "query_kernels.hpp"
 #include "grid.hpp"
+#include "query_plan.hpp"
 #include "serra09_plan.hpp"
 #include "device_buffer.hpp"
 
@@ -5222,6 +5223,83 @@ static int run_ftm2d_tiles(acx_ctx *c, const std::vector<acx_grid_tile> &mine, i
     return ACX_OK;
 }
 
+// A pair list whose scores stay on the device, a chunk at a time: the chunk's pairs to c->d_pairs, its destinations to
+// c->d_idx, then score(n) -- the pair kernel into d_out (room for a chunk) and the scatter from there to the destinations.
+extern "C++" {
+template <typename T, typename S>
+static int run_list_chunks(acx_ctx *c, const int32_t *pairs, const int64_t *idx, int64_t K, DeviceBuffer<T> &d_out, S score)
+{
+    const int64_t CHUNK = (int64_t)1 << 22;
+    int rc;
+    if ((rc = ensure(c, c->d_pairs, (size_t)2 * std::min(K, CHUNK))) != ACX_OK) return rc;
+    if ((rc = ensure(c, d_out, (size_t)std::min(K, CHUNK))) != ACX_OK) return rc;
+    for (int64_t k0 = 0; k0 < K; k0 += CHUNK) {
+        const int n = (int)std::min(CHUNK, K - k0);
+        ACX_HIP(c, hipMemcpyAsync(c->d_pairs, pairs + 2 * k0, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
+        if ((rc = stage_idx(c, idx + k0, n)) != ACX_OK) return rc;
+        if ((rc = score(n)) != ACX_OK) return rc;
+        ACX_LAUNCHES_OK(c);
+        ACX_HIP(c, hipStreamSynchronize(c->stream));      // (the pinned staging of the destinations is reused by the next chunk)
+    }
+    return ACX_OK;
+}
+}  // extern "C++"
+
+// SiMPle: simple_kernel as acx_simple_pairs launches it, then the f64 -> f32 scatter of the grid path.
+static int run_simple_list(acx_ctx *c, const int32_t *pairs, const int64_t *idx, int64_t K, const acx_simple_params &sp, float *d_scores)
+{
+    size_t smem = 0;
+    const int rc = simple_front(c, sp.sslen, [&](auto visit) { for (int64_t k = 0; k < 2 * K; ++k) visit(pairs[k]); }, &smem);
+    if (rc != ACX_OK) return rc;
+    return run_list_chunks(c, pairs, idx, K, c->d_out64, [&](int n) -> int {
+        {
+            ProfScope ps(c, KS_SIMPLE, n);
+            const int rc2 = launch_simple_sslen(c, sp.sslen, n, smem, sp.oti);
+            if (rc2 != ACX_OK) return rc2;
+        }
+        hipLaunchKernelGGL(scatter_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_out64, c->d_idx, d_scores, n);
+        return ACX_OK;
+    });
+}
+
+// FTM2D: ftm2d_pairs_kernel as acx_ftm2d_pairs launches it (the same accumulation, the same bits), then the scatter
+// of the grid path.
+static int run_ftm2d_list(acx_ctx *c, const int32_t *pairs, const int64_t *idx, int64_t K, float *d_scores)
+{
+    return run_list_chunks(c, pairs, idx, K, c->d_out, [&](int n) -> int {
+        {
+            ProfScope ps(c, KS_FTMPAIRS, n);
+            hipLaunchKernelGGL(acx::ftm2d_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_ftm, c->ftm_dim,
+                               c->d_pairs, (int64_t)n, c->d_out);
+        }
+        hipLaunchKernelGGL(scatter_scores_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_out, c->d_idx, d_scores, n, 1);
+        return ACX_OK;
+    });
+}
+
+// Lowers the scratch limit a caller set by `bytes` (device memory the call holds beside the pair kernels' arenas) for
+// the length of a scope.
+struct ScratchReserve {
+    acx_ctx *c; int64_t saved;
+    ScratchReserve(acx_ctx *c_, int64_t bytes) : c(c_), saved(c_->scratch_limit) { if (saved > 0) c->scratch_limit = std::max<int64_t>(1, saved - bytes); }
+    ~ScratchReserve() { c->scratch_limit = saved; }
+};
+
+// The one place where an ACX_ALGO_* value and its params become a runner that leaves the scores of a pair list on the
+// device: pair k's planes at d_dst[idx[k] ...].  The Serra09 / ChenFusion / EarlyFusion kernels batch within the scratch
+// limit less reserve_bytes.  Nothing here waits for the stream beyond what the runners do themselves.
+static int run_pair_list(acx_ctx *c, int algo, const void *params, const int32_t *pairs, const int64_t *idx, int64_t K, float *d_dst,
+                         int64_t reserve_bytes)
+{
+    if (algo == ACX_ALGO_FTM2D) return run_ftm2d_list(c, pairs, idx, K, d_dst);
+    if (algo == ACX_ALGO_SIMPLE) return run_simple_list(c, pairs, idx, K, *static_cast<const acx_simple_params *>(params), d_dst);
+    ScratchReserve reserve(c, reserve_bytes);
+    DevDst dd{d_dst, idx};
+    if (algo == ACX_ALGO_EARLYFUSION)
+        return run_ef(c, pairs, K, *static_cast<const acx_ef_params *>(params), nullptr, nullptr, nullptr, 0, 0, &dd);
+    return run_serra09(c, pairs, K, *static_cast<const acx_serra09_params *>(params), nullptr, nullptr, algo == ACX_ALGO_CHENFUSION, &dd);
+}
+
 int acx_grid_run(acx_ctx *c, const acx_grid_spec *spec, const void *params, int32_t rank, int64_t first, int64_t count,
                  float *d_scores)
 {
@@ -5267,16 +5345,8 @@ int acx_grid_run(acx_ctx *c, const acx_grid_spec *spec, const void *params, int3
             acx::grid_tile_pairs(mine[t1], spec->symmetric, w, pairs, idx);
             ++t1;
         }
-        const int64_t K = (int64_t)idx.size();
-        if (K > 0) {
-            DevDst dd{d_scores, idx.data()};
-            if (spec->algo == ACX_ALGO_EARLYFUSION)
-                rc = run_ef(c, pairs.data(), K, *static_cast<const acx_ef_params *>(params), nullptr, nullptr, nullptr, 0, 0, &dd);
-            else
-                rc = run_serra09(c, pairs.data(), K, *static_cast<const acx_serra09_params *>(params), nullptr, nullptr,
-                                 spec->algo == ACX_ALGO_CHENFUSION, &dd);
-            if (rc != ACX_OK) return rc;
-        }
+        if (!idx.empty() && (rc = run_pair_list(c, spec->algo, params, pairs.data(), idx.data(), (int64_t)idx.size(), d_scores, 0)) != ACX_OK)
+            return rc;
         t0 = t1;
     }
     ACX_HIP(c, hipStreamSynchronize(c->stream));
@@ -5363,9 +5433,7 @@ int acx_pair_grid(acx_ctx *c, const acx_grid_spec *spec, const void *params, flo
 // A band is R query rows x N columns x planes floats on the device (the slab, plane fastest), filled by the pair
 // kernels through a DevDst and finished by query_kernels.hpp.  A band's device memory -- slab plus its results -- takes
 // at most HALF of the scratch limit; while the pair kernels of a band run under a limit the caller set, they see what
-// is left of it.  R <= QUERY_BAND_ROWS: with EarlyFusion a band x 128 collection tracks is then one dense rectangle.
-static const int QUERY_BAND_ROWS = 128;
-
+// is left of it.  Which pairs a band holds, its rows and the layout of a call's device block: query_plan.hpp.
 struct QueryCall {
     int algo = 0, w = 1, n = 0, symmetric = 0, mode = 0;
     const void *params = nullptr;
@@ -5410,146 +5478,88 @@ static int query_check(acx_ctx *c, const char *who, const acx_query_spec *spec, 
     return ACX_OK;
 }
 
-// Rows per band: `per_row` bytes of device memory per query row within half of the scratch limit.
-static int query_band_rows(acx_ctx *c, const char *who, int n_queries, int64_t per_row, int *rows)
+// Rows per band: `per_row` bytes of device memory per query row within half of the scratch limit, `cap` rows at most.
+static int query_band_rows(acx_ctx *c, const char *who, int n_queries, int64_t per_row, int64_t cap, int *rows)
 {
-    const int64_t half = scratch_limit_bytes(c) / 2;
-    if (half < per_row)
-        return fail(c, ACX_ERR_NOMEM, std::string(who) + ": one query row (" + std::to_string(per_row) + " bytes of scores and results) does not fit half of the scratch limit");
-    *rows = (int)std::min<int64_t>(std::min(n_queries, QUERY_BAND_ROWS), half / per_row);
+    *rows = acx::query_band_rows(n_queries, per_row, scratch_limit_bytes(c) / 2, cap);
+    if (*rows > 0) return ACX_OK;
+    return fail(c, ACX_ERR_NOMEM, std::string(who) + ": one query row (" + std::to_string(per_row) + " bytes of scores and results) does not fit half of the scratch limit");
+}
+
+extern "C++" {
+// Part `at` of a call's block as an array of T.  `src` is on its way there; NULL: the call has no such part, d is null.
+template <typename T>
+static int query_part(acx_ctx *c, char *d_mem, size_t at, const T *src, size_t count, const T *&d)
+{
+    d = src ? reinterpret_cast<const T *>(d_mem + at) : nullptr;
+    if (src && count > 0) ACX_HIP(c, hipMemcpyAsync(d_mem + at, src, sizeof(T) * count, hipMemcpyHostToDevice, c->stream));
     return ACX_OK;
 }
+template <typename T> static T *query_out(char *d_mem, size_t at) { return reinterpret_cast<T *>(d_mem + at); }
+}  // extern "C++"
 
-// The pairs of a band (queries q[0 .. nr) x the columns) and where their scores go in the slab.  Columns come in
-// blocks of 128, so that an EarlyFusion rectangle is one block x the band.  Pass 0: the cells computed as (query,
-// column) -- all of an ordered band, the columns above the query of a symmetric one --, column by column: neighbouring
-// pairs share their second track (what simple_kernel wants).  Pass 1 (symmetric): the cells computed as (column,
-// query), query by query.  A query's own column is left out.
-static void query_band_pairs(const int32_t *q, int nr, const int32_t *cols, int ncols, int n, int w, int symmetric,
-                             std::vector<int32_t> &pairs, std::vector<int64_t> &idx)
+// The head of every call's block: the slab, the column values (null without) and the queries, both on their way there.
+struct QueryHeadDev { float *slab; const double *col; const int32_t *q; };
+
+static int query_upload_head(acx_ctx *c, char *d_mem, const acx::QueryHead &h, const double *col, int n, const int32_t *queries, int n_queries,
+                             QueryHeadDev &d)
 {
-    pairs.clear(); idx.clear();
-    const int CB = 128;
-    for (int j0 = 0; j0 < ncols; j0 += CB) {
-        const int j1 = std::min(ncols, j0 + CB);
-        for (int j = j0; j < j1; ++j) {
-            const int col = cols ? cols[j] : j;
-            for (int r = 0; r < nr; ++r) {
-                if (col == q[r] || (symmetric && col < q[r])) continue;
-                pairs.push_back(q[r]); pairs.push_back(col);
-                idx.push_back(((int64_t)r * n + col) * w);
-            }
-        }
-        if (!symmetric) continue;
-        for (int r = 0; r < nr; ++r)
-            for (int j = j0; j < j1; ++j) {
-                const int col = cols ? cols[j] : j;
-                if (col >= q[r]) break;
-                pairs.push_back(col); pairs.push_back(q[r]);
-                idx.push_back(((int64_t)r * n + col) * w);
-            }
-    }
+    d.slab = query_out<float>(d_mem, h.slab);
+    const int rc = query_part(c, d_mem, h.col, col, (size_t)n, d.col);
+    return rc != ACX_OK ? rc : query_part(c, d_mem, h.queries, queries, (size_t)n_queries, d.q);
 }
 
-// SiMPle over a pair list whose scores stay on the device: simple_kernel as acx_simple_pairs launches it, then the
-// f64 -> f32 scatter of the grid path.
-static int run_simple_list(acx_ctx *c, const int32_t *pairs, const int64_t *idx, int64_t K, const acx_simple_params &sp, float *d_scores)
-{
-    size_t smem = 0;
-    int rc = simple_front(c, sp.sslen, [&](auto visit) { for (int64_t k = 0; k < 2 * K; ++k) visit(pairs[k]); }, &smem);
-    if (rc != ACX_OK) return rc;
-    const int64_t CHUNK = (int64_t)1 << 22;
-    if ((rc = ensure(c, c->d_pairs, (size_t)2 * std::min(K, CHUNK))) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_out64, (size_t)std::min(K, CHUNK))) != ACX_OK) return rc;
-    for (int64_t k0 = 0; k0 < K; k0 += CHUNK) {
-        const int n = (int)std::min(CHUNK, K - k0);
-        ACX_HIP(c, hipMemcpyAsync(c->d_pairs, pairs + 2 * k0, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
-        if ((rc = stage_idx(c, idx + k0, n)) != ACX_OK) return rc;
-        {
-            ProfScope ps(c, KS_SIMPLE, n);
-            if ((rc = launch_simple_sslen(c, sp.sslen, n, smem, sp.oti)) != ACX_OK) return rc;
-        }
-        hipLaunchKernelGGL(scatter_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_out64, c->d_idx, d_scores, n);
-        ACX_LAUNCHES_OK(c);
-        ACX_HIP(c, hipStreamSynchronize(c->stream));      // (the pinned staging of the destinations is reused by the next chunk)
-    }
-    return ACX_OK;
-}
-
-// FTM2D: the band as tiles of the tile kernel -- per query row and run of consecutive columns, the columns above the
-// query as a 1 x cols tile (query, column); those below it as a rows x 1 tile (column, query) when symmetric, as a
-// second 1 x cols tile otherwise.  A tile's scores are rows x cols floats at its offset: both shapes fill the slab row.
-static int run_ftm2d_band(acx_ctx *c, const int32_t *q, int nr, const int32_t *cols, int ncols, int n, int symmetric, float *d_slab)
-{
-    std::vector<acx_grid_tile> tiles;
-    auto add = [&](int r, int a, int b) {             // columns [a, b) of slab row r, none of them the query
-        if (a >= b) return;
-        acx_grid_tile t;
-        t.rank = 0; t.diagonal = 0; t.cost = 0.0;
-        t.offset = (int64_t)r * n + a;
-        if (symmetric && b <= q[r]) { t.row0 = a; t.rows = b - a; t.col0 = q[r]; t.cols = 1; }
-        else { t.row0 = q[r]; t.rows = 1; t.col0 = a; t.cols = b - a; }
-        tiles.push_back(t);
-    };
-    for (int j0 = 0; j0 < ncols;) {
-        int j1 = j0 + 1;
-        const int a = cols ? cols[j0] : 0;
-        if (cols) { while (j1 < ncols && cols[j1] == cols[j1 - 1] + 1) ++j1; } else j1 = ncols;
-        const int b = a + (j1 - j0);
-        for (int r = 0; r < nr; ++r) {
-            add(r, a, std::min(b, q[r]));
-            add(r, std::max(a, q[r] + 1), b);
-        }
-        j0 = j1;
-    }
-    ProfScope ps(c, KS_FTMTILE, (int64_t)nr * ncols);
-    return run_ftm2d_tiles(c, tiles, symmetric, d_slab);
-}
-
-// One band through the pair kernels: on return every score of the band lies in d_slab (the runners wait for their
-// last batch; the SiMPle and FTM2D paths are drained here).
-static int query_run_band(acx_ctx *c, const QueryCall &Q, const int32_t *q, int nr, const int32_t *cols, int ncols, float *d_slab,
+// One band through the pair kernels: rows queries[r0 .. r0 + nr) against the columns (`list`: ncols of them, NULL: all
+// of 0 .. ncols).  On return every score of the band lies in d_slab.  FTM2D takes the tile kernel (query_plan.hpp).
+static int query_run_band(acx_ctx *c, const QueryCall &Q, const int32_t *queries, int r0, int nr, const int32_t *cols, int ncols, float *d_slab,
                           int64_t band_bytes, std::vector<int32_t> &pairs, std::vector<int64_t> &idx)
 {
     ACX_HIP(c, hipMemsetAsync(d_slab, 0, sizeof(float) * (size_t)nr * Q.n * Q.w, c->stream));
+    int rc = ACX_OK;
     if (Q.algo == ACX_ALGO_FTM2D) {
-        const int rc = run_ftm2d_band(c, q, nr, cols, ncols, Q.n, Q.symmetric, d_slab);
-        if (rc != ACX_OK) return rc;
-        ACX_HIP(c, hipStreamSynchronize(c->stream));
-        return ACX_OK;
+        ProfScope ps(c, KS_FTMTILE, (int64_t)nr * ncols);
+        rc = run_ftm2d_tiles(c, acx::query_ftm2d_band_tiles(queries + r0, nr, cols, ncols, Q.n, Q.symmetric), Q.symmetric, d_slab);
+    } else {
+        acx::query_band_pairs(queries + r0, nr, cols, ncols, Q.n, Q.w, Q.symmetric, pairs, idx);
+        // a limit the caller set covers the band too: the pair kernels batch within what the band leaves of it
+        if (!idx.empty()) rc = run_pair_list(c, Q.algo, Q.params, pairs.data(), idx.data(), (int64_t)idx.size(), d_slab, band_bytes);
     }
-    query_band_pairs(q, nr, cols, ncols, Q.n, Q.w, Q.symmetric, pairs, idx);
-    const int64_t K = (int64_t)idx.size();
-    if (K == 0) { ACX_HIP(c, hipStreamSynchronize(c->stream)); return ACX_OK; }
-    if (Q.algo == ACX_ALGO_SIMPLE) return run_simple_list(c, pairs.data(), idx.data(), K, *static_cast<const acx_simple_params *>(Q.params), d_slab);
-    // a limit the caller set covers the band too: the pair kernels batch within what the band leaves of it
-    const int64_t saved = c->scratch_limit;
-    if (saved > 0) c->scratch_limit = std::max<int64_t>(1, saved - band_bytes);
-    DevDst dd{d_slab, idx.data()};
-    int rc;
-    if (Q.algo == ACX_ALGO_EARLYFUSION)
-        rc = run_ef(c, pairs.data(), K, *static_cast<const acx_ef_params *>(Q.params), nullptr, nullptr, nullptr, 0, 0, &dd);
-    else
-        rc = run_serra09(c, pairs.data(), K, *static_cast<const acx_serra09_params *>(Q.params), nullptr, nullptr,
-                         Q.algo == ACX_ALGO_CHENFUSION, &dd);
-    c->scratch_limit = saved;
     if (rc != ACX_OK) return rc;
     ACX_HIP(c, hipStreamSynchronize(c->stream));
     return ACX_OK;
 }
 
-// The bands of a call, R query rows each: every band through the pair kernels into d_slab, then launch(r0, nr) -- the
-// call's finishing kernel -- and, the launches checked, copies(r0, nr) -- its results on their way to the host.
+// One list band -- every query brings its own candidate list (acx_query_topk_lists): R query rows x L list positions x
+// planes floats (slab[(r L + j) W + e]), only the listed cells exist.  On return every listed cell's score lies in d_slab.
+static int query_run_list_band(acx_ctx *c, const QueryCall &Q, const int32_t *queries, int r0, int nr, const int32_t *lists, int L, float *d_slab,
+                               int64_t band_bytes, std::vector<int32_t> &pairs, std::vector<int64_t> &idx)
+{
+    if (L > 0) ACX_HIP(c, hipMemsetAsync(d_slab, 0, sizeof(float) * (size_t)nr * L * Q.w, c->stream));
+    acx::query_list_pairs(queries + r0, nr, lists + (size_t)r0 * L, L, Q.w, Q.symmetric, pairs, idx);
+    if (!idx.empty()) {
+        const int rc = run_pair_list(c, Q.algo, Q.params, pairs.data(), idx.data(), (int64_t)idx.size(), d_slab, band_bytes);
+        if (rc != ACX_OK) return rc;
+    }
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
+}
+
+typedef int (*QueryBandFill)(acx_ctx *, const QueryCall &, const int32_t *, int, int, const int32_t *, int, float *, int64_t, std::vector<int32_t> &,
+                             std::vector<int64_t> &);
+
+// The bands of a call, R query rows each: fill (query_run_band or query_run_list_band, with the call's `list` and `len`)
+// brings the band's scores into d_slab, then launch(r0, nr) -- the call's finishing kernel -- and, the launches checked,
+// copies(r0, nr) -- its results on their way to the host.
 extern "C++" {
 template <typename L, typename C>
-static int query_for_bands(acx_ctx *c, const QueryCall &Q, const int32_t *queries, int n_queries, int R, const int32_t *cols, int ncols,
-                           float *d_slab, int64_t per_row, L launch, C copies)
+static int query_for_bands(acx_ctx *c, const QueryCall &Q, const int32_t *queries, int n_queries, int R, QueryBandFill fill, const int32_t *list,
+                           int len, float *d_slab, int64_t per_row, L launch, C copies)
 {
     std::vector<int32_t> pairs;
     std::vector<int64_t> idx;
     for (int r0 = 0; r0 < n_queries; r0 += R) {
         const int nr = std::min(R, n_queries - r0);
-        int rc = query_run_band(c, Q, queries + r0, nr, cols, ncols, d_slab, (int64_t)R * per_row, pairs, idx);
+        int rc = fill(c, Q, queries, r0, nr, list, len, d_slab, (int64_t)R * per_row, pairs, idx);
         if (rc != ACX_OK) return rc;
         launch(r0, nr);
         ACX_LAUNCHES_OK(c);
@@ -5559,6 +5569,15 @@ static int query_for_bands(acx_ctx *c, const QueryCall &Q, const int32_t *querie
     return ACX_OK;
 }
 }  // extern "C++"
+
+// The results of a top-k band on their way to the host (acx_query_topk, acx_query_topk_lists)
+static int query_topk_copies(acx_ctx *c, int r0, int nr, int w, int k, const int32_t *d_idx, const float *d_sc, int32_t *out_idx, float *out_score)
+{
+    const size_t nres = (size_t)nr * w * k;
+    ACX_HIP(c, hipMemcpyAsync(out_idx + (size_t)r0 * w * k, d_idx, 4 * nres, hipMemcpyDeviceToHost, c->stream));
+    ACX_HIP(c, hipMemcpyAsync(out_score + (size_t)r0 * w * k, d_sc, 4 * nres, hipMemcpyDeviceToHost, c->stream));
+    return ACX_OK;
+}
 
 int acx_query_scores(acx_ctx *c, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
                      const double *col, float *const *rows, int64_t ld)
@@ -5574,21 +5593,19 @@ int acx_query_scores(acx_ctx *c, const acx_query_spec *spec, const void *params,
     if (n_queries == 0) return ACX_OK;
     const int64_t per_row = 2 * (int64_t)Q.n * Q.w * 4;           // the slab row and its finished copy
     int R = 0;
-    if ((rc = query_band_rows(c, "query_scores", n_queries, per_row, &R)) != ACX_OK) return rc;
+    if ((rc = query_band_rows(c, "query_scores", n_queries, per_row, acx::QUERY_BAND_ROWS, &R)) != ACX_OK) return rc;
     ACX_HIP(c, hipSetDevice(c->device));
-    const size_t slab_floats = (size_t)R * Q.n * Q.w;
-    const size_t o_col = 2 * slab_floats * 4, o_q = o_col + (col ? 8 * (size_t)Q.n : 0), total = o_q + 4 * (size_t)n_queries;
-    return with_device_block(c, "query_scores", total, [&](char *d_mem) -> int {
-        float *d_slab = reinterpret_cast<float *>(d_mem), *d_fin = d_slab + slab_floats;
-        const double *d_col = col ? reinterpret_cast<const double *>(d_mem + o_col) : nullptr;
-        int32_t *d_q = reinterpret_cast<int32_t *>(d_mem + o_q);
-        if (col) ACX_HIP(c, hipMemcpyAsync(d_mem + o_col, col, 8 * (size_t)Q.n, hipMemcpyHostToDevice, c->stream));
-        ACX_HIP(c, hipMemcpyAsync(d_q, queries, 4 * (size_t)n_queries, hipMemcpyHostToDevice, c->stream));
-        return query_for_bands(c, Q, queries, n_queries, R, nullptr, Q.n, d_slab, per_row,
+    const acx::QueryScoresLayout lay = acx::query_scores_layout((size_t)R * Q.n * Q.w, col ? Q.n : 0, n_queries);
+    return with_device_block(c, "query_scores", lay.total, [&](char *d_mem) -> int {
+        QueryHeadDev d;
+        const int rc2 = query_upload_head(c, d_mem, lay.head, col, Q.n, queries, n_queries, d);
+        if (rc2 != ACX_OK) return rc2;
+        float *d_fin = query_out<float>(d_mem, lay.fin);
+        return query_for_bands(c, Q, queries, n_queries, R, query_run_band, nullptr, Q.n, d.slab, per_row,
             [&](int r0, int nr) {
                 ProfScope ps(c, KS_QROWS, (int64_t)nr * Q.n * Q.w);
                 hipLaunchKernelGGL(acx::query_rows_kernel, dim3((unsigned)((Q.n + 255) / 256), (unsigned)nr, (unsigned)Q.w), dim3(256), 0, c->stream,
-                                   d_slab, Q.n, Q.w, nr, d_q + r0, d_col, Q.mode, d_fin);
+                                   d.slab, Q.n, Q.w, nr, d.q + r0, d.col, Q.mode, d_fin);
             },
             [&](int r0, int nr) -> int {
                 for (int e = 0; e < Q.w; ++e)
@@ -5611,7 +5628,7 @@ int acx_query_topk(acx_ctx *c, const acx_query_spec *spec, const void *params, c
     const int ncand = cands ? n_cands : Q.n;
     const int64_t per_row = (int64_t)Q.n * Q.w * 4 + 8 * (int64_t)Q.w * k;      // the slab row and its results
     int R = 0;
-    if ((rc = query_band_rows(c, "query_topk", n_queries, per_row, &R)) != ACX_OK) return rc;
+    if ((rc = query_band_rows(c, "query_topk", n_queries, per_row, acx::QUERY_BAND_ROWS, &R)) != ACX_OK) return rc;
     ACX_HIP(c, hipSetDevice(c->device));
     if (!c->query_attr) {
         ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::query_topk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -5620,34 +5637,23 @@ int acx_query_topk(acx_ctx *c, const acx_query_spec *spec, const void *params, c
     }
     int P = 4;
     while (P < std::min<int>(k, ncand)) P <<= 1;
-    // slab | col | queries | cands | the band's results (indices, scores)
-    const size_t slab_floats = (size_t)R * Q.n * Q.w, res = (size_t)R * Q.w * k;
-    const size_t o_col = slab_floats * 4, o_q = o_col + (col ? 8 * (size_t)Q.n : 0), o_c = o_q + 4 * (size_t)n_queries,
-                 o_res = o_c + (cands ? 4 * (size_t)n_cands : 0), total = o_res + 8 * res;
-    return with_device_block(c, "query_topk", total, [&](char *d_mem) -> int {
-        float *d_slab = reinterpret_cast<float *>(d_mem);
-        const double *d_col = col ? reinterpret_cast<const double *>(d_mem + o_col) : nullptr;
-        int32_t *d_q = reinterpret_cast<int32_t *>(d_mem + o_q);
-        const int32_t *d_c = cands ? reinterpret_cast<const int32_t *>(d_mem + o_c) : nullptr;
-        int32_t *d_idx = reinterpret_cast<int32_t *>(d_mem + o_res);
-        float *d_sc = reinterpret_cast<float *>(d_idx + res);
-        if (col) ACX_HIP(c, hipMemcpyAsync(d_mem + o_col, col, 8 * (size_t)Q.n, hipMemcpyHostToDevice, c->stream));
-        ACX_HIP(c, hipMemcpyAsync(d_q, queries, 4 * (size_t)n_queries, hipMemcpyHostToDevice, c->stream));
-        if (cands && n_cands > 0) ACX_HIP(c, hipMemcpyAsync(d_mem + o_c, cands, 4 * (size_t)n_cands, hipMemcpyHostToDevice, c->stream));
+    const acx::QueryTopkLayout lay = acx::query_topk_layout((size_t)R * Q.n * Q.w, col ? Q.n : 0, n_queries, cands ? n_cands : 0, (size_t)R * Q.w * k);
+    return with_device_block(c, "query_topk", lay.total, [&](char *d_mem) -> int {
+        QueryHeadDev d;
+        const int32_t *d_c;
+        int rc2 = query_upload_head(c, d_mem, lay.head, col, Q.n, queries, n_queries, d);
+        if (rc2 != ACX_OK || (rc2 = query_part(c, d_mem, lay.list, cands, (size_t)n_cands, d_c)) != ACX_OK) return rc2;
+        int32_t *d_idx = query_out<int32_t>(d_mem, lay.idx);
+        float *d_sc = query_out<float>(d_mem, lay.score);
         const bool in_lds = ncand <= acx::RANK_ROW_LDS;
         const size_t lds = 12 * (size_t)P + acx::RANK_SELECT_LDS_FIXED + (in_lds ? 4 * (size_t)ncand : 0);
-        return query_for_bands(c, Q, queries, n_queries, R, cands, ncand, d_slab, per_row,
+        return query_for_bands(c, Q, queries, n_queries, R, query_run_band, cands, ncand, d.slab, per_row,
             [&](int r0, int nr) {
                 ProfScope ps(c, KS_QTOPK, (int64_t)nr * ncand * Q.w);
-                ACX_LAUNCH_IN_LDS(query_topk_kernel, in_lds, dim3((unsigned)nr, (unsigned)Q.w), lds, d_slab, Q.n, Q.w, d_q + r0, d_c, ncand, d_col, Q.mode,
+                ACX_LAUNCH_IN_LDS(query_topk_kernel, in_lds, dim3((unsigned)nr, (unsigned)Q.w), lds, d.slab, Q.n, Q.w, d.q + r0, d_c, ncand, d.col, Q.mode,
                                   (int)k, P, d_idx, d_sc);
             },
-            [&](int r0, int nr) -> int {
-                const size_t nres = (size_t)nr * Q.w * k;
-                ACX_HIP(c, hipMemcpyAsync(out_idx + (size_t)r0 * Q.w * k, d_idx, 4 * nres, hipMemcpyDeviceToHost, c->stream));
-                ACX_HIP(c, hipMemcpyAsync(out_score + (size_t)r0 * Q.w * k, d_sc, 4 * nres, hipMemcpyDeviceToHost, c->stream));
-                return ACX_OK;
-            });
+            [&](int r0, int nr) { return query_topk_copies(c, r0, nr, Q.w, k, d_idx, d_sc, out_idx, out_score); });
     });
 }
 
@@ -5680,7 +5686,7 @@ int acx_query_ranks(acx_ctx *c, const acx_query_spec *spec, const void *params, 
     // the slab row and its results: every row is charged the longest mate list of the call (positions and flags per plane)
     const int64_t per_row = (int64_t)Q.n * Q.w * 4 + (int64_t)Q.w * (4 * maxm + 1);
     int R = 0;
-    if ((rc = query_band_rows(c, "query_ranks", n_queries, per_row, &R)) != ACX_OK) return rc;
+    if ((rc = query_band_rows(c, "query_ranks", n_queries, per_row, acx::QUERY_BAND_ROWS, &R)) != ACX_OK) return rc;
     ACX_HIP(c, hipSetDevice(c->device));
     if (!c->query_rank_attr) {
         ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::query_rank_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -5689,32 +5695,26 @@ int acx_query_ranks(acx_ctx *c, const acx_query_spec *spec, const void *params, 
     }
     int64_t band_m = 0;                                // the most positions one band returns per plane
     for (int r0 = 0; r0 < n_queries; r0 += R) band_m = std::max(band_m, moff[std::min(n_queries, r0 + R)] - moff[r0]);
-    // slab | moff | col | queries | mates | posn | the band's positions (plane by plane) | its flags
-    const size_t slab_floats = (size_t)R * Q.n * Q.w;
-    const size_t o_moff = (slab_floats * 4 + 7) & ~(size_t)7, o_col = o_moff + 8 * (size_t)(n_queries + 1), o_q = o_col + (col ? 8 * (size_t)Q.n : 0),
-                 o_m = o_q + 4 * (size_t)n_queries, o_posn = o_m + 4 * (size_t)M, o_pos = o_posn + (posn ? 4 * (size_t)Q.n : 0),
-                 o_flag = o_pos + 4 * (size_t)Q.w * (size_t)band_m, total = o_flag + (size_t)R * Q.w;
-    return with_device_block(c, "query_ranks", total, [&](char *d_mem) -> int {
-        float *d_slab = reinterpret_cast<float *>(d_mem);
-        const int64_t *d_moff = reinterpret_cast<const int64_t *>(d_mem + o_moff);
-        const double *d_col = col ? reinterpret_cast<const double *>(d_mem + o_col) : nullptr;
-        int32_t *d_q = reinterpret_cast<int32_t *>(d_mem + o_q);
-        const int32_t *d_mates = reinterpret_cast<const int32_t *>(d_mem + o_m);
-        const int32_t *d_posn = posn ? reinterpret_cast<const int32_t *>(d_mem + o_posn) : nullptr;
-        int32_t *d_pos = reinterpret_cast<int32_t *>(d_mem + o_pos);
-        uint8_t *d_flag = reinterpret_cast<uint8_t *>(d_mem + o_flag);
-        ACX_HIP(c, hipMemcpyAsync(d_mem + o_moff, moff, 8 * (size_t)(n_queries + 1), hipMemcpyHostToDevice, c->stream));
-        if (col) ACX_HIP(c, hipMemcpyAsync(d_mem + o_col, col, 8 * (size_t)Q.n, hipMemcpyHostToDevice, c->stream));
-        ACX_HIP(c, hipMemcpyAsync(d_q, queries, 4 * (size_t)n_queries, hipMemcpyHostToDevice, c->stream));
-        if (M > 0) ACX_HIP(c, hipMemcpyAsync(d_mem + o_m, mates, 4 * (size_t)M, hipMemcpyHostToDevice, c->stream));
-        if (posn) ACX_HIP(c, hipMemcpyAsync(d_mem + o_posn, posn, 4 * (size_t)Q.n, hipMemcpyHostToDevice, c->stream));
+    const acx::QueryRanksLayout lay = acx::query_ranks_layout((size_t)R * Q.n * Q.w, col ? Q.n : 0, n_queries, (size_t)M, posn ? Q.n : 0,
+                                                              (size_t)Q.w * (size_t)band_m, (size_t)R * Q.w);
+    return with_device_block(c, "query_ranks", lay.total, [&](char *d_mem) -> int {
+        QueryHeadDev d;
+        const int64_t *d_moff;
+        const int32_t *d_mates, *d_posn;
+        int rc2 = query_upload_head(c, d_mem, lay.head, col, Q.n, queries, n_queries, d);
+        if (rc2 != ACX_OK || (rc2 = query_part(c, d_mem, lay.moff, moff, (size_t)n_queries + 1, d_moff)) != ACX_OK ||
+            (rc2 = query_part(c, d_mem, lay.mates, mates, (size_t)M, d_mates)) != ACX_OK ||
+            (rc2 = query_part(c, d_mem, lay.posn, posn, (size_t)Q.n, d_posn)) != ACX_OK)
+            return rc2;
+        int32_t *d_pos = query_out<int32_t>(d_mem, lay.pos);
+        uint8_t *d_flag = query_out<uint8_t>(d_mem, lay.flag);
         const bool in_lds = Q.n <= acx::RANK_ROW_LDS;
         const size_t lds = acx::RANK_COUNT_LDS_FIXED + (in_lds ? 16 * (size_t)((Q.n + 3) / 4) : 0);
         // (a band's positions per plane: moff[r0 + nr] - moff[r0])
-        return query_for_bands(c, Q, queries, n_queries, R, nullptr, Q.n, d_slab, per_row,
+        return query_for_bands(c, Q, queries, n_queries, R, query_run_band, nullptr, Q.n, d.slab, per_row,
             [&](int r0, int nr) {
                 ProfScope ps(c, KS_QRANK, (int64_t)nr * Q.n * Q.w);
-                ACX_LAUNCH_IN_LDS(query_rank_kernel, in_lds, dim3((unsigned)nr, (unsigned)Q.w), lds, d_slab, Q.n, Q.w, d_q + r0, d_col, Q.mode, d_posn,
+                ACX_LAUNCH_IN_LDS(query_rank_kernel, in_lds, dim3((unsigned)nr, (unsigned)Q.w), lds, d.slab, Q.n, Q.w, d.q + r0, d.col, Q.mode, d_posn,
                                   d_moff + r0, d_mates + moff[r0], moff[r0], moff[r0 + nr] - moff[r0], d_pos, d_flag);
             },
             [&](int r0, int nr) -> int {
@@ -5726,15 +5726,6 @@ int acx_query_ranks(acx_ctx *c, const acx_query_spec *spec, const void *params, 
             });
     });
 }
-
-// ---- list bands: every query brings its own candidate list (acx_query_topk_lists) ------------------------------
-// A list band is R query rows x L list positions x planes floats (slab[(r L + j) W + e]): only the listed cells exist.
-// Its rows are not capped at QUERY_BAND_ROWS -- that cap makes a dense EarlyFusion rectangle of R x 128 tracks, and with
-// lists of a few hundred entries it would hand Serra09 a fraction of one 65535-pair batch per band.  A band is bounded by
-// memory (half of the scratch limit, as every band) and by QUERY_LIST_BAND_CELLS cells: four full Serra09 batches, so
-// that the two result slots of run_serra09 overlap within a band, while the host's pair list and destinations of a band
-// stay at 4 MB.  A design parameter: no measurement rests on it.
-static const int64_t QUERY_LIST_BAND_CELLS = (int64_t)1 << 18;
 
 // Everything acx_query_topk_lists checks of its lists, before anything is allocated or launched.
 static int query_check_lists(acx_ctx *c, const char *who, int n, int32_t n_queries, const int32_t *lists, int32_t list_len)
@@ -5761,84 +5752,6 @@ static int query_check_lists(acx_ctx *c, const char *who, int n, int32_t n_queri
     return ACX_OK;
 }
 
-// The cells of a list band -- rows q[0 .. nr) with their lists -- as pairs and slab destinations.  Cell (r, j) with
-// c = lists[r][j], c >= 0, c != q[r] is the pair (min, max) of a symmetric call, (q, c) of an ordered one; a pair two rows
-// want is computed twice.  The cells are enumerated grouped by the pair's second track (then by its first): neighbouring
-// pairs share a track (what simple_kernel wants), and the queries of one work share shortlist entries.  No pair kernel's
-// score depends on its place in the list.
-static void query_list_pairs(const int32_t *q, int nr, const int32_t *lists, int L, int w, int symmetric, std::vector<int32_t> &pairs,
-                             std::vector<int64_t> &idx)
-{
-    struct Cell { int32_t a, b; int64_t at; };
-    std::vector<Cell> cells;
-    for (int r = 0; r < nr; ++r)
-        for (int j = 0; j < L; ++j) {
-            const int32_t cnd = lists[(size_t)r * L + j];
-            if (cnd < 0 || cnd == q[r]) continue;
-            const bool swap = symmetric && cnd < q[r];
-            cells.push_back({swap ? cnd : q[r], swap ? q[r] : cnd, ((int64_t)r * L + j) * w});
-        }
-    std::sort(cells.begin(), cells.end(), [](const Cell &x, const Cell &y) {
-        return x.b != y.b ? x.b < y.b : x.a != y.a ? x.a < y.a : x.at < y.at;
-    });
-    pairs.resize(2 * cells.size()); idx.resize(cells.size());
-    for (size_t k = 0; k < cells.size(); ++k) { pairs[2 * k] = cells[k].a; pairs[2 * k + 1] = cells[k].b; idx[k] = cells[k].at; }
-}
-
-// FTM2D over a pair list whose scores stay on the device: ftm2d_pairs_kernel as acx_ftm2d_pairs launches it (the same
-// accumulation, the same bits), then the scatter of the grid path.
-static int run_ftm2d_list(acx_ctx *c, const int32_t *pairs, const int64_t *idx, int64_t K, float *d_scores)
-{
-    const int64_t CH = (int64_t)1 << 22;
-    int rc;
-    if ((rc = ensure(c, c->d_pairs, (size_t)2 * std::min(K, CH))) != ACX_OK) return rc;
-    if ((rc = ensure(c, c->d_out, (size_t)std::min(K, CH))) != ACX_OK) return rc;
-    for (int64_t k0 = 0; k0 < K; k0 += CH) {
-        const int64_t n = std::min(CH, K - k0);
-        ACX_HIP(c, hipMemcpyAsync(c->d_pairs, pairs + 2 * k0, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
-        if ((rc = stage_idx(c, idx + k0, n)) != ACX_OK) return rc;
-        {
-            ProfScope ps(c, KS_FTMPAIRS, n);
-            hipLaunchKernelGGL(acx::ftm2d_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_ftm, c->ftm_dim,
-                               c->d_pairs, n, c->d_out);
-        }
-        hipLaunchKernelGGL(scatter_scores_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_out, c->d_idx, d_scores, (int)n, 1);
-        ACX_LAUNCHES_OK(c);
-        ACX_HIP(c, hipStreamSynchronize(c->stream));      // (the pinned staging of the destinations is reused by the next chunk)
-    }
-    return ACX_OK;
-}
-
-// One list band through the pair kernels: on return every listed cell's score lies in d_slab.
-static int query_run_list_band(acx_ctx *c, const QueryCall &Q, const int32_t *q, int nr, const int32_t *lists, int L, float *d_slab,
-                               int64_t band_bytes, std::vector<int32_t> &pairs, std::vector<int64_t> &idx)
-{
-    if (L > 0) ACX_HIP(c, hipMemsetAsync(d_slab, 0, sizeof(float) * (size_t)nr * L * Q.w, c->stream));
-    query_list_pairs(q, nr, lists, L, Q.w, Q.symmetric, pairs, idx);
-    const int64_t K = (int64_t)idx.size();
-    int rc = ACX_OK;
-    if (K == 0) {
-    } else if (Q.algo == ACX_ALGO_FTM2D) {
-        rc = run_ftm2d_list(c, pairs.data(), idx.data(), K, d_slab);
-    } else if (Q.algo == ACX_ALGO_SIMPLE) {
-        rc = run_simple_list(c, pairs.data(), idx.data(), K, *static_cast<const acx_simple_params *>(Q.params), d_slab);
-    } else {
-        // a limit the caller set covers the band too: the pair kernels batch within what the band leaves of it
-        const int64_t saved = c->scratch_limit;
-        if (saved > 0) c->scratch_limit = std::max<int64_t>(1, saved - band_bytes);
-        DevDst dd{d_slab, idx.data()};
-        if (Q.algo == ACX_ALGO_EARLYFUSION)
-            rc = run_ef(c, pairs.data(), K, *static_cast<const acx_ef_params *>(Q.params), nullptr, nullptr, nullptr, 0, 0, &dd);
-        else
-            rc = run_serra09(c, pairs.data(), K, *static_cast<const acx_serra09_params *>(Q.params), nullptr, nullptr,
-                             Q.algo == ACX_ALGO_CHENFUSION, &dd);
-        c->scratch_limit = saved;
-    }
-    if (rc != ACX_OK) return rc;
-    ACX_HIP(c, hipStreamSynchronize(c->stream));
-    return ACX_OK;
-}
-
 int acx_query_topk_lists(acx_ctx *c, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
                          const int32_t *lists, int32_t list_len, const double *col, int32_t k, int32_t *out_idx, float *out_score)
 {
@@ -5851,10 +5764,8 @@ int acx_query_topk_lists(acx_ctx *c, const acx_query_spec *spec, const void *par
     if (n_queries == 0) return ACX_OK;
     const int L = list_len;
     const int64_t per_row = (int64_t)L * Q.w * 4 + 8 * (int64_t)Q.w * k;        // the slab row and its results
-    const int64_t half = scratch_limit_bytes(c) / 2;
-    if (half < per_row)
-        return fail(c, ACX_ERR_NOMEM, "query_topk_lists: one query row (" + std::to_string(per_row) + " bytes of scores and results) does not fit half of the scratch limit");
-    const int R = (int)std::min<int64_t>(std::min<int64_t>(n_queries, half / per_row), std::max<int64_t>(1, QUERY_LIST_BAND_CELLS / std::max(L, 1)));
+    int R = 0;                                                                  // (bounded by cells, not by rows: query_plan.hpp)
+    if ((rc = query_band_rows(c, "query_topk_lists", n_queries, per_row, acx::query_list_band_cap(L), &R)) != ACX_OK) return rc;
     ACX_HIP(c, hipSetDevice(c->device));
     if (!c->query_lists_attr) {
         ACX_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(acx::query_topk_lists_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -5863,40 +5774,23 @@ int acx_query_topk_lists(acx_ctx *c, const acx_query_spec *spec, const void *par
     }
     int P = 4;
     while (P < std::min<int>(k, L)) P <<= 1;
-    // slab | col | queries | lists | the band's results (indices, scores)
-    const size_t slab_floats = (size_t)R * L * Q.w, res = (size_t)R * Q.w * k, nl = (size_t)n_queries * L;
-    const size_t o_col = (slab_floats * 4 + 7) & ~(size_t)7, o_q = o_col + (col ? 8 * (size_t)Q.n : 0), o_l = o_q + 4 * (size_t)n_queries,
-                 o_res = o_l + 4 * nl, total = o_res + 8 * res;
-    return with_device_block(c, "query_topk_lists", total, [&](char *d_mem) -> int {
-        float *d_slab = reinterpret_cast<float *>(d_mem);
-        const double *d_col = col ? reinterpret_cast<const double *>(d_mem + o_col) : nullptr;
-        int32_t *d_q = reinterpret_cast<int32_t *>(d_mem + o_q);
-        const int32_t *d_l = reinterpret_cast<const int32_t *>(d_mem + o_l);
-        int32_t *d_idx = reinterpret_cast<int32_t *>(d_mem + o_res);
-        float *d_sc = reinterpret_cast<float *>(d_idx + res);
-        if (col) ACX_HIP(c, hipMemcpyAsync(d_mem + o_col, col, 8 * (size_t)Q.n, hipMemcpyHostToDevice, c->stream));
-        ACX_HIP(c, hipMemcpyAsync(d_q, queries, 4 * (size_t)n_queries, hipMemcpyHostToDevice, c->stream));
-        if (nl > 0) ACX_HIP(c, hipMemcpyAsync(d_mem + o_l, lists, 4 * nl, hipMemcpyHostToDevice, c->stream));
+    const acx::QueryTopkLayout lay = acx::query_topk_layout((size_t)R * L * Q.w, col ? Q.n : 0, n_queries, (size_t)n_queries * L, (size_t)R * Q.w * k);
+    return with_device_block(c, "query_topk_lists", lay.total, [&](char *d_mem) -> int {
+        QueryHeadDev d;
+        const int32_t *d_l;
+        int rc2 = query_upload_head(c, d_mem, lay.head, col, Q.n, queries, n_queries, d);
+        if (rc2 != ACX_OK || (rc2 = query_part(c, d_mem, lay.list, lists, (size_t)n_queries * L, d_l)) != ACX_OK) return rc2;
+        int32_t *d_idx = query_out<int32_t>(d_mem, lay.idx);
+        float *d_sc = query_out<float>(d_mem, lay.score);
         const bool in_lds = L <= acx::RANK_ROW_LDS;
         const size_t lds = 12 * (size_t)P + acx::RANK_SELECT_LDS_FIXED + 16 + (in_lds ? 4 * (size_t)L : 0);
-        std::vector<int32_t> pairs;
-        std::vector<int64_t> idx;
-        for (int r0 = 0; r0 < n_queries; r0 += R) {
-            const int nr = std::min(R, n_queries - r0);
-            int rc2 = query_run_list_band(c, Q, queries + r0, nr, lists + (size_t)r0 * L, L, d_slab, (int64_t)R * per_row, pairs, idx);
-            if (rc2 != ACX_OK) return rc2;
-            {
+        return query_for_bands(c, Q, queries, n_queries, R, query_run_list_band, lists, L, d.slab, per_row,
+            [&](int r0, int nr) {
                 ProfScope ps(c, KS_QTOPKL, (int64_t)nr * L * Q.w);
-                ACX_LAUNCH_IN_LDS(query_topk_lists_kernel, in_lds, dim3((unsigned)nr, (unsigned)Q.w), lds, d_slab, L, Q.w, d_q + r0, d_l + (size_t)r0 * L,
-                                  d_col, Q.mode, (int)k, P, d_idx, d_sc);
-            }
-            ACX_LAUNCHES_OK(c);
-            const size_t nres = (size_t)nr * Q.w * k;
-            ACX_HIP(c, hipMemcpyAsync(out_idx + (size_t)r0 * Q.w * k, d_idx, 4 * nres, hipMemcpyDeviceToHost, c->stream));
-            ACX_HIP(c, hipMemcpyAsync(out_score + (size_t)r0 * Q.w * k, d_sc, 4 * nres, hipMemcpyDeviceToHost, c->stream));
-            ACX_HIP(c, hipStreamSynchronize(c->stream));
-        }
-        return ACX_OK;
+                ACX_LAUNCH_IN_LDS(query_topk_lists_kernel, in_lds, dim3((unsigned)nr, (unsigned)Q.w), lds, d.slab, L, Q.w, d.q + r0, d_l + (size_t)r0 * L,
+                                  d.col, Q.mode, (int)k, P, d_idx, d_sc);
+            },
+            [&](int r0, int nr) { return query_topk_copies(c, r0, nr, Q.w, k, d_idx, d_sc, out_idx, out_score); });
     });
 }
 

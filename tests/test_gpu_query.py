@@ -333,6 +333,45 @@ def test_band_splitting(ctx):
     ctx.set_scratch_limit(0)
 
 
+def test_column_values_behind_an_odd_slab(ctx):
+    """One and three queries of 23 (SiMPle) and 37 (FTM2D) tracks, one plane: R * n and R * L are odd, the slab ends
+    4 bytes past a multiple of 8 and the f64 column values behind it have to move up to their alignment.  Every query
+    export with col given, against _query_ref on the rows of the pair-list entry points: a list row is query_topk of
+    its sorted valid entries, a position is the place in the full ranking (no tie, NaN or -inf in these rows)."""
+    for name in ("simple", "ftm2d"):
+        algo, sym, params, pair_fn, n, w, col, _ = _setup(ctx, name)
+        assert w == 1 and n % 2 == 1
+        cand = np.array([1, 8, n - 1], np.int32)
+        for queries in ([7], [7, 2, 9]):
+            raw = _raw_rows(pair_fn, n, queries, sym, w)[0]
+            rng = np.random.default_rng(n + len(queries))
+            lists = np.stack([rng.permutation(np.delete(np.arange(n), q))[:5] for q in queries]).astype(np.int32)
+            lists[0, 2] = -1
+            lists[-1, 0] = queries[-1]                        # the own track
+            moff = 2 * np.arange(len(queries) + 1)
+            mates = np.array([[(q + 1) % n, (q + 5) % n] for q in queries], np.int32).reshape(-1)
+            for mode in (1, 2):
+                what = (name, len(queries), mode)
+                fin = qref.scores(raw, queries, col, mode)
+                off_own = np.ones(fin.shape, bool)
+                off_own[np.arange(len(queries)), queries] = False
+                assert np.all(np.isfinite(fin[off_own])), what
+                assert _same(ctx.query_scores(algo, sym, params, queries, col=col, col_mode=mode)[0], fin), what
+                for cands in (None, cand):
+                    gi, gs = ctx.query_topk(algo, sym, params, queries, 4, candidates=cands, col=col, col_mode=mode)
+                    wi, ws = qref.topk(raw, queries, 4, candidates=cands, col=col, col_mode=mode)
+                    assert np.array_equal(gi[:, 0], wi) and _same(gs[:, 0], ws), what + (cands is not None,)
+                gi, gs = ctx.query_topk_lists(algo, sym, params, queries, lists, 4, col=col, col_mode=mode)
+                for i, q in enumerate(queries):
+                    wi, ws = qref.topk(raw[i:i + 1], [q], 4, candidates=np.sort(lists[i][lists[i] >= 0]), col=col, col_mode=mode)
+                    assert np.array_equal(gi[i, 0], wi[0]) and _same(gs[i, 0], ws[0]), what + (i,)
+                full, fs = qref.topk(raw, queries, n - 1, col=col, col_mode=mode)
+                assert np.all(fs[:, 1:] != fs[:, :-1]), "the rows hold no tie"
+                pos, flag = ctx.query_ranks(algo, sym, params, queries, moff, mates, col=col, col_mode=mode)
+                want = [1 + list(full[i]).index(m) for i in range(len(queries)) for m in mates[moff[i]:moff[i + 1]]]
+                assert pos.shape == (1, len(mates)) and np.array_equal(pos[0], want) and not flag.any(), what
+
+
 def test_rows_beyond_the_lds_budget(ctx):
     """20 000 tracks: a row no longer fits the LDS and is re-read per pass.  The rows are checked against the pair-list
     entry point; the lists against _query_ref on those rows (the one place where the new query_scores feeds the
