@@ -36,7 +36,7 @@ EXPORTS = [
     "acx_ftm2d_default_params", "acx_ftm2d_pool_begin", "acx_ftm2d_pool_tracks", "acx_ftm2d_pool_end",
     "acx_ftm2d_upload_shingles", "acx_ftm2d_download_shingles", "acx_ftm2d_debug_track", "acx_ftm2d_pairs",
     "acx_rank_columns", "acx_topk_rows",
-    "acx_query_scores", "acx_query_topk", "acx_query_ranks", "acx_query_topk_lists",
+    "acx_query_scores", "acx_query_topk", "acx_query_ranks", "acx_query_topk_lists", "acx_query_fused_lists",
     "acx_serra09_debug_bits", "acx_serra09_plan", "acx_serra09_family_name", "acx_serra09_fast_tail", "acx_serra09_fast_tail_launches",
     "acx_serra09_plane_launches",
     "acx_pool_append", "acx_pool_append_raw", "acx_pool_append_f64", "acx_ef_pool_append", "acx_ftm2d_append_shingles",
@@ -96,6 +96,33 @@ class QuerySpec(ctypes.Structure):
     """acx_query_spec (include/acx.h)."""
     _fields_ = [("algo", ctypes.c_int32), ("symmetric", ctypes.c_int32), ("col_mode", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
+
+
+FUSED_SQRTLEN, FUSED_INV1P = 1, 2
+
+
+class FusedSpec(ctypes.Structure):
+    """acx_fused_spec (include/acx.h)."""
+    _fields_ = [("n_types", ctypes.c_int32), ("count", ctypes.c_int32 * 2), ("planes", (ctypes.c_int32 * 4) * 2),
+                ("transform", ctypes.c_int32), ("K", ctypes.c_int32), ("niters", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("reg_diag", ctypes.c_double), ("mu", ctypes.c_double)]
+
+
+def fused_spec(planes, transform, K=20, niters=20, reg_diag=1.0, mu=0.5):
+    """acx_fused_spec: planes = one sequence of pair-kernel plane indices per fused type (at most 2 types of 2..4 planes),
+    in fusion order.  Sizes are checked here because the struct cannot hold more; the values are the library's to check."""
+    planes = [[int(p) for p in t] for t in planes]
+    if not 1 <= len(planes) <= 2 or any(not 2 <= len(t) <= 4 for t in planes):
+        raise ValueError("fused_spec: 1 or 2 fused types of 2..4 planes each, got %s" % (planes,))
+    f = FusedSpec()
+    f.n_types = len(planes)
+    for t, pl in enumerate(planes):
+        f.count[t] = len(pl)
+        for i, v in enumerate(pl):
+            f.planes[t][i] = v
+    f.transform, f.K, f.niters, f.reserved = int(transform), int(K), int(niters), 0
+    f.reg_diag, f.mu = float(reg_diag), float(mu)
+    return f
 
 
 class SimpleParams(ctypes.Structure):
@@ -333,6 +360,8 @@ def load():
     L.acx_query_topk.argtypes = [vp, qp, vp, ip, ctypes.c_int32, ip, ctypes.c_int32, dp, ctypes.c_int32, ip, fp]
     L.acx_query_topk_lists.argtypes = [vp, qp, vp, ip, ctypes.c_int32, ip, ctypes.c_int32, dp, ctypes.c_int32, ip, fp]
     L.acx_query_ranks.argtypes = [vp, qp, vp, ip, ctypes.c_int32, dp, ip, lp, ip, ip, ctypes.POINTER(ctypes.c_uint8)]
+    L.acx_query_fused_lists.argtypes = [vp, qp, vp, ip, ctypes.c_int32, ip, ctypes.c_int32, dp, ctypes.POINTER(FusedSpec), ctypes.c_int32, ip, fp,
+                                        ctypes.POINTER(ctypes.c_uint8)]
     L.acx_pool_append.argtypes = [vp, fp, lp, ctypes.c_int32, ctypes.c_int32]
     L.acx_pool_append_raw.argtypes = [vp, fp, lp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, lp]
     L.acx_pool_append_f64.argtypes = [vp, dp, lp, ctypes.c_int32, ctypes.c_int32]
@@ -1579,6 +1608,28 @@ class Context(object):
                                                  _iptr(lists), lists.shape[1], None if col is None else _dptr(col), k,
                                                  _iptr(idx), _fptr(score)))
         return idx, score
+
+    def query_fused_lists(self, algo, symmetric, params, queries, lists, k, fused, col=None, col_mode=0):
+        """acx_query_fused_lists: the fused (late-fusion) scores of every query within its own neighbourhood -- the query and
+        the valid entries of its row of `lists` (as query_topk_lists takes them) -- ranked: (idx (Q, types, k) int32, score
+        (Q, types, k) float32, flag (Q, types) uint8).  fused: a FusedSpec (fused_spec()).  Per query the result is what
+        snf_fuse_dists returns on the distance matrices of the sub-collection T = sorted({q} U list), row q without its own
+        column, rounded once to float32 and ranked as topk_rows ranks; indices are collection indices.  flag 1: an
+        off-diagonal distance of that query's neighbourhood is not finite (its row is NaN).  Costs n (n - 1) / 2 pair scores
+        per query; a neighbourhood needs at least K + 2 tracks."""
+        spec, queries, col = self._query_args(algo, symmetric, queries, col, col_mode)
+        k = int(k)
+        lists = np.ascontiguousarray(lists, dtype=np.int32)
+        if lists.ndim != 2 or lists.shape[0] != len(queries):
+            raise ValueError("query_fused_lists: lists must be (len(queries), L) = (%d, L), got shape %s" % (len(queries), lists.shape))
+        nt = int(fused.n_types)
+        idx = np.full((len(queries), nt, max(k, 0)), -1, np.int32)
+        score = np.full((len(queries), nt, max(k, 0)), np.nan, np.float32)
+        flag = np.zeros((len(queries), nt), np.uint8)
+        self._check(self._L.acx_query_fused_lists(self._h, ctypes.byref(spec), _params_ptr(params), _iptr(queries), len(queries),
+                                                  _iptr(lists), lists.shape[1], None if col is None else _dptr(col), ctypes.byref(fused), k,
+                                                  _iptr(idx), _fptr(score), flag.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        return idx, score, flag
 
     def query_ranks(self, algo, symmetric, params, queries, moff, mates, posn=None, col=None, col_mode=0):
         """acx_query_ranks: (pos (planes, M) int32, flag (Q, planes) uint8), M = moff[-1] -- for every plane, the 1-based

@@ -306,6 +306,11 @@ class CoverAlgorithm(object):
     _identify_planes = ("main",)
     _identify_fused = ()
     _identify_symmetric = True
+    # what rerank_fused() needs of a class with fused types: per fused type the device planes do_late_fusion hands to the
+    # fusion, in ITS order (the sweep's in-place aliasing makes the order matter), and the transform from score to distance
+    # (_lib.FUSED_*)
+    _fused_planes = {}
+    _fused_transform = None
 
     # the open appended() session (an AppendedSession), None outside one
     _session = None
@@ -330,7 +335,7 @@ class CoverAlgorithm(object):
         for t in types:
             if t in self._identify_fused:
                 raise NotImplementedError("%s: '%s' is a fusion of whole N x N matrices (do_late_fusion) and cannot be "
-                                          "computed for a band of query rows" % (who, t))
+                                          "computed for a band of query rows; rerank_fused() fuses it within a query's shortlist" % (who, t))
             if t not in self._identify_planes:
                 raise ValueError("%s: unknown similarity type '%s' (available: %s)" % (who, t, list(self._identify_planes)))
         q = np.asarray(queries)
@@ -649,10 +654,90 @@ class CoverAlgorithm(object):
         idx, score = ctx.query_topk_lists(algo, self._identify_symmetric, params, q, lists, k, col=col, col_mode=mode)
         return self._by_type(idx, score, types)
 
+    # ------------------------------------------------------------------ fused scores within a query's shortlist
+    def _fused_setup(self, who, similarity_types, K, niters):
+        """The fused types, K and niters of rerank_fused() and its relatives, checked without touching the library."""
+        if not self._identify_fused:
+            raise NotImplementedError("%s: %s has no fused similarity type (no do_late_fusion)" % (who, type(self).__name__))
+        types = list(self._identify_fused) if similarity_types is None else list(similarity_types)
+        if not types:
+            raise ValueError("%s: similarity_types must name at least one fused type of %s" % (who, list(self._identify_fused)))
+        for t in types:
+            if t in self._identify_planes:
+                raise ValueError("%s: '%s' is not a fused type (rerank() lists it); fused types: %s" % (who, t, list(self._identify_fused)))
+            if t not in self._identify_fused:
+                raise ValueError("%s: unknown similarity type '%s' (fused types: %s)" % (who, t, list(self._identify_fused)))
+        if len(set(types)) != len(types):
+            raise ValueError("%s: similarity_types names a fused type twice" % who)
+        K, niters = int(K), int(niters)
+        if K < 1:
+            raise ValueError("%s: K must be >= 1 (got %d)" % (who, K))
+        if K > 64:
+            raise NotImplementedError("%s: more than 64 neighbours are not supported on the device (K = %d)" % (who, K))
+        if niters < 1:
+            raise ValueError("%s: niters must be >= 1 (got %d)" % (who, niters))
+        return types, K, niters
+
+    @staticmethod
+    def _check_fused_lists(who, q, lists, K):
+        """Every neighbourhood -- the query and the valid entries of its row -- holds at least K + 2 tracks (below that the
+        K-neighbour cut of the fusion is not defined), and a row at most 1024 entries."""
+        if lists.shape[1] > 1024:
+            raise NotImplementedError("%s: shortlists of more than 1024 entries are not supported (got %d)" % (who, lists.shape[1]))
+        n = 1 + ((lists >= 0) & (lists != np.asarray(q).reshape(-1, 1))).sum(axis=1)
+        bad = np.nonzero(n < K + 2)[0]
+        if len(bad):
+            raise ValueError("%s: shortlists row %d gives a neighbourhood of %d tracks (the query included); the fusion needs at "
+                             "least K + 2 = %d" % (who, bad[0], n[bad[0]], K + 2))
+
+    def _fused_call(self, ctx, algo, params, mode, col, q, lists, k, types, K, niters):
+        planes = list(self._identify_planes)
+        spec = _lib.fused_spec([[planes.index(p) for p in self._fused_planes[t]] for t in types], self._fused_transform, K=K, niters=niters)
+        idx, score, _ = ctx.query_fused_lists(algo, self._identify_symmetric, params, q, lists, k, spec, col=col, col_mode=mode)
+        return {t: (np.ascontiguousarray(idx[:, i]), np.ascontiguousarray(score[:, i])) for i, t in enumerate(types)}
+
+    def rerank_fused(self, queries, shortlists, k=10, similarity_types=None, K=20, niters=20):
+        """rerank() for the class's FUSED similarity types (ChenFusion 'Late', EarlyFusion 'late' / 'early+late'; None: all
+        of them): {type: (idx (Q, k) int32, score (Q, k) float32)}.  Similarity network fusion is a function of a set of
+        tracks, so the fused score of a query is defined on its neighbourhood T = sorted({query} U valid shortlist entries):
+        row i holds exactly what the class computes on a collection of only those tracks -- all_pairwise(symmetric=True),
+        normalize_by_length() where the class has one, do_late_fusion() (K, niters: its constants by default),
+        top_matches(type, k, rows=[position of the query]) -- with the indices mapped back through T (acx_query_fused_lists:
+        the same bits).  shortlists as rerank() takes them.  A neighbourhood needs at least K + 2 tracks (ValueError naming
+        the row).  A query costs n (n - 1) / 2 alignments, n = len(T) -- 5 050 for a shortlist of 100, 1 275 for 50 -- where
+        rerank() costs len(shortlist); a pair two neighbourhoods share is computed twice.  A ChenFusion pair with raw score 0
+        (an empty plot) makes the rows of the neighbourhoods that hold it NaN, as it does in the whole-collection fusion.
+        `Ds` is not written.  Not a collective."""
+        who = "rerank_fused"
+        types, K, niters = self._fused_setup(who, similarity_types, K, niters)
+        q, _ = self._query_setup(who, queries, [])
+        k = self._check_k(who, k)
+        lists = self._check_shortlists(who, shortlists, len(q))
+        self._check_fused_lists(who, q, lists, K)
+        ctx, algo, params, mode, col = self._query_call()
+        return self._fused_call(ctx, algo, params, mode, col, q, lists, k, types, K, niters)
+
+    @refused_in_session
+    def rerank_tracks_fused(self, tracks, shortlists, k=10, similarity_types=None, K=20, niters=20):
+        """rerank_fused() for tracks the collection does NOT hold (tracks as identify_tracks() takes them, shortlist entries
+        in [0, N) or -1): exactly rerank_fused(s.indices, shortlists, ...) inside `with self.appended(tracks) as s`."""
+        return self._rerank_tracks_fused(tracks, shortlists, k, similarity_types, K, niters)
+
+    def _rerank_tracks_fused(self, tracks, shortlists, k, similarity_types, K, niters, **how):
+        who = "rerank_tracks_fused"
+        types, K, niters = self._fused_setup(who, similarity_types, K, niters)
+        k = self._check_k(who, k)
+        checked, Q, _, _ = self._tracks_setup(who, tracks, [], None, how)
+        lists = self._check_shortlists(who, shortlists, Q)
+        self._check_fused_lists(who, np.arange(self.N, self.N + Q), lists, K)
+        return self._with_appended(checked, Q, lambda ctx, algo, params, mode, col, q: self._fused_call(
+            ctx, algo, params, mode, col, q, lists, k, types, K, niters))
+
     def identify_cascade(self, first, queries, k=10, shortlist=200, first_type=None, similarity_types=None):
         """Two stages: `first` -- another device-backed algorithm object over the SAME collection, the cheap one (FTM2D) --
         shortlists `shortlist` (1 .. 1024) tracks per query by its similarity type `first_type` (None: its first plane),
-        and this object reranks them: self.rerank(queries, first.identify(queries, k=shortlist)[first_type][0], k)."""
+        and this object reranks them: self.rerank(queries, first.identify(queries, k=shortlist)[first_type][0], k).
+        identify_cascade_fused() is the same cascade with rerank_fused() as its second stage."""
         if getattr(first, "N", None) != self.N:
             raise ValueError("identify_cascade: first holds %s tracks, this collection %d" % (getattr(first, "N", None), self.N))
         shortlist = int(shortlist)
@@ -664,6 +749,27 @@ class CoverAlgorithm(object):
         first._query_setup("identify_cascade", q, [first_type])
         lists = first.identify(q, k=shortlist, similarity_types=[first_type])[first_type][0]
         return self.rerank(q, lists, k=k, similarity_types=similarity_types)
+
+    def identify_cascade_fused(self, first, queries, k=10, shortlist=200, first_type=None, similarity_types=None, K=20, niters=20):
+        """identify_cascade() with the class's FUSED types as the second stage: `first` shortlists `shortlist` (K + 1 .. 1024)
+        tracks per query and this object fuses within every query's shortlist:
+        self.rerank_fused(queries, first.identify(queries, k=shortlist)[first_type][0], k, similarity_types, K, niters)."""
+        who = "identify_cascade_fused"
+        if getattr(first, "N", None) != self.N:
+            raise ValueError("%s: first holds %s tracks, this collection %d" % (who, getattr(first, "N", None), self.N))
+        shortlist = int(shortlist)
+        if shortlist < 1 or shortlist > 1024:
+            raise ValueError("%s: shortlist must be in 1..1024 (got %d)" % (who, shortlist))
+        k = self._check_k(who, k)
+        types, K, niters = self._fused_setup(who, similarity_types, K, niters)
+        if min(shortlist, self._n_tracks() - 1) < K + 1:
+            raise ValueError("%s: a shortlist of %d of %d tracks gives neighbourhoods below K + 2 = %d tracks"
+                             % (who, shortlist, self._n_tracks(), K + 2))
+        q, _ = self._query_setup(who, queries, [])
+        first_type = first._identify_planes[0] if first_type is None else first_type
+        first._query_setup(who, q, [first_type])
+        lists = first.identify(q, k=shortlist, similarity_types=[first_type])[first_type][0]
+        return self.rerank_fused(q, lists, k=k, similarity_types=types, K=K, niters=niters)
 
     @refused_in_session
     def rerank_tracks(self, tracks, shortlists, k=10, similarity_types=None):

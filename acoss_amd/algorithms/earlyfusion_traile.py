@@ -141,6 +141,9 @@ class EarlyFusion(CoverAlgorithm):
 
     _identify_planes = ("mfccs", "ssms", "chromas", "early")
     _identify_fused = ("late", "early+late")
+    # do_late_fusion's two lists, as distances 1 / (1 + s)
+    _fused_planes = {"late": ("chromas", "ssms", "mfccs"), "early+late": ("chromas", "ssms", "mfccs", "early")}
+    _fused_transform = _lib.FUSED_INV1P
 
     def _grid(self):
         return (self._context(), _lib.ALGO_EARLYFUSION, _lib.EfParams(float(self.kappa), int(self.K)),

@@ -39,6 +39,9 @@ class ChenFusion(Serra09):
 
     _identify_planes = ("qmax", "dmax")
     _identify_fused = ("Late",)
+    # do_late_fusion fuses self.Ds in insertion order -- qmax, dmax -- as distances sqrt(T_c) / s (normalize_by_length)
+    _fused_planes = {"Late": ("qmax", "dmax")}
+    _fused_transform = _lib.FUSED_SQRTLEN
 
     def _identify_norm(self):
         """identify() / query_rows(): -(sqrt(T_c) / s), normalize_by_length with the sign flip of do_late_fusion."""
@@ -120,6 +123,11 @@ class ChenFusion(Serra09):
         got = []
         out[rows, slots] = self._align_pairs(pairs, got, plane)
         return out, _align.scatter_paths(idx, rows, slots, got)
+
+    @refused_in_session
+    def rerank_tracks_fused(self, tracks, shortlists, k=10, similarity_types=None, K=20, niters=20, raw=False):
+        """CoverAlgorithm.rerank_tracks_fused; tracks and raw as in identify_tracks."""
+        return self._rerank_tracks_fused(tracks, shortlists, k, similarity_types, K, niters, raw=raw)
 
     @refused_in_session
     def normalize_by_length(self):

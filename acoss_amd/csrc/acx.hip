@@ -38,6 +38,8 @@
 #include "query_kernels.hpp"
 #include "grid.hpp"
 #include "query_plan.hpp"
+#include "fused_plan.hpp"
+#include "snf_batch_kernels.hpp"
 #include "serra09_plan.hpp"
 #include "device_buffer.hpp"
 
@@ -55,7 +57,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_DLOCATE, KS_DPATH, KS_SIMPLEPROF, KS_XFMEANS, KS_XFAFFINITY, KS_XFSNF, KS_XFX, KS_XFSELECT, KS_EFALIGNLONG, KS_EFALIGN, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_DLOCATE, KS_DPATH, KS_SIMPLEPROF, KS_XFMEANS, KS_XFAFFINITY, KS_XFSNF, KS_XFX, KS_XFSELECT, KS_FUSEDSTAGE, KS_SNFBATCHPREP, KS_SNFBATCHUPDATE, KS_FUSEDROW, KS_EFALIGNLONG, KS_EFALIGN, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -222,6 +224,8 @@ struct acx_ctx {
                              {"dmax_locate_kernel", 0, 0, 0}, {"dmax_path_kernel", 0, 0, 0},
                              {"simple_profile_kernel", 0, 0, 0}, {"xf_means_kernel", 0, 0, 0}, {"xf_affinity_kernels", 0, 0, 0},
                              {"xf_snf_kernels", 0, 0, 0}, {"xf_x_kernel", 0, 0, 0}, {"xf_select_kernel", 0, 0, 0},
+                             {"fused_stage_kernel", 0, 0, 0}, {"snf_batch_prepare_kernels", 0, 0, 0}, {"snf_batch_update_kernels", 0, 0, 0},
+                             {"fused_row_kernel", 0, 0, 0},
                              {"ef_align_long_kernel", 0, 0, 0},
                              {"ef_align_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
@@ -5791,6 +5795,180 @@ int acx_query_topk_lists(acx_ctx *c, const acx_query_spec *spec, const void *par
                                   d.col, Q.mode, (int)k, P, d_idx, d_sc);
             },
             [&](int r0, int nr) { return query_topk_copies(c, r0, nr, Q.w, k, d_idx, d_sc, out_idx, out_score); });
+    });
+}
+
+// ---- fused scores for query shortlists: Q small similarity network fusions side by side (snf_batch_kernels.hpp) ------
+// What acx_query_fused_lists checks of its struct, before anything is allocated or launched.
+static int fused_check_spec(acx_ctx *c, const char *who, const acx_fused_spec *f, int W, int col_mode)
+{
+    const std::string w(who);
+    if (!f) return fail(c, ACX_ERR_INVALID, w + ": fused must not be NULL");
+    if (f->reserved != 0) return fail(c, ACX_ERR_INVALID, w + ": fused.reserved must be 0");
+    if (f->n_types < 1 || f->n_types > acx::FUSED_MAX_TYPES) return fail(c, ACX_ERR_INVALID, w + ": fused.n_types must be 1 or 2 (got " + std::to_string(f->n_types) + ")");
+    for (int t = 0; t < f->n_types; ++t) {
+        if (f->count[t] < 2 || f->count[t] > acx::FUSED_MAX_PLANES)
+            return fail(c, ACX_ERR_INVALID, w + ": fused.count[" + std::to_string(t) + "] must be in 2..4 (got " + std::to_string(f->count[t]) + ")");
+        for (int i = 0; i < f->count[t]; ++i)
+            if (f->planes[t][i] < 0 || f->planes[t][i] >= W)
+                return fail(c, ACX_ERR_INVALID, w + ": fused.planes[" + std::to_string(t) + "][" + std::to_string(i) + "] = " + std::to_string(f->planes[t][i]) +
+                                                    " is not a plane in [0, " + std::to_string(W) + ")");
+    }
+    if (f->transform != ACX_FUSED_SQRTLEN && f->transform != ACX_FUSED_INV1P) return fail(c, ACX_ERR_INVALID, w + ": fused.transform is not an ACX_FUSED_* value");
+    if (col_mode != (f->transform == ACX_FUSED_SQRTLEN ? 2 : 0))
+        return fail(c, ACX_ERR_INVALID, w + ": spec.col_mode must be 2 with ACX_FUSED_SQRTLEN and 0 with ACX_FUSED_INV1P");
+    if (f->K < 1) return fail(c, ACX_ERR_INVALID, w + ": fused.K must be >= 1 (got " + std::to_string(f->K) + ")");
+    if (f->K > acx::FUSED_MAX_K) return fail(c, ACX_ERR_UNSUPPORTED, w + ": more than 64 neighbours are not supported on the device (fused.K = " + std::to_string(f->K) + ")");
+    if (f->niters < 1) return fail(c, ACX_ERR_INVALID, w + ": fused.niters must be >= 1 (got " + std::to_string(f->niters) + ")");
+    if (!(f->mu > 0.0)) return fail(c, ACX_ERR_INVALID, w + ": fused.mu must be > 0");
+    if (!std::isfinite(f->reg_diag)) return fail(c, ACX_ERR_INVALID, w + ": fused.reg_diag must be finite");
+    return ACX_OK;
+}
+
+// The device side of a chunk, as its kernels take it
+struct FusedDev {
+    const acx::FusedProb *probs; const int32_t *tracks; double *mats; double *V; int32_t *J;
+    int P, max_n, M;
+};
+
+// One fused type of a chunk, all problems at once, launch for launch the sequence of acx_snf_fuse_dists (snf_prepare_dev per
+// matrix, snf_loop): the distances of the type's planes lie in the D slots; on return the fused matrices lie in the acc slots.
+static void fused_snf_batch(acx_ctx *c, const FusedDev &d, int m, int K, int niters, double reg_diag, double mu)
+{
+    const int M = d.M, n = d.max_n;
+    const unsigned P = (unsigned)d.P, cells = (unsigned)(((int64_t)n * n + 255) / 256), rows4 = (unsigned)((n + 3) / 4), t32 = (unsigned)((n + 31) / 32);
+    const int acc = acx::fused_slot_acc(M), ut = acx::fused_slot_ut(M), md = acx::fused_slot_md(M);
+    {
+        ProfScope ps(c, KS_SNFBATCHPREP, (int64_t)d.P * m);
+        for (int i = 0; i < m; ++i) {
+            hipLaunchKernelGGL(acx::snf_batch_sym_kernel, dim3(t32, t32, P), dim3(256), 0, c->stream, d.probs, d.mats, acx::fused_slot_dist(M, i), ut);
+            hipLaunchKernelGGL(acx::snf_batch_localscale_kernel, dim3(rows4, P), dim3(256), 0, c->stream, d.probs, d.mats, ut, md, K);
+            hipLaunchKernelGGL(acx::snf_batch_affinity_kernel, dim3(cells, P), dim3(256), 0, c->stream, d.probs, d.mats, ut, md, mu);
+            hipLaunchKernelGGL(acx::snf_batch_knn_kernel, dim3(rows4, P), dim3(256), 0, c->stream, d.probs, d.mats, ut, d.J, d.V, i, K);
+            hipLaunchKernelGGL(acx::snf_batch_rownorm_kernel, dim3((unsigned)n, P), dim3(256), 0, c->stream, d.probs, d.mats, ut, acx::fused_slot_cur(M, i));
+        }
+    }
+    ProfScope ps(c, KS_SNFBATCHUPDATE, (int64_t)d.P * m * niters);
+    for (int it = 0; it < niters; ++it)
+        for (int i = 0; i < m; ++i) {
+            // (from the second sweep on the two work lists alias, as in snf_loop)
+            acx::SnfSlots sp;
+            sp.count = 0;
+            for (int k = 0; k < m; ++k)
+                if (k != i) sp.s[sp.count++] = it == 0 ? acx::fused_slot_cur(M, k) : acx::fused_slot_nxt(M, k);
+            hipLaunchKernelGGL(acx::snf_batch_mean_kernel, dim3(cells, P), dim3(256), 0, c->stream, d.probs, d.mats, sp, 1.0 / (double)(m - 1), acc);
+            hipLaunchKernelGGL(acx::snf_batch_ast_kernel, dim3((unsigned)n, P), dim3(256), (size_t)n * sizeof(double), c->stream, d.probs, d.mats, acc, ut,
+                               d.J, d.V, i, K);
+            hipLaunchKernelGGL(acx::snf_batch_sut_kernel, dim3((unsigned)n, P), dim3(256), 0, c->stream, d.probs, d.mats, ut, acx::fused_slot_nxt(M, i), d.J,
+                               d.V, i, K, reg_diag);
+        }
+    acx::SnfSlots sp;
+    sp.count = m;
+    for (int k = 0; k < m; ++k) sp.s[k] = acx::fused_slot_nxt(M, k);
+    hipLaunchKernelGGL(acx::snf_batch_mean_kernel, dim3(cells, P), dim3(256), 0, c->stream, d.probs, d.mats, sp, 1.0 / (double)m, acc);
+}
+
+int acx_query_fused_lists(acx_ctx *c, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
+                          const int32_t *lists, int32_t list_len, const double *col, const acx_fused_spec *fused, int32_t k,
+                          int32_t *out_idx, float *out_score, uint8_t *out_flag)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const char *who = "query_fused_lists";
+    QueryCall Q;
+    int rc = query_check(c, who, spec, params, queries, n_queries, nullptr, 0, col, Q);
+    if (rc != ACX_OK) return rc;
+    if (Q.algo != ACX_ALGO_CHENFUSION && Q.algo != ACX_ALGO_EARLYFUSION)
+        return fail(c, ACX_ERR_INVALID, std::string(who) + ": spec.algo must be ACX_ALGO_CHENFUSION or ACX_ALGO_EARLYFUSION (the classes with a late fusion)");
+    if (Q.symmetric != 1) return fail(c, ACX_ERR_INVALID, std::string(who) + ": spec.symmetric must be 1 (a pair is scored as (min, max) and mirrored)");
+    if ((rc = fused_check_spec(c, who, fused, Q.w, Q.mode)) != ACX_OK) return rc;
+    if ((rc = rank_check_k(c, who, k, n_queries, out_idx, out_score)) != ACX_OK) return rc;
+    if (n_queries > 0 && !out_flag) return fail(c, ACX_ERR_INVALID, std::string(who) + ": out_flag must not be NULL");
+    if (list_len > acx::FUSED_MAX_LIST)
+        return fail(c, ACX_ERR_UNSUPPORTED, std::string(who) + ": list_len = " + std::to_string(list_len) + " is over the limit of " + std::to_string(acx::FUSED_MAX_LIST));
+    if ((rc = query_check_lists(c, who, Q.n, n_queries, lists, list_len)) != ACX_OK) return rc;
+    const int L = list_len, K = fused->K, nt = fused->n_types;
+    std::vector<int32_t> ns((size_t)n_queries);
+    for (int32_t i = 0; i < n_queries; ++i) {
+        int n = 1;
+        for (int j = 0; j < L; ++j) n += (lists[(size_t)i * L + j] >= 0 && lists[(size_t)i * L + j] != queries[i]) ? 1 : 0;
+        if (n < K + 2)
+            return fail(c, ACX_ERR_INVALID, std::string(who) + ": lists row " + std::to_string(i) + " gives a neighbourhood of " + std::to_string(n) +
+                                                " tracks (the query included); the fusion needs at least K + 2 = " + std::to_string(K + 2));
+        ns[i] = n;
+    }
+    if (n_queries == 0) return ACX_OK;
+    int M = 0;
+    for (int t = 0; t < nt; ++t) M = std::max(M, fused->count[t]);
+    int unfit = -1;
+    const std::vector<int> ends = acx::fused_chunks(ns, Q.w, M, K, nt, k, scratch_limit_bytes(c) / 2, &unfit);
+    if (unfit >= 0)
+        return fail(c, ACX_ERR_NOMEM, std::string(who) + ": the neighbourhood of lists row " + std::to_string(unfit) + " (" + std::to_string(ns[unfit]) + " tracks, " +
+                                          std::to_string(acx::fused_problem_bytes(ns[unfit], Q.w, M, K, nt, k)) + " bytes) does not fit half of the scratch limit");
+    // the block is sized for the largest chunk of each part
+    std::vector<acx::FusedChunk> chunks;
+    size_t mx_pairs = 0, mx_mat = 0, mx_list = 0, mx_probs = 0, mx_tracks = 0;
+    int max_n = 0;
+    for (size_t ci = 0, first = 0; ci < ends.size(); first = (size_t)ends[ci++]) {
+        chunks.push_back(acx::fused_chunk(queries, lists, L, (int)first, ends[ci], M, K));
+        const acx::FusedChunk &ch = chunks.back();
+        mx_pairs = std::max(mx_pairs, (size_t)ch.pairs); mx_mat = std::max(mx_mat, (size_t)ch.mat); mx_list = std::max(mx_list, (size_t)ch.list);
+        mx_probs = std::max(mx_probs, ch.probs.size()); mx_tracks = std::max(mx_tracks, ch.tracks.size());
+        max_n = std::max(max_n, ch.max_n);
+    }
+    ACX_HIP(c, hipSetDevice(c->device));
+    int P2 = 4;
+    while (P2 < std::min<int>(k, max_n - 1)) P2 <<= 1;
+    const size_t row_lds = 12 * (size_t)P2 + acx::RANK_SELECT_LDS_FIXED + 4 * (size_t)max_n;
+    const acx::FusedLayout lay = acx::fused_layout(mx_pairs * Q.w, col ? Q.n : 0, mx_mat, mx_list, mx_probs, mx_tracks, mx_probs * nt * k, mx_probs * nt);
+    return with_device_block(c, who, lay.total, [&](char *d_mem) -> int {
+        const double *d_col;
+        int rc2 = query_part(c, d_mem, lay.col, col, (size_t)Q.n, d_col);
+        if (rc2 != ACX_OK) return rc2;
+        float *d_slab = query_out<float>(d_mem, lay.slab);
+        int32_t *d_idx = query_out<int32_t>(d_mem, lay.idx);
+        float *d_sc = query_out<float>(d_mem, lay.score);
+        uint8_t *d_flag = query_out<uint8_t>(d_mem, lay.flag);
+        std::vector<int32_t> pairs;
+        std::vector<int64_t> idx;
+        int first = 0;
+        for (size_t ci = 0; ci < chunks.size(); first = ends[ci++]) {
+            const acx::FusedChunk &ch = chunks[ci];
+            const int P = (int)ch.probs.size();
+            FusedDev d;
+            d.mats = query_out<double>(d_mem, lay.mat); d.V = query_out<double>(d_mem, lay.V); d.J = query_out<int32_t>(d_mem, lay.J);
+            d.P = P; d.max_n = ch.max_n; d.M = M;
+            if ((rc2 = query_part(c, d_mem, lay.probs, ch.probs.data(), ch.probs.size(), d.probs)) != ACX_OK ||
+                (rc2 = query_part(c, d_mem, lay.tracks, ch.tracks.data(), ch.tracks.size(), d.tracks)) != ACX_OK)
+                return rc2;
+            ACX_HIP(c, hipMemsetAsync(d_slab, 0, sizeof(float) * (size_t)ch.pairs * Q.w, c->stream));
+            ACX_HIP(c, hipMemsetAsync(d_flag, 0, (size_t)P * nt, c->stream));
+            acx::fused_chunk_pairs(ch, Q.w, pairs, idx);
+            // a limit the caller set covers the chunk too: the pair kernels batch within what the chunk leaves of it
+            if ((rc2 = run_pair_list(c, Q.algo, Q.params, pairs.data(), idx.data(), (int64_t)idx.size(), d_slab, (int64_t)lay.total)) != ACX_OK) return rc2;
+            const unsigned cells = (unsigned)(((int64_t)ch.max_n * ch.max_n + 255) / 256);
+            for (int t = 0; t < nt; ++t) {
+                acx::FusedPlanes pl;
+                pl.count = fused->count[t];
+                for (int i = 0; i < acx::FUSED_MAX_PLANES; ++i) pl.p[i] = i < pl.count ? fused->planes[t][i] : 0;
+                {
+                    ProfScope ps(c, KS_FUSEDSTAGE, (int64_t)ch.pairs * pl.count);
+                    hipLaunchKernelGGL(acx::fused_stage_kernel, dim3(cells, (unsigned)P), dim3(256), 0, c->stream, d.probs, d_slab, Q.w, d_col, d.tracks, pl,
+                                       (int)fused->transform, d.mats, d_flag + t, nt);
+                }
+                fused_snf_batch(c, d, pl.count, K, fused->niters, fused->reg_diag, fused->mu);
+                ProfScope ps(c, KS_FUSEDROW, (int64_t)P);
+                hipLaunchKernelGGL(acx::fused_row_kernel, dim3((unsigned)P), dim3(acx::RANK_THREADS), row_lds, c->stream, d.probs, d.mats, acx::fused_slot_acc(M),
+                                   d.tracks, (int)k, P2, d_idx, d_sc, nt * (int)k, t * (int)k);
+            }
+            ACX_LAUNCHES_OK(c);
+            const size_t nres = (size_t)P * nt * k;
+            ACX_HIP(c, hipMemcpyAsync(out_idx + (size_t)first * nt * k, d_idx, 4 * nres, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(out_score + (size_t)first * nt * k, d_sc, 4 * nres, hipMemcpyDeviceToHost, c->stream));
+            ACX_HIP(c, hipMemcpyAsync(out_flag + (size_t)first * nt, d_flag, (size_t)P * nt, hipMemcpyDeviceToHost, c->stream));
+            // (the host vectors of the chunk and the descriptors' place in the block are reused by the next one)
+            ACX_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        return ACX_OK;
     });
 }
 

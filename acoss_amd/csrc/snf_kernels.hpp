@@ -10,11 +10,13 @@
 
 namespace acx {
 
-// P = W / rowsum(W) (rows that sum to 0 stay as they are); one workgroup per row
-__global__ __launch_bounds__(256) void snf_rownorm_kernel(const double *__restrict__ W, double *__restrict__ P, int n)
+// The bodies below are __device__ functions of a row (tile, cell) index: the kernels of this file call them with their
+// block index, the batched kernels of snf_batch_kernels.hpp with a problem's matrices and the block index within it.  One
+// body, one operation order, the same bits.
+
+// P = W / rowsum(W) (rows that sum to 0 stay as they are); one workgroup per row.  part: 256 doubles of LDS
+__device__ __forceinline__ void snf_rownorm_row(const double *__restrict__ W, double *__restrict__ P, int n, int i, double *part)
 {
-    __shared__ double part[256];
-    const int i = blockIdx.x;
     const double *w = W + (size_t)i * n;
     double s = 0.0;
     for (int c = threadIdx.x; c < n; c += 256) s += w[c];
@@ -29,27 +31,34 @@ __global__ __launch_bounds__(256) void snf_rownorm_kernel(const double *__restri
     double *p = P + (size_t)i * n;
     for (int c = threadIdx.x; c < n; c += 256) p[c] = w[c] / rs;
 }
+__global__ __launch_bounds__(256) void snf_rownorm_kernel(const double *__restrict__ W, double *__restrict__ P, int n)
+{
+    __shared__ double part[256];
+    snf_rownorm_row(W, P, n, (int)blockIdx.x, part);
+}
 
 // acc = (sum of the given matrices) * scale, elementwise; srcs: up to 8 pointers
 struct SnfSrc { const double *p[8]; int count; };
+__device__ __forceinline__ void snf_mean_cell(const SnfSrc &src, double scale, double *__restrict__ acc, int64_t e)
+{
+    double s = 0.0;
+    for (int k = 0; k < src.count; ++k) s += src.p[k][e];
+    acc[e] = s * scale;
+}
 __global__ __launch_bounds__(256) void snf_mean_kernel(SnfSrc src, double scale, double *__restrict__ acc, int64_t total)
 {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= total) return;
-    double s = 0.0;
-    for (int k = 0; k < src.count; ++k) s += src.p[k][e];
-    acc[e] = s * scale;
+    snf_mean_cell(src, scale, acc, e);
 }
 
 // UT = A S^T:  UT[j][i] = sum_k V[i][k] A[j][J[i][k]].  One workgroup per row j; the row of A sits in
 // LDS (n <= 20 000 doubles) and every thread gathers its K neighbours from it.  LDSROW = false:
 // the gathers go to global memory (any n).
 template <bool LDSROW>
-__global__ __launch_bounds__(256) void snf_ast_kernel(const double *__restrict__ A, const int32_t *__restrict__ J,
-                                                      const double *__restrict__ V, double *__restrict__ UT, int n, int K)
+__device__ __forceinline__ void snf_ast_row(const double *__restrict__ A, const int32_t *__restrict__ J, const double *__restrict__ V,
+                                            double *__restrict__ UT, int n, int K, int j, double *row)
 {
-    extern __shared__ double row[];
-    const int j = blockIdx.x;
     const double *a = A + (size_t)j * n;
     if (LDSROW) {
         for (int c = threadIdx.x; c < n; c += 256) row[c] = a[c];
@@ -65,14 +74,19 @@ __global__ __launch_bounds__(256) void snf_ast_kernel(const double *__restrict__
         ut[i] = s;
     }
 }
+template <bool LDSROW>
+__global__ __launch_bounds__(256) void snf_ast_kernel(const double *__restrict__ A, const int32_t *__restrict__ J,
+                                                      const double *__restrict__ V, double *__restrict__ UT, int n, int K)
+{
+    extern __shared__ double row[];
+    snf_ast_row<LDSROW>(A, J, V, UT, n, K, (int)blockIdx.x, row);
+}
 
 // P = S UT (+ reg on the diagonal):  P[i][c] = sum_k V[i][k] UT[J[i][k]][c].  One workgroup per row i,
 // threads over the columns: K coalesced row reads per output row.
-__global__ __launch_bounds__(256) void snf_sut_kernel(const double *__restrict__ UT, const int32_t *__restrict__ J,
-                                                      const double *__restrict__ V, double *__restrict__ P, int n, int K,
-                                                      double reg_diag)
+__device__ __forceinline__ void snf_sut_row(const double *__restrict__ UT, const int32_t *__restrict__ J, const double *__restrict__ V,
+                                            double *__restrict__ P, int n, int K, double reg_diag, int i)
 {
-    const int i = blockIdx.x;
     const int32_t *ji = J + (size_t)i * K;
     const double *vi = V + (size_t)i * K;
     double *p = P + (size_t)i * n;
@@ -82,6 +96,12 @@ __global__ __launch_bounds__(256) void snf_sut_kernel(const double *__restrict__
         if (c == i) s += reg_diag;
         p[c] = s;
     }
+}
+__global__ __launch_bounds__(256) void snf_sut_kernel(const double *__restrict__ UT, const int32_t *__restrict__ J,
+                                                      const double *__restrict__ V, double *__restrict__ P, int n, int K,
+                                                      double reg_diag)
+{
+    snf_sut_row(UT, J, V, P, n, K, reg_diag, (int)blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------
@@ -100,10 +120,10 @@ __device__ __forceinline__ double snf_unkey(unsigned long long k)
 }
 
 // S = 0.5 (D + D^T) with a zero diagonal; 32 x 32 tiles through LDS so that both reads are coalesced
-__global__ __launch_bounds__(256) void snf_sym_kernel(const double *__restrict__ D, double *__restrict__ S, int n)
+__device__ __forceinline__ void snf_sym_tile(const double *__restrict__ D, double *__restrict__ S, int n, int tile_x, int tile_y,
+                                             double (*tile)[33])
 {
-    __shared__ double tile[32][33];
-    const int bx = blockIdx.x * 32, by = blockIdx.y * 32;
+    const int bx = tile_x * 32, by = tile_y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;          // 32 x 8
     for (int r = ty; r < 32; r += 8) {
         const int i = bx + r, j = by + tx;                            // D[bx + r][by + tx]: the transposed tile
@@ -117,6 +137,11 @@ __global__ __launch_bounds__(256) void snf_sym_kernel(const double *__restrict__
             S[(size_t)i * n + j] = (i == j) ? 0.0 : v;
         }
     }
+}
+__global__ __launch_bounds__(256) void snf_sym_kernel(const double *__restrict__ D, double *__restrict__ S, int n)
+{
+    __shared__ double tile[32][33];
+    snf_sym_tile(D, S, n, (int)blockIdx.x, (int)blockIdx.y, tile);
 }
 
 // k-th smallest (0-based) key of a row of n doubles: binary search on the key, ballots count
@@ -138,9 +163,9 @@ __device__ __forceinline__ unsigned long long snf_select(const double *__restric
 
 // md[i] = mean of the K + 1 smallest of row i of S (the zero diagonal included) * (K + 1) / K
 // (similarity_fusion.py:27-30).  One wave per row; ties at the cut contribute their common value.
-__global__ __launch_bounds__(256) void snf_localscale_kernel(const double *__restrict__ S, double *__restrict__ md, int n, int K)
+__device__ __forceinline__ void snf_localscale_rows(const double *__restrict__ S, double *__restrict__ md, int n, int K, int blk)
 {
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int i = blk * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= n) return;
     const double *row = S + (size_t)i * n;
     const int take = K + 1 < n ? K + 1 : n;
@@ -155,12 +180,14 @@ __global__ __launch_bounds__(256) void snf_localscale_kernel(const double *__res
     for (int off = 32; off >= 1; off >>= 1) { s += __shfl_xor(s, off, 64); below += __shfl_xor(below, off, 64); }
     if (lane == 0) md[i] = (s + (double)(take - below) * t) / (double)take * (double)(K + 1) / (double)K;
 }
+__global__ __launch_bounds__(256) void snf_localscale_kernel(const double *__restrict__ S, double *__restrict__ md, int n, int K)
+{
+    snf_localscale_rows(S, md, n, K, (int)blockIdx.x);
+}
 
 // W = exp(-S^2 / (2 (mu eps)^2)), eps = (md_i + md_j + S_ij) / 3, zero denominators -> 1 (:31-36); in place
-__global__ __launch_bounds__(256) void snf_affinity_kernel(double *__restrict__ S, const double *__restrict__ md, int n, double mu)
+__device__ __forceinline__ void snf_affinity_cell(double *__restrict__ S, const double *__restrict__ md, int n, double mu, int64_t e)
 {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (int64_t)n * n) return;
     const int i = (int)(e / n), j = (int)(e - (int64_t)i * n);
     const double d = S[e];
     const double eps = (md[i] + md[j] + d) / 3.0;
@@ -168,17 +195,22 @@ __global__ __launch_bounds__(256) void snf_affinity_kernel(double *__restrict__ 
     if (den == 0.0) den = 1.0;
     S[e] = exp(-(d * d) / den);
 }
+__global__ __launch_bounds__(256) void snf_affinity_kernel(double *__restrict__ S, const double *__restrict__ md, int n, double mu)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)n * n) return;
+    snf_affinity_cell(S, md, n, mu, e);
+}
 
 // The K largest of every row of W (ties at the cut in column order -- a stable descending sort, like
 // the host's _knn_lists), ordered by (value descending, column), weights divided by their sum (getS).
 // One wave per row, K <= 64.
-__global__ __launch_bounds__(256) void snf_knn_kernel(const double *__restrict__ W, int32_t *__restrict__ J, double *__restrict__ V,
-                                                      int n, int K)
+// cv, cj: 4 x 64 slots of LDS, one row of 64 per wave.
+__device__ __forceinline__ void snf_knn_rows(const double *__restrict__ W, int32_t *__restrict__ J, double *__restrict__ V, int n, int K,
+                                             int blk, double (*cv)[64], int (*cj)[64])
 {
-    __shared__ double cv[4][64];
-    __shared__ int cj[4][64];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + wv;
+    const int i = blk * 4 + wv;
     if (i >= n) return;
     const double *row = W + (size_t)i * n;
     // K-th largest = (n - K)-th smallest (0-based)
@@ -235,6 +267,13 @@ __global__ __launch_bounds__(256) void snf_knn_kernel(const double *__restrict__
         J[(size_t)i * K + rank] = jj;
         V[(size_t)i * K + rank] = v / sum;
     }
+}
+__global__ __launch_bounds__(256) void snf_knn_kernel(const double *__restrict__ W, int32_t *__restrict__ J, double *__restrict__ V,
+                                                      int n, int K)
+{
+    __shared__ double cv[4][64];
+    __shared__ int cj[4][64];
+    snf_knn_rows(W, J, V, n, K, (int)blockIdx.x, cv, cj);
 }
 
 }  // namespace acx

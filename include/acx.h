@@ -1013,6 +1013,54 @@ int acx_query_ranks(acx_ctx *ctx, const acx_query_spec *spec, const void *params
 int acx_query_topk_lists(acx_ctx *ctx, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
                          const int32_t *lists, int32_t list_len, const double *col, int32_t k, int32_t *out_idx, float *out_score);
 
+/* Fused scores for query shortlists: similarity network fusion (acx_snf_fuse_dists) is a function of a SET of tracks, so
+ * it is defined on a query's neighbourhood -- the query and its shortlist -- as what the classes' late fusion computes on a
+ * collection that holds only those tracks.  queries / lists / list_len as in acx_query_topk_lists (any order, -1 = an
+ * empty slot, the query's own track is skipped, a track twice in a row is ACX_ERR_INVALID).  For query i:
+ *   T        = sorted({queries[i]} U valid entries of row i), ascending track index, n = |T|
+ *   scores   every unordered pair of T as the pair (min, max) -- spec->symmetric must be 1 -- with the bits of
+ *            acx_chenfusion_pairs / acx_earlyfusion_pairs, mirrored
+ *   dists    per fused type t and its planes fused->planes[t][0 .. count[t]) (pair-kernel plane indices, in THIS order: the
+ *            sweep's in-place aliasing makes the order matter), an n x n f64 matrix each:
+ *              ACX_FUSED_SQRTLEN  (double)(float)(col[c] / (double)s) for column c   (spec->col_mode 2, col = sqrt(T_c):
+ *                                 ChenFusion.normalize_by_length's f32 value, widened as do_late_fusion reads it)
+ *              ACX_FUSED_INV1P    1 / (1 + (double)s)                                (spec->col_mode 0, col NULL: EarlyFusion)
+ *            the diagonal is 0 (the fusion zeroes it whatever it holds)
+ *   fusion   acx_snf_fuse_dists(those matrices, K, niters, reg_diag, mu): the SAME bits (the batched kernels run the row
+ *            bodies of the single-problem kernels)
+ *   ranking  row queries[i] of the fused matrix without its own column, every value rounded ONCE to f32, in the order of
+ *            acx_topk_rows (larger first, ties by ascending track index, NaN last, tail -1 / NaN), as collection indices:
+ *            out_idx / out_score are n_queries x n_types x k
+ *   flag     out_flag[i * n_types + t] = 1 where an off-diagonal distance of type t is not finite (a ChenFusion raw score of
+ *            0): that row is NaN as in the whole-collection fusion; the other queries are unaffected
+ * With two fused types (EarlyFusion 'late' and 'early+late') the pairs are scored once and fused twice.
+ *   cost     n (n - 1) / 2 alignments per query (acx_query_topk_lists: list_len); a pair two neighbourhoods share is
+ *            computed twice
+ *   memory   the queries of a chunk hold their pair scores, (3 m + 2) n^2 + n doubles (distances, two generations of P,
+ *            two work matrices, the local scales), m n K list entries and their results at once, m = the most planes of a
+ *            type, within HALF of acx_set_scratch_limit; one neighbourhood that does not fit: ACX_ERR_NOMEM
+ *   errors   validated before anything is allocated or launched: the common rules above, spec->symmetric == 1, the struct
+ *            (n_types 1..2, count 2..4, planes in [0, planes of the algorithm), transform and its col_mode, reserved == 0,
+ *            1 <= K, K > 64: ACX_ERR_UNSUPPORTED, niters >= 1, mu > 0), k, list_len > 1024: ACX_ERR_UNSUPPORTED, the
+ *            lists, then n >= K + 2 for every row (the message names the row: the K-neighbour cut of the reference is not
+ *            defined below); a failure after that leaves nothing in flight
+ * n_queries == 0: ACX_OK. */
+#define ACX_FUSED_SQRTLEN 1
+#define ACX_FUSED_INV1P 2
+typedef struct {
+    int32_t n_types;        /* fused types of the call: 1 or 2 */
+    int32_t count[2];       /* planes of each type: 2 .. 4 */
+    int32_t planes[2][4];   /* their pair-kernel plane indices, in fusion order */
+    int32_t transform;      /* ACX_FUSED_* */
+    int32_t K, niters;      /* do_late_fusion: 20, 20 */
+    int32_t reserved;       /* 0 */
+    double reg_diag, mu;    /* do_late_fusion: 1, 0.5 */
+} acx_fused_spec;
+
+int acx_query_fused_lists(acx_ctx *ctx, const acx_query_spec *spec, const void *params, const int32_t *queries, int32_t n_queries,
+                          const int32_t *lists, int32_t list_len, const double *col, const acx_fused_spec *fused, int32_t k,
+                          int32_t *out_idx, float *out_score, uint8_t *out_flag);
+
 /* ---- appends: tracks behind an uploaded pool, and away again ------------- */
 
 /*
