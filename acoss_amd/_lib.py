@@ -51,6 +51,7 @@ EXPORTS = [
     "acx_ef_crossfusion_pairs", "acx_ef_crossfusion_debug", "acx_crossfusion_matrices", "acx_xsel_binary_sw",
     "acx_ef_download_pool",
     "acx_ef_align_long", "acx_sw_align_long_binary",
+    "acx_serra09_align_sections", "acx_qmax_sections_binary",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -72,6 +73,28 @@ SIMPLE_ALIGNMENT_DTYPE = np.dtype([("score", np.float64), ("best_dist", np.float
                                    ("best_r", np.int32), ("q0", np.int32), ("r0", np.int32), ("q1", np.int32), ("r1", np.int32),
                                    ("q_span", np.int32, (2,)), ("r_span", np.int32, (2,)), ("run_len", np.int32)])
 assert SIMPLE_ALIGNMENT_DTYPE.itemsize == 64
+
+
+class SectionOpts(ctypes.Structure):
+    """acx_section_opts (include/acx.h): how many sections of a pair at most, rows excluded on either side of one, and the
+    thresholds on a section's score (absolute, and relative to section 0's)."""
+    _fields_ = [("max_sections", ctypes.c_int32), ("pad", ctypes.c_int32), ("min_score", ctypes.c_float), ("min_ratio", ctypes.c_float)]
+
+
+def section_opts(who, max_sections=4, min_score=2.0, min_ratio=0.0, pad=0):
+    """The checks of acx_section_opts, worded by the caller's name `who`, before any library call -> SectionOpts."""
+    for name, v in (("max_sections", max_sections), ("pad", pad)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s: %s must be an integer, got %r" % (who, name, v))
+    if not 1 <= max_sections <= 16:
+        raise ValueError("%s: max_sections must be in [1, 16], got %r" % (who, max_sections))
+    if not 0 <= pad < 2 ** 31:
+        raise ValueError("%s: pad must be >= 0, got %r" % (who, pad))
+    if not np.float32(min_score) > 1:
+        raise ValueError("%s: min_score must be > 1 (a section has at least two cells), got %r" % (who, min_score))
+    if not 0 <= np.float32(min_ratio) <= 1:
+        raise ValueError("%s: min_ratio must be in [0, 1], got %r" % (who, min_ratio))
+    return SectionOpts(int(max_sections), int(pad), float(min_score), float(min_ratio))
 
 
 class EfParams(ctypes.Structure):
@@ -320,6 +343,10 @@ def load():
     L.acx_serra09_align_paths.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
     L.acx_qmax_path_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, pp, ctypes.c_void_p,
                                        ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_int64]
+    L.acx_serra09_align_sections.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.POINTER(SectionOpts), ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+    L.acx_qmax_sections_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, pp, ctypes.POINTER(SectionOpts),
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
     L.acx_chenfusion_align.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.c_int32, ctypes.c_void_p]
     L.acx_chenfusion_align_paths.argtypes = [vp, ip, ctypes.c_int64, pp, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_int64]
@@ -1328,6 +1355,49 @@ class Context(object):
         cells (L, 2) int32 from the start to the end; L == 0: no match).  cap: default min(M, N)."""
         p = params or serra09_params()
         return self._align_plot("acx_qmax_path_binary", R, "R", (ctypes.byref(p),), cap=cap, n_first=True)
+
+    def _sections_out(self, K, S, paths, cap):
+        """The buffers of a sections call over K pairs: records (K, S), counts (K,), offsets (K S + 1,) and cells (cap, 2) or None."""
+        out = np.zeros((K, S), ALIGNMENT_DTYPE)
+        n = np.zeros(K, np.int32)
+        if not paths:
+            return out, n, None, None
+        return out, n, np.zeros(K * S + 1, np.int64), np.zeros((max(int(cap), 1), 2), np.int32)
+
+    def serra09_align_sections(self, pairs, params=None, opts=None, paths=False, cap=None):
+        """EVERY matched section of every (query, reference) pair (acx_serra09_align_sections): (records, counts)
+        -- records a (K, max_sections) structured array (ALIGNMENT_DTYPE), section 0 first, the no-match record behind the counts[k]
+        sections of pair k -- and with paths=True (records, counts, offsets, cells): section s of pair k has the cells
+        cells[offsets[k * max_sections + s]:offsets[k * max_sections + s + 1]].  opts: a SectionOpts (section_opts(); default its
+        defaults).  cap: default the bound the library checks, the sum of min(Mq_k, max_sections * min(Mq_k, Mr_k))."""
+        p = params or serra09_params()
+        o = opts or section_opts("serra09_align_sections")
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        if paths and cap is None:
+            Ms = {t: max(self.serra09_embed_len(self.lengths[t], p), 0) for t in {int(t) for t in pairs.ravel()} if 0 <= t < len(self.lengths)}
+            cap = sum(min(Ms.get(int(i), 0), o.max_sections * min(Ms.get(int(i), 0), Ms.get(int(j), 0))) for i, j in pairs)
+        out, n, off, cells = self._sections_out(len(pairs), o.max_sections, paths, cap)
+        self._check(self._L.acx_serra09_align_sections(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), ctypes.byref(o), out.ctypes.data,
+                                                       n.ctypes.data, off.ctypes.data if paths else None,
+                                                       cells.ctypes.data if paths else None, int(cap) if paths else 0))
+        return (out, n, off, cells[:off[-1]].copy()) if paths else (out, n)
+
+    def qmax_sections_binary(self, R, params=None, opts=None, paths=True, cap=None):
+        """The same DP alone on a given binary (M, N) plot (acx_qmax_sections_binary): (records (max_sections,), count) and with
+        paths=True (records, count, offsets (max_sections + 1,), cells).  cap: default min(M, max_sections * min(M, N))."""
+        p = params or serra09_params()
+        o = opts or section_opts("qmax_sections_binary")
+        R = np.ascontiguousarray(R, dtype=np.uint8)
+        if R.ndim != 2:
+            raise ValueError("qmax_sections_binary: R must be (M, N), got shape %s" % (R.shape,))
+        if paths and cap is None:
+            cap = min(R.shape[0], o.max_sections * min(R.shape))
+        out, n, off, cells = self._sections_out(1, o.max_sections, paths, cap)
+        self._check(self._L.acx_qmax_sections_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), R.shape[0], R.shape[1],
+                                                     ctypes.byref(p), ctypes.byref(o), out.ctypes.data, n.ctypes.data,
+                                                     off.ctypes.data if paths else None, cells.ctypes.data if paths else None,
+                                                     int(cap) if paths else 0))
+        return (out[0], int(n[0]), off, cells[:off[-1]].copy()) if paths else (out[0], int(n[0]))
 
     def chenfusion_align(self, pairs, params=None, plane=0):
         """WHERE the alignment of one plane of chenfusion_pairs lies (acx_chenfusion_align): plane 0 Qmax -- serra09_align itself --,

@@ -124,6 +124,21 @@ class ChenFusion(Serra09):
         out[rows, slots] = self._align_pairs(pairs, got, plane)
         return out, _align.scatter_paths(idx, rows, slots, got)
 
+    def _sections_plane(self, who, similarity_type):
+        """The sections are the Qmax alignment's: 'dmax' and 'Late' have none, ValueError naming the method."""
+        if self._align_plane(who, similarity_type) != 0:
+            raise ValueError("%s: the sections are those of the Qmax alignment; similarity_type must be 'qmax', got '%s'" % (who, similarity_type))
+
+    def align_sections(self, idxs, max_sections=4, min_score=2.0, min_ratio=0.0, pad=0, paths=False, similarity_type="qmax"):
+        """Serra09.align_sections() of the plot the class scores twice: the Qmax sections ('qmax', the default and the only one)."""
+        self._sections_plane("align_sections", similarity_type)
+        return Serra09.align_sections(self, idxs, max_sections, min_score, min_ratio, pad, paths)
+
+    def align_match_sections(self, queries, indices, max_sections=4, min_score=2.0, min_ratio=0.0, pad=0, paths=False, similarity_type="qmax"):
+        """Serra09.align_match_sections() for 'qmax' (the default and the only one)."""
+        self._sections_plane("align_match_sections", similarity_type)
+        return Serra09.align_match_sections(self, queries, indices, max_sections, min_score, min_ratio, pad, paths)
+
     @refused_in_session
     def rerank_tracks_fused(self, tracks, shortlists, k=10, similarity_types=None, K=20, niters=20, raw=False):
         """CoverAlgorithm.rerank_tracks_fused; tracks and raw as in identify_tracks."""

@@ -248,15 +248,16 @@ class Serra09(CoverAlgorithm):
     def _align_pairs(self, pairs, paths=None, plane=0):
         """(K, 2) checked int32 pairs -> (K,) ALIGN_DTYPE.  paths: a list that receives the K (L_k, 2) int32 paths as well.
         plane: what a subclass with more than one alignment hands to its _align_call."""
-        out = np.zeros(len(pairs), self.ALIGN_DTYPE)
-        out["score"] = 0.0
-        for f in ("q0", "r0", "q1", "r1", "q_span", "r_span"):
-            out[f] = -1
         if len(pairs) == 0:
-            return out
+            return self._no_match_rows(0)
         al, off, cells = self._align_call(pairs, paths is not None, plane)
         if paths is not None:
             paths.extend(cells[off[k]:off[k + 1]] for k in range(len(pairs)))
+        return self._align_rows(al, pairs)
+
+    def _align_rows(self, al, pairs):
+        """(K,) records of the library for the (K, 2) pairs -> (K,) ALIGN_DTYPE: the fields, and the spans in pooled frames."""
+        out = self._no_match_rows(len(pairs))
         for f in _lib.ALIGNMENT_DTYPE.names:
             out[f] = al[f]
         hit = al["q0"] >= 0
@@ -319,6 +320,56 @@ class Serra09(CoverAlgorithm):
         got = []
         out[rows, slots] = self._align_pairs(pairs, got)
         return out, _align.scatter_paths(idx, rows, slots, got)
+
+    # ------------------------------------------------------------------ every matched section of a pair
+    def _section_pairs(self, pairs, o, want_paths):
+        """(P, 2) checked int32 pairs -> (a P-list of (n_k,) ALIGN_DTYPE arrays, a P-list of lists of n_k (L, 2) int32 paths or None)."""
+        if len(pairs) == 0:
+            return [], ([] if want_paths else None)
+        got = self._context().serra09_align_sections(pairs, self._params(), o, paths=want_paths)
+        al, n = got[0], got[1]
+        S = al.shape[1]
+        out = self._align_rows(al.reshape(-1), np.repeat(pairs, S, axis=0)).reshape(al.shape)      # (align()'s rows, a pair's S together)
+        sections = [out[k, :n[k]].copy() for k in range(len(pairs))]
+        if not want_paths:
+            return sections, None
+        off, cells = got[2], got[3]
+        return sections, [[cells[off[k * S + s]:off[k * S + s + 1]] for s in range(n[k])] for k in range(len(pairs))]
+
+    def align_sections(self, idxs, max_sections=4, min_score=2.0, min_ratio=0.0, pad=0, paths=False):
+        """EVERY matched section of a pair, not only the best one: a cover that repeats the chorus once more, a live version with
+        a solo between two matched halves, a medley that quotes two passages of one reference.  idxs: (K, 2) (query, reference)
+        track indices as for align().  Returns a K-list of (n_k,) structured arrays with align()'s fields and spans, n_k <=
+        max_sections (at most 16), section 0 first; with paths=True (sections, paths), paths[k] a list of n_k (L, 2) int32
+        arrays as align_paths() lists them.
+          section 0      exactly align()'s row for the pair, provided its score >= min_score; otherwise the pair has no sections
+          section k + 1  the Qmax alignment of what is left when the QUERY's embedded frames q0 .. q1 of every section found so
+                         far, and `pad` frames on either side of each (never across an earlier section), are excluded -- the
+                         recursion's value is 0 on those rows, so no alignment runs through them; reported iff its score >=
+                         max(min_score, min_ratio * section 0's score).  The search ends at the first section that fails.
+        Scores do not increase with k; every QUERY frame belongs to at most one section (the row ranges are disjoint), while
+        reference frames may be shared: the query repeats a chorus the reference plays once.  The sections segment the query;
+        for a segmentation of the reference swap the pair.  min_score must be > 1, 0 <= min_ratio <= 1, pad >= 0.
+        `Ds` is not written; not a collective."""
+        pairs = self._check_align_pairs("align_sections", idxs)
+        o = _lib.section_opts("align_sections", max_sections, min_score, min_ratio, pad)
+        sections, got = self._section_pairs(pairs, o, bool(paths))
+        return (sections, got) if paths else sections
+
+    def align_match_sections(self, queries, indices, max_sections=4, min_score=2.0, min_ratio=0.0, pad=0, paths=False):
+        """align_sections() for the hits of identify() / rerank(): queries (Q,) track indices, indices the (Q, k) int array either
+        returned (-1: an empty slot).  Returns a Q-list of k-lists of (n,) arrays as align_sections() returns them -- an empty slot
+        is an empty array -- and with paths=True (sections, paths), paths a Q-list of k-lists of lists of (L, 2) int32 arrays."""
+        idx, rows, slots, pairs = self._check_align_matches("align_match_sections", queries, indices)
+        o = _lib.section_opts("align_match_sections", max_sections, min_score, min_ratio, pad)
+        sections, got = self._section_pairs(pairs, o, bool(paths))
+        out = [[np.zeros(0, self.ALIGN_DTYPE) for _ in range(idx.shape[1])] for _ in range(idx.shape[0])]
+        out_paths = [[[] for _ in range(idx.shape[1])] for _ in range(idx.shape[0])]
+        for t, (r, s) in enumerate(zip(rows, slots)):
+            out[r][s] = sections[t]
+            if paths:
+                out_paths[r][s] = got[t]
+        return (out, out_paths) if paths else out
 
     @refused_in_session
     def normalize_by_length(self):

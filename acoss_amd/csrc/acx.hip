@@ -41,6 +41,7 @@
 #include "fused_plan.hpp"
 #include "snf_batch_kernels.hpp"
 #include "serra09_plan.hpp"
+#include "serra09_sections_kernels.hpp"
 #include "device_buffer.hpp"
 
 using acx::PairDesc;
@@ -57,7 +58,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_DLOCATE, KS_DPATH, KS_SIMPLEPROF, KS_XFMEANS, KS_XFAFFINITY, KS_XFSNF, KS_XFX, KS_XFSELECT, KS_FUSEDSTAGE, KS_SNFBATCHPREP, KS_SNFBATCHUPDATE, KS_FUSEDROW, KS_EFALIGNLONG, KS_EFALIGN, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_SECTIONS, KS_DLOCATE, KS_DPATH, KS_SIMPLEPROF, KS_XFMEANS, KS_XFAFFINITY, KS_XFSNF, KS_XFX, KS_XFSELECT, KS_FUSEDSTAGE, KS_SNFBATCHPREP, KS_SNFBATCHUPDATE, KS_FUSEDROW, KS_EFALIGNLONG, KS_EFALIGN, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -86,6 +87,10 @@ struct Serra09Slot {
     std::vector<int64_t> seam_off;
     DeviceBuffer<int64_t> d_seam_off;
     bool al = false;
+    // acx_serra09_align_sections: `sec` records per pair in d_al / h_al (0: one, acx_serra09_align's), and how many of them are sections
+    int sec = 0;
+    DeviceBuffer<int32_t> d_nsec;
+    PinnedBuffer<int32_t> h_nsec;
 };
 
 }  // namespace
@@ -221,6 +226,7 @@ struct acx_ctx {
                              {"topk_rows_kernel", 0, 0, 0}, {"ftm2d_tile_kernel", 0, 0, 0}, {"query_rows_kernel", 0, 0, 0},
                              {"query_topk_kernel", 0, 0, 0}, {"query_rank_kernel", 0, 0, 0}, {"query_topk_lists_kernel", 0, 0, 0},
                              {"ftm2d_pairs_kernel", 0, 0, 0}, {"qmax_locate_kernel", 0, 0, 0}, {"qmax_path_kernel", 0, 0, 0},
+                             {"qmax_sections_kernel", 0, 0, 0},
                              {"dmax_locate_kernel", 0, 0, 0}, {"dmax_path_kernel", 0, 0, 0},
                              {"simple_profile_kernel", 0, 0, 0}, {"xf_means_kernel", 0, 0, 0}, {"xf_affinity_kernels", 0, 0, 0},
                              {"xf_snf_kernels", 0, 0, 0}, {"xf_x_kernel", 0, 0, 0}, {"xf_select_kernel", 0, 0, 0},
@@ -620,11 +626,16 @@ int64_t scratch_limit_bytes(const acx_ctx *c)
 
 // Results of one batch come back through a pinned staging slot; two slots, so that the host packs
 // batch b + 1 (descriptors, size classes) while the device works on batch b.
-int collect_slot(acx_ctx *c, Serra09Slot &s, float *out, acx_alignment *al = nullptr)
+int collect_slot(acx_ctx *c, Serra09Slot &s, float *out, acx_alignment *al = nullptr, int32_t *nsec = nullptr)
 {
     if (!s.busy) return ACX_OK;
     ACX_HIP(c, hipEventSynchronize(s.done));
-    for (int k2 = 0; s.al && al && k2 < s.B; ++k2) al[s.k0 + s.perm[k2]] = s.h_al[(size_t)k2];
+    for (int k2 = 0; s.al && !s.sec && al && k2 < s.B; ++k2) al[s.k0 + s.perm[k2]] = s.h_al[(size_t)k2];
+    for (int k2 = 0; s.al && s.sec && al && nsec && k2 < s.B; ++k2) {      // (the sections of a pair stay together)
+        const size_t k = (size_t)(s.k0 + s.perm[k2]);
+        for (int e = 0; e < s.sec; ++e) al[k * s.sec + e] = s.h_al[(size_t)k2 * s.sec + e];
+        nsec[k] = s.h_nsec[(size_t)k2];
+    }
     for (int k2 = 0; !s.al && out && k2 < s.B; ++k2)
         for (int e = 0; e < s.w; ++e) out[(size_t)s.w * (s.k0 + s.perm[k2]) + e] = s.h_out[(size_t)s.w * k2 + e];
     s.busy = false;
@@ -778,6 +789,25 @@ void launch_qmax_locate(hipStream_t st, const PairDesc *pd, int B, const unsigne
         hipLaunchKernelGGL((acx::qmax_locate_kernel<false>), dim3(B), dim3(64), 0, st, pd, bits, seam, seam_off, dst, gamma_o, gamma_e, dp_start);
 }
 
+// What acx_serra09_align_sections adds to an alignment run (run_serra09_impl's `sec`).
+struct SectionRun {
+    acx_section_opts o;
+    int32_t *n;            // where the pairs' section counts go (K of them, in the order of the list)
+};
+
+// Every section of B pairs (serra09_sections_kernels.hpp), one wave per pair and one launch: pair k's o.max_sections records go to
+// dst[k * o.max_sections ..], their number to n_dst[k]; bitmaps and seam records as for launch_qmax_locate.
+void launch_qmax_sections(hipStream_t st, const PairDesc *pd, int B, const unsigned long long *bits, acx::LocSeam *seam, const int64_t *seam_off,
+                          acx_alignment *dst, int32_t *n_dst, float gamma_o, float gamma_e, int dp_start, const acx_section_opts &o)
+{
+    if (gamma_o == gamma_e)
+        hipLaunchKernelGGL((acx::qmax_sections_kernel<true>), dim3(B), dim3(64), 0, st, pd, bits, seam, seam_off, dst, n_dst, gamma_o, gamma_e,
+                           dp_start, o.max_sections, o.pad, o.min_score, o.min_ratio);
+    else
+        hipLaunchKernelGGL((acx::qmax_sections_kernel<false>), dim3(B), dim3(64), 0, st, pd, bits, seam, seam_off, dst, n_dst, gamma_o, gamma_e,
+                           dp_start, o.max_sections, o.pad, o.min_score, o.min_ratio);
+}
+
 // The same for the Dmax alignment (chen_align_kernels.hpp): same records, same seam buffer.
 void launch_dmax_locate(hipStream_t st, const PairDesc *pd, int B, const unsigned long long *bits, acx::LocSeam *seam, const int64_t *seam_off,
                         acx_alignment *dst, float gamma_o, float gamma_e, int dp_start)
@@ -793,12 +823,13 @@ void launch_dmax_locate(hipStream_t st, const PairDesc *pd, int B, const unsigne
 // go to dst(k2) as (q, r) from start to end; a pair without a match gets none.  The boxes run in CHUNKS: as many consecutive boxes as
 // fit path_budget_bytes (direction planes + seam records) and one launch's grid; a single box beyond it is ACX_ERR_NOMEM (`name(k2)`
 // says which pair).  Runs on the main stream and returns with it idle.  `dmax`: the records are a Dmax locating sweep's and the pass is
-// dmax_path_kernel (same boxes, planes, records and budget).
+// dmax_path_kernel (same boxes, planes, records and budget).  `per` (acx_serra09_align_sections): every pair has `per` records, record
+// k2 being section k2 % per of pair k2 / per -- its box names that pair's descriptor -- and dst / name take the record's index.
 int64_t path_budget_bytes(const acx_ctx *c) { return scratch_limit_bytes(c) / 2; }
 
 template <typename Dst, typename Name>
 int run_qmax_paths(acx_ctx *c, const PairDesc *dpd, const acx_alignment *recs, int B, float gamma_o, float gamma_e, Dst dst, Name name,
-                   bool dmax = false)
+                   bool dmax = false, int per = 1)
 {
     const std::string who = dmax ? "dmax_path: " : "qmax_path: ";
     const int64_t budget = path_budget_bytes(c);
@@ -806,6 +837,7 @@ int run_qmax_paths(acx_ctx *c, const PairDesc *dpd, const acx_alignment *recs, i
     std::vector<int> owner;
     std::vector<int32_t> h_n, h_cells;
     int k2 = 0;
+    B *= per;
     while (k2 < B) {
         boxes.clear(); owner.clear();
         int64_t words = 0, seams = 0, ncell = 0, bytes = 0, area = 0;
@@ -822,7 +854,7 @@ int run_qmax_paths(acx_ctx *c, const PairDesc *dpd, const acx_alignment *recs, i
                                                   " (half the scratch limit)");
             if (bytes + need > budget) break;
             acx::PathBox bx;
-            bx.pair = k2; bx.q0 = a.q0; bx.r0 = a.r0; bx.q1 = a.q1; bx.r1 = a.r1;
+            bx.pair = k2 / per; bx.q0 = a.q0; bx.r0 = a.r0; bx.q1 = a.q1; bx.r1 = a.r1;
             bx.max_cells = std::min(rows, width);
             bx.dir_off = words; bx.seam_off = seams; bx.cell_off = ncell;
             words += (int64_t)rows * acx::path_words(width);
@@ -901,10 +933,15 @@ void launch_streaming_class(acx_ctx *c, const PairDesc *dpd, const PairDesc *pd,
 // Runs the chain over `K` pairs in scratch-sized batches (behind run_serra09's guard, below).  `al` (acx_serra09_align): the sweep is
 // qmax_locate_kernel and pair k's record goes to al[k]; no scores are written.  `paths` (acx_serra09_align_paths, with `al`; K vectors):
 // the path pass runs behind the locating sweep of every batch, and pair k's cells go to (*paths)[k].  `al_dmax` (acx_chenfusion_align*,
-// plane 1; with `al`): the locating sweep and the path pass are the Dmax ones.
+// plane 1; with `al`): the locating sweep and the path pass are the Dmax ones.  `sec` (acx_serra09_align_sections, with `al`): the sweep is
+// qmax_sections_kernel, pair k's sec->o.max_sections records go to al[k * max_sections ..] and their number to sec->n[k]; `paths` then
+// has one vector per record.
 int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
-                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al, std::vector<std::vector<int32_t>> *paths, bool al_dmax)
+                     const DebugOut *dbg, bool both, const DevDst *dd, acx_alignment *al, std::vector<std::vector<int32_t>> *paths, bool al_dmax,
+                     const SectionRun *sec)
 {
+    const int per = sec ? sec->o.max_sections : 1;     // records per pair of an alignment run
+    int32_t *const nsec = sec ? sec->n : nullptr;
     if (!c->d_frames0) return fail(c, ACX_ERR_STATE, "serra09: feature pool not uploaded (acx_upload_pool)");
     if (c->dim != acx::NBIN) return fail(c, ACX_ERR_INVALID, "serra09: pool dim must be 12");
     int rc = check_params(c, p_in);
@@ -937,7 +974,7 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
     int64_t k0 = 0;
     for (int batch = 0; k0 < K; ++batch) {
         Serra09Slot &S = c->slot[batch & 1];
-        if ((rc = collect_slot(c, S, out, al)) != ACX_OK) return rc;
+        if ((rc = collect_slot(c, S, out, al, nsec)) != ACX_OK) return rc;
         // the plan of the batch (serra09_plan.hpp): its pairs and their arena offsets, then the sort by size-class key --
         // `S.perm[k]` = position in the batch of sorted pair k
         std::vector<PairDesc> &pd = S.pd;
@@ -968,8 +1005,10 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
             int64_t seams = 0;
             S.seam_off.resize((size_t)B);
             for (int k2 = 0; k2 < B; ++k2) { S.seam_off[(size_t)k2] = seams; seams += acx::loc_seam_records(pd[k2].Mq, pd[k2].Mr, p.dp_start); }
-            if ((rc = ensure(c, S.d_al, (size_t)B)) != ACX_OK) return rc;
-            if ((rc = ensure(c, S.h_al, (size_t)B)) != ACX_OK) return rc;
+            if ((rc = ensure(c, S.d_al, (size_t)B * per)) != ACX_OK) return rc;
+            if ((rc = ensure(c, S.h_al, (size_t)B * per)) != ACX_OK) return rc;
+            if (sec && (rc = ensure(c, S.d_nsec, (size_t)B)) != ACX_OK) return rc;
+            if (sec && (rc = ensure(c, S.h_nsec, (size_t)B)) != ACX_OK) return rc;
             if ((rc = ensure(c, S.d_seam_off, (size_t)B)) != ACX_OK) return rc;
             if ((rc = ensure(c, c->d_seam, (size_t)std::max<int64_t>(seams, 1))) != ACX_OK) return rc;
             ACX_HIP(c, hipMemcpyAsync(S.d_seam_off, S.seam_off.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, c->stream));
@@ -1052,7 +1091,10 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
                                       sw.cols, sw.pack);
                 }
             };
-            if (al) {                 // WHERE the alignment lies: one launch for the batch, every class the same kernel
+            if (sec) {                // every section: one launch for the batch, the loop over sections inside it
+                ProfScope ps(c, KS_SECTIONS, acx::serra09_extent(pd, 0, B).cells, qs);
+                launch_qmax_sections(qs, S.d_pd, B, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, S.d_nsec, p.gamma_o, p.gamma_e, p.dp_start, sec->o);
+            } else if (al) {          // WHERE the alignment lies: one launch for the batch, every class the same kernel
                 ProfScope ps(c, al_dmax ? KS_DLOCATE : KS_LOCATE, acx::serra09_extent(pd, 0, B).cells, qs);
                 if (al_dmax) launch_dmax_locate(qs, S.d_pd, B, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, p.gamma_o, p.gamma_e, p.dp_start);
                 else launch_qmax_locate(qs, S.d_pd, B, c->d_bits, c->d_seam, S.d_seam_off, S.d_al, p.gamma_o, p.gamma_e, p.dp_start);
@@ -1067,7 +1109,8 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         }
         ACX_LAUNCHES_OK(c);
         if (al) {
-            ACX_HIP(c, hipMemcpyAsync(S.h_al, S.d_al, sizeof(acx_alignment) * B, hipMemcpyDeviceToHost, qs));
+            ACX_HIP(c, hipMemcpyAsync(S.h_al, S.d_al, sizeof(acx_alignment) * B * per, hipMemcpyDeviceToHost, qs));
+            if (sec) ACX_HIP(c, hipMemcpyAsync(S.h_nsec, S.d_nsec, sizeof(int32_t) * B, hipMemcpyDeviceToHost, qs));
         } else if (dd) {
             hipLaunchKernelGGL(scatter_scores_kernel, dim3((B + 255) / 256), dim3(256), 0, qs,
                                S.d_out, S.d_idx, dd->base, B, w);
@@ -1076,12 +1119,12 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
             ACX_HIP(c, hipMemcpyAsync(S.h_out, S.d_out, sizeof(float) * B * w, hipMemcpyDeviceToHost, qs));
         }
         ACX_HIP(c, hipEventRecord(S.done, qs));
-        S.busy = true; S.on_q = use_q; S.B = B; S.w = w; S.k0 = k0; S.al = al != nullptr;
+        S.busy = true; S.on_q = use_q; S.B = B; S.w = w; S.k0 = k0; S.al = al != nullptr; S.sec = sec ? per : 0;
         if (al && paths) {     // the paths, while d_bits holds this batch: the boxes come from the batch's records, so the host waits here
             ACX_HIP(c, hipEventSynchronize(S.done));
             if ((rc = run_qmax_paths(c, S.d_pd, S.h_al, B, p.gamma_o, p.gamma_e,
-                                     [&](int k2) -> std::vector<int32_t> & { return (*paths)[(size_t)(k0 + perm[k2])]; },
-                                     [&](int k2) { return std::to_string(k0 + perm[k2]); }, al_dmax)) != ACX_OK) return rc;
+                                     [&](int k2) -> std::vector<int32_t> & { return (*paths)[(size_t)(k0 + perm[k2 / per]) * per + k2 % per]; },
+                                     [&](int k2) { return std::to_string(k0 + perm[k2 / per]); }, al_dmax, per)) != ACX_OK) return rc;
         }
 
         if (dbg && B >= 1) {
@@ -1102,15 +1145,15 @@ int run_serra09_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serr
         k0 = k;
     }
     for (int s = 0; s < 2; ++s)
-        if ((rc = collect_slot(c, c->slot[s], out, al)) != ACX_OK) return rc;
+        if ((rc = collect_slot(c, c->slot[s], out, al, nsec)) != ACX_OK) return rc;
     return ACX_OK;
 }
 
 int run_serra09(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params &p_in, float *out,
                 const DebugOut *dbg, bool both = false, const DevDst *dd = nullptr, acx_alignment *al = nullptr,
-                std::vector<std::vector<int32_t>> *paths = nullptr, bool al_dmax = false)
+                std::vector<std::vector<int32_t>> *paths = nullptr, bool al_dmax = false, const SectionRun *sec = nullptr)
 {
-    return guarded(c, [&] { return run_serra09_impl(c, pairs, K, p_in, out, dbg, both, dd, al, paths, al_dmax); });
+    return guarded(c, [&] { return run_serra09_impl(c, pairs, K, p_in, out, dbg, both, dd, al, paths, al_dmax, sec); });
 }
 
 }  // namespace
@@ -2373,6 +2416,49 @@ int acx_dmax_locate_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, c
     return locate_binary(c, R, M, N, params, out, true, "dmax_locate_binary");
 }
 
+// no more cells than this in the paths of one pair's `per` records: a path has no more cells than its plot's shorter side, and the
+// sections of a pair (per > 1) are row-disjoint with at most as many cells each as their box has rows (per == 1: min(Mq, Mr))
+static int64_t path_cells_bound(int Mq, int Mr, int per)
+{
+    return std::min<int64_t>(Mq, (int64_t)per * std::min(Mq, Mr));
+}
+
+// What the path exports check before the first launch: the run's own checks of the list, in its order, and `cap` against the bound
+// the host knows then -- the sum over the list of path_cells_bound(Mq_k, Mr_k, per) in embedded frames, `rule` in the message.
+static int check_path_cap(acx_ctx *c, const std::string &who, const int32_t *pairs, int64_t K, const acx_serra09_params &params, int64_t cap,
+                          int per, const char *rule)
+{
+    if (!c->d_frames0) return fail(c, ACX_ERR_STATE, "serra09: feature pool not uploaded (acx_upload_pool)");
+    if (c->dim != acx::NBIN) return fail(c, ACX_ERR_INVALID, "serra09: pool dim must be 12");
+    int rc = check_params(c, params);
+    if (rc != ACX_OK) return rc;
+    const acx::Serra09Lengths len{c->h_off0.data(), c->n_tracks, params.tau};
+    if ((rc = validate_serra09_pairs(c, len, pairs, K, params, false, scratch_limit_bytes(c) / 4)) != ACX_OK) return rc;
+    int64_t bound = 0;
+    for (int64_t k = 0; k < K; ++k) {
+        PairDesc d;
+        acx::Serra09Need need;
+        (void)acx::serra09_size_pair(len, pairs[2 * k], pairs[2 * k + 1], params, false, d, need);
+        bound += path_cells_bound(d.Mq, d.Mr, per);
+    }
+    if (cap < bound)
+        return fail(c, ACX_ERR_INVALID, who + ": cap " + std::to_string(cap) + " is too small: " + std::to_string(bound) +
+                                            " cells required (the sum of " + rule + " over the list)");
+    return ACX_OK;
+}
+
+// the paths of a run, one vector per record, packed behind one another: path_off[t + 1] = cells up to and including record t
+static void pack_paths(const std::vector<std::vector<int32_t>> &paths, int64_t *path_off, int32_t *cells)
+{
+    int64_t n = 0;
+    path_off[0] = 0;
+    for (size_t t = 0; t < paths.size(); ++t) {
+        if (!paths[t].empty()) memcpy(cells + 2 * n, paths[t].data(), sizeof(int32_t) * paths[t].size());
+        n += (int64_t)paths[t].size() / 2;
+        path_off[t + 1] = n;
+    }
+}
+
 // acx_serra09_align_paths, and (`al_dmax`) plane 1 of acx_chenfusion_align_paths; `who` names the entry point in errors.
 static int align_paths(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, acx_alignment *out,
                        int64_t *path_off, int32_t *cells, int64_t cap, bool al_dmax, const std::string &who)
@@ -2381,32 +2467,12 @@ static int align_paths(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_se
         return fail(c, ACX_ERR_INVALID, who + ": bad argument");
     path_off[0] = 0;
     if (K == 0) return ACX_OK;
-    // the run's own checks of the list, in its order, so that the bound on the cells is known before the first launch
-    if (!c->d_frames0) return fail(c, ACX_ERR_STATE, "serra09: feature pool not uploaded (acx_upload_pool)");
-    if (c->dim != acx::NBIN) return fail(c, ACX_ERR_INVALID, "serra09: pool dim must be 12");
-    int rc = check_params(c, *params);
+    // (no path has more cells than its plot's shorter side)
+    int rc = check_path_cap(c, who, pairs, K, *params, cap, 1, "min(Mq, Mr)");
     if (rc != ACX_OK) return rc;
-    const acx::Serra09Lengths len{c->h_off0.data(), c->n_tracks, params->tau};
-    if ((rc = validate_serra09_pairs(c, len, pairs, K, *params, false, scratch_limit_bytes(c) / 4)) != ACX_OK) return rc;
-    int64_t bound = 0;                           // no path has more cells than its plot's shorter side
-    for (int64_t k = 0; k < K; ++k) {
-        PairDesc d;
-        acx::Serra09Need need;
-        (void)acx::serra09_size_pair(len, pairs[2 * k], pairs[2 * k + 1], *params, false, d, need);
-        bound += std::min(d.Mq, d.Mr);
-    }
-    if (cap < bound)
-        return fail(c, ACX_ERR_INVALID, who + ": cap " + std::to_string(cap) + " is too small: " + std::to_string(bound) +
-                                            " cells required (the sum of min(Mq, Mr) over the list)");
     std::vector<std::vector<int32_t>> paths((size_t)K);
     if ((rc = run_serra09(c, pairs, K, *params, nullptr, nullptr, false, nullptr, out, &paths, al_dmax)) != ACX_OK) return rc;
-    int64_t n = 0;
-    for (int64_t k = 0; k < K; ++k) {
-        const std::vector<int32_t> &pk = paths[(size_t)k];
-        if (!pk.empty()) memcpy(cells + 2 * n, pk.data(), sizeof(int32_t) * pk.size());
-        n += (int64_t)pk.size() / 2;
-        path_off[k + 1] = n;
-    }
+    pack_paths(paths, path_off, cells);
     return ACX_OK;
 }
 
@@ -2473,6 +2539,89 @@ int acx_qmax_path_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, con
     if (!c) return ACX_ERR_INVALID;
     if (params && params->dmax != 0) return fail(c, ACX_ERR_UNSUPPORTED, "qmax_path_binary: the Qmax alignment only (params->dmax must be 0)");
     return path_binary(c, R, M, N, params, out, n_cells, cells, cap, false, "qmax_path_binary");
+}
+
+// ---- every section of a pair ----
+// The option checks of acx_serra09_align_sections / acx_qmax_sections_binary, before any launch.
+static int check_section_opts(acx_ctx *c, const std::string &who, const acx_section_opts &o)
+{
+    if (o.max_sections < 1 || o.max_sections > acx::SEC_MAX)
+        return fail(c, ACX_ERR_INVALID, who + ": max_sections must be in [1, " + std::to_string(acx::SEC_MAX) + "]");
+    if (o.pad < 0) return fail(c, ACX_ERR_INVALID, who + ": pad must be >= 0");
+    if (!(o.min_score > 1.0f)) return fail(c, ACX_ERR_INVALID, who + ": min_score must be > 1");
+    if (!(o.min_ratio >= 0.0f && o.min_ratio <= 1.0f)) return fail(c, ACX_ERR_INVALID, who + ": min_ratio must be in [0, 1]");
+    return ACX_OK;
+}
+
+int acx_serra09_align_sections(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_serra09_params *params, const acx_section_opts *opts,
+                               acx_alignment *out, int32_t *n_sections, int64_t *path_off, int32_t *cells, int64_t cap)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const std::string who = "serra09_align_sections";
+    if (params && params->dmax != 0) return fail(c, ACX_ERR_UNSUPPORTED, who + ": the Qmax alignment only (params->dmax must be 0)");
+    if (K < 0 || (K > 0 && (!pairs || !out || !n_sections)) || !params || !opts || (path_off == nullptr) != (cells == nullptr) || (cells && cap < 0))
+        return fail(c, ACX_ERR_INVALID, who + ": bad argument");
+    int rc = check_section_opts(c, who, *opts);
+    if (rc != ACX_OK) return rc;
+    const int S = opts->max_sections;
+    if (path_off) path_off[0] = 0;
+    if (K == 0) return ACX_OK;
+    SectionRun sec{*opts, n_sections};
+    if (!cells) return run_serra09(c, pairs, K, *params, nullptr, nullptr, false, nullptr, out, nullptr, false, &sec);
+    if ((rc = check_path_cap(c, who, pairs, K, *params, cap, S, "min(Mq, max_sections * min(Mq, Mr))")) != ACX_OK) return rc;
+    std::vector<std::vector<int32_t>> paths((size_t)K * S);
+    if ((rc = run_serra09(c, pairs, K, *params, nullptr, nullptr, false, nullptr, out, &paths, false, &sec)) != ACX_OK) return rc;
+    pack_paths(paths, path_off, cells);
+    return ACX_OK;
+}
+
+int acx_qmax_sections_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, const acx_section_opts *opts,
+                             acx_alignment *out, int32_t *n_sections, int64_t *path_off, int32_t *cells, int64_t cap)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const std::string who = "qmax_sections_binary";
+    if (params && params->dmax != 0) return fail(c, ACX_ERR_UNSUPPORTED, who + ": the Qmax alignment only (params->dmax must be 0)");
+    PairDesc d;
+    std::vector<unsigned long long> words;
+    static const int64_t seam_off = 0;
+    return guarded(c, [&]() -> int {
+        if (!R || !params || !opts || !out || !n_sections || M < 1 || N < 1 || (path_off == nullptr) != (cells == nullptr) || (cells && cap < 0))
+            return fail(c, ACX_ERR_INVALID, who + ": bad argument");
+        int rc = check_section_opts(c, who, *opts);
+        if (rc != ACX_OK) return rc;
+        const int S = opts->max_sections;
+        if (params->dp_start != 2 && params->dp_start != 3) return fail(c, ACX_ERR_INVALID, who + ": dp_start must be 2 or 3");
+        if (!(params->gamma_o >= 0.0f) || !(params->gamma_e >= 0.0f)) return fail(c, ACX_ERR_INVALID, who + ": gammas must be >= 0");
+        if ((int64_t)M * N + acx::LOC_STRIP >= ((int64_t)1 << 32)) return fail(c, ACX_ERR_UNSUPPORTED, who + ": the plot has 2^32 cells or more");
+        if (cells && cap < path_cells_bound(M, N, S))
+            return fail(c, ACX_ERR_INVALID, who + ": cap " + std::to_string(cap) + " is too small: " + std::to_string(path_cells_bound(M, N, S)) +
+                                                " cells required (min(M, max_sections * min(M, N)))");
+        ACX_HIP(c, hipSetDevice(c->device));
+        Serra09Slot &S0 = c->slot[0];
+        if ((rc = stage_serra09_plot(c, who, R, M, N, d, words)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_seam, (size_t)std::max<int64_t>(acx::loc_seam_records(M, N, params->dp_start), 1))) != ACX_OK) return rc;
+        if ((rc = ensure(c, S0.d_al, (size_t)S)) != ACX_OK) return rc;
+        if ((rc = ensure(c, S0.d_nsec, (size_t)1)) != ACX_OK) return rc;
+        if ((rc = ensure(c, S0.d_seam_off, (size_t)1)) != ACX_OK) return rc;
+        ACX_HIP(c, hipMemcpyAsync(S0.d_seam_off, &seam_off, sizeof(seam_off), hipMemcpyHostToDevice, c->stream));
+        {
+            ProfScope ps(c, KS_SECTIONS, (int64_t)M * N);
+            launch_qmax_sections(c->stream, S0.d_pd, 1, c->d_bits, c->d_seam, S0.d_seam_off, S0.d_al, S0.d_nsec, params->gamma_o, params->gamma_e,
+                                 params->dp_start, *opts);
+        }
+        ACX_HIP(c, hipGetLastError());
+        ACX_HIP(c, hipMemcpyAsync(out, S0.d_al, sizeof(acx_alignment) * S, hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipMemcpyAsync(n_sections, S0.d_nsec, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        drain_profile(c);
+        if (!cells) return ACX_OK;
+        std::vector<std::vector<int32_t>> paths((size_t)S);
+        rc = run_qmax_paths(c, S0.d_pd, out, 1, params->gamma_o, params->gamma_e,
+                            [&](int k2) -> std::vector<int32_t> & { return paths[(size_t)k2]; }, [](int) { return std::string("0"); }, false, S);
+        if (rc != ACX_OK) return rc;
+        pack_paths(paths, path_off, cells);
+        return ACX_OK;
+    });
 }
 
 int acx_dmax_path_binary(acx_ctx *c, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params, acx_alignment *out,

@@ -12,6 +12,9 @@
 //          being one monotone subtraction).
 //   start  S[i][j] = (i, j) where a path starts, S[pred] elsewhere; reported: S[end].
 // S is ONE u32 per cell, i * Mr + j: the host refuses a pair whose cells, plus one strip, reach 2^32.
+//
+// qmax_sections_kernel (serra09_sections_kernels.hpp) holds a COPY of this kernel's strip loop -- load_row, dp_row
+// and the wave's butterfly, line for line -- run per free interval of rows: a change to either is a change to both.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -87,6 +87,28 @@ def cover_set(n_works=None, versions=5, seed=4321, t_range=(300, 600), clique_si
     return dict(frames=frames, offsets=offsets, labels=labels)
 
 
+def work_ends(lengths, rng, slack=500, noise=0.05):
+    """Per pooled length T in `lengths` two versions (rolled, noisy) of ONE long chord sequence in cover_set's style: one of its first
+    T frames and one of its last T; the sequence is max(lengths) + slack frames long, so the two versions of a length share
+    T - slack frames of the work (none when T <= slack).  Returns (tracks, start, end): start[T] / end[T] index `tracks`.  The
+    draws are those of the pools of tests/test_gpu_qmax_path.py, so rng = default_rng([9, 16]) and that test's lengths give its tracks."""
+    tri = _triads()
+    W = max(lengths) + slack
+    chords = []
+    c = int(rng.integers(0, 24))
+    while len(chords) < W:
+        chords += [c] * int(rng.integers(4, 17))
+        c = (c + int(rng.choice([-5, -2, 2, 5, 7, 1]))) % 24
+    work = tri[np.array(chords[:W])]
+    tracks, start, end = [], {}, {}
+    for T in lengths:
+        for where, excerpt in ((start, work[:T]), (end, work[W - T:])):
+            where[T] = len(tracks)
+            x = np.roll(excerpt, int(rng.integers(0, 12)), axis=1) + noise * rng.random(excerpt.shape)
+            tracks.append(_frame_max_normalise(x))
+    return tracks, start, end
+
+
 COVERS80_CLIQUES = [2] * 77 + [3] * 2 + [4]   # 164 tracks / 80 works (covers80_annotations.csv)
 
 

@@ -277,6 +277,51 @@ int acx_qmax_path_binary(acx_ctx *ctx, const uint8_t *R, int32_t M, int32_t N, c
                          acx_alignment *out, int64_t *n_cells, int32_t *cells, int64_t cap);
 
 /*
+ * EVERY matched section of a pair, not only the best one: an excerpt played twice, two halves with a solo
+ * between them, a medley that quotes two passages of one reference.
+ *   section 0      the alignment above: bit for bit acx_serra09_align's record, provided its score is >= min_score; else the pair has none
+ *   free rows      the rows of the plot start as one free interval [0, Mq - 1].  A section with start row q0 and end row q1 that lies
+ *                  in the free interval [a, b] EXCLUDES rows [max(a, q0 - pad), min(b, q1 + pad)] (the pad never reaches across an
+ *                  earlier section); [a, b] is replaced by what is left above and below
+ *   section k + 1  the alignment above of Q', the same recursion with Q' = 0 on every cell of an excluded row (NOT the recursion on a
+ *                  plot with those rows cleared: a gap cell there would keep predecessor - gamma and bridge the stretch); reported iff
+ *                  its score >= max(min_score, min_ratio * score_0) (one f32 multiply; equality counts)
+ * The search ends at the first section that fails, or after max_sections.  Scores do not increase with k, the row ranges [q0, q1] of
+ * a pair's sections are pairwise disjoint -- every QUERY frame belongs to at most one section --, reference columns may be shared
+ * (the query repeats what the reference plays once; for a segmentation of the reference swap the pair).
+ *   1 <= max_sections <= 16, pad >= 0, min_score > 1 (a score above 1 has two path cells: q1 > q0), 0 <= min_ratio <= 1;
+ *   anything else -> ACX_ERR_INVALID before any launch.
+ */
+typedef struct { int32_t max_sections, pad; float min_score, min_ratio; } acx_section_opts;
+
+/*
+ * The sections of K (query, reference) pairs over the uploaded pool: the chain of acx_serra09_align (validation of the whole list
+ * before the first launch, batch plan, class sort, band / streaming kernels, error codes and messages), then ONE launch of
+ * qmax_sections_kernel per batch: one wave per pair, a sweep per free interval, the loop over sections inside the launch.
+ *   out         K x max_sections records: pair k's sections at out[k * max_sections ..], section 0 first; beyond n_sections[k] the
+ *               no-match record (score 0, -1 four times)
+ *   n_sections  K counts
+ *   path_off, cells, cap   both pointers NULL (cap ignored), or both given: the path of section s of pair k is
+ *               cells[2 * path_off[k * max_sections + s] .. 2 * path_off[k * max_sections + s + 1]), as acx_serra09_align_paths lists
+ *               a path (K * max_sections + 1 offsets); the path pass of section 17 over the sections' boxes, same budget and chunks.
+ *               cap is checked before the first launch against the sum over the list of min(Mq_k, max_sections * min(Mq_k, Mr_k))
+ *               (sections are row-disjoint, a path has at most as many cells as its box has rows): too small -> ACX_ERR_INVALID
+ *               with the required number in the message
+ * params->dmax != 0 -> ACX_ERR_UNSUPPORTED before anything else.
+ */
+int acx_serra09_align_sections(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_serra09_params *params,
+                               const acx_section_opts *opts, acx_alignment *out /* K x max_sections */, int32_t *n_sections /* K */,
+                               int64_t *path_off /* K x max_sections + 1, or NULL */, int32_t *cells /* cap x 2, or NULL */, int64_t cap);
+
+/*
+ * The same DP alone on a given binary (M, N) uint8 plot, as acx_qmax_locate_binary / acx_qmax_path_binary are: out max_sections
+ * records, *n_sections their number, path_off max_sections + 1 offsets; cap >= min(M, max_sections * min(M, N)).
+ */
+int acx_qmax_sections_binary(acx_ctx *ctx, const uint8_t *R, int32_t M, int32_t N, const acx_serra09_params *params,
+                             const acx_section_opts *opts, acx_alignment *out, int32_t *n_sections,
+                             int64_t *path_off, int32_t *cells, int64_t cap);
+
+/*
  * LateFusionChen: where the alignment of ONE of the two planes of acx_chenfusion_pairs lies, and its path.
  * plane 0: Qmax -- byte for byte acx_serra09_align / acx_serra09_align_paths; plane 1: Dmax (dmax_locate_kernel, dmax_path_kernel);
  * any other value -> ACX_ERR_INVALID before any launch.  params->dmax is ignored, as in acx_chenfusion_pairs.
