@@ -52,6 +52,7 @@ EXPORTS = [
     "acx_ef_download_pool",
     "acx_ef_align_long", "acx_sw_align_long_binary",
     "acx_serra09_align_sections", "acx_qmax_sections_binary",
+    "acx_ef_plan", "acx_ef_kernel_name",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -100,6 +101,15 @@ def section_opts(who, max_sections=4, min_score=2.0, min_ratio=0.0, pad=0):
 class EfParams(ctypes.Structure):
     """acx_ef_params (include/acx.h); defaults = EarlyFusion ctor, earlyfusion_traile.py:44-45."""
     _fields_ = [("kappa", ctypes.c_double), ("K", ctypes.c_int32)]
+
+
+class EfPlanRec(ctypes.Structure):
+    """acx_ef_plan_rec (include/acx.h)."""
+    _fields_ = [(name, ctypes.c_int32) for name in ("M", "N", "kbin", "batch", "path", "row_kernel", "col_kernel", "fuse_kernel",
+                                                    "sw_kernel", "reserved")] + [("run_pos", ctypes.c_int64), ("need", ctypes.c_int64)]
+
+
+EF_PLAN_STAGES = ("row_kernel", "col_kernel", "fuse_kernel", "sw_kernel")       # acx_ef_kernel_name's stage 0..3
 
 
 class GridSpec(ctypes.Structure):
@@ -315,6 +325,9 @@ def load():
     L.acx_set_ef_gemm.argtypes = [vp, ctypes.c_int32]
     L.acx_set_ef_fuse.argtypes = [vp, ctypes.c_int32]
     L.acx_earlyfusion_pairs.argtypes = [vp, ip, ctypes.c_int64, ep, fp]
+    L.acx_ef_plan.argtypes = [lp, ctypes.c_int32, ip, ctypes.c_int64, ep, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(EfPlanRec)]
+    L.acx_ef_kernel_name.restype = ctypes.c_char_p
+    L.acx_ef_kernel_name.argtypes = [ctypes.c_int32, ctypes.c_int32]
     L.acx_ef_debug_pair.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ep, fp, fp, fp, ip]
     L.acx_ef_debug_pairs.argtypes = [vp, ip, ctypes.c_int64, ep, ctypes.c_int64, fp, fp, fp, ip]
     L.acx_sw_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, fp]
@@ -510,6 +523,34 @@ def serra09_plan(lengths, pairs, params=None, scratch_limit=0):
         err.code = rc
         raise err
     return out
+
+
+def ef_plan(blocks, pairs, kappa=0.1, K=10, scratch_limit=0, keep_fused=False):
+    """acx_ef_plan: what acx_earlyfusion_pairs would do with the (K, 2) pair list on a pool whose tracks have these block counts -- a
+    pure host function, no GPU needed.  Returns a (K,) structured array with the fields of acx_ef_plan_rec (M, N, kbin, batch, path,
+    row_kernel, col_kernel, fuse_kernel, sw_kernel, run_pos, need), in the order of `pairs`.  A list the run would refuse raises
+    AcxError with the run's code as `.code`."""
+    L = load()
+    blocks = np.ascontiguousarray(blocks, dtype=np.int64)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    p = EfParams(float(kappa), int(K))
+    out = np.zeros(len(pairs), dtype=np.dtype(EfPlanRec))
+    rc = L.acx_ef_plan(_lptr(blocks), len(blocks), _iptr(pairs), len(pairs), ctypes.byref(p), int(scratch_limit), int(bool(keep_fused)),
+                       out.ctypes.data_as(ctypes.POINTER(EfPlanRec)))
+    if rc != ACX_OK:
+        err = AcxError("acx_ef_plan: code %d: %s" % (rc, (L.acx_last_error(None) or b"bad argument").decode()))
+        err.code = rc
+        raise err
+    return out
+
+
+def ef_kernel_name(stage, kernel):
+    """Printable name of a kernel of acx_ef_plan's records, as the library spells it: `stage` one of EF_PLAN_STAGES (or its index)."""
+    stage = EF_PLAN_STAGES.index(stage) if isinstance(stage, str) else int(stage)
+    name = load().acx_ef_kernel_name(stage, int(kernel))
+    if name is None:
+        raise ValueError("unknown EarlyFusion kernel %r of stage %r" % (kernel, stage))
+    return name.decode()
 
 
 def serra09_fast_tail(n_cells, role, params=None, debug=False):

@@ -41,6 +41,7 @@
 #include "fused_plan.hpp"
 #include "snf_batch_kernels.hpp"
 #include "serra09_plan.hpp"
+#include "ef_plan.hpp"
 #include "serra09_sections_kernels.hpp"
 #include "device_buffer.hpp"
 
@@ -1432,9 +1433,8 @@ static int launch_ef_gemms(acx_ctx *c, const SegBatch &seg, int B, int tiles_x, 
 // One pair of M x N at offset 0 of every arena: a caller's matrix or plot as a batch of its own.
 static acx::EfPair ef_one_pair(int M, int N, int kbin = 0)
 {
-    acx::EfPair d;
-    d.q = d.r = 0; d.M = M; d.N = N; d.oti = 0; d.pitchC = round_up(N, 64); d.pitchT = round_up(M, 64); d.kbin = kbin;
-    d.ctN = 0; d.pad = 0; d.offB = 0; d.offC = 0; d.offS = 0;
+    acx::EfPair d = acx::ef_pair_desc(0, 0, M, N, 1.0, false);
+    d.kbin = kbin;                        // (the caller's, not a kappa's)
     return d;
 }
 
@@ -1534,304 +1534,320 @@ static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, in
     return ACX_OK;
 }
 
-// `dd` (grid runs): the four scores of pair k go to dd->base[dd->idx[k] .. + 4) on the DEVICE instead of out[4 k ..].  (Behind
-// run_ef's guard, below.)
+// One batch on the host: its pair descriptors and arena extents (ef_pack_batch, ef_plan.hpp) and -- for the rectangle GEMM -- the
+// dense rectangles its pairs are laid out in.  Built for batch b + 1 WHILE the device works on batch b (two of these; the copies to
+// the device are staged before they return): ~1 ms per 16 384 pairs that the device used to wait for between batches.
+struct EfHostBatch {
+    std::vector<acx::EfPair> pd;
+    SegBatch seg;
+    std::vector<int32_t> qslot, rslot;          // (ef_build_rects' own)
+    int64_t k_begin = 0, k_end = 0;
+    acx::EfArena a;
+};
+
+// what run_ef_impl has settled about a checked list before its first batch
+struct EfRun {
+    acx::EfLengths len;
+    const int32_t *pairs;
+    int64_t K;
+    acx_ef_params p;
+    acx::EfMode mode;
+    int64_t batch_floats;
+    bool rect_gemm;
+};
+
+// `ht`: ACX_EF_HOST_TIMING's seconds for descriptors [0] and rectangles [1]
+static void prepare_ef_batch(acx_ctx *c, const EfRun &run, int64_t k_from, EfHostBatch &hb, double *ht)
+{
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_a = now();
+    hb.k_begin = k_from;
+    hb.k_end = acx::ef_pack_batch(run.len, run.pairs, k_from, run.K, run.p, run.mode, run.batch_floats, hb.pd, hb.a);
+    const double t_r = now();
+    ht[0] += t_r - t_a;
+    // the pairs of the batch laid out as dense rectangles (ef_gemm_rect_bf16x3_kernel)
+    if (run.rect_gemm) ef_build_rects(hb.pd, c->h_efoff, c->ef_ntracks, hb.seg, hb.qslot, hb.rslot);
+    ht[1] += now() - t_r;
+}
+
+// the one-row selection kernels (ACX_EF_ROW_2 / _4 / _LONG) in mode 0 (C), 1 (C^T) or 2 (the stored fused matrix)
+static void launch_ef_rowstat(acx_ctx *c, int kernel, dim3 grid, int mode, int Kn)
+{
+    switch (kernel) {
+    case ACX_EF_ROW_LONG:
+        hipLaunchKernelGGL(acx::ef_rowstat_long_kernel, grid, dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, mode, Kn);
+        break;
+    case ACX_EF_ROW_4:
+        hipLaunchKernelGGL((acx::ef_rowstat_kernel<4, false>), grid, dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_efbits, mode, Kn, 0);
+        break;
+    default:
+        hipLaunchKernelGGL((acx::ef_rowstat_kernel<2, false>), grid, dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_efbits, mode, Kn, 0);
+    }
+}
+
+// the fused matrix: made, thresholded and binarised row by row (stored too when keep_f)
+template <int NQ>
+static void launch_ef_fusesel(acx_ctx *c, dim3 grid, int Kn, int keep_f)
+{
+    if (c->ef_fuse == ACX_EF_FUSE_EXACT)
+        hipLaunchKernelGGL((acx::ef_rowstat_kernel<NQ, true, true>), grid, dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_efbits, 3, Kn, keep_f);
+    else
+        hipLaunchKernelGGL((acx::ef_rowstat_kernel<NQ, true, false>), grid, dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_efbits, 3, Kn, keep_f);
+}
+
+// `src`: the matrix of the float kernels (0: every feature of the grid, 3: the fused one); the bit kernels walk every plane of the grid
+static void launch_ef_sw(acx_ctx *c, int kernel, dim3 grid, int src)
+{
+    switch (kernel) {
+    case ACX_EF_SW_H16_8:
+        hipLaunchKernelGGL((acx::sw_bits_h16_kernel<8>), grid, dim3(64), 0, c->stream, c->d_efpd, c->d_efbits, c->d_out, 0);
+        break;
+    case ACX_EF_SW_H16_16:
+        hipLaunchKernelGGL((acx::sw_bits_h16_kernel<16>), grid, dim3(64), 0, c->stream, c->d_efpd, c->d_efbits, c->d_out, 0);
+        break;
+    case ACX_EF_SW_8:
+        hipLaunchKernelGGL((acx::sw_kernel<8>), grid, dim3(64), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_out, src);
+        break;
+    case ACX_EF_SW_16:
+        hipLaunchKernelGGL((acx::sw_kernel<16>), grid, dim3(64), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_out, src);
+        break;
+    default:
+        hipLaunchKernelGGL(acx::sw_long_kernel, grid, dim3(64), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_out, src);
+    }
+}
+
+// A batch on the device: its arenas and descriptors, then every launch of it, the kernels as the plan names them (`kn`:
+// ef_batch_kernels, ef_plan.hpp).  ext_matrix (test entries): the caller's extM x extN matrix is "feature 0" of the one pair.
+static int launch_ef_batch(acx_ctx *c, const EfHostBatch &hb, const acx::EfBatchKernels &kn, const acx::EfMode &mode, const acx_ef_params &p,
+                           const float *ext_matrix, int extM, int extN)
+{
+    const int B = (int)hb.pd.size(), maxM = hb.a.maxM, maxN = hb.a.maxN;
+    const int64_t cells = hb.a.cells;
+    int rc;
+    if ((rc = ensure(c, c->d_scratch, (size_t)hb.a.used)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_thr, (size_t)hb.a.used_s)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efbits, (size_t)hb.a.used_b)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efpd, (size_t)B)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_out, (size_t)4 * B)) != ACX_OK) return rc;
+    ACX_HIP(c, hipMemcpyAsync(c->d_efpd, hb.pd.data(), sizeof(acx::EfPair) * B, hipMemcpyHostToDevice, c->stream));
+    if (ext_matrix) {
+        ACX_HIP(c, hipMemcpy2DAsync(c->d_scratch, sizeof(float) * hb.pd[0].pitchC, ext_matrix, sizeof(float) * extN,
+                                    sizeof(float) * extN, extM, hipMemcpyHostToDevice, c->stream));
+    } else {
+        hipLaunchKernelGGL(acx::ef_oti_kernel, dim3((B + 255) / 256), dim3(256), 0, c->stream, c->d_efpd, B, c->d_efmed);
+        const int tiles_x = (maxN + acx::EF_TILE - 1) / acx::EF_TILE, tiles_y = (maxM + acx::EF_TILE - 1) / acx::EF_TILE;
+        ProfScope ps(c, KS_EFGEMM, cells);
+        if ((rc = launch_ef_gemms(c, hb.seg, B, tiles_x, tiles_y)) != ACX_OK) return rc;
+    }
+    const int nfeat = ext_matrix ? 1 : 3;
+    const int rows_g = (std::max(maxM, maxN) + 3) / 4;
+    {
+        ProfScope ps(c, KS_EFSTAT, cells);
+        if (kn.row == ACX_EF_ROW_TWO)
+            hipLaunchKernelGGL(acx::ef_rowstat2_kernel, dim3((maxM + 7) / 8, B, nfeat), dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr,
+                               c->d_efbits, p.K);
+        else
+            launch_ef_rowstat(c, kn.row, dim3(rows_g, B, nfeat), 0, p.K);
+        switch (kn.col) {
+        case ACX_EF_COL_ROWPASS:
+            launch_ef_rowstat(c, kn.row1, dim3(rows_g, B, 3), 1, p.K);
+            break;
+        case ACX_EF_COL_10:
+            hipLaunchKernelGGL((acx::ef_colstat_kernel<10>), dim3((maxN + 63) / 64, B, 3), dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, p.K);
+            break;
+        case ACX_EF_COL_16:
+            hipLaunchKernelGGL((acx::ef_colstat_kernel<acx::EF_COLSTAT_MAXK>), dim3((maxN + 63) / 64, B, 3), dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, p.K);
+            break;
+        default:          // (a caller's matrix: threshold = kbin smallest per row, no columns)
+            break;
+        }
+    }
+    if (mode.bits_path) {
+        if (kn.fuse != ACX_EF_FUSE_NONE) {
+            ProfScope ps(c, KS_EFFUSE, cells);
+            if (kn.fuse == ACX_EF_FUSE_WIDE) launch_ef_fusesel<4>(c, dim3((maxM + 3) / 4, B, 1), p.K, mode.keep_f ? 1 : 0);
+            else launch_ef_fusesel<2>(c, dim3((maxM + 3) / 4, B, 1), p.K, mode.keep_f ? 1 : 0);
+        }
+        ProfScope ps(c, KS_EFSW, cells);
+        launch_ef_sw(c, kn.sw, dim3(B, ext_matrix ? 1 : 4), 0);
+    } else {
+        {
+            ProfScope ps(c, KS_EFSW, cells);
+            launch_ef_sw(c, kn.sw, dim3(B, nfeat), 0);
+        }
+        if (kn.fuse == ACX_EF_FUSE_FLOAT) {
+            {
+                ProfScope ps(c, KS_EFFUSE, cells);
+                hipLaunchKernelGGL(acx::ef_fuse_kernel, dim3(maxM, B), dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->ef_fuse == ACX_EF_FUSE_EXACT ? 1 : 0);
+            }
+            {
+                ProfScope ps(c, KS_EFSTAT, 0);
+                launch_ef_rowstat(c, kn.row1, dim3(rows_g, B, 1), 2, p.K);
+            }
+            {
+                ProfScope ps(c, KS_EFSW, 0);
+                launch_ef_sw(c, kn.sw, dim3(B, 1), 3);
+            }
+        }
+    }
+    ACX_LAUNCHES_OK(c);
+    return ACX_OK;
+}
+
+// The four scores of the batch's pairs, queued behind its kernels: to out[4 k ..] on the host, or (`dd`, grid runs) to
+// dd->base[dd->idx[k] .. + 4) on the DEVICE.
+static int copy_ef_scores(acx_ctx *c, const EfHostBatch &hb, float *out, const DevDst *dd)
+{
+    const int B = (int)hb.pd.size();
+    if (!dd) {
+        ACX_HIP(c, hipMemcpyAsync(out + 4 * hb.k_begin, c->d_out, sizeof(float) * 4 * B, hipMemcpyDeviceToHost, c->stream));
+        return ACX_OK;
+    }
+    const int rc = stage_idx(c, dd->idx + hb.k_begin, B);
+    if (rc != ACX_OK) return rc;
+    hipLaunchKernelGGL(scatter_scores_kernel, dim3((B + 255) / 256), dim3(256), 0, c->stream, c->d_out, c->d_idx, dd->base, B, 4);
+    ACX_HIP(c, hipGetLastError());
+    return ACX_OK;
+}
+
+// The debug entries: what the (one) batch left behind for its pair `which`, on an idle stream.  `ext`: a caller's matrix has one
+// slot and no column means; a pair of the pool three features and the fused slot.
+static int ef_debug_readback(acx_ctx *c, const EfDebug &dbg, int64_t which, bool ext)
+{
+    acx::EfPair d;
+    ACX_HIP(c, hipMemcpy(&d, c->d_efpd + which, sizeof(acx::EfPair), hipMemcpyDeviceToHost));
+    if (dbg.oti) *dbg.oti = d.oti;
+    for (int sft = 0; sft < 3 && dbg.csm; ++sft)
+        ACX_HIP(c, hipMemcpy2D(dbg.csm + (size_t)sft * d.M * d.N, sizeof(float) * d.N,
+                               c->d_scratch + d.offC + (int64_t)sft * d.M * d.pitchC, sizeof(float) * d.pitchC,
+                               sizeof(float) * d.N, d.M, hipMemcpyDeviceToHost));
+    if (dbg.fused)
+        ACX_HIP(c, hipMemcpy2D(dbg.fused, sizeof(float) * d.N,
+                               c->d_scratch + d.offC + (int64_t)3 * d.M * d.pitchC + (int64_t)3 * d.ctN * d.pitchT,
+                               sizeof(float) * d.pitchC, sizeof(float) * d.N, d.M, hipMemcpyDeviceToHost));
+    const EfStats *st = dbg.stats;
+    if (!st) return ACX_OK;
+    // the vectors of d_thr (layout: ef_kernels.hpp, EfPair::offS) and the words of d_efbits as the kernels wrote them
+    const int nf = ext ? 1 : 3, nslots = ext ? 1 : 4;
+    const int64_t stride = acx::ef_s_stride(d);
+    if (st->bits)
+        ACX_HIP(c, hipMemcpy(st->bits, c->d_efbits + d.offB, sizeof(uint32_t) * (size_t)nslots * d.M * (d.pitchC / 32), hipMemcpyDeviceToHost));
+    for (int sl = 0; sl < nslots; ++sl) {
+        const float *S = c->d_thr + d.offS + sl * stride;
+        if (st->t) ACX_HIP(c, hipMemcpy(st->t + (size_t)sl * d.M, S, sizeof(float) * d.M, hipMemcpyDeviceToHost));
+        if (st->jcut) ACX_HIP(c, hipMemcpy(st->jcut + (size_t)sl * d.M, S + acx::ef_jcut_off(d, sl), sizeof(int32_t) * d.M, hipMemcpyDeviceToHost));
+        if (sl >= nf) continue;
+        if (st->r) ACX_HIP(c, hipMemcpy(st->r + (size_t)sl * d.M, S + d.pitchT, sizeof(float) * d.M, hipMemcpyDeviceToHost));
+        if (st->c && !ext) ACX_HIP(c, hipMemcpy(st->c + (size_t)sl * d.N, S + 2 * d.pitchT, sizeof(float) * d.N, hipMemcpyDeviceToHost));
+    }
+    return ACX_OK;
+}
+
+// The scratch limit of a run in floats: the context's, else ACX_SCRATCH_GB, else 36 GB (a whole 128 x 128 grid tile of 400-block
+// tracks -- 16 384 pairs, three float matrices each since the transposed and the fused matrices are gone -- in one batch).  Much
+// larger batches buy nothing (measured with the 7-matrix layout: 98 k pairs/s at 24 GB, 101 k at 115 GB, 94 k at 8 GB) and the
+// first hipMalloc of a 100 GB arena costs 3.4 s
+static int64_t ef_scratch_limit(const acx_ctx *c)
+{
+    if (c->scratch_limit > 0) return c->scratch_limit;
+    const char *env = getenv("ACX_SCRATCH_GB");
+    if (env && atof(env) > 0) return (int64_t)(atof(env) * (double)(1ull << 30));
+    return std::min<int64_t>((int64_t)(0.40 * (double)c->total_mem), (int64_t)36 << 30);
+}
+
+// The pool is up and the WHOLE list is good (ef_check_pairs, ef_plan.hpp), before the first launch: a bad pair behind the first
+// batch fails the call before any batch has run, as the reference fails a chunk (algorithm_template.py:174-177).  No pool: that,
+// whatever the indices are.  `upto` (or nullptr): the pair the list is good up to, where a caller's own per-pair rules come
+// before a track without blocks -- then ACX_ERR_SHORT is the caller's to report (ef_short_pair) once its rules have passed them.
+static int ef_short_pair(acx_ctx *c, int64_t k) { return fail(c, ACX_ERR_SHORT, "earlyfusion: track without blocks (pair " + std::to_string(k) + ")"); }
+
+// (the texts of ef_check_pairs' answers; c == nullptr: for acx_last_error(NULL))
+static int ef_check_text(acx_ctx *c, const acx::EfCheck &ck)
+{
+    if (ck.code == ACX_ERR_INVALID) return fail(c, ACX_ERR_INVALID, "earlyfusion: track index out of range in pair " + std::to_string(ck.k));
+    return ck.code == ACX_ERR_SHORT ? ef_short_pair(c, ck.k) : ACX_OK;
+}
+
+static int check_ef_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, int64_t *upto = nullptr)
+{
+    if (!c->d_ef[0] || c->ef_open) return fail(c, ACX_ERR_STATE, "earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)");
+    const acx::EfCheck ck = acx::ef_check_pairs(acx::EfLengths{c->h_efoff.data(), c->ef_ntracks}, pairs, K);
+    if (upto && ck.code != ACX_ERR_INVALID) { *upto = ck.k; return ACX_OK; }
+    return ef_check_text(c, ck);
+}
+
+// `dd` (grid runs): the four scores of pair k go to dd->base[dd->idx[k] .. + 4) on the DEVICE instead of out[4 k ..].  `pd_out`
+// (the cross-diffusion fusion): the caller goes on with the matrices this call leaves in d_scratch, where the descriptors of its
+// ONE batch say.  (Behind run_ef's guard, below.)
 static int run_ef_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params &p, float *out, const EfDebug *dbg,
                        const float *ext_matrix, int extM, int extN, const DevDst *dd, const EfAlign *aln, std::vector<acx::EfPair> *pd_out)
 {
-    using acx::EfPair;
+    int rc;
     if (!ext_matrix && (!c->d_ef[0] || c->ef_open)) return fail(c, ACX_ERR_STATE, "earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)");
     if (!(p.kappa >= 0.0)) return fail(c, ACX_ERR_INVALID, "earlyfusion: kappa must be >= 0");
     if (p.K < 1) return fail(c, ACX_ERR_INVALID, "earlyfusion: K must be >= 1");
     ACX_HIP(c, hipSetDevice(c->device));
-    // the WHOLE pair list is checked before the first launch (indices, tracks without blocks): a bad pair behind the
-    // first batch fails the call before any batch has run, as the reference fails a chunk (algorithm_template.py:174-177)
-    if (!ext_matrix)
-        for (int64_t k = 0; k < K; ++k) {
-            const int32_t q = pairs[2 * k], r = pairs[2 * k + 1];
-            if (q < 0 || r < 0 || q >= c->ef_ntracks || r >= c->ef_ntracks)
-                return fail(c, ACX_ERR_INVALID, "earlyfusion: track index out of range in pair " + std::to_string(k));
-            if (c->h_efoff[q + 1] - c->h_efoff[q] < 1 || c->h_efoff[r + 1] - c->h_efoff[r] < 1)
-                return fail(c, ACX_ERR_SHORT, "earlyfusion: track without blocks (pair " + std::to_string(k) + ")");
-        }
-    const double t_call = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    int64_t limit = c->scratch_limit;
-    if (limit <= 0) {
-        const char *env = getenv("ACX_SCRATCH_GB");
-        if (env && atof(env) > 0) limit = (int64_t)(atof(env) * (double)(1ull << 30));
-        // default: 36 GB (a whole 128 x 128 grid tile of 400-block tracks -- 16 384 pairs, three float matrices each since
-        // the transposed and the fused matrices are gone -- in one batch).  Much larger batches buy nothing (measured with
-        // the 7-matrix layout: 98 k pairs/s at 24 GB, 101 k at 115 GB, 94 k at 8 GB) and the first hipMalloc of a 100 GB arena costs 3.4 s
-        else limit = std::min<int64_t>((int64_t)(0.40 * (double)c->total_mem), (int64_t)36 << 30);
-    }
-    const int64_t limit_floats = limit / 4;
-    // the column statistics (mean of the K smallest of every column) come from C itself up to K = 16 (ef_colstat_kernel);
-    // larger neighbourhoods keep the transposed matrices and take the row-selection kernels
-    const bool keep_ct = !ext_matrix && p.K > acx::EF_COLSTAT_MAXK;
-    // tracks of up to EF_MAXNB blocks (rows that fit a wave's registers): the selection kernels leave the BINARISED rows
-    // behind, the fused matrix is made and binarised in registers (never stored, unless the debug entry asks for it) and
-    // the Smith-Waterman kernel walks bits; longer tracks keep the streaming kernels and the float matrices
-    bool bits_path = true;
-    if (ext_matrix) bits_path = extM <= acx::EF_MAXNB && extN <= acx::EF_MAXNB;
-    else
-        for (int64_t k = 0; k < K && bits_path; ++k) {
-            const int32_t q = pairs[2 * k], r = pairs[2 * k + 1];
-            if (q < 0 || r < 0 || q >= c->ef_ntracks || r >= c->ef_ntracks) break;      // (reported below)
-            if (c->h_efoff[q + 1] - c->h_efoff[q] > acx::EF_MAXNB || c->h_efoff[r + 1] - c->h_efoff[r] > acx::EF_MAXNB) bits_path = false;
-        }
-    const bool keep_f = !bits_path || (dbg && dbg->fused);
+    if (!ext_matrix && (rc = check_ef_pairs(c, pairs, K)) != ACX_OK) return rc;
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_call = now();
+    const int64_t limit = ef_scratch_limit(c), limit_floats = limit / 4;
+    const bool want_fused = dbg && dbg->fused;
+    const acx::EfLengths len{c->h_efoff.data(), c->ef_ntracks};
+    const acx::EfMode mode = ext_matrix ? acx::ef_mode_matrix(extM, extN, want_fused) : acx::ef_mode(len, pairs, K, p.K, want_fused);
+    EfRun run{len, pairs, K, p, mode, limit_floats, !ext_matrix && c->ef_gemm != ACX_EF_GEMM_F32 && c->ef_gemm != ACX_EF_GEMM_BF16X3_PAIRWISE};
     if (aln && (ext_matrix || dd || !out))          // (no export gets here: acx_ef_align passes the pool's pairs and a host buffer)
         return fail(c, ACX_ERR_STATE, "ef_align: the alignment option takes pairs of the pool and scores on the host");
-    if (aln && !bits_path && !aln->any_length)
+    if (aln && !mode.bits_path && !aln->any_length)
         return fail(c, ACX_ERR_UNSUPPORTED, "ef_align: alignment needs the bit path: at most 1024 blocks");
-    if (dbg && dbg->stats && dbg->stats->bits && !bits_path)
+    if (dbg && dbg->stats && dbg->stats->bits && !mode.bits_path)
         return fail(c, ACX_ERR_INVALID, "ef debug: a track of more than 1024 blocks takes the float path, which leaves no bitmaps (pass a null bitmap pointer)");
-    if (!ext_matrix)                              // (the last of the up-front checks: a pair that cannot fit the scratch limit on its own)
-        for (int64_t k = 0; k < K; ++k) {
-            const int64_t M = c->h_efoff[pairs[2 * k] + 1] - c->h_efoff[pairs[2 * k]], N = c->h_efoff[pairs[2 * k + 1] + 1] - c->h_efoff[pairs[2 * k + 1]];
-            if ((keep_f ? 4 : 3) * M * round_up((int)N, 64) + (keep_ct ? 3 * N * round_up((int)M, 64) : 0) > limit_floats)
-                return fail(c, ACX_ERR_NOMEM, "earlyfusion: pair " + std::to_string(k) + " does not fit the scratch limit");
-        }
-    // Batches of EQUAL size: a list that needs 1.3 limits runs as 0.65 + 0.65, not 1.0 + 0.3 (the last kernels of a batch
-    // run on a draining device; a small trailing batch pays that for little work -- a 128 x 128 grid tile of 400-block
-    // tracks is 16 384 pairs = 31 GB of matrices)
-    int64_t batch_floats = limit_floats;
-    if (!ext_matrix && K > 1) {
-        double total = 0.0;
-        for (int64_t k = 0; k < K; ++k) {
-            const int32_t q = pairs[2 * k], r = pairs[2 * k + 1];
-            if (q < 0 || r < 0 || q >= c->ef_ntracks || r >= c->ef_ntracks) { total = 0.0; break; }      // (reported below)
-            const double M = (double)(c->h_efoff[q + 1] - c->h_efoff[q]), N = (double)(c->h_efoff[r + 1] - c->h_efoff[r]);
-            total += (keep_f ? 4.0 : 3.0) * M * (double)round_up((int)N, 64) + (keep_ct ? 3.0 * N * (double)round_up((int)M, 64) : 0.0);
-        }
-        if (total > (double)limit_floats) {
-            const double nb = std::ceil(total / (double)limit_floats);
-            batch_floats = std::min<int64_t>(limit_floats, (int64_t)(total / nb * 1.02) + ((int64_t)1 << 22));
-        }
-    }
-    // One batch on the host: its pair descriptors and -- for the rectangle GEMM -- the dense rectangles its pairs are laid out in.
-    // Built for batch b + 1 WHILE the device works on batch b (two of these; the copies to the device are staged before they
-    // return): ~1 ms per 16 384 pairs that the device used to wait for between batches.
-    struct HostBatch {
-        std::vector<EfPair> pd;
-        SegBatch seg;
-        int64_t k_begin = 0, k_end = 0, used = 0, used_s = 0, used_b = 0, cells = 0;
-        int maxM = 0, maxN = 0;
-    };
-    HostBatch hbs[2];
-    std::vector<int32_t> qslot, rslot;
-    int rc;
-    const bool rect_gemm = !ext_matrix && c->ef_gemm != ACX_EF_GEMM_F32 && c->ef_gemm != ACX_EF_GEMM_BF16X3_PAIRWISE;
     // development aid (ACX_EF_HOST_TIMING=1): where the HOST's time of a call goes -- descriptors, rectangles, enqueue, waiting for the device
     static const bool host_timing = [] { const char *e = getenv("ACX_EF_HOST_TIMING"); return e && e[0] == '1'; }();
     double ht[5] = {0, 0, 0, 0, 0};
     int nbatches = 0;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    ht[4] = now() - t_call;
-    auto prepare = [&](HostBatch &hb, int64_t k_from) -> int {
-        const double t_a = now();
-        std::vector<EfPair> &pd = hb.pd;
-        pd.clear();
-        int64_t used = 0, used_s = 0, used_b = 0, cells = 0;
-        int maxM = 0, maxN = 0;
-        int64_t k = k_from;
-        for (; k < K && pd.size() < 65535; ++k) {
-            EfPair d;
-            if (ext_matrix) {
-                d = ef_one_pair(extM, extN);
-            } else {
-                d.q = pairs[2 * k]; d.r = pairs[2 * k + 1];
-                if (d.q < 0 || d.r < 0 || d.q >= c->ef_ntracks || d.r >= c->ef_ntracks)
-                    return fail(c, ACX_ERR_INVALID, "earlyfusion: track index out of range in pair " + std::to_string(k));
-                d.M = (int)(c->h_efoff[d.q + 1] - c->h_efoff[d.q]);
-                d.N = (int)(c->h_efoff[d.r + 1] - c->h_efoff[d.r]);
-            }
-            if (d.M < 1 || d.N < 1) return fail(c, ACX_ERR_SHORT, "earlyfusion: track without blocks (pair " + std::to_string(k) + ")");
-            d.oti = 0;
-            d.pitchC = round_up(d.N, 64);
-            d.pitchT = round_up(d.M, 64);
-            // csm_to_binary (cross_recurrence.py:149-154): kappa == 0 -> all ones; kappa < 1 ->
-            // int(round(kappa * ncols)) (numpy: half to even, in f64); else kappa neighbours
-            if (p.kappa == 0.0) d.kbin = d.N;
-            else if (p.kappa < 1.0) d.kbin = (int)std::nearbyint(p.kappa * (double)d.N);
-            else d.kbin = (int)p.kappa;
-            d.ctN = keep_ct ? d.N : 0;
-            d.pad = 0;
-            const int64_t need = (int64_t)(keep_f ? 4 : 3) * d.M * d.pitchC + (int64_t)3 * d.ctN * d.pitchT;
-            if (need > limit_floats) return fail(c, ACX_ERR_NOMEM, "earlyfusion: one pair does not fit the scratch limit");
-            if (used + need > batch_floats && !pd.empty()) break;
-            d.offC = used;
-            d.offS = used_s;
-            d.offB = used_b;
-            used_b += (int64_t)4 * d.M * (d.pitchC / 32);
-            used += need;
-            used_s += acx::ef_s_total(d);
-            maxM = std::max(maxM, d.M);
-            maxN = std::max(maxN, d.N);
-            cells += (int64_t)d.M * d.N;
-            pd.push_back(d);
-        }
-        hb.k_begin = k_from; hb.k_end = k;
-        hb.used = used; hb.used_s = used_s; hb.used_b = used_b; hb.cells = cells; hb.maxM = maxM; hb.maxN = maxN;
-        const double t_r = now();
-        ht[0] += t_r - t_a;
-        // the pairs of the batch laid out as dense rectangles (ef_gemm_rect_bf16x3_kernel)
-        if (rect_gemm) ef_build_rects(pd, c->h_efoff, c->ef_ntracks, hb.seg, qslot, rslot);
-        ht[1] += now() - t_r;
-        return ACX_OK;
-    };
-    if ((rc = prepare(hbs[0], 0)) != ACX_OK) return rc;
-    if (dbg && !ext_matrix && hbs[0].k_end < K)          // the debug entries show one batch: refused before the first launch
-        return fail(c, ACX_ERR_UNSUPPORTED, "ef debug: the list does not fit one batch");
-    // pd_out (the cross-diffusion fusion): the caller goes on with the matrices this call leaves in d_scratch, where the
-    // descriptors of its ONE batch say
-    if (pd_out && hbs[0].k_end < K) return fail(c, ACX_ERR_NOMEM, "earlyfusion: the pair and its two self pairs do not fit the scratch limit");
+    EfHostBatch hbs[2];
+    if (ext_matrix) {
+        // test entries: the caller's matrix as the one pair of the one batch
+        EfHostBatch &hb = hbs[0];
+        hb.pd.assign(1, acx::ef_pair_desc(0, 0, extM, extN, p.kappa, false));
+        if (acx::ef_pair_floats(hb.pd[0], mode.keep_f) > limit_floats) return fail(c, ACX_ERR_NOMEM, "earlyfusion: one pair does not fit the scratch limit");
+        acx::ef_arena_add(hb.a, hb.pd[0], mode.keep_f);
+        hb.k_end = K;
+        ht[4] = now() - t_call;
+    } else {
+        // (the last of the up-front checks: a pair that cannot fit the scratch limit on its own)
+        const acx::EfSizes sz = acx::ef_batch_floats(run.len, pairs, K, p.kappa, mode, limit_floats);
+        if (sz.too_big >= 0) return fail(c, ACX_ERR_NOMEM, "earlyfusion: pair " + std::to_string(sz.too_big) + " does not fit the scratch limit");
+        run.batch_floats = sz.batch_floats;
+        ht[4] = now() - t_call;
+        prepare_ef_batch(c, run, 0, hbs[0], ht);
+        if (dbg && hbs[0].k_end < K)          // the debug entries show one batch: refused before the first launch
+            return fail(c, ACX_ERR_UNSUPPORTED, "ef debug: the list does not fit one batch");
+        if (pd_out && hbs[0].k_end < K) return fail(c, ACX_ERR_NOMEM, "earlyfusion: the pair and its two self pairs do not fit the scratch limit");
+    }
     for (int bi = 0; hbs[bi & 1].k_begin < K; ++bi) {
-        HostBatch &hb = hbs[bi & 1];
-        std::vector<EfPair> &pd = hb.pd;
-        SegBatch &seg = hb.seg;
-        const int64_t k0 = hb.k_begin, k = hb.k_end, used = hb.used, used_s = hb.used_s, used_b = hb.used_b, cells = hb.cells;
-        const int maxM = hb.maxM, maxN = hb.maxN;
+        EfHostBatch &hb = hbs[bi & 1];
         ++nbatches;
-        const int B = (int)pd.size();
         const double t_b = now();
-        if ((rc = ensure(c, c->d_scratch, (size_t)used)) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_thr, (size_t)used_s)) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_efbits, (size_t)used_b)) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_efpd, (size_t)B)) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_out, (size_t)4 * B)) != ACX_OK) return rc;
-        ACX_HIP(c, hipMemcpyAsync(c->d_efpd, pd.data(), sizeof(EfPair) * B, hipMemcpyHostToDevice, c->stream));
-        const int rows_g = (std::max(maxM, maxN) + 3) / 4;
-        if (ext_matrix) {
-            // test entry: the caller's matrix is "feature 0", threshold = kbin smallest per row
-            ACX_HIP(c, hipMemcpy2DAsync(c->d_scratch, sizeof(float) * pd[0].pitchC, ext_matrix, sizeof(float) * extN,
-                                        sizeof(float) * extN, extM, hipMemcpyHostToDevice, c->stream));
-        } else {
-            hipLaunchKernelGGL(acx::ef_oti_kernel, dim3((B + 255) / 256), dim3(256), 0, c->stream, c->d_efpd, B, c->d_efmed);
-            {
-                const int tiles_x = (maxN + acx::EF_TILE - 1) / acx::EF_TILE, tiles_y = (maxM + acx::EF_TILE - 1) / acx::EF_TILE;
-                ProfScope ps(c, KS_EFGEMM, cells);
-                if ((rc = launch_ef_gemms(c, seg, B, tiles_x, tiles_y)) != ACX_OK) return rc;
-            }
-        }
-        const int nfeat = ext_matrix ? 1 : 3;
-        // rows of more than 512 cells take the wide variants (16 values / columns per lane)
-        // more than 1024: a row no longer fits a wave's registers -- the streaming variants (any length)
-        const bool wide_rows = std::max(maxM, maxN) > 512, wide_cols = maxN > 512;
-        const bool long_rows = std::max(maxM, maxN) > acx::EF_MAXNB, long_cols = maxN > acx::EF_MAXNB;
-#define ACX_ROWSTAT(grid_, mode_) do { if (long_rows) hipLaunchKernelGGL(acx::ef_rowstat_long_kernel, grid_, dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, mode_, p.K); \
-                                       else if (wide_rows) hipLaunchKernelGGL((acx::ef_rowstat_kernel<4, false>), grid_, dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_efbits, mode_, p.K, 0); \
-                                       else hipLaunchKernelGGL((acx::ef_rowstat_kernel<2, false>), grid_, dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_efbits, mode_, p.K, 0); } while (0)
-#define ACX_FUSESEL_K(NQ_, EX_, grid_) hipLaunchKernelGGL((acx::ef_rowstat_kernel<NQ_, true, EX_>), grid_, dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_efbits, 3, p.K, keep_f ? 1 : 0)
-#define ACX_FUSESEL(grid_) do { const bool ex_ = c->ef_fuse == ACX_EF_FUSE_EXACT; \
-                                if (wide_rows) { if (ex_) ACX_FUSESEL_K(4, true, grid_); else ACX_FUSESEL_K(4, false, grid_); } \
-                                else { if (ex_) ACX_FUSESEL_K(2, true, grid_); else ACX_FUSESEL_K(2, false, grid_); } } while (0)
-#define ACX_SW(grid_, src_) do { if (long_cols) hipLaunchKernelGGL(acx::sw_long_kernel, grid_, dim3(64), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_out, src_); \
-                                 else if (wide_cols) hipLaunchKernelGGL((acx::sw_kernel<16>), grid_, dim3(64), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_out, src_); \
-                                 else hipLaunchKernelGGL((acx::sw_kernel<8>), grid_, dim3(64), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->d_out, src_); } while (0)
-        {
-            ProfScope ps(c, KS_EFSTAT, cells);
-            // rows of <= 512 cells: two rows per wave (ef_rowstat2_kernels.hpp; ACX_EF_ROWSTAT2=0 keeps the one-row kernel)
-            static const bool two_rows = [] { const char *e = getenv("ACX_EF_ROWSTAT2"); return !(e && e[0] == '0'); }();
-            if (two_rows && !long_rows && maxN <= 512)
-                hipLaunchKernelGGL(acx::ef_rowstat2_kernel, dim3((maxM + 7) / 8, B, nfeat), dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr,
-                                   c->d_efbits, p.K);
-            else
-                ACX_ROWSTAT(dim3(rows_g, B, nfeat), 0);
-            if (!ext_matrix) {
-                if (keep_ct) ACX_ROWSTAT(dim3(rows_g, B, 3), 1);
-                else if (p.K <= 10) hipLaunchKernelGGL((acx::ef_colstat_kernel<10>), dim3((maxN + 63) / 64, B, 3), dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, p.K);
-                else hipLaunchKernelGGL((acx::ef_colstat_kernel<acx::EF_COLSTAT_MAXK>), dim3((maxN + 63) / 64, B, 3), dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, p.K);
-            }
-        }
-        if (bits_path) {
-            if (!ext_matrix) {
-                ProfScope ps(c, KS_EFFUSE, cells);
-                ACX_FUSESEL(dim3((maxM + 3) / 4, B, 1));             // the fused matrix: made, thresholded and binarised row by row
-            }
-            ProfScope ps(c, KS_EFSW, cells);
-            // (packed 16-bit integers: rows of <= 1024 cells keep every score below 10 240 tenths)
-            if (wide_cols) hipLaunchKernelGGL((acx::sw_bits_h16_kernel<16>), dim3(B, ext_matrix ? 1 : 4), dim3(64), 0, c->stream, c->d_efpd, c->d_efbits, c->d_out, 0);
-            else hipLaunchKernelGGL((acx::sw_bits_h16_kernel<8>), dim3(B, ext_matrix ? 1 : 4), dim3(64), 0, c->stream, c->d_efpd, c->d_efbits, c->d_out, 0);
-        } else {
-            {
-                ProfScope ps(c, KS_EFSW, cells);
-                ACX_SW(dim3(B, nfeat), 0);
-            }
-            if (!ext_matrix) {
-                {
-                    ProfScope ps(c, KS_EFFUSE, cells);
-                    hipLaunchKernelGGL(acx::ef_fuse_kernel, dim3(maxM, B), dim3(256), 0, c->stream, c->d_efpd, c->d_scratch, c->d_thr, c->ef_fuse == ACX_EF_FUSE_EXACT ? 1 : 0);
-                }
-                {
-                    ProfScope ps(c, KS_EFSTAT, 0);
-                    ACX_ROWSTAT(dim3(rows_g, B, 1), 2);
-                }
-                {
-                    ProfScope ps(c, KS_EFSW, 0);
-                    ACX_SW(dim3(B, 1), 3);
-                }
-            }
-        }
-        ACX_LAUNCHES_OK(c);
-        if (dd) {
-            if ((rc = stage_idx(c, dd->idx + k0, B)) != ACX_OK) return rc;
-            hipLaunchKernelGGL(scatter_scores_kernel, dim3((B + 255) / 256), dim3(256), 0, c->stream, c->d_out, c->d_idx, dd->base, B, 4);
-            ACX_HIP(c, hipGetLastError());
-        } else {
-            ACX_HIP(c, hipMemcpyAsync(out + 4 * k0, c->d_out, sizeof(float) * 4 * B, hipMemcpyDeviceToHost, c->stream));
-        }
+        const acx::EfBatchKernels kn = acx::ef_batch_kernels(hb.a.maxM, hb.a.maxN, p.K, mode, ext_matrix != nullptr);
+        if ((rc = launch_ef_batch(c, hb, kn, mode, p, ext_matrix, extM, extN)) != ACX_OK) return rc;
+        if ((rc = copy_ef_scores(c, hb, out, dd)) != ACX_OK) return rc;
         // acx_ef_align / acx_ef_align_long: the records (and paths) of this batch, while d_efbits (the float path: d_scratch and d_thr)
         // still holds it
-        if (aln && (rc = run_ef_align_batch(c, pd, k0, limit / 2, *aln, out + 4 * k0, !bits_path)) != ACX_OK) return rc;
+        if (aln && (rc = run_ef_align_batch(c, hb.pd, hb.k_begin, limit / 2, *aln, out + 4 * hb.k_begin, !mode.bits_path)) != ACX_OK) return rc;
         const double t_s = now();
         ht[2] += t_s - t_b;
         // the next batch's descriptors and rectangles, while the device works on this one
-        HostBatch &nx = hbs[(bi & 1) ^ 1];
+        EfHostBatch &nx = hbs[(bi & 1) ^ 1];
         nx.k_begin = K;
-        int rc_next = ACX_OK;
-        if (k < K && !ext_matrix) rc_next = prepare(nx, k);
+        if (hb.k_end < K) prepare_ef_batch(c, run, hb.k_end, nx, ht);
         const double t_w = now();
         ACX_HIP(c, hipStreamSynchronize(c->stream));
         ht[3] += now() - t_w;
         drain_profile(c);
-        if (rc_next != ACX_OK) return rc_next;
-        if (pd_out) *pd_out = pd;
-        if (dbg && B >= 1) {
-            EfPair d;
-            ACX_HIP(c, hipMemcpy(&d, c->d_efpd + (dbg->which - k0), sizeof(EfPair), hipMemcpyDeviceToHost));
-            if (dbg->oti) *dbg->oti = d.oti;
-            for (int sft = 0; sft < 3 && dbg->csm; ++sft)
-                ACX_HIP(c, hipMemcpy2D(dbg->csm + (size_t)sft * d.M * d.N, sizeof(float) * d.N,
-                                       c->d_scratch + d.offC + (int64_t)sft * d.M * d.pitchC, sizeof(float) * d.pitchC,
-                                       sizeof(float) * d.N, d.M, hipMemcpyDeviceToHost));
-            if (dbg->fused)
-                ACX_HIP(c, hipMemcpy2D(dbg->fused, sizeof(float) * d.N,
-                                       c->d_scratch + d.offC + (int64_t)3 * d.M * d.pitchC + (int64_t)3 * d.ctN * d.pitchT,
-                                       sizeof(float) * d.pitchC, sizeof(float) * d.N, d.M, hipMemcpyDeviceToHost));
-            if (const EfStats *st = dbg->stats) {
-                // the vectors of d_thr (layout: ef_kernels.hpp, EfPair::offS) and the words of d_efbits as the kernels wrote them;
-                // the caller's matrix has one slot, a pair three features and the fused slot
-                const int nf = ext_matrix ? 1 : 3, nslots = ext_matrix ? 1 : 4;
-                const int64_t stride = acx::ef_s_stride(d);
-                if (st->bits)
-                    ACX_HIP(c, hipMemcpy(st->bits, c->d_efbits + d.offB, sizeof(uint32_t) * (size_t)nslots * d.M * (d.pitchC / 32), hipMemcpyDeviceToHost));
-                for (int sl = 0; sl < nslots; ++sl) {
-                    const float *S = c->d_thr + d.offS + sl * stride;
-                    if (st->t) ACX_HIP(c, hipMemcpy(st->t + (size_t)sl * d.M, S, sizeof(float) * d.M, hipMemcpyDeviceToHost));
-                    if (st->jcut) ACX_HIP(c, hipMemcpy(st->jcut + (size_t)sl * d.M, S + acx::ef_jcut_off(d, sl), sizeof(int32_t) * d.M, hipMemcpyDeviceToHost));
-                    if (sl >= nf) continue;
-                    if (st->r) ACX_HIP(c, hipMemcpy(st->r + (size_t)sl * d.M, S + d.pitchT, sizeof(float) * d.M, hipMemcpyDeviceToHost));
-                    if (st->c && !ext_matrix) ACX_HIP(c, hipMemcpy(st->c + (size_t)sl * d.N, S + 2 * d.pitchT, sizeof(float) * d.N, hipMemcpyDeviceToHost));
-                }
-            }
-        }
-        if (ext_matrix) break;
+        if (pd_out) *pd_out = hb.pd;
+        if (dbg && (rc = ef_debug_readback(c, *dbg, dbg->which - hb.k_begin, ext_matrix != nullptr)) != ACX_OK) return rc;
     }
-#undef ACX_ROWSTAT
-#undef ACX_FUSESEL
-#undef ACX_FUSESEL_K
-#undef ACX_SW
     if (host_timing)
         fprintf(stderr, "[acx ef host] %lld pairs in %d batches, %.1f ms: preamble %.1f, descriptors %.1f, rectangles %.1f, enqueue %.1f, waiting for the device %.1f\n",
                 (long long)K, nbatches, 1e3 * (now() - t_call), 1e3 * ht[4], 1e3 * ht[0], 1e3 * ht[1], 1e3 * ht[2], 1e3 * ht[3]);
@@ -3274,28 +3290,17 @@ int acx_earlyfusion_pairs(acx_ctx *c, const int32_t *pairs, int64_t K, const acx
     if (!c) return ACX_ERR_INVALID;
     if (K < 0 || (K > 0 && (!pairs || !out)) || !params) return fail(c, ACX_ERR_INVALID, "earlyfusion_pairs: bad argument");
     if (K == 0) return ACX_OK;
-    // (indices are checked HERE, on the caller's list: the sorted copy below would name a pair by its sorted position)
-    for (int64_t k = 0; k < K; ++k)
-        if (pairs[2 * k] < 0 || pairs[2 * k + 1] < 0 || pairs[2 * k] >= c->ef_ntracks || pairs[2 * k + 1] >= c->ef_ntracks)
-            return fail(c, c->d_ef[0] && !c->ef_open ? ACX_ERR_INVALID : ACX_ERR_STATE,
-                        c->d_ef[0] && !c->ef_open ? "earlyfusion: track index out of range in pair " + std::to_string(k)
-                                                  : std::string("earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)"));
-    // An arbitrary pair list is processed sorted by (first track, second track): pairs that share a track then fall
-    // into the same rectangle of the GEMMs (shared operands) and neighbouring pairs read neighbouring memory.  A list
-    // that is sorted already (a grid tile, np.triu_indices ...) goes through as it is.
-    bool sorted = true;
-    for (int64_t k = 1; k < K && sorted; ++k)
-        sorted = pairs[2 * k - 2] < pairs[2 * k] || (pairs[2 * k - 2] == pairs[2 * k] && pairs[2 * k - 1] <= pairs[2 * k + 1]);
-    if (sorted) return run_ef(c, pairs, K, *params, out, nullptr, nullptr, 0, 0);
-    std::vector<int64_t> order((size_t)K);
-    for (int64_t k = 0; k < K; ++k) order[(size_t)k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        return pairs[2 * a] != pairs[2 * b] ? pairs[2 * a] < pairs[2 * b] : pairs[2 * a + 1] < pairs[2 * b + 1];
-    });
-    std::vector<int32_t> sp((size_t)2 * K);
-    for (int64_t k = 0; k < K; ++k) { sp[(size_t)2 * k] = pairs[2 * order[(size_t)k]]; sp[(size_t)2 * k + 1] = pairs[2 * order[(size_t)k] + 1]; }
+    // (indices are checked HERE, on the caller's list: the sorted copy below would name a pair by its sorted position; a track
+    // without blocks is left to the run)
+    int64_t upto;
+    int rc = check_ef_pairs(c, pairs, K, &upto);
+    if (rc != ACX_OK) return rc;
+    // the list in run order (ef_run_order, ef_plan.hpp); one that is sorted already goes through as it is
+    std::vector<int64_t> order;
+    std::vector<int32_t> sp;
+    if (acx::ef_run_order(pairs, K, order, sp)) return run_ef(c, pairs, K, *params, out, nullptr, nullptr, 0, 0);
     std::vector<float> so((size_t)4 * K);
-    const int rc = run_ef(c, sp.data(), K, *params, so.data(), nullptr, nullptr, 0, 0);
+    rc = run_ef(c, sp.data(), K, *params, so.data(), nullptr, nullptr, 0, 0);
     if (rc != ACX_OK) return rc;
     for (int64_t k = 0; k < K; ++k)
         for (int e = 0; e < 4; ++e) out[4 * order[(size_t)k] + e] = so[(size_t)4 * k + e];
@@ -3333,9 +3338,7 @@ int acx_ef_debug_bits(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_
     if (!c) return ACX_ERR_INVALID;
     if (!params || !pairs || K < 1 || which < 0 || which >= K) return fail(c, ACX_ERR_INVALID, "ef_debug_bits: bad argument");
     // the list as acx_earlyfusion_pairs hands it to run_ef: sorted, the fused matrix not stored
-    for (int64_t k = 1; k < K; ++k)
-        if (!(pairs[2 * k - 2] < pairs[2 * k] || (pairs[2 * k - 2] == pairs[2 * k] && pairs[2 * k - 1] <= pairs[2 * k + 1])))
-            return fail(c, ACX_ERR_INVALID, "ef_debug_bits: the pair list must be sorted by (first track, second track)");
+    if (!acx::ef_in_run_order(pairs, K)) return fail(c, ACX_ERR_INVALID, "ef_debug_bits: the pair list must be sorted by (first track, second track)");
     std::vector<float> sc((size_t)4 * K);
     const EfStats st{bits, t, jcut, r, cm};
     EfDebug dbg{nullptr, nullptr, nullptr, which, &st};
@@ -3481,42 +3484,36 @@ static int ef_align_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_
     if (path_off) path_off[0] = 0;
     if (K == 0) return ACX_OK;
     // the whole list before the first launch, on the caller's list (the sorted copy below would name a pair by its sorted position)
-    const bool pool = c->d_ef[0] && !c->ef_open;
-    for (int64_t k = 0; k < K; ++k)
-        if (pairs[2 * k] < 0 || pairs[2 * k + 1] < 0 || pairs[2 * k] >= c->ef_ntracks || pairs[2 * k + 1] >= c->ef_ntracks)
-            return fail(c, pool ? ACX_ERR_INVALID : ACX_ERR_STATE,
-                        pool ? "earlyfusion: track index out of range in pair " + std::to_string(k)
-                             : std::string("earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)"));
-    if (!pool) return fail(c, ACX_ERR_STATE, "earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)");
+    int64_t good;                                // (this entry's own rule comes before a later track without blocks)
+    int rc = check_ef_pairs(c, pairs, K, &good);
+    if (rc != ACX_OK) return rc;
+    const acx::EfLengths len{c->h_efoff.data(), c->ef_ntracks};
     int64_t bound = 0;                           // no path has more cells than its matrix's shorter side
-    for (int64_t k = 0; k < K; ++k) {
-        const int64_t M = c->h_efoff[pairs[2 * k] + 1] - c->h_efoff[pairs[2 * k]], N = c->h_efoff[pairs[2 * k + 1] + 1] - c->h_efoff[pairs[2 * k + 1]];
-        if (M < 1 || N < 1) return fail(c, ACX_ERR_SHORT, "earlyfusion: track without blocks (pair " + std::to_string(k) + ")");
+    for (int64_t k = 0; k < good; ++k) {
+        const int64_t M = len.blocks(pairs[2 * k]), N = len.blocks(pairs[2 * k + 1]);
         if (!any_length && (M > acx::EF_MAXNB || N > acx::EF_MAXNB))
             return fail(c, ACX_ERR_UNSUPPORTED, std::string("ef_align: ") + EF_ALIGN_TOO_LONG + " (pair " + std::to_string(k) + ": " + std::to_string(M) + " x " + std::to_string(N) + ")");
         bound += std::min(M, N);
     }
+    if (good < K) return ef_short_pair(c, good);
     if (path_off && cap < bound)
         return fail(c, ACX_ERR_INVALID, "ef_align: cap " + std::to_string(cap) + " is too small: " + std::to_string(bound) +
                                             " cells required (the sum of min(M, N) over the list)");
-    // the list runs sorted by (first track, second track), as acx_earlyfusion_pairs runs it; results go back in the caller's order
-    std::vector<int64_t> order((size_t)K);
-    for (int64_t k = 0; k < K; ++k) order[(size_t)k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        return pairs[2 * a] != pairs[2 * b] ? pairs[2 * a] < pairs[2 * b] : pairs[2 * a + 1] < pairs[2 * b + 1];
-    });
-    std::vector<int32_t> sp((size_t)2 * K);
-    for (int64_t k = 0; k < K; ++k) { sp[(size_t)2 * k] = pairs[2 * order[(size_t)k]]; sp[(size_t)2 * k + 1] = pairs[2 * order[(size_t)k] + 1]; }
+    // the list runs in run order, as acx_earlyfusion_pairs runs it; results go back in the caller's order
+    std::vector<int64_t> order;
+    std::vector<int32_t> sp;
+    const bool sorted = acx::ef_run_order(pairs, K, order, sp);
+    auto callers = [&](int64_t k) { return sorted ? k : order[(size_t)k]; };      // pair k of the run -> the caller's pair
     std::vector<float> so((size_t)4 * K);
     std::vector<acx_alignment> sal((size_t)K);
     std::vector<std::vector<int32_t>> paths(path_off ? (size_t)K : 0);
     const EfAlign aln{plane, sal.data(), path_off ? &paths : nullptr, any_length};
-    const int rc = run_ef(c, sp.data(), K, *params, so.data(), nullptr, nullptr, 0, 0, nullptr, &aln);
+    rc = run_ef(c, sorted ? pairs : sp.data(), K, *params, so.data(), nullptr, nullptr, 0, 0, nullptr, &aln);
     if (rc != ACX_OK) return rc;
-    for (int64_t k = 0; k < K; ++k) out[order[(size_t)k]] = sal[(size_t)k];
+    for (int64_t k = 0; k < K; ++k) out[callers(k)] = sal[(size_t)k];
     if (path_off) {
         std::vector<int64_t> where((size_t)K);                       // caller's pair -> its position in the run
-        for (int64_t k = 0; k < K; ++k) where[(size_t)order[(size_t)k]] = k;
+        for (int64_t k = 0; k < K; ++k) where[(size_t)callers(k)] = k;
         int64_t n = 0;
         for (int64_t k = 0; k < K; ++k) {
             const std::vector<int32_t> &pk = paths[(size_t)where[(size_t)k]];
@@ -4407,14 +4404,6 @@ static std::string xf_split_text(int M, int N, int K)
            std::to_string(k2) + "; needed: 1 <= k1 < M - 1 and 1 <= k2 < N - 1";
 }
 
-// csm_to_binary's neighbours per row (cross_recurrence.py:149-154), as run_ef sets EfPair::kbin
-static int xf_kbin(double kappa, int N)
-{
-    if (kappa == 0.0) return N;
-    if (kappa < 1.0) return (int)std::nearbyint(kappa * (double)N);
-    return (int)kappa;
-}
-
 static int xf_alloc(acx_ctx *c, XfRun &xr, int maxM, int maxN, int maxn, int K)
 {
     int rc = snf_alloc(c, xr.R, 3, maxn, K);
@@ -4526,17 +4515,12 @@ static int xf_pairs_impl(acx_ctx *c, const int32_t *pairs, int64_t Kp, const acx
     if (rc != ACX_OK) return rc;
     if (Kp == 0) return ACX_OK;
     // the whole list before the first launch, on the caller's list
-    const bool pool = c->d_ef[0] && !c->ef_open;
-    for (int64_t k = 0; k < Kp; ++k)
-        if (pairs[2 * k] < 0 || pairs[2 * k + 1] < 0 || pairs[2 * k] >= c->ef_ntracks || pairs[2 * k + 1] >= c->ef_ntracks)
-            return fail(c, pool ? ACX_ERR_INVALID : ACX_ERR_STATE,
-                        pool ? "earlyfusion: track index out of range in pair " + std::to_string(k)
-                             : std::string("earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)"));
-    if (!pool) return fail(c, ACX_ERR_STATE, "earlyfusion: block-feature pool not uploaded (acx_ef_upload_pool)");
+    int64_t good;                                // (this entry's own rules come before a later track without blocks)
+    if ((rc = check_ef_pairs(c, pairs, Kp, &good)) != ACX_OK) return rc;
+    const acx::EfLengths len{c->h_efoff.data(), c->ef_ntracks};
     int maxM = 0, maxN = 0, maxn = 0;
-    for (int64_t k = 0; k < Kp; ++k) {
-        const int64_t M = c->h_efoff[pairs[2 * k] + 1] - c->h_efoff[pairs[2 * k]], N = c->h_efoff[pairs[2 * k + 1] + 1] - c->h_efoff[pairs[2 * k + 1]];
-        if (M < 1 || N < 1) return fail(c, ACX_ERR_SHORT, "earlyfusion: track without blocks (pair " + std::to_string(k) + ")");
+    for (int64_t k = 0; k < good; ++k) {
+        const int64_t M = len.blocks(pairs[2 * k]), N = len.blocks(pairs[2 * k + 1]);
         if (M > acx::XF_MAXN || N > acx::XF_MAXN)
             return fail(c, ACX_ERR_UNSUPPORTED, "ef_crossfusion: the fusion needs the bit path: at most 1024 blocks (pair " + std::to_string(k) + ": " +
                                                     std::to_string(M) + " x " + std::to_string(N) + ")");
@@ -4545,6 +4529,7 @@ static int xf_pairs_impl(acx_ctx *c, const int32_t *pairs, int64_t Kp, const acx
             return fail(c, ACX_ERR_UNSUPPORTED, "ef_crossfusion: pair " + std::to_string(k) + ": " + xf_split_text((int)M, (int)N, params->K));
         maxM = std::max(maxM, (int)M); maxN = std::max(maxN, (int)N); maxn = std::max(maxn, (int)(M + N));
     }
+    if (good < Kp) return ef_short_pair(c, good);
     ACX_HIP(c, hipSetDevice(c->device));
     XfRun xr;
     if ((rc = xf_alloc(c, xr, maxM, maxN, maxn, params->K)) != ACX_OK) return rc;
@@ -4572,7 +4557,7 @@ static int xf_pairs_impl(acx_ctx *c, const int32_t *pairs, int64_t Kp, const acx
                 if (dbg->ssm_a) ACX_HIP(c, hipMemcpy2DAsync(dbg->ssm_a + (size_t)f * M * M, sizeof(float) * M, s.SA[f], sizeof(float) * s.ldA, sizeof(float) * M, M, hipMemcpyDeviceToHost, c->stream));
                 if (dbg->ssm_b) ACX_HIP(c, hipMemcpy2DAsync(dbg->ssm_b + (size_t)f * N * N, sizeof(float) * N, s.SB[f], sizeof(float) * s.ldB, sizeof(float) * N, N, hipMemcpyDeviceToHost, c->stream));
             }
-        if ((rc = xf_chain(c, xr, s, M, N, params->K, xf_kbin(params->kappa, N), niters, reg_diag, dbg ? dbg->tap : XfTaps(), out + k)) != ACX_OK) return rc;
+        if ((rc = xf_chain(c, xr, s, M, N, params->K, acx::ef_kbin(params->kappa, N), niters, reg_diag, dbg ? dbg->tap : XfTaps(), out + k)) != ACX_OK) return rc;
     }
     return ACX_OK;
 }
@@ -4620,7 +4605,7 @@ static int xf_matrices_impl(acx_ctx *c, const float *SA, const float *SB, const 
     s.ldA = M; s.ldB = N; s.ldC = N;
     for (int f = 0; f < 3; ++f) { s.SA[f] = dA + f * na; s.SB[f] = dB + f * nb; s.C[f] = dC + f * nc; }
     float sc = 0.0f;
-    if ((rc = xf_chain(c, xr, s, M, N, K, xf_kbin(kappa, N), niters, reg_diag, tap, &sc)) != ACX_OK) return rc;
+    if ((rc = xf_chain(c, xr, s, M, N, K, acx::ef_kbin(kappa, N), niters, reg_diag, tap, &sc)) != ACX_OK) return rc;
     if (score) *score = sc;
     return ACX_OK;
 }
@@ -4650,7 +4635,7 @@ static int xf_xsel_impl(acx_ctx *c, const double *X, int32_t M, int32_t N, doubl
     ACX_HIP(c, hipMemcpyAsync(xr.X, X, sizeof(double) * (size_t)M * N, hipMemcpyHostToDevice, c->stream));
     XfTaps tap;
     tap.bits = bits;
-    if ((rc = xf_select_sw(c, xr, M, N, xf_kbin(kappa, N), tap)) != ACX_OK) return rc;
+    if ((rc = xf_select_sw(c, xr, M, N, acx::ef_kbin(kappa, N), tap)) != ACX_OK) return rc;
     float sc = 0.0f;
     ACX_HIP(c, hipMemcpyAsync(&sc, c->d_out, sizeof(float), hipMemcpyDeviceToHost, c->stream));
     ACX_HIP(c, hipStreamSynchronize(c->stream));
@@ -5265,6 +5250,54 @@ int acx_serra09_plan(const int64_t *lengths, int32_t n_tracks, const int32_t *pa
 }
 
 const char *acx_serra09_family_name(int32_t family, int32_t m) { return acx::serra09_family_name(family, m); }
+
+// The EarlyFusion batch plan of a pair list without a device: acx_earlyfusion_pairs' run order and run_ef_impl's own checks, sizes,
+// packing and kernel choice (ef_plan.hpp), one record per pair.  Messages of a refused list: acx_last_error(NULL).
+int acx_ef_plan(const int64_t *blocks, int32_t n_tracks, const int32_t *pairs, int64_t K, const acx_ef_params *params, int64_t scratch_limit,
+                int32_t keep_fused, acx_ef_plan_rec *out)
+{
+    if (!blocks || n_tracks < 1 || K < 0 || (K > 0 && (!pairs || !out)) || !params) return ACX_ERR_INVALID;
+    if (!(params->kappa >= 0.0)) return fail(nullptr, ACX_ERR_INVALID, "earlyfusion: kappa must be >= 0");
+    if (params->K < 1) return fail(nullptr, ACX_ERR_INVALID, "earlyfusion: K must be >= 1");
+    std::vector<int64_t> off((size_t)n_tracks + 1, 0);
+    for (int t = 0; t < n_tracks; ++t) off[t + 1] = off[t] + std::max<int64_t>(blocks[t], 0);
+    const acx::EfLengths len{off.data(), n_tracks};
+    int rc = ef_check_text(nullptr, acx::ef_check_pairs(len, pairs, K));
+    if (rc != ACX_OK) return rc;
+    std::vector<int64_t> order;
+    std::vector<int32_t> sp;
+    const bool sorted = acx::ef_run_order(pairs, K, order, sp);
+    const int32_t *run = sorted ? pairs : sp.data();
+    const char *env = getenv("ACX_SCRATCH_GB");
+    const int64_t limit_floats = scratch_limit > 0 ? scratch_limit / 4
+                                 : (env && atof(env) > 0 ? (int64_t)(atof(env) * (double)(1ull << 30)) / 4 : INT64_MAX / 4);
+    const acx::EfMode mode = acx::ef_mode(len, run, K, params->K, keep_fused != 0);
+    const acx::EfSizes sz = acx::ef_batch_floats(len, run, K, params->kappa, mode, limit_floats);
+    if (sz.too_big >= 0) return fail(nullptr, ACX_ERR_NOMEM, "earlyfusion: pair " + std::to_string(sz.too_big) + " does not fit the scratch limit");
+    std::vector<acx::EfPair> pd;
+    int64_t k0 = 0;
+    for (int batch = 0; k0 < K; ++batch) {
+        acx::EfArena used;
+        const int64_t k1 = acx::ef_pack_batch(len, run, k0, K, *params, mode, sz.batch_floats, pd, used);
+        if (k1 == k0) return ACX_ERR_STATE;
+        const acx::EfBatchKernels kn = acx::ef_batch_kernels(used.maxM, used.maxN, params->K, mode, false);
+        for (int64_t k = k0; k < k1; ++k) {
+            const acx::EfPair &d = pd[(size_t)(k - k0)];
+            acx_ef_plan_rec &r = out[sorted ? k : order[(size_t)k]];
+            r.M = d.M; r.N = d.N; r.kbin = d.kbin;
+            r.batch = batch;
+            r.path = mode.bits_path ? 0 : 1;
+            r.row_kernel = kn.row; r.col_kernel = kn.col; r.fuse_kernel = kn.fuse; r.sw_kernel = kn.sw;
+            r.reserved = 0;
+            r.run_pos = k;
+            r.need = acx::ef_pair_floats(d, mode.keep_f);
+        }
+        k0 = k1;
+    }
+    return ACX_OK;
+}
+
+const char *acx_ef_kernel_name(int32_t stage, int32_t kernel) { return acx::ef_kernel_name(stage, kernel); }
 
 int64_t acx_serra09_fast_tail_launches(void) { return (int64_t)acx::fast_tail_launches(); }
 int64_t acx_serra09_plane_launches(void) { return (int64_t)acx::plane_launches(); }

@@ -647,6 +647,56 @@ int acx_ef_debug_pairs(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_
 int acx_ef_debug_bits(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_ef_params *params, int64_t which,
                       uint32_t *bits, float *t, int32_t *jcut, float *r, float *c, float *scores);
 
+/*
+ * The batch plan of a pair list, for tests and tools -- no context, no device: what acx_earlyfusion_pairs would do with the
+ * list on a pool whose tracks have these block counts, told by the functions the run itself calls
+ * (acoss_amd/csrc/ef_plan.hpp; the per-process switch ACX_EF_ROWSTAT2 applies).
+ *   blocks        blocks per track, as uploaded (n_tracks of them)
+ *   scratch_limit bytes, as acx_set_scratch_limit; <= 0: the default without a device -- env ACX_SCRATCH_GB, else unbounded
+ *                 (a context's default is 40 % of ITS device's memory, at most 36 GB)
+ *   keep_fused    != 0: as the debug entries that return the fused matrix run the list (acx_ef_debug_pair / _pairs): it is stored
+ *   out           K records, in the order of `pairs`:
+ *     M, N        blocks of the pair's tracks (rows, columns of its matrices); kbin: csm_to_binary's neighbours per row
+ *     batch       the batch the pair runs in; run_pos: its position in run order (sorted by first track, second track --
+ *                 batches are contiguous runs of THAT order)
+ *     path        0: the bit path, 1: the float path (a track of more than 1024 blocks anywhere in the list)
+ *     row_kernel, col_kernel, fuse_kernel, sw_kernel   ACX_EF_ROW_* / _COL_* / _FUSE_* / _SW_* of its batch
+ *     need        floats of the scratch arena the pair takes
+ * A list the run would refuse returns the run's code for it (ACX_ERR_INVALID: an index, or the parameters; ACX_ERR_SHORT: a
+ * track without blocks; ACX_ERR_NOMEM: a pair beyond the scratch limit) and fills nothing; the message: acx_last_error(NULL).
+ */
+enum { ACX_EF_ROW_TWO = 0,      /* ef_rowstat2_kernel: two rows per wave, rows of <= 512 cells                      */
+       ACX_EF_ROW_2 = 1,        /* ef_rowstat_kernel<2, false>: 8 values per lane, <= 512 cells                     */
+       ACX_EF_ROW_4 = 2,        /* ef_rowstat_kernel<4, false>: 16 values per lane, <= 1024 cells                   */
+       ACX_EF_ROW_LONG = 3 };   /* ef_rowstat_long_kernel: any length                                               */
+enum { ACX_EF_COL_ROWPASS = 0,  /* the row kernel on the transposed matrices (K > 16)                               */
+       ACX_EF_COL_10 = 1,       /* ef_colstat_kernel<10> (K <= 10)                                                  */
+       ACX_EF_COL_16 = 2,       /* ef_colstat_kernel<16>                                                            */
+       ACX_EF_COL_NONE = 3 };   /* a caller's matrix has no column statistics (never in this report)                */
+enum { ACX_EF_FUSE_NARROW = 0,  /* ef_rowstat_kernel<2, true>: fused matrix made and binarised in registers         */
+       ACX_EF_FUSE_WIDE = 1,    /* ef_rowstat_kernel<4, true>                                                       */
+       ACX_EF_FUSE_FLOAT = 2,   /* ef_fuse_kernel stores it; the one-row kernel of row_kernel's class selects on it */
+       ACX_EF_FUSE_NONE = 3 };  /* a caller's matrix is not fused (never in this report)                            */
+enum { ACX_EF_SW_H16_8 = 0,     /* sw_bits_h16_kernel<8>: bitmaps, rows of <= 512 cells                             */
+       ACX_EF_SW_H16_16 = 1,    /* sw_bits_h16_kernel<16>: <= 1024 cells                                            */
+       ACX_EF_SW_8 = 2,         /* sw_kernel<8>: float matrices, <= 512 cells                                       */
+       ACX_EF_SW_16 = 3,        /* sw_kernel<16>: <= 1024 cells                                                     */
+       ACX_EF_SW_LONG = 4 };    /* sw_long_kernel: any length                                                       */
+typedef struct acx_ef_plan_rec {
+    int32_t M, N, kbin;
+    int32_t batch;
+    int32_t path;
+    int32_t row_kernel, col_kernel, fuse_kernel, sw_kernel;
+    int32_t reserved;
+    int64_t run_pos;
+    int64_t need;
+} acx_ef_plan_rec;
+int acx_ef_plan(const int64_t *blocks, int32_t n_tracks, const int32_t *pairs, int64_t K, const acx_ef_params *params,
+                int64_t scratch_limit, int32_t keep_fused, acx_ef_plan_rec *out);
+/* Printable name of a kernel of the report: stage 0..3 (row statistics, column statistics, fused selection, Smith-Waterman) and
+ * the enum's value; NULL for an unknown one.  The string is static. */
+const char *acx_ef_kernel_name(int32_t stage, int32_t kernel);
+
 /* The run of acx_csm_binary_sw for one (M, N) f32 matrix with the caller's neighbourhood size K, and what it left behind (tests):
  * bits (M, pitch / 32), t (M), jcut (M), r (M) as above, and the Smith-Waterman score.  Any output may be NULL; M or N above 1024:
  * `bits` must be NULL. */

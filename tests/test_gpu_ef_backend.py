@@ -457,6 +457,11 @@ def test_float_path_on_short_batches_equals_the_bit_path(ctx, pools):
         used += need
     assert all(len(bt) == 1 for bt in batches if any(L in pr for pr in bt)) and sum(L in pr for bt in batches for pr in bt) == 2
     assert len(batches) >= 4
+    # ... and the library's own report of its plan (acx_ef_plan: no device) gives the same batches
+    from acoss_amd import _lib
+    plan = _lib.ef_plan(nb, Bl, scratch_limit=4 * limit_floats)
+    assert np.all(plan["path"] == 1) and plan["run_pos"].tolist() == list(range(len(Bl)))
+    assert [[(int(q), int(r)) for (q, r) in Bl[plan["batch"] == b]] for b in range(int(plan["batch"].max()) + 1)] == batches
     for fuse in ("fast", "exact"):
         ctx.set_ef_fuse(fuse)
         try:
