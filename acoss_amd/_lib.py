@@ -53,6 +53,7 @@ EXPORTS = [
     "acx_ef_align_long", "acx_sw_align_long_binary",
     "acx_serra09_align_sections", "acx_qmax_sections_binary",
     "acx_ef_plan", "acx_ef_kernel_name",
+    "acx_ef_align_sections", "acx_sw_sections_binary",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -370,7 +371,11 @@ def load():
                                       ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     L.acx_ef_align_long.argtypes = L.acx_ef_align.argtypes
     L.acx_sw_align_long_binary.argtypes = L.acx_sw_align_binary.argtypes
-    epp = ctypes.POINTER(EfPrepParams)
+    L.acx_ef_align_sections.argtypes = [vp, ip, ctypes.c_int64, ep, ctypes.c_int32, ctypes.POINTER(SectionOpts), ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+    L.acx_sw_sections_binary.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(SectionOpts),
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+    epp =ctypes.POINTER(EfPrepParams)
     L.acx_ef_block_features.argtypes = [vp, fp, ctypes.c_int64, fp, ctypes.c_int64, ctypes.c_int32, lp, ctypes.c_int32, epp,
                                         fp, fp, fp, dp]
     L.acx_ef_upload_raw_pool.argtypes = [vp, fp, lp, fp, lp, ctypes.c_int32, lp, lp, ctypes.c_int32, epp, lp]
@@ -1438,6 +1443,45 @@ class Context(object):
                                                      ctypes.byref(p), ctypes.byref(o), out.ctypes.data, n.ctypes.data,
                                                      off.ctypes.data if paths else None, cells.ctypes.data if paths else None,
                                                      int(cap) if paths else 0))
+        return (out[0], int(n[0]), off, cells[:off[-1]].copy()) if paths else (out[0], int(n[0]))
+
+    def ef_align_sections(self, pairs, kappa=0.1, K=10, plane=3, opts=None, paths=False, cap=None):
+        """EVERY matched section of every (query, reference) pair in one binarised matrix (acx_ef_align_sections, DESIGN.md section
+        29; plane as in ef_align): (records, counts) and with paths=True (records, counts, offsets, cells), laid out as
+        serra09_align_sections lays them out.  Tracks of at most 1024 blocks.  cap: default the bound the library checks, the sum
+        of min(M_k, max_sections * min(M_k, N_k)) from the block counts of the pool this object uploaded; for a pool it did not see
+        uploaded, the bound of any list the library accepts."""
+        p = EfParams(float(kappa), int(K))
+        o = opts or section_opts("ef_align_sections")
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        if paths and cap is None:
+            nb = getattr(self, "ef_blocks", None)
+            if nb is None:
+                cap = 1024 * len(pairs)
+            else:
+                nb = np.asarray(nb, dtype=np.int64)
+                ok = np.all((pairs >= 0) & (pairs < len(nb)), axis=1) if len(pairs) else np.zeros(0, bool)
+                M, N = nb[pairs[ok, 0]], nb[pairs[ok, 1]]
+                cap = int(np.minimum(M, o.max_sections * np.minimum(M, N)).sum())
+        out, n, off, cells = self._sections_out(len(pairs), o.max_sections, paths, cap)
+        self._check(self._L.acx_ef_align_sections(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), ctypes.byref(o),
+                                                  out.ctypes.data, n.ctypes.data, off.ctypes.data if paths else None,
+                                                  cells.ctypes.data if paths else None, int(cap) if paths else 0))
+        return (out, n, off, cells[:off[-1]].copy()) if paths else (out, n)
+
+    def sw_sections_binary(self, B, opts=None, paths=True, cap=None):
+        """The same DP alone on a given binary (M, N) plot of at most 1024 x 1024 (acx_sw_sections_binary): (records (max_sections,),
+        count) and with paths=True (records, count, offsets (max_sections + 1,), cells).  cap: default min(M, max_sections * min(M, N))."""
+        o = opts or section_opts("sw_sections_binary")
+        B = np.ascontiguousarray(B, dtype=np.uint8)
+        if B.ndim != 2:
+            raise ValueError("sw_sections_binary: B must be (M, N), got shape %s" % (B.shape,))
+        if paths and cap is None:
+            cap = min(B.shape[0], o.max_sections * min(B.shape))
+        out, n, off, cells = self._sections_out(1, o.max_sections, paths, cap)
+        self._check(self._L.acx_sw_sections_binary(self._h, B.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), B.shape[0], B.shape[1],
+                                                   ctypes.byref(o), out.ctypes.data, n.ctypes.data, off.ctypes.data if paths else None,
+                                                   cells.ctypes.data if paths else None, int(cap) if paths else 0))
         return (out[0], int(n[0]), off, cells[:off[-1]].copy()) if paths else (out[0], int(n[0]))
 
     def chenfusion_align(self, pairs, params=None, plane=0):

@@ -309,6 +309,69 @@ class EarlyFusion(CoverAlgorithm):
         out[rows, slots] = self._align_pairs(pairs, plane, got)
         return out, _align.scatter_paths(idx, rows, slots, got)
 
+    # ------------------------------------------------------------------ every matched section of a pair
+    def _check_sections(self, who, similarity_type, max_sections, min_score, min_ratio, pad):
+        """The plane and the options, before the first library call."""
+        return self._align_plane(who, similarity_type), _lib.section_opts(who, max_sections, min_score, min_ratio, pad)
+
+    def _section_pairs(self, who, pairs, plane, o, want_paths):
+        """(P, 2) checked int32 pairs -> (a P-list of (n_k,) ALIGN_DTYPE arrays, a P-list of lists of n_k (L, 2) int32 paths or None)."""
+        if len(pairs) == 0:
+            return [], ([] if want_paths else None)
+        ctx = self._context()
+        if ctx.ef_has_long_track(pairs) and getattr(ctx, "ef_blocks", None) is not None:
+            raise NotImplementedError("%s: sections need the bit path: tracks of at most 1024 blocks (align() serves longer ones)" % who)
+        got = ctx.ef_align_sections(pairs, self.kappa, self.K, plane, o, paths=want_paths)
+        al, n = got[0], got[1]
+        S = al.shape[1]
+        out = _align.no_match_rows(al.shape, self.ALIGN_DTYPE)
+        for f in _lib.ALIGNMENT_DTYPE.names:
+            out[f] = al[f]
+        hit = al["q0"] >= 0
+        for side in ("q", "r"):                                     # (align()'s spans: block b covers beats b .. b + blocksize - 1)
+            span = np.stack([al[side + "0"], al[side + "1"] + int(self.blocksize) - 1], axis=-1)
+            out[side + "_span"][hit] = span[hit]
+        sections = [out[k, :n[k]].copy() for k in range(len(pairs))]
+        if not want_paths:
+            return sections, None
+        off, cells = got[2], got[3]
+        return sections, [[cells[off[k * S + s]:off[k * S + s + 1]] for s in range(n[k])] for k in range(len(pairs))]
+
+    def align_sections(self, idxs, similarity_type="early", max_sections=4, min_score=2.0, min_ratio=0.0, pad=0, paths=False):
+        """EVERY matched section of a pair, not only the best alignment: a cover that plays the chorus once more, the two halves
+        around an inserted solo, the passages a medley quotes.  idxs and similarity_type as for align().  Returns a K-list of
+        (n_k,) structured arrays with align()'s fields (positions in BLOCKS, spans in BEATS), n_k <= max_sections (at most 16),
+        section 0 first; with paths=True (sections, paths), paths[k] a list of n_k (L, 2) int32 arrays as align_paths() lists them.
+          section 0      exactly align()'s row for the pair, provided its score >= min_score; otherwise the pair has no sections
+          section k + 1  the Smith-Waterman alignment of what is left when the QUERY's blocks q0 .. q1 of every section found so
+                         far, and `pad` blocks on either side of each (never across an earlier section), are excluded -- the
+                         recursion's value is 0 on those rows, so no alignment runs through them; reported iff its score >=
+                         max(min_score, min_ratio * section 0's score).  The search ends at the first section that fails.
+        Scores do not increase with k; every QUERY block belongs to at most one section (the row ranges are disjoint), while
+        reference blocks may be shared.  For a segmentation of the reference swap the pair.  min_score must be > 1, 0 <=
+        min_ratio <= 1, pad >= 0.  Tracks of at most 1024 blocks (NotImplementedError naming the method otherwise).  `Ds` is
+        not written; not a collective."""
+        plane, o = self._check_sections("align_sections", similarity_type, max_sections, min_score, min_ratio, pad)
+        pairs = _align.check_pairs("align_sections", _align.check_indices("align_sections", idxs), self._n_tracks())
+        sections, got = self._section_pairs("align_sections", pairs, plane, o, bool(paths))
+        return (sections, got) if paths else sections
+
+    def align_match_sections(self, queries, indices, similarity_type="early", max_sections=4, min_score=2.0, min_ratio=0.0, pad=0, paths=False):
+        """align_sections() for the hits of identify() / rerank(): queries (Q,) track indices, indices the (Q, k) int array either
+        returned (-1: an empty slot).  Returns a Q-list of k-lists of (n,) arrays as align_sections() returns them, slot s of row i
+        for the ORDERED pair (queries[i], indices[i, s]) -- an empty slot is an empty array -- and with paths=True (sections,
+        paths), paths a Q-list of k-lists of lists of (L, 2) int32 arrays."""
+        plane, o = self._check_sections("align_match_sections", similarity_type, max_sections, min_score, min_ratio, pad)
+        idx, rows, slots, pairs = self._check_align_matches("align_match_sections", queries, indices)
+        sections, got = self._section_pairs("align_match_sections", pairs, plane, o, bool(paths))
+        out = [[np.zeros(0, self.ALIGN_DTYPE) for _ in range(idx.shape[1])] for _ in range(idx.shape[0])]
+        out_paths = [[[] for _ in range(idx.shape[1])] for _ in range(idx.shape[0])]
+        for t, (r, s) in enumerate(zip(rows, slots)):
+            out[r][s] = sections[t]
+            if paths:
+                out_paths[r][s] = got[t]
+        return (out, out_paths) if paths else out
+
     def _fusion_context(self):
         """The GPU context of the pair grid, or a fresh one (scores loaded with precomputed=True)."""
         if getattr(self, "_ctx", None) is None:

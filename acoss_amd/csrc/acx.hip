@@ -31,6 +31,7 @@
 #include "ef_kernels.hpp"
 #include "ef_rowstat2_kernels.hpp"
 #include "ef_align_kernels.hpp"
+#include "ef_sections_kernels.hpp"
 #include "ef_gemm_dma_kernels.hpp"
 #include "ef_prep_kernels.hpp"
 #include "ftm2d_kernels.hpp"
@@ -59,7 +60,7 @@ struct KStat {
     int64_t launches;
     int64_t cells;
 };
-enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_SECTIONS, KS_DLOCATE, KS_DPATH, KS_SIMPLEPROF, KS_XFMEANS, KS_XFAFFINITY, KS_XFSNF, KS_XFX, KS_XFSELECT, KS_FUSEDSTAGE, KS_SNFBATCHPREP, KS_SNFBATCHUPDATE, KS_FUSEDROW, KS_EFALIGNLONG, KS_EFALIGN, KS_COUNT };
+enum { KS_OTI = 0, KS_NORMS, KS_BAND, KS_CSM, KS_SEL, KS_QMAX, KS_SIMPLE, KS_EFGEMM, KS_EFSTAT, KS_EFFUSE, KS_EFSW, KS_RANK, KS_TOPK, KS_FTMTILE, KS_QROWS, KS_QTOPK, KS_QRANK, KS_QTOPKL, KS_FTMPAIRS, KS_LOCATE, KS_PATH, KS_SECTIONS, KS_DLOCATE, KS_DPATH, KS_SIMPLEPROF, KS_XFMEANS, KS_XFAFFINITY, KS_XFSNF, KS_XFX, KS_XFSELECT, KS_FUSEDSTAGE, KS_SNFBATCHPREP, KS_SNFBATCHUPDATE, KS_FUSEDROW, KS_EFSECTIONS, KS_EFALIGNLONG, KS_EFALIGN, KS_COUNT };
 
 struct PendingEvent {
     hipEvent_t a, b;
@@ -233,6 +234,7 @@ struct acx_ctx {
                              {"xf_snf_kernels", 0, 0, 0}, {"xf_x_kernel", 0, 0, 0}, {"xf_select_kernel", 0, 0, 0},
                              {"fused_stage_kernel", 0, 0, 0}, {"snf_batch_prepare_kernels", 0, 0, 0}, {"snf_batch_update_kernels", 0, 0, 0},
                              {"fused_row_kernel", 0, 0, 0},
+                             {"ef_sections_kernel", 0, 0, 0},
                              {"ef_align_long_kernel", 0, 0, 0},
                              {"ef_align_kernel", 0, 0, 0}};
     std::vector<PendingEvent> pending;
@@ -1171,7 +1173,13 @@ struct EfDebug { float *csm, *fused; int32_t *oti; int64_t which = 0; const EfSt
 // when `paths` is given (K vectors), the cells (q, r) of its path from start to end.  Pair k of the run's list -> al[k], (*paths)[k].
 // any_length (acx_ef_align_long): a list with a track of more than 1024 blocks is not refused -- its batches take the float path, and
 // ef_align_long_kernel reads the plot off the float matrices.
-struct EfAlign { int plane; acx_alignment *al; std::vector<std::vector<int32_t>> *paths; bool any_length; };
+// sec (acx_ef_align_sections): EVERY section of a pair -- the batch's chunks run ef_sections_kernel in place of
+// ef_align_kernel, pair k's sec->max_sections records go to al[k * max_sections ..], their number to n_sec[k] and, with `paths`
+// (K * max_sections vectors), the cells of record t to (*paths)[t].  The bit path only.
+struct EfAlign {
+    int plane; acx_alignment *al; std::vector<std::vector<int32_t>> *paths; bool any_length;
+    const acx_section_opts *sec = nullptr; int32_t *n_sec = nullptr;
+};
 
 // pinned host staging + device copy of `n` score destinations idx[0 .. n)
 static int stage_idx(acx_ctx *c, const int64_t *idx, int64_t n)
@@ -1462,6 +1470,41 @@ static int decode_ef_alignment(acx_ctx *c, const std::string &who, const std::st
     return ACX_OK;
 }
 
+// One job's result of ef_sections_kernel on the host: `n` its number of sections, `rec` its S records of EFA_REC
+// words, `src` its cells -- the sections' behind one another, each as the traceback left it -- read only where `paths` (S vectors) is
+// given, `room` what the job had for them.  Every section goes through decode_ef_alignment: section 0 must have the bits of `score`
+// (or nullptr), every section its cells from the reported end to the reported start.  Beyond that: the count is within S, the
+// records behind it are the no-match record, scores do not increase, and the row ranges are pairwise disjoint.
+static int decode_ef_sections(acx_ctx *c, const std::string &who, const std::string &of, int S, int n, const int32_t *rec, const int32_t *src,
+                              int64_t room, int side, const float *score, float min_score, acx_alignment *out, int32_t &n_out,
+                              std::vector<int32_t> *paths)
+{
+    if (n < 0 || n > S) return fail(c, ACX_ERR_STATE, who + ": the sections" + of + " number " + std::to_string(n));
+    const float zero = 0.0f;
+    int64_t used = 0;
+    for (int s = 0; s < S; ++s) {
+        const int32_t *r = rec + (size_t)acx::EFA_REC * s;
+        const int ns = r[5];
+        if (ns < 0 || used + ns > room) return fail(c, ACX_ERR_STATE, who + ": the traceback" + of + " returned " + std::to_string(ns) + " cells");
+        // a pair whose alignment stays below min_score has no sections: section 0's score is then not the kernel's to report
+        const float *want = s == 0 && n > 0 ? score : (s >= n ? &zero : nullptr);
+        int rc = decode_ef_alignment(c, who, of, r, src ? src + 2 * used : nullptr, side, want, out[s], paths ? &paths[s] : nullptr);
+        if (rc != ACX_OK) return rc;
+        used += ns;
+        if (s < n) {
+            if (!(out[s].score > 0.0f) || (s > 0 && out[s].score > out[s - 1].score))
+                return fail(c, ACX_ERR_STATE, who + ": the scores of the sections" + of + " are not in order");
+            for (int t = 0; t < s; ++t)
+                if (out[s].q0 <= out[t].q1 && out[t].q0 <= out[s].q1)
+                    return fail(c, ACX_ERR_STATE, who + ": sections " + std::to_string(t) + " and " + std::to_string(s) + of + " share a row");
+        }
+    }
+    if (n == 0 && score && *score >= min_score)
+        return fail(c, ACX_ERR_STATE, who + ": no section" + of + " although the pair's score reaches min_score");
+    n_out = n;
+    return ACX_OK;
+}
+
 // The alignment pass (ef_align_kernels.hpp) behind a batch's Smith-Waterman launch, while d_efbits and d_efpd
 // still hold the batch: `pd` are the batch's descriptors on the host, pair b of the batch is pair k0 + b of the run, `scores` its
 // four scores (queued behind the batch's kernels: valid after a wait).  The batch's pairs run in CHUNKS: as many consecutive pairs
@@ -1482,6 +1525,7 @@ static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, in
 {
     const int B = (int)pd.size();
     const int64_t wave_cap = ef_align_wave_cap();
+    const int S = aln.sec ? aln.sec->max_sections : 0;              // > 0: every section of a pair (ef_sections_kernel)
     std::vector<acx::EfAlignJob> jobs;
     std::vector<int32_t> h_res;
     int b = 0;
@@ -1494,14 +1538,16 @@ static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, in
             const int64_t w = float_path ? acx::ef_align_long_dir_words(d.M, d.N) : acx::ef_align_dir_words(d.M, d.pitchC);
             if (!jobs.empty() && 4 * (words + w) > budget) break;
             acx::EfAlignJob j;
-            j.pair = b; j.max_cells = std::min(d.M, d.N); j.dir_off = words; j.cell_off = ncell;
+            // (sections: the room of ALL the pair's sections, ef_sections_room)
+            j.pair = b; j.max_cells = S ? (int)acx::ef_sections_room(d.M, d.N, S) : std::min(d.M, d.N); j.dir_off = words; j.cell_off = ncell;
             words += w;
             ncell += j.max_cells;
             area += (int64_t)d.M * d.N;
             jobs.push_back(j);
         }
         const int nb = (int)jobs.size();
-        const size_t nrec = (size_t)acx::EFA_REC * nb, nres = nrec + 2 * (size_t)ncell;
+        // (sections: the counts, then S records a job)
+        const size_t nrec = S ? (size_t)nb + (size_t)acx::EFA_REC * S * nb : (size_t)acx::EFA_REC * nb, nres = nrec + 2 * (size_t)ncell;
         int rc;
         if ((rc = ensure(c, c->d_efdir, (size_t)words)) != ACX_OK) return rc;
         if ((rc = ensure(c, c->d_efjob, (size_t)nb)) != ACX_OK) return rc;
@@ -1512,6 +1558,10 @@ static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, in
             // free behind the batch's Smith-Waterman launches on this stream)
             ProfScope ps(c, KS_EFALIGNLONG, area);
             hipLaunchKernelGGL(acx::ef_align_long_kernel, dim3(nb), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_scratch, c->d_thr, c->d_efdir, c->d_efres, aln.plane);
+        } else if (S) {
+            ProfScope ps(c, KS_EFSECTIONS, area);
+            hipLaunchKernelGGL(acx::ef_sections_kernel, dim3(nb), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, aln.plane,
+                               S, aln.sec->pad, aln.sec->min_score, aln.sec->min_ratio);
         } else {
             ProfScope ps(c, KS_EFALIGN, area);
             hipLaunchKernelGGL(acx::ef_align_kernel, dim3(nb), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, aln.plane);
@@ -1525,6 +1575,15 @@ static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, in
             const acx::EfAlignJob &j = jobs[(size_t)t];
             const int64_t k = k0 + b0 + t;
             const int32_t *src = aln.paths ? h_res.data() + nrec + 2 * (size_t)j.cell_off : nullptr;
+            if (S) {
+                const acx::EfPair &d = pd[(size_t)j.pair];
+                if ((rc = decode_ef_sections(c, "ef_align_sections", " of pair " + std::to_string(k), S, h_res[(size_t)t],
+                                             h_res.data() + nb + (size_t)acx::EFA_REC * S * t, src, j.max_cells, std::min(d.M, d.N),
+                                             scores + 4 * (size_t)(b0 + t) + aln.plane, aln.sec->min_score, aln.al + (size_t)k * S, aln.n_sec[k],
+                                             aln.paths ? &(*aln.paths)[(size_t)k * S] : nullptr)) != ACX_OK)
+                    return rc;
+                continue;
+            }
             if ((rc = decode_ef_alignment(c, "ef_align", " of pair " + std::to_string(k), h_res.data() + (size_t)acx::EFA_REC * t, src, j.max_cells,
                                           scores + 4 * (size_t)(b0 + t) + aln.plane, aln.al[k], aln.paths ? &(*aln.paths)[(size_t)k] : nullptr)) != ACX_OK)
                 return rc;
@@ -3474,13 +3533,17 @@ int acx_sw_bits_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, float
 // ---------------------------------------------------------------------------------------
 static const char *const EF_ALIGN_TOO_LONG = "alignment needs the bit path: at most 1024 blocks";
 
+// opts (acx_ef_align_sections): every section of a pair -- `out` holds max_sections records a pair, n_sections
+// their numbers, path_off one entry per record; `who` names the entry point in errors.
 static int ef_align_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params *params, int32_t plane, acx_alignment *out,
-                         int64_t *path_off, int32_t *cells, int64_t cap, bool any_length)
+                         int64_t *path_off, int32_t *cells, int64_t cap, bool any_length, const acx_section_opts *opts = nullptr,
+                         int32_t *n_sections = nullptr, const std::string &who = "ef_align")
 {
-    if (K < 0 || (K > 0 && (!pairs || !out)) || !params || cap < 0) return fail(c, ACX_ERR_INVALID, "ef_align: bad argument");
+    if (K < 0 || (K > 0 && (!pairs || !out)) || !params || cap < 0) return fail(c, ACX_ERR_INVALID, who + ": bad argument");
     if ((path_off == nullptr) != (cells == nullptr))
-        return fail(c, ACX_ERR_INVALID, "ef_align: path_off and cells must both be given (the paths) or both be NULL (the records alone)");
-    if (plane < 0 || plane > 3) return fail(c, ACX_ERR_INVALID, "ef_align: plane must be 0..3 (mfccs, ssms, chromas, early), got " + std::to_string(plane));
+        return fail(c, ACX_ERR_INVALID, who + ": path_off and cells must both be given (the paths) or both be NULL (the records alone)");
+    if (plane < 0 || plane > 3) return fail(c, ACX_ERR_INVALID, who + ": plane must be 0..3 (mfccs, ssms, chromas, early), got " + std::to_string(plane));
+    const int S = opts ? opts->max_sections : 1;                 // records a pair
     if (path_off) path_off[0] = 0;
     if (K == 0) return ACX_OK;
     // the whole list before the first launch, on the caller's list (the sorted copy below would name a pair by its sorted position)
@@ -3492,34 +3555,38 @@ static int ef_align_impl(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_
     for (int64_t k = 0; k < good; ++k) {
         const int64_t M = len.blocks(pairs[2 * k]), N = len.blocks(pairs[2 * k + 1]);
         if (!any_length && (M > acx::EF_MAXNB || N > acx::EF_MAXNB))
-            return fail(c, ACX_ERR_UNSUPPORTED, std::string("ef_align: ") + EF_ALIGN_TOO_LONG + " (pair " + std::to_string(k) + ": " + std::to_string(M) + " x " + std::to_string(N) + ")");
-        bound += std::min(M, N);
+            return fail(c, ACX_ERR_UNSUPPORTED, who + ": " + EF_ALIGN_TOO_LONG + " (pair " + std::to_string(k) + ": " + std::to_string(M) + " x " + std::to_string(N) + ")");
+        bound += opts ? path_cells_bound((int)M, (int)N, S) : std::min(M, N);
     }
     if (good < K) return ef_short_pair(c, good);
     if (path_off && cap < bound)
-        return fail(c, ACX_ERR_INVALID, "ef_align: cap " + std::to_string(cap) + " is too small: " + std::to_string(bound) +
-                                            " cells required (the sum of min(M, N) over the list)");
+        return fail(c, ACX_ERR_INVALID, who + ": cap " + std::to_string(cap) + " is too small: " + std::to_string(bound) + " cells required (the sum of " +
+                                            (opts ? "min(M, max_sections * min(M, N))" : "min(M, N)") + " over the list)");
     // the list runs in run order, as acx_earlyfusion_pairs runs it; results go back in the caller's order
     std::vector<int64_t> order;
     std::vector<int32_t> sp;
     const bool sorted = acx::ef_run_order(pairs, K, order, sp);
     auto callers = [&](int64_t k) { return sorted ? k : order[(size_t)k]; };      // pair k of the run -> the caller's pair
     std::vector<float> so((size_t)4 * K);
-    std::vector<acx_alignment> sal((size_t)K);
-    std::vector<std::vector<int32_t>> paths(path_off ? (size_t)K : 0);
-    const EfAlign aln{plane, sal.data(), path_off ? &paths : nullptr, any_length};
+    std::vector<acx_alignment> sal((size_t)K * S);
+    std::vector<int32_t> sn(opts ? (size_t)K : 0);
+    std::vector<std::vector<int32_t>> paths(path_off ? (size_t)K * S : 0);
+    const EfAlign aln{plane, sal.data(), path_off ? &paths : nullptr, any_length, opts, sn.data()};
     rc = run_ef(c, sorted ? pairs : sp.data(), K, *params, so.data(), nullptr, nullptr, 0, 0, nullptr, &aln);
     if (rc != ACX_OK) return rc;
-    for (int64_t k = 0; k < K; ++k) out[callers(k)] = sal[(size_t)k];
+    for (int64_t k = 0; k < K; ++k) {
+        std::copy(sal.begin() + k * S, sal.begin() + (k + 1) * S, out + callers(k) * S);
+        if (opts) n_sections[callers(k)] = sn[(size_t)k];
+    }
     if (path_off) {
         std::vector<int64_t> where((size_t)K);                       // caller's pair -> its position in the run
         for (int64_t k = 0; k < K; ++k) where[(size_t)callers(k)] = k;
         int64_t n = 0;
-        for (int64_t k = 0; k < K; ++k) {
-            const std::vector<int32_t> &pk = paths[(size_t)where[(size_t)k]];
+        for (int64_t t = 0; t < K * S; ++t) {                        // record t of the caller's list: section t % S of its pair t / S
+            const std::vector<int32_t> &pk = paths[(size_t)(where[(size_t)(t / S)] * S + t % S)];
             if (!pk.empty()) memcpy(cells + 2 * n, pk.data(), sizeof(int32_t) * pk.size());
             n += (int64_t)pk.size() / 2;
-            path_off[k + 1] = n;
+            path_off[t + 1] = n;
         }
     }
     return ACX_OK;
@@ -3596,6 +3663,68 @@ int acx_sw_align_long_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N,
 {
     if (!c) return ACX_ERR_INVALID;
     return sw_align_plot(c, "sw_align_long_binary", true, B, M, N, out, cells, cap, n_cells);
+}
+
+// ---- every section of a pair ----
+int acx_ef_align_sections(acx_ctx *c, const int32_t *pairs, int64_t K, const acx_ef_params *params, int32_t plane, const acx_section_opts *opts,
+                          acx_alignment *out, int32_t *n_sections, int64_t *path_off, int32_t *cells, int64_t cap)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const std::string who = "ef_align_sections";
+    return guarded(c, [&]() -> int {
+        if (!opts || (K > 0 && !n_sections)) return fail(c, ACX_ERR_INVALID, who + ": bad argument");
+        int rc = check_section_opts(c, who, *opts);
+        if (rc != ACX_OK) return rc;
+        return ef_align_impl(c, pairs, K, params, plane, out, path_off, cells, cells ? cap : 0, false, opts, n_sections, who);
+    });
+}
+
+// ef_sections_kernel alone on a caller's plot, staged as acx_sw_align_binary stages it: one job.
+int acx_sw_sections_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, const acx_section_opts *opts, acx_alignment *out,
+                           int32_t *n_sections, int64_t *path_off, int32_t *cells, int64_t cap)
+{
+    if (!c) return ACX_ERR_INVALID;
+    const std::string who = "sw_sections_binary";
+    acx::EfPair d;
+    acx::EfAlignJob job;
+    std::vector<uint32_t> W;
+    std::vector<int32_t> res;
+    return guarded(c, [&]() -> int {
+        if (!B || !opts || !out || !n_sections || M < 1 || N < 1 || (path_off == nullptr) != (cells == nullptr) || (cells && cap < 0))
+            return fail(c, ACX_ERR_INVALID, who + ": bad argument");
+        int rc = check_section_opts(c, who, *opts);
+        if (rc != ACX_OK) return rc;
+        const int S = opts->max_sections;
+        if (M > acx::EF_MAXNB || N > acx::EF_MAXNB) return fail(c, ACX_ERR_UNSUPPORTED, who + ": " + EF_ALIGN_TOO_LONG);
+        const int64_t room = acx::ef_sections_room(M, N, S);
+        if (cells && cap < room)
+            return fail(c, ACX_ERR_INVALID, who + ": cap " + std::to_string(cap) + " is too small: " + std::to_string(room) +
+                                                " cells required (min(M, max_sections * min(M, N)))");
+        if (path_off) path_off[0] = 0;
+        if ((rc = stage_ef_bit_plot(c, who, B, M, N, d, W)) != ACX_OK) return rc;
+        job.pair = 0; job.max_cells = (int)room; job.dir_off = 0; job.cell_off = 0;
+        const size_t nrec = 1 + (size_t)acx::EFA_REC * S, nres = nrec + 2 * (size_t)room;
+        res.resize(nres);
+        if ((rc = ensure(c, c->d_efjob, (size_t)1)) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_efdir, (size_t)acx::ef_align_dir_words(M, d.pitchC))) != ACX_OK) return rc;
+        if ((rc = ensure(c, c->d_efres, nres)) != ACX_OK) return rc;
+        ACX_HIP(c, hipMemcpyAsync(c->d_efjob, &job, sizeof(job), hipMemcpyHostToDevice, c->stream));
+        {
+            ProfScope ps(c, KS_EFSECTIONS, (int64_t)M * N);
+            hipLaunchKernelGGL(acx::ef_sections_kernel, dim3(1), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, 0,
+                               S, opts->pad, opts->min_score, opts->min_ratio);
+        }
+        ACX_HIP(c, hipGetLastError());
+        ACX_HIP(c, hipMemcpyAsync(res.data(), c->d_efres, sizeof(int32_t) * (cells ? nres : nrec), hipMemcpyDeviceToHost, c->stream));
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        drain_profile(c);
+        std::vector<std::vector<int32_t>> paths(cells ? (size_t)S : 0);
+        if ((rc = decode_ef_sections(c, who, "", S, res[0], res.data() + 1, cells ? res.data() + nrec : nullptr, room, std::min(M, N), nullptr,
+                                     opts->min_score, out, *n_sections, cells ? paths.data() : nullptr)) != ACX_OK)
+            return rc;
+        if (cells) pack_paths(paths, path_off, cells);
+        return ACX_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------------------

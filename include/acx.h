@@ -766,6 +766,38 @@ int acx_ef_align_long(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_e
 int acx_sw_align_long_binary(acx_ctx *ctx, const uint8_t *B, int32_t M, int32_t N, acx_alignment *out, int32_t *cells, int64_t cap,
                              int64_t *n_cells);
 
+/* EVERY matched section of every listed pair in ONE binarised matrix, not only the best alignment (ABI 4, additive).  pairs, params,
+ * plane, the T frame, score, end, predecessor, start and path: acx_ef_align's.  opts: the acx_section_opts of
+ * acx_serra09_align_sections with the same checks (max_sections S in 1..16, min_score > 1, min_ratio in 0..1, pad >= 0; else
+ * ACX_ERR_INVALID).
+ *   section 0       acx_ef_align's record for that pair and plane, bit for bit, reported iff its score >= min_score; otherwise the
+ *                   pair has no sections
+ *   free intervals  the rows start as one free interval [0, M - 1]; a section with rows q0..q1 inside the free interval [a, b]
+ *                   EXCLUDES [max(a, q0 - pad), min(b, q1 + pad)], and [a, b] is replaced by what is left above and below
+ *   section k + 1   the alignment of T', the same recursion with T' = 0 on every cell of an excluded row -- U' = (B ? 0 : -7) there,
+ *                   what rows 0 and 1 hold: no alignment runs through an excluded stretch.  Reported iff its f32 score >=
+ *                   max(min_score, min_ratio * score_0) (one f32 multiply, equality counts); the search ends at the first section
+ *                   that fails, or after S
+ * Scores do not increase with k, the row ranges [q0, q1] of a pair's sections are pairwise disjoint, reference columns may be
+ * shared, and max_sections = 1 is acx_ef_align.
+ *   out             K x S records, pair k's from out[k * S], section 0 first; behind its n_sections[k] sections the no-match record
+ *   path_off, cells both NULL: the records alone.  Both given: path_off has K * S + 1 entries, record t = k * S + s has the cells
+ *                   cells[2 path_off[t] .. 2 path_off[t + 1]) from its start to its end.  Exactly one NULL: ACX_ERR_INVALID.
+ *   cap             at least the sum of min(M_k, S * min(M_k, N_k)) over the list, checked before the first launch; too small ->
+ *                   ACX_ERR_INVALID with the required number in the message
+ * Tracks of at most 1024 blocks: a longer one anywhere in the list -> ACX_ERR_UNSUPPORTED for the whole list before any launch, as
+ * acx_ef_align refuses it.  Every other check, code and message of the list: acx_ef_align's.  A failed call leaves nothing in flight,
+ * and a valid call after it succeeds. */
+int acx_ef_align_sections(acx_ctx *ctx, const int32_t *pairs, int64_t K, const acx_ef_params *params, int32_t plane /* 0..3 */,
+                          const acx_section_opts *opts, acx_alignment *out /* K x max_sections */, int32_t *n_sections /* K */,
+                          int64_t *path_off /* K x max_sections + 1, or NULL */, int32_t *cells /* cap x 2, or NULL */, int64_t cap);
+
+/* The same DP alone on a caller's binary (M, N) uint8 plot (tests), packed as acx_sw_align_binary packs it: out holds max_sections
+ * records, *n_sections their number, path_off (max_sections + 1) and cells as above with cap >= min(M, max_sections * min(M, N)).
+ * M or N above 1024: ACX_ERR_UNSUPPORTED; a value above 1 in B: ACX_ERR_INVALID; nothing is launched then. */
+int acx_sw_sections_binary(acx_ctx *ctx, const uint8_t *B, int32_t M, int32_t N, const acx_section_opts *opts,
+                           acx_alignment *out, int32_t *n_sections, int64_t *path_off, int32_t *cells, int64_t cap);
+
 /* ---- FTM2D (2D Fourier transform magnitudes, Bertin-Mahieux & Ellis) ------ */
 
 /* Constructor arguments of FTM2D (ftm2d.py:23): defaults PWR 1.96, WIN 75, C 5. */
