@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -1520,6 +1521,44 @@ static int64_t ef_align_wave_cap()
     return v >= 1 && v < 65535 ? v : 65535;
 }
 
+// What run_ef_align_jobs launches: ef_align_long_kernel (`float_path`), ef_sections_kernel (`sec`) or ef_align_kernel, on `plane`.
+// `cells`: the jobs' cells come back behind the records.  `prof_area` >= 0: a profile scope of that many cells (the caller drains).
+struct EfAlignLaunch {
+    bool float_path; int plane; const acx_section_opts *sec; bool cells; int64_t prof_area;
+};
+
+// words of nb jobs' records in a result block, in front of the cells (sections: the counts, then S records a job)
+static size_t ef_align_nrec(int nb, int S) { return S ? (size_t)nb + (size_t)acx::EFA_REC * S * nb : (size_t)acx::EFA_REC * nb; }
+
+// One launch over `jobs`, whose pairs d_efpd holds and whose direction planes take `words` u32 in all: ensures d_efdir, d_efjob and
+// d_efres, copies the jobs, launches, brings the result block back into `h_res`, and waits.
+static int run_ef_align_jobs(acx_ctx *c, const std::vector<acx::EfAlignJob> &jobs, int64_t words, const EfAlignLaunch &L, std::vector<int32_t> &h_res)
+{
+    const int nb = (int)jobs.size(), S = L.sec ? L.sec->max_sections : 0;
+    const size_t nrec = ef_align_nrec(nb, S), nres = nrec + 2 * (size_t)(jobs.back().cell_off + jobs.back().max_cells);
+    int rc;
+    if ((rc = ensure(c, c->d_efdir, (size_t)words)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efjob, (size_t)nb)) != ACX_OK) return rc;
+    if ((rc = ensure(c, c->d_efres, nres)) != ACX_OK) return rc;
+    ACX_HIP(c, hipMemcpyAsync(c->d_efjob, jobs.data(), sizeof(acx::EfAlignJob) * nb, hipMemcpyHostToDevice, c->stream));
+    {
+        std::optional<ProfScope> ps;
+        if (L.prof_area >= 0) ps.emplace(c, L.float_path ? KS_EFALIGNLONG : (S ? KS_EFSECTIONS : KS_EFALIGN), L.prof_area);
+        if (L.float_path)       // (no bitmaps: the plot from the float matrices, thresholds and tie columns; the record areas are free by now)
+            hipLaunchKernelGGL(acx::ef_align_long_kernel, dim3(nb), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_scratch, c->d_thr, c->d_efdir, c->d_efres, L.plane);
+        else if (S)
+            hipLaunchKernelGGL(acx::ef_sections_kernel, dim3(nb), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, L.plane,
+                               S, L.sec->pad, L.sec->min_score, L.sec->min_ratio);
+        else
+            hipLaunchKernelGGL(acx::ef_align_kernel, dim3(nb), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, L.plane);
+    }
+    ACX_HIP(c, hipGetLastError());
+    h_res.resize(L.cells ? nres : nrec);                             // (records and counts alone when no path is wanted)
+    ACX_HIP(c, hipMemcpyAsync(h_res.data(), c->d_efres, sizeof(int32_t) * h_res.size(), hipMemcpyDeviceToHost, c->stream));
+    ACX_HIP(c, hipStreamSynchronize(c->stream));
+    return ACX_OK;
+}
+
 static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, int64_t k0, int64_t budget, const EfAlign &aln, const float *scores,
                               bool float_path)
 {
@@ -1546,31 +1585,9 @@ static int run_ef_align_batch(acx_ctx *c, const std::vector<acx::EfPair> &pd, in
             jobs.push_back(j);
         }
         const int nb = (int)jobs.size();
-        // (sections: the counts, then S records a job)
-        const size_t nrec = S ? (size_t)nb + (size_t)acx::EFA_REC * S * nb : (size_t)acx::EFA_REC * nb, nres = nrec + 2 * (size_t)ncell;
+        const size_t nrec = ef_align_nrec(nb, S);
         int rc;
-        if ((rc = ensure(c, c->d_efdir, (size_t)words)) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_efjob, (size_t)nb)) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_efres, nres)) != ACX_OK) return rc;
-        ACX_HIP(c, hipMemcpyAsync(c->d_efjob, jobs.data(), sizeof(acx::EfAlignJob) * nb, hipMemcpyHostToDevice, c->stream));
-        if (float_path) {
-            // (the batch keeps no bitmaps: the plot from its float matrices, thresholds and tie columns; the pairs' record areas are
-            // free behind the batch's Smith-Waterman launches on this stream)
-            ProfScope ps(c, KS_EFALIGNLONG, area);
-            hipLaunchKernelGGL(acx::ef_align_long_kernel, dim3(nb), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_scratch, c->d_thr, c->d_efdir, c->d_efres, aln.plane);
-        } else if (S) {
-            ProfScope ps(c, KS_EFSECTIONS, area);
-            hipLaunchKernelGGL(acx::ef_sections_kernel, dim3(nb), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, aln.plane,
-                               S, aln.sec->pad, aln.sec->min_score, aln.sec->min_ratio);
-        } else {
-            ProfScope ps(c, KS_EFALIGN, area);
-            hipLaunchKernelGGL(acx::ef_align_kernel, dim3(nb), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, aln.plane);
-        }
-        ACX_HIP(c, hipGetLastError());
-        const size_t ncopy = aln.paths ? nres : nrec;                // (records and counts alone when no path is wanted)
-        h_res.resize(ncopy);
-        ACX_HIP(c, hipMemcpyAsync(h_res.data(), c->d_efres, sizeof(int32_t) * ncopy, hipMemcpyDeviceToHost, c->stream));
-        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        if ((rc = run_ef_align_jobs(c, jobs, words, {float_path, aln.plane, aln.sec, aln.paths != nullptr, area}, h_res)) != ACX_OK) return rc;
         for (int t = 0; t < nb; ++t) {
             const acx::EfAlignJob &j = jobs[(size_t)t];
             const int64_t k = k0 + b0 + t;
@@ -3615,7 +3632,7 @@ static int sw_align_plot(acx_ctx *c, const std::string &who, bool any_size, cons
                          int32_t *cells, int64_t cap, int64_t *n_cells)
 {
     acx::EfPair d;
-    acx::EfAlignJob job;
+    std::vector<acx::EfAlignJob> jobs(1);
     std::vector<uint32_t> W;
     std::vector<float> Cm;
     std::vector<int32_t> res;
@@ -3628,22 +3645,11 @@ static int sw_align_plot(acx_ctx *c, const std::string &who, bool any_size, cons
         if (n_cells) *n_cells = 0;
         int rc = any_size ? stage_ef_float_plot(c, who, B, M, N, d, Cm) : stage_ef_bit_plot(c, who, B, M, N, d, W);
         if (rc != ACX_OK) return rc;
-        job.pair = 0; job.max_cells = std::min(M, N); job.dir_off = 0; job.cell_off = 0;
-        const size_t nres = (size_t)acx::EFA_REC + 2 * (size_t)job.max_cells;
-        res.resize(nres);
-        if ((rc = ensure(c, c->d_efjob, (size_t)1)) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_efdir, (size_t)(any_size ? acx::ef_align_long_dir_words(M, N) : acx::ef_align_dir_words(M, d.pitchC)))) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_efres, nres)) != ACX_OK) return rc;
-        ACX_HIP(c, hipMemcpyAsync(c->d_efjob, &job, sizeof(job), hipMemcpyHostToDevice, c->stream));
-        if (any_size)
-            hipLaunchKernelGGL(acx::ef_align_long_kernel, dim3(1), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_scratch, c->d_thr, c->d_efdir, c->d_efres, 0);
-        else
-            hipLaunchKernelGGL(acx::ef_align_kernel, dim3(1), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, 0);
-        ACX_HIP(c, hipGetLastError());
-        ACX_HIP(c, hipMemcpyAsync(res.data(), c->d_efres, sizeof(int32_t) * (cells ? nres : (size_t)acx::EFA_REC), hipMemcpyDeviceToHost, c->stream));
-        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        jobs[0].pair = 0; jobs[0].max_cells = std::min(M, N); jobs[0].dir_off = 0; jobs[0].cell_off = 0;
+        const int64_t words = any_size ? acx::ef_align_long_dir_words(M, N) : acx::ef_align_dir_words(M, d.pitchC);
+        if ((rc = run_ef_align_jobs(c, jobs, words, {any_size, 0, nullptr, cells != nullptr, -1}, res)) != ACX_OK) return rc;
         std::vector<int32_t> path;
-        if ((rc = decode_ef_alignment(c, who, "", res.data(), res.data() + acx::EFA_REC, job.max_cells, nullptr, *out, cells ? &path : nullptr)) != ACX_OK)
+        if ((rc = decode_ef_alignment(c, who, "", res.data(), cells ? res.data() + acx::EFA_REC : nullptr, jobs[0].max_cells, nullptr, *out, cells ? &path : nullptr)) != ACX_OK)
             return rc;
         if (cells) {
             if (!path.empty()) memcpy(cells, path.data(), sizeof(int32_t) * path.size());
@@ -3686,7 +3692,7 @@ int acx_sw_sections_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, c
     if (!c) return ACX_ERR_INVALID;
     const std::string who = "sw_sections_binary";
     acx::EfPair d;
-    acx::EfAlignJob job;
+    std::vector<acx::EfAlignJob> jobs(1);
     std::vector<uint32_t> W;
     std::vector<int32_t> res;
     return guarded(c, [&]() -> int {
@@ -3702,21 +3708,9 @@ int acx_sw_sections_binary(acx_ctx *c, const uint8_t *B, int32_t M, int32_t N, c
                                                 " cells required (min(M, max_sections * min(M, N)))");
         if (path_off) path_off[0] = 0;
         if ((rc = stage_ef_bit_plot(c, who, B, M, N, d, W)) != ACX_OK) return rc;
-        job.pair = 0; job.max_cells = (int)room; job.dir_off = 0; job.cell_off = 0;
-        const size_t nrec = 1 + (size_t)acx::EFA_REC * S, nres = nrec + 2 * (size_t)room;
-        res.resize(nres);
-        if ((rc = ensure(c, c->d_efjob, (size_t)1)) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_efdir, (size_t)acx::ef_align_dir_words(M, d.pitchC))) != ACX_OK) return rc;
-        if ((rc = ensure(c, c->d_efres, nres)) != ACX_OK) return rc;
-        ACX_HIP(c, hipMemcpyAsync(c->d_efjob, &job, sizeof(job), hipMemcpyHostToDevice, c->stream));
-        {
-            ProfScope ps(c, KS_EFSECTIONS, (int64_t)M * N);
-            hipLaunchKernelGGL(acx::ef_sections_kernel, dim3(1), dim3(64), 0, c->stream, c->d_efpd, c->d_efjob, c->d_efbits, c->d_efdir, c->d_efres, 0,
-                               S, opts->pad, opts->min_score, opts->min_ratio);
-        }
-        ACX_HIP(c, hipGetLastError());
-        ACX_HIP(c, hipMemcpyAsync(res.data(), c->d_efres, sizeof(int32_t) * (cells ? nres : nrec), hipMemcpyDeviceToHost, c->stream));
-        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        jobs[0].pair = 0; jobs[0].max_cells = (int)room; jobs[0].dir_off = 0; jobs[0].cell_off = 0;
+        const size_t nrec = ef_align_nrec(1, S);
+        if ((rc = run_ef_align_jobs(c, jobs, acx::ef_align_dir_words(M, d.pitchC), {false, 0, opts, cells != nullptr, (int64_t)M * N}, res)) != ACX_OK) return rc;
         drain_profile(c);
         std::vector<std::vector<int32_t>> paths(cells ? (size_t)S : 0);
         if ((rc = decode_ef_sections(c, who, "", S, res[0], res.data() + 1, cells ? res.data() + nrec : nullptr, room, std::min(M, N), nullptr,

@@ -39,28 +39,28 @@ struct EfAlignJob {
 
 __host__ __device__ __forceinline__ int64_t ef_align_dir_words(int M, int pitch) { return (int64_t)M * (pitch / EFA_CPL); }
 
-// The traceback of both kernels, on ONE lane behind the fence that makes the other lanes' codes visible: from the end cell (y1, x1)
-// along the codes of `plane` (wpr words a row, word j / 16 of a row holds column j) while a cell has one, at most max_cells cells,
-// written to dst END FIRST.  Returns the number of cells and the start in (y0, x0).  The path stays inside the counted rectangle
-// (every step lowers row and column; a predecessor outside rows [2, M-2] x columns [2, N-2] has T = 0 and ends it), and the bounds
-// keep a plane that broke that promise from being read outside, or the job's cells from being written outside.
-// (The listings of both kernels are held instruction for instruction: they follow the order in which x, y and n are declared here, and
-// the record's passing by value below.)
-__device__ __forceinline__ int ef_align_traceback(const unsigned *plane, int64_t wpr, int M, int N, int y1, int x1, int max_cells, int32_t *dst,
-                                                  int &y0, int &x0)
+// The traceback of every kernel here and of ef_sections_kernel, on ONE lane behind the fence that makes the other lanes' codes
+// visible: from the end cell (y1, x1) along the codes of `plane` (wpr words a row, word j / 16 of a row holds column j) while a cell
+// has one, at most max_cells cells, written to dst END FIRST.  Returns the number of cells and the start in (y0, x0).  lo .. hi are the
+// rows the sweep behind the codes ran over (2 .. M - 2 for a whole plot; a free interval's for a section): rows lo - 1 and lo - 2 hold
+// T = 0, so a predecessor above lo ends the chain, and no row outside lo .. hi is read (in a sections run the rows above may hold the
+// codes of an earlier round).  The path stays inside rows [lo, hi] x columns [2, N-2] (every step lowers row and column), and the
+// bounds keep a plane that broke that promise from being read outside, or the job's cells from being written outside.
+__device__ __forceinline__ int ef_align_traceback(const unsigned *plane, int64_t wpr, int lo, int hi, int N, int y1, int x1, int max_cells,
+                                                  int32_t *dst, int &y0, int &x0)
 {
     auto code_at = [&](int yy, int xx) -> unsigned {
         const unsigned wd = __hip_atomic_load(plane + (size_t)yy * wpr + (xx >> 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return (wd >> (2 * (xx & 15))) & 3u;
     };
     int x = x1, y = y1, n = 0;
-    if (y >= 2 && y <= M - 2 && x >= 2 && x <= N - 2) {
+    if (y >= lo && y <= hi && x >= 2 && x <= N - 2) {
         unsigned code = code_at(y, x);
         while (code != 0u && n < max_cells) {
             dst[2 * n] = y; dst[2 * n + 1] = x;
             ++n;
             const int py = y - (code == 2u ? 2 : 1), px = x - (code == 3u ? 2 : 1);
-            if (py < 2 || px < 2) break;                             // rows / columns 0, 1: T = 0
+            if (py < lo || px < 2) break;                            // above the swept rows, or columns 0, 1: T = 0
             code = code_at(py, px);                                  // 0: T == 0 there, (y, x) was the start
             if (code != 0u) { y = py; x = px; }
         }
@@ -75,6 +75,98 @@ __device__ __forceinline__ void ef_align_store(int32_t *rec, const acx_alignment
     rec[0] = __float_as_int(a.score); rec[1] = a.q0; rec[2] = a.r0; rec[3] = a.q1; rec[4] = a.r1; rec[5] = n;
 }
 
+// The sweep of ef_align_kernel and of ef_sections_kernel (ef_sections_kernels.hpp): rows lo .. hi of a job's bitmap (`rows`: M rows of
+// pitch / 8 bytes), started from the BITS of rows lo - 1 and lo - 2 -- T = 0 there, U = delta(B): what rows 0 and 1 hold, and what an
+// excluded row of a sections run holds.  Writes rows lo .. hi of the direction plane `my_dir` and returns, the same in every lane, the
+// maximum in tenths and the counted cell, first in row-major order, that attains it (row * EF_MAXNB + column; 0x7fffffff with a
+// maximum of 0).  2 <= lo, hi <= M - 2; no row at all (hi < lo) gives (0, 0x7fffffff).
+struct EfBest { int tenths, cell; };
+
+__device__ __forceinline__ EfBest ef_align_sweep(const unsigned char *rows, int M, int N, int pitch, unsigned *my_dir, int lo, int hi)
+{
+    constexpr int CPL = EFA_CPL;
+    const int lane = threadIdx.x;
+    const int rowbytes = pitch >> 3, wpr = pitch / CPL;
+    const int j0 = CPL * lane;
+    const bool inrow = j0 < pitch;
+    auto load = [&](int row) -> unsigned {
+        const int r = row < M ? row : M - 1;                         // (rows past the last one: a valid address, never used)
+        return inrow ? (unsigned)*reinterpret_cast<const unsigned short *>(rows + (size_t)r * rowbytes + 2 * lane) : 0u;
+    };
+    // A cell is held as V = 4 (U + 8) (U >= -7: positive; the two low bits are free), so that the maximum of the three
+    // predecessors AND which one it is come from one v_max3 of V + 2, V + 1, V + 0 in the order (i-1, j-1), (i-2, j-1),
+    // (i-1, j-2): equal U's leave the first with the largest key.  With base = key & ~3 = 4 (max U + 8):
+    //   4 T = max(0, base - 32 +- 40),  new V = 4 T + (B ? 32 : 4),  code = 3 - (key & 3) where T > 0.
+    // valid: bit e = column j0 + e is counted (2 <= j <= N - 2).  T is forced to 0 elsewhere: columns 0, 1 by the recursion's
+    // definition, columns right of N - 2 because they feed only columns further right -- so a cell with T > 0 is a counted one.
+    unsigned valid = 0u;
+#pragma unroll
+    for (int e = 0; e < CPL; ++e) valid |= (j0 + e >= 2 && j0 + e <= N - 2) ? (1u << e) : 0u;
+    int V1[CPL], V2[CPL];                                            // rows i-1, i-2
+    {
+        const unsigned w0 = load(lo - 2), w1 = load(lo - 1);         // T = 0 there, U = delta(B)
+#pragma unroll
+        for (int e = 0; e < CPL; ++e) {
+            V2[e] = 4 + 28 * (int)((w0 >> e) & 1u);
+            V1[e] = 4 + 28 * (int)((w1 >> e) & 1u);
+        }
+    }
+    // The running maximum of a lane as ONE integer, (4 T) << 14 | (1023 - i) << 4 | (15 - e): larger T first, then the earlier
+    // row, then the smaller column (4 T <= 40 960 < 2^16: 30 bits).
+    int best_key = 0;
+    // one row: VA = row i-1, VB = row i-2 (overwritten with row i, from the right: cell e reads VB[e - 1] before it is replaced)
+    auto dp_row = [&](int i, unsigned wb, int (&VA)[CPL], int (&VB)[CPL]) {
+        const int a1 = lane_prev_i(VA[CPL - 1]), a2 = lane_prev_i(VA[CPL - 2]), b1 = lane_prev_i(VB[CPL - 1]);
+        const int row_key = (EF_MAXNB - 1 - i) << 4;
+        unsigned codes = 0u;
+        // (opaque per row: sixteen loop-invariant lane masks hoisted out of the row loop would take 32 SGPRs and spill)
+        int vm = (int)valid;
+        asm volatile("" : "+v"(vm));
+#pragma unroll
+        for (int e = CPL - 1; e >= 0; --e) {
+            const int k2 = ((e >= 1) ? VA[e - 1] : a1) + 2;                               // (i-1, j-1)
+            const int k3 = ((e >= 1) ? VB[e - 1] : b1) + 1;                               // (i-2, j-1)
+            const int k4 = (e >= 2) ? VA[e - 2] : (e == 1 ? a1 : a2);                     // (i-1, j-2)
+            const int key = max(max(k2, k3), k4);
+            const int bit = (int)((wb >> e) & 1u);
+            int t4 = (key & ~3) - 72 + 80 * bit;
+            t4 = max(t4, 0) & __builtin_amdgcn_sbfe(vm, e, 1);                    // (sbfe of one bit: 0 or -1)
+            VB[e] = t4 + 4 + 28 * bit;
+            const unsigned code = t4 > 0 ? 3u - (unsigned)(key & 3) : 0u;
+            codes |= code << (2 * e);
+            best_key = max(best_key, ((t4 << 14) | (15 - e)) | row_key);
+        }
+        if (inrow) my_dir[(size_t)i * wpr + lane] = codes;
+    };
+    // rows in flight ahead of the recursion, as in sw_bits_h16_kernel.  The ring starts at row lo, whatever its row & 7, and the
+    // register rows only alternate, so lo may have either parity: row lo - 1 is V1, and SW_PF is even
+    constexpr int SW_PF = 8;
+    unsigned ring[SW_PF];
+#pragma unroll
+    for (int sl = 0; sl < SW_PF; ++sl) ring[sl] = load(lo + sl);
+    for (int i0 = lo; i0 <= hi; i0 += SW_PF) {
+#pragma unroll
+        for (int sl = 0; sl < SW_PF; ++sl) {
+            const int i = i0 + sl;
+            if (i <= hi) {                                           // wave-uniform
+                const unsigned wb = ring[sl];
+                ring[sl] = load(i + SW_PF);
+                if (sl & 1) dp_row(i, wb, V2, V1); else dp_row(i, wb, V1, V2);
+            }
+        }
+    }
+    // the maximum and, among equal maxima, the smallest cell index (a plain maximum would lose which lane's cell comes first)
+    EfBest r;
+    r.tenths = best_key >> 16;                                       // (4 T) >> 2
+    r.cell = r.tenths > 0 ? (EF_MAXNB - 1 - ((best_key >> 4) & (EF_MAXNB - 1))) * EF_MAXNB + j0 + 15 - (best_key & 15) : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int ob = __shfl_xor(r.tenths, o, 64), oc = __shfl_xor(r.cell, o, 64);
+        if (ob > r.tenths || (ob == r.tenths && oc < r.cell)) { r.tenths = ob; r.cell = oc; }
+    }
+    return r;
+}
+
 __global__ __launch_bounds__(64) void ef_align_kernel(const EfPair *__restrict__ pd, const EfAlignJob *__restrict__ jobs,
                                                       const unsigned *__restrict__ bits, unsigned *dir,
                                                       int32_t *__restrict__ res, int plane)
@@ -82,7 +174,6 @@ __global__ __launch_bounds__(64) void ef_align_kernel(const EfPair *__restrict__
     // res: EFA_REC words per job -- the acx_alignment record (score's bits, q0, r0, q1, r1) and the number of cells -- then the
     // cells of all jobs (job.cell_off), so that one copy brings a chunk's results back
     int32_t *cells = res + (size_t)EFA_REC * gridDim.x;
-    constexpr int CPL = EFA_CPL;
     const int lane = threadIdx.x;
     const EfAlignJob job = jobs[blockIdx.x];
     const EfPair P = pd[job.pair];
@@ -92,90 +183,16 @@ __global__ __launch_bounds__(64) void ef_align_kernel(const EfPair *__restrict__
     int n = 0;
     if (M >= 4 && N >= 4) {
         const unsigned char *rows = reinterpret_cast<const unsigned char *>(bits + P.offB + (int64_t)plane * M * (pitch >> 5));
-        const int rowbytes = pitch >> 3, wpr = pitch / CPL;
         unsigned *my_dir = dir + job.dir_off;
-        const int j0 = CPL * lane;
-        const bool inrow = j0 < pitch;
-        auto load = [&](int row) -> unsigned {
-            const int r = row < M ? row : M - 1;                     // (rows past the last one: a valid address, never used)
-            return inrow ? (unsigned)*reinterpret_cast<const unsigned short *>(rows + (size_t)r * rowbytes + 2 * lane) : 0u;
-        };
-        // A cell is held as V = 4 (U + 8) (U >= -7: positive; the two low bits are free), so that the maximum of the three
-        // predecessors AND which one it is come from one v_max3 of V + 2, V + 1, V + 0 in the order (i-1, j-1), (i-2, j-1),
-        // (i-1, j-2): equal U's leave the first with the largest key.  With base = key & ~3 = 4 (max U + 8):
-        //   4 T = max(0, base - 32 +- 40),  new V = 4 T + (B ? 32 : 4),  code = 3 - (key & 3) where T > 0.
-        // valid: bit e = column j0 + e is counted (2 <= j <= N - 2).  T is forced to 0 elsewhere: columns 0, 1 by the recursion's
-        // definition, columns right of N - 2 because they feed only columns further right -- so a cell with T > 0 is a counted one.
-        unsigned valid = 0u;
-#pragma unroll
-        for (int e = 0; e < CPL; ++e) valid |= (j0 + e >= 2 && j0 + e <= N - 2) ? (1u << e) : 0u;
-        int V1[CPL], V2[CPL];                                        // rows i-1, i-2
-        {
-            const unsigned w0 = load(0), w1 = load(1);               // rows 0 and 1: T = 0, U = delta(B)
-#pragma unroll
-            for (int e = 0; e < CPL; ++e) {
-                V2[e] = 4 + 28 * (int)((w0 >> e) & 1u);
-                V1[e] = 4 + 28 * (int)((w1 >> e) & 1u);
-            }
-        }
-        // The running maximum of a lane as ONE integer, (4 T) << 14 | (1023 - i) << 4 | (15 - e): larger T first, then the earlier
-        // row, then the smaller column (4 T <= 40 960 < 2^16: 30 bits).
-        int best_key = 0;
-        // one row: VA = row i-1, VB = row i-2 (overwritten with row i, from the right: cell e reads VB[e - 1] before it is replaced)
-        auto dp_row = [&](int i, unsigned wb, int (&VA)[CPL], int (&VB)[CPL]) {
-            const int a1 = lane_prev_i(VA[CPL - 1]), a2 = lane_prev_i(VA[CPL - 2]), b1 = lane_prev_i(VB[CPL - 1]);
-            const int row_key = (EF_MAXNB - 1 - i) << 4;
-            unsigned codes = 0u;
-            // (opaque per row: sixteen loop-invariant lane masks hoisted out of the row loop would take 32 SGPRs and spill)
-            int vm = (int)valid;
-            asm volatile("" : "+v"(vm));
-#pragma unroll
-            for (int e = CPL - 1; e >= 0; --e) {
-                const int k2 = ((e >= 1) ? VA[e - 1] : a1) + 2;                           // (i-1, j-1)
-                const int k3 = ((e >= 1) ? VB[e - 1] : b1) + 1;                           // (i-2, j-1)
-                const int k4 = (e >= 2) ? VA[e - 2] : (e == 1 ? a1 : a2);                 // (i-1, j-2)
-                const int key = max(max(k2, k3), k4);
-                const int bit = (int)((wb >> e) & 1u);
-                int t4 = (key & ~3) - 72 + 80 * bit;
-                t4 = max(t4, 0) & __builtin_amdgcn_sbfe(vm, e, 1);                // (sbfe of one bit: 0 or -1)
-                VB[e] = t4 + 4 + 28 * bit;
-                const unsigned code = t4 > 0 ? 3u - (unsigned)(key & 3) : 0u;
-                codes |= code << (2 * e);
-                best_key = max(best_key, ((t4 << 14) | (15 - e)) | row_key);
-            }
-            if (inrow) my_dir[(size_t)i * wpr + lane] = codes;
-        };
-        constexpr int SW_PF = 8;                                     // rows in flight ahead of the recursion, as in sw_bits_h16_kernel
-        unsigned ring[SW_PF];
-#pragma unroll
-        for (int sl = 0; sl < SW_PF; ++sl) ring[sl] = load(2 + sl);
-        for (int i0 = 2; i0 <= M - 2; i0 += SW_PF) {
-#pragma unroll
-            for (int sl = 0; sl < SW_PF; ++sl) {
-                const int i = i0 + sl;
-                if (i <= M - 2) {                                    // wave-uniform
-                    const unsigned wb = ring[sl];
-                    ring[sl] = load(i + SW_PF);
-                    if (sl & 1) dp_row(i, wb, V2, V1); else dp_row(i, wb, V1, V2);      // (i0 and SW_PF are even: row i-1 is V1 for even sl)
-                }
-            }
-        }
-        // the maximum and, among equal maxima, the smallest cell index (a plain maximum would lose which lane's cell comes first)
-        int best = best_key >> 16;                                   // tenths: (4 T) >> 2
-        int best_cell = best > 0 ? (EF_MAXNB - 1 - ((best_key >> 4) & (EF_MAXNB - 1))) * EF_MAXNB + j0 + 15 - (best_key & 15) : 0x7fffffff;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const int ob = __shfl_xor(best, o, 64), oc = __shfl_xor(best_cell, o, 64);
-            if (ob > best || (ob == best && oc < best_cell)) { best = ob; best_cell = oc; }
-        }
+        const EfBest b = ef_align_sweep(rows, M, N, pitch, my_dir, 2, M - 2);
         // the traceback reads the whole plane: same wave, but other lanes' stores, through memory
         __threadfence();
-        if (lane == 0 && best > 0) {
-            int y = best_cell / EF_MAXNB, x = best_cell % EF_MAXNB;
-            n = ef_align_traceback(my_dir, wpr, M, N, y, x, job.max_cells, cells + 2 * job.cell_off, y, x);
-            a.score = (float)best / 10.0f;                           // (a positive score without a cell: the driver reports it)
+        if (lane == 0 && b.tenths > 0) {
+            int y = b.cell / EF_MAXNB, x = b.cell % EF_MAXNB;
+            n = ef_align_traceback(my_dir, pitch / EFA_CPL, 2, M - 2, N, y, x, job.max_cells, cells + 2 * job.cell_off, y, x);
+            a.score = (float)b.tenths / 10.0f;                       // (a positive score without a cell: the driver reports it)
             if (n > 0) {
-                a.q1 = best_cell / EF_MAXNB; a.r1 = best_cell % EF_MAXNB;
+                a.q1 = b.cell / EF_MAXNB; a.r1 = b.cell % EF_MAXNB;
                 a.q0 = y; a.r0 = x;
             }
         }
@@ -317,7 +334,7 @@ __global__ __launch_bounds__(64) void ef_align_long_kernel(const EfPair *__restr
         }
         if (lane == 0 && bT > 0) {
             int y = bRow, x = bCol;
-            n = ef_align_traceback(my_dir, wpr, M, N, y, x, job.max_cells, cells + 2 * job.cell_off, y, x);
+            n = ef_align_traceback(my_dir, wpr, 2, M - 2, N, y, x, job.max_cells, cells + 2 * job.cell_off, y, x);
             a.score = (float)bT / 10.0f;                             // sw_long_kernel's expression: the same bits
             if (n > 0) {
                 a.q1 = bRow; a.r1 = bCol;

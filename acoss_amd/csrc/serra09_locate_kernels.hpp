@@ -13,8 +13,8 @@
 //   start  S[i][j] = (i, j) where a path starts, S[pred] elsewhere; reported: S[end].
 // S is ONE u32 per cell, i * Mr + j: the host refuses a pair whose cells, plus one strip, reach 2^32.
 //
-// qmax_sections_kernel (serra09_sections_kernels.hpp) holds a COPY of this kernel's strip loop -- load_row, dp_row
-// and the wave's butterfly, line for line -- run per free interval of rows: a change to either is a change to both.
+// The sweep itself is qmax_locate_sweep: this kernel runs it once over rows 2 .. Me - 1, qmax_sections_kernel
+// (serra09_sections_kernels.hpp) once per free interval of rows.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -59,24 +59,24 @@ __device__ __forceinline__ unsigned loc_sel_eq0(unsigned k, unsigned x, unsigned
     return r;
 }
 
+// The sweep of qmax_locate_kernel and qmax_sections_kernel: rows lo .. hi (2 <= lo, hi <= Me - 1) of the pair's recurrence bitmap in
+// strips of 2048 columns, started from two ZERO rows and zero seam records -- rows 0 and 1 of Q, and every excluded row of a sections
+// run, are zero.  Me x Ne: the DP's extent; bnd: the pair's seam records (two buffers of P.Mq; unused with one strip).  Returns, the
+// same in every lane, max Q over these rows, the row-major first cell that attains it and that cell's path start (all 0 where no
+// cell is positive).  A strip ends in __threadfence(): the next strip, and a later sweep over the same records, go through memory.
+struct LocBest { float best; unsigned end, start; };
+
 template <bool EQG>
-__global__ __launch_bounds__(64) void qmax_locate_kernel(const PairDesc *__restrict__ pd,
-                                                         const unsigned long long *__restrict__ bits,
-                                                         LocSeam *__restrict__ seam, const int64_t *__restrict__ seam_off,
-                                                         acx_alignment *__restrict__ out,
-                                                         float go, float ge, int dp_start)
+__device__ __forceinline__ LocBest qmax_locate_sweep(const PairDesc &P, const unsigned long long *bits, LocSeam *bnd, int Me, int Ne,
+                                                     float go, float ge, int lo, int hi)
 {
     constexpr int CPL = LOC_CPL;
     constexpr int NP = EQG ? 1 : CPL;
     const int lane = threadIdx.x;
-    const PairDesc P = pd[blockIdx.x];
-    int Me = P.Mq, Ne = P.Mr;
-    if (dp_start == 3) { Me -= 1; Ne -= 1; }       // cell (i, j) of the oracle reads R[i-1][j-1]: the same DP on the plot less its last row / column
     const int ndw = 2 * P.nw;
     const unsigned *rows = reinterpret_cast<const unsigned *>(bits + P.offT);
     const unsigned W = (unsigned)P.Mr;             // S = i * W + j
     const int nstrips = loc_strips(Ne);
-    LocSeam *bnd = nstrips > 1 ? seam + seam_off[blockIdx.x] : nullptr;
     float best = 0.0f;                             // this lane's first maximum so far, its cell and its path start
     unsigned bend = 0u, bstart = 0u;
 
@@ -108,13 +108,8 @@ __global__ __launch_bounds__(64) void qmax_locate_kernel(const PairDesc *__restr
                 if (has1) d1 = r[dw0 + 1];
             }
         };
-        if (more && lane == 63) {                  // rows 0 and 1 of Q are zero
-            const LocSeam z = {0.0f, 0.0f, 0.0f, 0.0f, 0u, 0u, 0u, 0u};
-            if (Me > 0) bout[0] = z;
-            if (Me > 1) bout[1] = z;
-        }
-        LocSeam recA = {0.0f, 0.0f, 0.0f, 0.0f, 0u, 0u, 0u, 0u}, recB = recA;      // the left strip's rows i - 1 and i - 2
-        if (s > 0 && Me > 2) { recB = bin[0]; recA = bin[1]; }
+        // the left strip's rows i - 1 and i - 2: zero above row lo, its records cover rows lo .. hi only
+        LocSeam recA = {0.0f, 0.0f, 0.0f, 0.0f, 0u, 0u, 0u, 0u}, recB = recA;
 
         // One DP row: QA / SA / PA = row i-1, QB / SB / PB = row i-2 (overwritten with row i), descending column order
         auto dp_row = [&](int i, unsigned d0, unsigned d1, float (&QA)[CPL], float (&QB)[CPL], unsigned (&SA)[CPL], unsigned (&SB)[CPL],
@@ -198,14 +193,14 @@ __global__ __launch_bounds__(64) void qmax_locate_kernel(const PairDesc *__restr
             recB = recA; recA = recN;
         };
 
-        unsigned a0, a1, b0, b1;
-        load_row(2, a0, a1); load_row(3, b0, b1);
-        for (int i = 2; i < Me; i += 2) {
+        unsigned a0, a1, b0, b1;                   // lo may have either parity: the register rows only alternate
+        load_row(lo, a0, a1); load_row(lo + 1, b0, b1);
+        for (int i = lo; i <= hi; i += 2) {
             unsigned n0, n1;
             load_row(i + 2, n0, n1);
             dp_row(i, a0, a1, Q1, Q2, S1, S2, P1, P2);
             a0 = n0; a1 = n1;
-            if (i + 1 < Me) {
+            if (i + 1 <= hi) {
                 load_row(i + 3, n0, n1);
                 dp_row(i + 1, b0, b1, Q2, Q1, S2, S1, P2, P1);
                 b0 = n0; b1 = n1;
@@ -223,12 +218,28 @@ __global__ __launch_bounds__(64) void qmax_locate_kernel(const PairDesc *__restr
         const unsigned oe = loc_shfl_xor_u(bend, m), os = loc_shfl_xor_u(bstart, m);
         if (ov > best || (ov == best && oe < bend)) { best = ov; bend = oe; bstart = os; }
     }
-    if (lane == 0) {
+    return {best, bend, bstart};
+}
+
+template <bool EQG>
+__global__ __launch_bounds__(64) void qmax_locate_kernel(const PairDesc *__restrict__ pd,
+                                                         const unsigned long long *__restrict__ bits,
+                                                         LocSeam *__restrict__ seam, const int64_t *__restrict__ seam_off,
+                                                         acx_alignment *__restrict__ out,
+                                                         float go, float ge, int dp_start)
+{
+    const PairDesc P = pd[blockIdx.x];
+    int Me = P.Mq, Ne = P.Mr;
+    if (dp_start == 3) { Me -= 1; Ne -= 1; }       // cell (i, j) of the oracle reads R[i-1][j-1]: the same DP on the plot less its last row / column
+    LocSeam *bnd = loc_strips(Ne) > 1 ? seam + seam_off[blockIdx.x] : nullptr;
+    const LocBest r = qmax_locate_sweep<EQG>(P, bits, bnd, Me, Ne, go, ge, 2, Me - 1);
+    if (threadIdx.x == 0) {
+        const unsigned W = (unsigned)P.Mr;
         acx_alignment a;
-        a.score = best;
-        if (best > 0.0f) {
-            a.q0 = (int32_t)(bstart / W); a.r0 = (int32_t)(bstart % W);
-            a.q1 = (int32_t)(bend / W); a.r1 = (int32_t)(bend % W);
+        a.score = r.best;
+        if (r.best > 0.0f) {
+            a.q0 = (int32_t)(r.start / W); a.r0 = (int32_t)(r.start % W);
+            a.q1 = (int32_t)(r.end / W); a.r1 = (int32_t)(r.end % W);
         } else {
             a.q0 = -1; a.r0 = -1; a.q1 = -1; a.r1 = -1;
         }
