@@ -1061,32 +1061,37 @@ class Context(object):
                                                ctypes.byref(sc)))
         return bits, float(sc.value)
 
-    def _align_list(self, export, pairs, extra, paths, cap, cap_rule):
-        """A list call of the align family: export(ctx, pairs, K, *extra, out, path_off, cells, cap).  The records alone (NULL path
-        pointers), or with paths=True (records, offsets (K + 1,) int64, cells (offsets[-1], 2) int32); cap None: cap_rule(pairs)."""
+    def _align_list(self, export, pairs, extra, paths=None, cap=None, cap_rule=None):
+        """A list call of the align family: export(ctx, pairs, K, *extra, out[, path_off, cells, cap]).  paths None: the export takes
+        the records alone; False: NULL path pointers and cap 0; True: (records, offsets (K + 1,) int64, cells (offsets[-1], 2) int32);
+        cap None: cap_rule(pairs)."""
         pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
         out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
         if paths and cap is None:
             cap = cap_rule(pairs)                   # (may refuse: before the library is touched)
         head = (self._h, _iptr(pairs), len(pairs)) + tuple(extra) + (out.ctypes.data,)
         if not paths:
-            self._check(getattr(self._L, export)(*head, None, None, 0))
+            self._check(getattr(self._L, export)(*head) if paths is None else getattr(self._L, export)(*head, None, None, 0))
             return out
         off = np.zeros(len(pairs) + 1, np.int64)
         cells = np.zeros((max(int(cap), 1), 2), np.int32)
         self._check(getattr(self._L, export)(*head, off.ctypes.data, cells.ctypes.data, int(cap)))
         return out, off, cells[:off[-1]].copy()
 
-    def _align_plot(self, export, P, what, extra=(), paths=True, cap=None, n_first=False):
-        """A plot call of the align family on a binary (M, N) plot `P` (`what`: its name in the method's signature):
-        export(ctx, P, M, N, *extra, out, ...).  paths None: the export takes the record alone; False: NULL path pointers and cap 0;
-        True: (record (1,), cells (L, 2) int32), the tail being (n_cells, cells, cap) with n_first, else (cells, cap, n_cells).
-        cap: default min(M, N)."""
+    def _plot_head(self, export, P, what):
+        """A binary (M, N) plot `P` (`what`: its name in the method's signature) -> (the uint8 array, (ctx, P, M, N))."""
         P = np.ascontiguousarray(P, dtype=np.uint8)
         if P.ndim != 2:
             raise ValueError("%s: %s must be (M, N), got shape %s" % (export[len("acx_"):], what, P.shape,))
+        return P, (self._h, P.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), P.shape[0], P.shape[1])
+
+    def _align_plot(self, export, P, what, extra=(), paths=True, cap=None, n_first=False):
+        """A plot call of the align family: export(ctx, P, M, N, *extra, out, ...).  paths None: the export takes the record alone;
+        False: NULL path pointers and cap 0; True: (record (1,), cells (L, 2) int32), the tail being (n_cells, cells, cap) with
+        n_first, else (cells, cap, n_cells).  cap: default min(M, N)."""
+        P, head = self._plot_head(export, P, what)
         out = np.zeros(1, ALIGNMENT_DTYPE)
-        args = (self._h, P.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), P.shape[0], P.shape[1]) + tuple(extra) + (out.ctypes.data,)
+        args = head + tuple(extra) + (out.ctypes.data,)
         fn = getattr(self._L, export)
         if not paths:
             self._check(fn(*args) if paths is None else fn(*args, None, 0, None))
@@ -1099,20 +1104,52 @@ class Context(object):
         self._check(fn(*(args + tail)))
         return out, cells[:n.value].copy()
 
-    def _ef_cap(self, pairs, unseen):
-        """The sum of min(M_k, N_k) over the list from the block counts of the pool this object uploaded; unseen(pairs) for a pool it
-        did not see.  (A list the library refuses -- an index out of range -- is refused before it looks at cap.)"""
+    def _sections(self, export, head, K, o, paths, cap):
+        """The sections call itself over K pairs: export(*head, opts, out, counts, path_off, cells, cap) -> (records (K, S), counts (K,))
+        and with paths (records, counts, offsets (K S + 1,), cells cut at offsets[-1]); without, NULL path pointers and cap 0."""
+        S = o.max_sections
+        out, n = np.zeros((K, S), ALIGNMENT_DTYPE), np.zeros(K, np.int32)
+        tail = (ctypes.byref(o), out.ctypes.data, n.ctypes.data)
+        if not paths:
+            self._check(getattr(self._L, export)(*head, *tail, None, None, 0))
+            return out, n
+        off, cells = np.zeros(K * S + 1, np.int64), np.zeros((max(int(cap), 1), 2), np.int32)
+        self._check(getattr(self._L, export)(*head, *tail, off.ctypes.data, cells.ctypes.data, int(cap)))
+        return out, n, off, cells[:off[-1]].copy()
+
+    def _sections_list(self, export, pairs, extra, o, paths, cap, cap_rule):
+        """A list call of the sections family: export(ctx, pairs, K, *extra, opts, ...); cap None: cap_rule(pairs, max_sections)."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        if paths and cap is None:
+            cap = cap_rule(pairs, o.max_sections)
+        return self._sections(export, (self._h, _iptr(pairs), len(pairs)) + tuple(extra), len(pairs), o, paths, cap)
+
+    def _sections_plot(self, export, P, what, extra, o, paths, cap):
+        """A plot call of the sections family: export(ctx, P, M, N, *extra, opts, ...) -> (records (S,), count[, offsets (S + 1,), cells]).
+        cap: default min(M, S min(M, N))."""
+        P, head = self._plot_head(export, P, what)
+        if paths and cap is None:
+            cap = min(P.shape[0], o.max_sections * min(P.shape))
+        got = self._sections(export, head + tuple(extra), 1, o, paths, cap)
+        return (got[0][0], int(got[1][0])) + got[2:]
+
+    def _ef_cap(self, pairs, unseen, S=1):
+        """The sum of min(M_k, S min(M_k, N_k)) over the list -- S sections a pair; S = 1: min(M_k, N_k) -- from the block counts of the
+        pool this object uploaded; unseen(pairs) for a pool it did not see.  (A list the library refuses -- an index out of range -- is
+        refused before it looks at cap.)"""
         nb = getattr(self, "ef_blocks", None)
         if nb is None:
             return unseen(pairs)
         nb = np.asarray(nb, dtype=np.int64)
         ok = np.all((pairs >= 0) & (pairs < len(nb)), axis=1) if len(pairs) else np.zeros(0, bool)
-        return int(np.minimum(nb[pairs[ok, 0]], nb[pairs[ok, 1]]).sum())
+        M, N = nb[pairs[ok, 0]], nb[pairs[ok, 1]]
+        return int(np.minimum(M, S * np.minimum(M, N)).sum())
 
-    def _serra09_cap(self, pairs, p):
-        """The sum of min(Mq_k, Mr_k) over the list (acx_serra09_embed_len); an index out of range counts nothing, as in _ef_cap."""
+    def _serra09_cap(self, pairs, p, S=1):
+        """The sum of min(Mq_k, S min(Mq_k, Mr_k)) over the list (acx_serra09_embed_len); an index out of range counts nothing, as in
+        _ef_cap."""
         Ms = {t: max(self.serra09_embed_len(self.lengths[t], p), 0) for t in {int(t) for t in pairs.ravel()} if 0 <= t < len(self.lengths)}
-        return sum(min(Ms.get(int(i), 0), Ms.get(int(j), 0)) for i, j in pairs)
+        return sum(min(Ms.get(int(i), 0), S * min(Ms.get(int(i), 0), Ms.get(int(j), 0))) for i, j in pairs)
 
     def ef_align(self, pairs, kappa=0.1, K=10, plane=3, paths=False, cap=None):
         """WHERE the Smith-Waterman alignment of every (query, reference) pair lies in one binarised matrix (acx_ef_align; plane
@@ -1378,10 +1415,7 @@ class Context(object):
         (ALIGNMENT_DTYPE) -- score = what serra09_pairs returns, (q0, r0) the start and (q1, r1) the end of the path in
         embedded frames (rows / columns of the recurrence plot); a pair without a match: score 0 and -1 four times."""
         p = params or serra09_params()
-        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
-        self._check(self._L.acx_serra09_align(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), out.ctypes.data))
-        return out
+        return self._align_list("acx_serra09_align", pairs, (ctypes.byref(p),))
 
     def qmax_locate_binary(self, R, params=None):
         """The same for a given binary (M, N) cross recurrence plot (acx_qmax_locate_binary): a (1,) structured array."""
@@ -1402,14 +1436,6 @@ class Context(object):
         p = params or serra09_params()
         return self._align_plot("acx_qmax_path_binary", R, "R", (ctypes.byref(p),), cap=cap, n_first=True)
 
-    def _sections_out(self, K, S, paths, cap):
-        """The buffers of a sections call over K pairs: records (K, S), counts (K,), offsets (K S + 1,) and cells (cap, 2) or None."""
-        out = np.zeros((K, S), ALIGNMENT_DTYPE)
-        n = np.zeros(K, np.int32)
-        if not paths:
-            return out, n, None, None
-        return out, n, np.zeros(K * S + 1, np.int64), np.zeros((max(int(cap), 1), 2), np.int32)
-
     def serra09_align_sections(self, pairs, params=None, opts=None, paths=False, cap=None):
         """EVERY matched section of every (query, reference) pair (acx_serra09_align_sections): (records, counts)
         -- records a (K, max_sections) structured array (ALIGNMENT_DTYPE), section 0 first, the no-match record behind the counts[k]
@@ -1418,32 +1444,14 @@ class Context(object):
         defaults).  cap: default the bound the library checks, the sum of min(Mq_k, max_sections * min(Mq_k, Mr_k))."""
         p = params or serra09_params()
         o = opts or section_opts("serra09_align_sections")
-        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        if paths and cap is None:
-            Ms = {t: max(self.serra09_embed_len(self.lengths[t], p), 0) for t in {int(t) for t in pairs.ravel()} if 0 <= t < len(self.lengths)}
-            cap = sum(min(Ms.get(int(i), 0), o.max_sections * min(Ms.get(int(i), 0), Ms.get(int(j), 0))) for i, j in pairs)
-        out, n, off, cells = self._sections_out(len(pairs), o.max_sections, paths, cap)
-        self._check(self._L.acx_serra09_align_sections(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), ctypes.byref(o), out.ctypes.data,
-                                                       n.ctypes.data, off.ctypes.data if paths else None,
-                                                       cells.ctypes.data if paths else None, int(cap) if paths else 0))
-        return (out, n, off, cells[:off[-1]].copy()) if paths else (out, n)
+        return self._sections_list("acx_serra09_align_sections", pairs, (ctypes.byref(p),), o, paths, cap, lambda pr, S: self._serra09_cap(pr, p, S))
 
     def qmax_sections_binary(self, R, params=None, opts=None, paths=True, cap=None):
         """The same DP alone on a given binary (M, N) plot (acx_qmax_sections_binary): (records (max_sections,), count) and with
         paths=True (records, count, offsets (max_sections + 1,), cells).  cap: default min(M, max_sections * min(M, N))."""
         p = params or serra09_params()
         o = opts or section_opts("qmax_sections_binary")
-        R = np.ascontiguousarray(R, dtype=np.uint8)
-        if R.ndim != 2:
-            raise ValueError("qmax_sections_binary: R must be (M, N), got shape %s" % (R.shape,))
-        if paths and cap is None:
-            cap = min(R.shape[0], o.max_sections * min(R.shape))
-        out, n, off, cells = self._sections_out(1, o.max_sections, paths, cap)
-        self._check(self._L.acx_qmax_sections_binary(self._h, R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), R.shape[0], R.shape[1],
-                                                     ctypes.byref(p), ctypes.byref(o), out.ctypes.data, n.ctypes.data,
-                                                     off.ctypes.data if paths else None, cells.ctypes.data if paths else None,
-                                                     int(cap) if paths else 0))
-        return (out[0], int(n[0]), off, cells[:off[-1]].copy()) if paths else (out[0], int(n[0]))
+        return self._sections_plot("acx_qmax_sections_binary", R, "R", (ctypes.byref(p),), o, paths, cap)
 
     def ef_align_sections(self, pairs, kappa=0.1, K=10, plane=3, opts=None, paths=False, cap=None):
         """EVERY matched section of every (query, reference) pair in one binarised matrix (acx_ef_align_sections, DESIGN.md section
@@ -1453,46 +1461,21 @@ class Context(object):
         uploaded, the bound of any list the library accepts."""
         p = EfParams(float(kappa), int(K))
         o = opts or section_opts("ef_align_sections")
-        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        if paths and cap is None:
-            nb = getattr(self, "ef_blocks", None)
-            if nb is None:
-                cap = 1024 * len(pairs)
-            else:
-                nb = np.asarray(nb, dtype=np.int64)
-                ok = np.all((pairs >= 0) & (pairs < len(nb)), axis=1) if len(pairs) else np.zeros(0, bool)
-                M, N = nb[pairs[ok, 0]], nb[pairs[ok, 1]]
-                cap = int(np.minimum(M, o.max_sections * np.minimum(M, N)).sum())
-        out, n, off, cells = self._sections_out(len(pairs), o.max_sections, paths, cap)
-        self._check(self._L.acx_ef_align_sections(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), ctypes.byref(o),
-                                                  out.ctypes.data, n.ctypes.data, off.ctypes.data if paths else None,
-                                                  cells.ctypes.data if paths else None, int(cap) if paths else 0))
-        return (out, n, off, cells[:off[-1]].copy()) if paths else (out, n)
+        return self._sections_list("acx_ef_align_sections", pairs, (ctypes.byref(p), int(plane)), o, paths, cap,
+                                   lambda pr, S: self._ef_cap(pr, lambda q: 1024 * len(q), S))
 
     def sw_sections_binary(self, B, opts=None, paths=True, cap=None):
         """The same DP alone on a given binary (M, N) plot of at most 1024 x 1024 (acx_sw_sections_binary): (records (max_sections,),
         count) and with paths=True (records, count, offsets (max_sections + 1,), cells).  cap: default min(M, max_sections * min(M, N))."""
         o = opts or section_opts("sw_sections_binary")
-        B = np.ascontiguousarray(B, dtype=np.uint8)
-        if B.ndim != 2:
-            raise ValueError("sw_sections_binary: B must be (M, N), got shape %s" % (B.shape,))
-        if paths and cap is None:
-            cap = min(B.shape[0], o.max_sections * min(B.shape))
-        out, n, off, cells = self._sections_out(1, o.max_sections, paths, cap)
-        self._check(self._L.acx_sw_sections_binary(self._h, B.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), B.shape[0], B.shape[1],
-                                                   ctypes.byref(o), out.ctypes.data, n.ctypes.data, off.ctypes.data if paths else None,
-                                                   cells.ctypes.data if paths else None, int(cap) if paths else 0))
-        return (out[0], int(n[0]), off, cells[:off[-1]].copy()) if paths else (out[0], int(n[0]))
+        return self._sections_plot("acx_sw_sections_binary", B, "B", (), o, paths, cap)
 
     def chenfusion_align(self, pairs, params=None, plane=0):
         """WHERE the alignment of one plane of chenfusion_pairs lies (acx_chenfusion_align): plane 0 Qmax -- serra09_align itself --,
         plane 1 Dmax (score = chenfusion_pairs' column 1).  A (K,) structured array as serra09_align returns it.  The Dmax start need
         not hold Q = 1 and can be a gap cell beside the recurrence the alignment begins at."""
         p = params or serra09_params()
-        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        out = np.zeros(len(pairs), ALIGNMENT_DTYPE)
-        self._check(self._L.acx_chenfusion_align(self._h, _iptr(pairs), len(pairs), ctypes.byref(p), int(plane), out.ctypes.data))
-        return out
+        return self._align_list("acx_chenfusion_align", pairs, (ctypes.byref(p), int(plane)))
 
     def chenfusion_align_paths(self, pairs, params=None, plane=0, cap=None):
         """The alignments of one plane AND their paths (acx_chenfusion_align_paths): (records, offsets, cells) as serra09_align_paths

@@ -30,7 +30,21 @@ __all__ = ["EarlyFusion"]
 _KEYS = ("mfccs", "ssms", "chromas", "chroma_med")
 
 
-class EarlyFusion(CoverAlgorithm):
+class EarlyFusion(_align.AlignMixin, CoverAlgorithm):
+    """Alignments (align, align_paths, align_matches, align_match_paths, align_sections, align_match_sections: _align.AlignMixin):
+    the Smith-Waterman alignment of one of the four matrices the device binarises; similarity_type 'mfccs', 'ssms', 'chromas' or
+    'early' (the default); 'late' and 'early+late' are fused from whole score matrices and have no alignment of their own:
+    ValueError.  score is the value similarity() stores for that ORDERED pair and type.  Positions (q0, r0, q1, r1, the cells of a
+    path, the rows a section excludes and its `pad`) are BLOCKS, rows (query) and columns (reference) of the binarised
+    cross-similarity matrix (include/acx.h acx_ef_align); q_span / r_span are BEATS of each track: block b starts at beat b and spans
+    `blocksize` beats, so a span is [q0, q1 + blocksize - 1] (a track of n beats has n - blocksize blocks: no clipping).
+    align_matches() and its kin align the ordered pair (queries[i], indices[i, s]).  identify() of this symmetric class scored the
+    cell (min, max) of the two indices: the score listed there is that of the pair (min(queries[i], indices[i, s]), max(...)), and
+    passing THAT pair to align() gives the alignment behind the listed score; where the query has the larger index the row of
+    align_matches() is the alignment of the transposed matrix, whose score may differ (locate_tracks() aligns the pair the listed
+    score belongs to).  A list with a track of more than 1024 blocks takes the strip-wise alignment (ef_align_long), any other list
+    runs as it always did; the sections need the bit path: tracks of at most 1024 blocks, NotImplementedError naming the method
+    otherwise (align() serves longer ones)."""
     n_chunks = 1
 
     def __init__(self, dataset_csv, datapath, chroma_type='hpcp', shortname='Covers80', blocksize=20,
@@ -211,166 +225,39 @@ class EarlyFusion(CoverAlgorithm):
             score[i, :len(order)] = s_i[order]
         return idx, score
 
-    # ------------------------------------------------------------------ where the alignment lies
-    # align() / align_matches(): acx_alignment's fields in BLOCKS and the spans in BEATS, [first, last] inclusive
-    ALIGN_DTYPE = np.dtype(_lib.ALIGNMENT_DTYPE.descr + [("q_span", np.int32, (2,)), ("r_span", np.int32, (2,))])
-
-    def _align_plane(self, who, similarity_type):
-        """The device plane of a similarity type; checked before anything else."""
-        if similarity_type in self._identify_fused:
-            raise ValueError("%s: '%s' is fused from whole score matrices and has no alignment of its own; similarity_type must be one of %s"
-                             % (who, similarity_type, list(self._identify_planes)))
-        if similarity_type not in self._identify_planes:
-            raise ValueError("%s: unknown similarity type %r; similarity_type must be one of %s" % (who, similarity_type, list(self._identify_planes)))
-        return self._identify_planes.index(similarity_type)
-
+    # ------------------------------------------------------------------ where the alignment lies: AlignMixin's hooks
     # locate_tracks(): 'early' unless asked otherwise, and the pair the listed score belongs to, (hit, new track)
     _locate_type = "early"
     _locate_hit_first = True
 
-    def _align_kw(self, who, similarity_type):
-        st = "early" if similarity_type is None else similarity_type
-        self._align_plane(who, st)
-        return {"similarity_type": st}
-
-    def _no_match_rows(self, shape):
-        return _align.no_match_rows(shape, self.ALIGN_DTYPE)
-
-    def _align_pairs(self, pairs, plane, paths=None):
-        """(K, 2) checked int32 pairs -> (K,) ALIGN_DTYPE.  paths: a list that receives the K (L_k, 2) int32 paths as well."""
-        out = _align.no_match_rows(len(pairs), self.ALIGN_DTYPE)
-        if len(pairs) == 0:
-            return out
+    def _align_call(self, pairs, want_paths, plane):
         ctx = self._context()
         # a listed track of more than 1024 blocks: the strip-wise alignment of the float path (ef_align_long); else ef_align, with the
         # launches it always had
         fn = ctx.ef_align_long if ctx.ef_has_long_track(pairs) else ctx.ef_align
-        if paths is None:
-            al = fn(pairs, self.kappa, self.K, plane)
-        else:
-            al, off, cells = fn(pairs, self.kappa, self.K, plane, paths=True)
-            paths.extend(cells[off[k]:off[k + 1]] for k in range(len(pairs)))
-        for f in _lib.ALIGNMENT_DTYPE.names:
-            out[f] = al[f]
-        hit = al["q0"] >= 0
-        for side in ("q", "r"):
-            span = np.stack([al[side + "0"], al[side + "1"] + int(self.blocksize) - 1], axis=1)
-            out[side + "_span"][hit] = span[hit]
-        return out
+        if not want_paths:
+            return fn(pairs, self.kappa, self.K, plane), None, None
+        return fn(pairs, self.kappa, self.K, plane, paths=True)
 
-    def align(self, idxs, similarity_type="early"):
-        """WHERE in the two recordings does the Smith-Waterman alignment lie?  idxs: (K, 2) (query, reference) track indices
-        over the uploaded collection; similarity_type: one of the four matrices the device binarises, 'mfccs', 'ssms',
-        'chromas' or 'early' ('late' and 'early+late' are fused from whole score matrices: ValueError).  Returns a (K,)
-        structured array: score (the value similarity() stores for that ordered pair and type), the path's start (q0, r0) and
-        end (q1, r1) in BLOCKS -- rows (query) and columns (reference) of the binarised cross-similarity matrix; the end is
-        the row-major first maximum of the score matrix, the start is found by following the recursion's predecessors back
-        (include/acx.h acx_ef_align) -- and q_span / r_span, [first, last] inclusive in BEATS of each track: block b starts
-        at beat b and spans `blocksize` beats, so a span is [q0, q1 + blocksize - 1] (a track of n beats has n - blocksize
-        blocks: no clipping).  A pair without a match (score 0) has -1 everywhere.  `Ds` is not written; not a
-        collective."""
-        plane = self._align_plane("align", similarity_type)
-        return self._align_pairs(_align.check_pairs("align", _align.check_indices("align", idxs), self._n_tracks()), plane)
-
-    def align_paths(self, idxs, similarity_type="early"):
-        """align() and, for every pair, the PATH of its alignment: (al, paths).  al is exactly what align(idxs, similarity_type)
-        returns; paths is a list of K (L_k, 2) int32 arrays, the cells (q, r) in blocks that the recursion's predecessors visit
-        between the start and the end, both included, listed from (q0, r0) to (q1, r1) -- which block of the query corresponds
-        to which block of the reference.  Consecutive cells differ by (1, 1), (2, 1) or (1, 2); a pair without a match has an
-        empty (0, 2) path.  `Ds` is not written; not a collective."""
-        plane = self._align_plane("align_paths", similarity_type)
-        paths = []
-        al = self._align_pairs(_align.check_pairs("align_paths", _align.check_indices("align_paths", idxs), self._n_tracks()), plane, paths)
-        return al, (paths if len(al) else [])
-
-    def _check_align_matches(self, who, queries, indices):
-        return _align.check_matches(who, _align.check_indices(who, queries), _align.check_indices(who, indices), self._n_tracks())
-
-    def align_matches(self, queries, indices, similarity_type="early"):
-        """align() for the hits of identify() / rerank(): queries (Q,) track indices, indices the (Q, k) int array either
-        returned (-1: an empty slot).  Returns a (Q, k) structured array as align() does, row i slot s being the alignment of the
-        ORDERED pair (queries[i], indices[i, s]); an empty slot comes back as a no-match row.  identify() of this symmetric
-        class scored the cell (min, max) of the two indices: the score listed there is that of the pair (min(queries[i],
-        indices[i, s]), max(...)), and passing THAT pair to align() gives the alignment behind the listed score; where the query
-        has the larger index the row here is the alignment of the transposed matrix, whose score may differ."""
-        plane = self._align_plane("align_matches", similarity_type)
-        idx, rows, slots, pairs = self._check_align_matches("align_matches", queries, indices)
-        out = _align.no_match_rows(idx.shape, self.ALIGN_DTYPE)
-        out[rows, slots] = self._align_pairs(pairs, plane)
-        return out
-
-    def align_match_paths(self, queries, indices, similarity_type="early"):
-        """align_matches() with the paths: (the (Q, k) array align_matches returns, a Q-list of k-lists of (L, 2) int32 paths as
-        align_paths lists them); an empty slot (-1) has an empty path."""
-        plane = self._align_plane("align_match_paths", similarity_type)
-        idx, rows, slots, pairs = self._check_align_matches("align_match_paths", queries, indices)
-        out = _align.no_match_rows(idx.shape, self.ALIGN_DTYPE)
-        got = []
-        out[rows, slots] = self._align_pairs(pairs, plane, got)
-        return out, _align.scatter_paths(idx, rows, slots, got)
-
-    # ------------------------------------------------------------------ every matched section of a pair (DESIGN.md section 29)
-    def _check_sections(self, who, similarity_type, max_sections, min_score, min_ratio, pad):
-        """The plane and the options, before the first library call."""
-        return self._align_plane(who, similarity_type), _lib.section_opts(who, max_sections, min_score, min_ratio, pad)
-
-    def _section_pairs(self, who, pairs, plane, o, want_paths):
-        """(P, 2) checked int32 pairs -> (a P-list of (n_k,) ALIGN_DTYPE arrays, a P-list of lists of n_k (L, 2) int32 paths or None)."""
-        if len(pairs) == 0:
-            return [], ([] if want_paths else None)
+    def _sections_call(self, who, pairs, plane, o, want_paths):
         ctx = self._context()
         if ctx.ef_has_long_track(pairs) and getattr(ctx, "ef_blocks", None) is not None:
             raise NotImplementedError("%s: sections need the bit path: tracks of at most 1024 blocks (align() serves longer ones)" % who)
-        got = ctx.ef_align_sections(pairs, self.kappa, self.K, plane, o, paths=want_paths)
-        al, n = got[0], got[1]
-        S = al.shape[1]
-        out = _align.no_match_rows(al.shape, self.ALIGN_DTYPE)
-        for f in _lib.ALIGNMENT_DTYPE.names:
-            out[f] = al[f]
-        hit = al["q0"] >= 0
-        for side in ("q", "r"):                                     # (align()'s spans: block b covers beats b .. b + blocksize - 1)
-            span = np.stack([al[side + "0"], al[side + "1"] + int(self.blocksize) - 1], axis=-1)
-            out[side + "_span"][hit] = span[hit]
-        sections = [out[k, :n[k]].copy() for k in range(len(pairs))]
-        if not want_paths:
-            return sections, None
-        off, cells = got[2], got[3]
-        return sections, [[cells[off[k * S + s]:off[k * S + s + 1]] for s in range(n[k])] for k in range(len(pairs))]
+        return ctx.ef_align_sections(pairs, self.kappa, self.K, plane, o, paths=want_paths)
 
-    def align_sections(self, idxs, similarity_type="early", max_sections=4, min_score=2.0, min_ratio=0.0, pad=0, paths=False):
-        """EVERY matched section of a pair, not only the best alignment: a cover that plays the chorus once more, the two halves
-        around an inserted solo, the passages a medley quotes.  idxs and similarity_type as for align().  Returns a K-list of
-        (n_k,) structured arrays with align()'s fields (positions in BLOCKS, spans in BEATS), n_k <= max_sections (at most 16),
-        section 0 first; with paths=True (sections, paths), paths[k] a list of n_k (L, 2) int32 arrays as align_paths() lists them.
-          section 0      exactly align()'s row for the pair, provided its score >= min_score; otherwise the pair has no sections
-          section k + 1  the Smith-Waterman alignment of what is left when the QUERY's blocks q0 .. q1 of every section found so
-                         far, and `pad` blocks on either side of each (never across an earlier section), are excluded -- the
-                         recursion's value is 0 on those rows, so no alignment runs through them; reported iff its score >=
-                         max(min_score, min_ratio * section 0's score).  The search ends at the first section that fails.
-        Scores do not increase with k; every QUERY block belongs to at most one section (the row ranges are disjoint), while
-        reference blocks may be shared.  For a segmentation of the reference swap the pair.  min_score must be > 1, 0 <=
-        min_ratio <= 1, pad >= 0.  Tracks of at most 1024 blocks (NotImplementedError naming the method otherwise).  `Ds` is
-        not written; not a collective."""
-        plane, o = self._check_sections("align_sections", similarity_type, max_sections, min_score, min_ratio, pad)
-        pairs = _align.check_pairs("align_sections", _align.check_indices("align_sections", idxs), self._n_tracks())
-        sections, got = self._section_pairs("align_sections", pairs, plane, o, bool(paths))
-        return (sections, got) if paths else sections
+    def _spans(self, al, pairs):
+        """[q0, q1 + blocksize - 1] in beats: block b covers beats b .. b + blocksize - 1."""
+        return [np.stack([al[side + "0"], al[side + "1"] + int(self.blocksize) - 1], axis=1) for side in ("q", "r")]
 
-    def align_match_sections(self, queries, indices, similarity_type="early", max_sections=4, min_score=2.0, min_ratio=0.0, pad=0, paths=False):
-        """align_sections() for the hits of identify() / rerank(): queries (Q,) track indices, indices the (Q, k) int array either
-        returned (-1: an empty slot).  Returns a Q-list of k-lists of (n,) arrays as align_sections() returns them, slot s of row i
-        for the ORDERED pair (queries[i], indices[i, s]) -- an empty slot is an empty array -- and with paths=True (sections,
-        paths), paths a Q-list of k-lists of lists of (L, 2) int32 arrays."""
-        plane, o = self._check_sections("align_match_sections", similarity_type, max_sections, min_score, min_ratio, pad)
-        idx, rows, slots, pairs = self._check_align_matches("align_match_sections", queries, indices)
-        sections, got = self._section_pairs("align_match_sections", pairs, plane, o, bool(paths))
-        out = [[np.zeros(0, self.ALIGN_DTYPE) for _ in range(idx.shape[1])] for _ in range(idx.shape[0])]
-        out_paths = [[[] for _ in range(idx.shape[1])] for _ in range(idx.shape[0])]
-        for t, (r, s) in enumerate(zip(rows, slots)):
-            out[r][s] = sections[t]
-            if paths:
-                out_paths[r][s] = got[t]
-        return (out, out_paths) if paths else out
+    # every matched section of a pair (DESIGN.md section 29): this class's positional order, similarity_type right behind the indices
+    def align_sections(self, idxs, similarity_type=None, max_sections=4, min_score=2.0, min_ratio=0.0, pad=0, paths=False):
+        """AlignMixin.align_sections() -- sections of the Smith-Waterman alignment, rows and `pad` in BLOCKS -- with similarity_type
+        right behind the indices.  Tracks of at most 1024 blocks (NotImplementedError naming the method otherwise)."""
+        return _align.AlignMixin.align_sections(self, idxs, max_sections, min_score, min_ratio, pad, paths, similarity_type)
+
+    def align_match_sections(self, queries, indices, similarity_type=None, max_sections=4, min_score=2.0, min_ratio=0.0, pad=0, paths=False):
+        """AlignMixin.align_match_sections() with similarity_type right behind the indices; as align_sections()."""
+        return _align.AlignMixin.align_match_sections(self, queries, indices, max_sections, min_score, min_ratio, pad, paths, similarity_type)
 
     def _fusion_context(self):
         """The GPU context of the pair grid, or a fresh one (scores loaded with precomputed=True)."""

@@ -29,7 +29,7 @@ def pool_median(chroma, fac):
     return np.concatenate(parts, axis=0).astype(chroma.dtype, copy=False)
 
 
-class Serra09(CoverAlgorithm):
+class Serra09(_align.AlignMixin, CoverAlgorithm):
     """
     Attributes (as in the reference): chroma_type, downsample_fac, all_feats, oti, kappa,
     tau, m.  Extra keywords (all optional, behind the reference's):
@@ -53,6 +53,15 @@ class Serra09(CoverAlgorithm):
                                +14 ... 27 % pairs/s, but not the same bits: about one score in seven moves (by 0.5 - 4.5), MAP
                                stays within 1e-4 on the cover sets of tests/test_gpu_serra09.py
                  tests/test_essentia_pin.py finds the combination that reproduces essentia wherever it is installed.
+
+    Alignments (align, align_paths, align_matches, align_match_paths, align_sections, align_match_sections: _align.AlignMixin):
+    the Qmax alignment of the pair's cross recurrence plot; one similarity type, 'main' (the default); with engine dmax set the
+    scores are not Qmax's and every method refuses (ValueError).  score is the value similarity() stores, before
+    normalize_by_length.  Positions (q0, r0, q1, r1, the cells of a path, the rows a section excludes and its `pad`) are EMBEDDED
+    frames, rows (query) and columns (reference) of the plot; q_span / r_span are POOLED frames of each track.  The device decimates
+    the pooled track by tau and embeds it with stride 1 (DESIGN.md sections 2 and 3: the stack at base frame e tau holds frames
+    (e + k) tau, k < m), so embedded frame e starts at pooled frame tau e and covers pooled frames tau e .. tau (e + m - 1), and a
+    span is [tau q0, tau (q1 + m - 1)], clipped to the track (inside a session: to the session's tracks as well).
     """
     n_chunks = 1      # the whole pair list goes to the GPU in one similarity() call
 
@@ -215,12 +224,6 @@ class Serra09(CoverAlgorithm):
         T = self._pooled_lengths()
         return T if self._session is None else np.concatenate([T, self._session.pooled_len])
 
-    def _align_kw(self, who, similarity_type):
-        if similarity_type not in (None, "main"):
-            raise ValueError("%s: unknown similarity type %r; similarity_type must be one of %s" % (who, similarity_type, list(self._identify_planes)))
-        self._check_align(who, np.zeros((0, 2), np.int32))
-        return {}
-
     @refused_in_session
     def similarity(self, idxs):
         idxs = np.asarray(idxs).reshape(-1, 2)
@@ -230,146 +233,26 @@ class Serra09(CoverAlgorithm):
         for key in self.Ds.keys():
             self.Ds[key][idxs[:, 0], idxs[:, 1]] = scores
 
-    # ------------------------------------------------------------------ where the alignment lies
-    # align() / align_matches(): acx_alignment's fields and the spans in POOLED frames, [first, last] inclusive
-    ALIGN_DTYPE = np.dtype(_lib.ALIGNMENT_DTYPE.descr + [("q_span", np.int32, (2,)), ("r_span", np.int32, (2,))])
-
-    def _check_align(self, who, idxs):
-        if self._engine.get("dmax"):
+    # ------------------------------------------------------------------ where the alignment lies: AlignMixin's hooks
+    def _check_align(self, who, idxs, plane):
+        if plane == 0 and self._engine.get("dmax"):
             raise ValueError("%s: the Qmax alignment only (engine dmax must be 0)" % who)
         return _align.check_indices(who, idxs)
 
-    def _align_call(self, pairs, want_paths, plane=0):
-        """The library call behind _align_pairs: (records, offsets, cells), the last two None without paths."""
+    def _align_call(self, pairs, want_paths, plane):
         if not want_paths:
             return self._context().serra09_align(pairs, self._params()), None, None
         return self._context().serra09_align_paths(pairs, self._params())
 
-    def _align_pairs(self, pairs, paths=None, plane=0):
-        """(K, 2) checked int32 pairs -> (K,) ALIGN_DTYPE.  paths: a list that receives the K (L_k, 2) int32 paths as well.
-        plane: what a subclass with more than one alignment hands to its _align_call."""
-        if len(pairs) == 0:
-            return self._no_match_rows(0)
-        al, off, cells = self._align_call(pairs, paths is not None, plane)
-        if paths is not None:
-            paths.extend(cells[off[k]:off[k + 1]] for k in range(len(pairs)))
-        return self._align_rows(al, pairs)
+    def _sections_call(self, who, pairs, plane, o, want_paths):
+        return self._context().serra09_align_sections(pairs, self._params(), o, paths=want_paths)
 
-    def _align_rows(self, al, pairs):
-        """(K,) records of the library for the (K, 2) pairs -> (K,) ALIGN_DTYPE: the fields, and the spans in pooled frames."""
-        out = self._no_match_rows(len(pairs))
-        for f in _lib.ALIGNMENT_DTYPE.names:
-            out[f] = al[f]
-        hit = al["q0"] >= 0
+    def _spans(self, al, pairs):
+        """[tau q0, min(tau (q1 + m - 1), T - 1)] in pooled frames, for the query and for the reference."""
         T = self._track_lengths()
         tau, m = int(self.tau), int(self.m)
-        for side, col in (("q", 0), ("r", 1)):
-            last = T[pairs[:, col]] - 1
-            span = np.stack([tau * al[side + "0"].astype(np.int64), np.minimum(tau * (al[side + "1"].astype(np.int64) + m - 1), last)], axis=1)
-            out[side + "_span"][hit] = span[hit]
-        return out
-
-    def align(self, idxs):
-        """WHERE in the two recordings does the Qmax alignment lie?  idxs: (K, 2) (query, reference) track indices over
-        the uploaded collection.  Returns a (K,) structured array: score (the value similarity() stores, before
-        normalize_by_length), the path's start (q0, r0) and end (q1, r1) in EMBEDDED frames -- rows (query) and columns
-        (reference) of the cross recurrence plot; the end is the row-major first maximum of Qmax, the start is found by
-        following the recursion's predecessors back (include/acx.h acx_alignment) -- and q_span / r_span, [first, last]
-        inclusive in POOLED frames of each track.  The device decimates the pooled track by tau and embeds it with stride
-        1 (DESIGN.md sections 2 and 3: the stack at base frame e tau holds frames (e + k) tau, k < m), so embedded frame e
-        covers pooled frames tau e .. tau (e + m - 1) and a span is [tau q0, tau (q1 + m - 1)], clipped to the track.  A pair
-        without a match (score 0) has -1 everywhere.  `Ds` is not written; not a collective."""
-        return self._align_pairs(self._check_align_pairs("align", idxs))
-
-    def _check_align_pairs(self, who, idxs):
-        """align() / align_paths(): idxs -> (K, 2) int32, every check before the first library call."""
-        return _align.check_pairs(who, self._check_align(who, idxs), self._n_tracks())
-
-    def _check_align_matches(self, who, queries, indices):
-        """align_matches() / align_match_paths(): -> (the (Q, k) index array, rows and slots of its filled slots, their (P, 2) pairs)."""
-        return _align.check_matches(who, self._check_align(who, queries), self._check_align(who, indices), self._n_tracks())
-
-    def _no_match_rows(self, shape):
-        return _align.no_match_rows(shape, self.ALIGN_DTYPE)
-
-    def align_matches(self, queries, indices):
-        """align() for the hits of identify() / rerank(): queries (Q,) track indices, indices the (Q, k) int array
-        either returned (-1: an empty slot).  Returns a (Q, k) structured array as align() does, row i slot s being the
-        alignment of (queries[i], indices[i, s]); an empty slot comes back as a no-match row."""
-        idx, rows, slots, pairs = self._check_align_matches("align_matches", queries, indices)
-        out = self._no_match_rows(idx.shape)
-        out[rows, slots] = self._align_pairs(pairs)
-        return out
-
-    def align_paths(self, idxs):
-        """align() and, for every pair, the PATH of its alignment: (al, paths).  al is exactly what align(idxs) returns; paths is a
-        list of K (L_k, 2) int32 arrays, the cells (q, r) of the cross recurrence plot that the recursion's predecessors visit
-        between the start and the end, both included, listed from (q0, r0) to (q1, r1) -- which frame of the query corresponds to
-        which frame of the reference.  Consecutive cells differ by (1, 1), (2, 1) or (1, 2); a pair without a match has an empty
-        (0, 2) path.  Cells are EMBEDDED frames: embedded frame e starts at pooled frame tau * e (and stacks pooled frames
-        tau e .. tau (e + m - 1), as in align()).  `Ds` is not written; not a collective."""
-        paths = []
-        al = self._align_pairs(self._check_align_pairs("align_paths", idxs), paths)
-        return al, (paths if len(al) else [])
-
-    def align_match_paths(self, queries, indices):
-        """align_matches() with the paths: (the (Q, k) array align_matches returns, a Q-list of k-lists of (L, 2) int32 paths as
-        align_paths lists them); an empty slot (-1) has an empty path."""
-        idx, rows, slots, pairs = self._check_align_matches("align_match_paths", queries, indices)
-        out = self._no_match_rows(idx.shape)
-        got = []
-        out[rows, slots] = self._align_pairs(pairs, got)
-        return out, _align.scatter_paths(idx, rows, slots, got)
-
-    # ------------------------------------------------------------------ every matched section of a pair (DESIGN.md section 28)
-    def _section_pairs(self, pairs, o, want_paths):
-        """(P, 2) checked int32 pairs -> (a P-list of (n_k,) ALIGN_DTYPE arrays, a P-list of lists of n_k (L, 2) int32 paths or None)."""
-        if len(pairs) == 0:
-            return [], ([] if want_paths else None)
-        got = self._context().serra09_align_sections(pairs, self._params(), o, paths=want_paths)
-        al, n = got[0], got[1]
-        S = al.shape[1]
-        out = self._align_rows(al.reshape(-1), np.repeat(pairs, S, axis=0)).reshape(al.shape)      # (align()'s rows, a pair's S together)
-        sections = [out[k, :n[k]].copy() for k in range(len(pairs))]
-        if not want_paths:
-            return sections, None
-        off, cells = got[2], got[3]
-        return sections, [[cells[off[k * S + s]:off[k * S + s + 1]] for s in range(n[k])] for k in range(len(pairs))]
-
-    def align_sections(self, idxs, max_sections=4, min_score=2.0, min_ratio=0.0, pad=0, paths=False):
-        """EVERY matched section of a pair, not only the best one: a cover that repeats the chorus once more, a live version with
-        a solo between two matched halves, a medley that quotes two passages of one reference.  idxs: (K, 2) (query, reference)
-        track indices as for align().  Returns a K-list of (n_k,) structured arrays with align()'s fields and spans, n_k <=
-        max_sections (at most 16), section 0 first; with paths=True (sections, paths), paths[k] a list of n_k (L, 2) int32
-        arrays as align_paths() lists them.
-          section 0      exactly align()'s row for the pair, provided its score >= min_score; otherwise the pair has no sections
-          section k + 1  the Qmax alignment of what is left when the QUERY's embedded frames q0 .. q1 of every section found so
-                         far, and `pad` frames on either side of each (never across an earlier section), are excluded -- the
-                         recursion's value is 0 on those rows, so no alignment runs through them; reported iff its score >=
-                         max(min_score, min_ratio * section 0's score).  The search ends at the first section that fails.
-        Scores do not increase with k; every QUERY frame belongs to at most one section (the row ranges are disjoint), while
-        reference frames may be shared: the query repeats a chorus the reference plays once.  The sections segment the query;
-        for a segmentation of the reference swap the pair.  min_score must be > 1, 0 <= min_ratio <= 1, pad >= 0.
-        `Ds` is not written; not a collective."""
-        pairs = self._check_align_pairs("align_sections", idxs)
-        o = _lib.section_opts("align_sections", max_sections, min_score, min_ratio, pad)
-        sections, got = self._section_pairs(pairs, o, bool(paths))
-        return (sections, got) if paths else sections
-
-    def align_match_sections(self, queries, indices, max_sections=4, min_score=2.0, min_ratio=0.0, pad=0, paths=False):
-        """align_sections() for the hits of identify() / rerank(): queries (Q,) track indices, indices the (Q, k) int array either
-        returned (-1: an empty slot).  Returns a Q-list of k-lists of (n,) arrays as align_sections() returns them -- an empty slot
-        is an empty array -- and with paths=True (sections, paths), paths a Q-list of k-lists of lists of (L, 2) int32 arrays."""
-        idx, rows, slots, pairs = self._check_align_matches("align_match_sections", queries, indices)
-        o = _lib.section_opts("align_match_sections", max_sections, min_score, min_ratio, pad)
-        sections, got = self._section_pairs(pairs, o, bool(paths))
-        out = [[np.zeros(0, self.ALIGN_DTYPE) for _ in range(idx.shape[1])] for _ in range(idx.shape[0])]
-        out_paths = [[[] for _ in range(idx.shape[1])] for _ in range(idx.shape[0])]
-        for t, (r, s) in enumerate(zip(rows, slots)):
-            out[r][s] = sections[t]
-            if paths:
-                out_paths[r][s] = got[t]
-        return (out, out_paths) if paths else out
+        return [np.stack([tau * al[side + "0"].astype(np.int64), np.minimum(tau * (al[side + "1"].astype(np.int64) + m - 1), T[pairs[:, col]] - 1)], axis=1)
+                for side, col in (("q", 0), ("r", 1))]
 
     @refused_in_session
     def normalize_by_length(self):

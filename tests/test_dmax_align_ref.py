@@ -140,13 +140,19 @@ def test_python_methods_exist_and_check_their_arguments_first(tmp_path, monkeypa
         assert algo._ctx is None, "no library call was made"
     finally:
         algo.cleanup_memmap()
-    # Serra09 keeps its signature and its refusal
+    # Serra09 has one type, 'main' (None: the default; ChenFusion's types are unknown to it), and keeps its refusal
     import inspect
-    assert "similarity_type" not in inspect.signature(Serra09.align).parameters
+    assert inspect.signature(Serra09.align).parameters["similarity_type"].default is None
     algo = Serra09(str(csv), "feat/", shortname="dmaxargs2", engine={"dmax": 1})
     try:
         algo.set_pooled_features(tracks, ["w0", "w0"])
+        for t in ("qmax", "dmax"):
+            with pytest.raises(ValueError, match="align: unknown similarity type '%s'" % t):
+                algo.align([[0, 1]], similarity_type=t)
         with pytest.raises(ValueError, match="align: the Qmax alignment only"):
             algo.align([[0, 1]])
+        with pytest.raises(ValueError, match="align: the Qmax alignment only"):
+            algo.align([[0, 1]], similarity_type="main")
+        assert algo._ctx is None, "no library call was made"
     finally:
         algo.cleanup_memmap()

@@ -145,8 +145,8 @@ def test_python_side_argument_errors_come_first(tmp_path, monkeypatch):
             fn([0, 3], [[1, -2], [3, 4]])
         with pytest.raises(ValueError, match="integers"):
             fn([0, 3], [[1.0, 2.0], [3.0, 4.0]])
-    # similarity_type: the four device planes only, checked before the indices
-    for bad in ("late", "early+late", "nope", None):
+    # similarity_type: the four device planes only (None: the default, 'early'), checked before the indices
+    for bad in ("late", "early+late", "nope", 3):
         with pytest.raises(ValueError, match="similarity_type must be one of"):
             algo.align([[0, 99]], similarity_type=bad)
         with pytest.raises(ValueError, match="similarity_type must be one of"):

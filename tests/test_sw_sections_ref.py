@@ -175,8 +175,8 @@ def test_python_methods_check_their_arguments_first(tmp_path, monkeypatch):
             algo.align_sections([[0, 1]], **bad)
         with pytest.raises(ValueError, match="align_match_sections: %s" % what):
             algo.align_match_sections([0], [[1]], **bad)
-    # similarity_type: the four device planes only, checked before the options and the indices
-    for bad in ("late", "early+late", "nope", None):
+    # similarity_type: the four device planes only (None: the default, 'early'), checked before the options and the indices
+    for bad in ("late", "early+late", "nope", 3):
         with pytest.raises(ValueError, match="align_sections: .*similarity_type must be one of"):
             algo.align_sections([[0, 99]], similarity_type=bad, min_score=0.0)
         with pytest.raises(ValueError, match="align_match_sections: .*similarity_type must be one of"):
