@@ -54,6 +54,7 @@ EXPORTS = [
     "acx_serra09_align_sections", "acx_qmax_sections_binary",
     "acx_ef_plan", "acx_ef_kernel_name",
     "acx_ef_align_sections", "acx_sw_sections_binary",
+    "acx_debug_set_alloc_fill", "acx_debug_fill_arenas",
 ]
 ABI_VERSION = 4           # include/acx.h ACX_ABI_VERSION this shim was written against
 COMM_ID_BYTES = 128
@@ -413,9 +414,19 @@ def load():
     L.acx_ef_pool_append.argtypes = [vp, fp, fp, fp, dp, lp, ctypes.c_int32]
     L.acx_ftm2d_append_shingles.argtypes = [vp, dp, ctypes.c_int32, ctypes.c_int32]
     L.acx_pool_truncate.argtypes = [vp, ctypes.c_int32, ctypes.c_int32]
+    L.acx_debug_set_alloc_fill.argtypes = [ctypes.c_int, ctypes.c_uint32]
+    L.acx_debug_fill_arenas.argtypes = [vp, ctypes.c_uint32]
     _check_hip_version(L)
     _lib = L
     return L
+
+
+def set_alloc_fill(on, word=0):
+    """acx_debug_set_alloc_fill (process-wide): while `on`, every device block the library allocates is filled with the 32-bit
+    `word` before anyone uses it -- what a kernel finds in memory it never wrote is then the caller's choice.  Off by default."""
+    rc = load().acx_debug_set_alloc_fill(1 if on else 0, int(word) & 0xFFFFFFFF)
+    if rc != ACX_OK:
+        raise AcxError("acx_debug_set_alloc_fill failed (%d)" % rc)
 
 
 ARITH = {"exact": 0, "f16x2": 1}
@@ -1795,6 +1806,10 @@ class Context(object):
                                             _lptr(moff), _iptr(mates), _iptr(pos),
                                             flag.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
         return pos, flag
+
+    def debug_fill_arenas(self, word):
+        """acx_debug_fill_arenas: every scratch block of the context (DESIGN.md lists them), to capacity, becomes the 32-bit `word`."""
+        self._check(self._L.acx_debug_fill_arenas(self._h, int(word) & 0xFFFFFFFF))
 
     def profile_enable(self, on=True):
         self._check(self._L.acx_profile_enable(self._h, int(bool(on))))

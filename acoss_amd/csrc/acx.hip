@@ -6277,6 +6277,44 @@ int acx_query_fused_lists(acx_ctx *c, const acx_query_spec *spec, const void *pa
     });
 }
 
+// ---- debug: what a kernel finds in memory it did not write ("Device blocks of a context") --------------
+int acx_debug_set_alloc_fill(int on, uint32_t word)
+{
+    acx::g_alloc_fill.on = on != 0;
+    acx::g_alloc_fill.word = word;
+    return ACX_OK;
+}
+
+int acx_debug_fill_arenas(acx_ctx *c, uint32_t word)
+{
+    if (!c) return ACX_ERR_INVALID;
+    ACX_HIP(c, hipSetDevice(c->device));
+    return guarded(c, [&]() -> int {
+        ACX_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->qstream) ACX_HIP(c, hipStreamSynchronize(c->qstream));
+        if (c->qstream2) ACX_HIP(c, hipStreamSynchronize(c->qstream2));
+        // every SCRATCH block of DESIGN.md's table, to capacity (pools and descriptors keep their contents; d_pbox, a descriptor, is
+        // filled with the path pass's other blocks: its boxes are uploaded before every launch)
+        for (Serra09Slot &S : c->slot) {
+            ACX_HIP(c, S.d_out.fill(word));
+            ACX_HIP(c, S.d_al.fill(word));
+            ACX_HIP(c, S.d_nsec.fill(word));
+        }
+        for (DeviceBuffer<float> *b : {&c->d_scratch, &c->d_thr, &c->d_out, &c->rank_d[0], &c->rank_d[1]}) ACX_HIP(c, b->fill(word));
+        for (DeviceBuffer<double> *b : {&c->d_out64, &c->d_spmp}) ACX_HIP(c, b->fill(word));
+        for (DeviceBuffer<unsigned> *b : {&c->d_efbits, &c->d_efdir, &c->d_efctr}) ACX_HIP(c, b->fill(word));
+        for (DeviceBuffer<unsigned long long> *b : {&c->d_bits, &c->d_dir}) ACX_HIP(c, b->fill(word));
+        for (DeviceBuffer<int32_t> *b : {&c->d_spmpi, &c->d_pcells, &c->d_pn, &c->d_efres}) ACX_HIP(c, b->fill(word));
+        ACX_HIP(c, c->d_sprec.fill(word));
+        ACX_HIP(c, c->d_seam.fill(word));
+        ACX_HIP(c, c->d_pseam.fill(word));
+        ACX_HIP(c, c->d_pbox.fill(word));
+        ACX_HIP(c, c->d_nf.fill(word));
+        ACX_HIP(c, hipDeviceSynchronize());
+        return ACX_OK;
+    });
+}
+
 // ---- device buffers for hosts that hold no GPU runtime of their own ------------------------------------------
 int acx_dev_alloc(acx_ctx *c, int64_t bytes, void **d_ptr)
 {

@@ -1289,6 +1289,21 @@ int acx_debug_sqrt(acx_ctx *ctx, const float *in, int64_t n, float *out);
 /* the sqrt of the EarlyFusion distance epilogues (v_sqrt_f32 + one Newton step: within 1 ulp, almost always exact) */
 int acx_debug_ef_sqrt(acx_ctx *ctx, const float *in, int64_t n, float *out);
 
+/* ---- debug: history independence ---------------------------------------- */
+
+/* No result may depend on what device memory held before a call.  These two exports let a test decide what that is (tests/
+ * test_gpu_arena_history.py); they use no environment variable and change nothing while unused.
+ *
+ * acx_debug_set_alloc_fill   process-wide.  While `on`, every DEVICE block the library allocates (the contexts' grow-only arenas and
+ *                            pools, and the work buffers an entry point allocates for the length of a call) is filled with `word`
+ *                            before anyone uses it.  Pinned host buffers are not filled; acx_dev_alloc stays zero-filled.
+ * acx_debug_fill_arenas      drains the context's streams, fills TO CAPACITY every device block of the context that is scratch --
+ *                            sized per call, no input: DESIGN.md lists every block of a context with its class -- and waits.
+ *                            Uploaded and derived pools, and the descriptor blocks the host uploads before every launch, keep
+ *                            their contents. */
+int acx_debug_set_alloc_fill(int on, uint32_t word);
+int acx_debug_fill_arenas(acx_ctx *ctx, uint32_t word);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,22 @@ def test_header_and_library_agree():
     assert L.acx_abi_version() == _lib.ABI_VERSION == 4
 
 
+def test_debug_fill_exports():
+    """acx_debug_set_alloc_fill / acx_debug_fill_arenas (history independence, tests/test_gpu_arena_history.py): declared, exported,
+    wrapped, appended without a new ABI number; the switch is process-wide and needs no context or device, the fill needs a context."""
+    L = _lib.load()
+    for s in ("acx_debug_set_alloc_fill", "acx_debug_fill_arenas"):
+        assert s in _declared_symbols() and s in _lib.EXPORTS and hasattr(L, s)
+    assert _lib.EXPORTS[-2:] == ["acx_debug_set_alloc_fill", "acx_debug_fill_arenas"]
+    try:
+        _lib.set_alloc_fill(True, 0xFFFFFFFF)
+        _lib.set_alloc_fill(True, 0x55555555)
+    finally:
+        _lib.set_alloc_fill(False, 0)
+    assert L.acx_debug_fill_arenas(None, 0) == _lib.ACX_ERR_INVALID
+    assert callable(_lib.Context.debug_fill_arenas)
+
+
 def test_default_params_match_reference_ctor():
     L = _lib.load()
     p = _lib.Serra09Params()

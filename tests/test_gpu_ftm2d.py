@@ -43,12 +43,8 @@ CASES = [(1, 1), (1, 2), (1, 2600), (2, 2), (2, 700), (3, 3), (3, 4), (16, 16), 
          (74, 80), (75, 75), (75, 76), (75, 160), (76, 77), (128, 128), (128, 129), (256, 256), (256, 257), (256, 300)]
 
 
-@pytest.mark.parametrize("win,nbeats", CASES)
-def test_stages_against_numpy(ctx, win, nbeats):
-    rng = np.random.default_rng(1000 * win + nbeats)
-    pwr, C = ((0.5, 1.0), (1.96, 5.0))[(win + nbeats) % 2]
-    X, on = _track(rng, nbeats, intro=5000 if nbeats == 90 else 0)
-    got = ctx.ftm2d_debug_track(X, on, pwr, win, C)
+def _check_stages(got, X, on, pwr, win, C, nbeats):
+    """What acx_ftm2d_debug_track returned for (X, on), stage by stage, each from the device's previous one, and the whole chain."""
     # stage 1: bit-identical to np.median per bin and segment
     np.testing.assert_array_equal(got["synced"], ref.beat_sync(X, on).T)
     # stage 2 from the device's stage 1
@@ -68,6 +64,14 @@ def test_stages_against_numpy(ctx, win, nbeats):
     # and the whole chain against the checker on the raw input
     full = ref.stages(X, on, pwr, win, C)
     assert np.max(np.abs(got["shingle"] - full["shingle"])) <= 1e-9
+
+
+@pytest.mark.parametrize("win,nbeats", CASES)
+def test_stages_against_numpy(ctx, win, nbeats):
+    rng = np.random.default_rng(1000 * win + nbeats)
+    pwr, C = ((0.5, 1.0), (1.96, 5.0))[(win + nbeats) % 2]
+    X, on = _track(rng, nbeats, intro=5000 if nbeats == 90 else 0)
+    _check_stages(ctx.ftm2d_debug_track(X, on, pwr, win, C), X, on, pwr, win, C, nbeats)
 
 
 @pytest.mark.parametrize("k", [0, 1])

@@ -27,6 +27,13 @@ def _scores(rng, n, m):
     return out
 
 
+def _check_fused(Ws_want, want, Ws_dev, dev):
+    """The affinity matrices and the fused matrix of acx_snf_fuse_dists against a specification's."""
+    for a, b in zip(Ws_want, Ws_dev):
+        np.testing.assert_allclose(b, a, rtol=1e-12, atol=1e-300)
+    np.testing.assert_allclose(dev, want, rtol=1e-10, atol=1e-14)
+
+
 @pytest.mark.parametrize("n,m,K,niters", [(30, 2, 5, 3), (61, 3, 20, 20), (200, 4, 20, 20), (257, 3, 7, 5), (700, 2, 64, 2)])
 def test_fused_matrix_matches_oracle(ctx, n, m, K, niters):
     """acx_snf_fuse_dists (affinity matrices, neighbour lists and diffusion on the device) and
@@ -37,9 +44,7 @@ def test_fused_matrix_matches_oracle(ctx, n, m, K, niters):
     Scores = _scores(rng, n, m)
     Ws_o, want = oracle.snf_fuse(Scores, K=K, niters=niters, reg_diag=1)
     Ws_d, dev = sf.doSimilarityFusion(Scores, K=K, niters=niters, reg_diag=1, ctx=ctx)
-    for a, b in zip(Ws_o, Ws_d):
-        np.testing.assert_allclose(b, a, rtol=1e-12, atol=1e-300)
-    np.testing.assert_allclose(dev, want, rtol=1e-10, atol=1e-14)
+    _check_fused(Ws_o, want, Ws_d, dev)
     assert sf.doSimilarityFusion(Scores, K=K, niters=1, reg_diag=1, ctx=ctx, want_ws=False)[0] is None
     if n == 30:     # the reference's own call, positional, no libacx vocabulary (similarity_fusion.py:188): default context
         Ws_b, bare = sf.doSimilarityFusion(Scores, K, niters, 1)
